@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LM iterations/s of the Sim(3) pose-graph hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one Levenberg-Marquardt iteration (chi2, per-edge residual + numeric Jacobians,
@@ -60,7 +60,36 @@ def parse():
                          "on the library's stream) or gloo (host-staged callbacks; lets N ranks share "
                          "one GPU for dry runs)")
     ap.add_argument("--cpu-sample-vertices", type=int, default=1000)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to a caller (the vertex "
+                         "estimates, chi2 and lambda) as DIR/<name>.npy, float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(directory, G, stats):
+    """What the timed path handed its caller after the last timed step: every vertex estimate
+    (sim3opt_get_vertices, n x 8: qx qy qz qw tx ty tz s) and that step's chi2 before /
+    after and lambda.  Above the size cap a fixed, seeded sample of rows is written together with
+    its row indices, so two builds given the same arguments can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    states = G.get_vertices()
+    last = stats[-1]
+    out = {"lm_last_step": np.array([last.chi2_before, last.chi2_after, last.lambda_], dtype=np.float64)}
+    max_rows = (DUMP_MAX_BYTES - 4096) // (states.shape[1] * 8 + 8)
+    if states.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(20240613).choice(states.shape[0], max_rows, replace=False))
+        out["vertices_sample_rows"] = rows.astype(np.float64)
+        out["vertices_sample"] = states[rows]
+    else:
+        out["vertices"] = states
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(args, g, gpu_ms_linearize, gpu_value, threads=1):
@@ -415,6 +444,8 @@ def main():
     kt = G.kernel_times()
     ct = G.comm_times() if world > 1 else None  # (before the chi2 below adds its own all-reduce)
     chi2_final = G.chi2()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, G, stats)
 
     if rank == 0:
         K = args.steps
