@@ -131,6 +131,10 @@ typedef struct sim3opt_options {
                                         arrays with everything outside the rank's range poisoned (0xFF = NaN) and
                                         checked after every linearisation / optimize -- a write there is an error,
                                         a read shows as NaN (the test of the ranges)          [SIM3OPT_DEBUG_FULL_ARRAYS] */
+  int32_t jacobians;        /* 0     how the linearisation differentiates EdgeSim3's residual: 0 = central differences
+                                        with step fd_delta (g2o's BaseBinaryEdge default: the reference's arithmetic),
+                                        1 = closed form, J = +-J_l(e)^-1 Ad (DESIGN.md "Analytic Jacobians"); needs
+                                        fix_small_angle_b = 1 (sim3opt_set_options refuses it with the as-written B) */
 } sim3opt_options;
 
 /* Per-iteration record (g2o G2OBatchStatistics role; bal_example.cpp:55-56). */
@@ -244,6 +248,15 @@ int sim3opt_get_comm_times(sim3opt_graph* g, sim3opt_comm_times* out);
 /* ---- kernel-level access (parity tests against the CPU oracle, bench roofline) ---- */
 /* per-edge residuals e (m x 7), edge insertion order                EdgeSim3::computeError */
 int sim3opt_edge_errors(sim3opt_graph* g, double* e_out);
+/* closed-form Jacobians (options.jacobians = 1) of every edge at the current estimates, edge insertion order:
+ * e (m x 7) as sim3opt_edge_errors, J (m x 7 x 14, row-major per edge: J[98 k + 14 r + c]; columns 0..6 = de/dd0,
+ * 7..13 = de/dd1 for the updates S <- exp(d) S; options.dof_mask zeroes frozen columns), evaluated on the
+ * device by the functions the linearisation uses.  Needs fix_small_angle_b = 1.          EdgeSim3::linearizeOplus */
+int sim3opt_edge_jacobians(sim3opt_graph* g, double* e_out, double* J_out);
+/* the same for one edge, on the host (no GPU needed): e[7], J[98] as above; o NULL = defaults, which are refused
+ * (fix_small_angle_b = 0) */
+int sim3opt_sim3_edge_jacobian(const double meas[8], const double s0[8], const double s1[8],
+                               const sim3opt_options* o, double e[7], double J[98]);
 /* runs the linearisation kernels once on the current estimates     BlockSolver::buildSystem */
 int sim3opt_linearize(sim3opt_graph* g);
 /* dimensions of the block-CSR system: free block rows, stored 7x7 blocks */

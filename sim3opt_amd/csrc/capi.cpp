@@ -18,6 +18,7 @@
 #include "direct.hpp"
 #include "engine.hpp"
 #include "graph.hpp"
+#include "sim3_jac.hpp"
 
 using namespace sim3opt;
 
@@ -118,7 +119,8 @@ int add_edge_impl(sim3opt_graph* g, int32_t id0, int32_t id1, const double* meas
 
 extern "C" {
 
-int sim3opt_version(void) { return 110; }  // 1.1: multigrid preconditioner, hierarchy / BAL entry points
+// 1.1: multigrid preconditioner, hierarchy / BAL entry points; 1.2: closed-form Jacobians (options.jacobians)
+int sim3opt_version(void) { return 120; }
 
 void sim3opt_options_default(sim3opt_options* o) {
   if (!o) return;
@@ -161,6 +163,7 @@ void sim3opt_options_default(sim3opt_options* o) {
   o->amg_over[1] = 1.6;
   o->direct_max_pairs = 0;
   o->debug_full_arrays = 0;
+  o->jacobians = 0;
 }
 
 // Debug overrides: a SIM3OPT_* environment variable replaces the option field of the same name when the
@@ -221,6 +224,12 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
       !(o->tau > 0) || o->pcg_check_every < 0 || o->amg_virtual_ranks < 0 || o->pcg_batch < 0 ||
       o->direct_max_pairs < 0 || !(o->amg_omega > 0) || !(o->amg_over[0] > 0) || !(o->amg_over[1] > 0))
     return fail(g, SIM3OPT_ERR_ARG, "set_options: value out of range");
+  if (o->jacobians != 0 && o->jacobians != 1)
+    return fail(g, SIM3OPT_ERR_ARG, "set_options: jacobians must be 0 (numeric) or 1 (analytic)");
+  if (o->jacobians == 1 && o->fix_small_angle_b != 1)
+    return fail(g, SIM3OPT_ERR_ARG,
+                "set_options: jacobians = 1 needs fix_small_angle_b = 1 (the closed form differentiates the exact "
+                "map; log's as-written small-angle B departs from it by O(1) below theta ~ 4.5e-3)");
   g->opt = *o;
   if (g->engine) engine_set_options(g->engine, g->opt);
   return SIM3OPT_OK;
@@ -458,6 +467,30 @@ int sim3opt_edge_errors(sim3opt_graph* g, double* e_out) {
   if (!g || !e_out) return fail(g, SIM3OPT_ERR_ARG, "edge_errors: null argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "edge_errors: call sim3opt_initialize first");
   return engine_edge_errors(g->engine, e_out, g->err);
+}
+
+int sim3opt_edge_jacobians(sim3opt_graph* g, double* e_out, double* J_out) {
+  if (!g || !e_out || !J_out) return fail(g, SIM3OPT_ERR_ARG, "edge_jacobians: null argument");
+  if (g->opt.fix_small_angle_b != 1)
+    return fail(g, SIM3OPT_ERR_ARG, "edge_jacobians: needs fix_small_angle_b = 1 (closed form of the exact map)");
+  if (!g->initialized || g->dirty)
+    return fail(g, SIM3OPT_ERR_STATE, "edge_jacobians: call sim3opt_initialize first");
+  return engine_edge_jacobians(g->engine, e_out, J_out, g->err);
+}
+
+int sim3opt_sim3_edge_jacobian(const double meas[8], const double s0[8], const double s1[8],
+                               const sim3opt_options* o, double e[7], double J[98]) {
+  if (!meas || !s0 || !s1 || !e || !J) return SIM3OPT_ERR_ARG;
+  if (!state_ok(meas) || !state_ok(s0) || !state_ok(s1)) return SIM3OPT_ERR_ARG;
+  sim3opt_options d;
+  if (!o) {
+    sim3opt_options_default(&d);
+    o = &d;
+  }
+  if (o->fix_small_angle_b != 1 || !(o->exp_eps > 0)) return SIM3OPT_ERR_ARG;
+  const sim3::Opts mo{o->exp_eps, o->small_rot_half, o->fix_small_angle_b};
+  sim3::edge_jacobians(to_sim3(meas), to_sim3(s0), to_sim3(s1), mo, o->dof_mask, e, J);
+  return SIM3OPT_OK;
 }
 
 int sim3opt_linearize(sim3opt_graph* g) {

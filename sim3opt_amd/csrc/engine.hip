@@ -1,6 +1,7 @@
 // engine.hip -- initialisation, linearisation, chi2 and the LM trial loop (g2o: SparseOptimizer::optimize ->
 // OptimizationAlgorithmLevenberg::solve, kitti_surf.cpp:674-675); the C++ interface capi.cpp calls
 #include "engine_impl.hpp"
+#include "sim3_jac.hpp"
 
 namespace sim3opt {
 
@@ -363,9 +364,10 @@ int Engine::check_foreign_ranges(std::string& err) {
 
 int Engine::linearize(std::string& err) {
   const sim3::Opts mo = mopts();
-  if (!d_ptab) HIPCHK(dev_malloc((void**)&d_ptab, 14 * sizeof(Sim3)));
-  if (ptab_delta != opt.fd_delta || ptab_opts.eps != mo.eps || ptab_opts.small_rot_half != mo.small_rot_half ||
-      ptab_opts.fix_small_b != mo.fix_small_b) {
+  const bool analytic = opt.jacobians == 1;  // closed form: no perturbation table
+  if (!analytic && !d_ptab) HIPCHK(dev_malloc((void**)&d_ptab, 14 * sizeof(Sim3)));
+  if (!analytic && (ptab_delta != opt.fd_delta || ptab_opts.eps != mo.eps ||
+                    ptab_opts.small_rot_half != mo.small_rot_half || ptab_opts.fix_small_b != mo.fix_small_b)) {
     hipLaunchKernelGGL(k_perturbation_table, dim3(1), dim3(64), 0, stream, opt.fd_delta, mo, d_ptab);
     ptab_delta = opt.fd_delta;
     ptab_opts = mo;
@@ -375,7 +377,16 @@ int Engine::linearize(std::string& err) {
             (const Sim3*)d_ptab, opt.dof_mask, d_sc};
   const int g = (n_active + EPB - 1) / EPB;
   if (g == 0) HIPCHK(hipMemsetAsync(&d_sc->maxdiag_bits, 0, sizeof(unsigned long long), stream));
-  if (g > 0) {
+  if (g > 0 && analytic) {
+    if (has_info && has_kernel)
+      hipLaunchKernelGGL((k_linearize_analytic<true, true>), dim3(g), dim3(WG), 0, stream, A);
+    else if (has_info)
+      hipLaunchKernelGGL((k_linearize_analytic<true, false>), dim3(g), dim3(WG), 0, stream, A);
+    else if (has_kernel)
+      hipLaunchKernelGGL((k_linearize_analytic<false, true>), dim3(g), dim3(WG), 0, stream, A);
+    else
+      hipLaunchKernelGGL((k_linearize_analytic<false, false>), dim3(g), dim3(WG), 0, stream, A);
+  } else if (g > 0) {
     if (has_info && has_kernel)
       hipLaunchKernelGGL((k_linearize_numeric<true, true>), dim3(g), dim3(WG), 0, stream, A);
     else if (has_info)
@@ -661,6 +672,27 @@ int engine_edge_errors(Engine* e, double* out, std::string& err) {
   dev_free(d_out);
   if (le != hipSuccess) {
     err = std::string("edge_errors: ") + hipGetErrorString(le);
+    return SIM3OPT_ERR_HIP;
+  }
+  return SIM3OPT_OK;
+}
+
+int engine_edge_jacobians(Engine* e, double* e_out, double* J_out, std::string& err) {
+  const size_t m = (size_t)e->ne;
+  double* d_out = nullptr;
+  HIPCHK(dev_malloc((void**)&d_out, sizeof(double) * 105 * std::max<size_t>(m, 1)));
+  EdgeArgs ea = e->edge_args();
+  ea.e_lo = 0;
+  ea.e_hi = e->ne;
+  hipLaunchKernelGGL(k_edge_jacobians, dim3(grid_for(e->ne, WG)), dim3(WG), 0, e->stream, ea, e->opt.dof_mask,
+                     d_out, d_out + 7 * m);
+  hipError_t le = hipGetLastError();
+  if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+  if (le == hipSuccess) le = hipMemcpy(e_out, d_out, sizeof(double) * 7 * m, hipMemcpyDeviceToHost);
+  if (le == hipSuccess) le = hipMemcpy(J_out, d_out + 7 * m, sizeof(double) * 98 * m, hipMemcpyDeviceToHost);
+  dev_free(d_out);
+  if (le != hipSuccess) {
+    err = std::string("edge_jacobians: ") + hipGetErrorString(le);
     return SIM3OPT_ERR_HIP;
   }
   return SIM3OPT_OK;

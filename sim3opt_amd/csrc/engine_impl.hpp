@@ -14,6 +14,7 @@
 //   EdgeSim3::computeError                     -> k_chi2, k_edge_errors, k_linearize_numeric
 //   BaseBinaryEdge::linearizeOplus (numeric)   -> k_linearize_numeric (lane = one +-delta evaluation)
 //   BaseBinaryEdge::constructQuadraticForm     -> k_linearize_numeric (Gram phase) + k_diag_reduce
+//   (options.jacobians = 1: closed-form J)     -> k_linearize_analytic (sim3_jac.hpp; same Gram phase)
 //   BlockSolverX::buildSystem / setLambda      -> block-CSR values in HBM; lambda folded into SpMV
 //   LinearSolverEigen::solve (SimplicialLDLT)  -> preconditioned CG: k_spmv_span, k_pcg_*; block-Jacobi
 //                                                 (k_jacobi), chain segments (k_chain_*) or aggregation

@@ -193,6 +193,69 @@ __global__ __launch_bounds__(64) void k_perturbation_table(double delta, sim3::O
   tab[t] = sim3::exp(xi, opts);
 }
 
+// The Gram phase of both linearisation kernels, entered after the Jacobian columns (J[0..13]) and e (J[14]) of
+// this half-wavefront's edge are in LDS: Omega (J | e), the Huber weight, the 119 Gram tasks, the plain stores.
+// (Every thread of the workgroup calls it: it holds the workgroup barriers.)
+template <bool HAS_INFO, bool HAS_KERNEL>
+__device__ __forceinline__ void linearize_gram_store(const LinArgs& A, int edge, bool valid, int l,
+                                                     double (*J)[7], double (*O)[7], double (*G)[15]) {
+  __syncthreads();
+  if (HAS_INFO) {
+    if (valid) {
+      const double* Om = A.info + (size_t)49 * edge;  // column-major
+      for (int t = l; t < 105; t += 32) {
+        const int a = t / 7, r = t % 7;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) acc += Om[7 * k + r] * J[a][k];
+        O[a][r] = acc;
+      }
+    }
+    __syncthreads();
+  }
+  double (*OJ)[7] = HAS_INFO ? O : J;
+  double w = 1.0;
+  if (HAS_KERNEL) {
+    if (valid && A.kdelta[edge] > 0.0) {
+      double chi = 0.0, rho;
+#pragma unroll
+      for (int r = 0; r < 7; ++r) chi += J[14][r] * OJ[14][r];
+      huber(chi, A.kdelta[edge], rho, w);
+    }
+  }
+  if (valid) {
+    for (int t = l; t < 119; t += 32) {
+      const int a = c_tab.ga[t], b = c_tab.gb[t];
+      double acc = 0.0;
+#pragma unroll
+      for (int r = 0; r < 7; ++r) acc += J[a][r] * OJ[b][r];
+      G[a][b] = (b == 14 ? -w : w) * acc;
+    }
+  }
+  __syncthreads();
+  if (valid) {
+    const int s01 = A.slot01[edge], s10 = A.slot10[edge];
+    const int i0 = A.inc0[edge], i1 = A.inc1[edge];
+    for (int o = l; o < 168; o += 32) {
+      if (o < 49) {  // H01 = A^T W B, column-major
+        if (s01 >= 0) A.vals[(size_t)49 * s01 + o] = G[o % 7][7 + o / 7];
+      } else if (o < 98) {  // H10 = H01^T
+        const int p = o - 49;
+        if (s10 >= 0) A.vals[(size_t)49 * s10 + p] = G[p / 7][7 + p % 7];
+      } else if (o < 133) {  // endpoint 0: upper(A^T W A), -A^T W e
+        const int t = o - 98;
+        if (i0 >= 0)
+          A.scratch[(size_t)35 * i0 + t] = t < 28 ? G[c_tab.tr[t]][c_tab.tc[t]] : G[t - 28][14];
+      } else {  // endpoint 1
+        const int t = o - 133;
+        if (i1 >= 0)
+          A.scratch[(size_t)35 * i1 + t] =
+              t < 28 ? G[7 + c_tab.tr[t]][7 + c_tab.tc[t]] : G[7 + t - 28][14];
+      }
+    }
+  }
+}
+
 template <bool HAS_INFO, bool HAS_KERNEL>
 __global__ __launch_bounds__(WG) void k_linearize_numeric(LinArgs A) {
   __shared__ double s_in[EPB][24];
@@ -237,60 +300,112 @@ __global__ __launch_bounds__(WG) void k_linearize_numeric(LinArgs A) {
       s_J[es][l >> 1][r] = ((A.dof_mask >> ((l % 14) >> 1)) & 1) ? scalar * (e[r] - other) : 0.0;
     if (valid && l == 28) s_J[es][14][r] = e[r];
   }
-  __syncthreads();
-  if (HAS_INFO) {
-    if (valid) {
-      const double* Om = A.info + (size_t)49 * edge;  // column-major
-      for (int t = l; t < 105; t += 32) {
-        const int a = t / 7, r = t % 7;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) acc += Om[7 * k + r] * s_J[es][a][k];
-        s_O[es][a][r] = acc;
-      }
-    }
-    __syncthreads();
-  }
-  double (*OJ)[7] = HAS_INFO ? s_O[es] : s_J[es];
-  double w = 1.0;
-  if (HAS_KERNEL) {
-    if (valid && A.kdelta[edge] > 0.0) {
-      double chi = 0.0, rho;
-#pragma unroll
-      for (int r = 0; r < 7; ++r) chi += s_J[es][14][r] * OJ[14][r];
-      huber(chi, A.kdelta[edge], rho, w);
-    }
-  }
+  linearize_gram_store<HAS_INFO, HAS_KERNEL>(A, edge, valid, l, s_J[es], HAS_INFO ? s_O[es] : s_J[es], s_G[es]);
+}
+
+// ------------------------------------------------------------------------------------------
+// linearisation, closed-form Jacobians (options.jacobians = 1; sim3_jac.hpp)
+//   the same half-wavefront per edge, LinArgs, outputs and Gram phase as k_linearize_numeric:
+//     every lane : e = log(C S0 S1^-1) (the numeric path's residual, bit for bit)
+//     lanes 0-11 : Gauss-Legendre node l of J_l(e)          -> LDS, 30 weighted values per node
+//     lane 12    : exp(e) (R, t, s: 13 values)              -> LDS, next to the nodes
+//     lanes 0-29 : value l summed over the nodes in node order (as sim3::left_jacobian_blocks sums them);
+//                  lanes 0-12 also move exp(e) next to the sums
+//     lanes 0-13 : Jacobian column l (block substitution with J_SO3 and V), lane 14: e
+//   The node table is dead once summed: it shares LDS with the Jacobian / Gram arrays (the sums sit past it,
+//   where only the Gram array overlaps them, and that is written after they are read).
+// ------------------------------------------------------------------------------------------
+template <bool HAS_INFO, bool HAS_KERNEL>
+__global__ __launch_bounds__(WG) void k_linearize_analytic(LinArgs A) {
+  constexpr int NJ = EPB * 15 * 7, NO = HAS_INFO ? NJ : 7, NG = EPB * 14 * 15;
+  constexpr int NS = sim3::JAC_SUMS + 13;  // per edge: the J_l blocks, then exp(e)
+  constexpr int NN = EPB * (sim3::JAC_NODES + 1) * sim3::JAC_SUMS, NM = EPB * NS;
+  constexpr int NLDS = NN + NM > NJ + NO + NG ? NN + NM : NJ + NO + NG;
+  __shared__ double s_in[EPB][24];
+  __shared__ double s_lds[NLDS];
+  double (*s_node)[sim3::JAC_NODES + 1][sim3::JAC_SUMS] =
+      reinterpret_cast<double (*)[sim3::JAC_NODES + 1][sim3::JAC_SUMS]>(s_lds);
+  double (*s_M)[NS] = reinterpret_cast<double (*)[NS]>(s_lds + NN);
+  double (*s_J)[15][7] = reinterpret_cast<double (*)[15][7]>(s_lds);
+  double (*s_O)[15][7] = reinterpret_cast<double (*)[15][7]>(s_lds + NJ);
+  double (*s_G)[14][15] = reinterpret_cast<double (*)[14][15]>(s_lds + NJ + NO);
+  const int l = threadIdx.x & 31, es = threadIdx.x >> 5;
+  const int ai = blockIdx.x * EPB + es;
+  const bool valid = ai < A.n_active;
+  if (blockIdx.x == 0 && threadIdx.x == 0) A.sc->maxdiag_bits = 0ull;
+  int edge = 0;
   if (valid) {
-    for (int t = l; t < 119; t += 32) {
-      const int a = c_tab.ga[t], b = c_tab.gb[t];
-      double acc = 0.0;
+    edge = A.active[ai];
+    if (l < 8) s_in[es][l] = reinterpret_cast<const double*>(A.meas + edge)[l];
+    else if (l < 16) s_in[es][l] = reinterpret_cast<const double*>(A.states + A.ev0[edge])[l - 8];
+    else if (l < 24) s_in[es][l] = reinterpret_cast<const double*>(A.states + A.ev1[edge])[l - 16];
+  }
+  __syncthreads();
+  double e[7] = {0, 0, 0, 0, 0, 0, 0};
+  Sim3 C;
+  if (valid) {
+    Sim3 S0, S1;
+    const double* in = s_in[es];
+    C.q[0] = in[0]; C.q[1] = in[1]; C.q[2] = in[2]; C.q[3] = in[3];
+    C.t[0] = in[4]; C.t[1] = in[5]; C.t[2] = in[6]; C.s = in[7];
+    S0.q[0] = in[8]; S0.q[1] = in[9]; S0.q[2] = in[10]; S0.q[3] = in[11];
+    S0.t[0] = in[12]; S0.t[1] = in[13]; S0.t[2] = in[14]; S0.s = in[15];
+    S1.q[0] = in[16]; S1.q[1] = in[17]; S1.q[2] = in[18]; S1.q[3] = in[19];
+    S1.t[0] = in[20]; S1.t[1] = in[21]; S1.t[2] = in[22]; S1.s = in[23];
+    sim3::edge_error(C, S0, S1, A.opts, e);
+    if (l < sim3::JAC_NODES) {
+      double v[sim3::JAC_SUMS];
+      sim3::left_jacobian_node(e, l, v);
 #pragma unroll
-      for (int r = 0; r < 7; ++r) acc += s_J[es][a][r] * OJ[b][r];
-      s_G[es][a][b] = (b == 14 ? -w : w) * acc;
+      for (int i = 0; i < sim3::JAC_SUMS; ++i) s_node[es][l][i] = v[i];
+    } else if (l == sim3::JAC_NODES) {
+      double X[13];
+      sim3::exp_of_residual(e, X);
+#pragma unroll
+      for (int i = 0; i < 13; ++i) s_node[es][l][i] = X[i];
     }
   }
   __syncthreads();
-  if (valid) {
-    const int s01 = A.slot01[edge], s10 = A.slot10[edge];
-    const int i0 = A.inc0[edge], i1 = A.inc1[edge];
-    double (*G)[15] = s_G[es];
-    for (int o = l; o < 168; o += 32) {
-      if (o < 49) {  // H01 = A^T W B, column-major
-        if (s01 >= 0) A.vals[(size_t)49 * s01 + o] = G[o % 7][7 + o / 7];
-      } else if (o < 98) {  // H10 = H01^T
-        const int p = o - 49;
-        if (s10 >= 0) A.vals[(size_t)49 * s10 + p] = G[p / 7][7 + p % 7];
-      } else if (o < 133) {  // endpoint 0: upper(A^T W A), -A^T W e
-        const int t = o - 98;
-        if (i0 >= 0)
-          A.scratch[(size_t)35 * i0 + t] = t < 28 ? G[c_tab.tr[t]][c_tab.tc[t]] : G[t - 28][14];
-      } else {  // endpoint 1
-        const int t = o - 133;
-        if (i1 >= 0)
-          A.scratch[(size_t)35 * i1 + t] =
-              t < 28 ? G[7 + c_tab.tr[t]][7 + c_tab.tc[t]] : G[7 + t - 28][14];
-      }
+  if (valid && l < sim3::JAC_SUMS) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < sim3::JAC_NODES; ++k) acc += s_node[es][k][l];
+    s_M[es][l] = acc;
+    if (l < 13) s_M[es][sim3::JAC_SUMS + l] = s_node[es][sim3::JAC_NODES][l];
+  }
+  __syncthreads();
+  if (valid && l < 15) {
+    double col[7];
+    if (l < 14) {
+      sim3::edge_jacobian_column(s_M[es], s_M[es] + sim3::JAC_SUMS, C, l, A.dof_mask, col);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 7; ++r) col[r] = e[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 7; ++r) s_J[es][l][r] = col[r];
+  }
+  linearize_gram_store<HAS_INFO, HAS_KERNEL>(A, edge, valid, l, s_J[es], HAS_INFO ? s_O[es] : s_J[es], s_G[es]);
+}
+
+// sim3opt_edge_jacobians: one lane per edge, the functions k_linearize_analytic runs, summed in the same order
+__global__ __launch_bounds__(WG) void k_edge_jacobians(EdgeArgs A, int dof_mask, double* __restrict__ e_out,
+                                                      double* __restrict__ J_out) {
+  for (int k = A.e_lo + blockIdx.x * WG + threadIdx.x; k < A.e_hi; k += gridDim.x * WG) {
+    const Sim3 C = load_sim3(A.meas + k);
+    const Sim3 S0 = load_sim3(A.states + A.ev0[k]);
+    const Sim3 S1 = load_sim3(A.states + A.ev1[k]);
+    double e[7], M[sim3::JAC_SUMS], X[13];
+    sim3::edge_error(C, S0, S1, A.opts, e);
+    sim3::left_jacobian_blocks(e, M);
+    sim3::exp_of_residual(e, X);
+#pragma unroll
+    for (int r = 0; r < 7; ++r) e_out[(size_t)7 * k + r] = e[r];
+    for (int c = 0; c < 14; ++c) {
+      double col[7];
+      sim3::edge_jacobian_column(M, X, C, c, dof_mask, col);
+#pragma unroll
+      for (int r = 0; r < 7; ++r) J_out[(size_t)98 * k + 14 * r + c] = col[r];
     }
   }
 }

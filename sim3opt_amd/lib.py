@@ -60,6 +60,7 @@ class Options(C.Structure):
         ("amg_over", C.c_double * 2),
         ("direct_max_pairs", C.c_int64),
         ("debug_full_arrays", C.c_int32),
+        ("jacobians", C.c_int32),
     ]
 
 
@@ -149,6 +150,8 @@ SYMBOLS = {
     "sim3opt_get_kernel_times": (C.c_int, [_vp, C.POINTER(KernelTimes)]),
     "sim3opt_reset_kernel_times": (C.c_int, [_vp]),
     "sim3opt_edge_errors": (C.c_int, [_vp, _dp]),
+    "sim3opt_edge_jacobians": (C.c_int, [_vp, _dp, _dp]),
+    "sim3opt_sim3_edge_jacobian": (C.c_int, [_dp, _dp, _dp, C.POINTER(Options), _dp, _dp]),
     "sim3opt_linearize": (C.c_int, [_vp]),
     "sim3opt_system_dims": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64)]),
     "sim3opt_system_pattern": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64), _ip, _ip]),
@@ -502,6 +505,14 @@ class Graph:
         self._chk(self._L.sim3opt_edge_errors(self._g, _p(e, _dp)))
         return e
 
+    def edge_jacobians(self):
+        """Closed-form Jacobians of every edge at the current estimates (needs fix_small_angle_b=1):
+        e (m, 7) and J (m, 7, 14), columns 0..6 = de/dd0, 7..13 = de/dd1 (updates S <- exp(d) S)."""
+        m = self.num_edges
+        e, J = np.empty((m, 7)), np.empty((m, 7, 14))
+        self._chk(self._L.sim3opt_edge_jacobians(self._g, _p(e, _dp), _p(J, _dp)))
+        return e, J
+
     def linearize(self):
         self._chk(self._L.sim3opt_linearize(self._g))
 
@@ -672,6 +683,20 @@ class Graph:
     def write_poses(self, path, image_ids=None):
         ids = None if image_ids is None else _i32(image_ids)
         self._chk(self._L.sim3opt_write_poses(self._g, os.fsencode(path), _p(ids, _ip)))
+
+
+def edge_jacobian_host(meas, s0, s1, **opts):
+    """sim3opt_sim3_edge_jacobian: e = log(meas s0 s1^-1) (7,) and its closed-form Jacobian J (7, 14), computed on
+    the host by the code the device runs.  opts are Options fields; fix_small_angle_b defaults to 1 here."""
+    opts.setdefault("fix_small_angle_b", 1)
+    o = default_options(**opts)
+    m, a, b = _f64(meas), _f64(s0), _f64(s1)
+    assert m.shape == a.shape == b.shape == (8,)
+    e, J = np.empty(7), np.empty((7, 14))
+    rc = load().sim3opt_sim3_edge_jacobian(_p(m, _dp), _p(a, _dp), _p(b, _dp), C.byref(o), _p(e, _dp), _p(J, _dp))
+    if rc != OK:
+        raise Sim3OptError(rc, "sim3_edge_jacobian: bad state (non-finite, scale <= 0) or fix_small_angle_b != 1")
+    return e, J
 
 
 def read_keyframe_bin(path):
