@@ -311,6 +311,31 @@ int sim3opt_direct_plan(sim3opt_graph* g, int64_t max_pairs, int64_t dims[8], in
                         int32_t* colptr, int32_t* lrow, int32_t* srcptr, int32_t* src,
                         int32_t* pairptr, int32_t* pa, int32_t* pb, int32_t* gptr, int32_t* lcolp,
                         int32_t* rptr, int32_t* cells);
+/* ---- marginal covariances (g2o SparseOptimizer::computeMarginals) ----
+ * Blocks of (H + lambda I)^-1, H linearised at the CURRENT estimates, rows/cols in the tangent order
+ * [omega upsilon sigma] of the oplus increment; cov is n x 49, column-major 7x7 blocks, rows = id_a's
+ * tangent, cols = id_b's.  Pairs: a vertex with itself, or the two ends of any edge (anything else in the
+ * factor's pattern works too; outside it, or a fixed vertex: SIM3OPT_ERR_ARG).  Computed by a selected
+ * inversion on the pattern of the exact block Cholesky, in a context of its own
+ * built at the first call (at most options.direct_max_pairs block products, else 3e7; a refused plan:
+ * SIM3OPT_ERR_STATE with the reason in sim3opt_last_error).  The LM's solver choice and state are left
+ * as they are: optimize() after this call runs exactly as without it.  A singular H + lambda I (lambda = 0
+ * without a fixed vertex, or with a cleared dof_mask bit): SIM3OPT_ERR_STATE.  One GPU only
+ * (world > 1: SIM3OPT_ERR_STATE). */
+int sim3opt_marginals(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_a,
+                      const int32_t* id_b, double* cov);
+/* All free vertices' diagonal blocks, insertion order (nfree x 49); as sim3opt_marginals. */
+int sim3opt_marginal_covariances(sim3opt_graph* g, double lambda, double* cov);
+/* Plan of the selected inversion (host only, no GPU needed, may be called before initialize), on the
+ * factor plan of sim3opt_direct_plan (perm, colptr, lrow, gptr, lcolp as there).  Block s of Z is
+ * ( Z0 - sum_p op(Z[za[p]]) L[zl[p]] ) L(j,j)^-1 over p in zptr[s]..zptr[s+1], in that order, where
+ * op transposes when zt[p] = 1 and Z0 = L(j,j)^-T on a diagonal block, 0 elsewhere; Z and L share the
+ * block numbering of L.  Levels run top-down, off-diagonal blocks of a level before its diagonal ones.
+ * dims = {columns, blocks of L, products, elimination-tree height, groups, levels}.  Two calls: arrays
+ * NULL to size them, then filled.  max_pairs <= 0: 3e7. */
+int sim3opt_marginal_plan(sim3opt_graph* g, int64_t max_pairs, int64_t dims[6], int32_t* perm,
+                          int32_t* colptr, int32_t* lrow, int32_t* gptr, int32_t* lcolp, int32_t* zptr,
+                          int32_t* za, int32_t* zt, int32_t* zl);
 /* Structure of the multigrid hierarchy `preconditioner = 2` would use for this graph (host only, no
  * GPU needed, may be called before initialize): *n_levels levels; rows[l] / blocks[l] = block rows
  * and stored 7x7 blocks of level l (up to `capacity` levels are written); aggregate_of_row (may be

@@ -258,6 +258,8 @@ class Vertex {  // g2o::OptimizableGraph::Vertex, as far as the reference touche
   void setFixed(bool f) { fixed_ = f; }
   bool fixed() const { return fixed_; }
   void setMarginalized(bool) {}  // kitti_surf.cpp:619, :805-813 always pass false
+  // block row of this vertex in H: the k-th free vertex in insertion order, -1 if fixed (or not added)
+  int hessianIndex() const { return hidx_; }
  protected:
   friend class SparseOptimizer;
   friend class G2oEdgeScaleTrans;
@@ -267,6 +269,7 @@ class Vertex {  // g2o::OptimizableGraph::Vertex, as far as the reference touche
   bool pull(double s[8]) const;
   int id_ = -1;
   bool fixed_ = false;
+  int hidx_ = -1;
   SparseOptimizer* owner_ = nullptr;
 };
 
@@ -416,6 +419,30 @@ template <typename T, typename... A> std::unique_ptr<T> make_unique(A&&... a) {
   return std::unique_ptr<T>(new T(std::forward<A>(a)...));
 }
 
+// g2o::SparseBlockMatrix, as far as computeMarginals fills it: blocks addressed by (row, column) block
+// index, M a fixed-size 7 x 7 matrix type with operator()(r, c) (Eigen::Matrix<double, 7, 7>)
+template <class M> class SparseBlockMatrix {
+ public:
+  // the block, or nullptr when it is not stored and alloc is false (alloc: a zero block is added)
+  M* block(int r, int c, bool alloc = false) {
+    auto it = blocks_.find(std::make_pair(r, c));
+    if (it != blocks_.end()) return &it->second;
+    if (!alloc) return nullptr;
+    M z;
+    for (int i = 0; i < 7; ++i)
+      for (int j = 0; j < 7; ++j) z(i, j) = 0.0;
+    return &blocks_.emplace(std::make_pair(r, c), z).first->second;
+  }
+  const M* block(int r, int c) const {
+    auto it = blocks_.find(std::make_pair(r, c));
+    return it == blocks_.end() ? nullptr : &it->second;
+  }
+  size_t nonZeroBlocks() const { return blocks_.size(); }
+  void clear() { blocks_.clear(); }
+ private:
+  std::map<std::pair<int, int>, M> blocks_;
+};
+
 class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 638, 674-675, 688, 726)
  public:
   SparseOptimizer() : g_(sim3opt_create()) { if (!g_) throw std::bad_alloc(); }
@@ -444,6 +471,10 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
     v->state(s);
     if (sim3opt_add_vertex(g_, v->id_, s, v->fixed_ ? 1 : 0) != SIM3OPT_OK) return false;
     v->owner_ = this;
+    if (!v->fixed_) {  // (fixed-ness is passed on at addVertex: the numbering cannot change later)
+      v->hidx_ = (int)free_ids_.size();
+      free_ids_.push_back(v->id_);
+    }
     verts_[v->id_] = std::move(own);
     return true;
   }
@@ -469,6 +500,36 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
   const char* lastError() const { return sim3opt_last_error(g_); }
   sim3opt_graph* handle() { return g_; }
 
+  // Marginal covariances (g2o SparseOptimizer::computeMarginals): the blocks (r, c) of H^-1 at the current
+  // estimates for the listed pairs of hessianIndex() values -- a vertex with itself or the two ends of an
+  // edge -- into spinv.block(r, c).  False (spinv unchanged) when a pair is out of range or outside the
+  // factor's pattern, or H is singular; lastError() says why.  Needs initializeOptimization().
+  template <class M>
+  bool computeMarginals(SparseBlockMatrix<M>& spinv, const std::vector<std::pair<int, int>>& blockIndices) {
+    const int32_t n = (int32_t)blockIndices.size();
+    const int32_t nfree = (int32_t)free_ids_.size();
+    std::vector<int32_t> a(n > 0 ? n : 1), b(n > 0 ? n : 1);
+    for (int32_t q = 0; q < n; ++q) {
+      const int r = blockIndices[q].first, c = blockIndices[q].second;
+      if (r < 0 || c < 0 || r >= nfree || c >= nfree) return false;
+      a[q] = free_ids_[r];
+      b[q] = free_ids_[c];
+    }
+    std::vector<double> cov(49 * (size_t)(n > 0 ? n : 1));
+    if (sim3opt_marginals(g_, 0.0, n, a.data(), b.data(), cov.data()) != SIM3OPT_OK) return false;
+    for (int32_t q = 0; q < n; ++q) {
+      M* m = spinv.block(blockIndices[q].first, blockIndices[q].second, true);
+      for (int c = 0; c < 7; ++c)
+        for (int r = 0; r < 7; ++r) (*m)(r, c) = cov[49 * (size_t)q + r + 7 * c];
+    }
+    return true;
+  }
+  template <class M> bool computeMarginals(SparseBlockMatrix<M>& spinv, const Vertex* vertex) {
+    if (!vertex || vertex->hessianIndex() < 0) return false;
+    const int h = vertex->hessianIndex();
+    return computeMarginals(spinv, std::vector<std::pair<int, int>>{{h, h}});
+  }
+
  private:
   friend class Vertex;
   // the first vertex / edge decides what this optimizer optimises (kitti_surf.cpp:809-814)
@@ -486,6 +547,7 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
   GraphKind kind_ = GraphKind::Unset;
   std::unique_ptr<OptimizationAlgorithmLevenberg> alg_;
   std::map<int, std::unique_ptr<Vertex>> verts_;
+  std::vector<int> free_ids_;  // id of the vertex of each hessianIndex
 };
 
 inline void Vertex::push() {
@@ -508,6 +570,7 @@ using sim3opt_shim::LinearSolverEigen;
 using sim3opt_shim::make_unique;
 using sim3opt_shim::OptimizationAlgorithmLevenberg;
 using sim3opt_shim::Sim3;
+using sim3opt_shim::SparseBlockMatrix;
 using sim3opt_shim::SparseOptimizer;
 }  // namespace g2o
 namespace vio {

@@ -597,6 +597,66 @@ int sim3opt_direct_plan(sim3opt_graph* g, int64_t max_pairs, int64_t dims[8], in
   }
 }
 
+int sim3opt_marginals(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_a,
+                      const int32_t* id_b, double* cov) {
+  try {
+  if (!g || n < 0 || (n > 0 && (!id_a || !id_b || !cov))) return fail(g, SIM3OPT_ERR_ARG, "marginals: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "marginals: call sim3opt_initialize first");
+  std::vector<int32_t> ra(std::max(n, 1)), rb(std::max(n, 1));
+  for (int32_t q = 0; q < n; ++q) {
+    const auto a = g->host.id2idx.find(id_a[q]), b = g->host.id2idx.find(id_b[q]);
+    if (a == g->host.id2idx.end() || b == g->host.id2idx.end()) return fail(g, SIM3OPT_ERR_ARG, "marginals: unknown vertex id");
+    ra[q] = g->structure.hidx[a->second];
+    rb[q] = g->structure.hidx[b->second];
+    if (ra[q] < 0 || rb[q] < 0) return fail(g, SIM3OPT_ERR_ARG, "marginals: fixed vertex in a pair");
+  }
+  return engine_marginals(g->engine, lambda, n, ra.data(), rb.data(), cov, g->err);
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "marginals: out of host memory or internal error");
+  }
+}
+
+int sim3opt_marginal_covariances(sim3opt_graph* g, double lambda, double* cov) {
+  try {
+  if (!g || !cov) return fail(g, SIM3OPT_ERR_ARG, "marginal_covariances: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "marginal_covariances: call sim3opt_initialize first");
+  std::vector<int32_t> rows;  // free vertices in insertion order
+  for (int32_t v = 0; v < g->host.nv(); ++v)
+    if (g->structure.hidx[v] >= 0) rows.push_back(g->structure.hidx[v]);
+  return engine_marginals(g->engine, lambda, (int32_t)rows.size(), rows.data(), rows.data(), cov, g->err);
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "marginal_covariances: out of host memory or internal error");
+  }
+}
+
+int sim3opt_marginal_plan(sim3opt_graph* g, int64_t max_pairs, int64_t dims[6], int32_t* perm,
+                          int32_t* colptr, int32_t* lrow, int32_t* gptr, int32_t* lcolp, int32_t* zptr,
+                          int32_t* za, int32_t* zt, int32_t* zl) {
+  try {
+  if (!g || !dims) return fail(g, SIM3OPT_ERR_ARG, "marginal_plan: bad argument");
+  Structure st;
+  if (!build_structure(g->host, st, g->err)) return SIM3OPT_ERR_STATE;
+  DirectPlan P;
+  SelinvPlan S;
+  std::string why;
+  if (!build_direct_plan(st.nb, st.rowptr.data(), st.colidx.data(), max_pairs > 0 ? max_pairs : 30000000, 0, P, why) ||
+      !build_selinv_plan(P, S, why)) {
+    g->err = "marginal_plan: " + why;
+    return SIM3OPT_ERR_STATE;
+  }
+  dims[0] = P.nb; dims[1] = P.nL; dims[2] = S.nprod; dims[3] = P.height; dims[4] = P.ngroups();
+  dims[5] = (int64_t)P.lcolp.size() - 1;
+  auto out = [](int32_t* dst, const std::vector<int32_t>& v) {
+    if (dst && !v.empty()) std::memcpy(dst, v.data(), sizeof(int32_t) * v.size());
+  };
+  out(perm, P.perm); out(colptr, P.colptr); out(lrow, P.lrow); out(gptr, P.gptr); out(lcolp, P.lcolp);
+  out(zptr, S.zptr); out(za, S.za); out(zt, S.zt); out(zl, S.zl);
+  return SIM3OPT_OK;
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "marginal_plan: out of host memory or internal error");
+  }
+}
+
 int sim3opt_amg_hierarchy(sim3opt_graph* g, int32_t capacity, int32_t* n_levels, int32_t* rows,
                           int64_t* blocks, int32_t* aggregate_of_row) {
   try {

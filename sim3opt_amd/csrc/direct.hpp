@@ -73,4 +73,21 @@ struct DirectPlan {
 bool build_direct_plan(int32_t nb, const int32_t* rowptr, const int32_t* colidx, int64_t max_pairs,
                        int32_t subtree_cols, DirectPlan& plan, std::string& why, int32_t sub_waves = 8);
 
+// Selected inverse Z = (H + lambda I)^-1 on the pattern of L (selinv.cpp, selinv_kernels.hpp): block s of
+// Z (same slot numbering as L) is Z0 - sum of the listed products, times L(j,j)^-1, where product p is
+// op(Z[za[p]]) L[zl[p]] (op = transpose when zt[p]) and Z0 = L(j,j)^-T on a diagonal block, 0 elsewhere.
+// The lists run over the column's rows k in ascending REFERENCE position (the order of the backward solve,
+// bord): the same order of summation under every schedule.
+struct SelinvPlan {
+  int64_t nprod = 0;            // 7x7x7 products of one selected inversion
+  std::vector<int32_t> zptr;    // nL + 1 -> za / zt / zl
+  std::vector<int32_t> za;      // slot of Z(max(i,k), min(i,k))
+  std::vector<int32_t> zt;      // 1: that block is used transposed (Z(i,k) = Z(k,i)^T for k > i)
+  std::vector<int32_t> zl;      // slot of L(k, j)
+};
+
+// Lists of the selected inversion for a plan of build_direct_plan.  False (with a reason) only when the
+// pattern is not closed under the recursion -- an internal error.
+bool build_selinv_plan(const DirectPlan& plan, SelinvPlan& sel, std::string& why);
+
 }  // namespace sim3opt

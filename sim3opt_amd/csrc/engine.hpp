@@ -38,6 +38,9 @@ int engine_get_system(Engine* e, int32_t* rowptr, int32_t* colidx, double* value
                       std::string& err);
 int engine_solve(Engine* e, double lambda, double* x, int32_t* iters, double* rel_res,
                  std::string& err);
+// blocks (row_a[q], row_b[q]) of (H + lambda I)^-1, H linearised at the current estimates (engine_direct.hip)
+int engine_marginals(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
+                     std::string& err);
 int engine_bench_spmv(Engine* e, int32_t reps, double* ms_mean, std::string& err);
 int engine_bench_stream(Engine* e, int32_t mode, int32_t reps, double* ms_mean, std::string& err);
 int engine_preconditioner(const Engine* e);

@@ -3,6 +3,7 @@
 //   engine_pcg.hip     the preconditioned CG (LinearSolverEigen's role on graphs too large to factor), halo exchange
 //   engine_amg.hip     the aggregation-multigrid preconditioner: set-up per linearisation / per trial, the cycle
 //   engine_direct.hip  the exact sparse block Cholesky (LinearSolverEigen's role on KITTI-00-like graphs)
+//                      and the selected inversion on its pattern (marginal covariances; selinv_kernels.hpp)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
 // engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, direct_kernels.hpp -> engine_direct.hip); only the
 // SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through an Engine method.
@@ -429,6 +430,28 @@ class Engine {
   // caller together with the trial's chi2: no extra round trip).
   int direct_solve(double lambda, std::string& err);
   void direct_gather();  // once per linearisation: H in the layout of L, b permuted (k_ldl_gather)
+
+  // ---- marginal covariances: blocks of (H + lambda I)^-1 by a selected inversion (selinv.cpp,
+  // selinv_kernels.hpp) ----
+  // A context of its own -- plan, factor, flag -- whatever linear solver the LM uses, built at the first
+  // call: the LM's buffers and scalars are never written, so a call between two optimize() calls leaves
+  // the second one as it was (the relinearisation it does is repeated by every LM iteration anyway).
+  DirectPlan mplan;
+  SelinvPlan msel;
+  LdlArgs mldl{};
+  std::vector<int32_t> mpos;  // block row of H -> column of L
+  const int32_t *m_zptr = nullptr, *m_za = nullptr, *m_zt = nullptr, *m_zl = nullptr;
+  double* m_Z = nullptr;
+  DevScalars* m_sc = nullptr;  // the factor's flag (fail); followed by m_singular (k_selinv_pivots)
+  int32_t* m_singular = nullptr;
+  int m_wg_sub = LDL_WG_SUB;
+  bool marg_ready = false;
+  std::string marg_refused;  // why the plan was refused (the call fails the same way every time)
+  int marginal_init(std::string& err);
+  // cov[q] (column-major 7x7) = block (row_a[q], row_b[q]) of (H + lambda I)^-1, H linearised at the current
+  // estimates; rows are block rows of H (free vertices)
+  int marginals(double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
+                std::string& err);
   // block-Jacobi inverses Minv = omega (D + lambda W)^-1 of rows [lo, hi) (k_jacobi; engine_pcg.hip)
   void jacobi(int lo, int hi, const int32_t* rowptr, double* vals, double lambda, double* Minv, double omega,
               const double* diagH, const double* W, float* vals32, DevScalars* sc = nullptr,

@@ -164,6 +164,10 @@ SYMBOLS = {
     "sim3opt_linear_solver_in_use": (C.c_int, [_vp]),
     "sim3opt_direct_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _ip,
                                       _ip, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_marginals": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp]),
+    "sim3opt_marginal_covariances": (C.c_int, [_vp, C.c_double, _dp]),
+    "sim3opt_marginal_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _ip,
+                                        _ip, _ip, _ip]),
     "sim3opt_comm_allgather_plan": (C.c_int, [C.c_int32, C.c_int32, _ip, C.POINTER(C.c_int64),
                                               C.POINTER(C.c_int64)]),
     "sim3opt_comm_unique_id": (C.c_int, [_up]),
@@ -602,6 +606,37 @@ class Graph:
         out = {k: out[k][:n] for k, n in arr.items()}
         out.update(nb=nb, nL=nL, npairs=npairs, height=height, ngroups=ngroups, nlevels=nlev,
                    nrounds=nrounds)
+        return out
+
+    def marginals(self, pairs, lam=0.0):
+        """Blocks (a, b) of (H + lam I)^-1 at the current estimates for pairs [(id_a, id_b), ...]: (n, 7, 7)
+        indexed [q, r, c], rows = id_a's tangent [omega upsilon sigma], cols = id_b's."""
+        pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, b = _i32(pr[:, 0]), _i32(pr[:, 1])
+        n = pr.shape[0]
+        cov = np.empty((max(n, 1), 49))
+        self._chk(self._L.sim3opt_marginals(self._g, float(lam), n, _p(a, _ip), _p(b, _ip), _p(cov, _dp)))
+        return cov[:n].reshape(-1, 7, 7).transpose(0, 2, 1).copy()
+
+    def marginal_covariances(self, lam=0.0):
+        """Diagonal blocks of (H + lam I)^-1 of every free vertex, insertion order: (nfree, 7, 7)."""
+        nb, _ = self.system_dims()
+        cov = np.empty((max(nb, 1), 49))
+        self._chk(self._L.sim3opt_marginal_covariances(self._g, float(lam), _p(cov, _dp)))
+        return cov[:nb].reshape(-1, 7, 7).transpose(0, 2, 1).copy()
+
+    def marginal_plan(self, max_pairs=0):
+        """Plan of the selected inversion (on the factor's plan) as a dict of numpy arrays; host only."""
+        dims = np.zeros(6, dtype=np.int64)
+        dp = dims.ctypes.data_as(C.POINTER(C.c_int64))
+        self._chk(self._L.sim3opt_marginal_plan(self._g, int(max_pairs), dp, *([None] * 9)))
+        nb, nL, nprod, height, ngroups, nlev = (int(x) for x in dims)
+        arr = dict(perm=nb, colptr=nb + 1, lrow=nL, gptr=ngroups + 1, lcolp=nlev + 1, zptr=nL + 1,
+                   za=nprod, zt=nprod, zl=nprod)
+        out = {k: np.zeros(max(n, 1), dtype=np.int32) for k, n in arr.items()}
+        self._chk(self._L.sim3opt_marginal_plan(self._g, int(max_pairs), dp, *[_p(out[k], _ip) for k in arr]))
+        out = {k: out[k][:n] for k, n in arr.items()}
+        out.update(nb=nb, nL=nL, nprod=nprod, height=height, ngroups=ngroups, nlevels=nlev)
         return out
 
     def amg_hierarchy(self):
