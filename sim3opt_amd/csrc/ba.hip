@@ -19,8 +19,8 @@
 //                 A^T A) - sum over the listed observation pairs Z_o1 (A^T B)_o2^T (lane = pair, fixed-order
 //                 butterfly sum); the diagonal block's wavefront also forms g_i = b_c,i - sum Z_o b_p(o)
 //   k_ldl*        the reduced camera system S dx_c = g solved exactly: the level-scheduled block
-//                 Cholesky of direct.hpp / direct_kernels.hpp (written for the 7x7 blocks of the
-//                 Sim(3) graphs; the 6x6 camera blocks are stored padded to 7x7 with a unit diagonal
+//                 Cholesky of direct.hpp, run by a BlockLdl (direct_factor.hpp; written for the 7x7 blocks
+//                 of the Sim(3) graphs; the 6x6 camera blocks are stored padded to 7x7 with a unit diagonal
 //                 entry, which leaves the factorisation of the 6x6 part untouched)
 //   k_ba_pcg      fallback when a factorisation would be too large: block-Jacobi PCG in ONE workgroup
 //   k_ba_backsub  thread / point: dx_p = H_pp^-1 b_p - sum Z_o^T dx_c(cam(o))
@@ -40,7 +40,7 @@
 
 #include "../../include/sim3opt.h"
 #include "devmem.hpp"
-#include "direct.hpp"
+#include "direct_factor.hpp"
 
 namespace sim3opt_bundle {
 
@@ -65,10 +65,7 @@ struct Scal {
   double pcg_rel;
 };
 
-// the exact block Cholesky kernels, instantiated for this translation unit
-using DevScalars = Scal;
-using sim3opt::DirectPlan;
-#include "direct_kernels.hpp"
+using sim3opt::ldl_sum_over_c;
 
 __device__ __forceinline__ void quat_to_R(const double q[4], double R[9]) {
   const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -627,14 +624,12 @@ struct Problem {
   Scal *d_sc = nullptr, *h_sc = nullptr;
   int32_t nblk = 0;
   int grid_chi = 1;
-  DirectPlan dplan;  // exact factorisation of the reduced camera system (empty: PCG fallback)
-  LdlArgs ldl{};
-  bool use_direct = false;
-  int ldl_wg_sub = LDL_WG_TOP;
+  sim3opt::BlockLdl direct;  // exact factorisation of the reduced camera system (not ready: PCG fallback)
 
   ~Problem() { release(); }
   void release() {
     if (stream) (void)hipStreamSynchronize(stream);
+    direct.release();
     for (void* p : owned)
       if (p) sim3opt::dev_free(p);  // (the library's block cache: an out-of-memory hipMalloc elsewhere flushes it)
     owned.clear();
@@ -737,8 +732,6 @@ struct Problem {
     cam_fixed.resize(NC, 0);
     BCHK(up(d_fixed, cam_fixed));
     // the reduced camera system's factorisation plan (nested dissection, level schedule: direct.hpp)
-    use_direct = false;
-    dplan = DirectPlan();
     if (opt.linear_solver != 0) {
       int64_t max_pairs = 8000000;
       if (const char* ev = std::getenv("SIM3OPT_BA_MAX_PAIRS")) max_pairs = std::atoll(ev);
@@ -746,42 +739,15 @@ struct Problem {
       // camera chain is a wide band (tracks span several keyframes), its separators are several
       // columns wide and the top of the tree is expensive -- more of it goes to the parallel groups
       // than for the pose graphs (profiles/r2_ba_sweep.log)
-      int32_t subtree = std::max(16, NC / 6);
-      if (const char* ev = std::getenv("SIM3OPT_BA_SUBTREE")) subtree = std::atoi(ev);  // tuning knobs
-      if (const char* ev = std::getenv("SIM3OPT_BA_WG_SUB")) ldl_wg_sub = std::max(64, std::min(LDL_WG_TOP, std::atoi(ev) / 64 * 64));
+      const int32_t subtree = std::max(16, NC / 6);
       std::string why;
-      if (sim3opt::build_direct_plan(NC, rptr.data(), bcol.data(), max_pairs, subtree, dplan, why, ldl_wg_sub / 64)) {
-        int32_t *pperm, *pcolptr, *plrow, *plcol, *psrcptr, *psrc, *ppairptr, *ppa, *ppb, *ppcol, *pgptr, *plcolp,
-            *prptr, *pcells, *pbord, *pbrow, *ptpre, *ptprey;
-        BCHK(up(pperm, dplan.perm)); BCHK(up(pcolptr, dplan.colptr)); BCHK(up(plrow, dplan.lrow));
-        BCHK(up(plcol, dplan.lcol)); BCHK(up(psrcptr, dplan.srcptr)); BCHK(up(psrc, dplan.src));
-        BCHK(up(ppairptr, dplan.pairptr)); BCHK(up(ppa, dplan.pa)); BCHK(up(ppb, dplan.pb));
-        BCHK(up(ppcol, dplan.pcol)); BCHK(up(pgptr, dplan.gptr)); BCHK(up(plcolp, dplan.lcolp));
-        BCHK(up(prptr, dplan.rptr)); BCHK(up(pcells, dplan.cells));
-        BCHK(up(pbord, dplan.bord)); BCHK(up(pbrow, dplan.brow));
-        BCHK(up(ptpre, dplan.tpre)); BCHK(up(ptprey, dplan.tprey));
-        ldl.tpre = ptpre; ldl.tprey = ptprey;
-        ldl.ntpre = (int32_t)dplan.tpre.size(); ldl.ntprey = (int32_t)dplan.tprey.size();
-        ldl.perm = pperm; ldl.colptr = pcolptr; ldl.lrow = plrow; ldl.lcol = plcol; ldl.srcptr = psrcptr;
-        ldl.src = psrc; ldl.pairptr = ppairptr; ldl.pa = ppa; ldl.pb = ppb; ldl.pcol = ppcol; ldl.gptr = pgptr;
-        ldl.lcolp = plcolp; ldl.rptr = prptr; ldl.cells = pcells; ldl.bord = pbord; ldl.brow = pbrow;
-        ldl.nb = NC;
-        ldl.nL = (int32_t)dplan.nL;
-        BCHK(alloc(ldl.Aperm, 49 * (size_t)dplan.nL)); BCHK(alloc(ldl.bp, 7 * (size_t)NC));
-        BCHK(alloc(ldl.L, 49 * (size_t)dplan.nL)); BCHK(alloc(ldl.Dinv, 49 * (size_t)NC));
-        BCHK(alloc(ldl.y, 7 * (size_t)NC)); BCHK(alloc(ldl.xp, 7 * (size_t)NC));
-        ldl.dbg = nullptr;
-        if (std::getenv("SIM3OPT_BA_TRACE")) {  // tuning aid: time stamps of the top group's levels / rounds
-          double* p = nullptr;
-          BCHK(alloc(p, 256));
-          ldl.dbg = reinterpret_cast<long long*>(p);
-        }
-        ldl.lambda = 0.0;  // S carries the damping already
-        use_direct = true;
+      if (direct.build_plan(NC, rptr.data(), bcol.data(), max_pairs, subtree, "SIM3OPT_BA", false, why)) {
+        BA_HIPCHK(direct.upload(stream));  // (synchronised below)
+        const sim3opt::DirectPlan& P = direct.plan();
         if (opt.verbose)
           std::fprintf(stderr, "sim3opt ba: exact block Cholesky of the reduced system: %d cameras, %lld blocks in L, "
-                       "%lld block products, tree height %d, %d groups\n", NC, (long long)dplan.nL,
-                       (long long)dplan.npairs, dplan.height, dplan.ngroups());
+                       "%lld block products, tree height %d, %d groups\n", NC, (long long)P.nL,
+                       (long long)P.npairs, P.height, P.ngroups());
       } else if (opt.linear_solver == 1) {
         err = "linear_solver = 1: " + why;
         return SIM3OPT_ERR_ARG;
@@ -877,21 +843,9 @@ struct Problem {
         hipLaunchKernelGGL(k_ba_reduced, dim3((nblk + 3) / 4), dim3(WG), 0, stream, nblk, d_brow, d_bcol,
                            d_sptr, d_sa, d_sb, d_op, d_lin, d_Z, d_bp, d_fixed, lambda, d_S, d_g, d_bc,
                            d_cdmax);
-        if (use_direct) {
-          ldl.vals = d_S; ldl.b = d_g; ldl.x = d_xc; ldl.sc = d_sc;
-          hipLaunchKernelGGL(k_ldl_gather, dim3(std::max(1, std::min(1024, (ldl.nL + 3) / 4))), dim3(WG), 0, stream, ldl);
-          const int ng = dplan.ngroups();
-          if (ng > 1) hipLaunchKernelGGL((k_ldl<true, false>), dim3(ng - 1), dim3(ldl_wg_sub), 0, stream, ldl, 0);
-          hipLaunchKernelGGL((k_ldl<true, true>), dim3(1), dim3(LDL_WG_TOP), 0, stream, ldl, ng - 1);
-          if (ng > 1) hipLaunchKernelGGL((k_ldl<false, true>), dim3(ng - 1), dim3(ldl_wg_sub), 0, stream, ldl, 0);
-          if (ldl.dbg) {
-            long long h[256];
-            BA_HIPCHK(hipStreamSynchronize(stream));
-            BA_HIPCHK(hipMemcpy(h, ldl.dbg, sizeof(h), hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "sim3opt ba: top group stamps [us] (level start, after A+B of each round, ..., down start, end):");
-            for (long long i = 0; i < h[255] && i < 255; ++i) std::fprintf(stderr, " %.1f", (h[i] - h[0]) * 0.01);
-            std::fprintf(stderr, "\n");
-          }
+        if (direct.ready()) {
+          direct.gather(d_S, d_g, stream);
+          BA_HIPCHK(direct.factor(0.0, &d_sc->fail, 1, d_xc, stream));  // lambda 0: S carries the damping already
         } else {
           hipLaunchKernelGGL(k_ba_pcg, dim3(1), dim3(1024), 0, stream, NC, d_rptr, d_bcol, d_S, d_g, d_xc, d_r,
                              d_z, d_p, d_q, d_Dinv, opt.pcg_max_iters > 0 ? opt.pcg_max_iters : 20 * NC + 100,

@@ -1,5 +1,5 @@
-// dev_common.hpp -- device helpers shared by every kernel header (included by engine_impl.hpp inside
-// namespace sim3opt, after DevScalars): fixed-order reductions, the Sim3 load, the FP32 pair layout.
+// dev_common.hpp -- device helpers shared by every kernel header (included inside namespace sim3opt, after WG
+// and Sim3, by engine_impl.hpp and direct_factor.hip): fixed-order reductions, the Sim3 load, the FP32 pair layout.
 #pragma once
 // ------------------------------------------------------------------------------------------
 // reductions (fixed order => deterministic)

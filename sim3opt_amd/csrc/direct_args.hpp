@@ -1,6 +1,5 @@
 // direct_args.hpp -- argument block and launch constants of the exact block Cholesky kernels
-// (direct_kernels.hpp); included inside the namespace of the translation unit that uses them (the pose-graph
-// engine, the bundle adjuster), after DevScalars and direct.hpp.
+// (direct_kernels.hpp); included by direct_factor.hip only, inside namespace sim3opt, after direct.hpp.
 #pragma once
 struct LdlArgs {
   const int32_t* perm;
@@ -32,15 +31,15 @@ struct LdlArgs {
   double* xp;          // 7 nb, elimination order
   double* x;           // 7 nb, block rows of H (the result)
   int32_t nb, nL;
-  int32_t fail_token = 1;  // what a non-positive pivot writes into sc->fail (the engine: a number per solve)
+  int32_t fail_token = 1;  // what a non-positive pivot writes into *fail (the LM: a number per solve)
   double lambda;
-  DevScalars* sc;
-  long long* dbg;  // tuning aid (SIM3OPT_DIRECT_TRACE): wall_clock64 stamps of the top group's levels
+  int32_t* fail;           // the caller's fail word
+  long long* dbg;  // tuning aid (<knobs>_TRACE, direct_factor.hpp): wall_clock64 stamps of the top group's levels
 };
 
 constexpr int LDL_WG_TOP = 64 * DirectPlan::CELL_WAVES;  // the top of the tree: one workgroup of 8
 // wavefronts (512 threads leave each wavefront 256 VGPRs: with 1024 the operand batches spilled)
-constexpr int LDL_WG_SUB = 512;                          // bottom subtrees: 8 wavefronts each too (round 3 sweep)
+constexpr int LDL_WG_SUB = 512;                          // bottom subtrees: 8 wavefronts each too (round 3 sweep; BA too)
 constexpr int LDL_CS = DirectPlan::CELL_SLOTS;
 constexpr int LDL_ST = DirectPlan::CELL_STRIDE;
 constexpr int LDL_NW = DirectPlan::CELL_WAVES;

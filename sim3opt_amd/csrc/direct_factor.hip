@@ -1,0 +1,150 @@
+// direct_factor.hip -- BlockLdl (direct_factor.hpp): the one translation unit that holds and launches the exact
+// block Cholesky kernels (direct_kernels.hpp) and the selected inversion on their pattern (selinv_kernels.hpp).
+#include "direct_factor.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <cstdio>
+#include <cstdlib>
+
+#include "sim3_math.hpp"
+
+namespace sim3opt {
+
+using sim3::Sim3;
+constexpr int WG = 256;  // the streaming kernels: 4 wavefronts of 64
+
+#include "dev_common.hpp"
+#include "direct_args.hpp"
+#include "direct_kernels.hpp"
+#include "selinv_kernels.hpp"
+
+struct BlockLdl::Dev {
+  LdlArgs A{};
+  SelArgs S{};  // (maxdiag_bits, singular: per call)
+  int32_t* flags = nullptr;
+};
+
+BlockLdl::BlockLdl() : d_(new Dev) {}
+BlockLdl::~BlockLdl() { release(); }
+int32_t* BlockLdl::selinv_flags() const { return d_->flags; }
+
+bool BlockLdl::build_plan(int32_t nb, const int32_t* rowptr, const int32_t* colidx, int64_t max_pairs,
+                          int32_t subtree, const char* knobs, bool with_selinv, std::string& why) {
+  release();
+  knobs_ = knobs;
+  auto knob = [&](const char* name) { return std::getenv((knobs_ + name).c_str()); };
+  if (const char* ev = knob("_SUBTREE")) subtree = std::atoi(ev);
+  wg_sub_ = LDL_WG_SUB;
+  if (const char* ev = knob("_WG_SUB")) wg_sub_ = std::max(64, std::min(LDL_WG_TOP, std::atoi(ev) / 64 * 64));
+  trace_ = knob("_TRACE") != nullptr;  // tuning aid: time stamps of the top group's levels / rounds
+  if (build_direct_plan(nb, rowptr, colidx, max_pairs, subtree, plan_, why, wg_sub_ / 64) &&
+      (!with_selinv || build_selinv_plan(plan_, sel_, why)))
+    return true;
+  release();
+  return false;
+}
+
+hipError_t BlockLdl::upload(hipStream_t stream, StagedUploads* staged) {
+  hipError_t e = hipSuccess;
+  auto up = [&](const int32_t*& dptr, const std::vector<int32_t>& h) {
+    int32_t* p = nullptr;
+    if (e == hipSuccess) e = dev_malloc((void**)&p, sizeof(int32_t) * std::max<size_t>(h.size(), 1));
+    if (e != hipSuccess) return;
+    owned_.push_back(p);
+    dptr = p;
+    if (!h.empty())
+      e = staged ? staged->put(p, h.data(), sizeof(int32_t) * h.size(), stream)
+                 : hipMemcpyAsync(p, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice, stream);
+  };
+  auto alloc = [&](double*& dptr, size_t count) {
+    count = std::max<size_t>(count, 1);
+    if (e == hipSuccess) e = dev_malloc((void**)&dptr, sizeof(double) * count);
+    if (e != hipSuccess) return;
+    owned_.push_back(dptr);
+    e = hipMemset(dptr, 0, sizeof(double) * count);
+  };
+  const DirectPlan& P = plan_;
+  LdlArgs& A = d_->A;
+  up(A.perm, P.perm); up(A.colptr, P.colptr); up(A.lrow, P.lrow); up(A.lcol, P.lcol);
+  up(A.srcptr, P.srcptr); up(A.src, P.src); up(A.pairptr, P.pairptr); up(A.pa, P.pa); up(A.pb, P.pb);
+  up(A.pcol, P.pcol); up(A.gptr, P.gptr); up(A.lcolp, P.lcolp); up(A.tpre, P.tpre); up(A.tprey, P.tprey);
+  up(A.bord, P.bord); up(A.brow, P.brow); up(A.rptr, P.rptr); up(A.cells, P.cells);
+  A.ntpre = (int32_t)P.tpre.size(); A.ntprey = (int32_t)P.tprey.size();
+  A.nb = P.nb; A.nL = (int32_t)P.nL;
+  alloc(A.Aperm, 49 * (size_t)P.nL); alloc(A.bp, 7 * (size_t)P.nb); alloc(A.L, 49 * (size_t)P.nL);
+  alloc(A.Dinv, 49 * (size_t)P.nb); alloc(A.y, 7 * (size_t)P.nb); alloc(A.xp, 7 * (size_t)P.nb);
+  double* p = nullptr;
+  if (trace_) {
+    alloc(p, 256);
+    A.dbg = reinterpret_cast<long long*>(p);
+  }
+  if (!sel_.zptr.empty()) {  // (selected inversion planned)
+    SelArgs& S = d_->S;
+    up(S.zptr, sel_.zptr); up(S.za, sel_.za); up(S.zt, sel_.zt); up(S.zl, sel_.zl);
+    alloc(S.Z, 49 * (size_t)P.nL);
+    S.colptr = A.colptr; S.lrow = A.lrow; S.lcol = A.lcol; S.gptr = A.gptr; S.lcolp = A.lcolp;
+    S.L = A.L; S.Dinv = A.Dinv; S.nb = A.nb;
+    alloc(p, 1);
+    d_->flags = reinterpret_cast<int32_t*>(p);
+  }
+  ready_ = e == hipSuccess;
+  return e;
+}
+
+void BlockLdl::gather(const double* vals, const double* b, hipStream_t stream) {
+  LdlArgs& A = d_->A;
+  A.vals = vals;
+  A.b = b;
+  hipLaunchKernelGGL(k_ldl_gather, dim3(std::max(1, std::min(1024, (A.nL + 3) / 4))), dim3(WG), 0, stream, A);
+}
+
+hipError_t BlockLdl::factor(double lambda, int32_t* fail, int32_t token, double* x, hipStream_t stream) {
+  LdlArgs& A = d_->A;
+  A.lambda = lambda;
+  A.fail = fail;
+  A.fail_token = token;
+  A.x = x;
+  const int ng = plan_.ngroups();
+  if (ng > 1) hipLaunchKernelGGL((k_ldl<true, false>), dim3(ng - 1), dim3(wg_sub_), 0, stream, A, 0);
+  if (x) hipLaunchKernelGGL((k_ldl<true, true>), dim3(1), dim3(LDL_WG_TOP), 0, stream, A, ng - 1);
+  else hipLaunchKernelGGL((k_ldl<true, false>), dim3(1), dim3(LDL_WG_TOP), 0, stream, A, ng - 1);
+  if (x && ng > 1) hipLaunchKernelGGL((k_ldl<false, true>), dim3(ng - 1), dim3(wg_sub_), 0, stream, A, 0);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !x || !A.dbg) return e;
+  long long h[256];
+  e = hipStreamSynchronize(stream);
+  if (e == hipSuccess) e = hipMemcpy(h, A.dbg, sizeof(h), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  std::fprintf(stderr, "sim3opt: %s_TRACE: top group stamps [us from start] (level start / after A+B per round / "
+               "... / down start / end):", knobs_.c_str());
+  for (long long i = 0; i < h[255] && i < 255; ++i) std::fprintf(stderr, " %.1f", (h[i] - h[0]) * 0.01);
+  std::fprintf(stderr, "\n");
+  return hipSuccess;
+}
+
+void BlockLdl::selinv(const unsigned long long* maxdiag_bits, int32_t* singular, hipStream_t stream) {
+  SelArgs& S = d_->S;
+  S.maxdiag_bits = maxdiag_bits;
+  S.singular = singular;
+  const int ng = plan_.ngroups();
+  hipLaunchKernelGGL(k_selinv_pivots, dim3((7 * S.nb + WG - 1) / WG), dim3(WG), 0, stream, S);
+  hipLaunchKernelGGL(k_selinv, dim3(1), dim3(LDL_WG_TOP), 0, stream, S, ng - 1);
+  if (ng > 1) hipLaunchKernelGGL(k_selinv, dim3(ng - 1), dim3(wg_sub_), 0, stream, S, 0);
+}
+
+void BlockLdl::pick(const int32_t* slot, const int32_t* trans, int32_t n, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_selinv_pick, dim3((49 * n + WG - 1) / WG), dim3(WG), 0, stream, (const double*)d_->S.Z, slot,
+                     trans, n, out);
+}
+
+void BlockLdl::release() {
+  for (void* p : owned_) dev_free(p);
+  owned_.clear();
+  *d_ = Dev{};
+  plan_ = DirectPlan();
+  sel_ = SelinvPlan();
+  ready_ = false;
+}
+
+}  // namespace sim3opt

@@ -1,7 +1,7 @@
-// direct_kernels.hpp -- device side of the exact sparse block Cholesky (included by engine.hip after
-// DevScalars; plan from direct.cpp).  Stands in for LinearSolverEigen::solve (SimplicialLDLT,
-// kitti_surf.cpp:553-554) where the step has to be exact: (H + lambda I) = L L^T on the 7x7 block
-// pattern, then L y = b and L^T x = y, all in elimination order, result scattered back.
+// direct_kernels.hpp -- device side of the exact sparse block Cholesky (included by direct_factor.hip only;
+// plan from direct.cpp).  Stands in for LinearSolverEigen::solve (SimplicialLDLT, kitti_surf.cpp:553-554)
+// where the step has to be exact: (H + lambda I) = L L^T on the 7x7 block pattern, then L y = b and
+// L^T x = y, all in elimination order, result scattered back.
 //
 // Left-looking by levels of the elimination tree; a level is a contiguous range of columns and of
 // stored blocks (direct.hpp).  One workgroup owns one group of the schedule and walks its levels
@@ -29,24 +29,7 @@
 // lane walking its LDS copy, 2.6 us; 10-12 us in all.  Now: staging 1.5, products from LDS 2.9, Cholesky
 // + inverse in registers + y 2.0, phase C 0.8 = 7.2 us.
 #pragma once
-// (included inside namespace sim3opt)
-
-#include "direct_args.hpp"
-
-// sum over the 7 lanes that share this lane's column index c (lanes 7c .. 7c+6)
-__device__ __forceinline__ double ldl_sum_over_r(double v, int c49) {
-  double s = 0.0;
-#pragma unroll
-  for (int rr = 0; rr < 7; ++rr) s += __shfl(v, 7 * c49 + rr);
-  return s;
-}
-// sum over the 7 lanes that share this lane's row index r (lanes r, r+7, ..., r+42)
-__device__ __forceinline__ double ldl_sum_over_c(double v, int r49) {
-  double s = 0.0;
-#pragma unroll
-  for (int cc = 0; cc < 7; ++cc) s += __shfl(v, r49 + 7 * cc);
-  return s;
-}
+// (included inside namespace sim3opt, after direct_args.hpp; lane sums: direct_factor.hpp)
 
 // once per linearisation: Aperm[s] = sum of the H blocks behind block s of L; bp = permuted b
 __global__ __launch_bounds__(WG) void k_ldl_gather(LdlArgs A) {
@@ -95,7 +78,7 @@ __device__ __forceinline__ void ldl_factor_diag(const LdlArgs& A, int s, int j, 
       a[rr][k] = v * inv;
     }
   }
-  if (!ok && lane == 0) A.sc->fail = A.fail_token;
+  if (!ok && lane == 0) *A.fail = A.fail_token;
   // column `lane` of the inverse of the lower-triangular factor (lanes 0..6; the others follow along)
   double wic[7];
   {

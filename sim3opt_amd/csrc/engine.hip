@@ -49,9 +49,8 @@ void Engine::release_under_device() {
   parts.clear();
   n_sharded = 0;
   batch_release();
-  for (void* p : direct_owned)
-    if (p) dev_free(p);
-  direct_owned.clear();
+  lm_factor.release();
+  marg_factor.release();
   staged.release();
   if (h_sc) host_free(h_sc);
   for (hipEvent_t e : pool) event_release(e);
@@ -408,7 +407,7 @@ int Engine::linearize(std::string& err) {
     rc = comm.allreduce(&d_sc->trace, 1, 0, stream, err);  // (every rank must take the same decisions)
     if (rc) return rc;
   }
-  if (use_direct) direct_gather();  // the factorisation's starting blocks: H in the layout of L, b permuted
+  if (use_direct) lm_factor.gather(d_vals, d_b, stream);  // the factorisation's starting blocks (k_ldl_gather)
   linearized = true;
   amg_stale = true;
   trace_stale = true;

@@ -2,11 +2,11 @@
 //   engine.hip         initialisation, linearisation, chi2, the LM trial loop (OptimizationAlgorithmLevenberg::solve)
 //   engine_pcg.hip     the preconditioned CG (LinearSolverEigen's role on graphs too large to factor), halo exchange
 //   engine_amg.hip     the aggregation-multigrid preconditioner: set-up per linearisation / per trial, the cycle
-//   engine_direct.hip  the exact sparse block Cholesky (LinearSolverEigen's role on KITTI-00-like graphs)
-//                      and the selected inversion on its pattern (marginal covariances; selinv_kernels.hpp)
+//   engine_direct.hip  when the LM factorises exactly (LinearSolverEigen's role on KITTI-00-like graphs) and the
+//                      marginal covariances: policy over two BlockLdl (direct_factor.hpp, direct_factor.hip)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
-// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, direct_kernels.hpp -> engine_direct.hip); only the
-// SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through an Engine method.
+// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
+// the SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through a method.
 #pragma once
 // (formerly all of engine.hip) -- device-resident Levenberg-Marquardt on a Sim(3) pose graph, gfx950 (MI355X).
 //
@@ -47,7 +47,7 @@
 #include "amg.hpp"
 #include "comm.hpp"
 #include "devmem.hpp"
-#include "direct.hpp"
+#include "direct_factor.hpp"
 #include "engine.hpp"
 
 namespace sim3opt {
@@ -100,7 +100,6 @@ struct DevScalars {
 };
 
 #include "dev_common.hpp"
-#include "direct_args.hpp"
 struct EdgeArgs;  // lm_kernels.hpp
 
 // ------------------------------------------------------------------------------------------
@@ -255,14 +254,11 @@ class Engine {
     if (!use_amg || use_direct || comm.active() || !amg_fp32 || amg_additive || opt.pcg_batch == 1) return 0;
     return opt.pcg_batch > 1 ? std::min(opt.pcg_batch, KB) : KB;
   }
-  // exact sparse block Cholesky (direct.hpp, direct_kernels.hpp): LinearSolverEigen's role on
-  // graphs whose factorisation is cheap (KITTI-00 and other chain-like graphs)
-  DirectPlan dplan;
+  // exact sparse block Cholesky (direct_factor.hpp): LinearSolverEigen's role on graphs whose factorisation
+  // is cheap (KITTI-00 and other chain-like graphs)
+  BlockLdl lm_factor;
   bool use_direct = false;
-  LdlArgs ldl{};
-  int ldl_wg_sub = LDL_WG_SUB;
   int fail_token = 1;  // number of the current exact solve (>= 2): see direct_solve
-  std::vector<void*> direct_owned;
   // chi2 of the current estimates when it is already known (the last accepted trial computed it)
   bool chi_known = false;
   double chi_cache = 0.0;
@@ -406,22 +402,6 @@ class Engine {
   int amg_apply(std::string& err);
 
   // ---- exact sparse block Cholesky ----
-  template <typename T>
-  int direct_up(const T*& dptr, const std::vector<T>& h, std::string& err) {
-    T* p = nullptr;
-    HIPCHK(dev_malloc((void**)&p, sizeof(T) * std::max<size_t>(h.size(), 1)));
-    direct_owned.push_back(p);
-    if (!h.empty()) HIPCHK(staged.put(p, h.data(), sizeof(T) * h.size(), stream));
-    dptr = p;
-    return SIM3OPT_OK;
-  }
-  int direct_alloc(double*& dptr, size_t count, std::string& err) {
-    HIPCHK(dev_malloc((void**)&dptr, sizeof(double) * std::max<size_t>(count, 1)));
-    direct_owned.push_back(dptr);
-    HIPCHK(hipMemset(dptr, 0, sizeof(double) * std::max<size_t>(count, 1)));
-    return SIM3OPT_OK;
-  }
-
   // plan (host, once per initialize) + buffers; leaves use_direct false when the factorisation
   // would be too expensive (the PCG takes over) unless the caller insists
   int direct_init(const Structure& s, std::string& err);
@@ -429,23 +409,14 @@ class Engine {
   // (H + lambda I) x = b, exactly; x in d_x.  A non-positive pivot raises d_sc->fail (read by the
   // caller together with the trial's chi2: no extra round trip).
   int direct_solve(double lambda, std::string& err);
-  void direct_gather();  // once per linearisation: H in the layout of L, b permuted (k_ldl_gather)
 
   // ---- marginal covariances: blocks of (H + lambda I)^-1 by a selected inversion (selinv.cpp,
   // selinv_kernels.hpp) ----
   // A context of its own -- plan, factor, flag -- whatever linear solver the LM uses, built at the first
   // call: the LM's buffers and scalars are never written, so a call between two optimize() calls leaves
   // the second one as it was (the relinearisation it does is repeated by every LM iteration anyway).
-  DirectPlan mplan;
-  SelinvPlan msel;
-  LdlArgs mldl{};
+  BlockLdl marg_factor;
   std::vector<int32_t> mpos;  // block row of H -> column of L
-  const int32_t *m_zptr = nullptr, *m_za = nullptr, *m_zt = nullptr, *m_zl = nullptr;
-  double* m_Z = nullptr;
-  DevScalars* m_sc = nullptr;  // the factor's flag (fail); followed by m_singular (k_selinv_pivots)
-  int32_t* m_singular = nullptr;
-  int m_wg_sub = LDL_WG_SUB;
-  bool marg_ready = false;
   std::string marg_refused;  // why the plan was refused (the call fails the same way every time)
   int marginal_init(std::string& err);
   // cov[q] (column-major 7x7) = block (row_a[q], row_b[q]) of (H + lambda I)^-1, H linearised at the current

@@ -1,5 +1,5 @@
 // selinv_kernels.hpp -- device side of the block selected inversion (g2o's computeMarginals; included by
-// engine_direct.hip after direct_kernels.hpp; lists from selinv.cpp, maths there).  Runs after k_ldl has
+// direct_factor.hip after direct_kernels.hpp; lists from selinv.cpp, maths there).  Runs after k_ldl has
 // factored (H + lambda I) = L L^T (its UP path) into the marginal context's own buffers.
 //
 // One workgroup owns one group of the factor's schedule and walks its levels TOP-DOWN: the top group in
@@ -34,8 +34,8 @@ struct SelArgs {
   const double* Dinv;  // nb x 49, L(j,j)^-1
   double* Z;           // nL x 49, the result
   int32_t nb;
-  const DevScalars* lm_sc;  // the linearisation's max |H_dd| (read only)
-  int32_t* singular;        // set by k_selinv_pivots (k_ldl flags a non-positive pivot in its own scalars)
+  const unsigned long long* maxdiag_bits;  // the linearisation's max |H_dd|, as raw bits (read only)
+  int32_t* singular;  // set by k_selinv_pivots (k_ldl flags a non-positive pivot in its own fail word)
 };
 
 // The 7x7 Cholesky of k_ldl flags a non-positive pivot only.  A singular H (no fixed vertex: the gauge
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(WG) void k_selinv_pivots(SelArgs S) {
   if (t >= 7 * S.nb) return;
   const int j = t / 7, r = t % 7;
   double maxdiag;
-  const unsigned long long bits = S.lm_sc->maxdiag_bits;
+  const unsigned long long bits = *S.maxdiag_bits;
   __builtin_memcpy(&maxdiag, &bits, sizeof(double));
   const double l = S.L[(size_t)49 * S.colptr[j] + 8 * r];
   if (!(l * l > SEL_PIVOT_REL * maxdiag)) *S.singular = 1;  // (the same value from every writer)
