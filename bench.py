@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LM iterations/s of the Sim(3) pose-graph hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one Levenberg-Marquardt iteration (chi2, per-edge residual + numeric Jacobians,
@@ -10,12 +10,20 @@ BASELINE.json configs[2]: the synthetic Manhattan-grid Sim(3) graph, 100k vertic
 inputs resident in HBM before the timed region.  N > 1: the same graph, block rows partitioned
 across the ranks (strong scaling), RCCL all-gather of the PCG direction + fused scalar all-reduce.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints rank 0's ONE
+JSON line: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and what the
+timed steps measured anyway, among it
   roofline      dominant kernel (k_spmv: block-CSR SpMV of the PCG) against the 8 TB/s HBM peak,
                 duration measured live with HIP events on the library's stream in the timed region
+--full adds everything that takes runs of its own, after the timed region:
+  roofline.box_stream / box_clocks   a bare stream of the block array and the clocks under load
+  block_jacobi_pcg, reference_arithmetic, optimize100_to_terminate   comparison legs (--main-only
+                skips them)
   cpu_baseline  the CPU oracle (port of the reference's g2o configuration) timed on rank 0 on the
                 phases of the same workload a CPU can run at full size; plus the KITTI-00 table
-                (reference configuration) where both sides run the whole optimisation
+                (reference configuration) where both sides run the whole optimisation and ba_demo
+                (--no-cpu-baseline skips the three)
+  partition     at N > 1, the row partition the collectives serve
 """
 import argparse
 import json
@@ -51,10 +59,15 @@ def parse():
     ap.add_argument("--time-kernels", type=int, default=1,
                     help="1: HIP-event pair around every SpMV launch of the PCG (roofline figure; "
                          "disables hipGraph replay), 0: untimed launches")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: the box's bare stream "
+                         "and clocks (roofline), the comparison legs, the CPU baselines and the N > 1 "
+                         "partition figures; a plain run does only what the headline needs")
     ap.add_argument("--main-only", action="store_true",
-                    help="skip the comparison legs (block-Jacobi PCG, reference arithmetic): the run "
-                         "rocprofv3 profiles, so its per-kernel averages are those of the timed path")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the comparison legs (block-Jacobi PCG, reference arithmetic, "
+                         "optimize(100))")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines (cpu_baseline, KITTI-00 table, ba_demo)")
     ap.add_argument("--transport", choices=["rccl", "gloo"], default="rccl",
                     help="multi-rank collectives: rccl (default; ncclAllReduce / grouped ncclBroadcast "
                          "on the library's stream) or gloo (host-staged callbacks; lets N ranks share "
@@ -484,7 +497,7 @@ def main():
                     if traffic is not None else None,
                     "avg_launch_ms": avg_ms, "launches": int(kt.n_spmv),
                     "algorithmic_bytes_per_launch": int(spmv_bytes)}
-            if world == 1:
+            if world == 1 and args.full:
                 # what THIS box delivers for a bare stream of the same block array (16 B per lane, non-temporal,
                 # after the timed region): the pool's boxes differ by up to 12 % (profiles/README.md)
                 try:
@@ -573,6 +586,7 @@ def main():
                                             # (N - 1) / N of an all-gather); sent + received bytes of this rank
                                             # for the neighbour exchanges; per PCG iteration
                                             bytes_per_pcg_iteration=by_all / npcg)
+        if ct is not None and args.full:
             # the partition the collectives serve: rows in breadth-first locality order, equal spans
             _, _, bnd, cut = G.partition_plan(world)
             out["partition"] = {"row_order": "breadth-first locality order", "rows": int(nb),
@@ -583,7 +597,7 @@ def main():
                                 # allocated on rank 0 / what one rank holding the whole graph allocates
                                 "block_array_MB_rank0": G.device_bytes()[0] / 1e6,
                                 "block_array_MB_one_rank": G.device_bytes()[1] / 1e6}
-        if world == 1 and G.preconditioner_in_use() != 0 and not args.main_only:
+        if args.full and world == 1 and G.preconditioner_in_use() != 0 and not args.main_only:
             # same K steps with plain block-Jacobi PCG, for comparison (not part of `value`)
             J = L.Graph(device=local_rank, pcg_rel_tol=args.pcg_rel_tol, preconditioner=0,
                         fix_small_angle_b=args.fix_small_angle_b)
@@ -611,7 +625,7 @@ def main():
                 "unconverged_solves": int(sum(int(s.pcg_capped) for s in jstats)),
                 "note": "preconditioner = 0: solves stop at the 1000-iteration cap (truncated, i.e. inexact LM steps)"}
             J.close()
-        if world == 1 and args.fix_small_angle_b == 1 and not args.main_only:
+        if args.full and world == 1 and args.fix_small_angle_b == 1 and not args.main_only:
             # same K steps in the reference's as-written arithmetic (not part of `value`)
             R = L.Graph(device=local_rank, pcg_rel_tol=args.pcg_rel_tol, fix_small_angle_b=0)
             R.add_vertices(g["states"], g["fixed"])
@@ -648,9 +662,9 @@ def main():
                         "iteration).  A trial whose system breaks the PCG down (p.Ap <= 0) is rejected like "
                         "g2o's failed Cholesky"}
             R.close()
-        if world == 1 and not args.main_only:
+        if args.full and world == 1 and not args.main_only:
             out["optimize100_to_terminate"] = optimize100_leg(args, g, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, g, out["ms_linearize_mean"], out["value"])
             # configs both sides actually ran, in the reference's own configuration
             out["kitti00_reference_configuration"] = kitti_table(local_rank)

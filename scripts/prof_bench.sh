@@ -1,13 +1,16 @@
 #!/bin/bash
-# rocprofv3 --kernel-trace --stats of the timed path of bench.py -> gpurun_out/prof_bench/<tag>_kernel_stats.csv
+# rocprofv3 --kernel-trace --stats of the timed path of bench.py -> $OUT/prof_bench/<tag>_kernel_stats.csv
+# (OUT: the results directory, default bench_out, git-ignored)
 TAG=${1:-bench}
 shift
 cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-/root/repo}
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_bench -o $TAG -- python3 bench.py --main-only --no-cpu-baseline "$@" > gpurun_out/prof_bench_$TAG.log 2>&1
-grep -m1 "^{\"metric\"" gpurun_out/prof_bench_$TAG.log > gpurun_out/prof_bench_${TAG}_line.json
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o $TAG -- python3 bench.py --main-only --no-cpu-baseline "$@" > $OUT/prof_bench_$TAG.log 2>&1
+grep -m1 "^{\"metric\"" $OUT/prof_bench_$TAG.log > $OUT/prof_bench_${TAG}_line.json
 python3 - <<PY
 import csv
-rows=list(csv.DictReader(open("gpurun_out/prof_bench/${TAG}_kernel_stats.csv")))
+rows=list(csv.DictReader(open("$OUT/prof_bench/${TAG}_kernel_stats.csv")))
 tot=sum(float(r["TotalDurationNs"]) for r in rows)
 print("total kernel ms %.1f"%(tot/1e6))
 for r in rows[:28]:

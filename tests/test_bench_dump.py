@@ -57,3 +57,12 @@ def test_steps_sets_the_timed_steps(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
     with pytest.raises(SystemExit):
         bench.parse()
+
+
+def test_full_is_opt_in(monkeypatch):
+    # a plain run does only what the headline needs; the legs of their own run behind --full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    args = bench.parse()
+    assert not args.full and (args.steps, args.warmup) == (20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full
