@@ -38,7 +38,25 @@ enum {
   SIM3OPT_ERR_COMM = -6        /* RCCL communicator failure                          */
 };
 
-enum { SIM3OPT_KERNEL_NONE = 0, SIM3OPT_KERNEL_HUBER = 1 };
+/* Robust kernels of an edge (g2o RobustKernel*, robust_kernel_impl.cpp).  rho(e2) and w = rho'(e2) at
+ * e2 = e^T Omega e, d = the kernel's delta:
+ *   NONE           e2                                              1
+ *   HUBER          e2 <= d^2: e2;  else 2 d sqrt(e2) - d^2          1;  d / sqrt(e2)
+ *   PSEUDO_HUBER   2 d^2 (sqrt(1 + e2/d^2) - 1)                    1 / sqrt(1 + e2/d^2)
+ *   CAUCHY         d^2 log(1 + e2/d^2)                             1 / (1 + e2/d^2)
+ *   GEMAN_MCCLURE  d e2 / (d + e2)                                 d^2 / (d + e2)^2
+ *   WELSCH         d^2 (1 - exp(-e2/d^2))                          exp(-e2/d^2)
+ *   FAIR           2 d^2 (a - log(1 + a)),  a = sqrt(e2) / d       1 / (1 + a)
+ *   TUKEY          e2 <= d^2: d^2/3 (1 - (1 - e2/d^2)^3); else d^2/3   (1 - e2/d^2)^2;  0
+ *   SATURATED      e2 <= d^2: e2;  else d^2                        1;  0
+ *   DCS            s = 2d / (d + e2);  s >= 1: e2;  else s^2 e2    1;  s^2
+ * Geman-McClure and DCS take d unsquared (as g2o); DCS's rho is not the integral of its w (g2o's definition).
+ * First order, as g2o: an edge contributes w J^T Omega J and -w J^T Omega e, chi2 sums rho, rho'' is ignored.
+ * Every kind but NONE needs a finite delta > 0. */
+enum { SIM3OPT_KERNEL_NONE = 0, SIM3OPT_KERNEL_HUBER = 1, SIM3OPT_KERNEL_PSEUDO_HUBER = 2,
+       SIM3OPT_KERNEL_CAUCHY = 3, SIM3OPT_KERNEL_GEMAN_MCCLURE = 4, SIM3OPT_KERNEL_WELSCH = 5,
+       SIM3OPT_KERNEL_FAIR = 6, SIM3OPT_KERNEL_TUKEY = 7, SIM3OPT_KERNEL_SATURATED = 8,
+       SIM3OPT_KERNEL_DCS = 9 };
 
 /* Solver configuration.  Replaces the reference's
  *   OptimizationAlgorithmLevenberg(BlockSolverX(LinearSolverEigen))   kitti_surf.cpp:552-558
@@ -212,6 +230,18 @@ int sim3opt_add_edges(sim3opt_graph* g, int32_t m, const int32_t* id_v0, const i
                       const double* meas /*m x 8*/, const double* info /*NULL or m x 49*/,
                       int32_t kernel, double kernel_delta);
 
+/* e->setRobustKernel(rk) for n edges (edge insertion indices; NULL = 0..n-1); before or after initialize;
+ * later entries win; validated as a whole before anything changes (SIM3OPT_ERR_ARG: unknown kind, delta not
+ * finite and > 0 for a kind other than NONE, index outside 0..m-1).  After initialize the next chi2 /
+ * linearize / optimize uses the new kernels; the graph does not need sim3opt_initialize again.
+ * Partitioned runs: every rank makes the same call, as with add_edges. */
+int sim3opt_set_edge_kernels(sim3opt_graph* g, int32_t n, const int32_t* edges, const int32_t* kinds,
+                             const double* deltas);
+/* kind and delta of every edge (NONE edges: delta 0); NULL outputs skipped */
+int sim3opt_get_edge_kernels(const sim3opt_graph* g, int32_t* kinds /*m*/, double* deltas /*m*/);
+/* the kernel formulas above on the host, no GPU needed: rho[0] = rho(e2), rho[1] = rho'(e2) (e2 >= 0) */
+int sim3opt_robustify(int32_t kind, double delta, double e2, double rho[2]);
+
 int32_t sim3opt_num_vertices(const sim3opt_graph* g);
 int32_t sim3opt_num_edges(const sim3opt_graph* g);
 /* edges()[k]: endpoint ids and measurement of the k-th edge added   (g2o OptimizableGraph::edges) */
@@ -248,6 +278,9 @@ int sim3opt_get_comm_times(sim3opt_graph* g, sim3opt_comm_times* out);
 /* ---- kernel-level access (parity tests against the CPU oracle, bench roofline) ---- */
 /* per-edge residuals e (m x 7), edge insertion order                EdgeSim3::computeError */
 int sim3opt_edge_errors(sim3opt_graph* g, double* e_out);
+/* e->chi2() (e^T Omega e) of every edge, and rho / rho' of its kernel at the current estimates, edge insertion
+ * order (NULL outputs skipped); partitioned runs: every rank gets every edge            Edge::chi2, robustify */
+int sim3opt_edge_chi2(sim3opt_graph* g, double* chi2 /*m*/, double* rho /*m*/, double* weight /*m*/);
 /* closed-form Jacobians (options.jacobians = 1) of every edge at the current estimates, edge insertion order:
  * e (m x 7) as sim3opt_edge_errors, J (m x 7 x 14, row-major per edge: J[98 k + 14 r + c]; columns 0..6 = de/dd0,
  * 7..13 = de/dd1 for the updates S <- exp(d) S; options.dof_mask zeroes frozen columns), evaluated on the

@@ -319,19 +319,69 @@ class G2oVertexScaleTrans : public Vertex {  // vio::G2oVertexScaleTrans (kitti_
   double st_[4] = {1, 0, 0, 0};
 };
 
+// g2o::RobustKernel and its robust_kernel_impl.cpp family: a kind (include/sim3opt.h lists rho and rho' of
+// each) and a delta, default 1 as in g2o.  The formulas run in the library: on the device inside chi2 and the
+// linearisation, on the host through robustify() (sim3opt_robustify).
+class RobustKernel {
+ public:
+  virtual ~RobustKernel() = default;
+  void setDelta(double delta) { delta_ = delta; }
+  double delta() const { return delta_; }
+  int kind() const { return kind_; }
+  // rho[0] = rho(e2), rho[1] = rho'(e2), rho[2] = 0 (first order only); anything with rho[i]
+  template <class V3> void robustify(double e2, V3& rho) const {
+    double r[2] = {0.0, 0.0};
+    sim3opt_robustify(kind_, delta_, e2, r);
+    rho[0] = r[0];
+    rho[1] = r[1];
+    rho[2] = 0.0;
+  }
+ protected:
+  explicit RobustKernel(int kind) : kind_(kind) {}
+ private:
+  int kind_;
+  double delta_ = 1.0;
+};
+#define SIM3OPT_SHIM_KERNEL(NAME, KIND) \
+  class NAME : public RobustKernel {   \
+   public:                             \
+    NAME() : RobustKernel(KIND) {}     \
+  };
+SIM3OPT_SHIM_KERNEL(RobustKernelHuber, SIM3OPT_KERNEL_HUBER)
+SIM3OPT_SHIM_KERNEL(RobustKernelPseudoHuber, SIM3OPT_KERNEL_PSEUDO_HUBER)
+SIM3OPT_SHIM_KERNEL(RobustKernelCauchy, SIM3OPT_KERNEL_CAUCHY)
+SIM3OPT_SHIM_KERNEL(RobustKernelGemanMcClure, SIM3OPT_KERNEL_GEMAN_MCCLURE)
+SIM3OPT_SHIM_KERNEL(RobustKernelWelsch, SIM3OPT_KERNEL_WELSCH)
+SIM3OPT_SHIM_KERNEL(RobustKernelFair, SIM3OPT_KERNEL_FAIR)
+SIM3OPT_SHIM_KERNEL(RobustKernelTukey, SIM3OPT_KERNEL_TUKEY)
+SIM3OPT_SHIM_KERNEL(RobustKernelSaturated, SIM3OPT_KERNEL_SATURATED)
+SIM3OPT_SHIM_KERNEL(RobustKernelDCS, SIM3OPT_KERNEL_DCS)
+#undef SIM3OPT_SHIM_KERNEL
+
 class Edge {  // binary edge, as far as the reference touches it
  public:
   virtual ~Edge() = default;
   void setVertex(int slot, Vertex* v) { v_[slot] = v; }
-  void setRobustKernelHuber(double delta) { kernel_ = SIM3OPT_KERNEL_HUBER; kdelta_ = delta; }
+  // takes ownership, as g2o's edge does (nullptr: no kernel).  On an edge already added the optimizer takes
+  // the new kernel at once: the next optimize / chi2 uses it, no initializeOptimization() needed.
+  inline void setRobustKernel(RobustKernel* k);
+  RobustKernel* robustKernel() const { return rk_.get(); }
+  void setRobustKernelHuber(double delta) {
+    RobustKernel* k = new RobustKernelHuber();
+    k->setDelta(delta);
+    setRobustKernel(k);
+  }
  protected:
   friend class SparseOptimizer;
   virtual GraphKind kind() const = 0;
   virtual void measurement(double m[8]) const = 0;
   virtual bool information77(double out[49]) const = 0;  // false: identity
+  int kernel() const { return rk_ ? rk_->kind() : SIM3OPT_KERNEL_NONE; }
+  double kernelDelta() const { return rk_ ? rk_->delta() : 0.0; }
   Vertex* v_[2] = {nullptr, nullptr};
-  int kernel_ = SIM3OPT_KERNEL_NONE;
-  double kdelta_ = 0.0;
+  std::unique_ptr<RobustKernel> rk_;
+  SparseOptimizer* owner_ = nullptr;  // set by addEdge, with the edge's insertion index
+  int32_t index_ = -1;
 };
 
 class EdgeSim3 : public Edge {  // vio::EdgeSim3 (kitti_surf.cpp:633-638, :663-668)
@@ -478,14 +528,19 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
     verts_[v->id_] = std::move(own);
     return true;
   }
-  bool addEdge(Edge* e) {
+  bool addEdge(Edge* e) {  // owns the edge, like g2o (kept: setRobustKernel may follow)
     std::unique_ptr<Edge> own(e);
     if (!e->v_[0] || !e->v_[1] || !claim(e->kind())) return false;
     double m[8], info[49];
     e->measurement(m);
     const bool has = e->information77(info);
-    return sim3opt_add_edge(g_, e->v_[0]->id(), e->v_[1]->id(), m, has ? info : nullptr, e->kernel_,
-                            e->kdelta_) == SIM3OPT_OK;
+    if (sim3opt_add_edge(g_, e->v_[0]->id(), e->v_[1]->id(), m, has ? info : nullptr, e->kernel(),
+                         e->kernelDelta()) != SIM3OPT_OK)
+      return false;
+    e->owner_ = this;
+    e->index_ = sim3opt_num_edges(g_) - 1;
+    edges_.push_back(std::move(own));
+    return true;
   }
   Vertex* vertex(int id) {
     auto it = verts_.find(id);
@@ -532,6 +587,7 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
 
  private:
   friend class Vertex;
+  friend class Edge;
   // the first vertex / edge decides what this optimizer optimises (kitti_surf.cpp:809-814)
   bool claim(GraphKind k) {
     if (kind_ == GraphKind::Unset) {
@@ -548,7 +604,16 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
   std::unique_ptr<OptimizationAlgorithmLevenberg> alg_;
   std::map<int, std::unique_ptr<Vertex>> verts_;
   std::vector<int> free_ids_;  // id of the vertex of each hessianIndex
+  std::vector<std::unique_ptr<Edge>> edges_;
 };
+
+inline void Edge::setRobustKernel(RobustKernel* k) {
+  rk_.reset(k);
+  if (!owner_) return;
+  const int32_t kind = kernel();
+  const double delta = kernelDelta();
+  sim3opt_set_edge_kernels(owner_->g_, 1, &index_, &kind, &delta);
+}
 
 inline void Vertex::push() {
   if (!owner_) return;
@@ -569,6 +634,16 @@ using sim3opt_shim::BlockSolverX;
 using sim3opt_shim::LinearSolverEigen;
 using sim3opt_shim::make_unique;
 using sim3opt_shim::OptimizationAlgorithmLevenberg;
+using sim3opt_shim::RobustKernel;
+using sim3opt_shim::RobustKernelCauchy;
+using sim3opt_shim::RobustKernelDCS;
+using sim3opt_shim::RobustKernelFair;
+using sim3opt_shim::RobustKernelGemanMcClure;
+using sim3opt_shim::RobustKernelHuber;
+using sim3opt_shim::RobustKernelPseudoHuber;
+using sim3opt_shim::RobustKernelSaturated;
+using sim3opt_shim::RobustKernelTukey;
+using sim3opt_shim::RobustKernelWelsch;
 using sim3opt_shim::Sim3;
 using sim3opt_shim::SparseBlockMatrix;
 using sim3opt_shim::SparseOptimizer;

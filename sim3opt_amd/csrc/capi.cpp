@@ -18,6 +18,7 @@
 #include "direct.hpp"
 #include "engine.hpp"
 #include "graph.hpp"
+#include "robust.hpp"
 #include "sim3_jac.hpp"
 
 using namespace sim3opt;
@@ -77,6 +78,20 @@ int sync_host_states(sim3opt_graph* g) {
   return engine_get_states(g->engine, g->host.states.data(), g->err);
 }
 
+// a kind / delta pair as sim3opt_add_edge and sim3opt_set_edge_kernels accept it
+bool kernel_ok(int32_t kind, double delta) {
+  if (kind < 0 || kind >= ROBUST_KINDS) return false;
+  return kind == SIM3OPT_KERNEL_NONE || (std::isfinite(delta) && delta > 0.0);
+}
+
+// first edge with a kernel: every earlier edge gets SIM3OPT_KERNEL_NONE
+void materialise_kernels(HostGraph& h) {
+  if (h.has_kernel) return;
+  h.has_kernel = true;
+  h.kdelta.assign(h.ev0.size(), 0.0);
+  h.kkind.assign(h.ev0.size(), (uint8_t)SIM3OPT_KERNEL_NONE);
+}
+
 int add_edge_impl(sim3opt_graph* g, int32_t id0, int32_t id1, const double* meas,
                   const double* info, int32_t kernel, double kdelta) {
   auto a = g->host.id2idx.find(id0), b = g->host.id2idx.find(id1);
@@ -84,10 +99,9 @@ int add_edge_impl(sim3opt_graph* g, int32_t id0, int32_t id1, const double* meas
     return fail(g, SIM3OPT_ERR_ARG, "add_edge: unknown vertex id");
   if (a->second == b->second) return fail(g, SIM3OPT_ERR_ARG, "add_edge: identical endpoints");
   if (!state_ok(meas)) return fail(g, SIM3OPT_ERR_ARG, "add_edge: non-finite measurement or scale <= 0");
-  if (kernel != SIM3OPT_KERNEL_NONE && kernel != SIM3OPT_KERNEL_HUBER)
-    return fail(g, SIM3OPT_ERR_ARG, "add_edge: unknown robust kernel");
-  if (kernel == SIM3OPT_KERNEL_HUBER && !(kdelta > 0.0))
-    return fail(g, SIM3OPT_ERR_ARG, "add_edge: Huber delta must be > 0");
+  if (kernel < 0 || kernel >= ROBUST_KINDS) return fail(g, SIM3OPT_ERR_ARG, "add_edge: unknown robust kernel");
+  if (!kernel_ok(kernel, kdelta))
+    return fail(g, SIM3OPT_ERR_ARG, "add_edge: robust kernel delta must be finite and > 0");
   HostGraph& h = g->host;
   const size_t m = h.ev0.size();
   const bool nonident = info && !is_identity77(info);
@@ -103,12 +117,12 @@ int add_edge_impl(sim3opt_graph* g, int32_t id0, int32_t id1, const double* meas
     if (info) std::memcpy(&h.info[off], info, sizeof(double) * 49);
     else for (int d = 0; d < 7; ++d) h.info[off + 8 * d] = 1.0;
   }
-  const bool has_k = kernel == SIM3OPT_KERNEL_HUBER;
-  if (has_k && !h.has_kernel) {
-    h.has_kernel = true;
-    h.kdelta.assign(m, 0.0);
+  const bool has_k = kernel != SIM3OPT_KERNEL_NONE;
+  if (has_k) materialise_kernels(h);
+  if (h.has_kernel) {
+    h.kdelta.push_back(has_k ? kdelta : 0.0);
+    h.kkind.push_back((uint8_t)kernel);
   }
-  if (h.has_kernel) h.kdelta.push_back(has_k ? kdelta : 0.0);
   h.ev0.push_back(a->second);
   h.ev1.push_back(b->second);
   h.meas.push_back(to_sim3(meas));
@@ -119,8 +133,9 @@ int add_edge_impl(sim3opt_graph* g, int32_t id0, int32_t id1, const double* meas
 
 extern "C" {
 
-// 1.1: multigrid preconditioner, hierarchy / BAL entry points; 1.2: closed-form Jacobians (options.jacobians)
-int sim3opt_version(void) { return 120; }
+// 1.1: multigrid preconditioner, hierarchy / BAL entry points; 1.2: closed-form Jacobians (options.jacobians);
+// 1.3: robust kernels beyond Huber, per edge and changeable after initialize
+int sim3opt_version(void) { return 130; }
 
 void sim3opt_options_default(sim3opt_options* o) {
   if (!o) return;
@@ -314,6 +329,52 @@ int sim3opt_add_edges(sim3opt_graph* g, int32_t m, const int32_t* id_v0, const i
   }
 }
 
+int sim3opt_set_edge_kernels(sim3opt_graph* g, int32_t n, const int32_t* edges, const int32_t* kinds,
+                             const double* deltas) {
+  try {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (n < 0 || (n > 0 && (!kinds || !deltas))) return fail(g, SIM3OPT_ERR_ARG, "set_edge_kernels: bad argument");
+  HostGraph& h = g->host;
+  const int32_t m = h.ne();
+  bool any = false;
+  for (int32_t i = 0; i < n; ++i) {  // the whole call is checked before anything changes
+    const int32_t k = edges ? edges[i] : i;
+    if (k < 0 || k >= m) return fail(g, SIM3OPT_ERR_ARG, "set_edge_kernels: edge index out of range");
+    if (!kernel_ok(kinds[i], deltas[i]))
+      return fail(g, SIM3OPT_ERR_ARG, "set_edge_kernels: unknown kind, or delta not finite and > 0");
+    any = any || kinds[i] != SIM3OPT_KERNEL_NONE;
+  }
+  if (!any && !h.has_kernel) return SIM3OPT_OK;  // NONE on a kernel-free graph: nothing changes
+  materialise_kernels(h);
+  for (int32_t i = 0; i < n; ++i) {  // (later entries win)
+    const int32_t k = edges ? edges[i] : i;
+    h.kkind[k] = (uint8_t)kinds[i];
+    h.kdelta[k] = kinds[i] == SIM3OPT_KERNEL_NONE ? 0.0 : deltas[i];
+  }
+  // an initialised graph takes the new kernels at once; a changed one gets them at its next initialize
+  if (g->initialized && !g->dirty) return engine_set_kernels(g->engine, h, g->err);
+  return SIM3OPT_OK;
+  } catch (...) {  // (std::bad_alloc, std::length_error ...: nothing crosses the C boundary)
+    return fail(g, SIM3OPT_ERR_ARG, "set_edge_kernels: out of host memory or internal error");
+  }
+}
+
+int sim3opt_get_edge_kernels(const sim3opt_graph* g, int32_t* kinds, double* deltas) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  const HostGraph& h = g->host;
+  for (int32_t k = 0; k < h.ne(); ++k) {
+    if (kinds) kinds[k] = h.has_kernel ? (int32_t)h.kkind[k] : SIM3OPT_KERNEL_NONE;
+    if (deltas) deltas[k] = h.has_kernel ? h.kdelta[k] : 0.0;
+  }
+  return SIM3OPT_OK;
+}
+
+int sim3opt_robustify(int32_t kind, double delta, double e2, double rho[2]) {
+  if (!rho || !kernel_ok(kind, delta) || !(e2 >= 0.0)) return SIM3OPT_ERR_ARG;
+  robustify(kind, delta, e2, rho[0], rho[1]);
+  return SIM3OPT_OK;
+}
+
 int32_t sim3opt_num_vertices(const sim3opt_graph* g) { return g ? g->host.nv() : 0; }
 int32_t sim3opt_num_edges(const sim3opt_graph* g) { return g ? g->host.ne() : 0; }
 
@@ -467,6 +528,12 @@ int sim3opt_edge_errors(sim3opt_graph* g, double* e_out) {
   if (!g || !e_out) return fail(g, SIM3OPT_ERR_ARG, "edge_errors: null argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "edge_errors: call sim3opt_initialize first");
   return engine_edge_errors(g->engine, e_out, g->err);
+}
+
+int sim3opt_edge_chi2(sim3opt_graph* g, double* chi2, double* rho, double* weight) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "edge_chi2: call sim3opt_initialize first");
+  return engine_edge_chi2(g->engine, chi2, rho, weight, g->err);
 }
 
 int sim3opt_edge_jacobians(sim3opt_graph* g, double* e_out, double* J_out) {

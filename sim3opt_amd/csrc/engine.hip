@@ -1,6 +1,7 @@
 // engine.hip -- initialisation, linearisation, chi2 and the LM trial loop (g2o: SparseOptimizer::optimize ->
 // OptimizationAlgorithmLevenberg::solve, kitti_surf.cpp:674-675); the C++ interface capi.cpp calls
 #include "engine_impl.hpp"
+#include "robust.hpp"
 #include "sim3_jac.hpp"
 
 namespace sim3opt {
@@ -9,7 +10,7 @@ namespace sim3opt {
 
 EdgeArgs Engine::edge_args() const {
   return EdgeArgs{e_lo, e_hi, d_ev0, d_ev1, d_meas, has_info ? d_info : nullptr,
-                  has_kernel ? d_kdelta : nullptr, d_states, mopts()};
+                  has_kernel ? d_kdelta : nullptr, has_kernel ? d_kkind : nullptr, d_states, mopts()};
 }
 
 void Engine::release() {
@@ -29,7 +30,7 @@ void Engine::release_under_device() {
   // cached blocks are handed out again without the device-wide wait a hipFree implies
   if (stream) (void)hipStreamSynchronize(stream);
   void* ptrs[] = {d_states, d_backup, d_meas, d_ev0, d_ev1, d_hidx, d_active, d_info, d_kdelta,
-                  d_rowptr, d_colidx, d_incptr, d_wrow, d_slot01, d_slot10, d_inc0, d_inc1,
+                  d_kkind, d_rowptr, d_colidx, d_incptr, d_wrow, d_slot01, d_slot10, d_inc0, d_inc1,
                   d_b, d_Minv, d_x, d_r, d_z, d_p, d_q, d_s, d_part_a, d_part_b, d_sc,
                   d_sub_first, d_sub_cnt, d_Gm, d_ptab};
   for (void* p : ptrs)
@@ -132,6 +133,7 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
   HIPCHK(upload(staged, stream, d_active, l_active));
   if (has_info) HIPCHK(upload(staged, stream, d_info, g.info));
   if (has_kernel) HIPCHK(upload(staged, stream, d_kdelta, g.kdelta));
+  if (has_kernel) HIPCHK(upload(staged, stream, d_kkind, g.kkind));
   HIPCHK(upload(staged, stream, d_rowptr, s.rowptr));
   HIPCHK(upload(staged, stream, d_colidx, s.colidx));
   HIPCHK(upload(staged, stream, d_incptr, s.incptr));
@@ -309,7 +311,8 @@ int Engine::pool_drain(std::string& err) {
 // same launch as chi2's
 int Engine::chi2(double* out, std::string& err, hipEvent_t before_fetch, int scale_parts) {
   const int g = grid_for(e_hi - e_lo, WG);
-  hipLaunchKernelGGL(k_chi2, dim3(g), dim3(WG), 0, stream, edge_args(), d_part_a);
+  if (has_kernel) hipLaunchKernelGGL(k_chi2<true>, dim3(g), dim3(WG), 0, stream, edge_args(), d_part_a);
+  else hipLaunchKernelGGL(k_chi2<false>, dim3(g), dim3(WG), 0, stream, edge_args(), d_part_a);
   // (exact solver on one GPU: small systems, where the copy of the scalar block is a visible share of a trial)
   const bool mirror = scale_parts > 0 && use_direct && !comm.active() && !opt.time_kernels;
   if (scale_parts > 0)
@@ -371,7 +374,7 @@ int Engine::linearize(std::string& err) {
     ptab_delta = opt.fd_delta;
     ptab_opts = mo;
   }
-  LinArgs A{n_active, d_active, d_ev0, d_ev1, d_meas, d_info, d_kdelta, d_states,
+  LinArgs A{n_active, d_active, d_ev0, d_ev1, d_meas, d_info, d_kdelta, d_kkind, d_states,
             d_slot01, d_slot10, d_inc0, d_inc1, d_vals, d_scratch, opt.fd_delta, mo,
             (const Sim3*)d_ptab, opt.dof_mask, d_sc};
   const int g = (n_active + EPB - 1) / EPB;
@@ -673,6 +676,47 @@ int engine_edge_errors(Engine* e, double* out, std::string& err) {
     err = std::string("edge_errors: ") + hipGetErrorString(le);
     return SIM3OPT_ERR_HIP;
   }
+  return SIM3OPT_OK;
+}
+
+int engine_edge_chi2(Engine* e, double* chi2, double* rho, double* weight, std::string& err) {
+  const size_t m = (size_t)e->ne;
+  double* d_out = nullptr;
+  HIPCHK(dev_malloc((void**)&d_out, sizeof(double) * 3 * std::max<size_t>(m, 1)));
+  EdgeArgs ea = e->edge_args();  // (replicated states: every rank evaluates every edge)
+  ea.e_lo = 0;
+  ea.e_hi = e->ne;
+  hipLaunchKernelGGL(k_edge_chi2, dim3(grid_for(e->ne, WG)), dim3(WG), 0, e->stream, ea,
+                     chi2 ? d_out : nullptr, rho ? d_out + m : nullptr, weight ? d_out + 2 * m : nullptr);
+  hipError_t le = hipGetLastError();
+  if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+  if (le == hipSuccess && chi2) le = hipMemcpy(chi2, d_out, sizeof(double) * m, hipMemcpyDeviceToHost);
+  if (le == hipSuccess && rho) le = hipMemcpy(rho, d_out + m, sizeof(double) * m, hipMemcpyDeviceToHost);
+  if (le == hipSuccess && weight) le = hipMemcpy(weight, d_out + 2 * m, sizeof(double) * m, hipMemcpyDeviceToHost);
+  dev_free(d_out);
+  if (le != hipSuccess) {
+    err = std::string("edge_chi2: ") + hipGetErrorString(le);
+    return SIM3OPT_ERR_HIP;
+  }
+  return SIM3OPT_OK;
+}
+
+int engine_set_kernels(Engine* e, const HostGraph& g, std::string& err) {
+  const size_t m = (size_t)e->ne;
+  if (g.kdelta.size() != m || g.kkind.size() != m) {
+    err = "set_edge_kernels: host arrays out of step with the engine";
+    return SIM3OPT_ERR_STATE;
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));  // (a launch in flight may still read the old arrays)
+  if (!e->d_kdelta) HIPCHK(dev_malloc((void**)&e->d_kdelta, sizeof(double) * std::max<size_t>(m, 1)));
+  if (!e->d_kkind) HIPCHK(dev_malloc((void**)&e->d_kkind, sizeof(uint8_t) * std::max<size_t>(m, 1)));
+  if (m) {
+    HIPCHK(hipMemcpy(e->d_kdelta, g.kdelta.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_kkind, g.kkind.data(), sizeof(uint8_t) * m, hipMemcpyHostToDevice));
+  }
+  e->has_kernel = true;
+  e->linearized = false;  // the next chi2 / linearize / optimize sees the new kernels
+  e->chi_known = false;
   return SIM3OPT_OK;
 }
 

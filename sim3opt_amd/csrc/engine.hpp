@@ -32,6 +32,10 @@ int engine_chi2(Engine* e, double* chi2, std::string& err);
 int engine_get_states(Engine* e, sim3::Sim3* out, std::string& err);
 int engine_set_states(Engine* e, const sim3::Sim3* in, std::string& err);
 int engine_edge_errors(Engine* e, double* out, std::string& err);
+// g2o Edge::chi2() (e^T Omega e), rho and rho' of each edge's kernel, all edges in insertion order (null: skipped)
+int engine_edge_chi2(Engine* e, double* chi2, double* rho, double* weight, std::string& err);
+// uploads g.kdelta / g.kkind (allocated on first use); the next chi2 / linearisation uses them
+int engine_set_kernels(Engine* e, const HostGraph& g, std::string& err);
 int engine_edge_jacobians(Engine* e, double* e_out, double* J_out, std::string& err);
 int engine_linearize(Engine* e, std::string& err);
 int engine_get_system(Engine* e, int32_t* rowptr, int32_t* colidx, double* values, double* b,

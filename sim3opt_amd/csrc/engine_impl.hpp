@@ -132,6 +132,7 @@ class Engine {
   Sim3 *d_states = nullptr, *d_backup = nullptr, *d_meas = nullptr;
   int32_t *d_ev0 = nullptr, *d_ev1 = nullptr, *d_hidx = nullptr, *d_active = nullptr;
   double *d_info = nullptr, *d_kdelta = nullptr;
+  uint8_t* d_kkind = nullptr;  // per-edge SIM3OPT_KERNEL_*, allocated with d_kdelta
   // system
   int32_t *d_rowptr = nullptr, *d_colidx = nullptr, *d_incptr = nullptr, *d_wrow = nullptr;
   int span_grid = 0;  // workgroups of the span SpMV

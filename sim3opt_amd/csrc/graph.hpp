@@ -28,7 +28,8 @@ struct HostGraph {
   bool has_info = false;       // some edge carries a non-identity information matrix
   bool has_kernel = false;     // some edge carries a robust kernel
   std::vector<double> info;    // m x 49 once has_info, else empty
-  std::vector<double> kdelta;  // m once has_kernel (0 = none, >0 = Huber delta), else empty
+  std::vector<double> kdelta;  // m once has_kernel: the kernel's delta (0 for SIM3OPT_KERNEL_NONE), else empty
+  std::vector<uint8_t> kkind;  // m once has_kernel: SIM3OPT_KERNEL_* of the edge (robust.hpp), else empty
 
   int32_t nv() const { return (int32_t)vid.size(); }
   int32_t ne() const { return (int32_t)ev0.size(); }

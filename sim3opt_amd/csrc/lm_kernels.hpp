@@ -73,20 +73,6 @@ __device__ __forceinline__ double quad_form(const double e[7], const double* __r
   return acc;
 }
 
-// g2o RobustKernelHuber: rho(e2) and rho'(e2)
-__device__ __forceinline__ void huber(double e2, double delta, double& rho, double& w) {
-  const double dsqr = delta * delta;
-  if (e2 <= dsqr) {
-    rho = e2;
-    w = 1.0;
-  } else {
-    const double sq = sqrt(e2);
-    rho = 2 * sq * delta - dsqr;
-    w = delta / sq;
-  }
-}
-
-
 struct EdgeArgs {
   int32_t e_lo, e_hi;  // edge range evaluated by this launch (rank's share in multi-GPU chi2)
   const int32_t* ev0;
@@ -94,11 +80,15 @@ struct EdgeArgs {
   const Sim3* meas;
   const double* info;    // nullptr: identity
   const double* kdelta;  // nullptr: no robust kernel
+  const uint8_t* kkind;  // per edge SIM3OPT_KERNEL_* (robust.hpp); set together with kdelta
   const Sim3* states;
   sim3::Opts opts;
 };
 
 // computeActiveErrors + activeRobustChi2: one lane per edge, block partials in fixed order.
+// (HAS_KERNEL: the edge's robust kernel, robustify(); the kinds of one wavefront may diverge -- a few FP64
+// operations next to edge_error)
+template <bool HAS_KERNEL>
 __global__ __launch_bounds__(WG) void k_chi2(EdgeArgs A, double* __restrict__ partials) {
   __shared__ double sh[4];
   double acc = 0.0;
@@ -116,15 +106,41 @@ __global__ __launch_bounds__(WG) void k_chi2(EdgeArgs A, double* __restrict__ pa
 #pragma unroll
       for (int r = 0; r < 7; ++r) chi += e[r] * e[r];
     }
-    if (A.kdelta && A.kdelta[k] > 0.0) {
+    if (HAS_KERNEL) {
       double rho, w;
-      huber(chi, A.kdelta[k], rho, w);
+      robustify(A.kkind[k], A.kdelta[k], chi, rho, w);
       chi = rho;
     }
     acc += chi;
   }
   const double s = block_sum(acc, sh);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// e->chi2() (e^T Omega e, g2o's Edge::chi2), rho and rho' of its kernel for the edges [e_lo, e_hi): one lane per
+// edge, the arithmetic of k_chi2; an output may be null
+__global__ __launch_bounds__(WG) void k_edge_chi2(EdgeArgs A, double* __restrict__ chi_out,
+                                                  double* __restrict__ rho_out, double* __restrict__ w_out) {
+  for (int k = A.e_lo + blockIdx.x * WG + threadIdx.x; k < A.e_hi; k += gridDim.x * WG) {
+    const Sim3 C = load_sim3(A.meas + k);
+    const Sim3 S0 = load_sim3(A.states + A.ev0[k]);
+    const Sim3 S1 = load_sim3(A.states + A.ev1[k]);
+    double e[7];
+    sim3::edge_error(C, S0, S1, A.opts, e);
+    double chi;
+    if (A.info) {
+      chi = quad_form(e, A.info + (size_t)49 * k);
+    } else {
+      chi = 0.0;
+#pragma unroll
+      for (int r = 0; r < 7; ++r) chi += e[r] * e[r];
+    }
+    double rho = chi, w = 1.0;
+    if (A.kkind) robustify(A.kkind[k], A.kdelta[k], chi, rho, w);
+    if (chi_out) chi_out[k] = chi;
+    if (rho_out) rho_out[k] = rho;
+    if (w_out) w_out[k] = w;
+  }
 }
 
 __global__ __launch_bounds__(WG) void k_edge_errors(EdgeArgs A, double* __restrict__ out) {
@@ -157,6 +173,7 @@ struct LinArgs {
   const Sim3* meas;
   const double* info;
   const double* kdelta;
+  const uint8_t* kkind;
   const Sim3* states;
   const int32_t* slot01;
   const int32_t* slot10;
@@ -194,7 +211,8 @@ __global__ __launch_bounds__(64) void k_perturbation_table(double delta, sim3::O
 }
 
 // The Gram phase of both linearisation kernels, entered after the Jacobian columns (J[0..13]) and e (J[14]) of
-// this half-wavefront's edge are in LDS: Omega (J | e), the Huber weight, the 119 Gram tasks, the plain stores.
+// this half-wavefront's edge are in LDS: Omega (J | e), the robust weight w = rho'(e^T Omega e) (uniform over the
+// half-wavefront), the 119 Gram tasks, the plain stores.
 // (Every thread of the workgroup calls it: it holds the workgroup barriers.)
 template <bool HAS_INFO, bool HAS_KERNEL>
 __device__ __forceinline__ void linearize_gram_store(const LinArgs& A, int edge, bool valid, int l,
@@ -216,11 +234,11 @@ __device__ __forceinline__ void linearize_gram_store(const LinArgs& A, int edge,
   double (*OJ)[7] = HAS_INFO ? O : J;
   double w = 1.0;
   if (HAS_KERNEL) {
-    if (valid && A.kdelta[edge] > 0.0) {
+    if (valid) {
       double chi = 0.0, rho;
 #pragma unroll
       for (int r = 0; r < 7; ++r) chi += J[14][r] * OJ[14][r];
-      huber(chi, A.kdelta[edge], rho, w);
+      robustify(A.kkind[edge], A.kdelta[edge], chi, rho, w);
     }
   }
   if (valid) {

@@ -17,7 +17,11 @@ LIB_PATH = os.environ.get("SIM3OPT_LIB") or os.path.join(_HERE, "libsim3opt.so")
 # environment variable redirects the dlopen)
 
 OK, ERR_ARG, ERR_STATE, ERR_NO_DEVICE, ERR_HIP, ERR_IO, ERR_COMM = 0, -1, -2, -3, -4, -5, -6
-KERNEL_NONE, KERNEL_HUBER = 0, 1
+# robust kernels of an edge (include/sim3opt.h lists rho and rho' of each)
+(KERNEL_NONE, KERNEL_HUBER, KERNEL_PSEUDO_HUBER, KERNEL_CAUCHY, KERNEL_GEMAN_MCCLURE, KERNEL_WELSCH, KERNEL_FAIR,
+ KERNEL_TUKEY, KERNEL_SATURATED, KERNEL_DCS) = range(10)
+KERNEL_NAMES = ("none", "huber", "pseudo_huber", "cauchy", "geman_mcclure", "welsch", "fair", "tukey", "saturated",
+                "dcs")
 
 
 class Options(C.Structure):
@@ -134,6 +138,10 @@ SYMBOLS = {
     "sim3opt_add_vertices": (C.c_int, [_vp, C.c_int32, _ip, _dp, _up]),
     "sim3opt_add_edge": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_double]),
     "sim3opt_add_edges": (C.c_int, [_vp, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.c_double]),
+    "sim3opt_set_edge_kernels": (C.c_int, [_vp, C.c_int32, _ip, _ip, _dp]),
+    "sim3opt_get_edge_kernels": (C.c_int, [_vp, _ip, _dp]),
+    "sim3opt_robustify": (C.c_int, [C.c_int32, C.c_double, C.c_double, _dp]),
+    "sim3opt_edge_chi2": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sim3opt_num_vertices": (C.c_int32, [_vp]),
     "sim3opt_num_edges": (C.c_int32, [_vp]),
     "sim3opt_get_edge": (C.c_int, [_vp, C.c_int32, _ip, _ip, _dp]),
@@ -368,14 +376,46 @@ class Graph:
                                            int(kernel), float(kernel_delta)))
 
     def add_edges(self, v0, v1, meas, info=None, kernel=KERNEL_NONE, kernel_delta=0.0):
+        """kernel / kernel_delta: one kind and delta for every edge, or per-edge arrays of length m."""
         a, b = _i32(v0), _i32(v1)
         m = _f64(meas).reshape(-1, 8)
         inf = None
         if info is not None:  # (m, 7, 7) [k, r, c] -> column-major blocks
             inf = _f64(np.asarray(info).reshape(-1, 7, 7).transpose(0, 2, 1)).reshape(-1, 49)
+        per_edge = np.ndim(kernel) > 0 or np.ndim(kernel_delta) > 0
+        if per_edge:  # checked before the edges go in, then set on them as set_edge_kernels sets them
+            kinds = _i32(np.broadcast_to(kernel, a.shape))
+            deltas = _f64(np.broadcast_to(kernel_delta, a.shape))
+            bad = (kinds < 0) | (kinds >= len(KERNEL_NAMES)) | (
+                (kinds != KERNEL_NONE) & ~(np.isfinite(deltas) & (deltas > 0)))
+            if bad.any():
+                raise Sim3OptError(ERR_ARG, f"add_edges: bad robust kernel or delta at edge {int(np.argmax(bad))}")
+        m0 = self.num_edges
         self._chk(self._L.sim3opt_add_edges(self._g, a.shape[0], _p(a, _ip), _p(b, _ip),
-                                            _p(m, _dp), _p(inf, _dp), int(kernel),
-                                            float(kernel_delta)))
+                                            _p(m, _dp), _p(inf, _dp), KERNEL_NONE if per_edge else int(kernel),
+                                            0.0 if per_edge else float(kernel_delta)))
+        if per_edge:
+            self.set_edge_kernels(np.arange(m0, m0 + a.shape[0]), kinds, deltas)
+
+    def set_edge_kernels(self, edges, kinds, deltas):
+        """e->setRobustKernel for the edges listed (insertion indices; None = 0..n-1), before or after
+        initialize; kinds / deltas: scalars or arrays of the same length.  Bad input changes nothing."""
+        if edges is None:
+            n = max(np.size(kinds), np.size(deltas))
+            e = None
+        else:
+            e = _i32(np.atleast_1d(edges))
+            n = e.shape[0]
+        k = _i32(np.broadcast_to(kinds, (n,)))
+        d = _f64(np.broadcast_to(deltas, (n,)))
+        self._chk(self._L.sim3opt_set_edge_kernels(self._g, n, _p(e, _ip), _p(k, _ip), _p(d, _dp)))
+
+    def edge_kernels(self):
+        """(kinds int32 (m,), deltas (m,)) of every edge."""
+        m = self.num_edges
+        k, d = np.empty(m, np.int32), np.empty(m)
+        self._chk(self._L.sim3opt_get_edge_kernels(self._g, _p(k, _ip), _p(d, _dp)))
+        return k, d
 
     @property
     def num_vertices(self):
@@ -508,6 +548,14 @@ class Graph:
         e = np.empty((self.num_edges, 7))
         self._chk(self._L.sim3opt_edge_errors(self._g, _p(e, _dp)))
         return e
+
+    def edge_chi2(self):
+        """(chi2, rho, weight), each (m,): e^T Omega e of every edge (g2o Edge::chi2) and rho / rho' of its
+        robust kernel at the current estimates; rho sums to chi2()."""
+        m = self.num_edges
+        c, r, w = np.empty(m), np.empty(m), np.empty(m)
+        self._chk(self._L.sim3opt_edge_chi2(self._g, _p(c, _dp), _p(r, _dp), _p(w, _dp)))
+        return c, r, w
 
     def edge_jacobians(self):
         """Closed-form Jacobians of every edge at the current estimates (needs fix_small_angle_b=1):
@@ -718,6 +766,15 @@ class Graph:
     def write_poses(self, path, image_ids=None):
         ids = None if image_ids is None else _i32(image_ids)
         self._chk(self._L.sim3opt_write_poses(self._g, os.fsencode(path), _p(ids, _ip)))
+
+
+def robustify(kind, delta, e2):
+    """sim3opt_robustify: (rho(e2), rho'(e2)) of a robust kernel, on the host."""
+    out = np.empty(2)
+    rc = load().sim3opt_robustify(int(kind), float(delta), float(e2), _p(out, _dp))
+    if rc != OK:
+        raise Sim3OptError(rc, "robustify: unknown kind, delta not finite and > 0, or e2 < 0")
+    return float(out[0]), float(out[1])
 
 
 def edge_jacobian_host(meas, s0, s1, **opts):
