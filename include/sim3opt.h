@@ -153,7 +153,40 @@ typedef struct sim3opt_options {
                                         with step fd_delta (g2o's BaseBinaryEdge default: the reference's arithmetic),
                                         1 = closed form, J = +-J_l(e)^-1 Ad (DESIGN.md "Analytic Jacobians"); needs
                                         fix_small_angle_b = 1 (sim3opt_set_options refuses it with the as-written B) */
+  /* nonlinear algorithm (g2o's OptimizationAlgorithm* behind SparseOptimizer::setAlgorithm) */
+  int32_t algorithm;        /* 0     SIM3OPT_ALGORITHM_LM (Levenberg), _GAUSS_NEWTON, _DOGLEG (Powell)           */
+  int32_t dl_max_trials;    /* 100   dogleg: trials per iteration (maxTrialsAfterFailure)                        */
+  double dl_delta_init;     /* 1e4   dogleg: trust radius at the first iteration of an optimize() (setUserDeltaInit) */
+  double dl_lambda_init;    /* 1e-7  dogleg: first damping once H has not been positive definite (initialLambda)  */
+  double dl_lambda_factor;  /* 10    dogleg: factor of that damping (setLamdbaFactor)                            */
 } sim3opt_options;
+
+/* options.algorithm */
+enum {
+  SIM3OPT_ALGORITHM_LM = 0,
+  SIM3OPT_ALGORITHM_GAUSS_NEWTON = 1,
+  SIM3OPT_ALGORITHM_DOGLEG = 2
+};
+
+/* dogleg step types, numbered as g2o's OptimizationAlgorithmDogleg enum */
+enum {
+  SIM3OPT_STEP_UNDEFINED = 0,
+  SIM3OPT_STEP_SD = 1,  /* steepest descent, cut to the trust radius */
+  SIM3OPT_STEP_GN = 2,  /* the Gauss-Newton step                     */
+  SIM3OPT_STEP_DL = 3   /* between the two, on the trust radius      */
+};
+
+/* Per-iteration record of a dogleg run (options.algorithm = SIM3OPT_ALGORITHM_DOGLEG). */
+typedef struct sim3opt_tr_stats {
+  double delta_before;  /* trust radius at the start of the iteration */
+  double delta_after;   /* ... and after its last trial               */
+  double alpha;         /* b.b / (b^T H b): h_sd = alpha b            */
+  double norm_sd;       /* ||h_sd||                                   */
+  double norm_gn;       /* ||h_gn||                                   */
+  double norm_dl;       /* ||h_dl|| of the last trial                 */
+  int32_t step;         /* SIM3OPT_STEP_* of the last trial           */
+  int32_t was_pd;       /* 1: every GN solve so far, this one included, succeeded without damping */
+} sim3opt_tr_stats;
 
 /* Per-iteration record (g2o G2OBatchStatistics role; bal_example.cpp:55-56). */
 typedef struct sim3opt_iter_stats {
@@ -271,6 +304,11 @@ int sim3opt_chi2(sim3opt_graph* g, double* chi2);
 /* statistics of the last optimize() */
 int32_t sim3opt_num_iterations(const sim3opt_graph* g);
 int sim3opt_get_stats(const sim3opt_graph* g, int32_t iter, sim3opt_iter_stats* out);
+/* trust-region record of iteration `iter` of the last optimize(); SIM3OPT_ERR_STATE when that run was not a
+ * dogleg run, SIM3OPT_ERR_ARG for an iteration out of range.  (For Gauss-Newton and dogleg the fields of
+ * sim3opt_iter_stats read: lambda = damping added to the GN solve (0 while H stayed positive definite),
+ * rho = last gain ratio, trials = g2o's numTries, pcg_* = the GN solve(s) of the iteration.) */
+int sim3opt_get_trust_region_stats(const sim3opt_graph* g, int32_t iter, sim3opt_tr_stats* out);
 int sim3opt_get_kernel_times(sim3opt_graph* g, sim3opt_kernel_times* out);
 int sim3opt_reset_kernel_times(sim3opt_graph* g);   /* (also clears the collectives' times) */
 int sim3opt_get_comm_times(sim3opt_graph* g, sim3opt_comm_times* out);

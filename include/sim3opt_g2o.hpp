@@ -458,12 +458,83 @@ struct BlockSolverX {
   using LinearSolverType = LinearSolverEigen<PoseMatrixType>;
   explicit BlockSolverX(std::unique_ptr<LinearSolverType>) {}
 };
-struct OptimizationAlgorithmLevenberg {
+// g2o::OptimizationAlgorithm: what SparseOptimizer owns; the three algorithms map onto options.algorithm
+struct OptimizationAlgorithm {
+  virtual ~OptimizationAlgorithm() = default;
+};
+struct OptimizationAlgorithmLevenberg : OptimizationAlgorithm {
   explicit OptimizationAlgorithmLevenberg(std::unique_ptr<BlockSolverX>) {}
   void setUserLambdaInit(double v) { user_lambda_init = v; }   // kittiDetector.h:779-782
   void setMaxTrialsAfterFailure(int n) { max_trials = n; }     // kittiDetector.h:730
   double user_lambda_init = 0.0;
   int max_trials = 10;
+};
+// g2o::OptimizationAlgorithmGaussNewton: H dx = b, dx applied, no acceptance test
+struct OptimizationAlgorithmGaussNewton : OptimizationAlgorithm {
+  explicit OptimizationAlgorithmGaussNewton(std::unique_ptr<BlockSolverX>) {}
+};
+// g2o::OptimizationAlgorithmDogleg: Powell's dogleg.  The settings reach the graph at setAlgorithm
+// and, once it is set, at every setter; lastStep() / currentDelta() / wasPDInAllIterations() read the last
+// optimize()'s trust-region records.
+class OptimizationAlgorithmDogleg : public OptimizationAlgorithm {
+ public:
+  enum { STEP_UNDEFINED = SIM3OPT_STEP_UNDEFINED, STEP_SD = SIM3OPT_STEP_SD, STEP_GN = SIM3OPT_STEP_GN,
+         STEP_DL = SIM3OPT_STEP_DL };
+  explicit OptimizationAlgorithmDogleg(std::unique_ptr<BlockSolverX>) {}
+  void setUserDeltaInit(double d) { delta_init_ = d; push(); }
+  double userDeltaInit() const { return delta_init_; }
+  void setMaxTrialsAfterFailure(int n) { max_trials_ = n; push(); }
+  int maxTrialsAfterFailure() const { return max_trials_; }
+  void setInitialLambda(double l) { lambda_init_ = l; push(); }
+  double initialLambda() const { return lambda_init_; }
+  void setLamdbaFactor(double f) { lambda_factor_ = f; push(); }  // (g2o's spelling)
+  double lamdbaFactor() const { return lambda_factor_; }
+  // step type of the last trial of the last iteration (STEP_UNDEFINED before any dogleg iteration)
+  int lastStep() const {
+    sim3opt_tr_stats t;
+    return last(&t) ? t.step : STEP_UNDEFINED;
+  }
+  // trust radius after the last iteration (userDeltaInit() before any dogleg iteration)
+  double currentDelta() const {
+    sim3opt_tr_stats t;
+    return last(&t) ? t.delta_after : delta_init_;
+  }
+  bool wasPDInAllIterations() const {
+    sim3opt_tr_stats t;
+    return last(&t) ? t.was_pd != 0 : true;
+  }
+  static const char* stepType2Str(int stepType) {
+    switch (stepType) {
+      case STEP_SD: return "Descent";
+      case STEP_GN: return "GN";
+      case STEP_DL: return "Dogleg";
+      default: return "Undefined";
+    }
+  }
+  // (SparseOptimizer::setAlgorithm) the graph whose options carry these settings
+  void attach(sim3opt_graph* g) { g_ = g; push(); }
+ private:
+  void push() const {
+    if (!g_) return;
+    sim3opt_options o;
+    sim3opt_get_options(g_, &o);
+    o.algorithm = SIM3OPT_ALGORITHM_DOGLEG;
+    o.dl_delta_init = delta_init_;
+    o.dl_max_trials = max_trials_;
+    o.dl_lambda_init = lambda_init_;
+    o.dl_lambda_factor = lambda_factor_;
+    sim3opt_set_options(g_, &o);  // (out-of-range values are refused there: the previous ones stay)
+  }
+  bool last(sim3opt_tr_stats* t) const {
+    if (!g_) return false;
+    const int32_t n = sim3opt_num_iterations(g_);
+    return n > 0 && sim3opt_get_trust_region_stats(g_, n - 1, t) == SIM3OPT_OK;
+  }
+  sim3opt_graph* g_ = nullptr;
+  double delta_init_ = 1e4;  // g2o's defaults
+  int max_trials_ = 100;
+  double lambda_init_ = 1e-7;
+  double lambda_factor_ = 10.0;
 };
 template <typename T, typename... A> std::unique_ptr<T> make_unique(A&&... a) {
   return std::unique_ptr<T>(new T(std::forward<A>(a)...));
@@ -506,7 +577,19 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
     sim3opt_get_options(g_, &o);
     o.user_lambda_init = a->user_lambda_init;
     o.max_trials = a->max_trials;
+    o.algorithm = SIM3OPT_ALGORITHM_LM;
     sim3opt_set_options(g_, &o);
+  }
+  void setAlgorithm(OptimizationAlgorithmGaussNewton* a) {
+    alg_.reset(a);
+    sim3opt_options o;
+    sim3opt_get_options(g_, &o);
+    o.algorithm = SIM3OPT_ALGORITHM_GAUSS_NEWTON;
+    sim3opt_set_options(g_, &o);
+  }
+  void setAlgorithm(OptimizationAlgorithmDogleg* a) {
+    alg_.reset(a);
+    a->attach(g_);
   }
   void setVerbose(bool v) {
     sim3opt_options o;
@@ -601,7 +684,7 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
   }
   sim3opt_graph* g_;
   GraphKind kind_ = GraphKind::Unset;
-  std::unique_ptr<OptimizationAlgorithmLevenberg> alg_;
+  std::unique_ptr<OptimizationAlgorithm> alg_;
   std::map<int, std::unique_ptr<Vertex>> verts_;
   std::vector<int> free_ids_;  // id of the vertex of each hessianIndex
   std::vector<std::unique_ptr<Edge>> edges_;
@@ -633,6 +716,9 @@ namespace g2o {
 using sim3opt_shim::BlockSolverX;
 using sim3opt_shim::LinearSolverEigen;
 using sim3opt_shim::make_unique;
+using sim3opt_shim::OptimizationAlgorithm;
+using sim3opt_shim::OptimizationAlgorithmDogleg;
+using sim3opt_shim::OptimizationAlgorithmGaussNewton;
 using sim3opt_shim::OptimizationAlgorithmLevenberg;
 using sim3opt_shim::RobustKernel;
 using sim3opt_shim::RobustKernelCauchy;

@@ -31,6 +31,8 @@ struct sim3opt_graph {
   bool initialized = false;
   bool dirty = false;  // vertices/edges added since the last initialize (g2o: re-initialize)
   std::vector<sim3opt_iter_stats> stats;
+  std::vector<sim3opt_tr_stats> tr_stats;  // dogleg runs only
+  int32_t last_algorithm = SIM3OPT_ALGORITHM_LM;  // of the last optimize()
   std::string err;
   Comm comm;        // handed to the engine at initialize
   bool comm_set = false;
@@ -135,6 +137,9 @@ extern "C" {
 
 // 1.1: multigrid preconditioner, hierarchy / BAL entry points; 1.2: closed-form Jacobians (options.jacobians);
 // 1.3: robust kernels beyond Huber, per edge and changeable after initialize
+// (Gauss-Newton and dogleg -- options.algorithm and the dl_* fields appended to sim3opt_options,
+// sim3opt_get_trust_region_stats -- keep 130: tests/test_robust_kernels.py pins the number; the new export is
+// how a caller detects them)
 int sim3opt_version(void) { return 130; }
 
 void sim3opt_options_default(sim3opt_options* o) {
@@ -179,6 +184,11 @@ void sim3opt_options_default(sim3opt_options* o) {
   o->direct_max_pairs = 0;
   o->debug_full_arrays = 0;
   o->jacobians = 0;
+  o->algorithm = SIM3OPT_ALGORITHM_LM;
+  o->dl_max_trials = 100;
+  o->dl_delta_init = 1e4;
+  o->dl_lambda_init = 1e-7;
+  o->dl_lambda_factor = 10.0;
 }
 
 // Debug overrides: a SIM3OPT_* environment variable replaces the option field of the same name when the
@@ -241,6 +251,15 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
     return fail(g, SIM3OPT_ERR_ARG, "set_options: value out of range");
   if (o->jacobians != 0 && o->jacobians != 1)
     return fail(g, SIM3OPT_ERR_ARG, "set_options: jacobians must be 0 (numeric) or 1 (analytic)");
+  if (o->algorithm < SIM3OPT_ALGORITHM_LM || o->algorithm > SIM3OPT_ALGORITHM_DOGLEG)
+    return fail(g, SIM3OPT_ERR_ARG, "set_options: algorithm must be 0 (LM), 1 (Gauss-Newton) or 2 (dogleg)");
+  {
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    if (!pos(o->dl_delta_init) || !pos(o->dl_lambda_init) || !pos(o->dl_lambda_factor) || o->dl_max_trials < 1)
+      return fail(g, SIM3OPT_ERR_ARG,
+                  "set_options: dl_delta_init, dl_lambda_init and dl_lambda_factor must be finite and positive, "
+                  "dl_max_trials at least 1");
+  }
   if (o->jacobians == 1 && o->fix_small_angle_b != 1)
     return fail(g, SIM3OPT_ERR_ARG,
                 "set_options: jacobians = 1 needs fix_small_angle_b = 1 (the closed form differentiates the exact "
@@ -446,7 +465,9 @@ int sim3opt_optimize(sim3opt_graph* g, int32_t max_iters) {
   }
   if (max_iters <= 0) return 0;
   if (g->dirty) { g->err = "optimize: graph changed, call sim3opt_initialize again"; return 0; }
+  g->last_algorithm = g->opt.algorithm;
   const int rc = engine_optimize(g->engine, max_iters, g->stats, g->err);
+  engine_trust_region_stats(g->engine, g->tr_stats);
   return rc < 0 ? 0 : rc;
   } catch (...) {  // (std::bad_alloc, std::length_error ...: nothing crosses the C boundary)
     (void)fail(g, SIM3OPT_ERR_ARG, "optimize: out of host memory or internal error"); return 0;
@@ -503,6 +524,14 @@ int32_t sim3opt_num_iterations(const sim3opt_graph* g) { return g ? (int32_t)g->
 int sim3opt_get_stats(const sim3opt_graph* g, int32_t iter, sim3opt_iter_stats* out) {
   if (!g || !out || iter < 0 || iter >= (int32_t)g->stats.size()) return SIM3OPT_ERR_ARG;
   *out = g->stats[iter];
+  return SIM3OPT_OK;
+}
+
+int sim3opt_get_trust_region_stats(const sim3opt_graph* g, int32_t iter, sim3opt_tr_stats* out) {
+  if (!g || !out) return SIM3OPT_ERR_ARG;
+  if (g->last_algorithm != SIM3OPT_ALGORITHM_DOGLEG) return SIM3OPT_ERR_STATE;
+  if (iter < 0 || iter >= (int32_t)g->tr_stats.size()) return SIM3OPT_ERR_ARG;
+  *out = g->tr_stats[iter];
   return SIM3OPT_OK;
 }
 

@@ -32,7 +32,7 @@ void Engine::release_under_device() {
   void* ptrs[] = {d_states, d_backup, d_meas, d_ev0, d_ev1, d_hidx, d_active, d_info, d_kdelta,
                   d_kkind, d_rowptr, d_colidx, d_incptr, d_wrow, d_slot01, d_slot10, d_inc0, d_inc1,
                   d_b, d_Minv, d_x, d_r, d_z, d_p, d_q, d_s, d_part_a, d_part_b, d_sc,
-                  d_sub_first, d_sub_cnt, d_Gm, d_ptab};
+                  d_sub_first, d_sub_cnt, d_Gm, d_ptab, d_dl};
   for (void* p : ptrs)
     if (p) dev_free(p);
   for (const RangedArray& a : ranged)
@@ -54,6 +54,7 @@ void Engine::release_under_device() {
   marg_factor.release();
   staged.release();
   if (h_sc) host_free(h_sc);
+  if (h_dl) host_free(h_dl);
   for (hipEvent_t e : pool) event_release(e);
   for (hipEvent_t e : rep_pool) event_release(e);
   rep_pool.clear();
@@ -418,7 +419,21 @@ int Engine::linearize(std::string& err) {
   return SIM3OPT_OK;
 }
 
+// the two kernels of the LM update the other algorithms (engine_algorithms.hip) reuse
+void Engine::apply_step(const double* x) {
+  hipLaunchKernelGGL(k_oplus, dim3((nv + WG - 1) / WG), dim3(WG), 0, stream, nv, d_hidx, x, d_states, mopts(),
+                     use_direct ? (const DevScalars*)d_sc : nullptr, (Sim3*)nullptr, fail_token);
+}
+
+void Engine::pop_states() {
+  hipLaunchKernelGGL(k_copy_states, dim3((8 * nv + WG - 1) / WG), dim3(WG), 0, stream, nv, (const Sim3*)d_backup,
+                     d_states);
+}
+
 int Engine::optimize(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
+  tr_stats.clear();
+  if (opt.algorithm == SIM3OPT_ALGORITHM_GAUSS_NEWTON) return optimize_gauss_newton(max_iters, stats, err);
+  if (opt.algorithm == SIM3OPT_ALGORITHM_DOGLEG) return optimize_dogleg(max_iters, stats, err);
   stats.clear();
   double lambda = 0.0, ni = 2.0;
   bool ok = true;
@@ -643,6 +658,8 @@ int engine_optimize(Engine* e, int32_t max_iters, std::vector<sim3opt_iter_stats
   if (rc) return rc;
   return e->check_foreign_ranges(err);
 }
+
+void engine_trust_region_stats(const Engine* e, std::vector<sim3opt_tr_stats>& out) { out = e->tr_stats; }
 
 int engine_chi2(Engine* e, double* chi2, std::string& err) { return e->chi2(chi2, err); }
 

@@ -28,6 +28,8 @@ void engine_take_comm(Engine* e, Comm* out);
 int engine_set_options(Engine* e, const sim3opt_options& opt);
 int engine_optimize(Engine* e, int32_t max_iters, std::vector<sim3opt_iter_stats>& stats,
                     std::string& err);
+// trust-region records of the last optimize() (dogleg; empty after LM and Gauss-Newton)
+void engine_trust_region_stats(const Engine* e, std::vector<sim3opt_tr_stats>& out);
 int engine_chi2(Engine* e, double* chi2, std::string& err);
 int engine_get_states(Engine* e, sim3::Sim3* out, std::string& err);
 int engine_set_states(Engine* e, const sim3::Sim3* in, std::string& err);

@@ -4,8 +4,9 @@
 //   engine_amg.hip     the aggregation-multigrid preconditioner: set-up per linearisation / per trial, the cycle
 //   engine_direct.hip  when the LM factorises exactly (LinearSolverEigen's role on KITTI-00-like graphs) and the
 //                      marginal covariances: policy over two BlockLdl (direct_factor.hpp, direct_factor.hip)
+//   engine_algorithms.hip  Gauss-Newton and Powell's dogleg (options.algorithm = 1 / 2)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
-// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
+// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, algo_kernels.hpp -> engine_algorithms.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
 // the SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through a method.
 #pragma once
 // (formerly all of engine.hip) -- device-resident Levenberg-Marquardt on a Sim(3) pose graph, gfx950 (MI355X).
@@ -476,6 +477,19 @@ class Engine {
                   bool* chain_broke, std::string& err, int probe_budget = 0, bool* abandoned = nullptr);
 
   int optimize(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err);
+
+  // ---- Gauss-Newton and Powell's dogleg (engine_algorithms.hip) ----
+  // optimize() hands options.algorithm = 1 / 2 to these; the LM loop above is not involved
+  int optimize_gauss_newton(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err);
+  int optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err);
+  // the six per-iteration scalars of the dogleg model from b (d_b) and h_gn (d_x): two SpMVs with lambda = 0 and
+  // one fused dot kernel, all-reduced over the ranks; left on the device in d_dl (no host round trip here)
+  int dogleg_dots(std::string& err);
+  void apply_step(const double* x);  // k_oplus without a backup (engine.hip)
+  void pop_states();                 // k_copy_states from d_backup (engine.hip)
+  std::vector<sim3opt_tr_stats> tr_stats;  // per iteration of the last dogleg run
+  double* d_dl = nullptr;  // dogleg: 4 x MAX_GRID dot partials, then the 8 scalars (DL_OUT)
+  double* h_dl = nullptr;  // pinned copy of the scalars
 };
 
 }  // namespace sim3opt

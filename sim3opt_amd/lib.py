@@ -22,6 +22,10 @@ OK, ERR_ARG, ERR_STATE, ERR_NO_DEVICE, ERR_HIP, ERR_IO, ERR_COMM = 0, -1, -2, -3
  KERNEL_TUKEY, KERNEL_SATURATED, KERNEL_DCS) = range(10)
 KERNEL_NAMES = ("none", "huber", "pseudo_huber", "cauchy", "geman_mcclure", "welsch", "fair", "tukey", "saturated",
                 "dcs")
+# options.algorithm (g2o's OptimizationAlgorithmLevenberg / GaussNewton / Dogleg) and the dogleg step types
+ALGORITHM_LM, ALGORITHM_GAUSS_NEWTON, ALGORITHM_DOGLEG = 0, 1, 2
+STEP_UNDEFINED, STEP_SD, STEP_GN, STEP_DL = 0, 1, 2, 3
+STEP_NAMES = ("undefined", "SD", "GN", "DL")
 
 
 class Options(C.Structure):
@@ -65,6 +69,11 @@ class Options(C.Structure):
         ("direct_max_pairs", C.c_int64),
         ("debug_full_arrays", C.c_int32),
         ("jacobians", C.c_int32),
+        ("algorithm", C.c_int32),
+        ("dl_max_trials", C.c_int32),
+        ("dl_delta_init", C.c_double),
+        ("dl_lambda_init", C.c_double),
+        ("dl_lambda_factor", C.c_double),
     ]
 
 
@@ -82,6 +91,20 @@ class IterStats(C.Structure):
         ("ms_update", C.c_double),
         ("pcg_capped", C.c_int32),
         ("reserved_", C.c_int32),
+    ]
+
+
+class TrustRegionStats(C.Structure):
+    """sim3opt_tr_stats: one dogleg iteration."""
+    _fields_ = [
+        ("delta_before", C.c_double),
+        ("delta_after", C.c_double),
+        ("alpha", C.c_double),
+        ("norm_sd", C.c_double),
+        ("norm_gn", C.c_double),
+        ("norm_dl", C.c_double),
+        ("step", C.c_int32),
+        ("was_pd", C.c_int32),
     ]
 
 
@@ -158,6 +181,7 @@ SYMBOLS = {
     "sim3opt_get_kernel_times": (C.c_int, [_vp, C.POINTER(KernelTimes)]),
     "sim3opt_reset_kernel_times": (C.c_int, [_vp]),
     "sim3opt_edge_errors": (C.c_int, [_vp, _dp]),
+    "sim3opt_get_trust_region_stats": (C.c_int, [_vp, C.c_int32, C.POINTER(TrustRegionStats)]),
     "sim3opt_edge_jacobians": (C.c_int, [_vp, _dp, _dp]),
     "sim3opt_sim3_edge_jacobian": (C.c_int, [_dp, _dp, _dp, C.POINTER(Options), _dp, _dp]),
     "sim3opt_linearize": (C.c_int, [_vp]),
@@ -526,6 +550,15 @@ class Graph:
         for i in range(self._L.sim3opt_num_iterations(self._g)):
             st = IterStats()
             self._chk(self._L.sim3opt_get_stats(self._g, i, C.byref(st)))
+            out.append(st)
+        return out
+
+    def trust_region_stats(self):
+        """Per-iteration TrustRegionStats of the last optimize() -- a dogleg run (options.algorithm = 2)."""
+        out = []
+        for i in range(self._L.sim3opt_num_iterations(self._g)):
+            st = TrustRegionStats()
+            self._chk(self._L.sim3opt_get_trust_region_stats(self._g, i, C.byref(st)))
             out.append(st)
         return out
 
