@@ -26,7 +26,7 @@
 //   k_ba_backsub  thread / point: dx_p = H_pp^-1 b_p - sum Z_o^T dx_c(cam(o))
 //   k_ba_update   exp-map update of the cameras, additive update of the points (backup kept)
 //   k_ba_chi2     thread / observation: robustified chi2, fixed-order block sums
-// The host runs g2o's lambda policy on three scalars per trial, as in engine.hip.
+// The host runs g2o's lambda policy on three scalars per trial: engine.hip's LmDamping (lm_damping.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +41,7 @@
 #include "../../include/sim3opt.h"
 #include "devmem.hpp"
 #include "direct_factor.hpp"
+#include "lm_damping.hpp"
 
 namespace sim3opt_bundle {
 
@@ -66,6 +67,7 @@ struct Scal {
 };
 
 using sim3opt::ldl_sum_over_c;
+using sim3opt::LmDamping;
 
 __device__ __forceinline__ void quat_to_R(const double q[4], double R[9]) {
   const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -800,7 +802,7 @@ struct Problem {
     stats.clear();
     const int NC = nc(), NP = np(), NO = no();
     const int go = (NO + WG - 1) / WG, gp = (NP + WG - 1) / WG;
-    double lambda = 0.0, ni = 2.0;
+    LmDamping damp;
     bool ok = true;
     int iters = 0;
     for (int it = 0; it < max_iters && ok; ++it) {
@@ -809,33 +811,33 @@ struct Problem {
       int rc = chi2(&currentChi);
       if (rc) return rc;
       T.chi2_before = currentChi;
-      double tempChi = currentChi;
       hipLaunchKernelGGL(k_ba_obs, dim3(go), dim3(WG), 0, stream, oargs(), d_lin);
       double rho = 0.0;
       int qmax = 0;
       do {
         BA_HIPCHK(hipMemcpyAsync(d_cams_bk, d_cams, sizeof(Cam) * NC, hipMemcpyDeviceToDevice, stream));
         BA_HIPCHK(hipMemcpyAsync(d_pts_bk, d_pts, sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, stream));
-        if (it == 0 && qmax == 0 && !(opt.user_lambda_init > 0)) {
-          // computeLambdaInit: tau * max diagonal entry of the (undamped) Hessian over all vertices
-          hipLaunchKernelGGL(k_ba_points, dim3(gp), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_lin, 1.0,
-                             d_Hinv, d_bp, d_pdmax);
-          hipLaunchKernelGGL(k_ba_obs2, dim3(go), dim3(WG), 0, stream, NO, d_op, d_lin, d_Hinv, d_Z);
-          hipLaunchKernelGGL(k_ba_reduced, dim3((nblk + 3) / 4), dim3(WG), 0, stream, nblk, d_brow, d_bcol,
-                             d_sptr, d_sa, d_sb, d_op, d_lin, d_Z, d_bp, d_fixed, 1.0, d_S, d_g, d_bc,
-                             d_cdmax);
-          hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)nullptr, 0,
-                             (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)d_pdmax, NP,
-                             (const double*)d_cdmax, 7 * NC, d_sc);
-          BA_HIPCHK(hipGetLastError());
-          rc = fetch();
-          if (rc) return rc;
-          lambda = opt.tau * h_sc->maxdiag;
-          ni = 2.0;
-        } else if (it == 0 && qmax == 0) {
-          lambda = opt.user_lambda_init;
-          ni = 2.0;
+        if (it == 0 && qmax == 0) {
+          double maxdiag = 0.0;
+          if (!(opt.user_lambda_init > 0)) {
+            // computeLambdaInit: tau * max diagonal entry of the (undamped) Hessian over all vertices
+            hipLaunchKernelGGL(k_ba_points, dim3(gp), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_lin, 1.0,
+                               d_Hinv, d_bp, d_pdmax);
+            hipLaunchKernelGGL(k_ba_obs2, dim3(go), dim3(WG), 0, stream, NO, d_op, d_lin, d_Hinv, d_Z);
+            hipLaunchKernelGGL(k_ba_reduced, dim3((nblk + 3) / 4), dim3(WG), 0, stream, nblk, d_brow, d_bcol,
+                               d_sptr, d_sa, d_sb, d_op, d_lin, d_Z, d_bp, d_fixed, 1.0, d_S, d_g, d_bc,
+                               d_cdmax);
+            hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)nullptr, 0,
+                               (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)d_pdmax, NP,
+                               (const double*)d_cdmax, 7 * NC, d_sc);
+            BA_HIPCHK(hipGetLastError());
+            rc = fetch();
+            if (rc) return rc;
+            maxdiag = h_sc->maxdiag;
+          }
+          damp.start(opt.user_lambda_init, opt.tau, maxdiag);
         }
+        const double lambda = damp.lambda;
         BA_HIPCHK(hipMemsetAsync(&d_sc->pcg_iters, 0, 2 * sizeof(int32_t), stream));
         hipLaunchKernelGGL(k_ba_points, dim3(gp), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_lin, lambda,
                            d_Hinv, d_bp, d_pdmax);
@@ -869,34 +871,26 @@ struct Problem {
         if (rc) return rc;
         T.pcg_iters += h_sc->pcg_iters;
         T.pcg_rel_res = h_sc->pcg_rel;
-        double scale = h_sc->scale;
-        tempChi = h_sc->fail ? DBL_MAX : h_sc->chi2;
-        if (h_sc->fail) scale = 0.0;
-        rho = (currentChi - tempChi) / (scale + 1e-3);
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1.0 - std::pow(2 * rho - 1, 3);
-          alpha = std::min(alpha, 2.0 / 3.0);
-          lambda *= std::max(1.0 / 3.0, alpha);
-          ni = 2.0;
+        const double tempChi = h_sc->fail ? DBL_MAX : h_sc->chi2;
+        const double scale = h_sc->fail ? 0.0 : h_sc->scale;
+        if (damp.update(currentChi, tempChi, scale, 1.0 / 3.0, 2.0 / 3.0, rho)) {
           currentChi = tempChi;
         } else {
-          lambda *= ni;
-          ni *= 2.0;
           BA_HIPCHK(hipMemcpyAsync(d_cams, d_cams_bk, sizeof(Cam) * NC, hipMemcpyDeviceToDevice, stream));
           BA_HIPCHK(hipMemcpyAsync(d_pts, d_pts_bk, sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, stream));
         }
         ++qmax;
       } while (rho < 0 && qmax < opt.max_trials);
       T.chi2_after = currentChi;
-      T.lambda = lambda;
+      T.lambda = damp.lambda;
       T.rho = rho;
       T.trials = qmax;
       stats.push_back(T);
       ++iters;
       if (opt.verbose)
         std::fprintf(stderr, "ba iteration= %d\t chi2= %.9g\t lambda= %.6g\t levenbergIter= %d\t pcg= %d (rel %.1e)\n",
-                     it, currentChi, lambda, qmax, T.pcg_iters, T.pcg_rel_res);
-      if (qmax == opt.max_trials || rho == 0 || !std::isfinite(lambda)) ok = false;
+                     it, currentChi, damp.lambda, qmax, T.pcg_iters, T.pcg_rel_res);
+      if (damp.terminate(qmax, opt.max_trials, rho)) ok = false;
     }
     BA_HIPCHK(hipStreamSynchronize(stream));
     BA_HIPCHK(hipMemcpy(cams.data(), d_cams, sizeof(Cam) * NC, hipMemcpyDeviceToHost));

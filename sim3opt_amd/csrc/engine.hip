@@ -1,6 +1,7 @@
-// engine.hip -- initialisation, linearisation, chi2 and the LM trial loop (g2o: SparseOptimizer::optimize ->
-// OptimizationAlgorithmLevenberg::solve, kitti_surf.cpp:674-675); the C++ interface capi.cpp calls
+// engine.hip -- initialisation, linearisation, chi2, the iteration frame and the LM trial loop (g2o: SparseOptimizer::
+// optimize -> OptimizationAlgorithmLevenberg::solve, kitti_surf.cpp:674-675); the C++ interface capi.cpp calls
 #include "engine_impl.hpp"
+#include "lm_damping.hpp"
 #include "robust.hpp"
 #include "sim3_jac.hpp"
 
@@ -258,17 +259,14 @@ int Engine::fetch_scalars(std::string& err) {
 }
 
 // ---- timing helpers ----
-int Engine::timed_begin(std::string& err) {
-  HIPCHK(hipEventRecord(ev_a, stream));
-  return SIM3OPT_OK;
-}
-
-int Engine::timed_end(double& ms_acc, std::string& err) {
-  HIPCHK(hipEventRecord(ev_b, stream));
-  HIPCHK(hipEventSynchronize(ev_b));
+// Phase times of an iteration are event stamps on the stream (ev_ph[0] linearise | 1 solve | 2 update | 3), read
+// after the trial's chi2 fetch: ONE host round trip per trial; waiting on every phase's end event left the GPU idle
+// a quarter of the time on the small graphs.
+int Engine::phase_ms(int a, int b, double& acc, std::string& err) {
+  if (!phase_timing) return SIM3OPT_OK;
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, ev_a, ev_b));
-  ms_acc += ms;
+  HIPCHK(hipEventElapsedTime(&ms, ev_ph[a], ev_ph[b]));
+  acc += ms;
   return SIM3OPT_OK;
 }
 
@@ -419,10 +417,37 @@ int Engine::linearize(std::string& err) {
   return SIM3OPT_OK;
 }
 
-// the two kernels of the LM update the other algorithms (engine_algorithms.hip) reuse
-void Engine::apply_step(const double* x) {
+// ---- the iteration frame of LM, Gauss-Newton and dogleg (the other two: engine_algorithms.hip) ----
+int Engine::iter_begin(sim3opt_iter_stats& T, double& chi, std::string& err) {
+  if (phase_timing) HIPCHK(hipEventRecord(ev_ph[0], stream));
+  // computeActiveErrors at the start of an iteration: the estimates are those the last trial
+  // evaluated (accepted) or restored (rejected), and the evaluation is deterministic, so the
+  // value is already here -- one host round trip less per iteration
+  if (chi_known) chi = chi_cache;
+  else {
+    int rc = chi2(&chi, err);
+    if (rc) return rc;
+  }
+  T.chi2_before = chi;
+  return linearize(err);
+}
+
+void Engine::iter_end(sim3opt_iter_stats& T, double chi, std::vector<sim3opt_iter_stats>& stats) {
+  kt.ms_linearize += T.ms_linearize;
+  kt.ms_update += T.ms_update;
+  chi_known = true;
+  chi_cache = chi;
+  T.chi2_after = chi;
+  stats.push_back(T);
+}
+
+// pcg() reports success on the exact path: a non-positive pivot comes back in the scalars of the caller's next
+// fetch (k_oplus left the estimates alone then)
+bool Engine::direct_rejected() const { return use_direct && h_sc->fail == fail_token; }
+
+void Engine::apply_step(const double* x, bool push) {
   hipLaunchKernelGGL(k_oplus, dim3((nv + WG - 1) / WG), dim3(WG), 0, stream, nv, d_hidx, x, d_states, mopts(),
-                     use_direct ? (const DevScalars*)d_sc : nullptr, (Sim3*)nullptr, fail_token);
+                     use_direct ? (const DevScalars*)d_sc : nullptr, push ? d_backup : (Sim3*)nullptr, fail_token);
 }
 
 void Engine::pop_states() {
@@ -431,184 +456,84 @@ void Engine::pop_states() {
 }
 
 int Engine::optimize(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
+  stats.clear();
   tr_stats.clear();
+  chi_known = false;  // (options or estimates may have changed since the last call)
   if (opt.algorithm == SIM3OPT_ALGORITHM_GAUSS_NEWTON) return optimize_gauss_newton(max_iters, stats, err);
   if (opt.algorithm == SIM3OPT_ALGORITHM_DOGLEG) return optimize_dogleg(max_iters, stats, err);
-  stats.clear();
-  double lambda = 0.0, ni = 2.0;
+  LmDamping damp;
   bool ok = true;
   int iters = 0;
-  chi_known = false;  // (options or estimates may have changed since the last call)
   for (int it = 0; it < max_iters && ok; ++it) {
     sim3opt_iter_stats T{};
     double currentChi = 0.0;
-    int rc = SIM3OPT_OK;
-    // phase times: event stamps on the stream, read after the trial's chi2 fetch -- the loop has
-    // ONE host round trip per trial (plus lambda_0's at the first iteration); waiting on every
-    // phase's end event left the GPU idle a quarter of the time on the small graphs
-    if (phase_timing) HIPCHK(hipEventRecord(ev_ph[0], stream));
-    // computeActiveErrors at the start of an iteration: the estimates are those the last trial
-    // evaluated (accepted) or restored (rejected), and the evaluation is deterministic, so the
-    // value is already here -- one host round trip less per iteration
-    if (chi_known) currentChi = chi_cache;
-    else {
-      rc = chi2(&currentChi, err);
-      if (rc) return rc;
-    }
-    double tempChi = currentChi;
-    T.chi2_before = currentChi;
-    rc = linearize(err);
+    int rc = iter_begin(T, currentChi, err);
     if (rc) return rc;
-    bool lin_pending = true;  // ev_ph[0] -> the first trial's ev_ph[1]
-    if (it == 0) {
+    if (it == 0) {  // lambda_0: one host round trip more
       rc = fetch_scalars(err);
       if (rc) return rc;
       double maxdiag;
       std::memcpy(&maxdiag, &h_sc->maxdiag_bits, sizeof(double));
-      lambda = opt.user_lambda_init > 0 ? opt.user_lambda_init : opt.tau * maxdiag;
-      ni = 2.0;
+      damp.start(opt.user_lambda_init, opt.tau, maxdiag);
     }
     double rho = 0.0;
     int qmax = 0;
-    // solutions of the next trials, solved together after a rejection (engine_batch.hip)
-    struct { int n = 0, next = 0; double lam[KB]; int32_t iters[KB]; double rel[KB]; bool capped[KB]; } batch;
-    bool prev_ok = false, prev_capped = false;  // the previous trial's solve (of this LM iteration)
-    int32_t prev_pit = 0;
-    auto elapsed = [&](int a, int b, double& acc) -> int {
-      if (!phase_timing) return SIM3OPT_OK;
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev_ph[a], ev_ph[b]));
-      acc += ms;
-      return SIM3OPT_OK;
-    };
     do {
       if (phase_timing) HIPCHK(hipEventRecord(ev_ph[1], stream));  // (push(): k_oplus keeps the old estimates itself)
+      const double* xsol = d_x;  // the step of this trial
       int32_t pit = 0;
       double rres = 0.0;
       bool ok2 = true;
-      const double* xsol = d_x;  // the step of this trial
-      bool from_batch = false;
-      if (batch.next < batch.n && batch.lam[batch.next] == lambda) {
-        from_batch = true;
-      } else {
-        batch.n = batch.next = 0;
-        // A rejection has just happened: g2o's rule fixes the dampings of the next trials (lambda *= nu, nu *= 2
-        // per rejection), so the systems of the trials that may follow are solved TOGETHER -- one pass over the
-        // blocks for all of them -- and evaluated one after the other exactly as before; a trial that is
-        // accepted leaves the rest unused.  Only systems the hierarchy would solve anyway: a damping-dominated
-        // one (lambda >= the block-Jacobi gate, adaptive_prec) is cheaper on its own.
-        // ... and only while this iteration's solves behave: a batch runs until its LAST system is done, every
-        // iteration at the price of all of them, and one failing system sends the whole batch to the sequential
-        // path's fall-backs -- in the as-written arithmetic (solves of hundreds of iterations, break-downs, a
-        // capped one) that made the reference_arithmetic leg 1.7x SLOWER; there the trials stay sequential.
-        const bool calm = prev_ok && !prev_capped && prev_pit > 0 && prev_pit <= 100;
-        const int cap = qmax >= 1 && calm ? std::min(batch_capacity(), opt.max_trials - qmax) : 0;
-        if (cap >= 2) {
-          double gate = DBL_MAX;
-          if (adaptive_prec && !trace_stale && mean_diag > 0.0) gate = bj_gate >= 0.0 ? bj_gate : 0.05 * mean_diag;
-          int nsys = 0;
-          double l = lambda, nu = ni;
-          while (nsys < cap && l < gate && std::isfinite(l)) {
-            batch.lam[nsys++] = l;
-            l *= nu;
-            nu *= 2.0;
-          }
-          if (nsys >= 2) {
-            bool usable = false;
-            rc = pcg_batch(batch.lam, nsys, batch.iters, batch.rel, batch.capped, &usable, err);
-            if (rc) return rc;
-            if (usable) {
-              batch.n = nsys;
-              from_batch = true;
-            }
-          }
-        }
-      }
-      if (from_batch) {
-        const int s = batch.next++;
-        xsol = b_x + (size_t)s * b_vs;
-        pit = batch.iters[s];
-        rres = batch.rel[s];
-        last_capped = batch.capped[s];
-      } else {
-        rc = pcg(lambda, &pit, &rres, &ok2, err);
-        if (rc) return rc;
-      }
+      rc = lm_trial_solve(qmax, damp.lambda, damp.ni, &xsol, &pit, &rres, &ok2, err);
+      if (rc) return rc;
       if (phase_timing) HIPCHK(hipEventRecord(ev_ph[2], stream));
       T.pcg_iters += pit;
       T.pcg_rel_res = rres;
       if (last_capped) T.pcg_capped += 1;
       if (opt.verbose >= 2)
-        std::fprintf(stderr, "  trial %d: lambda %.6g, %d PCG iterations (rel %.2e)\n", qmax, lambda, pit, rres);
-      double scale = 0.0;
+        std::fprintf(stderr, "  trial %d: lambda %.6g, %d PCG iterations (rel %.2e)\n", qmax, damp.lambda, pit, rres);
+      double tempChi = DBL_MAX, scale = 0.0;  // (solver failed: g2o forces rejection)
       if (ok2) {
-        hipLaunchKernelGGL(k_oplus, dim3((nv + WG - 1) / WG), dim3(WG), 0, stream, nv, d_hidx,
-                           xsol, d_states, mopts(), use_direct ? (const DevScalars*)d_sc : nullptr, d_backup,
-                           fail_token);
+        apply_step(xsol, true);
         const int ge = grid_for(7 * (int64_t)(r1 - r0), WG);
         hipLaunchKernelGGL(k_scale, dim3(ge), dim3(WG), 0, stream, 7 * r0, 7 * r1, xsol, d_b,
-                           lambda, d_part_b);
+                           damp.lambda, d_part_b);
         HIPCHK(hipGetLastError());
         rc = chi2(&tempChi, err, phase_timing ? ev_ph[3] : nullptr, ge);  // also sums and brings back scale (and the factorisation's verdict)
         if (rc) return rc;
-        rc = elapsed(2, 3, T.ms_update);
+        rc = phase_ms(2, 3, T.ms_update, err);
         if (rc) return rc;
         scale = h_sc->scale;
         kt.n_update += 1;
-        if (use_direct && h_sc->fail == fail_token) {  // not positive definite: g2o's solver returns false
+        if (direct_rejected()) {  // not positive definite: g2o's solver returns false
           tempChi = DBL_MAX;
           scale = 0.0;
         }
       } else {
-        tempChi = DBL_MAX;  // solver failed: g2o forces rejection
         if (phase_timing) HIPCHK(hipEventSynchronize(ev_ph[2]));
         else HIPCHK(hipStreamSynchronize(stream));
       }
-      rc = elapsed(1, 2, T.ms_solve);
+      rc = phase_ms(1, 2, T.ms_solve, err);
       if (rc) return rc;
-      if (lin_pending) {
-        rc = elapsed(0, 1, T.ms_linearize);
-        if (rc) return rc;
-        kt.ms_linearize += T.ms_linearize;
-        lin_pending = false;
-      }
-      rho = currentChi - tempChi;
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1.0 - std::pow(2 * rho - 1, 3);
-        alpha = std::min(alpha, opt.good_step_upper);
-        lambda *= std::max(opt.good_step_lower, alpha);
-        ni = 2.0;
+      if (qmax == 0 && (rc = phase_ms(0, 1, T.ms_linearize, err))) return rc;
+      if (damp.update(currentChi, tempChi, scale, opt.good_step_lower, opt.good_step_upper, rho))
         currentChi = tempChi;  // discardTop
-      } else {
-        lambda *= ni;
-        ni *= 2.0;
-        if (ok2)  // pop (a failed solve never touched the estimates -- nor the backup)
-          hipLaunchKernelGGL(k_copy_states, dim3((8 * nv + WG - 1) / WG), dim3(WG), 0, stream, nv,
-                             (const Sim3*)d_backup, d_states);
-      }
-      prev_ok = ok2;
-      prev_capped = last_capped;
-      prev_pit = pit;
+      else if (ok2)
+        pop_states();  // (a failed solve never touched the estimates -- nor the backup)
       ++qmax;
     } while (rho < 0 && qmax < opt.max_trials);
-    kt.ms_update += T.ms_update;
-    chi_known = true;
-    chi_cache = currentChi;
-    T.chi2_after = currentChi;
-    T.lambda = lambda;
+    T.lambda = damp.lambda;
     T.rho = rho;
     T.trials = qmax;
-    stats.push_back(T);
+    iter_end(T, currentChi, stats);
     ++iters;
     if (opt.verbose)
       std::fprintf(stderr,
                    "iteration= %d\t chi2= %.9g\t lambda= %.6g\t levenbergIter= %d\t pcg= %d "
                    "(rel %.2e)\t ms lin/solve/upd= %.3f/%.3f/%.3f\n",
-                   it, currentChi, lambda, qmax, T.pcg_iters, T.pcg_rel_res, T.ms_linearize,
+                   it, currentChi, damp.lambda, qmax, T.pcg_iters, T.pcg_rel_res, T.ms_linearize,
                    T.ms_solve, T.ms_update);
-    if (qmax == opt.max_trials || rho == 0 || !std::isfinite(lambda)) ok = false;  // Terminate
+    if (damp.terminate(qmax, opt.max_trials, rho)) ok = false;
   }
   HIPCHK(hipStreamSynchronize(stream));
   return iters;
@@ -797,7 +722,7 @@ int engine_solve(Engine* e, double lambda, double* x, int32_t* iters, double* re
   if (e->use_direct) {  // the factorisation reports a non-positive pivot through the scalars
     rc = e->fetch_scalars(err);
     if (rc) return rc;
-    ok = e->h_sc->fail != e->fail_token;
+    ok = !e->direct_rejected();
   }
   if (iters) *iters = it;
   if (rel_res) *rel_res = rr;

@@ -7,26 +7,25 @@ namespace sim3opt {
 
 #include "algo_kernels.hpp"
 
+int Engine::fail_iteration(int it, sim3opt_iter_stats& T, double chi, std::vector<sim3opt_iter_stats>& stats,
+                           const char* why, std::string& err) {
+  iter_end(T, chi, stats);
+  err = why;
+  if (opt.verbose) std::fprintf(stderr, "iteration= %d\t %s\n", it, err.c_str());
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // Gauss-Newton: linearise, solve H x = b (lambda = 0), S <- exp(x) S, chi2.  No acceptance test; a failed solve
 // (CG breakdown, a non-positive pivot of the exact factorisation) is g2o's Fail: optimize() returns 0.
 // ------------------------------------------------------------------------------------------
 int Engine::optimize_gauss_newton(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
-  stats.clear();
-  chi_known = false;  // (options or estimates may have changed since the last call)
   int iters = 0;
   for (int it = 0; it < max_iters; ++it) {
     sim3opt_iter_stats T{};
-    int rc = SIM3OPT_OK;
-    if (phase_timing) HIPCHK(hipEventRecord(ev_ph[0], stream));
     double currentChi = 0.0;
-    if (chi_known) currentChi = chi_cache;
-    else {
-      rc = chi2(&currentChi, err);
-      if (rc) return rc;
-    }
-    T.chi2_before = currentChi;
-    rc = linearize(err);
+    int rc = iter_begin(T, currentChi, err);
     if (rc) return rc;
     if (phase_timing) HIPCHK(hipEventRecord(ev_ph[1], stream));
     int32_t pit = 0;
@@ -38,44 +37,24 @@ int Engine::optimize_gauss_newton(int32_t max_iters, std::vector<sim3opt_iter_st
     T.pcg_iters = pit;
     T.pcg_rel_res = rres;
     if (last_capped) T.pcg_capped = 1;
+    T.trials = 1;
     double newChi = DBL_MAX;
     if (ok) {  // (exact path: the verdict comes back with chi2; k_oplus leaves the estimates alone on a failure)
-      apply_step(d_x);
+      apply_step(d_x, false);
       HIPCHK(hipGetLastError());
       rc = chi2(&newChi, err, phase_timing ? ev_ph[3] : nullptr);
       if (rc) return rc;
       kt.n_update += 1;
-      if (use_direct && h_sc->fail == fail_token) ok = false;
+      if (direct_rejected()) ok = false;
+      else if ((rc = phase_ms(2, 3, T.ms_update, err))) return rc;
+    } else if (phase_timing) {
+      HIPCHK(hipStreamSynchronize(stream));  // (ev_ph[2] was recorded after the solve's last fetch)
     }
-    if (phase_timing) {
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev_ph[0], ev_ph[1]));
-      T.ms_linearize = ms;
-      HIPCHK(hipEventElapsedTime(&ms, ev_ph[1], ev_ph[2]));
-      T.ms_solve = ms;
-      if (ok) {
-        HIPCHK(hipEventElapsedTime(&ms, ev_ph[2], ev_ph[3]));
-        T.ms_update = ms;
-      }
-      kt.ms_linearize += T.ms_linearize;
-      kt.ms_update += T.ms_update;
-    }
-    T.trials = 1;
-    if (!ok) {
-      T.chi2_after = currentChi;
-      stats.push_back(T);
-      chi_known = true;  // (the estimates were not touched)
-      chi_cache = currentChi;
-      err = "optimize: Gauss-Newton: the linear solve failed (H not positive definite)";
-      if (opt.verbose) std::fprintf(stderr, "iteration= %d\t %s\n", it, err.c_str());
-      HIPCHK(hipStreamSynchronize(stream));
-      return 0;
-    }
-    chi_known = true;
-    chi_cache = newChi;
-    T.chi2_after = newChi;
-    stats.push_back(T);
+    if ((rc = phase_ms(0, 1, T.ms_linearize, err)) || (rc = phase_ms(1, 2, T.ms_solve, err))) return rc;
+    if (!ok)
+      return fail_iteration(it, T, currentChi, stats,
+                            "optimize: Gauss-Newton: the linear solve failed (H not positive definite)", err);
+    iter_end(T, newChi, stats);
     ++iters;
     if (opt.verbose)
       std::fprintf(stderr, "iteration= %d\t chi2= %.9g\t pcg= %d (rel %.2e)\t ms lin/solve/upd= %.3f/%.3f/%.3f\n", it,
@@ -110,9 +89,6 @@ int Engine::dogleg_dots(std::string& err) {
 }
 
 int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
-  stats.clear();
-  tr_stats.clear();
-  chi_known = false;
   if (!d_dl) {
     HIPCHK(dev_malloc((void**)&d_dl, sizeof(double) * (4 * MAX_GRID + DL_OUT + 8)));
     HIPCHK(hipMemset(d_dl, 0, sizeof(double) * (4 * MAX_GRID + DL_OUT + 8)));
@@ -131,27 +107,12 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
   const double factor = opt.dl_lambda_factor;
   int iters = 0;
   bool ok_all = true;
-  auto elapsed = [&](int a, int b, double& acc) -> int {
-    if (!phase_timing) return SIM3OPT_OK;
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev_ph[a], ev_ph[b]));
-    acc += ms;
-    return SIM3OPT_OK;
-  };
   for (int it = 0; it < max_iters && ok_all; ++it) {
     sim3opt_iter_stats T{};
     sim3opt_tr_stats R{};
-    int rc = SIM3OPT_OK;
-    if (phase_timing) HIPCHK(hipEventRecord(ev_ph[0], stream));
-    double currentChi = 0.0;
-    if (chi_known) currentChi = chi_cache;
-    else {
-      rc = chi2(&currentChi, err);
-      if (rc) return rc;
-    }
-    T.chi2_before = currentChi;
     R.delta_before = delta;
-    rc = linearize(err);
+    double currentChi = 0.0;
+    int rc = iter_begin(T, currentChi, err);
     if (rc) return rc;
     if (comm.active()) {  // every replica forms the whole step from b
       rc = comm.allgatherv(d_b, offs, stream, err);
@@ -177,7 +138,7 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
       HIPCHK(hipMemcpyAsync(h_dl, d_out, sizeof(double) * 6, hipMemcpyDeviceToHost, stream));
       rc = fetch_scalars(err);
       if (rc) return rc;
-      if (use_direct) ok = h_sc->fail != fail_token;
+      if (direct_rejected()) ok = false;
       was_pd = was_pd && ok;
       if (!was_pd) {
         if (ok) {
@@ -196,24 +157,14 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
         std::fprintf(stderr, "  GN solve: lambda %.6g, %s, %d PCG iterations (rel %.2e)\n", lam,
                      ok ? "ok" : "failed", pit, rres);
     }
-    rc = elapsed(0, 1, T.ms_linearize);
-    if (rc) return rc;
-    rc = elapsed(1, 2, T.ms_solve);
-    if (rc) return rc;
-    kt.ms_linearize += T.ms_linearize;
+    if ((rc = phase_ms(0, 1, T.ms_linearize, err)) || (rc = phase_ms(1, 2, T.ms_solve, err))) return rc;
     R.was_pd = was_pd ? 1 : 0;
     if (!solved) {
-      T.chi2_after = currentChi;
       T.lambda = lam_c;
       R.delta_after = delta;
-      stats.push_back(T);
       tr_stats.push_back(R);
-      chi_known = true;
-      chi_cache = currentChi;
-      err = "optimize: dogleg: the damped linear solve still failed at lambda 1e3";
-      if (opt.verbose) std::fprintf(stderr, "iteration= %d\t %s\n", it, err.c_str());
-      HIPCHK(hipStreamSynchronize(stream));
-      return 0;
+      return fail_iteration(it, T, currentChi, stats,
+                            "optimize: dogleg: the damped linear solve still failed at lambda 1e3", err);
     }
     const double bb = h_dl[DL_BB], bHb = h_dl[DL_BHB], gg = h_dl[DL_GG], bg = h_dl[DL_BG], hbg = h_dl[DL_HBG],
                  gHg = h_dl[DL_GHG];
@@ -262,7 +213,7 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
       rc = chi2(&newChi, err, phase_timing ? ev_ph[3] : nullptr);
       if (rc) return rc;
       kt.n_update += 1;
-      rc = elapsed(1, 3, T.ms_update);
+      rc = phase_ms(1, 3, T.ms_update, err);
       if (rc) return rc;
       if (std::fabs(linearGain) < 1e-12) linearGain = 1e-12;
       rho = (currentChi - newChi) / linearGain;
@@ -278,15 +229,11 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
         std::fprintf(stderr, "  trial %d: step %d, ||h_dl|| %.6g, rho %.6g, delta %.6g\n", tries, R.step, R.norm_dl,
                      rho, delta);
     } while (!good && tries < opt.dl_max_trials);
-    kt.ms_update += T.ms_update;
     R.delta_after = delta;
-    chi_known = true;
-    chi_cache = currentChi;
-    T.chi2_after = currentChi;
+    tr_stats.push_back(R);
     T.rho = rho;
     T.trials = tries;
-    stats.push_back(T);
-    tr_stats.push_back(R);
+    iter_end(T, currentChi, stats);
     ++iters;
     if (opt.verbose)
       std::fprintf(stderr,

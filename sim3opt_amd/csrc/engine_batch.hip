@@ -2,8 +2,9 @@
 // trials of one LM iteration (OptimizationAlgorithmLevenberg::solve, reached from kitti_surf.cpp:675) solve
 // (H + lambda_k I) x_k = b for a known sequence lambda_k; after the first rejection the next ones are solved
 // together -- one pass over the blocks for K vectors, K vectors per coarse launch -- and evaluated in g2o's
-// order (Engine::optimize).  Per system the arithmetic is that of Engine::pcg_attempt with the multigrid
-// preconditioner, operation by operation: the K solutions are bit for bit those of K sequential solves.
+// order (Engine::lm_trial_solve, at the end, decides and hands them out).  Per system the arithmetic is that of
+// Engine::pcg_attempt with the multigrid preconditioner, operation by operation: the K solutions are bit for bit
+// those of K sequential solves.
 #include "engine_impl.hpp"
 
 namespace sim3opt {
@@ -268,6 +269,63 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   kt.n_batched_solves += nsys;
   kt.n_batches += 1;
   *usable = good;
+  return SIM3OPT_OK;
+}
+
+// The solve of LM trial q at damping lambda; ni is the factor the next rejection applies.  After a rejection g2o's
+// rule fixes the dampings of the next trials (lambda *= ni, ni *= 2 per rejection), so the systems of the trials
+// that may follow are solved TOGETHER -- one pass over the blocks for all of them -- and handed to the trials one
+// after the other, evaluated exactly as before; a trial that is accepted leaves the rest unused.
+// Only systems the hierarchy would solve anyway: a damping-dominated one (lambda >= the block-Jacobi gate,
+// adaptive_prec) is cheaper on its own.
+// ... and only while this iteration's solves behave: a batch runs until its LAST system is done, every iteration
+// at the price of all of them, and one failing system sends the whole batch to the sequential path's fall-backs --
+// in the as-written arithmetic (solves of hundreds of iterations, break-downs, a capped one) that made the
+// reference_arithmetic leg 1.7x SLOWER; there the trials stay sequential.
+int Engine::lm_trial_solve(int q, double lambda, double ni, const double** x, int32_t* iters, double* rel_res,
+                           bool* ok, std::string& err) {
+  TrialBatch& B = trial_batch;
+  bool from_batch = q > 0 && B.next < B.n && B.lam[B.next] == lambda;
+  if (!from_batch) {
+    B.n = B.next = 0;
+    const bool calm = B.prev_ok && !B.prev_capped && B.prev_pit > 0 && B.prev_pit <= 100;
+    const int cap = q >= 1 && calm ? std::min(batch_capacity(), opt.max_trials - q) : 0;
+    if (cap >= 2) {
+      double gate = DBL_MAX;
+      if (adaptive_prec && !trace_stale && mean_diag > 0.0) gate = bj_gate >= 0.0 ? bj_gate : 0.05 * mean_diag;
+      int nsys = 0;
+      double l = lambda, nu = ni;
+      while (nsys < cap && l < gate && std::isfinite(l)) {
+        B.lam[nsys++] = l;
+        l *= nu;
+        nu *= 2.0;
+      }
+      if (nsys >= 2) {
+        bool usable = false;
+        int rc = pcg_batch(B.lam, nsys, B.iters, B.rel, B.capped, &usable, err);
+        if (rc) return rc;
+        if (usable) {
+          B.n = nsys;
+          from_batch = true;
+        }
+      }
+    }
+  }
+  if (from_batch) {
+    const int s = B.next++;
+    *x = b_x + (size_t)s * b_vs;
+    *iters = B.iters[s];
+    *rel_res = B.rel[s];
+    *ok = true;
+    last_capped = B.capped[s];
+  } else {
+    *x = d_x;
+    int rc = pcg(lambda, iters, rel_res, ok, err);
+    if (rc) return rc;
+  }
+  B.prev_ok = *ok;
+  B.prev_capped = last_capped;
+  B.prev_pit = *iters;
   return SIM3OPT_OK;
 }
 

@@ -1,9 +1,11 @@
 // engine_impl.hpp -- the Engine class shared by the translation units of the device-resident LM:
-//   engine.hip         initialisation, linearisation, chi2, the LM trial loop (OptimizationAlgorithmLevenberg::solve)
+//   engine.hip         initialisation, linearisation, chi2, the iteration frame of LM, Gauss-Newton and dogleg, the
+//                      LM trial loop (OptimizationAlgorithmLevenberg::solve; its damping rule: lm_damping.hpp)
 //   engine_pcg.hip     the preconditioned CG (LinearSolverEigen's role on graphs too large to factor), halo exchange
 //   engine_amg.hip     the aggregation-multigrid preconditioner: set-up per linearisation / per trial, the cycle
 //   engine_direct.hip  when the LM factorises exactly (LinearSolverEigen's role on KITTI-00-like graphs) and the
 //                      marginal covariances: policy over two BlockLdl (direct_factor.hpp, direct_factor.hip)
+//   engine_batch.hip   the multigrid PCG for several right-hand sides: an LM trial's solve (lm_trial_solve)
 //   engine_algorithms.hip  Gauss-Newton and Powell's dogleg (options.algorithm = 1 / 2)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
 // engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, algo_kernels.hpp -> engine_algorithms.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
@@ -251,6 +253,15 @@ class Engine {
   double* b_cycle(int l, double* cur, double* other);
   int pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_res, bool* capped, bool* usable,
                 std::string& err);
+  // the solve of LM trial q at damping lambda (ni: the rule's next factor); *x: d_x or its system of a batch
+  int lm_trial_solve(int q, double lambda, double ni, const double** x, int32_t* iters, double* rel_res, bool* ok,
+                     std::string& err);
+  struct TrialBatch {  // the current LM iteration's batch (systems n, the next to hand out) and previous trial's solve
+    int n = 0, next = 0;
+    double lam[KB], rel[KB];
+    int32_t iters[KB], prev_pit = 0;
+    bool capped[KB], prev_ok = false, prev_capped = false;
+  } trial_batch;
   // most systems a batch may hold for this graph and these options (0: no batching)
   int batch_capacity() const {
     if (!use_amg || use_direct || comm.active() || !amg_fp32 || amg_additive || opt.pcg_batch == 1) return 0;
@@ -306,7 +317,7 @@ class Engine {
   int exchange_level(int l, double* vec, std::string& err);
   // timing
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  // phase stamps of the LM loop (linearise | solve | update): recorded without waiting, read after
+  // phase stamps of an iteration (linearise | solve | update; phase_ms): recorded without waiting, read after
   // the trial's one host round trip (the chi2 fetch)
   hipEvent_t ev_ph[4] = {nullptr, nullptr, nullptr, nullptr};
   // per-iteration phase times (IterStats::ms_*): three event markers per LM trial, ~5.6 us of idle stream each --
@@ -338,8 +349,7 @@ class Engine {
   int fetch_scalars(std::string& err);
 
   // ---- timing helpers ----
-  int timed_begin(std::string& err);
-  int timed_end(double& ms_acc, std::string& err);
+  int phase_ms(int a, int b, double& acc, std::string& err);  // acc += stamp ev_ph[a] -> ev_ph[b] (both complete)
   int pool_get(hipEvent_t& a, hipEvent_t& b, std::string& err);
   // after a stream sync: fold the recorded SpMV event pairs into the accumulators
   // (h_sc must be fresh).  Launches enqueued after the solve finished return at once; they are
@@ -476,17 +486,25 @@ class Engine {
   int pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res, bool* ok,
                   bool* chain_broke, std::string& err, int probe_budget = 0, bool* abandoned = nullptr);
 
+  // ---- the iteration frame of LM, Gauss-Newton and dogleg (engine.hip) ----
+  int iter_begin(sim3opt_iter_stats& T, double& chi, std::string& err);  // stamp 0, chi2 (cached or not), linearise
+  void iter_end(sim3opt_iter_stats& T, double chi, std::vector<sim3opt_iter_stats>& stats);  // cache chi, record T
+  bool direct_rejected() const;  // after the caller's fetch: the exact factorisation met a non-positive pivot
+  void apply_step(const double* x, bool push);  // k_oplus; push: the old estimates into d_backup first
+  void pop_states();                            // k_copy_states from d_backup
+
   int optimize(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err);
 
   // ---- Gauss-Newton and Powell's dogleg (engine_algorithms.hip) ----
-  // optimize() hands options.algorithm = 1 / 2 to these; the LM loop above is not involved
+  // optimize() clears the stats and the chi2 cache, then hands options.algorithm = 1 / 2 to these
   int optimize_gauss_newton(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err);
   int optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err);
+  // g2o's Fail: iteration `it` is recorded with the estimates it started from; optimize() returns 0
+  int fail_iteration(int it, sim3opt_iter_stats& T, double chi, std::vector<sim3opt_iter_stats>& stats,
+                     const char* why, std::string& err);
   // the six per-iteration scalars of the dogleg model from b (d_b) and h_gn (d_x): two SpMVs with lambda = 0 and
   // one fused dot kernel, all-reduced over the ranks; left on the device in d_dl (no host round trip here)
   int dogleg_dots(std::string& err);
-  void apply_step(const double* x);  // k_oplus without a backup (engine.hip)
-  void pop_states();                 // k_copy_states from d_backup (engine.hip)
   std::vector<sim3opt_tr_stats> tr_stats;  // per iteration of the last dogleg run
   double* d_dl = nullptr;  // dogleg: 4 x MAX_GRID dot partials, then the 8 scalars (DL_OUT)
   double* h_dl = nullptr;  // pinned copy of the scalars
