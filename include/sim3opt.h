@@ -415,6 +415,38 @@ int sim3opt_marginal_plan(sim3opt_graph* g, int64_t max_pairs, int64_t dims[6], 
 int sim3opt_amg_hierarchy(sim3opt_graph* g, int32_t capacity, int32_t* n_levels, int32_t* rows,
                           int64_t* blocks, int32_t* aggregate_of_row);
 
+/* ---- diagnostic read-outs of the PCG's preconditioners (tests/test_gpu_preconditioners.py compares them with a
+ * long-double restatement, tests/amg_ref.py).  Inspection calls like sim3opt_get_system: nothing in the solver uses
+ * them, and a solve or optimize() after one of them computes bit for bit what it computes without it. ---- */
+/* Diagnostic.  Structure of level `level` of the hierarchy sim3opt_amg_hierarchy describes (host only, no GPU, may be
+ * called before initialize): *n_levels, the level's block rows and blocks, its pattern (rowptr n_block_rows + 1,
+ * colidx n_blocks; level 0: the system's; coarse levels: diagonal first, then unique ascending columns) and, on
+ * every level but the coarsest, the aggregate (row of level + 1) of each row.  Any pointer may be NULL: call once
+ * for the sizes, once for the arrays. */
+int sim3opt_amg_level_structure(sim3opt_graph* g, int32_t level, int32_t* n_levels, int32_t* n_block_rows,
+                                int64_t* n_blocks, int32_t* rowptr, int32_t* colidx, int32_t* aggregate_of_row);
+/* Diagnostic.  Numbers of level `level` after the set-up a multigrid PCG solve with damping `lambda` runs on the
+ * last linearisation (Galerkin products if the linearisation is new, then the per-trial part).  Any pointer may be
+ * NULL.  rowptr / colidx: the pattern as the device holds it; values: n_blocks x 49 column-major blocks (level 0:
+ * H undamped; coarse levels: the diagonal blocks damped by lambda W); values32: the FP32 copy the cycle's matrix
+ * passes stream, de-interleaved to n_blocks x 49 (options.amg_fp32 = 0: SIM3OPT_ERR_STATE); W = P^T P and diagH =
+ * the undamped diagonal blocks (n_block_rows x 49 column-major; coarse levels only); Minv = omega (D + lambda W)^-1
+ * (n_block_rows x 49 ROW-major, as stored); P = Ad(S_v) of every level-0 row (column-major; level 0 only).
+ * A non-positive pivot in the set-up: SIM3OPT_ERR_STATE (a solve would fall back to block-Jacobi).  One GPU only
+ * (world > 1: SIM3OPT_ERR_STATE), multigrid graphs only. */
+int sim3opt_amg_level_numbers(sim3opt_graph* g, double lambda, int32_t level, int32_t* rowptr, int32_t* colidx,
+                              double* values, float* values32, double* W, double* diagH, double* Minv, double* P);
+/* Diagnostic.  The dense inverse of the coarsest level for `lambda` (7 rows x 7 rows of that level, row-major);
+ * otherwise as sim3opt_amg_level_numbers. */
+int sim3opt_amg_coarsest_inverse(sim3opt_graph* g, double lambda, double* Ainv);
+/* Diagnostic.  z[q] = M^-1 r[q], q < nrhs (vectors of 7 x block rows, one after the other), for prec = 0 block-Jacobi,
+ * 1 chain segments, 2 aggregation multigrid -- 1 and 2 only on a graph initialised with that preconditioner
+ * (sim3opt_preconditioner_in_use) -- on the last linearisation: ONE set-up for `lambda`, then per right-hand side
+ * the launches of a PCG iteration with the engine's current cycle options.  A failed set-up pivot is
+ * SIM3OPT_ERR_STATE.  One GPU only. */
+int sim3opt_preconditioner_apply(sim3opt_graph* g, int32_t prec, double lambda, int32_t nrhs, const double* r,
+                                 double* z);
+
 /* ---- row-partitioned multi-GPU (one process per GPU, RCCL over xGMI) ----
  * Every rank adds the SAME full graph; rank r then owns a contiguous range of block rows (equal
  * length), linearises the edges incident to them, streams its rows in the SpMV and keeps

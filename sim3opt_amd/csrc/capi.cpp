@@ -753,19 +753,14 @@ int sim3opt_marginal_plan(sim3opt_graph* g, int64_t max_pairs, int64_t dims[6], 
   }
 }
 
-int sim3opt_amg_hierarchy(sim3opt_graph* g, int32_t capacity, int32_t* n_levels, int32_t* rows,
-                          int64_t* blocks, int32_t* aggregate_of_row) {
-  try {
-  if (!g || !n_levels || capacity < 0) return fail(g, SIM3OPT_ERR_ARG, "amg_hierarchy: bad argument");
-  // (the hierarchy sim3opt_initialize would build on ONE rank with the handle's options: row order,
-  // matching passes, dense-level cap and, with amg_virtual_ranks, the aggregation of an N-rank partition)
+// the hierarchy sim3opt_initialize would build on ONE rank with the handle's options: row order, matching passes,
+// dense-level cap and, with amg_virtual_ranks, the aggregation of an N-rank partition (host only)
+static int host_hierarchy(sim3opt_graph* g, const char* who, Structure& st, std::vector<AmgLevelHost>& levels) {
   sim3opt_options o = g->opt;
   apply_env_overrides(o);
-  Structure st;
   std::vector<int32_t> order;
   if (o.row_order == 1) locality_order(g->host, order);
   if (!build_structure(g->host, st, g->err, o.row_order == 1 ? &order : nullptr)) return SIM3OPT_ERR_STATE;
-  std::vector<AmgLevelHost> levels;
   std::string why;
   AmgBuildOptions bo;
   bo.max_coarsest = o.amg_coarsest;
@@ -779,9 +774,20 @@ int sim3opt_amg_hierarchy(sim3opt_graph* g, int32_t capacity, int32_t* n_levels,
     bo.row_begin = vbegin.data();
   }
   if (!build_amg_hierarchy(st.nb, st.rowptr.data(), st.colidx.data(), levels, why, bo)) {
-    g->err = "amg_hierarchy: " + why;
+    g->err = std::string(who) + ": " + why;
     return SIM3OPT_ERR_STATE;
   }
+  return SIM3OPT_OK;
+}
+
+int sim3opt_amg_hierarchy(sim3opt_graph* g, int32_t capacity, int32_t* n_levels, int32_t* rows,
+                          int64_t* blocks, int32_t* aggregate_of_row) {
+  try {
+  if (!g || !n_levels || capacity < 0) return fail(g, SIM3OPT_ERR_ARG, "amg_hierarchy: bad argument");
+  Structure st;
+  std::vector<AmgLevelHost> levels;
+  const int rc = host_hierarchy(g, "amg_hierarchy", st, levels);
+  if (rc) return rc;
   *n_levels = (int32_t)levels.size();
   for (int32_t l = 0; l < *n_levels && l < capacity; ++l) {
     if (rows) rows[l] = levels[l].nb;
@@ -792,6 +798,53 @@ int sim3opt_amg_hierarchy(sim3opt_graph* g, int32_t capacity, int32_t* n_levels,
   } catch (...) {  // (std::bad_alloc, std::length_error ...: nothing crosses the C boundary)
     return fail(g, SIM3OPT_ERR_ARG, "amg_hierarchy: out of host memory or internal error");
   }
+}
+
+int sim3opt_amg_level_structure(sim3opt_graph* g, int32_t level, int32_t* n_levels, int32_t* n_block_rows,
+                                int64_t* n_blocks, int32_t* rowptr, int32_t* colidx, int32_t* aggregate_of_row) {
+  try {
+  if (!g || level < 0) return fail(g, SIM3OPT_ERR_ARG, "amg_level_structure: bad argument");
+  Structure st;
+  std::vector<AmgLevelHost> levels;
+  const int rc = host_hierarchy(g, "amg_level_structure", st, levels);
+  if (rc) return rc;
+  if (n_levels) *n_levels = (int32_t)levels.size();
+  if (level >= (int32_t)levels.size()) return fail(g, SIM3OPT_ERR_ARG, "amg_level_structure: no such level");
+  const AmgLevelHost& L = levels[level];
+  if (n_block_rows) *n_block_rows = L.nb;
+  if (n_blocks) *n_blocks = L.nnzb;
+  const int32_t* rp = level == 0 ? st.rowptr.data() : L.rowptr.data();
+  const int32_t* ci = level == 0 ? st.colidx.data() : L.colidx.data();
+  if (rowptr) std::memcpy(rowptr, rp, sizeof(int32_t) * (size_t)(L.nb + 1));
+  if (colidx) std::memcpy(colidx, ci, sizeof(int32_t) * (size_t)L.nnzb);
+  if (aggregate_of_row && !L.agg.empty()) std::memcpy(aggregate_of_row, L.agg.data(), sizeof(int32_t) * (size_t)L.nb);
+  return SIM3OPT_OK;
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "amg_level_structure: out of host memory or internal error");
+  }
+}
+
+int sim3opt_amg_level_numbers(sim3opt_graph* g, double lambda, int32_t level, int32_t* rowptr, int32_t* colidx,
+                              double* values, float* values32, double* W, double* diagH, double* Minv, double* P) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "amg_level_numbers: call sim3opt_initialize first");
+  if (!std::isfinite(lambda) || lambda < 0.0) return fail(g, SIM3OPT_ERR_ARG, "amg_level_numbers: bad lambda");
+  return engine_amg_level_numbers(g->engine, lambda, level, rowptr, colidx, values, values32, W, diagH, Minv, P, g->err);
+}
+
+int sim3opt_amg_coarsest_inverse(sim3opt_graph* g, double lambda, double* Ainv) {
+  if (!g || !Ainv) return fail(g, SIM3OPT_ERR_ARG, "amg_coarsest_inverse: null argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "amg_coarsest_inverse: call sim3opt_initialize first");
+  if (!std::isfinite(lambda) || lambda < 0.0) return fail(g, SIM3OPT_ERR_ARG, "amg_coarsest_inverse: bad lambda");
+  return engine_amg_coarsest_inverse(g->engine, lambda, Ainv, g->err);
+}
+
+int sim3opt_preconditioner_apply(sim3opt_graph* g, int32_t prec, double lambda, int32_t nrhs, const double* r,
+                                 double* z) {
+  if (!g || !r || !z || nrhs < 1 || prec < 0 || prec > 2 || !std::isfinite(lambda) || lambda < 0.0)
+    return fail(g, SIM3OPT_ERR_ARG, "preconditioner_apply: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "preconditioner_apply: call sim3opt_initialize first");
+  return engine_precond_apply(g->engine, prec, lambda, nrhs, r, z, g->err);
 }
 
 int sim3opt_partition_plan(sim3opt_graph* g, int32_t world, int32_t locality, int32_t* vertex_of_row,

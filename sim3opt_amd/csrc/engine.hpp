@@ -47,6 +47,12 @@ int engine_solve(Engine* e, double lambda, double* x, int32_t* iters, double* re
 // blocks (row_a[q], row_b[q]) of (H + lambda I)^-1, H linearised at the current estimates (engine_direct.hip)
 int engine_marginals(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
                      std::string& err);
+// diagnostic read-outs of the preconditioners (one GPU; the solver's state is left as it was)
+int engine_amg_level_numbers(Engine* e, double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals,
+                             float* vals32, double* W, double* diagH, double* Minv, double* P, std::string& err);
+int engine_amg_coarsest_inverse(Engine* e, double lambda, double* Ainv, std::string& err);
+int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, const double* r, double* z,
+                         std::string& err);
 int engine_bench_spmv(Engine* e, int32_t reps, double* ms_mean, std::string& err);
 int engine_bench_stream(Engine* e, int32_t mode, int32_t reps, double* ms_mean, std::string& err);
 int engine_preconditioner(const Engine* e);

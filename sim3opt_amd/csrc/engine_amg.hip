@@ -462,4 +462,88 @@ int Engine::amg_apply(std::string& err) {
   return SIM3OPT_OK;
 }
 
+// ---- diagnostic read-outs (see engine_impl.hpp) ----
+int Engine::amg_numbers(double lambda, std::string& err) {
+  if (!linearized) {
+    err = "amg read-out: call sim3opt_linearize (or optimize) first";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (comm.world > 1) {
+    err = "amg read-out: one GPU only";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (!use_amg || amg.empty()) {
+    err = "amg read-out: this graph was not initialised with the multigrid preconditioner";
+    return SIM3OPT_ERR_STATE;
+  }
+  DevScalars sd, sh;
+  int rc = diag_begin(lambda, sd, sh, err);
+  if (rc) return rc;
+  if (amg_stale) rc = amg_setup(err);
+  if (rc == SIM3OPT_OK) {
+    amg_prepare(lambda);
+    rc = fetch_scalars(err);
+    if (rc == SIM3OPT_OK && h_sc->fail) {
+      err = "amg read-out: the set-up met a non-positive pivot";
+      rc = SIM3OPT_ERR_STATE;
+    }
+  }
+  std::string err2;
+  const int rc_end = diag_end(sd, sh, err2);
+  if (rc == SIM3OPT_OK && rc_end) {
+    err = err2;
+    rc = rc_end;
+  }
+  return rc;
+}
+
+int Engine::amg_level_readout(double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals,
+                              float* vals32, double* W, double* diagH, double* Minv, double* P, std::string& err) {
+  int rc = amg_numbers(lambda, err);
+  if (rc) return rc;
+  if (level < 0 || level >= (int32_t)amg.size() || ((W || diagH) && level == 0) || (P && level != 0)) {
+    err = "amg read-out: no such level, or an array this level does not have (W, diagH: coarse levels; P: level 0)";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (vals32 && !amg_fp32) {
+    err = "amg read-out: no FP32 copies (options.amg_fp32 = 0)";
+    return SIM3OPT_ERR_STATE;
+  }
+  const AmgLevel& L = amg[level];
+  const size_t nbl = (size_t)L.nb, nz = (size_t)L.nnzb;
+  HIPCHK(hipStreamSynchronize(stream));
+  if (rowptr) HIPCHK(hipMemcpy(rowptr, L.rowptr, sizeof(int32_t) * (nbl + 1), hipMemcpyDeviceToHost));
+  if (colidx) HIPCHK(hipMemcpy(colidx, L.colidx, sizeof(int32_t) * nz, hipMemcpyDeviceToHost));
+  if (vals) HIPCHK(hipMemcpy(vals, L.vals, sizeof(double) * 49 * nz, hipMemcpyDeviceToHost));
+  if (vals32) {  // pairs of blocks interleaved (f32_pair_index) -> nnzb x 49
+    std::vector<float> buf((size_t)98 * ((std::max<size_t>(nz, 1) + 1) / 2));
+    HIPCHK(hipMemcpy(buf.data(), L.vals32, sizeof(float) * buf.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nz; ++k)
+      for (int e = 0; e < 49; ++e) vals32[49 * k + e] = buf[f32_pair_index((int64_t)k, e)];
+  }
+  if (W) HIPCHK(hipMemcpy(W, L.W, sizeof(double) * 49 * nbl, hipMemcpyDeviceToHost));
+  if (diagH) HIPCHK(hipMemcpy(diagH, L.diagH, sizeof(double) * 49 * nbl, hipMemcpyDeviceToHost));
+  if (Minv) HIPCHK(hipMemcpy(Minv, L.Minv, sizeof(double) * 49 * nbl, hipMemcpyDeviceToHost));
+  if (P) HIPCHK(hipMemcpy(P, d_P, sizeof(double) * 49 * nbl, hipMemcpyDeviceToHost));
+  return SIM3OPT_OK;
+}
+
+int Engine::amg_coarsest_inverse(double lambda, double* Ainv, std::string& err) {
+  int rc = amg_numbers(lambda, err);
+  if (rc) return rc;
+  const size_t nc = (size_t)7 * amg.back().nb;
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipMemcpy(Ainv, d_Ainv, sizeof(double) * nc * nc, hipMemcpyDeviceToHost));
+  return SIM3OPT_OK;
+}
+
+int engine_amg_level_numbers(Engine* e, double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals,
+                             float* vals32, double* W, double* diagH, double* Minv, double* P, std::string& err) {
+  return e->amg_level_readout(lambda, level, rowptr, colidx, vals, vals32, W, diagH, Minv, P, err);
+}
+
+int engine_amg_coarsest_inverse(Engine* e, double lambda, double* Ainv, std::string& err) {
+  return e->amg_coarsest_inverse(lambda, Ainv, err);
+}
+
 }  // namespace sim3opt

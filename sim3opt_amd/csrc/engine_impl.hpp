@@ -486,6 +486,21 @@ class Engine {
   int pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res, bool* ok,
                   bool* chain_broke, std::string& err, int probe_budget = 0, bool* abandoned = nullptr);
 
+  // ---- diagnostic read-outs of the preconditioners (tests/test_gpu_preconditioners.py; one GPU only) ----
+  // They run the set-up a PCG solve runs and then put back what it wrote of the solver's state: the DevScalars on
+  // both sides.  Everything else they touch -- the level numbers for a lambda, d_Minv, the PCG vectors -- is
+  // rewritten by every pcg_attempt before it is read, and amg_setup is a function of the linearisation alone, so a
+  // solve or optimize() that follows is bit for bit the one without the read-out.
+  int diag_begin(double lambda, DevScalars& saved_d, DevScalars& saved_h, std::string& err);
+  int diag_end(const DevScalars& saved_d, const DevScalars& saved_h, std::string& err);
+  // amg_setup if stale, amg_prepare(lambda) -- as pcg_attempt -- and, unlike it, a failed pivot is SIM3OPT_ERR_STATE
+  int amg_numbers(double lambda, std::string& err);                                      // engine_amg.hip
+  int amg_level_readout(double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals, float* vals32,
+                        double* W, double* diagH, double* Minv, double* P, std::string& err);  // engine_amg.hip
+  int amg_coarsest_inverse(double lambda, double* Ainv, std::string& err);                // engine_amg.hip
+  // z[q] = M^-1 r[q] for nrhs right-hand sides with ONE set-up: the launches of a PCG iteration (engine_pcg.hip)
+  int precond_apply(int prec, double lambda, int32_t nrhs, const double* r, double* z, std::string& err);
+
   // ---- the iteration frame of LM, Gauss-Newton and dogleg (engine.hip) ----
   int iter_begin(sim3opt_iter_stats& T, double& chi, std::string& err);  // stamp 0, chi2 (cached or not), linearise
   void iter_end(sim3opt_iter_stats& T, double chi, std::vector<sim3opt_iter_stats>& stats);  // cache chi, record T

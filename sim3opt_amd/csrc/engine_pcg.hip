@@ -453,6 +453,103 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
   return SIM3OPT_OK;
 }
 
+// ---- diagnostic read-outs (see engine_impl.hpp) ----
+int Engine::diag_begin(double lambda, DevScalars& saved_d, DevScalars& saved_h, std::string& err) {
+  HIPCHK(hipStreamSynchronize(stream));
+  saved_h = *h_sc;
+  HIPCHK(hipMemcpy(&saved_d, d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
+  // the PCG fields as pcg_attempt sets them: not done (level-0 launches test it), no failure yet, this damping
+  DevScalars s = saved_d;
+  s.rz[0] = s.rz[1] = s.alpha[0] = s.alpha[1] = s.rz0 = 0.0;
+  s.iter = 0;
+  s.done = s.stop = s.fail = 0;
+  s.lambda = lambda;
+  HIPCHK(hipMemcpy(d_sc, &s, sizeof(DevScalars), hipMemcpyHostToDevice));
+  return SIM3OPT_OK;
+}
+
+int Engine::diag_end(const DevScalars& saved_d, const DevScalars& saved_h, std::string& err) {
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipMemcpy(d_sc, &saved_d, sizeof(DevScalars), hipMemcpyHostToDevice));
+  *h_sc = saved_h;
+  return SIM3OPT_OK;
+}
+
+int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r, double* z, std::string& err) {
+  if (!linearized) {
+    err = "precond_apply: call sim3opt_linearize (or optimize) first";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (comm.world > 1) {
+    err = "precond_apply: one GPU only";
+    return SIM3OPT_ERR_STATE;
+  }
+  if ((prec == 2 && !use_amg) || (prec == 1 && !use_chain)) {
+    err = "precond_apply: this graph was not initialised with that preconditioner";
+    return SIM3OPT_ERR_STATE;
+  }
+  const int nloc = r1 - r0;
+  const int gv = grid_for((nloc + 8) / 9, 4);
+  const int nseg = (nloc + chain_seg - 1) / chain_seg;
+  DevScalars sd, sh;
+  int rc = diag_begin(lambda, sd, sh, err);
+  if (rc) return rc;
+  auto body = [&]() -> int {
+    if (prec == 2) {
+      if (amg_stale) {
+        int rc2 = amg_setup(err);
+        if (rc2) return rc2;
+      }
+      amg_prepare(lambda);
+    } else if (prec == 1) {
+      hipLaunchKernelGGL(k_chain_factor, dim3(std::max(1, (nseg + 63) / 64)), dim3(64), 0, stream, r0, r1, chain_seg,
+                         d_rowptr, d_vals, d_sub_first, d_sub_cnt, lambda, d_Minv, d_Gm, d_sc);
+    } else {
+      hipLaunchKernelGGL(k_jacobi, dim3(std::max(1, (nloc + WG - 1) / WG)), dim3(WG), 0, stream, r0, r1, d_rowptr,
+                         d_vals, lambda, d_Minv, d_sc, 1.0, (const double*)nullptr, (const double*)nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    int rc2 = fetch_scalars(err);
+    if (rc2) return rc2;
+    if (h_sc->fail) {
+      err = "precond_apply: the set-up met a non-positive pivot";
+      return SIM3OPT_ERR_STATE;
+    }
+    for (int32_t q = 0; q < nrhs; ++q) {
+      // r -> d_r and d_z = Minv_0 r, the arithmetic k_pcg_step leaves them with (d_q: staging, a solve rewrites it)
+      HIPCHK(hipMemcpyAsync(d_q, r + (size_t)q * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
+      hipLaunchKernelGGL(k_pcg_init, dim3(gv), dim3(WG), 0, stream, r0, r1, (const double*)d_q,
+                         prec == 1 ? (const double*)nullptr : (const double*)d_Minv, d_x, d_r, d_z, d_p, d_s);
+      const double* res = d_z;
+      if (prec == 1) {
+        hipLaunchKernelGGL(k_chain_apply, dim3(grid_for(nseg, 4)), dim3(WG), 0, stream, r0, r1, chain_seg, d_Minv, d_Gm,
+                           d_r, d_z, (const DevScalars*)d_sc);
+      } else if (prec == 2) {
+        rc2 = amg_apply(err);
+        if (rc2) return rc2;
+        res = d_az;
+      }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(stream));
+      HIPCHK(hipMemcpy(z + (size_t)q * n, res, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  std::string err2;
+  const int rc_end = diag_end(sd, sh, err2);
+  if (rc == SIM3OPT_OK && rc_end) {
+    err = err2;
+    rc = rc_end;
+  }
+  return rc;
+}
+
+int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, const double* r, double* z,
+                         std::string& err) {
+  return e->precond_apply(prec, lambda, nrhs, r, z, err);
+}
+
 int engine_bench_spmv(Engine* e, int32_t reps, double* ms_mean, std::string& err) {
   if (!e->linearized) {
     err = "bench_spmv: call sim3opt_linearize (or optimize) first";

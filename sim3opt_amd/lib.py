@@ -193,6 +193,11 @@ SYMBOLS = {
     "sim3opt_bench_stream": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),
     "sim3opt_preconditioner_in_use": (C.c_int, [_vp]),
     "sim3opt_amg_hierarchy": (C.c_int, [_vp, C.c_int32, _ip, _ip, _vp, _ip]),
+    "sim3opt_amg_level_structure": (C.c_int, [_vp, C.c_int32, _ip, _ip, C.POINTER(C.c_int64), _ip, _ip, _ip]),
+    "sim3opt_amg_level_numbers": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp, C.POINTER(C.c_float), _dp,
+                                            _dp, _dp, _dp]),
+    "sim3opt_amg_coarsest_inverse": (C.c_int, [_vp, C.c_double, _dp]),
+    "sim3opt_preconditioner_apply": (C.c_int, [_vp, C.c_int32, C.c_double, C.c_int32, _dp, _dp]),
     "sim3opt_linear_solver_in_use": (C.c_int, [_vp]),
     "sim3opt_direct_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _ip,
                                       _ip, _ip, _ip, _ip, _ip, _ip]),
@@ -730,6 +735,64 @@ class Graph:
         self._chk(self._L.sim3opt_amg_hierarchy(self._g, 16, C.byref(nl), _p(rows, _ip),
                                                 blocks.ctypes.data_as(C.c_void_p), _p(agg, _ip)))
         return rows[:nl.value].copy(), blocks[:nl.value].copy(), agg
+
+    # ---- diagnostic read-outs of the preconditioners (tests/test_gpu_preconditioners.py) ----
+    def amg_structure(self):
+        """Every level of the hierarchy `amg_hierarchy` describes, host only: a list of dict(nb, nnzb, rowptr, colidx,
+        agg), agg = row of the next level for each row (None on the coarsest level)."""
+        out = []
+        nl = C.c_int32(1)
+        level = 0
+        while level < nl.value:
+            nb, nnzb = C.c_int32(), C.c_int64()
+            self._chk(self._L.sim3opt_amg_level_structure(self._g, level, C.byref(nl), C.byref(nb), C.byref(nnzb),
+                                                          None, None, None))
+            rowptr = np.zeros(nb.value + 1, dtype=np.int32)
+            colidx = np.zeros(max(nnzb.value, 1), dtype=np.int32)
+            agg = np.full(max(nb.value, 1), -1, dtype=np.int32)
+            self._chk(self._L.sim3opt_amg_level_structure(self._g, level, None, None, None, _p(rowptr, _ip),
+                                                          _p(colidx, _ip), _p(agg, _ip)))
+            out.append(dict(nb=nb.value, nnzb=nnzb.value, rowptr=rowptr, colidx=colidx[:nnzb.value],
+                            agg=agg[:nb.value] if level + 1 < nl.value else None))
+            level += 1
+        return out
+
+    def amg_level_numbers(self, lam, level, nb, nnzb, fp32=True):
+        """Numbers of one level after the set-up for `lam` (nb, nnzb: the level's sizes, from amg_structure): dict of
+        rowptr, colidx, vals [k, r, c], vals32 (float32, [k, r, c]; None without fp32), Minv [i, r, c], and W, diagH
+        [i, r, c] on coarse levels / P [i, r, c] on level 0."""
+        rowptr = np.zeros(nb + 1, dtype=np.int32)
+        colidx = np.zeros(max(nnzb, 1), dtype=np.int32)
+        vals = np.zeros((max(nnzb, 1), 49))
+        v32 = np.zeros((max(nnzb, 1), 49), dtype=np.float32) if fp32 else None
+        Minv = np.zeros((nb, 49))
+        W = np.zeros((nb, 49)) if level > 0 else None
+        dH = np.zeros((nb, 49)) if level > 0 else None
+        P = np.zeros((nb, 49)) if level == 0 else None
+        fp = C.POINTER(C.c_float)
+        self._chk(self._L.sim3opt_amg_level_numbers(
+            self._g, float(lam), int(level), _p(rowptr, _ip), _p(colidx, _ip), _p(vals, _dp),
+            v32.ctypes.data_as(fp) if fp32 else None, _p(W, _dp) if W is not None else None,
+            _p(dH, _dp) if dH is not None else None, _p(Minv, _dp), _p(P, _dp) if P is not None else None))
+        cm = lambda a: None if a is None else a.reshape(-1, 7, 7).transpose(0, 2, 1).copy()  # column-major blocks
+        return dict(rowptr=rowptr, colidx=colidx[:nnzb], vals=cm(vals[:nnzb]), vals32=cm(v32[:nnzb]) if fp32 else None,
+                    Minv=Minv.reshape(-1, 7, 7).copy(), W=cm(W), diagH=cm(dH), P=cm(P))
+
+    def amg_coarsest_inverse(self, lam, nb_coarsest):
+        """Dense inverse of the coarsest level for `lam`, (7 nb_c, 7 nb_c)."""
+        n = 7 * int(nb_coarsest)
+        A = np.zeros((n, n))
+        self._chk(self._L.sim3opt_amg_coarsest_inverse(self._g, float(lam), _p(A, _dp)))
+        return A
+
+    def preconditioner_apply(self, prec, lam, r):
+        """z = M^-1 r for prec 0 block-Jacobi / 1 chain segments / 2 multigrid; r: (7 nb,) or (nrhs, 7 nb); one
+        set-up per call."""
+        r2 = _f64(np.atleast_2d(r))
+        z = np.zeros_like(r2)
+        self._chk(self._L.sim3opt_preconditioner_apply(self._g, int(prec), float(lam), r2.shape[0], _p(r2, _dp),
+                                                       _p(z, _dp)))
+        return z.reshape(np.shape(r))
 
     def partition_plan(self, world, locality=True):
         """(vertex of every block row, row_begin, boundary rows per rank, cut edges); host only."""

@@ -494,12 +494,15 @@ def test_huber_and_information_lm():
 
 
 def test_three_level_multigrid_lm_matches_exact_oracle(monkeypatch):
-    """The coarse-level kernels under the oracle (missing #3): a Manhattan graph of
-    1500 vertices / 15 000 edges whose hierarchy has THREE levels (1499 -> 174 -> 20 rows with the
+    """An LM run whose PCG goes through a THREE-level cycle, against the oracle (missing #3): a
+    Manhattan graph of 1500 vertices / 15 000 edges (1499 -> 174 -> 20 rows with the
     dense level capped at 64 rows), so that level 1 runs the residual pass, the fused
     prolongation + smoothing pass (`k_spmv_span<..., 3, float>`), the coarse restriction
     (`k_amg_restrict`), FP32 block copies and over-correction -- everything config 3's four-level
-    cycle runs below level 0 -- while the oracle's exact LDL^T still finishes in ~25 s.  delta = 1e-6,
+    cycle runs below level 0 -- while the oracle's exact LDL^T still finishes in ~25 s.  What this pins is the
+    SYSTEM being solved and the LM around it: CG reaches the same x with any symmetric positive definite M^-1, so a
+    coarse-level kernel that is subtly wrong only costs iterations here.  The kernels themselves are compared with a
+    long-double restatement, operator by operator, in test_gpu_preconditioners.py.  delta = 1e-6,
     PCG tolerance 1e-12: chi2 trace equal to 1e-8 relative, identical trial counts, trajectory RMSE
     < 1e-4 (measured 9e-6 on the 3000-vertex run of scripts/gpu_parity_3000.py)."""
     monkeypatch.setenv("SIM3OPT_AMG_COARSEST", "64")
