@@ -1,5 +1,6 @@
 // amg_kernels.hpp -- device side of the aggregation-multigrid preconditioner (included by
-// engine.hip after DevScalars / load_sim3; structure from amg.cpp).
+// engine_amg.hip only, after DevScalars / load_sim3; structure from amg.cpp).  The set-up kernels work on the
+// hierarchy; the cycle's transfer kernels are templates on the number of right-hand sides (below).
 //
 // Level 0 is the LM system itself; level l+1 = P_l^T (H_l) P_l (Galerkin) with
 //   P_0 = block rows Ad(S_v) of the aggregate's members (the near-kernel of a pose-graph Hessian is
@@ -173,47 +174,77 @@ __global__ __launch_bounds__(WG) void k_amg_wsum(int nc, const int32_t* __restri
   if (lane < 49) Wc[(size_t)49 * a + lane] = acc;
 }
 
+// ---- the cycle's transfer kernels, for K right-hand sides at once ----
+// K = 1 is the one-system kernel (the stride terms fold away).  K > 1 (the rejected trials of one LM iteration,
+// solved together: Engine::pcg_batch): P, the aggregation and the index work are shared, vectors and inverses of
+// system s live at base + s * stride; per system the operations and their order are those of K = 1, so the K
+// results are bit for bit K one-system results (asserted in tests/test_gpu_parity.py).  gridDim.y > 1 (coarse
+// levels: launch-latency-bound): every slice of the grid takes K of the systems.
+
 // Coarse levels (piecewise-constant prolongation): r_c[a] = sum over members i of t_f[i]; then
 // x_c[a] = Minv_c[a] r_c[a] (first smoothing step of the coarser level from a zero guess).
 // 63 lanes = 9 aggregates x 7 entries.
+template <int K>
 __global__ __launch_bounds__(WG) void k_amg_restrict(int a_lo, int nc, const int32_t* __restrict__ mptr,
                                                      const int32_t* __restrict__ mem,
                                                      const double* __restrict__ t_f,
                                                      double* __restrict__ r_c,
                                                      const double* __restrict__ Minv_c,
-                                                     double* __restrict__ x_c) {
+                                                     double* __restrict__ x_c, int64_t vs_f, int64_t vs_c,
+                                                     int64_t ms_c) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int sub = lane / 7, rr = lane % 7, base = lane - rr;
+  if (gridDim.y > 1) {
+    const size_t s0 = (size_t)blockIdx.y * K;
+    t_f += s0 * vs_f;
+    r_c += s0 * vs_c;
+    x_c += s0 * vs_c;
+    if (Minv_c) Minv_c += s0 * ms_c;
+  }
   for (int a0 = a_lo + (blockIdx.x * 4 + wave) * 9; a0 < nc; a0 += gridDim.x * 36) {  // aggregates [a_lo, nc)
     const int a = a0 + sub;
     const bool act = lane < 63 && a < nc;
     const int e0 = act ? mptr[a] : 0, e1 = act ? mptr[a + 1] : 0;
-    double acc = 0.0;
-    int e = e0;
-    for (; e + 3 < e1; e += 4) {  // four members in flight
-      const int i0 = mem[e], i1 = mem[e + 1], i2 = mem[e + 2], i3 = mem[e + 3];
-      const double v0 = t_f[(size_t)7 * i0 + rr], v1 = t_f[(size_t)7 * i1 + rr];
-      const double v2 = t_f[(size_t)7 * i2 + rr], v3 = t_f[(size_t)7 * i3 + rr];
-      acc += (v0 + v1) + (v2 + v3);
-    }
-    for (; e < e1; ++e) acc += t_f[(size_t)7 * mem[e] + rr];
-    if (act) r_c[(size_t)7 * a + rr] = acc;
-    if (Minv_c) {
-      double xv = 0.0;
 #pragma unroll
-      for (int cc = 0; cc < 7; ++cc) {
-        const double rc = __shfl(acc, base + cc);
-        if (act) xv += Minv_c[(size_t)49 * a + 7 * rr + cc] * rc;
+    for (int s = 0; s < K; ++s) {
+      const double* tf = t_f + (size_t)s * vs_f;
+      double acc = 0.0;
+      int e = e0;
+      for (; e + 3 < e1; e += 4) {  // four members in flight
+        const int i0 = mem[e], i1 = mem[e + 1], i2 = mem[e + 2], i3 = mem[e + 3];
+        const double v0 = tf[(size_t)7 * i0 + rr], v1 = tf[(size_t)7 * i1 + rr];
+        const double v2 = tf[(size_t)7 * i2 + rr], v3 = tf[(size_t)7 * i3 + rr];
+        acc += (v0 + v1) + (v2 + v3);
       }
-      if (act) x_c[(size_t)7 * a + rr] = xv;
+      for (; e < e1; ++e) acc += tf[(size_t)7 * mem[e] + rr];
+      if (act) r_c[(size_t)s * vs_c + (size_t)7 * a + rr] = acc;
+      if (Minv_c) {
+        double xv = 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 7; ++cc) {
+          const double rc = __shfl(acc, base + cc);
+          if (act) xv += Minv_c[(size_t)s * ms_c + (size_t)49 * a + 7 * rr + cc] * rc;
+        }
+        if (act) x_c[(size_t)s * vs_c + (size_t)7 * a + rr] = xv;
+      }
     }
   }
+}
+
+// a launch that tests `done` returns at once when all of its K systems have finished
+template <int K>
+__device__ inline bool all_done(const DevScalars* __restrict__ sc) {
+  bool done = sc != nullptr;
+#pragma unroll
+  for (int s = 0; s < K; ++s) done = done && sc[s].done;
+  return done;
 }
 
 // Level-0 restriction, one wavefront per aggregate: lane (m, c) = entry l49 = m + 7c of P_i (one
 // coalesced 392-byte read per member), r_c[c] = sum_i sum_m P_i[m][c] t_i[m]; then the coarse
 // level's first smoothing step x_c = Minv_c r_c with Minv_c read the same way.
+template <int K>
 __global__ __launch_bounds__(WG) void k_amg_restrict0(int a_lo, int nc, const int32_t* __restrict__ mptr,
                                                       const int32_t* __restrict__ mem,
                                                       const double* __restrict__ P,
@@ -221,30 +252,38 @@ __global__ __launch_bounds__(WG) void k_amg_restrict0(int a_lo, int nc, const in
                                                       double* __restrict__ r_c,
                                                       const double* __restrict__ Minv_c,
                                                       double* __restrict__ x_c,
-                                                      const DevScalars* __restrict__ sc) {
-  if (sc && sc->done) return;
+                                                      const DevScalars* __restrict__ sc, int64_t vs_f, int64_t vs_c,
+                                                      int64_t ms_c) {
+  if (all_done<K>(sc)) return;
   const int lane = threadIdx.x & 63;
   const int a = a_lo + __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));  // [a_lo, nc)
   if (a >= nc) return;
   const int l49 = lane < 49 ? lane : lane - 49;
   const int m = l49 % 7, c = l49 / 7;
-  double acc = 0.0;
+  double acc[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) acc[s] = 0.0;
   const int e0 = mptr[a], e1 = mptr[a + 1];
   for (int e = e0; e < e1; ++e) {
     const int i = mem[e];  // (multi-GPU: an aggregate's members all belong to the rank that owns it)
-    acc += P[(size_t)49 * i + l49] * t_f[(size_t)7 * i + m];
+    const double pv = P[(size_t)49 * i + l49];
+#pragma unroll
+    for (int s = 0; s < K; ++s) acc[s] += pv * t_f[(size_t)s * vs_f + (size_t)7 * i + m];
   }
-  // sum over m inside each group of 7 lanes (fixed c): lanes 7c .. 7c+6
-  double rc = 0.0;
 #pragma unroll
-  for (int q = 0; q < 7; ++q) rc += __shfl(acc, 7 * c + q);
-  if (lane < 49 && m == 0) r_c[(size_t)7 * a + c] = rc;
-  if (Minv_c) {  // x_c[m] = sum_c Minv[m][c] r_c[c]; lane (m, c) holds r_c[c]
-    const double pr = Minv_c[(size_t)49 * a + l49] * rc;  // symmetric: entry (m, c)
-    double xv = pr;
+  for (int s = 0; s < K; ++s) {
+    // sum over m inside each group of 7 lanes (fixed c): lanes 7c .. 7c+6
+    double rc = 0.0;
 #pragma unroll
-    for (int q = 1; q < 7; ++q) xv += __shfl(pr, m + 7 * ((c + q) % 7));
-    if (lane < 7) x_c[(size_t)7 * a + lane] = xv;
+    for (int q = 0; q < 7; ++q) rc += __shfl(acc[s], 7 * c + q);
+    if (lane < 49 && m == 0) r_c[(size_t)s * vs_c + (size_t)7 * a + c] = rc;
+    if (Minv_c) {  // x_c[m] = sum_c Minv[m][c] r_c[c]; lane (m, c) holds r_c[c]
+      const double pr = Minv_c[(size_t)s * ms_c + (size_t)49 * a + l49] * rc;  // symmetric: entry (m, c)
+      double xv = pr;
+#pragma unroll
+      for (int q = 1; q < 7; ++q) xv += __shfl(pr, m + 7 * ((c + q) % 7));
+      if (lane < 7) x_c[(size_t)s * vs_c + (size_t)7 * a + lane] = xv;
+    }
   }
 }
 
@@ -269,33 +308,51 @@ __global__ __launch_bounds__(WG) void k_amg_bjapply(int nb, const double* __rest
   }
 }
 
-// x_out[i] = x_in[i] + P_i x_c[agg[i]]   (x_out may be x_in)
+// x_out[i] = x_in[i] + scale P_i x_c[agg[i]]   (x_out may be x_in; HASP false: P_i = I)
 // rows [row_lo, row_hi), or -- with a list -- rows list[row_lo .. row_hi)
-template <bool HASP>
+template <bool HASP, int K>
 __global__ __launch_bounds__(WG) void k_amg_prolong(int row_lo, int row_hi, const int32_t* __restrict__ list,
                                                     const int32_t* __restrict__ agg,
                                                     const double* __restrict__ P,
                                                     const double* __restrict__ x_c,
                                                     const double* x_in, double* x_out,
-                                                    const DevScalars* __restrict__ sc, double scale) {
-  if (sc && sc->done) return;
+                                                    const DevScalars* __restrict__ sc, double scale, int64_t vs_f,
+                                                    int64_t vs_c) {
+  if (all_done<K>(sc)) return;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int sub = lane / 7, rr = lane % 7, base = lane - rr;
   for (int row0 = row_lo + (blockIdx.x * 4 + wave) * 9; row0 < row_hi; row0 += gridDim.x * 36) {
     const bool act = lane < 63 && row0 + sub < row_hi;
     const int row = act ? (list ? list[row0 + sub] : row0 + sub) : 0;
-    const double xc = act ? x_c[(size_t)7 * agg[row] + rr] : 0.0;
-    double add = xc;
-    if (HASP) {
-      add = 0.0;
+    const int ag = act ? agg[row] : 0;
+    // several systems share the row's seven entries of P: held in registers across them (one system reads
+    // them where it uses them)
+    constexpr bool HOIST = HASP && K > 1;
+    double pm[HOIST ? 7 : 1];
+    if constexpr (HOIST) {
 #pragma unroll
-      for (int m = 0; m < 7; ++m) {
-        const double xm = __shfl(xc, base + m);
-        if (act) add += P[(size_t)49 * row + rr + 7 * m] * xm;
-      }
+      for (int m = 0; m < 7; ++m) pm[m] = act ? P[(size_t)49 * row + rr + 7 * m] : 0.0;
     }
-    if (act) x_out[(size_t)7 * row + rr] = x_in[(size_t)7 * row + rr] + scale * add;
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      const double xc = act ? x_c[(size_t)s * vs_c + (size_t)7 * ag + rr] : 0.0;
+      double add = xc;
+      if constexpr (HASP) {
+        add = 0.0;
+#pragma unroll
+        for (int m = 0; m < 7; ++m) {
+          const double xm = __shfl(xc, base + m);
+          if constexpr (HOIST) {
+            if (act) add += pm[m] * xm;
+          } else {
+            if (act) add += P[(size_t)49 * row + rr + 7 * m] * xm;
+          }
+        }
+      }
+      const size_t j = (size_t)s * vs_f + (size_t)7 * row + rr;
+      if (act) x_out[j] = x_in[j] + scale * add;
+    }
   }
 }
 
@@ -532,25 +589,34 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2))) void k_
 }
 
 // x = Ainv r on the coarsest level: a wavefront per row, lanes along the row (coalesced; r is a few
-// KB and stays in cache)
+// KB and stays in cache).  Every system has its own dense inverse: its damping is inside.
+template <int K>
 __global__ __launch_bounds__(WG) void k_amg_dense_apply(int n, const double* __restrict__ Ainv,
                                                         const double* __restrict__ r,
-                                                        double* __restrict__ x,
-                                                        const DevScalars* __restrict__ sc) {
-  if (sc && sc->done) return;
+                                                        double* __restrict__ x, int64_t as, int64_t vs) {
   const int lane = threadIdx.x & 63;
+  if (gridDim.y > 1) {
+    const size_t s0 = (size_t)blockIdx.y * K;
+    Ainv += s0 * as;
+    r += s0 * vs;
+    x += s0 * vs;
+  }
   for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
-    const double* row = Ainv + (size_t)i * n;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;  // four loads in flight per lane
-    int j = lane;
-    for (; j + 192 < n; j += 256) {
-      const double m0 = row[j], m1 = row[j + 64], m2 = row[j + 128], m3 = row[j + 192];
-      a0 += m0 * r[j]; a1 += m1 * r[j + 64]; a2 += m2 * r[j + 128]; a3 += m3 * r[j + 192];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      const double* row = Ainv + (size_t)s * as + (size_t)i * n;
+      const double* rs = r + (size_t)s * vs;
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;  // four loads in flight per lane
+      int j = lane;
+      for (; j + 192 < n; j += 256) {
+        const double m0 = row[j], m1 = row[j + 64], m2 = row[j + 128], m3 = row[j + 192];
+        a0 += m0 * rs[j]; a1 += m1 * rs[j + 64]; a2 += m2 * rs[j + 128]; a3 += m3 * rs[j + 192];
+      }
+      for (; j < n; j += 64) a0 += row[j] * rs[j];
+      double acc = (a0 + a1) + (a2 + a3);
+      acc = wave_sum(acc);
+      if (lane == 0) x[(size_t)s * vs + i] = acc;
     }
-    for (; j < n; j += 64) a0 += row[j] * r[j];
-    double acc = (a0 + a1) + (a2 + a3);
-    acc = wave_sum(acc);
-    if (lane == 0) x[i] = acc;
   }
 }
 
@@ -560,5 +626,3 @@ __global__ __launch_bounds__(WG) void k_to_f32(size_t n, const double* __restric
   for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG)
     dst[f32_pair_index((int64_t)(i / 49), (int)(i % 49))] = (float)src[i];
 }
-
-

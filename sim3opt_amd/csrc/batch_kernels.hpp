@@ -1,13 +1,13 @@
-// batch_kernels.hpp -- the PCG loop for K right-hand sides at once (included by engine_batch.hip only, inside
-// namespace sim3opt, after spmv_kernel.hpp): the rejected trials of one LM iteration solve
+// batch_kernels.hpp -- the vector kernels of the PCG loop for K right-hand sides at once (included by
+// engine_batch.hip only, inside namespace sim3opt): the rejected trials of one LM iteration solve
 // (H + lambda_k I) x_k = b for a KNOWN sequence lambda_k (g2o's OptimizationAlgorithmLevenberg: lambda *= nu,
-// nu *= 2 after every rejection), so after the first rejection the next K systems are solved together --
-// ONE pass over the matrix blocks for K vectors, K vectors per coarse launch -- and the trials are then
-// evaluated in g2o's order.  What LinearSolverEigen does K times in a row (kitti_surf.cpp:553-554, 675).
-// Every kernel here performs, per system, the operations of its one-system counterpart in the same order:
-// the K solutions are bit for bit those of K sequential solves (asserted in tests/test_gpu_parity.py).
-// Vectors of system s live at base + s * stride (BatchStrides, spmv_kernel.hpp, where the K-system SpMV lives:
-// the one-system kernel is its K = 1 instantiation).
+// nu *= 2 after every rejection), so after the first rejection the next K systems are solved together and the
+// trials are then evaluated in g2o's order.  What LinearSolverEigen does K times in a row (kitti_surf.cpp:553-554,
+// 675).  Every kernel here performs, per system, the operations of its one-system counterpart (pcg_kernels.hpp) in
+// the same order: the K solutions are bit for bit those of K sequential solves (asserted in
+// tests/test_gpu_parity.py).  Vectors of system s live at base + s * stride (BatchStrides, spmv_kernel.hpp).
+// Everything else of a batched iteration has no twin: the SpMV (spmv_kernel.hpp) and the multigrid cycle's
+// transfer kernels (amg_kernels.hpp) are templates on K whose one-system kernel is the K = 1 instantiation.
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -150,169 +150,6 @@ __global__ __launch_bounds__(WG) void k_pcg_step_k(int r0, int r1, int par, int 
       const int itn = it + 1;
       sc[s].iter = itn;
       if (itn >= sc[s].max_iter) sc[s].stop = 1;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// multigrid transfer kernels for K systems (k_amg_restrict0 / k_amg_restrict / k_amg_prolong<true> /
-// k_amg_dense_apply per system; P and the aggregation are shared)
-// ------------------------------------------------------------------------------------------
-template <int K>
-__global__ __launch_bounds__(WG) void k_amg_restrict0_k(int nc, const int32_t* __restrict__ mptr,
-                                                        const int32_t* __restrict__ mem,
-                                                        const double* __restrict__ P,
-                                                        const double* __restrict__ t_f, double* __restrict__ r_c,
-                                                        const double* __restrict__ Minv_c, double* __restrict__ x_c,
-                                                        const DevScalars* __restrict__ sc, int64_t vs_f, int64_t vs_c,
-                                                        int64_t ms_c) {
-  if (sc) {
-    bool all_done = true;
-#pragma unroll
-    for (int s = 0; s < K; ++s) all_done = all_done && sc[s].done;
-    if (all_done) return;
-  }
-  const int lane = threadIdx.x & 63;
-  const int a = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-  if (a >= nc) return;
-  const int l49 = lane < 49 ? lane : lane - 49;
-  const int m = l49 % 7, c = l49 / 7;
-  double acc[K];
-#pragma unroll
-  for (int s = 0; s < K; ++s) acc[s] = 0.0;
-  const int e0 = mptr[a], e1 = mptr[a + 1];
-  for (int e = e0; e < e1; ++e) {
-    const int i = mem[e];
-    const double pv = P[(size_t)49 * i + l49];
-#pragma unroll
-    for (int s = 0; s < K; ++s) acc[s] += pv * t_f[(size_t)s * vs_f + (size_t)7 * i + m];
-  }
-#pragma unroll
-  for (int s = 0; s < K; ++s) {
-    double rc = 0.0;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) rc += __shfl(acc[s], 7 * c + q);
-    if (lane < 49 && m == 0) r_c[(size_t)s * vs_c + (size_t)7 * a + c] = rc;
-    if (Minv_c) {
-      const double pr = Minv_c[(size_t)s * ms_c + (size_t)49 * a + l49] * rc;
-      double xv = pr;
-#pragma unroll
-      for (int q = 1; q < 7; ++q) xv += __shfl(pr, m + 7 * ((c + q) % 7));
-      if (lane < 7) x_c[(size_t)s * vs_c + (size_t)7 * a + lane] = xv;
-    }
-  }
-}
-
-template <int K>
-__global__ __launch_bounds__(WG) void k_amg_restrict_k(int nc, const int32_t* __restrict__ mptr,
-                                                       const int32_t* __restrict__ mem,
-                                                       const double* __restrict__ t_f, double* __restrict__ r_c,
-                                                       const double* __restrict__ Minv_c, double* __restrict__ x_c,
-                                                       int64_t vs_f, int64_t vs_c, int64_t ms_c) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int sub = lane / 7, rr = lane % 7, base = lane - rr;
-  if (gridDim.y > 1) {  // every slice of the grid takes K of the systems
-    const size_t s0 = (size_t)blockIdx.y * K;
-    t_f += s0 * vs_f;
-    r_c += s0 * vs_c;
-    x_c += s0 * vs_c;
-    if (Minv_c) Minv_c += s0 * ms_c;
-  }
-  for (int a0 = (blockIdx.x * 4 + wave) * 9; a0 < nc; a0 += gridDim.x * 36) {
-    const int a = a0 + sub;
-    const bool act = lane < 63 && a < nc;
-    const int e0 = act ? mptr[a] : 0, e1 = act ? mptr[a + 1] : 0;
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-      const double* tf = t_f + (size_t)s * vs_f;
-      double acc = 0.0;
-      int e = e0;
-      for (; e + 3 < e1; e += 4) {  // four members in flight (the one-system kernel's order of summation)
-        const int i0 = mem[e], i1 = mem[e + 1], i2 = mem[e + 2], i3 = mem[e + 3];
-        const double v0 = tf[(size_t)7 * i0 + rr], v1 = tf[(size_t)7 * i1 + rr];
-        const double v2 = tf[(size_t)7 * i2 + rr], v3 = tf[(size_t)7 * i3 + rr];
-        acc += (v0 + v1) + (v2 + v3);
-      }
-      for (; e < e1; ++e) acc += tf[(size_t)7 * mem[e] + rr];
-      if (act) r_c[(size_t)s * vs_c + (size_t)7 * a + rr] = acc;
-      if (Minv_c) {
-        double xv = 0.0;
-#pragma unroll
-        for (int cc = 0; cc < 7; ++cc) {
-          const double rc = __shfl(acc, base + cc);
-          if (act) xv += Minv_c[(size_t)s * ms_c + (size_t)49 * a + 7 * rr + cc] * rc;
-        }
-        if (act) x_c[(size_t)s * vs_c + (size_t)7 * a + rr] = xv;
-      }
-    }
-  }
-}
-
-// x_out[i] = x_in[i] + scale P_i x_c[agg[i]] (level 0), K systems
-template <int K>
-__global__ __launch_bounds__(WG) void k_amg_prolong0_k(int nb, const int32_t* __restrict__ agg,
-                                                       const double* __restrict__ P, const double* __restrict__ x_c,
-                                                       const double* x_in, double* x_out,
-                                                       const DevScalars* __restrict__ sc, double scale, int64_t vs_f,
-                                                       int64_t vs_c) {
-  if (sc) {
-    bool all_done = true;
-#pragma unroll
-    for (int s = 0; s < K; ++s) all_done = all_done && sc[s].done;
-    if (all_done) return;
-  }
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int sub = lane / 7, rr = lane % 7, base = lane - rr;
-  for (int row0 = (blockIdx.x * 4 + wave) * 9; row0 < nb; row0 += gridDim.x * 36) {
-    const int row = row0 + sub;
-    const bool act = lane < 63 && row < nb;
-    const int ag = act ? agg[row] : 0;
-    double pm[7];
-#pragma unroll
-    for (int m = 0; m < 7; ++m) pm[m] = act ? P[(size_t)49 * row + rr + 7 * m] : 0.0;
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-      const double xc = act ? x_c[(size_t)s * vs_c + (size_t)7 * ag + rr] : 0.0;
-      double add = 0.0;
-#pragma unroll
-      for (int m = 0; m < 7; ++m) {
-        const double xm = __shfl(xc, base + m);
-        if (act) add += pm[m] * xm;
-      }
-      if (act) x_out[(size_t)s * vs_f + (size_t)7 * row + rr] = x_in[(size_t)s * vs_f + (size_t)7 * row + rr] + scale * add;
-    }
-  }
-}
-
-// x_s = Ainv_s r_s on the coarsest level (every system has its own dense inverse: its damping is inside)
-template <int K>
-__global__ __launch_bounds__(WG) void k_amg_dense_apply_k(int n, const double* __restrict__ Ainv,
-                                                          const double* __restrict__ r, double* __restrict__ x,
-                                                          int64_t as, int64_t vs) {
-  const int lane = threadIdx.x & 63;
-  if (gridDim.y > 1) {  // every slice of the grid takes K of the systems
-    const size_t s0 = (size_t)blockIdx.y * K;
-    Ainv += s0 * as;
-    r += s0 * vs;
-    x += s0 * vs;
-  }
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-      const double* row = Ainv + (size_t)s * as + (size_t)i * n;
-      const double* rs = r + (size_t)s * vs;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      int j = lane;
-      for (; j + 192 < n; j += 256) {
-        const double m0 = row[j], m1 = row[j + 64], m2 = row[j + 128], m3 = row[j + 192];
-        a0 += m0 * rs[j]; a1 += m1 * rs[j + 64]; a2 += m2 * rs[j + 128]; a3 += m3 * rs[j + 192];
-      }
-      for (; j < n; j += 64) a0 += row[j] * rs[j];
-      double acc = (a0 + a1) + (a2 + a3);
-      acc = wave_sum(acc);
-      if (lane == 0) x[(size_t)s * vs + i] = acc;
     }
   }
 }

@@ -225,15 +225,15 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
     HIPCHK(dev_malloc((void**)v, sizeof(double) * n_alloc));
     HIPCHK(hipMemset(*v, 0, sizeof(double) * n_alloc));
   }
-  if (use_amg) {  // level 0 aliases the system's own arrays and vectors
-    int rc = amg_bind(s, err);
-    if (rc) return rc;
-  }
   HIPCHK(dev_malloc((void**)&d_part_a, sizeof(double) * SPAN_GRID_MAX));
   HIPCHK(dev_malloc((void**)&d_part_b, sizeof(double) * SPAN_GRID_MAX));
   HIPCHK(dev_malloc((void**)&d_sc, sizeof(DevScalars)));
   HIPCHK(hipMemset(d_sc, 0, sizeof(DevScalars)));
   HIPCHK(host_malloc((void**)&h_sc, sizeof(DevScalars)));
+  if (use_amg) {  // level 0 aliases the system's own arrays, vectors, scalars and partial sums
+    int rc = amg_bind(s, err);
+    if (rc) return rc;
+  }
   // Gram task tables
   GramTables tab;
   int t = 0;

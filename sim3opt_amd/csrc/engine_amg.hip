@@ -1,5 +1,9 @@
-// engine_amg.hip -- aggregation-multigrid preconditioner of the PCG: numbers per linearisation / per LM trial, the cycle
+// engine_amg.hip -- aggregation-multigrid preconditioner of the PCG: numbers per linearisation / per LM trial, and
+// the cycle -- ONE driver for one system (amg_apply) and for the K = 2 ... 4 systems of a batch of rejected LM trials
+// (Engine::pcg_batch, engine_batch.hip), told apart by the CycleView it is handed
 #include "engine_impl.hpp"
+
+#include <cassert>
 
 namespace sim3opt {
 
@@ -177,6 +181,18 @@ int Engine::amg_bind(const Structure& s, std::string& err) {
     if (comm.active()) std::fprintf(stderr, "; levels 0..%d partitioned over the ranks, the rest replicated", n_sharded - 1);
     std::fprintf(stderr, "; visits of levels 1, 2, 3: %d %d %d\n", amg_visits[1], amg_visits[2], amg_visits[3]);
   }
+  // the one-system cycle works on the levels' own arrays: no strides, the engine's scalars and r.z partials
+  cv_one = CycleView();
+  cv_one.lv.resize(nl);
+  for (int l = 0; l < nl; ++l) {
+    cv_one.lv[l].Minv = amg[l].Minv;
+    cv_one.lv[l].r = amg[l].r;
+    cv_one.lv[l].x = amg[l].x;
+    cv_one.lv[l].t = amg[l].t;
+  }
+  cv_one.sc = d_sc;
+  cv_one.Ainv = d_Ainv;
+  cv_one.rz_part = d_part_b;
   amg_host.clear();
   amg_host.shrink_to_fit();
   amg_stale = true;
@@ -282,86 +298,103 @@ void Engine::dense_inverse(const double* diag64, double* Aout, DevScalars* sc) {
   }  // the inverse is in Aout
 }
 
-// mode 3 (coarse levels): mode 2 on v + xc[agg], the coarser level's correction prolonged on the fly
-void Engine::spmv_mode(const AmgLevel& L, int mode, int level, const double* v, double* out,
-               const double* rvec, const double* xc) {
+// ---- the cycle: one driver for one system (cv_one) and for the systems of a batch (cv_batch) ----
+// A matrix pass of level `level` against its right-hand side lv[level].r (modes: spmv_kernel.hpp).
+void Engine::spmv_mode(const CycleView& V, int level, int mode, const double* v, double* out, const double* xc) {
+  const AmgLevel& L = amg[level];
+  const CycleLevel& B = V.lv[level];
   // level 0 carries the damping as a scalar (read from DevScalars: capturable); coarse levels
   // have it inside their diagonal blocks.  Level 0 streams once (non-temporal), the rest is small.
   // Only level-0 launches test the `done` flag: on the latency-bound coarse levels that dependent
   // scalar load in front of the kernel costs more than the few idle launches after convergence.
+  DevScalars* const sc = level == 0 ? V.sc : nullptr;
   // level 0's smoothing pass is the cycle's last kernel: it writes z = M^-1 r and leaves the partials
   // of r.z for the PCG (multiplicative cycle only)
-  double* const rz_part = level == 0 && mode == 2 && !amg_additive ? d_part_b : nullptr;
-#define AMG_SPMV(NTV, MODEV)                                                                     \
-hipLaunchKernelGGL((k_spmv_span<8, NTV, MODEV>), dim3(L.span_grid), dim3(WG), 0, stream, L.nb,  \
-                   L.wrow, L.rowptr, L.colidx, L.vals, v, out, 0.0, rz_part, rvec,              \
-                   const_cast<double*>(xc), level == 0 ? d_sc : (DevScalars*)nullptr, L.Minv, 1,   \
-                   (const int32_t*)L.agg, amg_over, BatchStrides{0, 0, 0, 0, 0}, (const float*)nullptr)
-#define AMG_SPMV32(NTV, MODEV)                                                                    \
-hipLaunchKernelGGL((k_spmv_span<(NTV) ? SIM3OPT_F32_CH : SIM3OPT_COARSE_CH, NTV, MODEV, float>), dim3(L.span_grid), dim3(WG), 0, stream,  \
-                   L.nb, L.wrow, L.rowptr, L.colidx, (const float*)L.vals32, v, out, 0.0,         \
-                   rz_part, rvec, const_cast<double*>(xc),                                        \
-                   level == 0 ? d_sc : (DevScalars*)nullptr, L.Minv, 1, (const int32_t*)L.agg, amg_over, BatchStrides{0, 0, 0, 0, 0}, (const float*)nullptr)
-  if (amg_fp32) {
-    if (level == 0) { if (mode == 1) AMG_SPMV32(true, 1); else AMG_SPMV32(true, 2); }
-    else { if (mode == 1) AMG_SPMV32(false, 1); else if (mode == 3) AMG_SPMV32(false, 3); else AMG_SPMV32(false, 2); }
+  double* const rz_part = level == 0 && mode == 2 && !amg_additive ? V.rz_part : nullptr;
+  const BatchStrides bs{B.vs, B.ms, level + 1 < (int)amg.size() ? V.lv[level + 1].vs : 0, B.ms, V.part};
+#define PASS(CHV, NTV, MODEV, VT, KV, DIAGV, SLICES, VALS)                                                           \
+  hipLaunchKernelGGL((k_spmv_span<CHV, NTV, MODEV, VT, KV, DIAGV>), dim3(L.span_grid, SLICES), dim3(WG), 0, stream, \
+                     L.nb, L.wrow, L.rowptr, L.colidx, (const VT*)(VALS), v, out, 0.0, rz_part, B.r,                 \
+                     const_cast<double*>(xc), sc, (const double*)B.Minv, 1, (const int32_t*)L.agg, amg_over, bs,     \
+                     (const float*)B.diag32)
+#define PASS_FINE(CHV, VT, KV, VALS) \
+  do { if (mode == 1) PASS(CHV, true, 1, VT, KV, false, 1, VALS); else PASS(CHV, true, 2, VT, KV, false, 1, VALS); } while (0)
+#define PASS_COARSE(CHV, VT, KV, DIAGV, SLICES, VALS)                 \
+  do {                                                                \
+    if (mode == 1) PASS(CHV, false, 1, VT, KV, DIAGV, SLICES, VALS);  \
+    else if (mode == 3) PASS(CHV, false, 3, VT, KV, DIAGV, SLICES, VALS); \
+    else PASS(CHV, false, 2, VT, KV, DIAGV, SLICES, VALS);            \
+  } while (0)
+  if (!V.batch) {
+    // one system: the damped diagonal sits in the level's own blocks (k_jacobi wrote it)
+    if (amg_fp32) {
+      if (level == 0) PASS_FINE(SIM3OPT_F32_CH, float, 1, L.vals32); else PASS_COARSE(SIM3OPT_COARSE_CH, float, 1, false, 1, L.vals32);
+    } else {
+      if (level == 0) PASS_FINE(8, double, 1, L.vals); else PASS_COARSE(8, double, 1, false, 1, L.vals);
+    }
+  } else if (level == 0) {
+    BATCH_DISPATCH(V.nsys, PASS_FINE(SIM3OPT_F32_CH, float, KS, L.vals32));
+  } else if (L.nnzb <= b_slice_blocks) {
+    // a level whose blocks stay in cache (levels >= 2 of config 3) runs one system per grid slice: its passes
+    // are launch-latency-bound, four times the wavefronts cost what one set costs, while one wavefront
+    // carrying four systems takes 2.5x as long (measured).  System s takes ITS diagonal blocks
+    // from diag32 (DIAGK)
+    PASS_COARSE(8, float, 1, true, V.nsys, L.vals32);
   } else {
-    if (level == 0) { if (mode == 1) AMG_SPMV(true, 1); else AMG_SPMV(true, 2); }
-    else { if (mode == 1) AMG_SPMV(false, 1); else if (mode == 3) AMG_SPMV(false, 3); else AMG_SPMV(false, 2); }
+    BATCH_DISPATCH(V.nsys, PASS_COARSE(8, float, KS, true, 1, L.vals32));
   }
-#undef AMG_SPMV32
-#undef AMG_SPMV
+#undef PASS_COARSE
+#undef PASS_FINE
+#undef PASS
 }
 
-void Engine::amg_restrict(int l, const double* t) {  // r_{l+1} = P^T t, x_{l+1} = Minv r_{l+1}
+void Engine::amg_restrict(const CycleView& V, int l, const double* t) {  // r_{l+1} = P^T t, x_{l+1} = Minv r_{l+1}
   const AmgLevel& F = amg[l];
   const AmgLevel& Cc = amg[l + 1];
+  const CycleLevel &BF = V.lv[l], &BC = V.lv[l + 1];
   // the aggregates this rank restricts into: those of its own rows (level l partitioned) or all
   const int a0 = Cc.own_lo, a1 = Cc.own_hi;
-  const int gr = grid_for((a1 - a0 + 8) / 9, 4);
   // a partitioned level above a replicated one: the owners' pieces of the restricted residual are
   // all-gathered, then every rank applies the first smoothing step to all rows
   const bool gather = comm.active() && sharded(l) && !sharded(l + 1);
-  const double* Minv_c = l + 2 < (int)amg.size() ? Cc.Minv : nullptr;  // coarsest: solved exactly
+  const double* Minv_c = l + 2 < (int)amg.size() ? BC.Minv : nullptr;  // coarsest: solved exactly
+  const double* Minv_k = gather ? nullptr : Minv_c;
   if (l == 0)
-    hipLaunchKernelGGL(k_amg_restrict0, dim3(std::max(1, (a1 - a0 + 3) / 4)), dim3(WG), 0, stream, a0, a1, F.mptr,
-                       F.mem, d_P, t, Cc.r, gather ? (const double*)nullptr : Minv_c, Cc.x,
-                       (const DevScalars*)d_sc);
-  else
-    hipLaunchKernelGGL(k_amg_restrict, dim3(gr), dim3(WG), 0, stream, a0, a1, F.mptr, F.mem, t, Cc.r,
-                       gather ? (const double*)nullptr : Minv_c, Cc.x);
+    BATCH_DISPATCH(V.nsys, hipLaunchKernelGGL((k_amg_restrict0<KS>), dim3(std::max(1, (a1 - a0 + 3) / 4)), dim3(WG), 0,
+                       stream, a0, a1, F.mptr, F.mem, d_P, t, BC.r, Minv_k, BC.x, (const DevScalars*)V.sc, BF.vs,
+                       BC.vs, BC.ms));
+  else  // (coarse vectors are a few MB at most: one system per grid slice, see spmv_mode)
+    hipLaunchKernelGGL((k_amg_restrict<1>), dim3(grid_for((a1 - a0 + 8) / 9, 4), V.nsys), dim3(WG), 0, stream, a0, a1,
+                       F.mptr, F.mem, t, BC.r, Minv_k, BC.x, BF.vs, BC.vs, BC.ms);
   if (gather) {
-    if (amg_status == SIM3OPT_OK) amg_status = comm.allgatherv(Cc.r, lvl_offs[l + 1], stream, amg_err);
+    if (amg_status == SIM3OPT_OK) amg_status = comm.allgatherv(BC.r, lvl_offs[l + 1], stream, amg_err);
     if (Minv_c)
       hipLaunchKernelGGL(k_amg_bjapply, dim3(grid_for((Cc.nb + 8) / 9, 4)), dim3(WG), 0, stream, Cc.nb, Minv_c,
-                         (const double*)Cc.r, Cc.x);
+                         (const double*)BC.r, BC.x);
   }
 }
 
 // x_out = x_in + scale P x_c on this rank's rows of level l -- and, when level l is partitioned, on the
 // foreign rows its rows read (their aggregates' corrections came with the exchange of x_c), so that the
 // smoothing pass that follows needs no exchange of its own
-void Engine::amg_prolong(int l, const double* xc, const double* xin, double* xout) {
+void Engine::amg_prolong(const CycleView& V, int l, const double* xc, const double* xin, double* xout) {
   const AmgLevel& F = amg[l];
-  const int gp = grid_for((F.hi - F.lo + 8) / 9, 4);
-  const DevScalars* scp = l == 0 ? (const DevScalars*)d_sc : (const DevScalars*)nullptr;
-  if (l == 0)
-    hipLaunchKernelGGL((k_amg_prolong<true>), dim3(gp), dim3(WG), 0, stream, F.lo, F.hi, (const int32_t*)nullptr,
-                       F.agg, d_P, xc, xin, xout, scp, amg_over);
-  else
-    hipLaunchKernelGGL((k_amg_prolong<false>), dim3(gp), dim3(WG), 0, stream, F.lo, F.hi, (const int32_t*)nullptr,
-                       F.agg, (const double*)nullptr, xc, xin, xout, scp, amg_over);
-  if (comm.active() && sharded(l) && !parts[l].neighbour) {  // (no neighbour plan: the whole vector travels)
-    amg_exchange(l, xout);
-  } else if (comm.active() && sharded(l) && parts[l].n_recv > 0 && !parts[l].self_test) {  // (self-test: own rows)
-    const int n = parts[l].n_recv, gl = grid_for((n + 8) / 9, 4);
+  const DevScalars* scp = l == 0 ? V.sc : nullptr;
+  const int64_t vs_f = V.lv[l].vs, vs_c = V.lv[l + 1].vs;
+  auto rows = [&](int lo, int hi, const int32_t* list) {  // rows [lo, hi), or list[lo .. hi)
+    const int g = grid_for((hi - lo + 8) / 9, 4);
     if (l == 0)
-      hipLaunchKernelGGL((k_amg_prolong<true>), dim3(gl), dim3(WG), 0, stream, 0, n, (const int32_t*)parts[l].d_recv,
-                         F.agg, d_P, xc, xin, xout, scp, amg_over);
+      BATCH_DISPATCH(V.nsys, hipLaunchKernelGGL((k_amg_prolong<true, KS>), dim3(g), dim3(WG), 0, stream, lo, hi, list,
+                         F.agg, d_P, xc, xin, xout, scp, amg_over, vs_f, vs_c));
     else
-      hipLaunchKernelGGL((k_amg_prolong<false>), dim3(gl), dim3(WG), 0, stream, 0, n, (const int32_t*)parts[l].d_recv,
-                         F.agg, (const double*)nullptr, xc, xin, xout, scp, amg_over);
-  }
+      BATCH_DISPATCH(V.nsys, hipLaunchKernelGGL((k_amg_prolong<false, KS>), dim3(g), dim3(WG), 0, stream, lo, hi, list,
+                         F.agg, (const double*)nullptr, xc, xin, xout, scp, amg_over, vs_f, vs_c));
+  };
+  rows(F.lo, F.hi, nullptr);
+  if (comm.active() && sharded(l) && !parts[l].neighbour)  // (no neighbour plan: the whole vector travels)
+    amg_exchange(l, xout);
+  else if (comm.active() && sharded(l) && parts[l].n_recv > 0 && !parts[l].self_test)  // (self-test: own rows)
+    rows(0, parts[l].n_recv, parts[l].d_recv);
 }
 
 // exchange on a partitioned level inside the cycle (errors are collected in amg_status)
@@ -370,13 +403,13 @@ void Engine::amg_exchange(int l, double* vec) {
   if (amg_status == SIM3OPT_OK) amg_status = exchange_level(l, vec, amg_err);
 }
 
-// Solves the level-(l+1) problem approximately (right-hand side amg[l+1].r, first iterate
-// amg[l+1].x = Minv r already there) by amg_visits[l+1] cycles; returns the buffer with the result
+// Solves the level-(l+1) problem approximately (right-hand side lv[l+1].r, first iterate
+// lv[l+1].x = Minv r already there) by amg_visits[l+1] cycles; returns the buffer with the result
 // (on a partitioned level: this rank's rows of it).
-double* Engine::amg_coarse(int l) {
+double* Engine::amg_coarse(const CycleView& V, int l) {
   // (time_kernels: the visits of the first level a rank partition replicates are bracketed by events --
   // what they add up to is the part of the cycle that does not shrink with the number of ranks)
-  if (opt.time_kernels && l + 1 == rep_level && part_world() > 1) {
+  if (opt.time_kernels && l + 1 == rep_level && part_world() > 1 && !V.batch) {
     if (rep_used + 2 > rep_pool.size()) {
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (event_acquire(&e0) == hipSuccess && event_acquire(&e1) == hipSuccess) {
@@ -386,31 +419,32 @@ double* Engine::amg_coarse(int l) {
     }
     if (rep_used + 2 <= rep_pool.size()) {
       (void)hipEventRecord(rep_pool[rep_used], stream);
-      double* res = amg_coarse_body(l);
+      double* res = amg_coarse_body(V, l);
       (void)hipEventRecord(rep_pool[rep_used + 1], stream);
       rep_used += 2;
       return res;
     }
   }
-  return amg_coarse_body(l);
+  return amg_coarse_body(V, l);
 }
 
-double* Engine::amg_coarse_body(int l) {
+double* Engine::amg_coarse_body(const CycleView& V, int l) {
   const int nl = (int)amg.size();
   const AmgLevel& Cc = amg[l + 1];
-  if (l + 2 == nl) {
-    hipLaunchKernelGGL(k_amg_dense_apply, dim3(std::max(1, std::min(256, (7 * Cc.nb + 3) / 4))), dim3(WG),
-                       0, stream, 7 * Cc.nb, d_Ainv, Cc.r, Cc.x, (const DevScalars*)nullptr);
-    return Cc.x;
+  const CycleLevel& BC = V.lv[l + 1];
+  if (l + 2 == nl) {  // (every system has its own dense inverse: one per grid slice)
+    hipLaunchKernelGGL((k_amg_dense_apply<1>), dim3(std::max(1, std::min(256, (7 * Cc.nb + 3) / 4)), V.nsys), dim3(WG),
+                       0, stream, 7 * Cc.nb, (const double*)V.Ainv, (const double*)BC.r, BC.x, V.as, BC.vs);
+    return BC.x;
   }
-  amg_exchange(l + 1, Cc.x);  // (a cycle reads its iterate on this rank's rows and on the rows they refer to)
-  double* res = amg_cycle(l + 1, Cc.x, Cc.t);
+  amg_exchange(l + 1, BC.x);  // (a cycle reads its iterate on this rank's rows and on the rows they refer to)
+  double* res = amg_cycle(V, l + 1, BC.x, BC.t);
   for (int g = 1; g < amg_visits[l + 1]; ++g) {  // W-cycle: again, from the current iterate
-    double* oth = res == Cc.x ? Cc.t : Cc.x;
+    double* oth = res == BC.x ? BC.t : BC.x;
     amg_exchange(l + 1, res);
-    spmv_mode(Cc, 2, l + 1, res, oth, Cc.r);  // pre-smoothing step
+    spmv_mode(V, l + 1, 2, res, oth);  // pre-smoothing step
     amg_exchange(l + 1, oth);
-    res = amg_cycle(l + 1, oth, res);
+    res = amg_cycle(V, l + 1, oth, res);
   }
   return res;
 }
@@ -419,19 +453,20 @@ double* Engine::amg_coarse_body(int l) {
 // level, on the foreign rows they read); `other` is scratch; returns the buffer that holds the new iterate
 // (always `other`; on a partitioned level: this rank's rows of it):
 //   t = r - A cur;  coarse correction;  cur += P x_c;  other = cur + Minv (r - A cur)
-double* Engine::amg_cycle(int l, double* cur, double* other) {
-  const AmgLevel& F = amg[l];
-  spmv_mode(F, 1, l, cur, other, F.r);
-  amg_restrict(l, other);
-  double* xc = amg_coarse(l);
+double* Engine::amg_cycle(const CycleView& V, int l, double* cur, double* other) {
+  // several systems: only where batch_capacity() admits a batch
+  assert(!V.batch || (amg_fp32 && !amg_additive && !comm.active()));
+  spmv_mode(V, l, 1, cur, other);
+  amg_restrict(V, l, other);
+  double* xc = amg_coarse(V, l);
   // the correction of a partitioned coarser level is needed for the aggregates of the foreign rows too
   amg_exchange(l + 1, xc);
   amg_over = amg_over_on ? amg_over_l[l] : 1.0;
   if (l == 0) {
-    amg_prolong(l, xc, cur, cur);
-    spmv_mode(F, 2, l, cur, other, F.r);
+    amg_prolong(V, l, xc, cur, cur);
+    spmv_mode(V, l, 2, cur, other);
   } else {  // piecewise-constant prolongation: added while the smoothing pass gathers its input
-    spmv_mode(F, 3, l, cur, other, F.r, xc);
+    spmv_mode(V, l, 3, cur, other, xc);
   }
   return other;
 }
@@ -445,14 +480,14 @@ double* Engine::amg_cycle(int l, double* cur, double* other) {
 int Engine::amg_apply(std::string& err) {
   amg_status = SIM3OPT_OK;
   if (amg_additive) {
-    amg_restrict(0, d_r);
-    double* xc0 = amg_coarse(0);
+    amg_restrict(cv_one, 0, d_r);
+    double* xc0 = amg_coarse(cv_one, 0);
     amg_exchange(1, xc0);
     amg_over = amg_over_on ? amg_over_l[0] : 1.0;
-    amg_prolong(0, xc0, d_z, d_az);
+    amg_prolong(cv_one, 0, xc0, d_z, d_az);
   } else {
     amg_exchange(0, d_z);
-    amg_cycle(0, d_z, d_az);
+    amg_cycle(cv_one, 0, d_z, d_az);
   }
   if (amg_status == SIM3OPT_OK) amg_exchange(0, d_az);  // the PCG's SpMV reads z on the neighbours' rows
   if (amg_status != SIM3OPT_OK) {

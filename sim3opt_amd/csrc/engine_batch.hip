@@ -2,9 +2,11 @@
 // trials of one LM iteration (OptimizationAlgorithmLevenberg::solve, reached from kitti_surf.cpp:675) solve
 // (H + lambda_k I) x_k = b for a known sequence lambda_k; after the first rejection the next ones are solved
 // together -- one pass over the blocks for K vectors, K vectors per coarse launch -- and evaluated in g2o's
-// order (Engine::lm_trial_solve, at the end, decides and hands them out).  Per system the arithmetic is that of
-// Engine::pcg_attempt with the multigrid preconditioner, operation by operation: the K solutions are bit for bit
-// those of K sequential solves.
+// order (Engine::lm_trial_solve, at the end, decides and hands them out).  Here: the buffers, the PCG loop for K
+// systems (batch_kernels.hpp) and its K-system SpMV; the preconditioner is the ONE multigrid cycle of
+// engine_amg.hip, handed the batch's view (cv_batch).  Per system the arithmetic is that of Engine::pcg_attempt
+// with the multigrid preconditioner, operation by operation: the K solutions are bit for bit those of K
+// sequential solves.
 #include "engine_impl.hpp"
 
 namespace sim3opt {
@@ -13,15 +15,6 @@ namespace sim3opt {
 #include "batch_kernels.hpp"
 
 static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
-
-// every batched kernel is instantiated for 2, 3 and 4 systems: a batch of three must not pay for four
-#define BATCH_DISPATCH(NS, ...) \
-  do {                          \
-    if ((NS) == 1) { constexpr int KS = 1; __VA_ARGS__; } \
-    else if ((NS) == 2) { constexpr int KS = 2; __VA_ARGS__; } \
-    else if ((NS) == 3) { constexpr int KS = 3; __VA_ARGS__; } \
-    else { constexpr int KS = 4; __VA_ARGS__; } \
-  } while (0)
 
 // buffers of the batched solve, allocated at its first use (single GPU, multigrid path)
 int Engine::batch_alloc(std::string& err) {
@@ -41,9 +34,13 @@ int Engine::batch_alloc(std::string& err) {
     int rc = alloc(*v, (size_t)KB * b_vs);
     if (rc) return rc;
   }
-  blv.assign(nl, BatchLevel());
+  // what the cycle (engine_amg.hip) works on for a batch: KB systems per level
+  CycleView& V = cv_batch;
+  V = CycleView();
+  V.batch = true;
+  V.lv.assign(nl, CycleLevel());
   for (int l = 0; l < nl; ++l) {
-    BatchLevel& B = blv[l];
+    CycleLevel& B = V.lv[l];
     const AmgLevel& L = amg[l];
     B.vs = l == 0 ? b_vs : pad64(7 * (int64_t)L.nb);
     B.ms = (int64_t)49 * L.nb;
@@ -71,6 +68,11 @@ int Engine::batch_alloc(std::string& err) {
   batch_owned.push_back(d_bsc);
   HIPCHK(hipMemsetAsync(d_bsc, 0, sizeof(DevScalars) * KB, stream));
   HIPCHK(host_malloc((void**)&h_bsc, sizeof(DevScalars) * KB));
+  V.sc = d_bsc;
+  V.Ainv = b_Ainv;
+  V.as = b_as;
+  V.rz_part = b_part_b;
+  V.part = SPAN_GRID_MAX;
   batch_ready = true;
   return SIM3OPT_OK;
 }
@@ -82,88 +84,8 @@ void Engine::batch_release() {
   if (h_bsc) host_free(h_bsc);
   h_bsc = nullptr;
   d_bsc = nullptr;
-  blv.clear();
+  cv_batch = CycleView();
   batch_ready = false;
-}
-
-// ---- the cycle for KB systems (mirrors spmv_mode / amg_restrict / amg_prolong / amg_coarse / amg_cycle) ----
-void Engine::b_spmv_mode(int level, int mode, const double* v, double* out, const double* rvec, const double* xc) {
-  const AmgLevel& L = amg[level];
-  const BatchLevel& B = blv[level];
-  double* const rz_part = level == 0 && mode == 2 ? b_part_b : nullptr;
-  BatchStrides bs{B.vs, B.ms, level + 1 < (int)amg.size() ? blv[level + 1].vs : 0, B.ms, SPAN_GRID_MAX};
-  const double over = amg_over;
-#define BSPMV(CHV, NTV, MODEV, DIAGV)                                                                              \
-  BATCH_DISPATCH(b_nsys, hipLaunchKernelGGL((k_spmv_span<CHV, NTV, MODEV, float, KS, DIAGV>), dim3(L.span_grid), \
-                     dim3(WG), 0, stream,   \
-                     L.nb, L.wrow, L.rowptr, L.colidx, (const float*)L.vals32, v, out, 0.0, rz_part, rvec,          \
-                     const_cast<double*>(xc), level == 0 ? d_bsc : (DevScalars*)nullptr, (const double*)B.Minv, 1,  \
-                     (const int32_t*)L.agg, over, bs, (const float*)B.diag32))
-  // a level whose blocks stay in cache (<= b_slice_blocks: levels >= 2 of config 3) runs one system per grid
-  // slice: its passes are launch-latency-bound, four times the wavefronts cost what one set costs, while one
-  // wavefront carrying four systems takes 2.5x as long (measured)
-#define BSPMV_SLICED(MODEV)                                                                                        \
-  hipLaunchKernelGGL((k_spmv_span<8, false, MODEV, float, 1, true>), dim3(L.span_grid, b_nsys), dim3(WG), 0,     \
-                     stream, L.nb, L.wrow, L.rowptr, L.colidx, (const float*)L.vals32, v, out, 0.0, rz_part, rvec,  \
-                     const_cast<double*>(xc), (DevScalars*)nullptr, (const double*)B.Minv, 1,                      \
-                     (const int32_t*)L.agg, over, bs, (const float*)B.diag32)
-  if (level > 0 && L.nnzb <= b_slice_blocks) {
-    if (mode == 1) BSPMV_SLICED(1); else if (mode == 3) BSPMV_SLICED(3); else BSPMV_SLICED(2);
-    return;
-  }
-  if (level == 0) { if (mode == 1) BSPMV(SIM3OPT_F32_CH, true, 1, false); else BSPMV(SIM3OPT_F32_CH, true, 2, false); }
-  else { if (mode == 1) BSPMV(8, false, 1, true); else if (mode == 3) BSPMV(8, false, 3, true); else BSPMV(8, false, 2, true); }
-#undef BSPMV_SLICED
-#undef BSPMV
-}
-
-void Engine::b_restrict(int l, const double* t) {
-  const AmgLevel& F = amg[l];
-  const AmgLevel& Cc = amg[l + 1];
-  const BatchLevel &BF = blv[l], &BC = blv[l + 1];
-  const double* Minv_c = l + 2 < (int)amg.size() ? BC.Minv : nullptr;  // coarsest: solved exactly
-  if (l == 0)
-    BATCH_DISPATCH(b_nsys, hipLaunchKernelGGL((k_amg_restrict0_k<KS>), dim3((Cc.nb + 3) / 4), dim3(WG), 0, stream, Cc.nb,
-                       F.mptr, F.mem, d_P, t, BC.r, Minv_c, BC.x, (const DevScalars*)d_bsc, BF.vs, BC.vs, BC.ms));
-  else  // (coarse vectors are a few MB at most: one system per grid slice, see b_spmv_mode)
-    hipLaunchKernelGGL((k_amg_restrict_k<1>), dim3(grid_for((Cc.nb + 8) / 9, 4), b_nsys), dim3(WG), 0, stream, Cc.nb,
-                       F.mptr, F.mem, t, BC.r, Minv_c, BC.x, BF.vs, BC.vs, BC.ms);
-}
-
-double* Engine::b_coarse(int l) {
-  const int nl = (int)amg.size();
-  const AmgLevel& Cc = amg[l + 1];
-  const BatchLevel& BC = blv[l + 1];
-  if (l + 2 == nl) {
-    hipLaunchKernelGGL((k_amg_dense_apply_k<1>), dim3(std::max(1, std::min(256, (7 * Cc.nb + 3) / 4)), b_nsys), dim3(WG), 0,
-                       stream, 7 * Cc.nb, (const double*)b_Ainv, (const double*)BC.r, BC.x, b_as, BC.vs);
-    return BC.x;
-  }
-  double* res = b_cycle(l + 1, BC.x, BC.t);
-  for (int g = 1; g < amg_visits[l + 1]; ++g) {
-    double* oth = res == BC.x ? BC.t : BC.x;
-    b_spmv_mode(l + 1, 2, res, oth, BC.r, nullptr);
-    res = b_cycle(l + 1, oth, res);
-  }
-  return res;
-}
-
-double* Engine::b_cycle(int l, double* cur, double* other) {
-  const AmgLevel& F = amg[l];
-  const BatchLevel& BF = blv[l];
-  b_spmv_mode(l, 1, cur, other, BF.r, nullptr);
-  b_restrict(l, other);
-  const double* xc = b_coarse(l);
-  amg_over = amg_over_on ? amg_over_l[l] : 1.0;
-  if (l == 0) {
-    BATCH_DISPATCH(b_nsys, hipLaunchKernelGGL((k_amg_prolong0_k<KS>), dim3(grid_for((F.nb + 8) / 9, 4)), dim3(WG), 0, stream,
-                       F.nb, F.agg, d_P, xc, (const double*)cur, cur, (const DevScalars*)d_bsc, amg_over, BF.vs,
-                       blv[1].vs));
-    b_spmv_mode(l, 2, cur, other, BF.r, nullptr);
-  } else {
-    b_spmv_mode(l, 3, cur, other, BF.r, xc);
-  }
-  return other;
 }
 
 // Solves (H + lams[s] I) x_s = b, s < nsys <= KB, together; x_s is left in b_x + s * b_vs.  *usable = false:
@@ -193,7 +115,7 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   for (int s = 0; s < nsys; ++s) {
     for (int l = 0; l < nl; ++l) {
       const AmgLevel& L = amg[l];
-      const BatchLevel& B = blv[l];
+      const CycleLevel& B = cv_batch.lv[l];
       jacobi(0, L.nb, L.rowptr, L.vals, lams[s], B.Minv + (size_t)s * B.ms, amg_omega, L.diagH, L.W, nullptr,
              d_bsc + s, l == nl - 1 ? b_diag64 + (size_t)s * 49 * L.nb : nullptr,
              l > 0 ? B.diag32 + (size_t)s * B.ms : nullptr);
@@ -202,9 +124,9 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   }
   const int gv = grid_for((nb + 8) / 9, 4);
   const int gs = span_grid;
-  const BatchLevel& B0 = blv[0];
+  const CycleLevel& B0 = cv_batch.lv[0];
   BatchStrides bs0{b_vs, B0.ms, 0, 0, SPAN_GRID_MAX};
-  b_nsys = nsys;
+  cv_batch.nsys = nsys;
   BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_pcg_init_k<KS>), dim3(gv), dim3(WG), 0, stream, 0, nb, (const double*)d_b,
                      (const double*)B0.Minv, b_x, b_r, b_z, b_p, b_s, bs0));
   HIPCHK(hipGetLastError());
@@ -212,7 +134,7 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   HIPCHK(hipStreamSynchronize(stream));
   for (int s = 0; s < nsys; ++s)
     if (h_bsc[s].fail) return SIM3OPT_OK;  // a non-positive pivot of some set-up: not usable
-  b_cycle(0, b_z, b_az);
+  amg_cycle(cv_batch, 0, b_z, b_az);
   const int chunk = std::min(4, std::max(1, opt.pcg_check_every));
   int it = 0, par = 0;
   for (;;) {
@@ -225,7 +147,7 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
     for (int s = 0; s < nsys; ++s)
       if (!(h_bsc[s].done || h_bsc[s].stop || h_bsc[s].fail)) live = s + 1;
     if (live == 0 || it >= max_it) break;
-    b_nsys = live;
+    cv_batch.nsys = live;
     const int todo = std::min(chunk, max_it - it);
     for (int c = 0; c < todo; ++c) {
       BATCH_DISPATCH(live, hipLaunchKernelGGL((k_spmv_span<8, true, 0, double, KS, false>), dim3(gs), dim3(WG), 0, stream,
@@ -237,7 +159,7 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
       BATCH_DISPATCH(live, hipLaunchKernelGGL((k_pcg_step_k<KS>), dim3(gv), dim3(WG), 0, stream, 0, nb, par, it,
                          (const double*)B0.Minv, (const double*)b_az, b_z, (const double*)b_q, b_p, b_s, b_x, b_r, d_bsc,
                          bs0));
-      b_cycle(0, b_z, b_az);
+      amg_cycle(cv_batch, 0, b_z, b_az);
       par ^= 1;
       ++it;
     }

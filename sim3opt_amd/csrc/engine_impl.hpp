@@ -3,12 +3,13 @@
 //                      LM trial loop (OptimizationAlgorithmLevenberg::solve; its damping rule: lm_damping.hpp)
 //   engine_pcg.hip     the preconditioned CG (LinearSolverEigen's role on graphs too large to factor), halo exchange
 //   engine_amg.hip     the aggregation-multigrid preconditioner: set-up per linearisation / per trial, the cycle
+//                      (one driver for one system and for the systems of a batch: CycleView)
 //   engine_direct.hip  when the LM factorises exactly (LinearSolverEigen's role on KITTI-00-like graphs) and the
 //                      marginal covariances: policy over two BlockLdl (direct_factor.hpp, direct_factor.hip)
-//   engine_batch.hip   the multigrid PCG for several right-hand sides: an LM trial's solve (lm_trial_solve)
+//   engine_batch.hip   the multigrid PCG loop for several right-hand sides: an LM trial's solve (lm_trial_solve)
 //   engine_algorithms.hip  Gauss-Newton and Powell's dogleg (options.algorithm = 1 / 2)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
-// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, algo_kernels.hpp -> engine_algorithms.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
+// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, batch_kernels.hpp -> engine_batch.hip, algo_kernels.hpp -> engine_algorithms.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
 // the SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through a method.
 #pragma once
 // (formerly all of engine.hip) -- device-resident Levenberg-Marquardt on a Sim(3) pose graph, gfx950 (MI355X).
@@ -79,6 +80,16 @@ constexpr int PCG_GRAPH_ITERS = 16;  // PCG iterations per captured hipGraph (ev
 constexpr int MAX_GRID = 2048;  // grid cap of the streaming kernels = number of reduction partials
 constexpr int SPAN_GRID_MAX = 65536;  // workgroups of the span SpMV (its partials: one pair each)
                                 // (256 CUs x 8 workgroups of 4 waves = full occupancy)
+
+// a kernel templated on the number of right-hand sides is instantiated for 1 ... KB: a batch of three must not
+// pay for four
+#define BATCH_DISPATCH(NS, ...) \
+  do {                          \
+    if ((NS) == 1) { constexpr int KS = 1; __VA_ARGS__; } \
+    else if ((NS) == 2) { constexpr int KS = 2; __VA_ARGS__; } \
+    else if ((NS) == 3) { constexpr int KS = 3; __VA_ARGS__; } \
+    else { constexpr int KS = 4; __VA_ARGS__; } \
+  } while (0)
 
 // Scalars that live in HBM so the PCG loop needs no host round trip per iteration.
 struct DevScalars {
@@ -230,27 +241,34 @@ class Engine {
   double mean_diag = 0.0;
   int amg_status = 0;                  // first collective error inside a cycle
   std::string amg_err;
-  // ---- several right-hand sides at once (engine_batch.hip): the rejected trials of an LM iteration ----
-  struct BatchLevel {
-    double *Minv = nullptr, *r = nullptr, *x = nullptr, *t = nullptr;  // KB systems each, strides ms / vs
-    float* diag32 = nullptr;  // coarse levels: every system's damped diagonal blocks, [row][49]
-    int64_t vs = 0, ms = 0;
+  // ---- whose vectors a multigrid cycle works on: ONE driver (engine_amg.hip) for one and for several systems ----
+  struct CycleLevel {
+    double *Minv = nullptr, *r = nullptr, *x = nullptr, *t = nullptr;  // per system, strides ms / vs
+    float* diag32 = nullptr;  // coarse levels of a batch: every system's damped diagonal blocks, [row][49]
+    int64_t vs = 0, ms = 0;   // (one system: the level's own damped blocks, no strides)
   };
-  std::vector<BatchLevel> blv;
+  struct CycleView {
+    int nsys = 1;            // systems the launches carry (a batch: the first `nsys` of its KB)
+    bool batch = false;      // storage for KB systems: per-system diagonals on coarse levels, FP32 passes only
+    std::vector<CycleLevel> lv;
+    DevScalars* sc = nullptr;     // the systems' scalars (level-0 launches test `done`)
+    double* Ainv = nullptr;       // dense inverse(s) of the coarsest level, stride as
+    int64_t as = 0;
+    double* rz_part = nullptr;    // where the cycle's last level-0 pass leaves the partials of r.z, stride part
+    int part = 0;
+  };
+  CycleView cv_one;    // aliases the AmgLevel arrays (amg_bind)
+  CycleView cv_batch;  // the buffers of batch_alloc
+  // ---- several right-hand sides at once (engine_batch.hip): the rejected trials of an LM iteration ----
   std::vector<void*> batch_owned;
   double *b_x = nullptr, *b_r = nullptr, *b_z = nullptr, *b_p = nullptr, *b_q = nullptr, *b_s = nullptr, *b_az = nullptr;
   double *b_Ainv = nullptr, *b_diag64 = nullptr, *b_part_a = nullptr, *b_part_b = nullptr;
   int64_t b_vs = 0, b_as = 0;
   DevScalars *d_bsc = nullptr, *h_bsc = nullptr;
   bool batch_ready = false;
-  int b_nsys = KB;  // systems of the batch being solved (kernels are instantiated for 2, 3, 4)
   int64_t b_slice_blocks = 100000;  // levels with at most this many blocks run one system per grid slice
   int batch_alloc(std::string& err);
   void batch_release();
-  void b_spmv_mode(int level, int mode, const double* v, double* out, const double* rvec, const double* xc);
-  void b_restrict(int l, const double* t);
-  double* b_coarse(int l);
-  double* b_cycle(int l, double* cur, double* other);
   int pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_res, bool* capped, bool* usable,
                 std::string& err);
   // the solve of LM trial q at damping lambda (ni: the rule's next factor); *x: d_x or its system of a batch
@@ -387,23 +405,24 @@ class Engine {
   // per trial: damped diagonal blocks, smoother inverses, dense inverse of the coarsest level
   void amg_prepare(double lambda);
 
+  // The cycle (every step on the view's vectors; launch choices: spmv_mode)
+  // a matrix pass of level `level` against its right-hand side: mode 1 out = r - A v, mode 2 out = v + Minv (r - A v),
   // mode 3 (coarse levels): mode 2 on v + xc[agg], the coarser level's correction prolonged on the fly
-  void spmv_mode(const AmgLevel& L, int mode, int level, const double* v, double* out,
-                 const double* rvec, const double* xc = nullptr);
+  void spmv_mode(const CycleView& V, int level, int mode, const double* v, double* out, const double* xc = nullptr);
 
-  void amg_restrict(int l, const double* t);
-  void amg_prolong(int l, const double* xc, const double* xin, double* xout);
+  void amg_restrict(const CycleView& V, int l, const double* t);
+  void amg_prolong(const CycleView& V, int l, const double* xc, const double* xin, double* xout);
 
-  // Solves the level-(l+1) problem approximately (right-hand side amg[l+1].r, first iterate
-  // amg[l+1].x = Minv r already there) by amg_visits[l+1] cycles; returns the buffer with the result.
-  double* amg_coarse(int l);
-  double* amg_coarse_body(int l);
+  // Solves the level-(l+1) problem approximately (right-hand side lv[l+1].r, first iterate
+  // lv[l+1].x = Minv r already there) by amg_visits[l+1] cycles; returns the buffer with the result.
+  double* amg_coarse(const CycleView& V, int l);
+  double* amg_coarse_body(const CycleView& V, int l);
   void amg_exchange(int l, double* vec);
 
   // One multigrid cycle on level l from the iterate `cur`; `other` is scratch; returns the buffer
   // that holds the new iterate (always `other`):
   //   t = r - A cur;  coarse correction;  cur += P x_c;  other = cur + Minv (r - A cur)
-  double* amg_cycle(int l, double* cur, double* other);
+  double* amg_cycle(const CycleView& V, int l, double* cur, double* other);
 
   // d_az = M^-1 d_r; on entry d_z = Minv_0 d_r (written by the PCG step).  Multiplicative: one
   // V(1,1) (or W) cycle from that iterate.  Additive on level 0 (no fine-level matrix pass in the

@@ -1,6 +1,6 @@
 // spmv_kernel.hpp -- the software-pipelined 7x7 block-CSR SpMV with its multigrid epilogues (a template:
-// instantiated by engine_pcg.hip for the PCG's own product, by engine_amg.hip for the cycle's matrix passes and by
-// engine_batch.hip for K right-hand sides at once -- ONE kernel source: the one-system kernel is K = 1; measured
+// instantiated by engine_pcg.hip for the PCG's own product, by engine_amg.hip for the cycle's matrix passes (one and
+// K right-hand sides) and by engine_batch.hip for the K-system product -- ONE kernel source: the one-system kernel is K = 1; measured
 // on the driver's command: 47.1-47.2 LM it/s against 46.6-46.9 with a separate one-system kernel).
 // LinearSolverEigen's role, kitti_surf.cpp:553-554; SURVEY.md 8(a) row a9.
 #pragma once
