@@ -128,7 +128,12 @@ typedef struct sim3opt_options {
                                         when partitioned)                                      [SIM3OPT_ROW_ORDER=insertion|bfs] */
   int32_t halo_exchange;    /* 1     partitioned runs exchange boundary rows only; 0 = whole-vector all-gather
                                                                                                [SIM3OPT_NO_HALO] */
-  int32_t span_grid;        /* 0     workgroups of the span SpMV; 0 = automatic                [SIM3OPT_SPAN_GRID] */
+  int32_t span_grid;        /* 0     workgroups of the span SpMV (four row spans each); 0 or less = automatic (so is
+                                        SIM3OPT_SPAN_GRID=0); a positive value is a REQUEST, clamped at every
+                                        sim3opt_initialize to 8 .. min((rows + 3) / 4, 65536) of that graph (of this
+                                        rank's rows when partitioned).  sim3opt_get_options reports the value in use;
+                                        the request is kept, and handing the reported value back to
+                                        sim3opt_set_options leaves it as it was                [SIM3OPT_SPAN_GRID] */
   int32_t force_collectives;/* 0     1: run every collective of the partitioned path even with one rank
                                         (transport self-test)                                  [SIM3OPT_FORCE_COMM] */
   int32_t amg_shard_rows;   /* 4096  partitioned runs: multigrid levels with more block rows than this are
@@ -446,6 +451,27 @@ int sim3opt_amg_coarsest_inverse(sim3opt_graph* g, double lambda, double* Ainv);
  * SIM3OPT_ERR_STATE.  One GPU only. */
 int sim3opt_preconditioner_apply(sim3opt_graph* g, int32_t prec, double lambda, int32_t nrhs, const double* r,
                                  double* z);
+/* ---- diagnostic read-outs of the PCG's own operator (tests/test_gpu_pcg_operator.py compares them with a
+ * long-double restatement, tests/pcg_ref.py); inspection calls like the ones above. ---- */
+/* Diagnostic.  The table of row spans the span SpMV's wavefronts work on, as the device holds it: *n_spans =
+ * 4 x workgroups, wrow (may be NULL: call once for the size) receives *n_spans + 1 ascending block rows; wavefront w
+ * owns rows wrow[w] .. wrow[w + 1] - 1 (a partitioned run: this rank's table). */
+int sim3opt_spmv_spans(sim3opt_graph* g, int32_t* n_spans, int32_t* wrow);
+/* Diagnostic.  The instantiation of the one-system span SpMV in use: *chunk = 4 or 8 blocks per lane group and load,
+ * *non_temporal = 1 if the blocks are streamed with non-temporal loads (SIM3OPT_SPMV="chunk,nt", read when the graph
+ * is initialised). */
+int sim3opt_spmv_variant(sim3opt_graph* g, int32_t* chunk, int32_t* non_temporal);
+/* Diagnostic.  q[s] = (H + lambda[s] I) p[s], pq[s] = p[s] . q[s] and, with rvec, rp[s] = rvec[s] . p[s] for s < nrhs
+ * (vectors of 7 x block rows, one after the other) on the last linearisation, by the launches of a PCG iteration:
+ * nrhs = 1 the one-system SpMV with the engine's current variant (SIM3OPT_SPMV) and span table, the damping read from
+ * the device's scalars, its partial sums added by the function a solve adds them with (the same value; a solve of up
+ * to 2048 workgroups adds them inside its step kernel, not in a launch of their own); nrhs = 2 .. 4 the SpMV of the
+ * batched trial solves (per-system damping, one pass over the blocks) and its sum -- on a graph with the multigrid
+ * preconditioner only (else SIM3OPT_ERR_STATE).  rvec and rp are both NULL or both given; for nrhs > 1 the batched
+ * solves themselves never pass rvec (their r.z comes from the cycle), so rp then exercises the kernel for this read-out
+ * alone.  One GPU only (world > 1: SIM3OPT_ERR_STATE). */
+int sim3opt_operator_apply(sim3opt_graph* g, int32_t nrhs, const double* lambda, const double* p, const double* rvec,
+                           double* q, double* pq, double* rp);
 
 /* ---- row-partitioned multi-GPU (one process per GPU, RCCL over xGMI) ----
  * Every rank adds the SAME full graph; rank r then owns a contiguous range of block rows (equal

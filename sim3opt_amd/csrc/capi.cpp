@@ -264,7 +264,13 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
     return fail(g, SIM3OPT_ERR_ARG,
                 "set_options: jacobians = 1 needs fix_small_angle_b = 1 (the closed form differentiates the exact "
                 "map; log's as-written small-angle B departs from it by O(1) below theta ~ 4.5e-3)");
+  // span_grid: the handle keeps the caller's REQUEST (clamped anew at every sim3opt_initialize) while
+  // sim3opt_get_options reports the value in use; a value that is the reported one leaves the request as it is, so
+  // that get / change another field / set does not turn the clamp into the request
+  const int32_t span_request = g->opt.span_grid;
+  const bool span_as_reported = g->engine && span_request > 0 && o->span_grid == engine_span_grid(g->engine);
   g->opt = *o;
+  if (span_as_reported) g->opt.span_grid = span_request;
   if (g->engine) engine_set_options(g->engine, g->opt);
   return SIM3OPT_OK;
 }
@@ -272,6 +278,7 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
 int sim3opt_get_options(const sim3opt_graph* g, sim3opt_options* o) {
   if (!g || !o) return SIM3OPT_ERR_ARG;
   *o = g->opt;
+  if (g->engine && o->span_grid > 0) o->span_grid = engine_span_grid(g->engine);  // (as clamped for this graph)
   return SIM3OPT_OK;
 }
 
@@ -845,6 +852,29 @@ int sim3opt_preconditioner_apply(sim3opt_graph* g, int32_t prec, double lambda, 
     return fail(g, SIM3OPT_ERR_ARG, "preconditioner_apply: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "preconditioner_apply: call sim3opt_initialize first");
   return engine_precond_apply(g->engine, prec, lambda, nrhs, r, z, g->err);
+}
+
+int sim3opt_spmv_spans(sim3opt_graph* g, int32_t* n_spans, int32_t* wrow) {
+  if (!g || !n_spans) return fail(g, SIM3OPT_ERR_ARG, "spmv_spans: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "spmv_spans: call sim3opt_initialize first");
+  return engine_spmv_spans(g->engine, n_spans, wrow, g->err);
+}
+
+int sim3opt_spmv_variant(sim3opt_graph* g, int32_t* chunk, int32_t* non_temporal) {
+  if (!g || !chunk || !non_temporal) return fail(g, SIM3OPT_ERR_ARG, "spmv_variant: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "spmv_variant: call sim3opt_initialize first");
+  engine_spmv_variant(g->engine, chunk, non_temporal);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_operator_apply(sim3opt_graph* g, int32_t nrhs, const double* lambda, const double* p, const double* rvec,
+                           double* q, double* pq, double* rp) {
+  if (!g || !lambda || !p || !q || !pq || nrhs < 1 || nrhs > 4 || (rvec == nullptr) != (rp == nullptr))
+    return fail(g, SIM3OPT_ERR_ARG, "operator_apply: bad argument");
+  for (int32_t s = 0; s < nrhs; ++s)
+    if (!std::isfinite(lambda[s]) || lambda[s] < 0.0) return fail(g, SIM3OPT_ERR_ARG, "operator_apply: bad lambda");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "operator_apply: call sim3opt_initialize first");
+  return engine_operator_apply(g->engine, nrhs, lambda, p, rvec, q, pq, rp, g->err);
 }
 
 int sim3opt_partition_plan(sim3opt_graph* g, int32_t world, int32_t locality, int32_t* vertex_of_row,

@@ -148,7 +148,8 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
     // rule: ~4 block rows per wavefront (16 per workgroup), but never fewer workgroups than the
     // resident set as long as every wavefront still gets a row
     span_grid = std::max(std::min(2048, (nloc + 3) / 4), (nloc + 15) / 16);
-    if (const char* ev = std::getenv("SIM3OPT_SPAN_GRID")) span_grid = std::min(std::atoi(ev), (nloc + 3) / 4);  // tuning knob
+    // tuning knob (options.span_grid; SIM3OPT_SPAN_GRID reaches it through sim3opt_initialize)
+    if (opt.span_grid > 0) span_grid = std::min(opt.span_grid, (nloc + 3) / 4);
     span_grid = std::max(8, std::min(SPAN_GRID_MAX, span_grid));
     const int nw = span_grid * 4;
     std::vector<int32_t> wrow(nw + 1);
@@ -742,6 +743,12 @@ void engine_local_rows(const Engine* e, int32_t* begin, int32_t* end) {
 int engine_preconditioner(const Engine* e) { return e->use_amg ? 2 : (e->use_chain ? 1 : 0); }
 
 int engine_linear_solver(const Engine* e) { return e->use_direct ? 1 : 0; }
+
+int engine_span_grid(const Engine* e) { return e->span_grid; }
+void engine_spmv_variant(const Engine* e, int32_t* chunk, int32_t* non_temporal) {  // (as spmv_raw branches)
+  *chunk = e->spmv_chunk <= 4 ? 4 : 8;
+  *non_temporal = e->spmv_nt ? 1 : 0;
+}
 
 void engine_device_bytes(const Engine* e, int64_t bytes[2]) {
   bytes[0] = e->ranged_bytes();

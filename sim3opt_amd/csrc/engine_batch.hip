@@ -194,6 +194,60 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   return SIM3OPT_OK;
 }
 
+// Diagnostic read-out (Engine::operator_apply brackets it): q_s = (H + lambda_s I) p_s, p_s . q_s and rvec_s . p_s by
+// the SpMV launch of pcg_batch and its sum.  pcg_batch itself always passes rvec = nullptr (its r.z comes from the
+// cycle): without rvec this is its launch, with rvec the kernel's r.p branch is taken for the read-out alone
+// (diagnostic only; q and p.q do not depend on it, tested).  The batch's scalars are put back on both sides; b_az, b_r
+// and b_q are rewritten by every pcg_batch before it reads them.
+int Engine::operator_apply_batch(int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,
+                                 double* pq, double* rp, std::string& err) {
+  int rc = batch_alloc(err);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(stream));
+  DevScalars saved_d[KB], saved_h[KB], s[KB];
+  HIPCHK(hipMemcpy(saved_d, d_bsc, sizeof(saved_d), hipMemcpyDeviceToHost));
+  std::memcpy(saved_h, h_bsc, sizeof(saved_h));
+  auto body = [&]() -> int {
+    std::memset(s, 0, sizeof(s));
+    for (int k = 0; k < KB; ++k) {
+      s[k].lambda = lambda[std::min<int>(k, nrhs - 1)];
+      s[k].done = k < nrhs ? 0 : 1;
+    }
+    HIPCHK(hipMemcpy(d_bsc, s, sizeof(s), hipMemcpyHostToDevice));
+    const size_t bytes = sizeof(double) * (size_t)n;
+    for (int k = 0; k < nrhs; ++k) {
+      HIPCHK(hipMemcpyAsync(b_az + (size_t)k * b_vs, p + (size_t)k * n, bytes, hipMemcpyHostToDevice, stream));
+      if (rvec) HIPCHK(hipMemcpyAsync(b_r + (size_t)k * b_vs, rvec + (size_t)k * n, bytes, hipMemcpyHostToDevice, stream));
+    }
+    const int gs = span_grid;
+    BatchStrides bs0{b_vs, cv_batch.lv[0].ms, 0, 0, SPAN_GRID_MAX};
+    BATCH_DISPATCH(nrhs, hipLaunchKernelGGL((k_spmv_span<8, true, 0, double, KS, false>), dim3(gs), dim3(WG), 0, stream,
+                       nb, d_wrow, d_rowptr, d_colidx, (const double*)d_vals, (const double*)b_az, b_q, 0.0, b_part_a,
+                       rvec ? (const double*)b_r : (const double*)nullptr, b_part_b, d_bsc, (const double*)nullptr, 1,
+                       (const int32_t*)nullptr, 1.0, bs0, (const float*)nullptr));
+    BATCH_DISPATCH(nrhs, hipLaunchKernelGGL((k_final_sum2_k<KS>), dim3(1), dim3(WG), 0, stream, (const double*)b_part_a,
+                       (const double*)b_part_b, gs, SPAN_GRID_MAX, d_bsc));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(s, d_bsc, sizeof(s), hipMemcpyDeviceToHost));
+    for (int k = 0; k < nrhs; ++k) {
+      HIPCHK(hipMemcpy(q + (size_t)k * n, b_q + (size_t)k * b_vs, bytes, hipMemcpyDeviceToHost));
+      pq[k] = s[k].tmp_pq;
+      if (rp) rp[k] = s[k].tmp_rz;
+    }
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(d_bsc, saved_d, sizeof(saved_d), hipMemcpyHostToDevice) != hipSuccess) {
+    if (rc == SIM3OPT_OK) {
+      err = "operator_apply: restoring the batch's scalars failed";
+      rc = SIM3OPT_ERR_HIP;
+    }
+  }
+  std::memcpy(h_bsc, saved_h, sizeof(saved_h));
+  return rc;
+}
+
 // The solve of LM trial q at damping lambda; ni is the factor the next rejection applies.  After a rejection g2o's
 // rule fixes the dampings of the next trials (lambda *= ni, ni *= 2 per rejection), so the systems of the trials
 // that may follow are solved TOGETHER -- one pass over the blocks for all of them -- and handed to the trials one

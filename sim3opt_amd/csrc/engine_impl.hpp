@@ -519,6 +519,19 @@ class Engine {
   int amg_coarsest_inverse(double lambda, double* Ainv, std::string& err);                // engine_amg.hip
   // z[q] = M^-1 r[q] for nrhs right-hand sides with ONE set-up: the launches of a PCG iteration (engine_pcg.hip)
   int precond_apply(int prec, double lambda, int32_t nrhs, const double* r, double* z, std::string& err);
+  // ---- ... and of the PCG's own operator (tests/test_gpu_pcg_operator.py) ----
+  // the span table as the device holds it (a copy: nothing is written)
+  int spmv_spans(int32_t* n_spans, int32_t* wrow, std::string& err);                      // engine_pcg.hip
+  // q = (H + lambda I) p with p.q and rvec.p: the SpMV launch of a PCG iteration and the sum of its partials; one
+  // system through spmv_raw (d_sc), several through the batch's launch (operator_apply_batch: d_bsc, batch buffers).
+  // The partials are added by k_final_sum2 / k_final_sum2_k: the FUNCTION a solve adds them with (sum_partials on the
+  // same arrays, count and block size), not the launch -- up to MAX_GRID partials k_pcg_step adds them in-step.  With
+  // rvec the K-system kernel takes a path pcg_batch never takes (its r.z comes from the cycle): diagnostic only.
+  // Vectors they stage in -- d_z, d_r, d_q, b_az, b_r, b_q -- are rewritten by every solve before it reads them.
+  int operator_apply(int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q, double* pq,
+                     double* rp, std::string& err);                                      // engine_pcg.hip
+  int operator_apply_batch(int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,
+                           double* pq, double* rp, std::string& err);                    // engine_batch.hip
 
   // ---- the iteration frame of LM, Gauss-Newton and dogleg (engine.hip) ----
   int iter_begin(sim3opt_iter_stats& T, double& chi, std::string& err);  // stamp 0, chi2 (cached or not), linearise

@@ -550,6 +550,71 @@ int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, c
   return e->precond_apply(prec, lambda, nrhs, r, z, err);
 }
 
+int Engine::spmv_spans(int32_t* n_spans, int32_t* wrow, std::string& err) {
+  *n_spans = 4 * span_grid;
+  if (!wrow) return SIM3OPT_OK;
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipMemcpy(wrow, d_wrow, sizeof(int32_t) * (size_t)(4 * span_grid + 1), hipMemcpyDeviceToHost));
+  return SIM3OPT_OK;
+}
+
+int Engine::operator_apply(int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,
+                           double* pq, double* rp, std::string& err) {
+  if (!linearized) {
+    err = "operator_apply: call sim3opt_linearize (or optimize) first";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (comm.world > 1) {
+    err = "operator_apply: one GPU only";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (nrhs > 1 && (!use_amg || amg.empty())) {
+    err = "operator_apply: several systems need the batch buffers of a multigrid graph";
+    return SIM3OPT_ERR_STATE;
+  }
+  DevScalars sd, sh;
+  int rc = diag_begin(lambda[0], sd, sh, err);
+  if (rc) return rc;
+  auto body = [&]() -> int {
+    if (nrhs > 1) return operator_apply_batch(nrhs, lambda, p, rvec, q, pq, rp, err);
+    // p -> d_z (what the PCG hands its SpMV), rvec -> d_r; the damping travels in d_sc as in pcg_attempt
+    const size_t bytes = sizeof(double) * (size_t)n;
+    HIPCHK(hipMemcpyAsync(d_z, p, bytes, hipMemcpyHostToDevice, stream));
+    if (rvec) HIPCHK(hipMemcpyAsync(d_r, rvec, bytes, hipMemcpyHostToDevice, stream));
+    const int gs = spmv_grid();
+    spmv_raw(lambda[0], d_z, d_q, rvec ? d_r : nullptr, d_sc);
+    // (k_pcg_step adds the partials by sum_partials in every workgroup, or reads the pair k_final_sum2 left when there
+    // are more than MAX_GRID of them: the same FUNCTION on the same arrays, count and block size, hence the same value
+    // -- one launch serves both; the in-step summation itself is exercised by the iterates of sim3opt_solve only)
+    hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gs, &d_sc->tmp_pq);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(q, d_q, bytes, hipMemcpyDeviceToHost));
+    double two[2];
+    HIPCHK(hipMemcpy(two, &d_sc->tmp_pq, sizeof(two), hipMemcpyDeviceToHost));
+    pq[0] = two[0];
+    if (rp) rp[0] = two[1];
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  std::string err2;
+  const int rc_end = diag_end(sd, sh, err2);
+  if (rc == SIM3OPT_OK && rc_end) {
+    err = err2;
+    rc = rc_end;
+  }
+  return rc;
+}
+
+int engine_spmv_spans(Engine* e, int32_t* n_spans, int32_t* wrow, std::string& err) {
+  return e->spmv_spans(n_spans, wrow, err);
+}
+
+int engine_operator_apply(Engine* e, int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,
+                          double* pq, double* rp, std::string& err) {
+  return e->operator_apply(nrhs, lambda, p, rvec, q, pq, rp, err);
+}
+
 int engine_bench_spmv(Engine* e, int32_t reps, double* ms_mean, std::string& err) {
   if (!e->linearized) {
     err = "bench_spmv: call sim3opt_linearize (or optimize) first";

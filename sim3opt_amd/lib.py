@@ -198,6 +198,9 @@ SYMBOLS = {
                                             _dp, _dp, _dp]),
     "sim3opt_amg_coarsest_inverse": (C.c_int, [_vp, C.c_double, _dp]),
     "sim3opt_preconditioner_apply": (C.c_int, [_vp, C.c_int32, C.c_double, C.c_int32, _dp, _dp]),
+    "sim3opt_spmv_spans": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_spmv_variant": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_operator_apply": (C.c_int, [_vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
     "sim3opt_linear_solver_in_use": (C.c_int, [_vp]),
     "sim3opt_direct_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _ip,
                                       _ip, _ip, _ip, _ip, _ip, _ip]),
@@ -793,6 +796,38 @@ class Graph:
         self._chk(self._L.sim3opt_preconditioner_apply(self._g, int(prec), float(lam), r2.shape[0], _p(r2, _dp),
                                                        _p(z, _dp)))
         return z.reshape(np.shape(r))
+
+    def spmv_spans(self):
+        """The span SpMV's row spans as the device holds them: wrow (4 x workgroups + 1,), wavefront w owns the block
+        rows wrow[w] .. wrow[w + 1] - 1."""
+        ns = C.c_int32()
+        self._chk(self._L.sim3opt_spmv_spans(self._g, C.byref(ns), None))
+        wrow = np.zeros(ns.value + 1, dtype=np.int32)
+        self._chk(self._L.sim3opt_spmv_spans(self._g, C.byref(ns), _p(wrow, _ip)))
+        return wrow
+
+    def spmv_variant(self):
+        """(chunk, non_temporal) of the one-system span SpMV in use (SIM3OPT_SPMV)."""
+        ch, nt = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_spmv_variant(self._g, C.byref(ch), C.byref(nt)))
+        return ch.value, nt.value
+
+    def operator_apply(self, lam, p, rvec=None):
+        """(q, p.q, rvec.p) of q = (H + lam I) p by the SpMV launch of a PCG iteration and the sum of its partials; p:
+        (7 nb,) with a scalar lam, or (nrhs, 7 nb) with nrhs dampings (nrhs 2 .. 4: the batched launch, multigrid graphs
+        only).  rvec.p is None without rvec."""
+        p2 = _f64(np.atleast_2d(p))
+        k = p2.shape[0]
+        lams = _f64(np.broadcast_to(np.asarray(lam, dtype=np.float64), (k,)))
+        r2 = None if rvec is None else _f64(np.atleast_2d(rvec))
+        assert r2 is None or r2.shape == p2.shape
+        q, pq = np.zeros_like(p2), np.zeros(k)
+        rp = None if r2 is None else np.zeros(k)
+        self._chk(self._L.sim3opt_operator_apply(self._g, k, _p(lams, _dp), _p(p2, _dp), _p(r2, _dp), _p(q, _dp),
+                                                 _p(pq, _dp), _p(rp, _dp)))
+        if np.ndim(p) == 1:
+            return q[0], float(pq[0]), None if rp is None else float(rp[0])
+        return q, pq, rp
 
     def partition_plan(self, world, locality=True):
         """(vertex of every block row, row_begin, boundary rows per rank, cut edges); host only."""
