@@ -164,6 +164,9 @@ typedef struct sim3opt_options {
   double dl_delta_init;     /* 1e4   dogleg: trust radius at the first iteration of an optimize() (setUserDeltaInit) */
   double dl_lambda_init;    /* 1e-7  dogleg: first damping once H has not been positive definite (initialLambda)  */
   double dl_lambda_factor;  /* 10    dogleg: factor of that damping (setLamdbaFactor)                            */
+  double cov_workspace_mb;  /* 256   sim3opt_covariances / sim3opt_gate_edges: most device memory [MiB], at least 1, for
+                                     the root paths of L^-1 behind the blocks outside the factor's pattern; a larger
+                                     request is worked off in chunks (same bits)  [SIM3OPT_COV_WORKSPACE_MB]          */
 } sim3opt_options;
 
 /* options.algorithm */
@@ -402,6 +405,31 @@ int sim3opt_marginals(sim3opt_graph* g, double lambda, int32_t n, const int32_t*
                       const int32_t* id_b, double* cov);
 /* All free vertices' diagonal blocks, insertion order (nfree x 49); as sim3opt_marginals. */
 int sim3opt_marginal_covariances(sim3opt_graph* g, double lambda, double* cov);
+/* Blocks of (H + lambda I)^-1 for ANY pairs of free vertices -- two keyframes no edge joins yet, say; layout,
+ * lambda, errors and the one-GPU rule as sim3opt_marginals (a fixed or unknown vertex: SIM3OPT_ERR_ARG).  Pairs on
+ * the factor's pattern are the selected inversion's, the same bits as sim3opt_marginals returns.  The others are
+ * sums over the common ancestors of the two vertices in the elimination tree of W(k,a)^T W(k,b), W = L^-1
+ * (DESIGN.md section 5f), on the same factorisation: exactly zero between two components of the graph; each unordered
+ * pair computed once, the reversed pair its exact transpose; bits that do not depend on the order, the duplicates or
+ * the split of the request, on the schedule of the factorisation or on options.cov_workspace_mb (which bounds the
+ * device memory of one chunk; too small for the root paths of a single pair: SIM3OPT_ERR_STATE). */
+int sim3opt_covariances(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_a,
+                        const int32_t* id_b, double* cov);
+/* What the last sim3opt_marginals / _covariances / _gate_edges call did: {chunks of pairs outside the pattern,
+ * root paths walked, distinct pairs outside the pattern, pairs on it, workspace bytes, selected inversion run}. */
+int sim3opt_covariance_stats(const sim3opt_graph* g, int64_t out[6]);
+/* Chi-square gate of candidate edges that are NOT added to the graph (is this loop closure consistent with what the
+ * optimiser believes?).  Per candidate (id_v0, id_v1, meas as sim3opt_add_edge takes it, info column-major or NULL
+ * for I): e[7] = EdgeSim3's residual at the current estimates; S[49] (column-major) = J0 S00 J0^T + J0 S01 J1^T +
+ * J1 S10 J0^T + J1 S11 J1^T + info^-1 with the Jacobians of options.jacobians (0: central differences with fd_delta,
+ * 1: closed form; columns as sim3opt_edge_jacobians, dof_mask applied) and Sxy the blocks sim3opt_covariances returns
+ * (one factorisation per call; zero for a fixed endpoint); d2 = e^T S^-1 e, chi-square with 7 degrees of freedom
+ * under the linearised Gaussian model.  v0 == v1, an unknown id, a non-finite measurement or an info that is not
+ * symmetric positive definite: SIM3OPT_ERR_ARG, nothing written.  Other errors as sim3opt_covariances.  The graph,
+ * its estimates and the LM state are untouched. */
+int sim3opt_gate_edges(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_v0, const int32_t* id_v1,
+                       const double* meas /* n x 8 */, const double* info /* NULL = I, or n x 49 */,
+                       double* e /* n x 7 */, double* S /* n x 49 col-major */, double* d2 /* n */);
 /* Plan of the selected inversion (host only, no GPU needed, may be called before initialize), on the
  * factor plan of sim3opt_direct_plan (perm, colptr, lrow, gptr, lcolp as there).  Block s of Z is
  * ( Z0 - sum_p op(Z[za[p]]) L[zl[p]] ) L(j,j)^-1 over p in zptr[s]..zptr[s+1], in that order, where

@@ -64,6 +64,11 @@ namespace detail {
 template <class V> auto at(const V& v, int i, int) -> decltype(static_cast<double>(v[i])) { return v[i]; }
 template <class V> auto at(const V& v, int i, long) -> decltype(static_cast<double>(v(i))) { return v(i); }
 template <class V> double el(const V& v, int i) { return at(v, i, 0); }
+// stands in for the matrix type of an output nobody asked for (SparseOptimizer::gateEdge without S)
+struct NoBlock {
+  double& operator()(int, int) { return v; }
+  double v = 0.0;
+};
 // quaternion-like: has w()
 template <class T> auto is_quat(const T& q, int) -> decltype(static_cast<double>(q.w()), std::true_type());
 template <class T> std::false_type is_quat(const T&, long);
@@ -639,9 +644,9 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
   sim3opt_graph* handle() { return g_; }
 
   // Marginal covariances (g2o SparseOptimizer::computeMarginals): the blocks (r, c) of H^-1 at the current
-  // estimates for the listed pairs of hessianIndex() values -- a vertex with itself or the two ends of an
-  // edge -- into spinv.block(r, c).  False (spinv unchanged) when a pair is out of range or outside the
-  // factor's pattern, or H is singular; lastError() says why.  Needs initializeOptimization().
+  // estimates for the listed pairs of hessianIndex() values -- any two free vertices, as in g2o, joined by an
+  // edge or not (sim3opt_covariances) -- into spinv.block(r, c).  False (spinv unchanged) when an index is out
+  // of range or H is singular; lastError() says why.  Needs initializeOptimization().
   template <class M>
   bool computeMarginals(SparseBlockMatrix<M>& spinv, const std::vector<std::pair<int, int>>& blockIndices) {
     const int32_t n = (int32_t)blockIndices.size();
@@ -654,7 +659,7 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
       b[q] = free_ids_[c];
     }
     std::vector<double> cov(49 * (size_t)(n > 0 ? n : 1));
-    if (sim3opt_marginals(g_, 0.0, n, a.data(), b.data(), cov.data()) != SIM3OPT_OK) return false;
+    if (sim3opt_covariances(g_, 0.0, n, a.data(), b.data(), cov.data()) != SIM3OPT_OK) return false;
     for (int32_t q = 0; q < n; ++q) {
       M* m = spinv.block(blockIndices[q].first, blockIndices[q].second, true);
       for (int c = 0; c < 7; ++c)
@@ -666,6 +671,23 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
     if (!vertex || vertex->hessianIndex() < 0) return false;
     const int h = vertex->hessianIndex();
     return computeMarginals(spinv, std::vector<std::pair<int, int>>{{h, h}});
+  }
+  // Chi-square gate of a candidate edge BEFORE addEdge (the edge stays the caller's): d2 = e^T S^-1 e with
+  // S = J Sigma J^T + information^-1 (sim3opt_gate_edges), chi-square with 7 degrees of freedom if the candidate
+  // agrees with what the optimiser believes; S, when asked for, is that 7 x 7 matrix.  False (outputs unchanged)
+  // for an edge of another kind or without both vertices in this optimizer, or when the call fails.
+  template <class M = detail::NoBlock> bool gateEdge(const Edge& e, double& d2, M* S = nullptr) {
+    if (!e.v_[0] || !e.v_[1] || kind_ != GraphKind::Sim3 || e.kind() != kind_) return false;
+    double m[8], info[49], err[7], Sv[49], d = 0.0;
+    e.measurement(m);
+    const bool has = e.information77(info);
+    const int32_t a = e.v_[0]->id(), b = e.v_[1]->id();
+    if (sim3opt_gate_edges(g_, 0.0, 1, &a, &b, m, has ? info : nullptr, err, Sv, &d) != SIM3OPT_OK) return false;
+    d2 = d;
+    if (S)
+      for (int c = 0; c < 7; ++c)
+        for (int r = 0; r < 7; ++r) (*S)(r, c) = Sv[r + 7 * c];
+    return true;
   }
 
  private:

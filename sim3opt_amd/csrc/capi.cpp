@@ -189,6 +189,7 @@ void sim3opt_options_default(sim3opt_options* o) {
   o->dl_delta_init = 1e4;
   o->dl_lambda_init = 1e-7;
   o->dl_lambda_factor = 10.0;
+  o->cov_workspace_mb = 256.0;
 }
 
 // Debug overrides: a SIM3OPT_* environment variable replaces the option field of the same name when the
@@ -224,6 +225,9 @@ static void apply_env_overrides(sim3opt_options& o) {
   }
   if (const char* ev = std::getenv("SIM3OPT_DIRECT_MAX_PAIRS")) o.direct_max_pairs = std::atoll(ev);
   if (const char* ev = std::getenv("SIM3OPT_DEBUG_FULL_ARRAYS")) o.debug_full_arrays = std::atoi(ev) != 0;
+  // (a fraction of a MiB is accepted here only: tests chunk a small request that way)
+  if (const char* ev = std::getenv("SIM3OPT_COV_WORKSPACE_MB"))
+    if (std::atof(ev) > 0.0) o.cov_workspace_mb = std::atof(ev);
 }
 
 sim3opt_graph* sim3opt_create(void) {
@@ -260,6 +264,10 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
                   "set_options: dl_delta_init, dl_lambda_init and dl_lambda_factor must be finite and positive, "
                   "dl_max_trials at least 1");
   }
+  // (a fraction put there by the environment override comes back through get / change another field / set)
+  if ((!(o->cov_workspace_mb >= 1.0) && o->cov_workspace_mb != g->opt.cov_workspace_mb) ||
+      !std::isfinite(o->cov_workspace_mb))
+    return fail(g, SIM3OPT_ERR_ARG, "set_options: cov_workspace_mb must be finite and at least 1");
   if (o->jacobians == 1 && o->fix_small_angle_b != 1)
     return fail(g, SIM3OPT_ERR_ARG,
                 "set_options: jacobians = 1 needs fix_small_angle_b = 1 (the closed form differentiates the exact "
@@ -716,6 +724,99 @@ int sim3opt_marginals(sim3opt_graph* g, double lambda, int32_t n, const int32_t*
   return engine_marginals(g->engine, lambda, n, ra.data(), rb.data(), cov, g->err);
   } catch (...) {
     return fail(g, SIM3OPT_ERR_ARG, "marginals: out of host memory or internal error");
+  }
+}
+
+int sim3opt_covariances(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_a,
+                        const int32_t* id_b, double* cov) {
+  try {
+  if (!g || n < 0 || (n > 0 && (!id_a || !id_b || !cov))) return fail(g, SIM3OPT_ERR_ARG, "covariances: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "covariances: call sim3opt_initialize first");
+  std::vector<int32_t> ra(std::max(n, 1)), rb(std::max(n, 1));
+  for (int32_t q = 0; q < n; ++q) {
+    const auto a = g->host.id2idx.find(id_a[q]), b = g->host.id2idx.find(id_b[q]);
+    if (a == g->host.id2idx.end() || b == g->host.id2idx.end()) return fail(g, SIM3OPT_ERR_ARG, "covariances: unknown vertex id");
+    ra[q] = g->structure.hidx[a->second];
+    rb[q] = g->structure.hidx[b->second];
+    if (ra[q] < 0 || rb[q] < 0) return fail(g, SIM3OPT_ERR_ARG, "covariances: fixed vertex in a pair");
+  }
+  return engine_covariances(g->engine, lambda, n, ra.data(), rb.data(), cov, g->err);
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "covariances: out of host memory or internal error");
+  }
+}
+
+int sim3opt_covariance_stats(const sim3opt_graph* g, int64_t out[6]) {
+  if (!g || !out) return SIM3OPT_ERR_ARG;
+  if (!g->initialized) return SIM3OPT_ERR_STATE;
+  engine_covariance_stats(g->engine, out);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_gate_edges(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_v0, const int32_t* id_v1,
+                       const double* meas, const double* info, double* e, double* S, double* d2) {
+  try {
+  if (!g || n < 0 || (n > 0 && (!id_v0 || !id_v1 || !meas || !e || !S || !d2)))
+    return fail(g, SIM3OPT_ERR_ARG, "gate_edges: bad argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "gate_edges: call sim3opt_initialize first");
+  const size_t m = (size_t)std::max(n, 1);
+  std::vector<int32_t> v0(m), v1(m), r0(m), r1(m);
+  std::vector<sim3::Sim3> cm(m);
+  std::vector<double> oi(49 * m, 0.0);
+  for (int32_t q = 0; q < n; ++q) {
+    const auto a = g->host.id2idx.find(id_v0[q]), b = g->host.id2idx.find(id_v1[q]);
+    if (a == g->host.id2idx.end() || b == g->host.id2idx.end()) return fail(g, SIM3OPT_ERR_ARG, "gate_edges: unknown vertex id");
+    if (a->second == b->second) return fail(g, SIM3OPT_ERR_ARG, "gate_edges: identical endpoints");
+    if (!state_ok(meas + 8 * (size_t)q)) return fail(g, SIM3OPT_ERR_ARG, "gate_edges: non-finite measurement or scale <= 0");
+    v0[q] = a->second; v1[q] = b->second;
+    r0[q] = g->structure.hidx[a->second]; r1[q] = g->structure.hidx[b->second];
+    cm[q] = to_sim3(meas + 8 * (size_t)q);
+    double* W = &oi[49 * (size_t)q];  // Omega^-1, column-major
+    if (!info) {
+      for (int d = 0; d < 7; ++d) W[8 * d] = 1.0;
+      continue;
+    }
+    // Omega = L L^T (symmetric, positive definite: else refused), Omega^-1 = L^-T L^-1
+    const double* Om = info + 49 * (size_t)q;
+    double Lc[7][7] = {}, Li[7][7] = {};
+    double amax = 0.0;
+    for (int k = 0; k < 49; ++k) {
+      if (!std::isfinite(Om[k])) return fail(g, SIM3OPT_ERR_ARG, "gate_edges: non-finite information matrix");
+      amax = std::max(amax, std::fabs(Om[k]));
+    }
+    for (int c = 0; c < 7; ++c)
+      for (int r = 0; r < c; ++r)
+        if (std::fabs(Om[r + 7 * c] - Om[c + 7 * r]) > 1e-12 * amax)
+          return fail(g, SIM3OPT_ERR_ARG, "gate_edges: information matrix is not symmetric");
+    for (int j = 0; j < 7; ++j) {
+      double d = Om[8 * j];
+      for (int k = 0; k < j; ++k) d -= Lc[j][k] * Lc[j][k];
+      if (!(d > 0.0)) return fail(g, SIM3OPT_ERR_ARG, "gate_edges: information matrix is not positive definite");
+      Lc[j][j] = std::sqrt(d);
+      for (int r = j + 1; r < 7; ++r) {
+        double v = Om[r + 7 * j];
+        for (int k = 0; k < j; ++k) v -= Lc[r][k] * Lc[j][k];
+        Lc[r][j] = v / Lc[j][j];
+      }
+    }
+    for (int c = 0; c < 7; ++c)
+      for (int r = c; r < 7; ++r) {
+        double v = r == c ? 1.0 : 0.0;
+        for (int k = c; k < r; ++k) v -= Lc[r][k] * Li[k][c];
+        Li[r][c] = v / Lc[r][r];
+      }
+    for (int r = 0; r < 7; ++r)
+      for (int c = 0; c <= r; ++c) {
+        double v = 0.0;
+        for (int k = r; k < 7; ++k) v += Li[k][r] * Li[k][c];
+        W[r + 7 * c] = v;
+        W[c + 7 * r] = v;
+      }
+  }
+  return engine_gate_edges(g->engine, lambda, n, v0.data(), v1.data(), r0.data(), r1.data(), cm.data(), oi.data(), e, S,
+                           d2, g->err);
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "gate_edges: out of host memory or internal error");
   }
 }
 

@@ -1,5 +1,6 @@
 // direct_factor.hip -- BlockLdl (direct_factor.hpp): the one translation unit that holds and launches the exact
-// block Cholesky kernels (direct_kernels.hpp) and the selected inversion on their pattern (selinv_kernels.hpp).
+// block Cholesky kernels (direct_kernels.hpp), the selected inversion on their pattern (selinv_kernels.hpp) and the
+// blocks of the inverse outside it (cov_kernels.hpp).
 #include "direct_factor.hpp"
 
 #include <algorithm>
@@ -18,10 +19,12 @@ constexpr int WG = 256;  // the streaming kernels: 4 wavefronts of 64
 #include "direct_args.hpp"
 #include "direct_kernels.hpp"
 #include "selinv_kernels.hpp"
+#include "cov_kernels.hpp"
 
 struct BlockLdl::Dev {
   LdlArgs A{};
   SelArgs S{};  // (maxdiag_bits, singular: per call)
+  CovArgs C{};  // (W, wblocks: per call)
   int32_t* flags = nullptr;
 };
 
@@ -87,6 +90,17 @@ hipError_t BlockLdl::upload(hipStream_t stream, StagedUploads* staged) {
     S.L = A.L; S.Dinv = A.Dinv; S.nb = A.nb;
     alloc(p, 1);
     d_->flags = reinterpret_cast<int32_t*>(p);
+    // the elimination tree, for the blocks outside the pattern: parents have larger indices
+    parent_.assign(P.nb, -1);
+    depth_.assign(P.nb, 0);
+    for (int32_t j = P.nb - 1; j >= 0; --j)
+      if (P.colptr[j + 1] - P.colptr[j] > 1) {
+        parent_[j] = P.lrow[P.colptr[j] + 1];
+        depth_[j] = depth_[parent_[j]] + 1;
+      }
+    CovArgs& C = d_->C;
+    up(C.depth, depth_);
+    C.colptr = A.colptr; C.lrow = A.lrow; C.L = A.L; C.Dinv = A.Dinv; C.nb = A.nb;
   }
   ready_ = e == hipSuccess;
   return e;
@@ -123,12 +137,13 @@ hipError_t BlockLdl::factor(double lambda, int32_t* fail, int32_t token, double*
   return hipSuccess;
 }
 
-void BlockLdl::selinv(const unsigned long long* maxdiag_bits, int32_t* singular, hipStream_t stream) {
+void BlockLdl::selinv(const unsigned long long* maxdiag_bits, int32_t* singular, hipStream_t stream, bool invert) {
   SelArgs& S = d_->S;
   S.maxdiag_bits = maxdiag_bits;
   S.singular = singular;
   const int ng = plan_.ngroups();
   hipLaunchKernelGGL(k_selinv_pivots, dim3((7 * S.nb + WG - 1) / WG), dim3(WG), 0, stream, S);
+  if (!invert) return;
   hipLaunchKernelGGL(k_selinv, dim3(1), dim3(LDL_WG_TOP), 0, stream, S, ng - 1);
   if (ng > 1) hipLaunchKernelGGL(k_selinv, dim3(ng - 1), dim3(wg_sub_), 0, stream, S, 0);
 }
@@ -138,12 +153,31 @@ void BlockLdl::pick(const int32_t* slot, const int32_t* trans, int32_t n, double
                      trans, n, out);
 }
 
+void BlockLdl::cov_paths(const int32_t* vcol, const int32_t* voff, int32_t nv, double* W, int32_t wblocks,
+                         hipStream_t stream) {
+  CovArgs C = d_->C;
+  C.W = W;
+  C.wblocks = wblocks;
+  if (nv > 0) hipLaunchKernelGGL(k_cov_paths, dim3((nv + COV_NW - 1) / COV_NW), dim3(WG), 0, stream, C, vcol, voff, nv);
+}
+
+void BlockLdl::cov_pairs(const int32_t* pa, const int32_t* pb, const int32_t* plen, int32_t np, double* W,
+                         int32_t wblocks, double* out, hipStream_t stream) {
+  CovArgs C = d_->C;
+  C.W = W;
+  C.wblocks = wblocks;
+  if (np > 0)
+    hipLaunchKernelGGL(k_cov_pairs, dim3((np + COV_NW - 1) / COV_NW), dim3(WG), 0, stream, C, pa, pb, plen, np, out);
+}
+
 void BlockLdl::release() {
   for (void* p : owned_) dev_free(p);
   owned_.clear();
   *d_ = Dev{};
   plan_ = DirectPlan();
   sel_ = SelinvPlan();
+  parent_.clear();
+  depth_.clear();
   ready_ = false;
 }
 

@@ -40,10 +40,20 @@ class BlockLdl {
   // writes `token` into *fail.
   hipError_t factor(double lambda, int32_t* fail, int32_t token, double* x, hipStream_t stream);
   // after factor(): Z = (H + lambda I)^-1 on the pattern of L; a pivot below 1e-13 max |H_dd| (raw bits) sets
-  // *singular
-  void selinv(const unsigned long long* maxdiag_bits, int32_t* singular, hipStream_t stream);
+  // *singular.  invert = false: the pivot check alone (no block of Z is wanted).
+  void selinv(const unsigned long long* maxdiag_bits, int32_t* singular, hipStream_t stream, bool invert = true);
   // out[q] = block slot[q] of Z, transposed where trans[q] (device arrays of n)
   void pick(const int32_t* slot, const int32_t* trans, int32_t n, double* out, hipStream_t stream);
+  // Blocks of Z outside the pattern (cov_kernels.hpp), with the selected inversion's plan only.  The elimination
+  // tree: parent (-1: a root) and number of proper ancestors of every column.
+  const std::vector<int32_t>& tree_parent() const { return parent_; }
+  const std::vector<int32_t>& tree_depth() const { return depth_; }
+  // after factor(): column vcol[v] of L^-1 on its root path, depth + 1 blocks from block voff[v] of W (device
+  // arrays of nv; W holds wblocks blocks of 49)
+  void cov_paths(const int32_t* vcol, const int32_t* voff, int32_t nv, double* W, int32_t wblocks, hipStream_t stream);
+  // out[p] = sum_t W[pa[p] + t]^T W[pb[p] + t], t < plen[p] ascending (device arrays of np)
+  void cov_pairs(const int32_t* pa, const int32_t* pb, const int32_t* plen, int32_t np, double* W, int32_t wblocks,
+                 double* out, hipStream_t stream);
   void release();  // frees everything (the caller has synchronised) and forgets the plan
 
  private:
@@ -52,6 +62,7 @@ class BlockLdl {
   std::string knobs_;
   bool trace_ = false, ready_ = false;
   int wg_sub_ = 0;
+  std::vector<int32_t> parent_, depth_;
   struct Dev;               // the kernels' argument blocks: device copies of the plan, the buffers
   std::unique_ptr<Dev> d_;
   std::vector<void*> owned_;

@@ -47,6 +47,16 @@ int engine_solve(Engine* e, double lambda, double* x, int32_t* iters, double* re
 // blocks (row_a[q], row_b[q]) of (H + lambda I)^-1, H linearised at the current estimates (engine_direct.hip)
 int engine_marginals(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
                      std::string& err);
+// ... for any pair of free vertices (blocks outside the factor's pattern: cov_kernels.hpp), and what the last such
+// call did: {chunks, root paths walked, distinct pairs outside the pattern, pairs on it, workspace bytes, selected
+// inversion run}
+int engine_covariances(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
+                       std::string& err);
+void engine_covariance_stats(const Engine* e, int64_t out[6]);
+// chi-square gate of candidate edges (vertex indices, their block rows or -1 when fixed, Omega^-1 n x 49)
+int engine_gate_edges(Engine* e, double lambda, int32_t n, const int32_t* v0, const int32_t* v1, const int32_t* row0,
+                      const int32_t* row1, const sim3::Sim3* meas, const double* infoinv, double* e_out, double* S_out,
+                      double* d2_out, std::string& err);
 // diagnostic read-outs of the preconditioners (one GPU; the solver's state is left as it was)
 int engine_amg_level_numbers(Engine* e, double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals,
                              float* vals32, double* W, double* diagH, double* Minv, double* P, std::string& err);

@@ -1,8 +1,14 @@
 // engine_direct.hip -- when the LM solves exactly (LinearSolverEigen = SimplicialLDLT, kitti_surf.cpp:553-554), and
-// the marginal covariances (SparseOptimizer::computeMarginals); the factorisations are BlockLdl's (direct_factor.hpp)
+// the marginal covariances (SparseOptimizer::computeMarginals) with the gate of candidate edges on top of them; the
+// factorisations are BlockLdl's (direct_factor.hpp)
 #include "engine_impl.hpp"
+#include "sim3_jac.hpp"
+
+#include <unordered_map>
 
 namespace sim3opt {
+
+#include "gate_kernels.hpp"
 
 // plan (host, once per initialize) + buffers; leaves use_direct false when the factorisation
 // would be too expensive (the PCG takes over) unless the caller insists
@@ -74,83 +80,281 @@ int Engine::marginal_init(std::string& err) {
   return SIM3OPT_OK;
 }
 
-int Engine::marginals(double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
-                      std::string& err) {
+// The blocks (row_a[q], row_b[q]) of Z = (H + lambda I)^-1 behind sim3opt_marginals (any_pair false: a pair outside
+// the pattern of the factor is refused), sim3opt_covariances (any pair of free vertices) and sim3opt_gate_edges
+// (fixed_zero: a fixed endpoint, row -1, gives a zero block).  One linearisation, one factorisation; pairs on the
+// pattern are picked from the selected inversion (skipped when there is none), the others are computed once per
+// unordered pair -- block rows ascending -- by k_cov_paths / k_cov_pairs in chunks whose workspace stays within
+// options.cov_workspace_mb, and transposed for the reversed pair.
+int Engine::cov_blocks(const char* who, bool any_pair, bool fixed_zero, double lambda, int32_t n,
+                       const int32_t* row_a, const int32_t* row_b, double* cov, std::string& err) {
+  const std::string pre = std::string(who) + ": ";
   if (comm.world > 1) {
-    err = "marginals: one GPU only (the graph is partitioned over ranks)";
+    err = pre + "one GPU only (the graph is partitioned over ranks)";
     return SIM3OPT_ERR_STATE;
   }
   if (!(lambda >= 0.0) || !(lambda < DBL_MAX)) {
-    err = "marginals: lambda must be finite and >= 0";
+    err = pre + "lambda must be finite and >= 0";
     return SIM3OPT_ERR_ARG;
   }
   if (!marg_factor.ready()) {
     int rc = marginal_init(err);
     if (rc) return rc;
   }
+  for (int64_t& v : cov_stats) v = 0;
   // the requested blocks: Z(a, b) is block (pos a, pos b) of Z, stored in the lower triangle
   const DirectPlan& P = marg_factor.plan();
-  std::vector<int32_t> slot(std::max(n, 1)), trans(std::max(n, 1));
+  const std::vector<int32_t>& parent = marg_factor.tree_parent();
+  const std::vector<int32_t>& depth = marg_factor.tree_depth();
+  enum { ZERO = 0, ON = 1, OFF = 2 };
+  std::vector<int32_t> kind(std::max(n, 1)), where(std::max(n, 1)), flip(std::max(n, 1));
+  std::vector<int32_t> slot, trans;                  // pairs on the pattern, request order
+  std::vector<std::pair<int32_t, int32_t>> off;      // unordered pairs outside it, block rows ascending, first use
+  std::unordered_map<int64_t, int32_t> off_index;    // lo * nb + hi -> index into off
   for (int32_t q = 0; q < n; ++q) {
+    if (fixed_zero && (row_a[q] < 0 || row_b[q] < 0)) {
+      kind[q] = ZERO;
+      continue;
+    }
     if (row_a[q] < 0 || row_b[q] < 0 || row_a[q] >= nb || row_b[q] >= nb) {
-      err = "marginals: fixed vertex in a pair";
+      err = pre + "fixed vertex in a pair";
       return SIM3OPT_ERR_ARG;
     }
     const int32_t pa = mpos[row_a[q]], pb = mpos[row_b[q]];
     const int32_t i = std::max(pa, pb), j = std::min(pa, pb);
     const auto b = P.lrow.begin() + P.colptr[j], e = P.lrow.begin() + P.colptr[j + 1];
     const auto it = std::lower_bound(b, e, i);
-    if (it == e || *it != i) {
-      err = "marginals: pair outside the pattern of the factor (not a vertex with itself or an edge)";
+    if (it != e && *it == i) {
+      kind[q] = ON;
+      where[q] = (int32_t)slot.size();
+      slot.push_back((int32_t)(it - P.lrow.begin()));
+      trans.push_back(pa < pb ? 1 : 0);
+      continue;
+    }
+    if (!any_pair) {
+      err = pre + "pair outside the pattern of the factor (not a vertex with itself or an edge)";
       return SIM3OPT_ERR_ARG;
     }
-    slot[q] = (int32_t)(it - P.lrow.begin());
-    trans[q] = pa < pb ? 1 : 0;
+    kind[q] = OFF;
+    flip[q] = row_a[q] > row_b[q] ? 1 : 0;
+    const int32_t lo = std::min(row_a[q], row_b[q]), hi = std::max(row_a[q], row_b[q]);
+    const auto ins = off_index.emplace((int64_t)lo * nb + hi, (int32_t)off.size());
+    if (ins.second) off.push_back({lo, hi});
+    where[q] = ins.first->second;
   }
+  const int32_t n_on = (int32_t)slot.size(), n_off = (int32_t)off.size();
+  // ---- chunks of the pairs outside the pattern: index arrays [vcol, voff | pa, pb, plen] per chunk ----
+  struct Chunk { int32_t iv, nv, ip, np, p0, blocks; };
+  std::vector<Chunk> chunks;
+  std::vector<int32_t> idx;  // everything the device reads, one upload: slot, trans, then the chunks' arrays
+  idx.insert(idx.end(), slot.begin(), slot.end());
+  idx.insert(idx.end(), trans.begin(), trans.end());
+  if (n_off > 0) {
+    const double lim = opt.cov_workspace_mb * 1048576.0 / 392.0;
+    const int64_t limit = (int64_t)std::max(1.0, std::min(lim, 1073741824.0));
+    std::vector<int32_t> voff_of(nb, -1), members, vcol, voff, ca, cb, cl;
+    int64_t total = 0;
+    int32_t p0 = 0;
+    auto flush = [&]() {
+      Chunk c;
+      c.nv = (int32_t)vcol.size(); c.np = (int32_t)ca.size(); c.p0 = p0; c.blocks = (int32_t)total;
+      c.iv = (int32_t)idx.size();
+      idx.insert(idx.end(), vcol.begin(), vcol.end());
+      idx.insert(idx.end(), voff.begin(), voff.end());
+      c.ip = (int32_t)idx.size();
+      idx.insert(idx.end(), ca.begin(), ca.end());
+      idx.insert(idx.end(), cb.begin(), cb.end());
+      idx.insert(idx.end(), cl.begin(), cl.end());
+      chunks.push_back(c);
+      p0 += c.np;
+      for (int32_t r : members) voff_of[r] = -1;
+      members.clear(); vcol.clear(); voff.clear(); ca.clear(); cb.clear(); cl.clear();
+      total = 0;
+    };
+    for (const auto& pr : off) {
+      const int32_t ra = pr.first, rb = pr.second, ja = mpos[ra], jb = mpos[rb];
+      auto need_of = [&]() {
+        return (int64_t)(voff_of[ra] < 0 ? depth[ja] + 1 : 0) + (voff_of[rb] < 0 ? depth[jb] + 1 : 0);
+      };
+      if (total + need_of() > limit && !ca.empty()) flush();
+      if (total + need_of() > limit) {
+        err = pre + "options.cov_workspace_mb is too small for the root paths of one pair of this graph";
+        return SIM3OPT_ERR_STATE;
+      }
+      for (const int32_t r : {ra, rb})
+        if (voff_of[r] < 0) {
+          voff_of[r] = (int32_t)total;
+          members.push_back(r);
+          vcol.push_back(mpos[r]);
+          voff.push_back((int32_t)total);
+          total += depth[mpos[r]] + 1;
+        }
+      // the common suffix of the two root paths starts at the lowest common ancestor (none: another tree)
+      int32_t x = ja, y = jb;
+      while (depth[x] > depth[y]) x = parent[x];
+      while (depth[y] > depth[x]) y = parent[y];
+      while (x != y && x >= 0) { x = parent[x]; y = parent[y]; }
+      const int32_t len = x >= 0 && x == y ? depth[x] + 1 : 0;
+      ca.push_back(voff_of[ra] + (len ? depth[ja] - depth[x] : 0));
+      cb.push_back(voff_of[rb] + (len ? depth[jb] - depth[x] : 0));
+      cl.push_back(len);
+    }
+    if (!ca.empty()) flush();
+  }
+  int64_t wblocks = 1;
+  for (const Chunk& c : chunks) {
+    wblocks = std::max<int64_t>(wblocks, c.blocks);
+    cov_stats[1] += c.nv;
+  }
+  cov_stats[0] = (int64_t)chunks.size();
+  cov_stats[2] = n_off;
+  cov_stats[3] = n_on;
+  cov_stats[4] = n_off > 0 ? wblocks * 392 : 0;
+  cov_stats[5] = n_on > 0 ? 1 : 0;
   int rc = linearize(err);  // H (and b, unused) at the current estimates
   if (rc) return rc;
   int32_t* flags = marg_factor.selinv_flags();  // the factor's fail word, the singular flag
   HIPCHK(hipMemsetAsync(flags, 0, 2 * sizeof(int32_t), stream));
   marg_factor.gather(d_vals, d_b, stream);
   HIPCHK(marg_factor.factor(lambda, flags, 1, nullptr, stream));
-  marg_factor.selinv(&d_sc->maxdiag_bits, flags + 1, stream);
+  marg_factor.selinv(&d_sc->maxdiag_bits, flags + 1, stream, n_on > 0);
   HIPCHK(hipGetLastError());
-  int32_t *d_idx = nullptr;
-  double* d_out = nullptr;
+  const int32_t n_out = n_on + n_off;
+  int32_t* d_idx = nullptr;
+  double *d_out = nullptr, *d_W = nullptr;
   int32_t hflags[2] = {0, 0};
-  hipError_t e = dev_malloc((void**)&d_idx, sizeof(int32_t) * 2 * (size_t)std::max(n, 1));
-  if (e == hipSuccess) e = dev_malloc((void**)&d_out, sizeof(double) * 49 * (size_t)std::max(n, 1));
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_idx, slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_idx + n, trans.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && n > 0) {
-    marg_factor.pick(d_idx, d_idx + n, n, d_out, stream);
+  std::vector<double> out((size_t)49 * std::max(n_out, 1));
+  hipError_t e = dev_malloc((void**)&d_idx, sizeof(int32_t) * std::max<size_t>(idx.size(), 1));
+  if (e == hipSuccess) e = dev_malloc((void**)&d_out, sizeof(double) * 49 * (size_t)std::max(n_out, 1));
+  if (e == hipSuccess && n_off > 0) e = dev_malloc((void**)&d_W, sizeof(double) * 49 * (size_t)wblocks);
+  if (e == hipSuccess && !idx.empty())
+    e = hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && n_on > 0) {
+    marg_factor.pick(d_idx, d_idx + n_on, n_on, d_out, stream);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && n > 0) e = hipMemcpyAsync(cov, d_out, sizeof(double) * 49 * n, hipMemcpyDeviceToHost, stream);
+  for (const Chunk& c : chunks) {
+    if (e != hipSuccess) break;
+    marg_factor.cov_paths(d_idx + c.iv, d_idx + c.iv + c.nv, c.nv, d_W, (int32_t)wblocks, stream);
+    marg_factor.cov_pairs(d_idx + c.ip, d_idx + c.ip + c.np, d_idx + c.ip + 2 * c.np, c.np, d_W, (int32_t)wblocks,
+                          d_out + (size_t)49 * (n_on + c.p0), stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && n_out > 0)
+    e = hipMemcpyAsync(out.data(), d_out, sizeof(double) * 49 * n_out, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (d_idx) dev_free(d_idx);
   if (d_out) dev_free(d_out);
+  if (d_W) dev_free(d_W);
   if (e != hipSuccess) {
-    err = std::string("marginals: ") + hipGetErrorString(e);
+    err = pre + hipGetErrorString(e);
     return SIM3OPT_ERR_HIP;
   }
   const int32_t fail = hflags[0], singular = hflags[1];
   bool finite = true;
-  for (size_t k = 0; k < (size_t)49 * n && finite; ++k) finite = std::isfinite(cov[k]);
+  for (size_t k = 0; k < (size_t)49 * n_out && finite; ++k) finite = std::isfinite(out[k]);
   if (fail || singular || !finite) {
-    err = fail ? "marginals: H + lambda I is not positive definite (a non-positive pivot)"
-          : singular ? "marginals: H + lambda I is numerically singular (a pivot below 1e-13 max |H_dd|)"
-                     : "marginals: non-finite result";
+    err = pre + (fail ? "H + lambda I is not positive definite (a non-positive pivot)"
+                 : singular ? "H + lambda I is numerically singular (a pivot below 1e-13 max |H_dd|)"
+                            : "non-finite result");
     err += ": no fixed vertex, a masked degree of freedom, or lambda too small for this H";
     return SIM3OPT_ERR_STATE;
   }
+  for (int32_t q = 0; q < n; ++q) {
+    double* dst = cov + (size_t)49 * q;
+    if (kind[q] == ZERO) {
+      for (int k = 0; k < 49; ++k) dst[k] = 0.0;
+      continue;
+    }
+    const double* src = out.data() + (size_t)49 * (kind[q] == ON ? where[q] : n_on + where[q]);
+    if (kind[q] == OFF && flip[q]) {
+      for (int c = 0; c < 7; ++c)
+        for (int r = 0; r < 7; ++r) dst[r + 7 * c] = src[c + 7 * r];
+    } else {
+      std::memcpy(dst, src, sizeof(double) * 49);
+    }
+  }
+  return SIM3OPT_OK;
+}
+
+int Engine::marginals(double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
+                      std::string& err) {
+  return cov_blocks("marginals", false, false, lambda, n, row_a, row_b, cov, err);
+}
+
+// e, S = J Sigma J^T + Omega^-1 and d2 = e^T S^-1 e of candidate edges (vertex indices v0 / v1, their block rows or
+// -1; infoinv: Omega^-1, n x 49): nothing of the graph, the estimates or the LM's state is written
+int Engine::gate_edges(double lambda, int32_t n, const int32_t* v0, const int32_t* v1, const int32_t* row0,
+                       const int32_t* row1, const Sim3* meas, const double* infoinv, double* e_out, double* S_out,
+                       double* d2_out, std::string& err) {
+  std::vector<int32_t> ra((size_t)3 * std::max(n, 1)), rb((size_t)3 * std::max(n, 1));
+  for (int32_t q = 0; q < n; ++q) {
+    ra[3 * q] = row0[q]; rb[3 * q] = row0[q];
+    ra[3 * q + 1] = row0[q]; rb[3 * q + 1] = row1[q];
+    ra[3 * q + 2] = row1[q]; rb[3 * q + 2] = row1[q];
+  }
+  std::vector<double> sigma((size_t)147 * std::max(n, 1));
+  int rc = cov_blocks("gate_edges", true, true, lambda, 3 * n, ra.data(), rb.data(), sigma.data(), err);
+  if (rc || n == 0) return rc;
+  const size_t m = (size_t)n;
+  // one device buffer: measurements (8 m), Sigma (147 m), Omega^-1 (49 m), then e (7 m), S (49 m), d2 (m)
+  double* d_buf = nullptr;
+  int32_t* d_v = nullptr;
+  hipError_t e = dev_malloc((void**)&d_buf, sizeof(double) * 261 * m);
+  if (e == hipSuccess) e = dev_malloc((void**)&d_v, sizeof(int32_t) * 2 * m);
+  double *d_meas_c = d_buf, *d_sigma = d_buf + 8 * m, *d_oi = d_buf + 155 * m, *d_e = d_buf + 204 * m,
+         *d_S = d_buf + 211 * m, *d_d2 = d_buf + 260 * m;
+  static_assert(sizeof(Sim3) == 8 * sizeof(double), "Sim3 is eight doubles");
+  std::vector<double> res(57 * m);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_sigma, sigma.data(), sizeof(double) * 147 * m, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_oi, infoinv, sizeof(double) * 49 * m, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_meas_c, meas, sizeof(Sim3) * m, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_v, v0, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_v + m, v1, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    GateArgs G{n, d_v, d_v + m, reinterpret_cast<const Sim3*>(d_meas_c), d_sigma, d_oi, d_states, mopts(),
+               opt.jacobians, opt.dof_mask, opt.fd_delta, d_e, d_S, d_d2};
+    hipLaunchKernelGGL(k_gate_edges, dim3((n + WG - 1) / WG), dim3(WG), 0, stream, G);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_e, sizeof(double) * 57 * m, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (d_buf) dev_free(d_buf);
+  if (d_v) dev_free(d_v);
+  if (e != hipSuccess) {
+    err = std::string("gate_edges: ") + hipGetErrorString(e);
+    return SIM3OPT_ERR_HIP;
+  }
+  for (size_t k = 0; k < 57 * m; ++k)
+    if (!std::isfinite(res[k])) {
+      err = "gate_edges: the innovation covariance J Sigma J^T + Omega^-1 of a candidate is not positive definite";
+      return SIM3OPT_ERR_STATE;
+    }
+  std::memcpy(e_out, res.data(), sizeof(double) * 7 * m);
+  std::memcpy(S_out, res.data() + 7 * m, sizeof(double) * 49 * m);
+  std::memcpy(d2_out, res.data() + 56 * m, sizeof(double) * m);
   return SIM3OPT_OK;
 }
 
 int engine_marginals(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
                      std::string& err) {
   return e->marginals(lambda, n, row_a, row_b, cov, err);
+}
+
+int engine_covariances(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
+                       std::string& err) {
+  return e->cov_blocks("covariances", true, false, lambda, n, row_a, row_b, cov, err);
+}
+
+void engine_covariance_stats(const Engine* e, int64_t out[6]) {
+  for (int k = 0; k < 6; ++k) out[k] = e->cov_stats[k];
+}
+
+int engine_gate_edges(Engine* e, double lambda, int32_t n, const int32_t* v0, const int32_t* v1, const int32_t* row0,
+                      const int32_t* row1, const sim3::Sim3* meas, const double* infoinv, double* e_out, double* S_out,
+                      double* d2_out, std::string& err) {
+  return e->gate_edges(lambda, n, v0, v1, row0, row1, meas, infoinv, e_out, S_out, d2_out, err);
 }
 
 }  // namespace sim3opt

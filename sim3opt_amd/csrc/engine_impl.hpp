@@ -9,7 +9,7 @@
 //   engine_batch.hip   the multigrid PCG loop for several right-hand sides: an LM trial's solve (lm_trial_solve)
 //   engine_algorithms.hip  Gauss-Newton and Powell's dogleg (options.algorithm = 1 / 2)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
-// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, batch_kernels.hpp -> engine_batch.hip, algo_kernels.hpp -> engine_algorithms.hip, direct_ / selinv_kernels.hpp -> direct_factor.hip); only
+// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, batch_kernels.hpp -> engine_batch.hip, algo_kernels.hpp -> engine_algorithms.hip, gate_kernels.hpp -> engine_direct.hip, direct_ / selinv_ / cov_kernels.hpp -> direct_factor.hip); only
 // the SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through a method.
 #pragma once
 // (formerly all of engine.hip) -- device-resident Levenberg-Marquardt on a Sim(3) pose graph, gfx950 (MI355X).
@@ -454,6 +454,15 @@ class Engine {
   // estimates; rows are block rows of H (free vertices)
   int marginals(double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
                 std::string& err);
+  // the same for marginals (any_pair false), covariances (any pair) and the gate (fixed_zero: row -1 = zero block)
+  int cov_blocks(const char* who, bool any_pair, bool fixed_zero, double lambda, int32_t n, const int32_t* row_a,
+                 const int32_t* row_b, double* cov, std::string& err);
+  // of the last cov_blocks: chunks, root paths walked, distinct pairs outside the pattern, pairs on it, workspace
+  // bytes, selected inversion run (sim3opt_covariance_stats)
+  int64_t cov_stats[6] = {0, 0, 0, 0, 0, 0};
+  int gate_edges(double lambda, int32_t n, const int32_t* v0, const int32_t* v1, const int32_t* row0,
+                 const int32_t* row1, const Sim3* meas, const double* infoinv, double* e_out, double* S_out,
+                 double* d2_out, std::string& err);  // gate_kernels.hpp
   // block-Jacobi inverses Minv = omega (D + lambda W)^-1 of rows [lo, hi) (k_jacobi; engine_pcg.hip)
   void jacobi(int lo, int hi, const int32_t* rowptr, double* vals, double lambda, double* Minv, double omega,
               const double* diagH, const double* W, float* vals32, DevScalars* sc = nullptr,

@@ -74,6 +74,7 @@ class Options(C.Structure):
         ("dl_delta_init", C.c_double),
         ("dl_lambda_init", C.c_double),
         ("dl_lambda_factor", C.c_double),
+        ("cov_workspace_mb", C.c_double),
     ]
 
 
@@ -206,6 +207,9 @@ SYMBOLS = {
                                       _ip, _ip, _ip, _ip, _ip, _ip]),
     "sim3opt_marginals": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp]),
     "sim3opt_marginal_covariances": (C.c_int, [_vp, C.c_double, _dp]),
+    "sim3opt_covariances": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp]),
+    "sim3opt_covariance_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "sim3opt_gate_edges": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "sim3opt_marginal_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _ip,
                                         _ip, _ip, _ip]),
     "sim3opt_comm_allgather_plan": (C.c_int, [C.c_int32, C.c_int32, _ip, C.POINTER(C.c_int64),
@@ -713,6 +717,43 @@ class Graph:
         cov = np.empty((max(nb, 1), 49))
         self._chk(self._L.sim3opt_marginal_covariances(self._g, float(lam), _p(cov, _dp)))
         return cov[:nb].reshape(-1, 7, 7).transpose(0, 2, 1).copy()
+
+    def covariances(self, pairs, lam=0.0):
+        """Blocks (a, b) of (H + lam I)^-1 for ANY pairs of free vertices [(id_a, id_b), ...]: (n, 7, 7), laid out
+        as marginals() returns them (and the same bits for the pairs marginals() accepts)."""
+        pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, b = _i32(pr[:, 0]), _i32(pr[:, 1])
+        n = pr.shape[0]
+        cov = np.empty((max(n, 1), 49))
+        self._chk(self._L.sim3opt_covariances(self._g, float(lam), n, _p(a, _ip), _p(b, _ip), _p(cov, _dp)))
+        return cov[:n].reshape(-1, 7, 7).transpose(0, 2, 1).copy()
+
+    def covariance_stats(self):
+        """What the last marginals / covariances / gate_edges call did, as a dict."""
+        o = (C.c_int64 * 6)()
+        self._chk(self._L.sim3opt_covariance_stats(self._g, o))
+        keys = ("chunks", "paths", "off_pattern_pairs", "on_pattern_pairs", "workspace_bytes", "selinv")
+        return dict(zip(keys, (int(x) for x in o)))
+
+    def gate_edges(self, v0, v1, meas, info=None, lam=0.0, out=None):
+        """Chi-square gate of candidate edges that are not added: (e (n, 7), S (n, 7, 7), d2 (n,)) with
+        S = J Sigma J^T + info^-1 and d2 = e^T S^-1 e at the current estimates.  out: (e, S49, d2) arrays the
+        library writes into (S49: (n, 49) column-major blocks), returned as they are."""
+        a, b = _i32(np.atleast_1d(v0)), _i32(np.atleast_1d(v1))
+        n = a.shape[0]
+        m = _f64(meas).reshape(-1, 8)
+        inf = None
+        if info is not None:  # (n, 7, 7) [k, r, c] -> column-major blocks
+            inf = _f64(np.asarray(info).reshape(-1, 7, 7).transpose(0, 2, 1)).reshape(-1, 49)
+        if out is None:
+            e, S, d2 = np.empty((max(n, 1), 7)), np.empty((max(n, 1), 49)), np.empty(max(n, 1))
+        else:
+            e, S, d2 = out
+        self._chk(self._L.sim3opt_gate_edges(self._g, float(lam), n, _p(a, _ip), _p(b, _ip), _p(m, _dp),
+                                             _p(inf, _dp), _p(e, _dp), _p(S, _dp), _p(d2, _dp)))
+        if out is not None:
+            return out
+        return e[:n].copy(), S[:n].reshape(-1, 7, 7).transpose(0, 2, 1).copy(), d2[:n].copy()
 
     def marginal_plan(self, max_pairs=0):
         """Plan of the selected inversion (on the factor's plan) as a dict of numpy arrays; host only."""
