@@ -79,8 +79,10 @@ typedef struct sim3opt_options {
                                         the scale+translation stage, kitti_surf.cpp:1020-1024)    */
   int32_t pcg_max_iters;    /* 0 = automatic: 2n for n = 7*free vertices <= 50000, else 1000 */
   double pcg_rel_tol;       /* 1e-10 stop when ||r||_Minv <= tol * ||b||_Minv            */
-  int32_t pcg_check_every;  /* 16    PCG iterations between host convergence polls (at most 4 with the
-                                        multigrid preconditioner: its iterations are ~1 ms each)  */
+  int32_t pcg_check_every;  /* 16    most PCG iterations between two looks of the host at the solver's state (the
+                                        first chunk of a multigrid solve: at most 4, its iterations are ~1 ms
+                                        each); later chunks are sized by the iterations still predicted
+                                        (sim3opt_pcg_schedule_stats).  1 = one iteration per look, no prediction */
   int32_t pcg_graph;        /* 1     replay the PCG iterations from a captured hipGraph (single GPU,
                                         time_kernels = 0); 0 = enqueue every launch               */
   int32_t preconditioner;   /* -1    0 = 7x7 block-Jacobi, 1 = block-tridiagonal chain segments,
@@ -320,6 +322,13 @@ int sim3opt_get_trust_region_stats(const sim3opt_graph* g, int32_t iter, sim3opt
 int sim3opt_get_kernel_times(sim3opt_graph* g, sim3opt_kernel_times* out);
 int sim3opt_reset_kernel_times(sim3opt_graph* g);   /* (also clears the collectives' times) */
 int sim3opt_get_comm_times(sim3opt_graph* g, sim3opt_comm_times* out);
+/* How the PCG loops were scheduled since initialize / the last reset (reset != 0 here, or sim3opt_reset_kernel_times):
+ * out[0] iterations enqueued, out[1] of them enqueued after the device had raised `done` (enqueued - executed),
+ * out[2] looks at the solver's scalars in the iteration loops that synchronised with an empty queue behind them,
+ * out[3] looks that were waited for with the next chunk already queued.  The host sizes its chunks from the
+ * reduction per iteration it has seen (options.pcg_check_every caps them; 1: one iteration per look, no prediction);
+ * the stopping iteration is the device's decision, so none of this shows in a result.  out may be NULL. */
+int sim3opt_pcg_schedule_stats(sim3opt_graph* g, int64_t out[4], int32_t reset);
 
 /* ---- kernel-level access (parity tests against the CPU oracle, bench roofline) ---- */
 /* per-edge residuals e (m x 7), edge insertion order                EdgeSim3::computeError */

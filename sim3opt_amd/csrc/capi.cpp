@@ -568,6 +568,13 @@ int sim3opt_reset_kernel_times(sim3opt_graph* g) {
   return engine_kernel_times(g->engine, nullptr, true);
 }
 
+int sim3opt_pcg_schedule_stats(sim3opt_graph* g, int64_t out[4], int32_t reset) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "pcg_schedule_stats: not initialized");
+  engine_pcg_schedule_stats(g->engine, out, reset != 0);
+  return SIM3OPT_OK;
+}
+
 int sim3opt_edge_errors(sim3opt_graph* g, double* e_out) {
   if (!g || !e_out) return fail(g, SIM3OPT_ERR_ARG, "edge_errors: null argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "edge_errors: call sim3opt_initialize first");

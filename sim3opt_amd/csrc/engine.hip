@@ -55,6 +55,10 @@ void Engine::release_under_device() {
   marg_factor.release();
   staged.release();
   if (h_sc) host_free(h_sc);
+  if (h_ring) host_free(h_ring);
+  h_ring = nullptr;
+  if (ring_ev) event_release(ring_ev);
+  ring_ev = nullptr;
   if (h_dl) host_free(h_dl);
   for (hipEvent_t e : pool) event_release(e);
   for (hipEvent_t e : rep_pool) event_release(e);
@@ -231,6 +235,8 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
   HIPCHK(dev_malloc((void**)&d_sc, sizeof(DevScalars)));
   HIPCHK(hipMemset(d_sc, 0, sizeof(DevScalars)));
   HIPCHK(host_malloc((void**)&h_sc, sizeof(DevScalars)));
+  HIPCHK(host_malloc((void**)&h_ring, sizeof(DevScalars) * KB));
+  HIPCHK(event_acquire(&ring_ev));
   if (use_amg) {  // level 0 aliases the system's own arrays, vectors, scalars and partial sums
     int rc = amg_bind(s, err);
     if (rc) return rc;
@@ -256,6 +262,19 @@ int Engine::fetch_scalars(std::string& err) {
   HIPCHK(hipMemcpyAsync(h_sc, d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   if (comm.timing && comm.ev_used) return comm.drain(err);
+  return SIM3OPT_OK;
+}
+
+int Engine::poll_async(const DevScalars* src, int nsc, std::string& err) {
+  HIPCHK(hipMemcpyAsync(h_ring, src, sizeof(DevScalars) * nsc, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipEventRecord(ring_ev, stream));
+  return SIM3OPT_OK;
+}
+
+int Engine::poll_wait(DevScalars* dst, int nsc, std::string& err) {
+  HIPCHK(hipEventSynchronize(ring_ev));
+  std::memcpy(dst, h_ring, sizeof(DevScalars) * nsc);
+  sched_stats[3] += 1;
   return SIM3OPT_OK;
 }
 
@@ -768,8 +787,16 @@ int engine_kernel_times(Engine* e, sim3opt_kernel_times* out, bool reset) {
   if (reset) {
     e->kt = sim3opt_kernel_times{};
     e->comm.times = sim3opt_comm_times{};
+    for (int64_t& v : e->sched_stats) v = 0;
   }
   return SIM3OPT_OK;
+}
+
+void engine_pcg_schedule_stats(Engine* e, int64_t out[4], bool reset) {
+  for (int i = 0; i < 4; ++i) {
+    if (out) out[i] = e->sched_stats[i];
+    if (reset) e->sched_stats[i] = 0;
+  }
 }
 
 int engine_comm_times(Engine* e, sim3opt_comm_times* out) {

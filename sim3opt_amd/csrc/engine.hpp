@@ -77,6 +77,9 @@ void engine_amg_in_use(const Engine* e, int32_t* n_levels, int32_t* n_partitione
 void engine_device_bytes(const Engine* e, int64_t bytes[2]);
 int engine_kernel_times(Engine* e, sim3opt_kernel_times* out, bool reset);
 int engine_comm_times(Engine* e, sim3opt_comm_times* out);
+// the PCG loops' schedule since the last reset: {iterations enqueued, of them after `done`, polls that synchronised
+// with an empty queue behind them, polls waited for with the next chunk queued}
+void engine_pcg_schedule_stats(Engine* e, int64_t out[4], bool reset);
 #ifdef SIM3OPT_BENCH_HOOKS
 int engine_bench_spmv_symmetric(Engine* e, int32_t reps, double out[4], std::string& err);
 int engine_bench_spmv_rowlane(Engine* e, int32_t reps, int32_t rows_per_group, double out[8], std::string& err);

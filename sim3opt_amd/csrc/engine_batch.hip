@@ -135,21 +135,20 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   for (int s = 0; s < nsys; ++s)
     if (h_bsc[s].fail) return SIM3OPT_OK;  // a non-positive pivot of some set-up: not usable
   amg_cycle(cv_batch, 0, b_z, b_az);
-  const int chunk = std::min(4, std::max(1, opt.pcg_check_every));
-  int it = 0, par = 0;
-  for (;;) {
-    HIPCHK(hipMemcpyAsync(h_bsc, d_bsc, sizeof(DevScalars) * KB, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    // systems still iterating: [0, live).  The dampings ascend with the trial, so the systems finish from the
-    // tail as a rule; the launches that follow carry the first `live` systems only (per system the same
-    // operations whatever K is: the results do not depend on when the others finished)
-    int live = 0;
-    for (int s = 0; s < nsys; ++s)
-      if (!(h_bsc[s].done || h_bsc[s].stop || h_bsc[s].fail)) live = s + 1;
-    if (live == 0 || it >= max_it) break;
-    cv_batch.nsys = live;
-    const int todo = std::min(chunk, max_it - it);
-    for (int c = 0; c < todo; ++c) {
+  // chunks and looks as in pcg_attempt: the prediction is per system, a chunk ends where the first of the live
+  // systems is predicted to finish -- so that `live` shrinks then and not up to three K-system iterations later
+  const int pce = std::max(1, opt.pcg_check_every);
+  const int chunk = std::min(4, pce);
+  const bool predict = pce > 1;
+  const int cap = pce >= 4 ? std::min(pce, std::max(4, sched_cap_mg)) : pce;
+  int it = 0, par = 0, seen = 0, live = 0;
+  // (the cycle after a chunk's last step goes to the head of the next chunk, as in pcg_attempt: the step that
+  // finishes the last live system is not followed by a K-system cycle nobody reads)
+  bool cycle_pending = false;
+  auto enqueue = [&](int count) -> int {
+    if (cycle_pending) amg_cycle(cv_batch, 0, b_z, b_az);
+    cycle_pending = false;
+    for (int c = 0; c < count; ++c) {
       BATCH_DISPATCH(live, hipLaunchKernelGGL((k_spmv_span<8, true, 0, double, KS, false>), dim3(gs), dim3(WG), 0, stream,
                          nb, d_wrow, d_rowptr, d_colidx, (const double*)d_vals, (const double*)b_az, b_q, 0.0, b_part_a,
                          (const double*)nullptr, b_part_b, d_bsc, (const double*)nullptr, 1, (const int32_t*)nullptr, 1.0,
@@ -159,11 +158,67 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
       BATCH_DISPATCH(live, hipLaunchKernelGGL((k_pcg_step_k<KS>), dim3(gv), dim3(WG), 0, stream, 0, nb, par, it,
                          (const double*)B0.Minv, (const double*)b_az, b_z, (const double*)b_q, b_p, b_s, b_x, b_r, d_bsc,
                          bs0));
-      amg_cycle(cv_batch, 0, b_z, b_az);
+      if (c + 1 == count) cycle_pending = true;
+      else amg_cycle(cv_batch, 0, b_z, b_az);
       par ^= 1;
       ++it;
     }
+    sched_stats[0] += count;
     HIPCHK(hipGetLastError());
+    return SIM3OPT_OK;
+  };
+  PcgRate rate[KB];
+  const int64_t enq0 = sched_stats[0];
+  // (the set-up's look above is the loop's first: no step has run since)
+  bool have = predict;
+  for (;;) {
+    if (!have) {
+      HIPCHK(hipMemcpyAsync(h_bsc, d_bsc, sizeof(DevScalars) * KB, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      sched_stats[2] += 1;
+      seen = it;
+    }
+    have = false;
+    // systems still iterating: [0, live).  The dampings ascend with the trial, so the systems finish from the
+    // tail as a rule; the launches that follow carry the first `live` systems only (per system the same
+    // operations whatever K is: the results do not depend on when the others finished)
+    live = 0;
+    for (int s = 0; s < nsys; ++s)
+      if (!(h_bsc[s].done || h_bsc[s].stop || h_bsc[s].fail)) live = s + 1;
+    if (opt.verbose >= 3)
+      for (int s = 0; s < nsys; ++s)
+        std::fprintf(stderr, "  batch look: system %d, enqueued %d, seen %d, iter %d, r.z %.6e of %.6e (tol2 %.3e), done %d\n", s,
+                     it, seen, h_bsc[s].iter, std::fabs(h_bsc[s].gam_last), h_bsc[s].rz0, h_bsc[s].tol2, h_bsc[s].done);
+    if (live == 0 || seen >= max_it) break;
+    double rem = -1.0;  // iterations beyond the `it` enqueued until the first of the live systems finishes
+    if (predict) {
+      double xmin = DBL_MAX;
+      for (int s = 0; s < live; ++s) {
+        const DevScalars& h = h_bsc[s];
+        if (h.done || h.stop || h.fail) continue;
+        rate[s].look(h.iter, h.rz0, h.gam_last);
+        const double x = rate[s].remaining(h.tol2 * h.rz0);
+        xmin = x < 0.0 ? -1.0 : std::min(xmin, x);
+        if (x < 0.0) break;
+      }
+      if (xmin >= 0.0) rem = std::max(0.0, xmin - (double)(it - seen));
+    }
+    const int todo = std::min(sched_chunk(rem, chunk, cap), max_it - it);
+    if (seen < it && (todo <= 0 || rem == 0.0)) continue;  // all that is predicted is in the queue: wait for it
+    cv_batch.nsys = live;
+    rc = enqueue(todo);
+    if (rc) return rc;
+    const int ahead = rem >= 0.0 ? std::min(sched_ahead(rem - todo, cap), max_it - it) : 0;
+    if (ahead >= 2) {  // no system is predicted to finish in the next chunk either: look without draining the queue
+      rc = poll_async(d_bsc, KB, err);
+      if (rc) return rc;
+      seen = it;
+      rc = enqueue(ahead);
+      if (rc) return rc;
+      rc = poll_wait(h_bsc, KB, err);
+      if (rc) return rc;
+      have = true;
+    }
   }
   // what the stopping test claims, checked in the 2-norm per system (see pcg_attempt)
   bool good = true;
@@ -174,6 +229,8 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_bsc, d_bsc, sizeof(DevScalars) * KB, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
+  // (the batch's counter starts at zero: K-system iterations that found every system finished)
+  sched_stats[1] += std::max<int64_t>(0, (sched_stats[0] - enq0) - (int64_t)h_bsc[0].n_spmv_work);
   int it_max = 0;
   for (int s = 0; s < nsys; ++s) {
     const DevScalars& h = h_bsc[s];

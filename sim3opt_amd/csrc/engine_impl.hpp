@@ -113,6 +113,42 @@ struct DevScalars {
   double trace;           // sum of the scalar diagonal of H (mean |H_dd|: when is a system damping-dominated?)
 };
 
+// What the host has seen of one system's r.z at its looks into DevScalars, and what that predicts (host only; it
+// sizes the chunks of the PCG loops and decides nothing else).  A look after `iter` executed steps carries gam_last =
+// r.z of the residual BEFORE step `iter`, i.e. after iter - 1 updates; rz0 is the same quantity before step 1.
+struct PcgRate {
+  static constexpr int NL = 8, SPAN = 4;
+  int k[NL];
+  double g[NL];
+  int n = 0;
+  void look(int iter, double rz0, double gam) {
+    if (iter < 1) return;
+    if (n == 0) { k[0] = 1; g[0] = std::fabs(rz0); n = 1; }
+    if (iter <= k[n - 1]) return;
+    if (n == NL) {
+      for (int i = 1; i < NL; ++i) { k[i - 1] = k[i]; g[i - 1] = g[i]; }
+      --n;
+    }
+    k[n] = iter; g[n] = std::fabs(gam); ++n;
+  }
+  // Launches still needed after the last look until the step that sees r.z <= target and raises `done` (that step
+  // included), at the reduction per iteration between the last look and the latest one at least SPAN iterations
+  // before it (r.z of CG is not monotone: a rate over one or two iterations is noise).  < 0: no rate yet, or none.
+  double remaining(double target) const {
+    if (n < 2) return -1.0;
+    int a = 0;
+    for (int i = n - 2; i > 0; --i)
+      if (k[i] <= k[n - 1] - SPAN) { a = i; break; }
+    const double gb = g[n - 1];
+    while (a > 0 && !(g[a] > gb)) --a;  // (r.z went up in between: the rate over a longer stretch)
+    const double ga = g[a];
+    if (!(ga > 0.0) || !(gb > 0.0) || !(gb < ga) || !(target > 0.0)) return -1.0;
+    if (gb <= target) return 0.0;
+    const double x = (double)(k[n - 1] - k[a]) * std::log(target / gb) / std::log(gb / ga);
+    return std::isfinite(x) ? std::max(x, 0.0) : -1.0;
+  }
+};
+
 #include "dev_common.hpp"
 struct EdgeArgs;  // lm_kernels.hpp
 
@@ -365,6 +401,38 @@ class Engine {
   int init(const HostGraph& g, const Structure& s, std::string& err);
 
   int fetch_scalars(std::string& err);
+
+  // ---- the PCG loops' schedule (pcg_attempt, pcg_batch) ----
+  // The stopping decision is the device's; the host only chooses how many iterations to enqueue before it looks
+  // again.  From two looks it has the reduction of r.z per iteration and from that the iterations still needed
+  // (PcgRate); chunks are sized by it, and while more than one chunk is predicted the look at chunk k is an
+  // asynchronous copy into a pinned slot + an event, waited for with chunk k + 1 already in the queue.  Only one
+  // such look is ever outstanding, so there is one slot and one event.
+  DevScalars* h_ring = nullptr;  // pinned, KB
+  hipEvent_t ring_ev = nullptr;
+  // longest multigrid chunk once a rate is known, and the share of the predicted remainder that is enqueued: the
+  // prediction is a straight line through a curve that bends either way, and what an iteration too many costs
+  // against a look too many is measured in DESIGN.md section 5 (neither value has been tuned)
+  static constexpr int sched_cap_mg = 8;
+  static constexpr double sched_frac = 0.85;
+  // iterations to enqueue now when `rem` more are predicted (rem < 0: no rate -> `fixed`), at most cap
+  int sched_chunk(double rem, int fixed, int cap) const {
+    if (rem < 0.0) return fixed;
+    return std::max(1, std::min(cap, (int)std::floor(sched_frac * rem)));
+  }
+  // ... and behind them, before the look at them is waited for (0: that look synchronises): half of what is
+  // predicted beyond the chunk -- these are enqueued on a rate one chunk older
+  int sched_ahead(double left, int cap) const {
+    const int c = std::min(cap, (int)std::floor(0.5 * left));
+    return c >= 2 ? c : 0;
+  }
+  // enqueues the copy of nsc DevScalars from `src` into the slot and its event
+  int poll_async(const DevScalars* src, int nsc, std::string& err);
+  // waits for that event and copies the slot to dst (h_sc or h_bsc)
+  int poll_wait(DevScalars* dst, int nsc, std::string& err);
+  // since the last reset: {iterations enqueued, enqueued after `done` (enqueued - executed), polls that synchronised
+  // with nothing queued behind them, polls waited for with the next chunk queued}
+  int64_t sched_stats[4] = {0, 0, 0, 0};
 
   // ---- timing helpers ----
   int phase_ms(int a, int b, double& acc, std::string& err);  // acc += stamp ev_ph[a] -> ev_ph[b] (both complete)

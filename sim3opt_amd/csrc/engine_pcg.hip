@@ -132,8 +132,8 @@ int Engine::spmv_launch(double lambda, const double* z, const double* rv, std::s
 }
 
 // Preconditioned CG on (H + lambda I) x = b in the single-reduction form (k_pcg_step); the
-// result stays in d_x.  Two launches and one reduction point per iteration; the host only polls
-// a 100-byte struct every `pcg_check_every` iterations.
+// result stays in d_x.  Two launches and one reduction point per iteration; the host only looks at
+// one small struct between chunks of iterations (see `chunk` in pcg_attempt).
 int Engine::agree_on_fail(std::string& err) {  // multi-GPU: fail on any rank = fail on all
   hipLaunchKernelGGL(k_fail_to_double, dim3(1), dim3(1), 0, stream, d_sc);
   int rc = comm.allreduce(&d_sc->tmp_pq, 1, 1, stream, err);
@@ -308,10 +308,16 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
     rc = exchange_rows(d_z, err);
     if (rc) return rc;
   }
-  // (a multigrid iteration is ~1 ms of GPU work and its coarse launches run even after `done`:
-  // poll more often)
-  const int chunk = use_mg ? std::min(4, std::max(1, opt.pcg_check_every))
-                           : (probe ? 8 : std::max(1, opt.pcg_check_every));
+  // Iterations per look into DevScalars.  Without a rate -- the first chunk of a solve, pcg_check_every = 1, the
+  // probe, several ranks (their collectives need the same count on every rank) -- a fixed number: pcg_check_every,
+  // for the multigrid at most 4 (an iteration is ~1 ms of GPU work and its coarse launches run even after `done`).
+  // With one (PcgRate) the share sched_frac of the iterations still predicted, at most `cap`: long chunks while the
+  // end is far, single iterations next to it.  The prediction sizes chunks and nothing else: `done`, `stop` and
+  // `fail` are raised on the device, a wrong guess costs a poll or an idle iteration.
+  const int pce = std::max(1, opt.pcg_check_every);
+  const int chunk = use_mg ? std::min(4, pce) : (probe ? 8 : pce);
+  const bool predict = !multi && !probe && pce > 1;
+  const int cap = use_mg ? (pce >= 4 ? std::min(pce, std::max(4, sched_cap_mg)) : pce) : pce;
   int it = 0, par = 0;
   // Launch-bound regime (small graphs: two ~3 us kernels per iteration): replay a captured
   // hipGraph of PCG_GRAPH_ITERS iterations instead of enqueueing them one by one.  The first
@@ -351,67 +357,154 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
     (void)hipGraphDestroy(gr);
     pcg_graph_kind = prec;
   }
-  for (;;) {
-    rc = fetch_scalars(err);
-    if (rc) return rc;
-    if (opt.time_kernels) {
-      rc = pool_drain(err);
-      if (rc) return rc;
-    } else {
-      spmv_work_seen = h_sc->n_spmv_work;
+  // enqueues `count` iterations -- whole replays of the captured graph where it applies (then fewer than asked
+  // for unless count is a multiple of graph_iters), one by one otherwise
+  // A chunk ends with k_pcg_step, the launch that decides: z = M^-1 r of a chunk's last step (chain segments, the
+  // multigrid cycle: ~0.3 ms of coarse launches that run whether the solve has finished or not) is enqueued at the
+  // head of the next chunk -- so the step that finds the tolerance met is not followed by a cycle nobody reads.
+  // (Several ranks: the cycle's collectives and the exchange of z stay where they were.)
+  const bool defer_prec = !multi && (use_chain || use_mg);
+  bool prec_pending = false;
+  auto apply_prec = [&]() -> int {
+    if (use_chain)
+      hipLaunchKernelGGL(k_chain_apply, dim3(gc), dim3(WG), 0, stream, r0, r1, chain_seg,
+                         d_Minv, d_Gm, d_r, d_z, (const DevScalars*)d_sc);
+    if (use_mg) return amg_apply(err);
+    return SIM3OPT_OK;
+  };
+  auto enqueue = [&](int count) -> int {
+    if (prec_pending) {
+      int rc2 = apply_prec();
+      if (rc2) return rc2;
+      prec_pending = false;
     }
-    if (h_sc->done || h_sc->stop || h_sc->fail || it >= max_it) break;
+    if (graphed && it > 0 && par == 1 && count >= graph_iters) {
+      // steps past max_iter cannot happen: the step that reaches it raises `stop`, and the
+      // following launches of the replay are no-ops
+      const int reps = count / graph_iters;
+      for (int k = 0; k < reps; ++k) HIPCHK(hipGraphLaunch(pcg_graph, stream));
+      it += reps * graph_iters;
+      sched_stats[0] += reps * graph_iters;
+      return SIM3OPT_OK;
+    }
+    for (int c = 0; c < count; ++c) {
+      int rc2 = spmv_launch(lambda, zin, spmv_r, err);
+      if (rc2) return rc2;
+      if (pre_sum)  // [w.z, r.z] -> tmp_pq, tmp_rz (adjacent)
+        hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gs,
+                           &d_sc->tmp_pq);
+      if (multi) {  // one 2-double all-reduce
+        rc2 = comm.allreduce(&d_sc->tmp_pq, 2, 0, stream, err);
+        if (rc2) return rc2;
+      }
+      hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(WG), 0, stream, r0, r1, par, it, scal,
+                         d_part_a, d_part_b, gs, Minv_arg, (const double*)zin, d_z, d_q, d_p, d_s,
+                         d_x, d_r, d_sc);
+      if (defer_prec && c + 1 == count) {
+        prec_pending = true;
+      } else {
+        rc2 = apply_prec();
+        if (rc2) return rc2;
+      }
+      if (multi && !use_mg) {  // the next SpMV gathers z from the neighbouring ranks
+        rc2 = exchange_rows(d_z, err);
+        if (rc2) return rc2;
+      }
+      par ^= 1;
+      ++it;
+    }
+    sched_stats[0] += count;
+    HIPCHK(hipGetLastError());
+    return SIM3OPT_OK;
+  };
+  // a look with nothing queued behind it: h_sc is fresh and every recorded event complete
+  auto poll_sync = [&]() -> int {
+    int rc2 = fetch_scalars(err);
+    if (rc2) return rc2;
+    sched_stats[2] += 1;
+    if (opt.time_kernels) return pool_drain(err);
+    spmv_work_seen = h_sc->n_spmv_work;
+    return SIM3OPT_OK;
+  };
+  // The captured graph starts at par == 1.  An eager chunk of several iterations on that path is cut by one where
+  // it would end at par == 0, so that whole graphs can be replayed again should the prediction grow (single
+  // iterations next to the end are left alone: two of them restore the parity).
+  auto keep_parity = [&](int n) { return graphed && it > 0 && n > 1 && n < graph_iters && ((par ^ (n & 1)) == 0) ? n - 1 : n; };
+  PcgRate rate;
+  int seen = 0;  // iterations that were enqueued before the look h_sc holds (seen < it: chunks still in the queue)
+  const int64_t enq0 = sched_stats[0];
+  // The set-up's fetch above has just read the scalars and no step has run since: with a prediction to make up
+  // for it the loop's first look is left out (it would only drain the queue the first cycle sits in).
+  bool have = predict && (use_chain || use_mg);
+  long long work0 = have ? h_sc->n_spmv_work : -1;
+  if (have && !opt.time_kernels) spmv_work_seen = h_sc->n_spmv_work;
+  for (;;) {
+    if (!have) {
+      rc = poll_sync();
+      if (rc) return rc;
+      seen = it;
+    }
+    have = false;
+    if (work0 < 0) work0 = h_sc->n_spmv_work;
+    if (opt.verbose >= 3)
+      std::fprintf(stderr, "  pcg look: enqueued %d, seen %d, iter %d, r.z %.6e of %.6e (tol2 %.3e), done %d\n", it, seen,
+                   h_sc->iter, std::fabs(h_sc->gam_last), h_sc->rz0, h_sc->tol2, h_sc->done);
+    if (h_sc->done || h_sc->stop || h_sc->fail || seen >= max_it) break;
     if (probe && it >= 8 && h_sc->rz0 > 0.0) {
       // squared M^-1-norm reduction after `it` iterations -> iterations to the tolerance at that rate
       const double ratio = std::fabs(h_sc->gam_last) / h_sc->rz0;
       const double need = ratio > 0.0 && ratio < 1.0 ? it * std::log(h_sc->tol2) / std::log(ratio) : 1e30;
       if (need > probe_budget) break;
     }
-    if (graphed && it > 0 && par == 1 && max_it - it >= graph_iters) {
-      // steps past max_iter cannot happen: the step that reaches it raises `stop`, and the
-      // following launches of the replay are no-ops
-      const int reps = std::max(1, std::min(chunk, max_it - it) / graph_iters);
-      for (int k = 0; k < reps; ++k) HIPCHK(hipGraphLaunch(pcg_graph, stream));
-      it += reps * graph_iters;
-      continue;
+    double rem = -1.0;  // iterations predicted to be needed beyond the `it` enqueued
+    if (predict) {
+      rate.look(h_sc->iter, h_sc->rz0, h_sc->gam_last);
+      const double x = rate.remaining(h_sc->tol2 * h_sc->rz0);
+      if (x >= 0.0) rem = std::max(0.0, x - (double)(it - seen));
     }
-    const int todo = graphed && it == 0 ? 1 : std::min(chunk, max_it - it);
-    for (int c = 0; c < todo; ++c) {
-      rc = spmv_launch(lambda, zin, spmv_r, err);
+    int todo = graphed && it == 0 ? 1 : std::min(sched_chunk(rem, chunk, cap), max_it - it);
+    if (seen < it && (todo <= 0 || rem == 0.0)) continue;  // all that is predicted is in the queue: wait for it
+    if (graphed && it > 0 && par == 1 && todo >= graph_iters) todo -= todo % graph_iters;
+    todo = keep_parity(todo);
+    rc = enqueue(todo);
+    if (rc) return rc;
+    // more than this chunk predicted: the look at it goes into a pinned slot and is waited for with the next
+    // chunk in the queue
+    int ahead = rem >= 0.0 ? std::min(sched_ahead(rem - todo, cap), max_it - it) : 0;
+    if (graphed && par == 1 && ahead >= graph_iters) ahead -= ahead % graph_iters;
+    ahead = keep_parity(ahead);
+    if (ahead >= 2) {
+      rc = poll_async(d_sc, 1, err);
       if (rc) return rc;
-      if (pre_sum)  // [w.z, r.z] -> tmp_pq, tmp_rz (adjacent)
-        hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gs,
-                           &d_sc->tmp_pq);
-      if (multi) {  // one 2-double all-reduce
-        rc = comm.allreduce(&d_sc->tmp_pq, 2, 0, stream, err);
-        if (rc) return rc;
-      }
-      hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(WG), 0, stream, r0, r1, par, it, scal,
-                         d_part_a, d_part_b, gs, Minv_arg, (const double*)zin, d_z, d_q, d_p, d_s,
-                         d_x, d_r, d_sc);
-      if (use_chain)
-        hipLaunchKernelGGL(k_chain_apply, dim3(gc), dim3(WG), 0, stream, r0, r1, chain_seg,
-                           d_Minv, d_Gm, d_r, d_z, (const DevScalars*)d_sc);
-      if (use_mg) {
-        rc = amg_apply(err);
-        if (rc) return rc;
-      }
-      if (multi && !use_mg) {  // the next SpMV gathers z from the neighbouring ranks
-        rc = exchange_rows(d_z, err);
-        if (rc) return rc;
-      }
-      par ^= 1;
-      ++it;
+      seen = it;
+      rc = enqueue(ahead);
+      if (rc) return rc;
+      rc = poll_wait(h_sc, 1, err);
+      if (rc) return rc;
+      if (!opt.time_kernels) spmv_work_seen = h_sc->n_spmv_work;
+      have = true;
     }
-    HIPCHK(hipGetLastError());
   }
+  // iterations enqueued that found the solve finished (h_sc: the last look of this solve)
+  auto count_idle = [&]() {
+    sched_stats[1] += std::max<int64_t>(0, (sched_stats[0] - enq0) - (int64_t)(h_sc->n_spmv_work - work0));
+  };
+  // stopped on a look that had a chunk queued behind it: the SpMV events are read once the stream has been waited for
+  bool drain_late = opt.time_kernels && seen < it;
   if (probe && abandoned && !h_sc->done && !h_sc->fail) {  // (ran out of budget or predicted to)
     *abandoned = true;
+    count_idle();
     kt.n_pcg_vec += h_sc->iter;
     *iters = h_sc->iter;
     *rel_res = h_sc->rz0 > 0 ? std::sqrt(std::fabs(h_sc->gam_last) / h_sc->rz0) : 0.0;
     *ok = true;
     return SIM3OPT_OK;
+  }
+  if (drain_late && !(use_mg && !h_sc->fail)) {
+    HIPCHK(hipStreamSynchronize(stream));
+    rc = pool_drain(err);
+    if (rc) return rc;
+    drain_late = false;
   }
   if (multi) {  // every rank updates its replica of all estimates
     rc = comm.allgatherv(d_x, offs, stream, err);  // (the whole step: every replica updates every estimate)
@@ -437,11 +530,16 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
     }
     rc = fetch_scalars(err);
     if (rc) return rc;
+    if (drain_late) {
+      rc = pool_drain(err);
+      if (rc) return rc;
+    }
     last_true_rel = h_sc->tmp_rz > 0 ? std::sqrt(h_sc->tmp_pq / h_sc->tmp_rz) : 0.0;
     if (opt.verbose)
       std::fprintf(stderr, "sim3opt: multigrid PCG: %d iterations, ||r||_Minv ratio %.2e, ||r||_2 / ||b||_2 %.2e\n",
                    h_sc->iter, h_sc->rz0 > 0 ? std::sqrt(std::fabs(h_sc->gam_last) / h_sc->rz0) : 0.0, last_true_rel);
   }
+  count_idle();
   kt.n_pcg_vec += h_sc->iter;
   *iters = h_sc->iter;
   // r.z seen by the last executed step, i.e. of the residual BEFORE that step's update

@@ -181,6 +181,7 @@ SYMBOLS = {
     "sim3opt_get_comm_times": (C.c_int, [_vp, C.POINTER(CommTimes)]),
     "sim3opt_get_kernel_times": (C.c_int, [_vp, C.POINTER(KernelTimes)]),
     "sim3opt_reset_kernel_times": (C.c_int, [_vp]),
+    "sim3opt_pcg_schedule_stats": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_int32]),
     "sim3opt_edge_errors": (C.c_int, [_vp, _dp]),
     "sim3opt_get_trust_region_stats": (C.c_int, [_vp, C.c_int32, C.POINTER(TrustRegionStats)]),
     "sim3opt_edge_jacobians": (C.c_int, [_vp, _dp, _dp]),
@@ -580,6 +581,14 @@ class Graph:
         if reset:
             self._chk(self._L.sim3opt_reset_kernel_times(self._g))
         return kt
+
+    def pcg_schedule_stats(self, reset=False):
+        """How the PCG loops were scheduled since initialize / the last reset: dict of iterations `enqueued`, of them
+        `past_done` (enqueued after the device had finished the solve), `sync_polls` (looks that drained the queue) and
+        `overlapped_polls` (looks waited for with the next chunk queued)."""
+        o = (C.c_int64 * 4)()
+        self._chk(self._L.sim3opt_pcg_schedule_stats(self._g, o, 1 if reset else 0))
+        return dict(zip(("enqueued", "past_done", "sync_polls", "overlapped_polls"), (int(x) for x in o)))
 
     def comm_times(self):
         """Device time, count and payload of the collectives since initialize / the last reset
