@@ -169,6 +169,14 @@ typedef struct sim3opt_options {
   double cov_workspace_mb;  /* 256   sim3opt_covariances / sim3opt_gate_edges: most device memory [MiB], at least 1, for
                                      the root paths of L^-1 behind the blocks outside the factor's pattern; a larger
                                      request is worked off in chunks (same bits)  [SIM3OPT_COV_WORKSPACE_MB]          */
+  int32_t cov_solver;       /* 0     how sim3opt_covariances / sim3opt_gate_edges obtain blocks of (H + lambda I)^-1:
+                                     0 = the exact factorisation (refused on graphs too large to factor), 1 = columns
+                                     of the inverse by PCG (needs a graph on the PCG path, linear_solver 0), 2 = exact
+                                     where the marginal plan is accepted, columns where it is refused.  sim3opt_marginals
+                                     and sim3opt_marginal_covariances are always exact            [SIM3OPT_COV_SOLVER] */
+  double cov_rel_tol;       /* 1e-8  cov_solver 1 / 2: every solved column y of a right-hand side g satisfies
+                                     ||g - (H + lambda I) y||_2 <= cov_rel_tol ||g||_2 (true residual, checked on the
+                                     device), else SIM3OPT_ERR_STATE; finite, in (0, 1e-2]       [SIM3OPT_COV_REL_TOL] */
 } sim3opt_options;
 
 /* options.algorithm */
@@ -427,6 +435,28 @@ int sim3opt_covariances(sim3opt_graph* g, double lambda, int32_t n, const int32_
 /* What the last sim3opt_marginals / _covariances / _gate_edges call did: {chunks of pairs outside the pattern,
  * root paths walked, distinct pairs outside the pattern, pairs on it, workspace bytes, selected inversion run}. */
 int sim3opt_covariance_stats(const sim3opt_graph* g, int64_t out[6]);
+/* ---- the same blocks on graphs too large to factor: columns of the inverse (options.cov_solver = 1, or 2 where the
+ * marginal plan is refused; DESIGN.md section 5f "Blocks by columns of the inverse") ----
+ * sim3opt_covariances and sim3opt_gate_edges then solve (H + lambda I) y = e_k for the seven unit vectors of a set of
+ * vertices that covers the request (every unordered pair has an endpoint in it; sim3opt_covariance_columns_plan) with
+ * the PCG and preconditioner the graph was initialised with -- on a multigrid graph four columns per pass over the
+ * blocks -- and read block (a, b) as rows a of the columns of b.  Each column is checked by its true residual against
+ * options.cov_rel_tol and refined at most twice; one that stays above it, a PCG breakdown or a failed set-up pivot:
+ * SIM3OPT_ERR_STATE naming the vertex and the residual, nothing written.  Every entry of a returned block is within
+ * cov_rel_tol / lambda_min(H + lambda I) of the true one; cond x eps is the floor of a residual in FP64, so an
+ * ill-conditioned H wants a lambda > 0.  Each unordered pair is computed once, the reversed pair is its exact
+ * transpose, a diagonal block is symmetrised, duplicates are identical; the bits of an off-diagonal block depend on
+ * which endpoint the cover chose, hence on the rest of the request (unlike the exact path), and on nothing else.  The
+ * LM state is left as it was.  The exact path's counters (sim3opt_covariance_stats) read 0 after such a call. */
+/* Host only, may be called before initialize.  The vertices (ids, in the order chosen) whose columns of
+ * (H + lambda I)^-1 cov_solver = 1 would solve for this request; two calls, vertices NULL to size it.  Greedy cover:
+ * repeatedly the vertex that covers the most pairs not yet covered, ties to the lowest block row.
+ * A fixed or unknown vertex: SIM3OPT_ERR_ARG. */
+int sim3opt_covariance_columns_plan(sim3opt_graph* g, int32_t n, const int32_t* id_a, const int32_t* id_b,
+                                    int32_t* n_vertices, int32_t* vertices);
+/* What the last column call did: counts = {vertices solved, columns, PCG iterations summed over the columns,
+ * refinement rounds, batches}; res = {largest ||g - (H + lambda I) y||_2 / ||g||_2 over the columns, cov_rel_tol used}. */
+int sim3opt_covariance_columns_stats(const sim3opt_graph* g, int64_t counts[5], double res[2]);
 /* Chi-square gate of candidate edges that are NOT added to the graph (is this loop closure consistent with what the
  * optimiser believes?).  Per candidate (id_v0, id_v1, meas as sim3opt_add_edge takes it, info column-major or NULL
  * for I): e[7] = EdgeSim3's residual at the current estimates; S[49] (column-major) = J0 S00 J0^T + J0 S01 J1^T +

@@ -602,6 +602,16 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
     o.verbose = v ? 1 : 0;
     sim3opt_set_options(g_, &o);
   }
+  // How computeMarginals and gateEdge obtain the blocks of H^-1 (options.cov_solver / cov_rel_tol): 0 = the exact
+  // factorisation, 1 = columns of the inverse by the PCG (graphs too large to factor; needs the PCG path), 2 = exact
+  // where its plan is accepted, columns where it is refused.  False (options unchanged) for a value out of range.
+  bool setCovarianceSolver(int solver, double rel_tol = 1e-8) {
+    sim3opt_options o;
+    sim3opt_get_options(g_, &o);
+    o.cov_solver = solver;
+    o.cov_rel_tol = rel_tol;
+    return sim3opt_set_options(g_, &o) == SIM3OPT_OK;
+  }
   bool addVertex(Vertex* v) {  // owns the vertex, like g2o
     std::unique_ptr<Vertex> own(v);
     if (!claim(v->kind())) return false;

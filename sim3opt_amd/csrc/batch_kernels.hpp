@@ -11,7 +11,8 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------------
-// PCG vector kernels for K systems (k_pcg_init / k_pcg_step / k_final_sum2 per system; b is shared)
+// PCG vector kernels for K systems (k_pcg_init / k_pcg_step / k_final_sum2 per system; b is shared -- or, OWNB: the
+// columns of the inverse, engine_columns.hip -- system s has its own right-hand side b + s * bstride)
 // ------------------------------------------------------------------------------------------
 template <int K>
 __global__ __launch_bounds__(WG) void k_final_sum2_k(const double* __restrict__ pa, const double* __restrict__ pb,
@@ -28,12 +29,12 @@ __global__ __launch_bounds__(WG) void k_final_sum2_k(const double* __restrict__ 
   }
 }
 
-template <int K>
+template <int K, bool OWNB = false>
 __global__ __launch_bounds__(WG) void k_pcg_init_k(int r0, int r1, const double* __restrict__ b,
                                                    const double* __restrict__ Minv, double* __restrict__ x,
                                                    double* __restrict__ r, double* __restrict__ z,
                                                    double* __restrict__ p, double* __restrict__ sv,
-                                                   BatchStrides bs) {
+                                                   BatchStrides bs, int64_t bstride = 0) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int sub = lane / 7, rr = lane % 7, base = lane - rr;
@@ -41,10 +42,11 @@ __global__ __launch_bounds__(WG) void k_pcg_init_k(int r0, int r1, const double*
     const int row = row0 + sub;
     const bool act = lane < 63 && row < r1;
     const size_t j = (size_t)7 * row + rr;
-    const double rv = act ? b[j] : 0.0;
+    double rv = act ? b[j] : 0.0;
 #pragma unroll
     for (int s = 0; s < K; ++s) {
       const size_t o = (size_t)s * bs.vec;
+      if (OWNB && s > 0) rv = act ? b[(size_t)s * bstride + j] : 0.0;
       if (act) {
         x[o + j] = 0.0;
         r[o + j] = rv;

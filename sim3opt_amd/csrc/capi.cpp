@@ -13,6 +13,7 @@
 #include "../../include/sim3opt.h"
 #include "../../include/sim3opt_bench.h"
 #include "amg.hpp"
+#include "col_plan.hpp"
 #include "comm.hpp"
 #include "devmem.hpp"
 #include "direct.hpp"
@@ -139,7 +140,7 @@ extern "C" {
 // 1.3: robust kernels beyond Huber, per edge and changeable after initialize
 // (Gauss-Newton and dogleg -- options.algorithm and the dl_* fields appended to sim3opt_options,
 // sim3opt_get_trust_region_stats -- keep 130: tests/test_robust_kernels.py pins the number; the new export is
-// how a caller detects them)
+// how a caller detects them; likewise options.cov_solver / cov_rel_tol and sim3opt_covariance_columns_plan / _stats)
 int sim3opt_version(void) { return 130; }
 
 void sim3opt_options_default(sim3opt_options* o) {
@@ -190,6 +191,8 @@ void sim3opt_options_default(sim3opt_options* o) {
   o->dl_lambda_init = 1e-7;
   o->dl_lambda_factor = 10.0;
   o->cov_workspace_mb = 256.0;
+  o->cov_solver = 0;
+  o->cov_rel_tol = 1e-8;
 }
 
 // Debug overrides: a SIM3OPT_* environment variable replaces the option field of the same name when the
@@ -228,6 +231,10 @@ static void apply_env_overrides(sim3opt_options& o) {
   // (a fraction of a MiB is accepted here only: tests chunk a small request that way)
   if (const char* ev = std::getenv("SIM3OPT_COV_WORKSPACE_MB"))
     if (std::atof(ev) > 0.0) o.cov_workspace_mb = std::atof(ev);
+  if (const char* ev = std::getenv("SIM3OPT_COV_SOLVER"))
+    if (std::atoi(ev) >= 0 && std::atoi(ev) <= 2) o.cov_solver = std::atoi(ev);
+  if (const char* ev = std::getenv("SIM3OPT_COV_REL_TOL"))
+    if (std::atof(ev) > 0.0 && std::atof(ev) <= 1e-2) o.cov_rel_tol = std::atof(ev);
 }
 
 sim3opt_graph* sim3opt_create(void) {
@@ -268,6 +275,10 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
   if ((!(o->cov_workspace_mb >= 1.0) && o->cov_workspace_mb != g->opt.cov_workspace_mb) ||
       !std::isfinite(o->cov_workspace_mb))
     return fail(g, SIM3OPT_ERR_ARG, "set_options: cov_workspace_mb must be finite and at least 1");
+  if (o->cov_solver < 0 || o->cov_solver > 2)
+    return fail(g, SIM3OPT_ERR_ARG, "set_options: cov_solver must be 0 (exact), 1 (columns by PCG) or 2 (exact where the plan is accepted)");
+  if (!std::isfinite(o->cov_rel_tol) || !(o->cov_rel_tol > 0.0) || !(o->cov_rel_tol <= 1e-2))
+    return fail(g, SIM3OPT_ERR_ARG, "set_options: cov_rel_tol must be finite and in (0, 1e-2]");
   if (o->jacobians == 1 && o->fix_small_angle_b != 1)
     return fail(g, SIM3OPT_ERR_ARG,
                 "set_options: jacobians = 1 needs fix_small_angle_b = 1 (the closed form differentiates the exact "
@@ -734,6 +745,17 @@ int sim3opt_marginals(sim3opt_graph* g, double lambda, int32_t n, const int32_t*
   }
 }
 
+// a column call that failed on one column names the vertex by its position; the caller knows it by its id
+static int name_failed_column(sim3opt_graph* g, int rc) {
+  if (rc != SIM3OPT_ERR_STATE || g->opt.cov_solver == 0) return rc;
+  int64_t counts[5];
+  double res[2];
+  int32_t v = -1;
+  engine_covariance_columns_stats(g->engine, counts, res, &v);
+  if (v >= 0 && v < g->host.nv()) g->err += " [vertex id " + std::to_string(g->host.vid[v]) + "]";
+  return rc;
+}
+
 int sim3opt_covariances(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_a,
                         const int32_t* id_b, double* cov) {
   try {
@@ -747,7 +769,7 @@ int sim3opt_covariances(sim3opt_graph* g, double lambda, int32_t n, const int32_
     rb[q] = g->structure.hidx[b->second];
     if (ra[q] < 0 || rb[q] < 0) return fail(g, SIM3OPT_ERR_ARG, "covariances: fixed vertex in a pair");
   }
-  return engine_covariances(g->engine, lambda, n, ra.data(), rb.data(), cov, g->err);
+  return name_failed_column(g, engine_covariances(g->engine, lambda, n, ra.data(), rb.data(), cov, g->err));
   } catch (...) {
     return fail(g, SIM3OPT_ERR_ARG, "covariances: out of host memory or internal error");
   }
@@ -758,6 +780,40 @@ int sim3opt_covariance_stats(const sim3opt_graph* g, int64_t out[6]) {
   if (!g->initialized) return SIM3OPT_ERR_STATE;
   engine_covariance_stats(g->engine, out);
   return SIM3OPT_OK;
+}
+
+int sim3opt_covariance_columns_stats(const sim3opt_graph* g, int64_t counts[5], double res[2]) {
+  if (!g || !counts || !res) return SIM3OPT_ERR_ARG;
+  if (!g->initialized) return SIM3OPT_ERR_STATE;
+  engine_covariance_columns_stats(g->engine, counts, res, nullptr);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_covariance_columns_plan(sim3opt_graph* g, int32_t n, const int32_t* id_a, const int32_t* id_b,
+                                    int32_t* n_vertices, int32_t* vertices) {
+  try {
+  if (!g || n < 0 || !n_vertices || (n > 0 && (!id_a || !id_b)))
+    return fail(g, SIM3OPT_ERR_ARG, "covariance_columns_plan: bad argument");
+  Structure st;
+  if (!build_structure(g->host, st, g->err)) return SIM3OPT_ERR_STATE;
+  std::vector<int32_t> ra(std::max(n, 1)), rb(std::max(n, 1));
+  for (int32_t q = 0; q < n; ++q) {
+    const auto a = g->host.id2idx.find(id_a[q]), b = g->host.id2idx.find(id_b[q]);
+    if (a == g->host.id2idx.end() || b == g->host.id2idx.end())
+      return fail(g, SIM3OPT_ERR_ARG, "covariance_columns_plan: unknown vertex id");
+    ra[q] = st.hidx[a->second];
+    rb[q] = st.hidx[b->second];
+    if (ra[q] < 0 || rb[q] < 0) return fail(g, SIM3OPT_ERR_ARG, "covariance_columns_plan: fixed vertex in a pair");
+  }
+  ColumnCover C;
+  covariance_columns_cover(st.nb, n, ra.data(), rb.data(), C);
+  *n_vertices = (int32_t)C.chosen.size();
+  if (vertices)
+    for (size_t k = 0; k < C.chosen.size(); ++k) vertices[k] = g->host.vid[st.row2vertex[C.chosen[k]]];
+  return SIM3OPT_OK;
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "covariance_columns_plan: out of host memory or internal error");
+  }
 }
 
 int sim3opt_gate_edges(sim3opt_graph* g, double lambda, int32_t n, const int32_t* id_v0, const int32_t* id_v1,
@@ -820,8 +876,8 @@ int sim3opt_gate_edges(sim3opt_graph* g, double lambda, int32_t n, const int32_t
         W[c + 7 * r] = v;
       }
   }
-  return engine_gate_edges(g->engine, lambda, n, v0.data(), v1.data(), r0.data(), r1.data(), cm.data(), oi.data(), e, S,
-                           d2, g->err);
+  return name_failed_column(g, engine_gate_edges(g->engine, lambda, n, v0.data(), v1.data(), r0.data(), r1.data(),
+                                                 cm.data(), oi.data(), e, S, d2, g->err));
   } catch (...) {
     return fail(g, SIM3OPT_ERR_ARG, "gate_edges: out of host memory or internal error");
   }

@@ -51,6 +51,7 @@ void Engine::release_under_device() {
   parts.clear();
   n_sharded = 0;
   batch_release();
+  cols_release();
   lm_factor.release();
   marg_factor.release();
   staged.release();

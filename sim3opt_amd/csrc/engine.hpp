@@ -53,6 +53,10 @@ int engine_marginals(Engine* e, double lambda, int32_t n, const int32_t* row_a, 
 int engine_covariances(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
                        std::string& err);
 void engine_covariance_stats(const Engine* e, int64_t out[6]);
+// what the last call that took the blocks by columns of the inverse did (options.cov_solver; engine_columns.hip):
+// counts = {vertices solved, columns, PCG iterations over the columns, refinement rounds, batches}, res = {largest
+// true relative residual, cov_rel_tol used}; failed_vertex (may be null): the vertex index of a column that failed, or -1
+void engine_covariance_columns_stats(const Engine* e, int64_t counts[5], double res[2], int32_t* failed_vertex);
 // chi-square gate of candidate edges (vertex indices, their block rows or -1 when fixed, Omega^-1 n x 49)
 int engine_gate_edges(Engine* e, double lambda, int32_t n, const int32_t* v0, const int32_t* v1, const int32_t* row0,
                       const int32_t* row1, const sim3::Sim3* meas, const double* infoinv, double* e_out, double* S_out,

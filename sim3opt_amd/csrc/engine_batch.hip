@@ -91,8 +91,12 @@ void Engine::batch_release() {
 // Solves (H + lams[s] I) x_s = b, s < nsys <= KB, together; x_s is left in b_x + s * b_vs.  *usable = false:
 // some system broke down or failed the true-residual check -- the caller then solves the trials one by one
 // (the sequential path has the fall-backs: plain cycle instead of the over-corrected one, block-Jacobi).
+// cols (columns of the inverse, engine_columns.hip): system s solves for ITS right-hand side cols->g + s * stride to
+// its own tolerance, all at lams[0] -- so ONE set-up (smoother inverses, FP32 diagonals, dense coarsest inverse: slot
+// 0, the caller has set the per-system strides of cv_batch to 0) serves them all, and the batches of a call that
+// follow the first (cols->setup false) run none.  The 2-norm check is the caller's, on the true residual.
 int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_res, bool* capped, bool* usable,
-                      std::string& err) {
+                      std::string& err, const BatchRhs* cols) {
   *usable = false;
   int rc = batch_alloc(err);
   if (rc) return rc;
@@ -106,13 +110,14 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
     DevScalars& h = h_bsc[s];
     std::memset(&h, 0, sizeof(DevScalars));
     h.max_iter = max_it;
-    h.tol2 = opt.pcg_rel_tol * opt.pcg_rel_tol;
+    h.tol2 = cols ? cols->tol[std::min(s, nsys - 1)] * cols->tol[std::min(s, nsys - 1)] : opt.pcg_rel_tol * opt.pcg_rel_tol;
     h.lambda = s < nsys ? lams[s] : lams[nsys - 1];
     h.done = s < nsys ? 0 : 1;  // (an unused slot: finished from the start, its vectors stay zero)
   }
   HIPCHK(hipMemcpyAsync(d_bsc, h_bsc, sizeof(DevScalars) * KB, hipMemcpyHostToDevice, stream));
   // per system: damped diagonal blocks, smoother inverses, dense inverse of the coarsest level (amg_prepare)
-  for (int s = 0; s < nsys; ++s) {
+  const int nsetup = cols ? (cols->setup ? 1 : 0) : nsys;
+  for (int s = 0; s < nsetup; ++s) {
     for (int l = 0; l < nl; ++l) {
       const AmgLevel& L = amg[l];
       const CycleLevel& B = cv_batch.lv[l];
@@ -127,8 +132,12 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   const CycleLevel& B0 = cv_batch.lv[0];
   BatchStrides bs0{b_vs, B0.ms, 0, 0, SPAN_GRID_MAX};
   cv_batch.nsys = nsys;
-  BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_pcg_init_k<KS>), dim3(gv), dim3(WG), 0, stream, 0, nb, (const double*)d_b,
-                     (const double*)B0.Minv, b_x, b_r, b_z, b_p, b_s, bs0));
+  if (cols)
+    BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_pcg_init_k<KS, true>), dim3(gv), dim3(WG), 0, stream, 0, nb, cols->g,
+                       (const double*)B0.Minv, b_x, b_r, b_z, b_p, b_s, bs0, cols->stride));
+  else
+    BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_pcg_init_k<KS>), dim3(gv), dim3(WG), 0, stream, 0, nb, (const double*)d_b,
+                       (const double*)B0.Minv, b_x, b_r, b_z, b_p, b_s, bs0, (int64_t)0));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_bsc, d_bsc, sizeof(DevScalars) * KB, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
@@ -224,7 +233,7 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   bool good = true;
   for (int s = 0; s < nsys; ++s) {
     if (h_bsc[s].fail) { good = false; continue; }
-    norms2(b_r + (size_t)s * b_vs, d_b, b_part_a, b_part_b, &d_bsc[s].tmp_pq);
+    if (!cols) norms2(b_r + (size_t)s * b_vs, d_b, b_part_a, b_part_b, &d_bsc[s].tmp_pq);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_bsc, d_bsc, sizeof(DevScalars) * KB, hipMemcpyDeviceToHost, stream));
@@ -234,11 +243,11 @@ int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_
   int it_max = 0;
   for (int s = 0; s < nsys; ++s) {
     const DevScalars& h = h_bsc[s];
-    const double true_rel = h.tmp_rz > 0 ? std::sqrt(h.tmp_pq / h.tmp_rz) : 0.0;
+    const double true_rel = !cols && h.tmp_rz > 0 ? std::sqrt(h.tmp_pq / h.tmp_rz) : 0.0;
     if (h.fail || true_rel > 1e-3) good = false;
     iters[s] = h.iter;
     rel_res[s] = h.rz0 > 0 ? std::sqrt(std::fabs(h.gam_last) / h.rz0) : 0.0;
-    capped[s] = !h.fail && h.iter >= max_it && rel_res[s] > opt.pcg_rel_tol;
+    capped[s] = !h.fail && h.iter >= max_it && rel_res[s] > (cols ? cols->tol[s] : opt.pcg_rel_tol);
     it_max = std::max(it_max, (int)h.iter);
     if (opt.verbose)
       std::fprintf(stderr, "sim3opt: batched multigrid PCG, system %d of %d: lambda %.6g, %d iterations, ||r||_Minv ratio %.2e, "

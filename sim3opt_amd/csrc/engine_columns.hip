@@ -1,0 +1,350 @@
+// engine_columns.hip -- blocks of (H + lambda I)^-1 by columns of the inverse: SparseOptimizer::computeMarginals and the
+// gate of candidate edges on the graphs the PCG was built for, where the exact block Cholesky behind
+// Engine::cov_blocks (engine_direct.hip) is refused.  Block (a, b) is rows a of the seven solutions of
+// (H + lambda I) y = e_{7 b + c}: the request is covered by vertices (col_plan.hpp), their columns are solved by the
+// PCG the graph was initialised with -- on a multigrid graph up to KB columns per pass over the blocks, through
+// pcg_batch with per-system right-hand sides and one set-up for all of them (they share lambda) -- and every column is
+// accepted on its TRUE residual g - (H + lambda I) y, formed by the SpMV, in the 2-norm against options.cov_rel_tol;
+// a column above it is refined at most twice (solve for the residual, add).  Per column the arithmetic does not depend
+// on the columns that share its batch (the batch's guarantee), so a block's bits depend on the endpoint the cover chose
+// and on nothing else of the request.  What the solves write of the solver's state is put back.
+#include "engine_impl.hpp"
+#include "col_plan.hpp"
+
+namespace sim3opt {
+
+#include "col_kernels.hpp"
+
+static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
+
+int Engine::cols_alloc(std::string& err) {
+  if (c_g) return SIM3OPT_OK;
+  c_vs = pad64(n);
+  double** v0[] = {&c_g, &c_y, &c_r, &c_d};
+  for (double** v : v0) {
+    HIPCHK(dev_malloc((void**)v, sizeof(double) * (size_t)KB * c_vs));
+    cols_owned.push_back(*v);
+    HIPCHK(hipMemsetAsync(*v, 0, sizeof(double) * (size_t)KB * c_vs, stream));
+  }
+  HIPCHK(dev_malloc((void**)&c_nrm, sizeof(double) * 2 * KB));
+  cols_owned.push_back(c_nrm);
+  return SIM3OPT_OK;
+}
+
+void Engine::cols_release() {
+  for (void* p : cols_owned)
+    if (p) dev_free(p);
+  cols_owned.clear();
+  c_g = c_y = c_r = c_d = c_nrm = nullptr;
+}
+
+int Engine::cols_solve(double lambda, int nsys, const double* g, const double* tol, bool setup, const double** x,
+                       int32_t* iters, bool* failed, std::string& err) {
+  const int width = cols_batch_width();
+  for (int s = 0; s < nsys; ++s) iters[s] = 0;
+  if (width > 0) {
+    double lams[KB], rel[KB];
+    bool capped[KB], usable = false;
+    for (int s = 0; s < KB; ++s) lams[s] = lambda;
+    const BatchRhs rhs{g, c_vs, tol, setup};
+    int rc = pcg_batch(lams, nsys, iters, rel, capped, &usable, err, &rhs);
+    if (rc) return rc;
+    for (int s = 0; s < nsys; ++s) {
+      // (a failed pivot of the shared set-up is raised on system 0 and ends the batch before its first step)
+      failed[s] = h_bsc[s].fail != 0 || h_bsc[0].fail != 0;
+      x[s] = b_x + (size_t)s * b_vs;
+    }
+    return SIM3OPT_OK;
+  }
+  // one column at a time through the one-system PCG: its right-hand side and tolerance for the length of the solve
+  double* const b_saved = d_b;
+  const double tol_saved = opt.pcg_rel_tol;
+  int rc = SIM3OPT_OK;
+  for (int s = 0; s < nsys && rc == SIM3OPT_OK; ++s) {  // (nsys = 1 here)
+    bool ok = true, broke = false;
+    double rr = 0.0;
+    d_b = const_cast<double*>(g) + (size_t)s * c_vs;
+    opt.pcg_rel_tol = tol[s];
+    rc = pcg_attempt(lambda, use_amg ? 2 : (use_chain ? 1 : 0), &iters[s], &rr, &ok, &broke, err);
+    failed[s] = !ok || broke;
+    x[s] = d_x;
+  }
+  d_b = b_saved;
+  opt.pcg_rel_tol = tol_saved;
+  return rc;
+}
+
+int Engine::cols_true_residuals(double lambda, int cnt, const int* sys, double* rel, std::string& err) {
+  const int ge = grid_for(n / 2, WG);
+  for (int j = 0; j < cnt; ++j) {
+    const size_t o = (size_t)sys[j] * c_vs;
+    spmv_raw(lambda, c_y + o, d_q, nullptr, nullptr);
+    hipLaunchKernelGGL(k_cols_residual, dim3(ge), dim3(WG), 0, stream, (int64_t)n, (const double*)(c_g + o),
+                       (const double*)d_q, c_r + o);
+    norms2(c_r + o, c_g + o, d_part_a, d_part_b, c_nrm + 2 * sys[j]);
+  }
+  HIPCHK(hipGetLastError());
+  double h[2 * KB];
+  HIPCHK(hipMemcpyAsync(h, c_nrm, sizeof(h), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  for (int j = 0; j < cnt; ++j) {
+    const double rr = h[2 * sys[j]], gg = h[2 * sys[j] + 1];
+    rel[j] = gg > 0.0 && rr == rr ? std::sqrt(rr / gg) : (rr == 0.0 ? 0.0 : INFINITY);
+  }
+  return SIM3OPT_OK;
+}
+
+int Engine::inverse_columns(double lambda, int32_t nvert, const int32_t* vertices, const int32_t* first,
+                            const int32_t* blk_row, double* blocks, std::string& err) {
+  const std::string pre = "columns of the inverse: ";
+  for (int64_t& v : col_counts) v = 0;
+  col_res[0] = 0.0;
+  col_res[1] = opt.cov_rel_tol;
+  col_fail_vertex = -1;
+  if (comm.world > 1) {
+    err = pre + "one GPU only (the graph is partitioned over ranks)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (use_direct) {
+    err = pre + "options.cov_solver needs a graph initialised on the PCG path (linear_solver = 0); this one factorises "
+          "exactly -- cov_solver = 0 is the path for it";
+    return SIM3OPT_ERR_STATE;
+  }
+  int rc = linearize(err);  // H at the current estimates (b is rewritten with the values it has)
+  if (rc) return rc;
+  if (nvert == 0) return SIM3OPT_OK;
+  rc = cols_alloc(err);
+  if (rc) return rc;
+  const int width = cols_batch_width();
+  if (width > 0 && (rc = batch_alloc(err))) return rc;
+  // ---- what the solves write of the solver's state, saved: the scalars on both sides, the batch's, the counters ----
+  HIPCHK(hipStreamSynchronize(stream));
+  DevScalars sd, sh = *h_sc, sbd[KB], sbh[KB];
+  HIPCHK(hipMemcpy(&sd, d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
+  std::vector<int64_t> ms_saved;
+  int64_t as_saved = 0;
+  if (width > 0) {
+    HIPCHK(hipMemcpy(sbd, d_bsc, sizeof(sbd), hipMemcpyDeviceToHost));
+    std::memcpy(sbh, h_bsc, sizeof(sbh));
+    // one set-up for all systems of a batch: slot 0 of the smoother inverses, the FP32 diagonals and the dense inverse
+    for (CycleLevel& B : cv_batch.lv) {
+      ms_saved.push_back(B.ms);
+      B.ms = 0;
+    }
+    as_saved = cv_batch.as;
+    cv_batch.as = 0;
+  }
+  const sim3opt_kernel_times kt_saved = kt;
+  int64_t sched_saved[4];
+  std::memcpy(sched_saved, sched_stats, sizeof(sched_saved));
+  const long long work_saved = spmv_work_seen;
+  const double true_rel_saved = last_true_rel;
+  const bool capped_saved = last_capped;
+
+  const int32_t nblk = first[nvert];
+  int32_t* d_rows = nullptr;
+  double* d_blocks = nullptr;
+  std::vector<double> out((size_t)49 * std::max(nblk, 1));
+  auto body = [&]() -> int {
+    HIPCHK(dev_malloc((void**)&d_rows, sizeof(int32_t) * (size_t)std::max(nblk, 1)));
+    HIPCHK(dev_malloc((void**)&d_blocks, sizeof(double) * 49 * (size_t)std::max(nblk, 1)));
+    HIPCHK(hipMemcpyAsync(d_rows, blk_row, sizeof(int32_t) * (size_t)nblk, hipMemcpyHostToDevice, stream));
+    const double ctol = opt.cov_rel_tol;
+    double first_pass = 0.01;
+    // (tuning, and the test of the refinement: 1 leaves the true residual above the bound on most graphs)
+    if (const char* ev = std::getenv("SIM3OPT_COLS_FIRST_PASS"))
+      if (std::atof(ev) > 0.0 && std::atof(ev) <= 1.0) first_pass = std::atof(ev);
+    const int64_t total = (int64_t)7 * nvert;
+    const int per = width > 0 ? width : 1;
+    const int ge = grid_for(n / 2, WG);
+    const size_t vbytes = sizeof(double) * (size_t)n;
+    bool setup = true;
+    for (int64_t c0 = 0; c0 < total; c0 += per) {
+      const int nsys = (int)std::min<int64_t>(per, total - c0);
+      ColUnits u;
+      for (int s = 0; s < KB; ++s) u.at[s] = s < nsys ? (int64_t)7 * vertices[(c0 + s) / 7] + (c0 + s) % 7 : -1;
+      BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_cols_rhs<KS>), dim3(ge), dim3(WG), 0, stream, (int64_t)n, c_vs, c_g, u));
+      HIPCHK(hipGetLastError());
+      // the PCG stops on ||r||_Minv, which the square root of the preconditioner's condition number separates from
+      // the 2-norm: two digits below the bound (each costs a few iterations; a refinement costs a solve with its
+      // set-up), and what they do not cover the refinement does
+      double tol[KB], rel[KB];
+      const double* x[KB];
+      int32_t its[KB] = {0, 0, 0, 0};
+      bool failed[KB];
+      int sys[KB];
+      for (int s = 0; s < KB; ++s) tol[s] = first_pass * ctol;
+      int rc2 = cols_solve(lambda, nsys, c_g, tol, setup, x, its, failed, err);
+      if (rc2) return rc2;
+      setup = false;
+      col_counts[4] += 1;
+      for (int s = 0; s < nsys; ++s) {
+        col_counts[2] += its[s];
+        if (failed[s]) {
+          col_fail_vertex = st.row2vertex[vertices[(c0 + s) / 7]];
+          err = pre + "the PCG broke down or its set-up met a non-positive pivot (column " + std::to_string((c0 + s) % 7) +
+                " of vertex #" + std::to_string(col_fail_vertex) + "): H + lambda I is not positive definite";
+          return SIM3OPT_ERR_STATE;
+        }
+        HIPCHK(hipMemcpyAsync(c_y + (size_t)s * c_vs, x[s], vbytes, hipMemcpyDeviceToDevice, stream));
+        sys[s] = s;
+      }
+      rc2 = cols_true_residuals(lambda, nsys, sys, rel, err);
+      if (rc2) return rc2;
+      double relc[KB];  // per system of the batch
+      for (int s = 0; s < nsys; ++s) relc[s] = rel[s];
+      for (int round = 0; round < 2; ++round) {
+        int bad[KB], nbad = 0;
+        for (int s = 0; s < nsys; ++s)
+          if (!(relc[s] <= ctol)) bad[nbad++] = s;
+        if (nbad == 0) break;
+        col_counts[3] += 1;
+        // solve for the residuals (to what is still missing, relative to them), add, look again
+        for (int j0 = 0; j0 < nbad; j0 += per) {
+          const int m = std::min(per, nbad - j0);
+          for (int j = 0; j < m; ++j) {
+            const int s = bad[j0 + j];
+            HIPCHK(hipMemcpyAsync(c_d + (size_t)j * c_vs, c_r + (size_t)s * c_vs, vbytes, hipMemcpyDeviceToDevice, stream));
+            tol[j] = std::isfinite(relc[s]) ? std::min(0.1, 0.1 * ctol / relc[s]) : 0.1;
+          }
+          rc2 = cols_solve(lambda, m, c_d, tol, false, x, its, failed, err);
+          if (rc2) return rc2;
+          for (int j = 0; j < m; ++j) {
+            const int s = bad[j0 + j];
+            col_counts[2] += its[j];
+            if (failed[j]) continue;  // (the column keeps its residual and is reported below)
+            hipLaunchKernelGGL(k_cols_axpy, dim3(ge), dim3(WG), 0, stream, (int64_t)n, x[j], c_y + (size_t)s * c_vs);
+            if (width == 0) {  // (one system: d_x is the next solve's too)
+              rc2 = cols_true_residuals(lambda, 1, &s, &relc[s], err);
+              if (rc2) return rc2;
+            }
+          }
+          HIPCHK(hipGetLastError());
+        }
+        if (width > 0) {
+          rc2 = cols_true_residuals(lambda, nbad, bad, rel, err);
+          if (rc2) return rc2;
+          for (int j = 0; j < nbad; ++j) relc[bad[j]] = rel[j];
+        }
+      }
+      for (int s = 0; s < nsys; ++s) {
+        if (relc[s] == relc[s]) col_res[0] = std::max(col_res[0], relc[s]);
+        if (!(relc[s] <= ctol)) {
+          col_fail_vertex = st.row2vertex[vertices[(c0 + s) / 7]];
+          char buf[96];
+          std::snprintf(buf, sizeof(buf), "%.3e, above cov_rel_tol = %.3e", relc[s], ctol);
+          err = pre + "column " + std::to_string((c0 + s) % 7) + " of vertex #" + std::to_string(col_fail_vertex) +
+                " reached ||g - (H + lambda I) y|| / ||g|| = " + buf +
+                " after two rounds of refinement: pass a lambda > 0 (cond x eps is the floor), a larger cov_rel_tol "
+                "or more pcg_max_iters";
+          return SIM3OPT_ERR_STATE;
+        }
+        const int32_t v = (int32_t)((c0 + s) / 7), cnt = first[v + 1] - first[v];
+        if (cnt > 0)
+          hipLaunchKernelGGL(k_cols_gather, dim3(grid_for(7 * (int64_t)cnt, WG)), dim3(WG), 0, stream, first[v], cnt,
+                             (int32_t)((c0 + s) % 7), (const int32_t*)d_rows, (const double*)(c_y + (size_t)s * c_vs),
+                             d_blocks);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(out.data(), d_blocks, sizeof(double) * 49 * (size_t)nblk, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  // ---- ... and put back ----
+  bool restored = hipStreamSynchronize(stream) == hipSuccess;
+  restored = restored && hipMemcpy(d_sc, &sd, sizeof(DevScalars), hipMemcpyHostToDevice) == hipSuccess;
+  *h_sc = sh;
+  if (width > 0) {
+    restored = restored && hipMemcpy(d_bsc, sbd, sizeof(sbd), hipMemcpyHostToDevice) == hipSuccess;
+    std::memcpy(h_bsc, sbh, sizeof(sbh));
+    for (size_t l = 0; l < cv_batch.lv.size(); ++l) cv_batch.lv[l].ms = ms_saved[l];
+    cv_batch.as = as_saved;
+  }
+  kt = kt_saved;
+  std::memcpy(sched_stats, sched_saved, sizeof(sched_saved));
+  spmv_work_seen = work_saved;
+  last_true_rel = true_rel_saved;
+  last_capped = capped_saved;
+  if (d_rows) dev_free(d_rows);
+  if (d_blocks) dev_free(d_blocks);
+  if (rc == SIM3OPT_OK && !restored) {
+    err = pre + "restoring the solver's scalars failed";
+    rc = SIM3OPT_ERR_HIP;
+  }
+  if (rc) return rc;
+  col_counts[0] = nvert;
+  col_counts[1] = (int64_t)7 * nvert;
+  std::memcpy(blocks, out.data(), sizeof(double) * 49 * (size_t)nblk);
+  return SIM3OPT_OK;
+}
+
+// The request of Engine::cov_blocks by columns: cover, solve, lay out.  Each unordered pair is computed once, from the
+// endpoint the cover chose; the reversed pair is its exact transpose, a diagonal block is symmetrised as (B + B^T) / 2.
+int Engine::cov_blocks_columns(const std::string& pre, bool fixed_zero, double lambda, int32_t n, const int32_t* row_a,
+                               const int32_t* row_b, double* cov, std::string& err) {
+  for (int64_t& v : cov_stats) v = 0;  // (the exact path's counters)
+  for (int32_t q = 0; q < n; ++q) {
+    if (fixed_zero && (row_a[q] < 0 || row_b[q] < 0)) continue;
+    if (row_a[q] < 0 || row_b[q] < 0 || row_a[q] >= nb || row_b[q] >= nb) {
+      err = pre + "fixed vertex in a pair";
+      return SIM3OPT_ERR_ARG;
+    }
+  }
+  ColumnCover C;
+  covariance_columns_cover(nb, n, row_a, row_b, C);
+  const int32_t nvert = (int32_t)C.chosen.size(), np = (int32_t)C.pairs.size();
+  // the blocks of a chosen vertex b: (a, b) for every pair {a, b} it covers
+  std::vector<int32_t> first(nvert + 1, 0), blk_of(np), blk_row(std::max(np, 1));
+  for (int32_t k = 0; k < np; ++k) ++first[C.owner[k] + 1];
+  for (int32_t v = 0; v < nvert; ++v) first[v + 1] += first[v];
+  {
+    std::vector<int32_t> fill(first.begin(), first.end() - 1);
+    for (int32_t k = 0; k < np; ++k) {
+      const int32_t b = C.chosen[C.owner[k]];
+      blk_of[k] = fill[C.owner[k]]++;
+      blk_row[blk_of[k]] = C.pairs[k].first == b ? C.pairs[k].second : C.pairs[k].first;
+    }
+  }
+  std::vector<double> blocks((size_t)49 * std::max(np, 1));
+  int rc = inverse_columns(lambda, nvert, C.chosen.data(), first.data(), blk_row.data(), blocks.data(), err);
+  if (rc) {
+    if (rc == SIM3OPT_ERR_STATE) err = pre + err;
+    return rc;
+  }
+  for (size_t k = 0; k < (size_t)49 * np; ++k)
+    if (!std::isfinite(blocks[k])) {
+      err = pre + "non-finite result";
+      return SIM3OPT_ERR_STATE;
+    }
+  for (int32_t q = 0; q < n; ++q) {
+    double* dst = cov + (size_t)49 * q;
+    const int32_t k = C.pair_of[q];
+    if (k < 0) {
+      for (int e = 0; e < 49; ++e) dst[e] = 0.0;
+      continue;
+    }
+    const double* src = blocks.data() + (size_t)49 * blk_of[k];
+    const int32_t b = C.chosen[C.owner[k]];
+    if (row_a[q] == row_b[q]) {
+      for (int c = 0; c < 7; ++c)
+        for (int r = 0; r < 7; ++r) dst[r + 7 * c] = 0.5 * (src[r + 7 * c] + src[c + 7 * r]);
+    } else if (row_b[q] == b) {  // stored as (a, b): rows a, columns b
+      std::memcpy(dst, src, sizeof(double) * 49);
+    } else {
+      for (int c = 0; c < 7; ++c)
+        for (int r = 0; r < 7; ++r) dst[r + 7 * c] = src[c + 7 * r];
+    }
+  }
+  return SIM3OPT_OK;
+}
+
+void engine_covariance_columns_stats(const Engine* e, int64_t counts[5], double res[2], int32_t* failed_vertex) {
+  for (int k = 0; k < 5; ++k) counts[k] = e->col_counts[k];
+  res[0] = e->col_res[0];
+  res[1] = e->col_res[1];
+  if (failed_vertex) *failed_vertex = e->col_fail_vertex;
+}
+
+}  // namespace sim3opt

@@ -97,8 +97,13 @@ int Engine::cov_blocks(const char* who, bool any_pair, bool fixed_zero, double l
     err = pre + "lambda must be finite and >= 0";
     return SIM3OPT_ERR_ARG;
   }
+  // options.cov_solver (covariances and the gate only): 1 = columns of the inverse by PCG, 2 = that where the plan of
+  // the exact factorisation is refused (engine_columns.hip)
+  if (any_pair && opt.cov_solver == 1) return cov_blocks_columns(pre, fixed_zero, lambda, n, row_a, row_b, cov, err);
   if (!marg_factor.ready()) {
     int rc = marginal_init(err);
+    if (rc == SIM3OPT_ERR_STATE && any_pair && opt.cov_solver == 2 && !marg_refused.empty())
+      return cov_blocks_columns(pre, fixed_zero, lambda, n, row_a, row_b, cov, err);
     if (rc) return rc;
   }
   for (int64_t& v : cov_stats) v = 0;

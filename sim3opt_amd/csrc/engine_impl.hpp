@@ -8,8 +8,9 @@
 //                      marginal covariances: policy over two BlockLdl (direct_factor.hpp, direct_factor.hip)
 //   engine_batch.hip   the multigrid PCG loop for several right-hand sides: an LM trial's solve (lm_trial_solve)
 //   engine_algorithms.hip  Gauss-Newton and Powell's dogleg (options.algorithm = 1 / 2)
+//   engine_columns.hip  blocks of (H + lambda I)^-1 by columns of the inverse (options.cov_solver)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
-// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, batch_kernels.hpp -> engine_batch.hip, algo_kernels.hpp -> engine_algorithms.hip, gate_kernels.hpp -> engine_direct.hip, direct_ / selinv_ / cov_kernels.hpp -> direct_factor.hip); only
+// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, batch_kernels.hpp -> engine_batch.hip, algo_kernels.hpp -> engine_algorithms.hip, gate_kernels.hpp -> engine_direct.hip, col_kernels.hpp -> engine_columns.hip, direct_ / selinv_ / cov_kernels.hpp -> direct_factor.hip); only
 // the SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through a method.
 #pragma once
 // (formerly all of engine.hip) -- device-resident Levenberg-Marquardt on a Sim(3) pose graph, gfx950 (MI355X).
@@ -305,8 +306,11 @@ class Engine {
   int64_t b_slice_blocks = 100000;  // levels with at most this many blocks run one system per grid slice
   int batch_alloc(std::string& err);
   void batch_release();
+  // per-system right-hand sides of a batch (the columns of the inverse): g + s * stride, tolerance tol[s]; one damping
+  // for all, so one set-up serves them -- run by the first batch of a call only (setup)
+  struct BatchRhs { const double* g; int64_t stride; const double* tol; bool setup; };
   int pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_res, bool* capped, bool* usable,
-                std::string& err);
+                std::string& err, const BatchRhs* cols = nullptr);
   // the solve of LM trial q at damping lambda (ni: the rule's next factor); *x: d_x or its system of a batch
   int lm_trial_solve(int q, double lambda, double ni, const double** x, int32_t* iters, double* rel_res, bool* ok,
                      std::string& err);
@@ -531,6 +535,41 @@ class Engine {
   int gate_edges(double lambda, int32_t n, const int32_t* v0, const int32_t* v1, const int32_t* row0,
                  const int32_t* row1, const Sim3* meas, const double* infoinv, double* e_out, double* S_out,
                  double* d2_out, std::string& err);  // gate_kernels.hpp
+  // ---- the same blocks by columns of the inverse (engine_columns.hip, col_kernels.hpp): graphs too large to factor ----
+  // options.cov_solver = 1, or 2 where the marginal plan is refused: block (a, b) is rows a of the seven solutions
+  // (H + lambda I) y = e_{7 b + c}, by the PCG the graph was initialised with -- on a multigrid graph up to KB columns
+  // per pass over the blocks (pcg_batch with per-system right-hand sides and ONE set-up), else one at a time
+  // (pcg_attempt) -- each checked on the device by its TRUE residual in the 2-norm against options.cov_rel_tol and
+  // refined at most twice.  The solver's state is put back as the diagnostic read-outs do.
+  std::vector<void*> cols_owned;
+  double *c_g = nullptr, *c_y = nullptr, *c_r = nullptr, *c_d = nullptr;  // KB right-hand sides, solutions, residuals, refinement right-hand sides
+  double* c_nrm = nullptr;  // [||r||^2, ||g||^2] per system
+  int64_t c_vs = 0;
+  int cols_alloc(std::string& err);
+  void cols_release();
+  // columns a solve carries: KB (or options.pcg_batch) through the batch on a multigrid graph that admits one, else 0
+  int cols_batch_width() const {
+    if (!use_amg || amg.empty() || comm.active() || !amg_fp32 || amg_additive) return 0;
+    return opt.pcg_batch >= 1 ? std::min(opt.pcg_batch, KB) : KB;
+  }
+  // solves nsys systems for the right-hand sides g + s * c_vs to the tolerances tol[s] (||r||_Minv); x[s]: where the
+  // solution of system s is; failed[s]: breakdown or a failed set-up pivot
+  int cols_solve(double lambda, int nsys, const double* g, const double* tol, bool setup, const double** x,
+                 int32_t* iters, bool* failed, std::string& err);
+  // ||g_s - (H + lambda I) y_s||_2 / ||g_s||_2 of the systems listed, by the SpMV (the residual itself: c_r)
+  int cols_true_residuals(double lambda, int cnt, const int* sys, double* rel, std::string& err);
+  // The columns of block rows vertices[0 .. nvert): vertex v contributes the blocks [first[v], first[v + 1]), block k =
+  // (blk_row[k], vertices[v]) of the inverse, column-major, into blocks (host, 49 doubles each).  Nothing is written
+  // unless every column met options.cov_rel_tol.
+  int inverse_columns(double lambda, int32_t nvert, const int32_t* vertices, const int32_t* first,
+                      const int32_t* blk_row, double* blocks, std::string& err);
+  int cov_blocks_columns(const std::string& pre, bool fixed_zero, double lambda, int32_t n, const int32_t* row_a,
+                         const int32_t* row_b, double* cov, std::string& err);
+  // of the last column call: {vertices solved, columns, PCG iterations summed over the columns, refinement rounds,
+  // batches}, {largest true relative residual, cov_rel_tol used}; the vertex (index) of a column that failed, or -1
+  int64_t col_counts[5] = {0, 0, 0, 0, 0};
+  double col_res[2] = {0.0, 0.0};
+  int32_t col_fail_vertex = -1;
   // block-Jacobi inverses Minv = omega (D + lambda W)^-1 of rows [lo, hi) (k_jacobi; engine_pcg.hip)
   void jacobi(int lo, int hi, const int32_t* rowptr, double* vals, double lambda, double* Minv, double omega,
               const double* diagH, const double* W, float* vals32, DevScalars* sc = nullptr,

@@ -75,6 +75,8 @@ class Options(C.Structure):
         ("dl_lambda_init", C.c_double),
         ("dl_lambda_factor", C.c_double),
         ("cov_workspace_mb", C.c_double),
+        ("cov_solver", C.c_int32),
+        ("cov_rel_tol", C.c_double),
     ]
 
 
@@ -211,6 +213,8 @@ SYMBOLS = {
     "sim3opt_covariances": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp]),
     "sim3opt_covariance_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "sim3opt_gate_edges": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "sim3opt_covariance_columns_plan": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _ip]),
+    "sim3opt_covariance_columns_stats": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp]),
     "sim3opt_marginal_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _ip,
                                         _ip, _ip, _ip]),
     "sim3opt_comm_allgather_plan": (C.c_int, [C.c_int32, C.c_int32, _ip, C.POINTER(C.c_int64),
@@ -743,6 +747,27 @@ class Graph:
         self._chk(self._L.sim3opt_covariance_stats(self._g, o))
         keys = ("chunks", "paths", "off_pattern_pairs", "on_pattern_pairs", "workspace_bytes", "selinv")
         return dict(zip(keys, (int(x) for x in o)))
+
+    def covariance_columns_plan(self, pairs):
+        """The vertex ids, in the order chosen, whose columns of (H + lam I)^-1 cov_solver = 1 would solve for
+        covariances(pairs): a greedy cover of the pairs; host only, may be called before initialize."""
+        pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, b = _i32(pr[:, 0]), _i32(pr[:, 1])
+        nv = C.c_int32()
+        self._chk(self._L.sim3opt_covariance_columns_plan(self._g, pr.shape[0], _p(a, _ip), _p(b, _ip), C.byref(nv), None))
+        out = np.zeros(max(nv.value, 1), dtype=np.int32)
+        self._chk(self._L.sim3opt_covariance_columns_plan(self._g, pr.shape[0], _p(a, _ip), _p(b, _ip), C.byref(nv),
+                                                          _p(out, _ip)))
+        return out[:nv.value].copy()
+
+    def covariance_columns_stats(self):
+        """What the last covariances / gate_edges call that went by columns of the inverse did, as a dict."""
+        c = (C.c_int64 * 5)()
+        r = np.zeros(2)
+        self._chk(self._L.sim3opt_covariance_columns_stats(self._g, c, _p(r, _dp)))
+        out = dict(zip(("vertices", "columns", "pcg_iters", "refinements", "batches"), (int(x) for x in c)))
+        out.update(max_rel_residual=float(r[0]), cov_rel_tol=float(r[1]))
+        return out
 
     def gate_edges(self, v0, v1, meas, info=None, lam=0.0, out=None):
         """Chi-square gate of candidate edges that are not added: (e (n, 7), S (n, 7, 7), d2 (n,)) with
