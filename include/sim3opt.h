@@ -707,6 +707,42 @@ int sim3opt_ba_get_stats(const sim3opt_ba* b, int32_t iter, sim3opt_iter_stats* 
 /* "% SE3 optimization result: kf id, tcinw, rc2w(qxyzw)" rows                        :223-238 */
 int sim3opt_ba_write_poses(const sim3opt_ba* b, const char* path);
 
+/* ---- read-outs of the bundle adjuster's intermediates, for tests ----
+ * Contract of all five: nothing in the solver uses them; they run the launch code of sim3opt_ba_optimize on the
+ * current estimate (uploading the problem first if need be), copy device buffers to the host and leave the estimate,
+ * the statistics and every later sim3opt_ba_optimize / sim3opt_ba_chi2 result bit for bit what they are without the
+ * call.  Camera vectors hold 7 doubles per camera [omega, upsilon, pad]; blocks are 7 x 7, column-major (entry (r, c)
+ * at r + 7 c), the 7th row / column zero but for a 1 at (6, 6) of the diagonal blocks.  SIM3OPT_ERR_STATE without a problem, SIM3OPT_ERR_ARG for a
+ * NULL output that is not marked optional or a non-finite lambda; the message is in sim3opt_ba_last_error. */
+/* Diagnostic.  Block-CSR pattern of the reduced camera system: *n_blocks, rptr (n_cams + 1), bcol (n_blocks), the
+ * diagonal block first in every row.  rptr = bcol = NULL: the size query. */
+int sim3opt_ba_debug_pattern(sim3opt_ba* b, int32_t* n_blocks, int32_t* rptr, int32_t* bcol);
+/* Diagnostic.  The linearisation of the current estimate as k_ba_obs writes it: n_obs x 20 = [A = sqrt(w) J_cam
+ * (2 x 6 row-major), B = sqrt(w) J_point (2 x 3 row-major), es = sqrt(w) e], w = Huber weight / pixel_noise^2. */
+int sim3opt_ba_debug_linearization(sim3opt_ba* b, double* lin);
+/* Diagnostic.  The reduced system of an LM trial with damping `lambda` (k_ba_obs, k_ba_points, k_ba_obs2,
+ * k_ba_reduced, the max-diagonal part of k_ba_final).  Every output may be NULL, not all of them:
+ * S (n_blocks x 49), g and b_c (n_cams x 7), Hpp_inv = (H_pp + lambda I)^-1 (n_points x 9), b_p (n_points x 3),
+ * Z = (A^T B) Hpp_inv (n_obs x 18, 6 x 3 row-major), point_maxdiag (n_points) and cam_maxdiag (n_cams x 7): the
+ * undamped diagonals' maxima per point / entries per camera, *maxdiag: the maximum over both. */
+int sim3opt_ba_debug_reduced(sim3opt_ba* b, double lambda, double* S, double* g, double* b_c, double* Hpp_inv,
+                             double* b_p, double* Z, double* point_maxdiag, double* cam_maxdiag, double* maxdiag);
+/* Diagnostic.  The step of an LM trial with damping `lambda`: the reduced system as above, S dx_c = g by solver = 1
+ * the exact block Cholesky (SIM3OPT_ERR_STATE when the problem was initialised without its plan) or solver = 0
+ * k_ba_pcg with at most pcg_max_iters iterations (0: automatic) to pcg_rel_tol -- a cap of k returns the iterate
+ * x_k --, then dx_p by k_ba_backsub.  dx_c (n_cams x 7), dx_p (n_points x 3) and *fail (a breakdown of the PCG or a
+ * non-positive pivot: the step is then meaningless, the return code still SIM3OPT_OK) are required; pcg_iters and
+ * pcg_rel may be NULL.  The estimate is not moved. */
+int sim3opt_ba_debug_step(sim3opt_ba* b, double lambda, int32_t solver, int32_t pcg_max_iters, double pcg_rel_tol,
+                          double* dx_c, double* dx_p, int32_t* pcg_iters, double* pcg_rel, int32_t* fail);
+/* Diagnostic.  What an LM trial makes of a caller's step dx_c (n_cams x 7), dx_p (n_points x 3), any numbers:
+ * the estimate k_ba_update produces (cam_qt n_cams x 7, points n_points x 3), its robustified chi2 (k_ba_chi2,
+ * k_ba_final) and scale = x . (lambda x + b) over cameras and points (k_ba_scale, k_ba_final; b = b_c, b_p of the
+ * current estimate).  with_fail != 0 runs the update with the trial's fail flag set: nothing may move.  The estimate
+ * is then restored from the trial's backup buffers.  The four outputs may be NULL, not all of them. */
+int sim3opt_ba_debug_update(sim3opt_ba* b, const double* dx_c, const double* dx_p, double lambda, int32_t with_fail,
+                            double* cam_qt, double* points, double* chi2, double* scale);
+
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933
  * Null vector of the edge equations s_C x[v0] - x[v1] = 0 (the reference: last column of V of

@@ -31,6 +31,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -798,10 +799,79 @@ struct Problem {
     return SIM3OPT_OK;
   }
 
+  // ---- the launches of one LM iteration, shared by optimize() and the diagnostic read-outs ----
+  int gobs() const { return (no() + WG - 1) / WG; }
+  int gpts() const { return (np() + WG - 1) / WG; }
+  void launch_linearize() {
+    hipLaunchKernelGGL(k_ba_obs, dim3(gobs()), dim3(WG), 0, stream, oargs(), d_lin);
+  }
+  int backup() {
+    BA_HIPCHK(hipMemcpyAsync(d_cams_bk, d_cams, sizeof(Cam) * nc(), hipMemcpyDeviceToDevice, stream));
+    BA_HIPCHK(hipMemcpyAsync(d_pts_bk, d_pts, sizeof(double) * 3 * np(), hipMemcpyDeviceToDevice, stream));
+    return SIM3OPT_OK;
+  }
+  int restore() {
+    BA_HIPCHK(hipMemcpyAsync(d_cams, d_cams_bk, sizeof(Cam) * nc(), hipMemcpyDeviceToDevice, stream));
+    BA_HIPCHK(hipMemcpyAsync(d_pts, d_pts_bk, sizeof(double) * 3 * np(), hipMemcpyDeviceToDevice, stream));
+    return SIM3OPT_OK;
+  }
+  // H_pp^-1, b_p, Z, then S, g, b_c and the undamped diagonals, for the damping `lambda`
+  void launch_reduced(double lambda) {
+    hipLaunchKernelGGL(k_ba_points, dim3(gpts()), dim3(WG), 0, stream, np(), d_pptr, d_pobs, d_lin, lambda,
+                       d_Hinv, d_bp, d_pdmax);
+    hipLaunchKernelGGL(k_ba_obs2, dim3(gobs()), dim3(WG), 0, stream, no(), d_op, d_lin, d_Hinv, d_Z);
+    hipLaunchKernelGGL(k_ba_reduced, dim3((nblk + 3) / 4), dim3(WG), 0, stream, nblk, d_brow, d_bcol,
+                       d_sptr, d_sa, d_sb, d_op, d_lin, d_Z, d_bp, d_fixed, lambda, d_S, d_g, d_bc,
+                       d_cdmax);
+  }
+  void launch_maxdiag() {
+    hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)nullptr, 0,
+                       (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)d_pdmax, np(),
+                       (const double*)d_cdmax, 7 * nc(), d_sc);
+  }
+  // pcg_iters, fail and pcg_rel (contiguous in Scal): what a solver leaves behind.  The exact solver writes only
+  // `fail`, so a pcg_rel left by an earlier k_ba_pcg launch (a read-out may ask for one) must not reach the statistics.
+  int clear_solver_flags() {
+    static_assert(offsetof(Scal, pcg_rel) == offsetof(Scal, pcg_iters) + 2 * sizeof(int32_t), "Scal layout");
+    BA_HIPCHK(hipMemsetAsync(&d_sc->pcg_iters, 0, 2 * sizeof(int32_t) + sizeof(double), stream));
+    return SIM3OPT_OK;
+  }
+  // S dx_c = g: the exact block Cholesky, or the one-workgroup PCG with the given cap (0: automatic) and tolerance
+  int launch_solve(bool exact, int pcg_max_iters, double pcg_rel_tol) {
+    if (exact) {
+      direct.gather(d_S, d_g, stream);
+      BA_HIPCHK(direct.factor(0.0, &d_sc->fail, 1, d_xc, stream));  // lambda 0: S carries the damping already
+    } else {
+      hipLaunchKernelGGL(k_ba_pcg, dim3(1), dim3(1024), 0, stream, nc(), d_rptr, d_bcol, d_S, d_g, d_xc, d_r,
+                         d_z, d_p, d_q, d_Dinv, pcg_max_iters > 0 ? pcg_max_iters : 20 * nc() + 100,
+                         pcg_rel_tol * pcg_rel_tol, d_sc);
+    }
+    return SIM3OPT_OK;
+  }
+  void launch_backsub() {
+    hipLaunchKernelGGL(k_ba_backsub, dim3(gpts()), dim3(WG), 0, stream, np(), d_pptr, d_pobs, d_oc, d_Hinv,
+                       d_bp, d_Z, d_xc, d_xp);
+  }
+  void launch_update() {
+    hipLaunchKernelGGL(k_ba_update, dim3((std::max(nc(), 3 * np()) + WG - 1) / WG), dim3(WG), 0, stream, nc(), np(),
+                       d_xc, d_xp, d_fixed, d_cams, d_pts, (const Scal*)d_sc);
+  }
+  // chi2 of the estimate and scale = x.(lambda x + b) over cameras and points, into d_sc
+  void launch_trial_sums(double lambda) {
+    const int NC = nc(), NP = np();
+    const int gsc = std::max(1, std::min(1024, (7 * NC + WG - 1) / WG));
+    const int gsp = std::max(1, std::min(1024, (3 * NP + WG - 1) / WG));
+    hipLaunchKernelGGL(k_ba_scale, dim3(gsc), dim3(WG), 0, stream, 7 * NC, d_xc, d_bc, lambda, d_pb);
+    hipLaunchKernelGGL(k_ba_scale, dim3(gsp), dim3(WG), 0, stream, 3 * NP, d_xp, d_bp, lambda, d_pc);
+    hipLaunchKernelGGL(k_ba_chi2, dim3(grid_chi), dim3(WG), 0, stream, oargs(), d_pa);
+    hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)d_pa, grid_chi,
+                       (const double*)d_pb, gsc, (const double*)d_pc, gsp, (const double*)nullptr, 0,
+                       (const double*)nullptr, 0, d_sc);
+  }
+
   int optimize(int max_iters) {
     stats.clear();
-    const int NC = nc(), NP = np(), NO = no();
-    const int go = (NO + WG - 1) / WG, gp = (NP + WG - 1) / WG;
+    const int NC = nc(), NP = np();
     LmDamping damp;
     bool ok = true;
     int iters = 0;
@@ -811,25 +881,18 @@ struct Problem {
       int rc = chi2(&currentChi);
       if (rc) return rc;
       T.chi2_before = currentChi;
-      hipLaunchKernelGGL(k_ba_obs, dim3(go), dim3(WG), 0, stream, oargs(), d_lin);
+      launch_linearize();
       double rho = 0.0;
       int qmax = 0;
       do {
-        BA_HIPCHK(hipMemcpyAsync(d_cams_bk, d_cams, sizeof(Cam) * NC, hipMemcpyDeviceToDevice, stream));
-        BA_HIPCHK(hipMemcpyAsync(d_pts_bk, d_pts, sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, stream));
+        rc = backup();
+        if (rc) return rc;
         if (it == 0 && qmax == 0) {
           double maxdiag = 0.0;
           if (!(opt.user_lambda_init > 0)) {
             // computeLambdaInit: tau * max diagonal entry of the (undamped) Hessian over all vertices
-            hipLaunchKernelGGL(k_ba_points, dim3(gp), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_lin, 1.0,
-                               d_Hinv, d_bp, d_pdmax);
-            hipLaunchKernelGGL(k_ba_obs2, dim3(go), dim3(WG), 0, stream, NO, d_op, d_lin, d_Hinv, d_Z);
-            hipLaunchKernelGGL(k_ba_reduced, dim3((nblk + 3) / 4), dim3(WG), 0, stream, nblk, d_brow, d_bcol,
-                               d_sptr, d_sa, d_sb, d_op, d_lin, d_Z, d_bp, d_fixed, 1.0, d_S, d_g, d_bc,
-                               d_cdmax);
-            hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)nullptr, 0,
-                               (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)d_pdmax, NP,
-                               (const double*)d_cdmax, 7 * NC, d_sc);
+            launch_reduced(1.0);
+            launch_maxdiag();
             BA_HIPCHK(hipGetLastError());
             rc = fetch();
             if (rc) return rc;
@@ -838,34 +901,14 @@ struct Problem {
           damp.start(opt.user_lambda_init, opt.tau, maxdiag);
         }
         const double lambda = damp.lambda;
-        BA_HIPCHK(hipMemsetAsync(&d_sc->pcg_iters, 0, 2 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(k_ba_points, dim3(gp), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_lin, lambda,
-                           d_Hinv, d_bp, d_pdmax);
-        hipLaunchKernelGGL(k_ba_obs2, dim3(go), dim3(WG), 0, stream, NO, d_op, d_lin, d_Hinv, d_Z);
-        hipLaunchKernelGGL(k_ba_reduced, dim3((nblk + 3) / 4), dim3(WG), 0, stream, nblk, d_brow, d_bcol,
-                           d_sptr, d_sa, d_sb, d_op, d_lin, d_Z, d_bp, d_fixed, lambda, d_S, d_g, d_bc,
-                           d_cdmax);
-        if (direct.ready()) {
-          direct.gather(d_S, d_g, stream);
-          BA_HIPCHK(direct.factor(0.0, &d_sc->fail, 1, d_xc, stream));  // lambda 0: S carries the damping already
-        } else {
-          hipLaunchKernelGGL(k_ba_pcg, dim3(1), dim3(1024), 0, stream, NC, d_rptr, d_bcol, d_S, d_g, d_xc, d_r,
-                             d_z, d_p, d_q, d_Dinv, opt.pcg_max_iters > 0 ? opt.pcg_max_iters : 20 * NC + 100,
-                             opt.pcg_rel_tol * opt.pcg_rel_tol, d_sc);
-        }
-        hipLaunchKernelGGL(k_ba_backsub, dim3(gp), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_oc, d_Hinv,
-                           d_bp, d_Z, d_xc, d_xp);
-        hipLaunchKernelGGL(k_ba_update, dim3((std::max(NC, 3 * NP) + WG - 1) / WG), dim3(WG), 0, stream, NC, NP,
-                           d_xc, d_xp, d_fixed, d_cams, d_pts, (const Scal*)d_sc);
-        // scale = x.(lambda x + b) over cameras and points
-        const int gsc = std::max(1, std::min(1024, (7 * NC + WG - 1) / WG));
-        const int gsp = std::max(1, std::min(1024, (3 * NP + WG - 1) / WG));
-        hipLaunchKernelGGL(k_ba_scale, dim3(gsc), dim3(WG), 0, stream, 7 * NC, d_xc, d_bc, lambda, d_pb);
-        hipLaunchKernelGGL(k_ba_scale, dim3(gsp), dim3(WG), 0, stream, 3 * NP, d_xp, d_bp, lambda, d_pc);
-        hipLaunchKernelGGL(k_ba_chi2, dim3(grid_chi), dim3(WG), 0, stream, oargs(), d_pa);
-        hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)d_pa, grid_chi,
-                           (const double*)d_pb, gsc, (const double*)d_pc, gsp, (const double*)nullptr, 0,
-                           (const double*)nullptr, 0, d_sc);
+        rc = clear_solver_flags();
+        if (rc) return rc;
+        launch_reduced(lambda);
+        rc = launch_solve(direct.ready(), opt.pcg_max_iters, opt.pcg_rel_tol);
+        if (rc) return rc;
+        launch_backsub();
+        launch_update();
+        launch_trial_sums(lambda);
         BA_HIPCHK(hipGetLastError());
         rc = fetch();
         if (rc) return rc;
@@ -876,8 +919,8 @@ struct Problem {
         if (damp.update(currentChi, tempChi, scale, 1.0 / 3.0, 2.0 / 3.0, rho)) {
           currentChi = tempChi;
         } else {
-          BA_HIPCHK(hipMemcpyAsync(d_cams, d_cams_bk, sizeof(Cam) * NC, hipMemcpyDeviceToDevice, stream));
-          BA_HIPCHK(hipMemcpyAsync(d_pts, d_pts_bk, sizeof(double) * 3 * NP, hipMemcpyDeviceToDevice, stream));
+          rc = restore();
+          if (rc) return rc;
         }
         ++qmax;
       } while (rho < 0 && qmax < opt.max_trials);
@@ -896,6 +939,87 @@ struct Problem {
     BA_HIPCHK(hipMemcpy(cams.data(), d_cams, sizeof(Cam) * NC, hipMemcpyDeviceToHost));
     BA_HIPCHK(hipMemcpy(pts.data(), d_pts, sizeof(double) * 3 * NP, hipMemcpyDeviceToHost));
     return iters;
+  }
+
+  // ---- diagnostic read-outs: the launches above, then copies to the host.  Every buffer they write is one
+  // optimize() rewrites before it reads it, and the estimate is restored from the trial's backup buffers. ----
+  int down(void* dst, const void* src, size_t bytes) {
+    if (!dst || !bytes) return SIM3OPT_OK;
+    BA_HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+    BA_HIPCHK(hipStreamSynchronize(stream));
+    return SIM3OPT_OK;
+  }
+  int read_lin(double* lin) {
+    launch_linearize();
+    BA_HIPCHK(hipGetLastError());
+    return down(lin, d_lin, sizeof(double) * 20 * no());
+  }
+  int read_reduced(double lambda, double* S, double* g, double* bc, double* Hinv, double* bp, double* Z,
+                   double* pdmax, double* cdmax, double* maxdiag) {
+    launch_linearize();
+    launch_reduced(lambda);
+    launch_maxdiag();
+    BA_HIPCHK(hipGetLastError());
+    int rc = fetch();
+    if (rc) return rc;
+    if (maxdiag) *maxdiag = h_sc->maxdiag;
+    const size_t NC = nc(), NP = np(), NO = no(), D = sizeof(double);
+    if ((rc = down(S, d_S, D * 49 * nblk)) || (rc = down(g, d_g, D * 7 * NC)) || (rc = down(bc, d_bc, D * 7 * NC)) ||
+        (rc = down(Hinv, d_Hinv, D * 9 * NP)) || (rc = down(bp, d_bp, D * 3 * NP)) || (rc = down(Z, d_Z, D * 18 * NO)) ||
+        (rc = down(pdmax, d_pdmax, D * NP)) || (rc = down(cdmax, d_cdmax, D * 7 * NC)))
+      return rc;
+    return SIM3OPT_OK;
+  }
+  int read_step(double lambda, bool exact, int pcg_max_iters, double pcg_rel_tol, double* dxc, double* dxp,
+                int32_t* iters, double* rel, int32_t* fail) {
+    launch_linearize();
+    int rc = clear_solver_flags();
+    if (rc) return rc;
+    launch_reduced(lambda);
+    rc = launch_solve(exact, pcg_max_iters, pcg_rel_tol);
+    if (rc) return rc;
+    launch_backsub();
+    BA_HIPCHK(hipGetLastError());
+    rc = fetch();
+    if (rc) return rc;
+    if (iters) *iters = h_sc->pcg_iters;
+    if (rel) *rel = exact ? 0.0 : h_sc->pcg_rel;
+    if (fail) *fail = h_sc->fail;
+    if ((rc = down(dxc, d_xc, sizeof(double) * 7 * nc())) || (rc = down(dxp, d_xp, sizeof(double) * 3 * np())))
+      return rc;
+    return clear_solver_flags();
+  }
+  int read_update(const double* dxc, const double* dxp, double lambda, bool with_fail, double* cam_qt, double* points,
+                  double* chi2_out, double* scale_out) {
+    const int NC = nc(), NP = np();
+    launch_linearize();
+    launch_reduced(lambda);  // b_c, b_p of the scale term
+    int rc = backup();
+    if (rc) return rc;
+    BA_HIPCHK(hipMemcpyAsync(d_xc, dxc, sizeof(double) * 7 * NC, hipMemcpyHostToDevice, stream));
+    BA_HIPCHK(hipMemcpyAsync(d_xp, dxp, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, stream));
+    const int32_t flags[2] = {0, with_fail ? 1 : 0};  // pcg_iters, fail
+    BA_HIPCHK(hipMemcpyAsync(&d_sc->pcg_iters, flags, sizeof(flags), hipMemcpyHostToDevice, stream));
+    launch_update();
+    launch_trial_sums(lambda);
+    BA_HIPCHK(hipGetLastError());
+    rc = fetch();
+    if (rc) return rc;
+    if (chi2_out) *chi2_out = h_sc->chi2;
+    if (scale_out) *scale_out = h_sc->scale;
+    std::vector<Cam> hc(cam_qt ? NC : 0);
+    if ((rc = down(hc.data(), d_cams, sizeof(Cam) * hc.size())) || (rc = down(points, d_pts, sizeof(double) * 3 * NP)))
+      return rc;
+    for (size_t c = 0; c < hc.size(); ++c) {
+      for (int i = 0; i < 4; ++i) cam_qt[7 * c + i] = hc[c].q[i];
+      for (int i = 0; i < 3; ++i) cam_qt[7 * c + 4 + i] = hc[c].t[i];
+    }
+    rc = restore();
+    if (rc) return rc;
+    rc = clear_solver_flags();
+    if (rc) return rc;
+    BA_HIPCHK(hipStreamSynchronize(stream));
+    return SIM3OPT_OK;
   }
 };
 
@@ -1085,6 +1209,100 @@ int sim3opt_ba_chi2(sim3opt_ba* b, double* chi2) {
   return b->chi2(chi2);
   } catch (...) {  // nothing crosses the C boundary
     b->err = "ba_chi2: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
+  }
+}
+
+// ---- diagnostic read-outs (include/sim3opt.h, "Diagnostic."): nothing in the solver uses them ----
+namespace {
+// the checks every read-out begins with; leaves the problem uploaded
+int ba_debug_enter(sim3opt_ba* b, const char* what) {
+  b->err.clear();
+  if (b->no() < 1) { b->err = std::string(what) + ": no problem set"; return SIM3OPT_ERR_STATE; }
+  if (!b->ready) { int rc = b->initialize(); if (rc) return rc; }
+  return SIM3OPT_OK;
+}
+}  // namespace
+
+int sim3opt_ba_debug_pattern(sim3opt_ba* b, int32_t* n_blocks, int32_t* rptr, int32_t* bcol) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  try {
+  int rc = ba_debug_enter(b, "ba_debug_pattern");
+  if (rc) return rc;
+  if (!n_blocks || (!rptr != !bcol)) { b->err = "ba_debug_pattern: NULL output"; return SIM3OPT_ERR_ARG; }
+  *n_blocks = b->nblk;
+  if (!rptr) return SIM3OPT_OK;  // size query
+  if ((rc = b->down(rptr, b->d_rptr, sizeof(int32_t) * (b->nc() + 1))) ||
+      (rc = b->down(bcol, b->d_bcol, sizeof(int32_t) * b->nblk)))
+    return rc;
+  return SIM3OPT_OK;
+  } catch (...) {  // nothing crosses the C boundary
+    b->err = "ba_debug_pattern: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
+  }
+}
+
+int sim3opt_ba_debug_linearization(sim3opt_ba* b, double* lin) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  try {
+  int rc = ba_debug_enter(b, "ba_debug_linearization");
+  if (rc) return rc;
+  if (!lin) { b->err = "ba_debug_linearization: NULL output"; return SIM3OPT_ERR_ARG; }
+  return b->read_lin(lin);
+  } catch (...) {  // nothing crosses the C boundary
+    b->err = "ba_debug_linearization: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
+  }
+}
+
+int sim3opt_ba_debug_reduced(sim3opt_ba* b, double lambda, double* S, double* g, double* b_c, double* Hpp_inv,
+                             double* b_p, double* Z, double* point_maxdiag, double* cam_maxdiag, double* maxdiag) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  try {
+  int rc = ba_debug_enter(b, "ba_debug_reduced");
+  if (rc) return rc;
+  if (!std::isfinite(lambda)) { b->err = "ba_debug_reduced: lambda is not finite"; return SIM3OPT_ERR_ARG; }
+  if (!S && !g && !b_c && !Hpp_inv && !b_p && !Z && !point_maxdiag && !cam_maxdiag && !maxdiag) {
+    b->err = "ba_debug_reduced: every output is NULL";
+    return SIM3OPT_ERR_ARG;
+  }
+  return b->read_reduced(lambda, S, g, b_c, Hpp_inv, b_p, Z, point_maxdiag, cam_maxdiag, maxdiag);
+  } catch (...) {  // nothing crosses the C boundary
+    b->err = "ba_debug_reduced: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
+  }
+}
+
+int sim3opt_ba_debug_step(sim3opt_ba* b, double lambda, int32_t solver, int32_t pcg_max_iters, double pcg_rel_tol,
+                          double* dx_c, double* dx_p, int32_t* pcg_iters, double* pcg_rel, int32_t* fail) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  try {
+  int rc = ba_debug_enter(b, "ba_debug_step");
+  if (rc) return rc;
+  if (!std::isfinite(lambda) || solver < 0 || solver > 1 || pcg_max_iters < 0 || !(pcg_rel_tol >= 0)) {
+    b->err = "ba_debug_step: value out of range";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (!dx_c || !dx_p || !fail) { b->err = "ba_debug_step: NULL output"; return SIM3OPT_ERR_ARG; }
+  if (solver == 1 && !b->direct.ready()) {
+    b->err = "ba_debug_step: the exact solver was asked of a problem initialised without a factorisation plan "
+             "(options.linear_solver = 0, or the plan was refused)";
+    return SIM3OPT_ERR_STATE;
+  }
+  return b->read_step(lambda, solver == 1, pcg_max_iters, pcg_rel_tol, dx_c, dx_p, pcg_iters, pcg_rel, fail);
+  } catch (...) {  // nothing crosses the C boundary
+    b->err = "ba_debug_step: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
+  }
+}
+
+int sim3opt_ba_debug_update(sim3opt_ba* b, const double* dx_c, const double* dx_p, double lambda, int32_t with_fail,
+                            double* cam_qt, double* points, double* chi2, double* scale) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  try {
+  int rc = ba_debug_enter(b, "ba_debug_update");
+  if (rc) return rc;
+  if (!dx_c || !dx_p) { b->err = "ba_debug_update: NULL step"; return SIM3OPT_ERR_ARG; }
+  if (!cam_qt && !points && !chi2 && !scale) { b->err = "ba_debug_update: every output is NULL"; return SIM3OPT_ERR_ARG; }
+  if (!std::isfinite(lambda)) { b->err = "ba_debug_update: lambda is not finite"; return SIM3OPT_ERR_ARG; }
+  return b->read_update(dx_c, dx_p, lambda, with_fail != 0, cam_qt, points, chi2, scale);
+  } catch (...) {  // nothing crosses the C boundary
+    b->err = "ba_debug_update: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
   }
 }
 

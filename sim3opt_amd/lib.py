@@ -259,6 +259,11 @@ SYMBOLS = {
     "sim3opt_ba_num_iterations": (C.c_int32, [_vp]),
     "sim3opt_ba_get_stats": (C.c_int, [_vp, C.c_int32, C.POINTER(IterStats)]),
     "sim3opt_ba_write_poses": (C.c_int, [_vp, C.c_char_p]),
+    "sim3opt_ba_debug_pattern": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "sim3opt_ba_debug_linearization": (C.c_int, [_vp, _dp]),
+    "sim3opt_ba_debug_reduced": (C.c_int, [_vp, C.c_double] + [_dp] * 9),
+    "sim3opt_ba_debug_step": (C.c_int, [_vp, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp, _dp, _ip, _dp, _ip]),
+    "sim3opt_ba_debug_update": (C.c_int, [_vp, _dp, _dp, C.c_double, C.c_int32, _dp, _dp, _dp, _dp]),
 }
 
 _lib = None
@@ -1149,6 +1154,65 @@ class BundleAdjuster:
 
     def write_poses(self, path):
         self._chk(self._L.sim3opt_ba_write_poses(self._b, os.fsencode(path)), "ba_write_poses")
+
+    # ---- diagnostic read-outs (sim3opt_ba_debug_*): nothing in the solver uses them, and an optimize() after one of
+    # them computes bit for bit what it computes without it ----
+    def debug_pattern(self):
+        """(rptr, bcol) of the reduced camera system's block-CSR pattern, the diagonal block first in every row."""
+        n = C.c_int32()
+        self._chk(self._L.sim3opt_ba_debug_pattern(self._b, C.byref(n), None, None), "ba_debug_pattern")
+        rptr, bcol = np.empty(self.dims()[0] + 1, dtype=np.int32), np.empty(n.value, dtype=np.int32)
+        self._chk(self._L.sim3opt_ba_debug_pattern(self._b, C.byref(n), _p(rptr, _ip), _p(bcol, _ip)),
+                  "ba_debug_pattern")
+        return rptr, bcol
+
+    def debug_linearization(self):
+        """lin (n_obs, 20) = [A (2x6), B (2x3), es (2)] of the current estimate, as k_ba_obs writes it."""
+        lin = np.empty((self.dims()[2], 20))
+        self._chk(self._L.sim3opt_ba_debug_linearization(self._b, _p(lin, _dp)), "ba_debug_linearization")
+        return lin
+
+    def debug_reduced(self, lam):
+        """The reduced system of an LM trial with damping lam: dict of S (nblk, 7, 7) [k, r, c], g, b_c (nc, 7),
+        Hpp_inv (np, 3, 3), b_p (np, 3), Z (no, 6, 3), point_maxdiag (np,), cam_maxdiag (nc, 7), maxdiag, and the
+        pattern rptr, bcol."""
+        nc, npt, no = self.dims()
+        rptr, bcol = self.debug_pattern()
+        nblk = bcol.shape[0]
+        S, g, bc = np.empty((nblk, 49)), np.empty((nc, 7)), np.empty((nc, 7))
+        Hi, bp, Z = np.empty((npt, 3, 3)), np.empty((npt, 3)), np.empty((no, 6, 3))
+        pd, cd, md = np.empty(npt), np.empty((nc, 7)), C.c_double()
+        self._chk(self._L.sim3opt_ba_debug_reduced(self._b, float(lam), _p(S, _dp), _p(g, _dp), _p(bc, _dp),
+                                                   _p(Hi, _dp), _p(bp, _dp), _p(Z, _dp), _p(pd, _dp), _p(cd, _dp),
+                                                   C.byref(md)), "ba_debug_reduced")
+        # stored column-major (entry (r, c) at r + 7 c): [k, r, c] is the transpose of the raw [k, c, r]
+        return dict(S=np.ascontiguousarray(S.reshape(nblk, 7, 7).transpose(0, 2, 1)), g=g, b_c=bc, Hpp_inv=Hi, b_p=bp,
+                    Z=Z, point_maxdiag=pd, cam_maxdiag=cd, maxdiag=md.value, rptr=rptr, bcol=bcol)
+
+    def debug_step(self, lam, solver=1, pcg_max_iters=0, pcg_rel_tol=1e-12):
+        """The step of an LM trial with damping lam: solver 1 the exact block Cholesky, 0 k_ba_pcg with the given cap
+        (the iterate x_k) and tolerance.  dict of dx_c (nc, 7), dx_p (np, 3), iters, rel, fail."""
+        nc, npt, _ = self.dims()
+        xc, xp = np.empty((nc, 7)), np.empty((npt, 3))
+        it, fail, rel = C.c_int32(), C.c_int32(), C.c_double()
+        self._chk(self._L.sim3opt_ba_debug_step(self._b, float(lam), int(solver), int(pcg_max_iters),
+                                                float(pcg_rel_tol), _p(xc, _dp), _p(xp, _dp), C.byref(it),
+                                                C.byref(rel), C.byref(fail)), "ba_debug_step")
+        return dict(dx_c=xc, dx_p=xp, iters=it.value, rel=rel.value, fail=fail.value)
+
+    def debug_update(self, dx_c, dx_p, lam=0.0, fail=False):
+        """What an LM trial makes of the step dx_c (nc, 7), dx_p (np, 3): dict of cams (nc, 7), points (np, 3), chi2
+        of that estimate and scale = x . (lam x + b).  The estimate is restored afterwards."""
+        nc, npt, _ = self.dims()
+        xc, xp = _f64(dx_c).reshape(-1), _f64(dx_p).reshape(-1)
+        if xc.shape[0] != 7 * nc or xp.shape[0] != 3 * npt:
+            raise ValueError("dx_c holds 7 numbers per camera, dx_p 3 per point")
+        cams, pts = np.empty((nc, 7)), np.empty((npt, 3))
+        chi, sc = C.c_double(), C.c_double()
+        self._chk(self._L.sim3opt_ba_debug_update(self._b, _p(xc, _dp), _p(xp, _dp), float(lam), int(bool(fail)),
+                                                  _p(cams, _dp), _p(pts, _dp), C.byref(chi), C.byref(sc)),
+                  "ba_debug_update")
+        return dict(cams=cams, points=pts, chi2=chi.value, scale=sc.value)
 
 
 def align_trajectory(query_xyz, train_xyz, with_scale=True):

@@ -156,6 +156,16 @@ def test_ba_argument_checks():
     assert b.optimize(5) == -1  # empty problem: g2o's optimize() returns -1 without edges
 
 
+def test_ba_readouts_refuse_without_a_problem():
+    """The diagnostic read-outs answer SIM3OPT_ERR_STATE with a message before they touch a device."""
+    b = L.BundleAdjuster()
+    for call in (b.debug_pattern, b.debug_linearization, lambda: b.debug_reduced(1.0), lambda: b.debug_step(1.0),
+                 lambda: b.debug_update(np.zeros((0, 7)), np.zeros((0, 3)))):
+        with pytest.raises(L.Sim3OptError) as e:
+            call()
+        assert e.value.code == L.ERR_STATE and "no problem set" in str(e.value)
+
+
 # ------------------------------------------------------------------------------------------ GPU
 def gpu_problem(P, **opts):
     b = L.BundleAdjuster(**opts)
