@@ -743,6 +743,67 @@ int sim3opt_ba_debug_step(sim3opt_ba* b, double lambda, int32_t solver, int32_t 
 int sim3opt_ba_debug_update(sim3opt_ba* b, const double* dx_c, const double* dx_p, double lambda, int32_t with_fail,
                             double* cam_qt, double* points, double* chi2, double* scale);
 
+/* ---- batched two-view bundle adjustment: the loop detector's refinement, every candidate in one launch ----
+ * BAOptimize (kittiDetector.h:845-954, helpers :712-788), which the detector calls once per accepted loop
+ * candidate (:1325) and whose result is line 4 of a loopConstraints.txt record: two VertexSE3Expmap cameras, the
+ * first fixed (:861-870), the matched points as VertexSBAPointXYZ (:892-894), two EdgeProjectXYZ2UV observations
+ * per point with information I and RobustKernelHuber (:753-770, :895-901), LM over BlockSolver_6_3 (:716-731).
+ * Problem k owns the points point_ptr[k] .. point_ptr[k+1]-1; all problems share one CameraParameters.  Device
+ * pipeline: sim3opt_amd/csrc/ba_batch.hip, one workgroup per problem, the whole LM loop on the device.  A
+ * problem's result does not depend on the other problems of the batch or on its place among them.  No CPU
+ * fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_ba_batch sim3opt_ba_batch;
+
+typedef struct sim3opt_ba_batch_options {
+  double huber_delta;       /* RobustKernelHuber delta; 0 = no robust kernel   default 3.0    :1325 OptParams(10, true, 3) */
+  double pixel_noise;       /* information = I / pixel_noise^2                  default 1.0    :758-764 (weight = 1)        */
+  double tau;               /* lambda_0 = tau * max diag(H) when user_lambda_init <= 0         default 1e-5                */
+  double user_lambda_init;  /* > 0: lambda_0                                    default 50.0   :779-782 setUserLambdaInit   */
+  double outlier_chi2;      /* an observation above it counts as an outlier     default 5.995  :847, :947-953               */
+  int32_t max_iters;        /* LM iterations                                    default 10     :1325, :786                  */
+  int32_t max_trials;       /* LM trials per iteration                          default 5      :730 setMaxTrialsAfterFailure */
+  int32_t device;           /* HIP device ordinal, -1 = current                 default -1                                  */
+} sim3opt_ba_batch_options;
+
+void sim3opt_ba_batch_options_default(sim3opt_ba_batch_options* o);
+sim3opt_ba_batch* sim3opt_ba_batch_create(void);
+void sim3opt_ba_batch_destroy(sim3opt_ba_batch* b);
+const char* sim3opt_ba_batch_last_error(const sim3opt_ba_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: max_iters < 1, max_trials < 1, pixel_noise <= 0, tau <= 0, huber_delta < 0, a
+ * non-finite value. */
+int sim3opt_ba_batch_set_options(sim3opt_ba_batch* b, const sim3opt_ba_batch_options* o);
+/* The arguments of BAOptimize (:845-846) for n_problems candidates at once: point_ptr (n_problems + 1, ragged,
+ * point_ptr[0] = 0), cam0 (n x 7 [qx qy qz qw tx ty tz] of T_w2c, fixed; the reference's is the identity, :861-869),
+ * cam1 (n x 7, the start: Rf2s and tfins, :873-887), points (total x 3 in camera 0's world: pointsXYZ), uv0 / uv1
+ * (total x 2: points1 / points2), focal / cx / cy of K (:850-854).  Quaternions are normalised as
+ * sim3opt_ba_set_problem normalises them.  SIM3OPT_ERR_ARG with nothing changed: n_problems < 1, a problem with no
+ * point, a non-monotone point_ptr, a non-finite number, a zero quaternion, focal <= 0, a NULL array. */
+int sim3opt_ba_batch_set_problems(sim3opt_ba_batch* b, int32_t n_problems, const int32_t* point_ptr,
+                                  const double* cam0, const double* cam1, const double* points, const double* uv0,
+                                  const double* uv1, double focal, double cx, double cy);
+int sim3opt_ba_batch_dims(const sim3opt_ba_batch* b, int32_t* n_problems, int32_t* total_points);
+/* runSparseBAOptimizer (:772-788) of every problem, ONE kernel launch for the batch.  Returns the number of
+ * problems optimised, or a negative SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no problems set).  The estimates move:
+ * another call continues from them, sim3opt_ba_batch_set_problems starts again. */
+int sim3opt_ba_batch_optimize(sim3opt_ba_batch* b);
+/* cam0 (n x 7, exactly as given) and / or cam1 (n x 7: Rf2s, tfins of :915-921); either may be NULL */
+int sim3opt_ba_batch_get_cameras(const sim3opt_ba_batch* b, double* cam0, double* cam1);
+int sim3opt_ba_batch_get_points(const sim3opt_ba_batch* b, double* points /* total x 3 */);
+/* LM iterations problem `problem` ran in the last optimize, and their records (chi2_before, chi2_after, lambda,
+ * rho, trials; the other fields 0) */
+int32_t sim3opt_ba_batch_num_iterations(const sim3opt_ba_batch* b, int32_t problem);
+int sim3opt_ba_batch_get_stats(const sim3opt_ba_batch* b, int32_t problem, int32_t iter, sim3opt_iter_stats* out);
+/* lambda_0 of every problem in the last optimize (n): user_lambda_init, or computeLambdaInit's tau * max diag(H)
+ * over camera 1 and the points.  SIM3OPT_ERR_STATE before the first optimize. */
+int sim3opt_ba_batch_get_lambda_init(const sim3opt_ba_batch* b, double* lambda_init);
+/* Of the last optimize, per problem: g2o's activeChi2 (not robustified) before and after, which the reference
+ * prints (:785-787, :907), active_before / active_after (n each); e->chi2() of every observation at the final
+ * estimate, edge_chi2 (total x 2: camera 0's, camera 1's observation of each point, the order of `edges`, :891-902);
+ * the observations above outlier_chi2, n_outlier_edges (n; :947-953).  Each may be NULL, not all.
+ * SIM3OPT_ERR_STATE before the first optimize. */
+int sim3opt_ba_batch_get_chi2(const sim3opt_ba_batch* b, double* active_before, double* active_after,
+                              double* edge_chi2, int32_t* n_outlier_edges);
+
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933
  * Null vector of the edge equations s_C x[v0] - x[v1] = 0 (the reference: last column of V of

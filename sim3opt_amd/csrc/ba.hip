@@ -27,6 +27,7 @@
 //   k_ba_update   exp-map update of the cameras, additive update of the points (backup kept)
 //   k_ba_chi2     thread / observation: robustified chi2, fixed-order block sums
 // The host runs g2o's lambda policy on three scalars per trial: engine.hip's LmDamping (lm_damping.hpp).
+// The camera / point arithmetic is ba_math.hpp's, shared with the batched two-view kernel (ba_batch.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +41,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "ba_math.hpp"
 #include "devmem.hpp"
 #include "direct_factor.hpp"
 #include "lm_damping.hpp"
@@ -70,33 +72,6 @@ struct Scal {
 using sim3opt::ldl_sum_over_c;
 using sim3opt::LmDamping;
 
-__device__ __forceinline__ void quat_to_R(const double q[4], double R[9]) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
-  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
-}
-
-// Eigen's Quaternion(Matrix3) (trace branch, else the largest diagonal entry)
-__device__ __forceinline__ void R_to_quat(const double R[9], double q[4]) {
-  const double tr = R[0] + R[4] + R[8];
-  if (tr > 0) {
-    double k = sqrt(tr + 1.0);
-    q[3] = 0.5 * k; k = 0.5 / k;
-    q[0] = (R[7] - R[5]) * k; q[1] = (R[2] - R[6]) * k; q[2] = (R[3] - R[1]) * k;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[4 * i]) i = 2;
-    const int j = (i + 1) % 3, l = (j + 1) % 3;
-    double k = sqrt(R[4 * i] - R[4 * j] - R[4 * l] + 1.0);
-    q[i] = 0.5 * k; k = 0.5 / k;
-    q[3] = (R[3 * l + j] - R[3 * j + l]) * k;
-    q[j] = (R[3 * j + i] + R[3 * i + j]) * k;
-    q[l] = (R[3 * l + i] + R[3 * i + l]) * k;
-  }
-}
-
 struct ObsArgs {
   int32_t n_obs;
   const int32_t* oc;
@@ -111,23 +86,7 @@ struct ObsArgs {
 __device__ __forceinline__ void ba_residual(const ObsArgs& A, int o, double R[9], double X[3], double e[2]) {
   const Cam c = A.cams[A.oc[o]];
   const double* p = A.pts + (size_t)3 * A.op[o];
-  quat_to_R(c.q, R);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) X[i] = R[3 * i] * p[0] + R[3 * i + 1] * p[1] + R[3 * i + 2] * p[2] + c.t[i];
-  e[0] = A.uv[2 * (size_t)o] - (A.f * X[0] / X[2] + A.cx);
-  e[1] = A.uv[2 * (size_t)o + 1] - (A.f * X[1] / X[2] + A.cy);
-}
-
-// g2o RobustKernelHuber on e2 = e^T Omega e
-__device__ __forceinline__ void ba_huber(double e2, double delta, double& rho, double& w) {
-  if (delta <= 0.0 || e2 <= delta * delta) {
-    rho = e2;
-    w = 1.0;
-  } else {
-    const double sq = sqrt(e2);
-    rho = 2 * sq * delta - delta * delta;
-    w = delta / sq;
-  }
+  ba_project_residual(c.q, c.t, p, A.uv[2 * (size_t)o], A.uv[2 * (size_t)o + 1], A.f, A.cx, A.cy, R, X, e);
 }
 
 // per observation: 20 doubles [A (2x6 row-major), B (2x3 row-major), es (2)], all scaled by sqrt(w Omega)
@@ -136,21 +95,11 @@ __global__ __launch_bounds__(WG) void k_ba_obs(ObsArgs A, double* __restrict__ l
   if (o >= A.n_obs) return;
   double R[9], X[3], e[2];
   ba_residual(A, o, R, X, e);
-  const double x = X[0], y = X[1], z = X[2], f = A.f, z2 = z * z;
   double rho, w;
   ba_huber(A.omega * (e[0] * e[0] + e[1] * e[1]), A.huber, rho, w);
   const double sw = sqrt(w * A.omega);
-  // EdgeProjectXYZ2UV::linearizeOplus (analytic): J_cam over [omega, upsilon]
-  double Jc[12] = {x * y / z2 * f, -(1 + x * x / z2) * f, y / z * f, -1.0 / z * f, 0.0, x / z2 * f,
-                   (1 + y * y / z2) * f, -x * y / z2 * f, -x / z * f, 0.0, -1.0 / z * f, y / z2 * f};
-  // J_point = -1/z [[f, 0, -f x/z], [0, f, -f y/z]] R
-  const double t0[3] = {f, 0.0, -x / z * f}, t1[3] = {0.0, f, -y / z * f};
-  double Jp[6];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    Jp[c] = -(t0[0] * R[c] + t0[1] * R[3 + c] + t0[2] * R[6 + c]) / z;
-    Jp[3 + c] = -(t1[0] * R[c] + t1[1] * R[3 + c] + t1[2] * R[6 + c]) / z;
-  }
+  double Jc[12], Jp[6];
+  ba_jacobians(R, X, A.f, Jc, Jp);
   double* d = lin + (size_t)20 * o;
 #pragma unroll
   for (int i = 0; i < 12; ++i) d[i] = sw * Jc[i];
@@ -184,14 +133,7 @@ __global__ __launch_bounds__(WG) void k_ba_points(int np, const int32_t* __restr
   }
   pdmax[p] = fmax(H[0], fmax(H[3], H[5]));
   const double a = H[0] + lambda, bb = H[1], c = H[2], dd = H[3] + lambda, ee = H[4], ff = H[5] + lambda;
-  // inverse of the symmetric 3x3 by cofactors
-  const double c00 = dd * ff - ee * ee, c01 = c * ee - bb * ff, c02 = bb * ee - c * dd;
-  const double det = a * c00 + bb * c01 + c * c02;
-  const double id = 1.0 / det;
-  double* Hi = Hinv + (size_t)9 * p;
-  Hi[0] = c00 * id; Hi[1] = c01 * id; Hi[2] = c02 * id;
-  Hi[3] = c01 * id; Hi[4] = (a * ff - c * c) * id; Hi[5] = (bb * c - a * ee) * id;
-  Hi[6] = c02 * id; Hi[7] = (bb * c - a * ee) * id; Hi[8] = (a * dd - bb * bb) * id;
+  ba_sym3_inverse(a, bb, c, dd, ee, ff, Hinv + (size_t)9 * p);
   bp[3 * (size_t)p] = b[0]; bp[3 * (size_t)p + 1] = b[1]; bp[3 * (size_t)p + 2] = b[2];
 }
 
@@ -472,50 +414,8 @@ __global__ __launch_bounds__(WG) void k_ba_update(int nc, int np, const double* 
   if (sc->fail) return;  // the host rejects the trial
   const int t = blockIdx.x * WG + threadIdx.x;
   if (t < nc && !fixed[t]) {
-    const double* u = xc + (size_t)7 * t;
-    const double th = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double Om[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
-    double Om2[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Om2[3 * i + j] = Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j] + Om[3 * i + 2] * Om[6 + j];
-    double R[9], V[9];
-    if (th < 1e-5) {  // se3quat.h: R = I + Omega + Omega^2, V = R
-#pragma unroll
-      for (int i = 0; i < 9; ++i) R[i] = Om[i] + Om2[i];
-      R[0] += 1; R[4] += 1; R[8] += 1;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) V[i] = R[i];
-    } else {
-      const double a = sin(th) / th, b = (1 - cos(th)) / (th * th), c = (th - sin(th)) / (th * th * th);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        R[i] = a * Om[i] + b * Om2[i];
-        V[i] = b * Om[i] + c * Om2[i];
-      }
-      R[0] += 1; R[4] += 1; R[8] += 1;
-      V[0] += 1; V[4] += 1; V[8] += 1;
-    }
     Cam cm = cams[t];
-    double Rc[9], Rn[9];
-    quat_to_R(cm.q, Rc);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Rn[3 * i + j] = R[3 * i] * Rc[j] + R[3 * i + 1] * Rc[3 + j] + R[3 * i + 2] * Rc[6 + j];
-    double tn[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      tn[i] = R[3 * i] * cm.t[0] + R[3 * i + 1] * cm.t[1] + R[3 * i + 2] * cm.t[2] +
-              V[3 * i] * u[3] + V[3 * i + 1] * u[4] + V[3 * i + 2] * u[5];
-    double q[4];
-    R_to_quat(Rn, q);
-    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cm.q[i] = q[i] / nq;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) cm.t[i] = tn[i];
+    ba_se3_oplus(xc + (size_t)7 * t, cm.q, cm.t);
     cams[t] = cm;
   }
   if (t < 3 * np) pts[t] += xp[t];

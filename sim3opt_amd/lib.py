@@ -127,6 +127,20 @@ class BaOptions(C.Structure):
     ]
 
 
+class BaBatchOptions(C.Structure):
+    """sim3opt_ba_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("huber_delta", C.c_double),
+        ("pixel_noise", C.c_double),
+        ("tau", C.c_double),
+        ("user_lambda_init", C.c_double),
+        ("outlier_chi2", C.c_double),
+        ("max_iters", C.c_int32),
+        ("max_trials", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -264,6 +278,21 @@ SYMBOLS = {
     "sim3opt_ba_debug_reduced": (C.c_int, [_vp, C.c_double] + [_dp] * 9),
     "sim3opt_ba_debug_step": (C.c_int, [_vp, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp, _dp, _ip, _dp, _ip]),
     "sim3opt_ba_debug_update": (C.c_int, [_vp, _dp, _dp, C.c_double, C.c_int32, _dp, _dp, _dp, _dp]),
+    "sim3opt_ba_batch_options_default": (None, [C.POINTER(BaBatchOptions)]),
+    "sim3opt_ba_batch_create": (_vp, []),
+    "sim3opt_ba_batch_destroy": (None, [_vp]),
+    "sim3opt_ba_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_ba_batch_set_options": (C.c_int, [_vp, C.POINTER(BaBatchOptions)]),
+    "sim3opt_ba_batch_set_problems": (C.c_int, [_vp, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double,
+                                                C.c_double]),
+    "sim3opt_ba_batch_dims": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_ba_batch_optimize": (C.c_int, [_vp]),
+    "sim3opt_ba_batch_get_cameras": (C.c_int, [_vp, _dp, _dp]),
+    "sim3opt_ba_batch_get_points": (C.c_int, [_vp, _dp]),
+    "sim3opt_ba_batch_num_iterations": (C.c_int32, [_vp, C.c_int32]),
+    "sim3opt_ba_batch_get_stats": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(IterStats)]),
+    "sim3opt_ba_batch_get_lambda_init": (C.c_int, [_vp, _dp]),
+    "sim3opt_ba_batch_get_chi2": (C.c_int, [_vp, _dp, _dp, _dp, _ip]),
 }
 
 _lib = None
@@ -1213,6 +1242,108 @@ class BundleAdjuster:
                                                   _p(cams, _dp), _p(pts, _dp), C.byref(chi), C.byref(sc)),
                   "ba_debug_update")
         return dict(cams=cams, points=pts, chi2=chi.value, scale=sc.value)
+
+
+class TwoViewBatch:
+    """sim3opt_ba_batch*: the loop detector's two-view refinement (BAOptimize, kittiDetector.h:845-954) of a whole
+    batch of loop candidates in one kernel launch -- camera 0 fixed, camera 1 and the points refined, Huber, LM with
+    the detector's settings (lambda_0 = 50, 5 trials, 10 iterations).  Problem k owns the points
+    point_ptr[k]:point_ptr[k+1] of the flat arrays."""
+
+    def __init__(self, **options):
+        self._L = load()
+        self._b = self._L.sim3opt_ba_batch_create()
+        if not self._b:
+            raise MemoryError("sim3opt_ba_batch_create")
+        if options:
+            self.set_options(**options)
+
+    def close(self):
+        if self._b:
+            self._L.sim3opt_ba_batch_destroy(self._b)
+            self._b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != OK:
+            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_ba_batch_last_error(self._b).decode()}")
+
+    def set_options(self, **kw):
+        o = BaBatchOptions()
+        self._L.sim3opt_ba_batch_options_default(C.byref(o))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        self._chk(self._L.sim3opt_ba_batch_set_options(self._b, C.byref(o)), "ba_batch_set_options")
+
+    def set_problems(self, point_ptr, cam0, cam1, points, uv0, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        ptr = _i32(point_ptr).reshape(-1)
+        c0, c1 = _f64(cam0).reshape(-1, 7), _f64(cam1).reshape(-1, 7)
+        pts, a, b = _f64(points).reshape(-1, 3), _f64(uv0).reshape(-1, 2), _f64(uv1).reshape(-1, 2)
+        n = ptr.shape[0] - 1
+        if n >= 1 and not (c0.shape[0] == c1.shape[0] == n):
+            raise ValueError("one camera pair per problem")
+        if n >= 1 and not (pts.shape[0] == a.shape[0] == b.shape[0] and pts.shape[0] >= ptr.max()):
+            raise ValueError("point and observation arrays shorter than point_ptr says")
+        self._chk(self._L.sim3opt_ba_batch_set_problems(self._b, n, _p(ptr, _ip), _p(c0, _dp), _p(c1, _dp),
+                                                        _p(pts, _dp), _p(a, _dp), _p(b, _dp), focal, cx, cy),
+                  "ba_batch_set_problems")
+
+    def dims(self):
+        """(problems, points of all problems)"""
+        a, b = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_ba_batch_dims(self._b, C.byref(a), C.byref(b)), "ba_batch_dims")
+        return a.value, b.value
+
+    def optimize(self):
+        """Problems optimised (one launch); raises when the library reports an error."""
+        n = self._L.sim3opt_ba_batch_optimize(self._b)
+        if n < 0:
+            self._chk(n, "ba_batch_optimize")
+        return n
+
+    def cameras(self):
+        """(cam0 as given, cam1), n x 7 each"""
+        n = self.dims()[0]
+        c0, c1 = np.empty((n, 7)), np.empty((n, 7))
+        self._chk(self._L.sim3opt_ba_batch_get_cameras(self._b, _p(c0, _dp), _p(c1, _dp)), "ba_batch_get_cameras")
+        return c0, c1
+
+    def points(self):
+        out = np.empty((self.dims()[1], 3))
+        self._chk(self._L.sim3opt_ba_batch_get_points(self._b, _p(out, _dp)), "ba_batch_get_points")
+        return out
+
+    def num_iterations(self):
+        return np.array([self._L.sim3opt_ba_batch_num_iterations(self._b, k) for k in range(self.dims()[0])],
+                        dtype=np.int32)
+
+    def stats(self, problem):
+        out = []
+        for i in range(self._L.sim3opt_ba_batch_num_iterations(self._b, int(problem))):
+            st = IterStats()
+            self._chk(self._L.sim3opt_ba_batch_get_stats(self._b, int(problem), i, C.byref(st)), "ba_batch_get_stats")
+            out.append({k: getattr(st, k) for k in ("chi2_before", "chi2_after", "lambda_", "rho", "trials")})
+        return out
+
+    def lambda_init(self):
+        out = np.empty(self.dims()[0])
+        self._chk(self._L.sim3opt_ba_batch_get_lambda_init(self._b, _p(out, _dp)), "ba_batch_get_lambda_init")
+        return out
+
+    def chi2(self):
+        """dict: active_before, active_after (n), edge_chi2 (total x 2), n_outlier_edges (n)"""
+        n, t = self.dims()
+        ab, aa, ec, no = np.empty(n), np.empty(n), np.empty((t, 2)), np.empty(n, dtype=np.int32)
+        self._chk(self._L.sim3opt_ba_batch_get_chi2(self._b, _p(ab, _dp), _p(aa, _dp), _p(ec, _dp), _p(no, _ip)),
+                  "ba_batch_get_chi2")
+        return dict(active_before=ab, active_after=aa, edge_chi2=ec, n_outlier_edges=no)
 
 
 def align_trajectory(query_xyz, train_xyz, with_scale=True):
