@@ -242,6 +242,16 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
     int rc = amg_bind(s, err);
     if (rc) return rc;
   }
+  // the one-system solve's view: the engine's own vectors, scalars and partial sums
+  pv_one = PcgView();
+  pv_one.x = d_x; pv_one.r = d_r; pv_one.z = d_z; pv_one.p = d_p; pv_one.q = d_q; pv_one.s = d_s; pv_one.az = d_az;
+  pv_one.Minv = d_Minv;
+  pv_one.b = d_b;
+  pv_one.sc = d_sc;
+  pv_one.h_sc = h_sc;
+  pv_one.part_a = d_part_a;
+  pv_one.part_b = d_part_b;
+  pv_one.cv = &cv_one;
   // Gram task tables
   GramTables tab;
   int t = 0;
@@ -259,8 +269,8 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
   return SIM3OPT_OK;
 }
 
-int Engine::fetch_scalars(std::string& err) {
-  HIPCHK(hipMemcpyAsync(h_sc, d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, stream));
+int Engine::fetch_scalars(PcgView& V, std::string& err) {
+  HIPCHK(hipMemcpyAsync(V.h_sc, V.sc, sizeof(DevScalars) * V.nsc, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   if (comm.timing && comm.ev_used) return comm.drain(err);
   return SIM3OPT_OK;

@@ -67,7 +67,7 @@ int engine_amg_level_numbers(Engine* e, double lambda, int32_t level, int32_t* r
 int engine_amg_coarsest_inverse(Engine* e, double lambda, double* Ainv, std::string& err);
 int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, const double* r, double* z,
                          std::string& err);
-// diagnostic read-outs of the PCG's operator (engine_pcg.hip, engine_batch.hip)
+// diagnostic read-outs of the PCG's operator (engine_pcg.hip)
 int engine_spmv_spans(Engine* e, int32_t* n_spans, int32_t* wrow, std::string& err);
 int engine_operator_apply(Engine* e, int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,
                           double* pq, double* rp, std::string& err);

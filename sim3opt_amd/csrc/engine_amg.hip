@@ -1,6 +1,6 @@
 // engine_amg.hip -- aggregation-multigrid preconditioner of the PCG: numbers per linearisation / per LM trial, and
 // the cycle -- ONE driver for one system (amg_apply) and for the K = 2 ... 4 systems of a batch of rejected LM trials
-// (Engine::pcg_batch, engine_batch.hip), told apart by the CycleView it is handed
+// (Engine::pcg_batch, engine_pcg.hip), told apart by the CycleView it is handed
 #include "engine_impl.hpp"
 
 #include <cassert>
@@ -512,7 +512,7 @@ int Engine::amg_numbers(double lambda, std::string& err) {
     return SIM3OPT_ERR_STATE;
   }
   DevScalars sd, sh;
-  int rc = diag_begin(lambda, sd, sh, err);
+  int rc = diag_begin(pv_one, &lambda, 1, &sd, &sh, err);
   if (rc) return rc;
   if (amg_stale) rc = amg_setup(err);
   if (rc == SIM3OPT_OK) {
@@ -523,13 +523,7 @@ int Engine::amg_numbers(double lambda, std::string& err) {
       rc = SIM3OPT_ERR_STATE;
     }
   }
-  std::string err2;
-  const int rc_end = diag_end(sd, sh, err2);
-  if (rc == SIM3OPT_OK && rc_end) {
-    err = err2;
-    rc = rc_end;
-  }
-  return rc;
+  return diag_end(pv_one, &sd, &sh, rc, err);
 }
 
 int Engine::amg_level_readout(double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals,

@@ -15,8 +15,6 @@ namespace sim3opt {
 
 #include "col_kernels.hpp"
 
-static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
-
 int Engine::cols_alloc(std::string& err) {
   if (c_g) return SIM3OPT_OK;
   c_vs = pad64(n);
@@ -56,21 +54,16 @@ int Engine::cols_solve(double lambda, int nsys, const double* g, const double* t
     }
     return SIM3OPT_OK;
   }
-  // one column at a time through the one-system PCG: its right-hand side and tolerance for the length of the solve
-  double* const b_saved = d_b;
-  const double tol_saved = opt.pcg_rel_tol;
+  // one column at a time through the one-system view, with its right-hand side and tolerance
   int rc = SIM3OPT_OK;
   for (int s = 0; s < nsys && rc == SIM3OPT_OK; ++s) {  // (nsys = 1 here)
     bool ok = true, broke = false;
     double rr = 0.0;
-    d_b = const_cast<double*>(g) + (size_t)s * c_vs;
-    opt.pcg_rel_tol = tol[s];
-    rc = pcg_attempt(lambda, use_amg ? 2 : (use_chain ? 1 : 0), &iters[s], &rr, &ok, &broke, err);
+    rc = pcg_attempt(lambda, use_amg ? 2 : (use_chain ? 1 : 0), &iters[s], &rr, &ok, &broke, err, 0, nullptr,
+                     g + (size_t)s * c_vs, tol[s]);
     failed[s] = !ok || broke;
     x[s] = d_x;
   }
-  d_b = b_saved;
-  opt.pcg_rel_tol = tol_saved;
   return rc;
 }
 
@@ -133,6 +126,7 @@ int Engine::inverse_columns(double lambda, int32_t nvert, const int32_t* vertice
     }
     as_saved = cv_batch.as;
     cv_batch.as = 0;
+    pv_batch.ms = 0;
   }
   const sim3opt_kernel_times kt_saved = kt;
   int64_t sched_saved[4];
@@ -261,6 +255,7 @@ int Engine::inverse_columns(double lambda, int32_t nvert, const int32_t* vertice
     std::memcpy(h_bsc, sbh, sizeof(sbh));
     for (size_t l = 0; l < cv_batch.lv.size(); ++l) cv_batch.lv[l].ms = ms_saved[l];
     cv_batch.as = as_saved;
+    pv_batch.ms = ms_saved[0];
   }
   kt = kt_saved;
   std::memcpy(sched_stats, sched_saved, sizeof(sched_saved));

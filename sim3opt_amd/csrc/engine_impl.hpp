@@ -1,16 +1,17 @@
 // engine_impl.hpp -- the Engine class shared by the translation units of the device-resident LM:
 //   engine.hip         initialisation, linearisation, chi2, the iteration frame of LM, Gauss-Newton and dogleg, the
 //                      LM trial loop (OptimizationAlgorithmLevenberg::solve; its damping rule: lm_damping.hpp)
-//   engine_pcg.hip     the preconditioned CG (LinearSolverEigen's role on graphs too large to factor), halo exchange
+//   engine_pcg.hip     the preconditioned CG (LinearSolverEigen's role on graphs too large to factor) -- one driver for
+//                      one system and for the systems of a batch: PcgView --, the batch's buffers, an LM trial's solve
+//                      (lm_trial_solve) and the halo exchange
 //   engine_amg.hip     the aggregation-multigrid preconditioner: set-up per linearisation / per trial, the cycle
 //                      (one driver for one system and for the systems of a batch: CycleView)
 //   engine_direct.hip  when the LM factorises exactly (LinearSolverEigen's role on KITTI-00-like graphs) and the
 //                      marginal covariances: policy over two BlockLdl (direct_factor.hpp, direct_factor.hip)
-//   engine_batch.hip   the multigrid PCG loop for several right-hand sides: an LM trial's solve (lm_trial_solve)
 //   engine_algorithms.hip  Gauss-Newton and Powell's dogleg (options.algorithm = 1 / 2)
 //   engine_columns.hip  blocks of (H + lambda I)^-1 by columns of the inverse (options.cov_solver)
 // Every kernel header belongs to ONE translation unit (lm_kernels.hpp -> engine.hip, pcg_kernels.hpp ->
-// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, batch_kernels.hpp -> engine_batch.hip, algo_kernels.hpp -> engine_algorithms.hip, gate_kernels.hpp -> engine_direct.hip, col_kernels.hpp -> engine_columns.hip, direct_ / selinv_ / cov_kernels.hpp -> direct_factor.hip); only
+// engine_pcg.hip, amg_kernels.hpp -> engine_amg.hip, algo_kernels.hpp -> engine_algorithms.hip, gate_kernels.hpp -> engine_direct.hip, col_kernels.hpp -> engine_columns.hip, direct_ / selinv_ / cov_kernels.hpp -> direct_factor.hip); only
 // the SpMV template (spmv_kernel.hpp) is shared.  A kernel another unit needs is reached through a method.
 #pragma once
 // (formerly all of engine.hip) -- device-resident Levenberg-Marquardt on a Sim(3) pose graph, gfx950 (MI355X).
@@ -75,7 +76,7 @@ using sim3::Sim3;
 #define SIM3OPT_F32_CH 8        // blocks per pipeline step of the level-0 FP32 passes (tuning: 16)
 #endif
 constexpr int WG = 256;         // 4 wavefronts of 64
-constexpr int KB = 4;            // right-hand sides the batched PCG solves together (engine_batch.hip)
+constexpr int KB = 4;            // most right-hand sides one PCG solves together (the batch's view)
 constexpr int CHAIN_SEG_MAX = 256;  // rows per segment of the chain preconditioner (LDS of k_chain_apply)
 constexpr int PCG_GRAPH_ITERS = 16;  // PCG iterations per captured hipGraph (even: parity returns)
 constexpr int MAX_GRID = 2048;  // grid cap of the streaming kernels = number of reduction partials
@@ -112,10 +113,15 @@ struct DevScalars {
   double lambda;     // damping of the current solve (read by the captured PCG launches)
   long long n_spmv_work;  // PCG SpMV launches that did their work (launches after `done` return at once)
   double trace;           // sum of the scalar diagonal of H (mean |H_dd|: when is a system damping-dominated?)
+  // (host) after a solve: ||r||_Minv against the first, by the r.z the last executed step saw, i.e. of the residual
+  // BEFORE that step's update; ||r||_2 / ||b||_2 where norms2 left the pair in tmp_pq, tmp_rz; stopped by the cap
+  double rel_res() const { return rz0 > 0 ? std::sqrt(std::fabs(gam_last) / rz0) : 0.0; }
+  double true_rel() const { return tmp_rz > 0 ? std::sqrt(tmp_pq / tmp_rz) : 0.0; }
+  bool capped(double tol) const { return !fail && iter >= max_iter && rel_res() > tol; }
 };
 
 // What the host has seen of one system's r.z at its looks into DevScalars, and what that predicts (host only; it
-// sizes the chunks of the PCG loops and decides nothing else).  A look after `iter` executed steps carries gam_last =
+// sizes the chunks of the PCG loop and decides nothing else).  A look after `iter` executed steps carries gam_last =
 // r.z of the residual BEFORE step `iter`, i.e. after iter - 1 updates; rz0 is the same quantity before step 1.
 struct PcgRate {
   static constexpr int NL = 8, SPAN = 4;
@@ -166,6 +172,7 @@ static hipError_t upload(StagedUploads& staged, hipStream_t stream, T*& dptr, co
   return e;
 }
 
+static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
 static inline int grid_for(int64_t items, int per_block) {
   const int64_t g = (items + per_block - 1) / per_block;
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_GRID));
@@ -296,7 +303,27 @@ class Engine {
   };
   CycleView cv_one;    // aliases the AmgLevel arrays (amg_bind)
   CycleView cv_batch;  // the buffers of batch_alloc
-  // ---- several right-hand sides at once (engine_batch.hip): the rejected trials of an LM iteration ----
+  // ---- which system or systems a PCG solve works on: ONE driver (pcg_run, engine_pcg.hip); nsys = 1 on the engine's
+  // own vectors is the one-system solve ----
+  struct PcgView {
+    int nsys = 1;          // systems of this solve: the first `nsys` of the view's nsc
+    int nsc = 1;           // scalar slots (and vector slots) the view has: 1, or KB
+    bool batch = false;    // the buffers of batch_alloc: the K-system SpMV launch, partials always summed before the step
+    double *x = nullptr, *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *s = nullptr, *az = nullptr;
+    int64_t vs = 0;        // between the systems' vectors
+    double* Minv = nullptr;  // level-0 smoother inverses (chain: its factors), stride ms
+    int64_t ms = 0;
+    const double* b = nullptr;  // right-hand side(s), stride bstride (0: one, shared by the systems)
+    int64_t bstride = 0;
+    double tol[KB] = {0, 0, 0, 0}, lam[KB] = {0, 0, 0, 0};  // per slot: relative tolerance on ||r||_Minv, damping
+    DevScalars *sc = nullptr, *h_sc = nullptr;  // nsc each; h_sc pinned
+    double *part_a = nullptr, *part_b = nullptr;  // the SpMV's partials of w.z and r.z, stride pstride
+    int pstride = 0;
+    CycleView* cv = nullptr;  // the multigrid cycle's view of the same systems
+  };
+  PcgView pv_one;    // d_x ... d_az, d_sc / h_sc, d_b (init)
+  PcgView pv_batch;  // b_x ... b_az, d_bsc / h_bsc (batch_alloc)
+  // ---- several right-hand sides at once (engine_pcg.hip): the rejected trials of an LM iteration ----
   std::vector<void*> batch_owned;
   double *b_x = nullptr, *b_r = nullptr, *b_z = nullptr, *b_p = nullptr, *b_q = nullptr, *b_s = nullptr, *b_az = nullptr;
   double *b_Ainv = nullptr, *b_diag64 = nullptr, *b_part_a = nullptr, *b_part_b = nullptr;
@@ -306,6 +333,8 @@ class Engine {
   int64_t b_slice_blocks = 100000;  // levels with at most this many blocks run one system per grid slice
   int batch_alloc(std::string& err);
   void batch_release();
+  // per system s < nsetup of the batch's view: damped diagonal blocks, smoother inverses, dense coarsest inverse
+  void batch_prepare(int nsetup);
   // per-system right-hand sides of a batch (the columns of the inverse): g + s * stride, tolerance tol[s]; one damping
   // for all, so one set-up serves them -- run by the first batch of a call only (setup)
   struct BatchRhs { const double* g; int64_t stride; const double* tol; bool setup; };
@@ -404,9 +433,10 @@ class Engine {
 
   int init(const HostGraph& g, const Structure& s, std::string& err);
 
-  int fetch_scalars(std::string& err);
+  int fetch_scalars(std::string& err) { return fetch_scalars(pv_one, err); }  // the LM's own
+  int fetch_scalars(PcgView& V, std::string& err);  // a look with nothing queued behind it: V.h_sc is fresh
 
-  // ---- the PCG loops' schedule (pcg_attempt, pcg_batch) ----
+  // ---- the PCG loop's schedule (pcg_run) ----
   // The stopping decision is the device's; the host only chooses how many iterations to enqueue before it looks
   // again.  From two looks it has the reduction of r.z per iteration and from that the iterations still needed
   // (PcgRate); chunks are sized by it, and while more than one chunk is predicted the look at chunk k is an
@@ -605,7 +635,9 @@ class Engine {
   void spmv_raw(double lambda, const double* v, double* q, const double* rvec, DevScalars* scp,
                 hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
-  int spmv_launch(double lambda, const double* z, const double* rv, std::string& err);
+  // the PCG's SpMV on a view's first `live` systems: V.q = (H + lambda_s I) v, partials of v.q and, with rvec, of
+  // rvec.v in V.part_a / V.part_b (timed: one system with options.time_kernels takes an event pair from the pool)
+  int pcg_spmv(const PcgView& V, int live, const double* v, const double* rvec, bool timed, std::string& err);
 
   // Preconditioned CG on (H + lambda I) x = b in the single-reduction form (k_pcg_step); the
   // result stays in d_x.  Two launches and one reduction point per iteration; the host only polls
@@ -619,16 +651,27 @@ class Engine {
   // reduction reached so far predicts the total; if that exceeds the budget -- or the budget runs out --
   // *abandoned is set and the caller solves again with the hierarchy
   int pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res, bool* ok,
-                  bool* chain_broke, std::string& err, int probe_budget = 0, bool* abandoned = nullptr);
+                  bool* chain_broke, std::string& err, int probe_budget = 0, bool* abandoned = nullptr,
+                  const double* rhs = nullptr, double rel_tol = 0.0);
+  int pcg_setup(PcgView& V, int prec, int nsetup, std::string& err);
+  // The solve itself, on the systems of V (V.lam, V.tol, V.b set by the caller): scalars reset, set-up of
+  // preconditioner `prec` (a batch: of its first nsetup systems), first residual, the look at the set-up's pivots
+  // (*setup_broke: a non-positive one, nothing was iterated), the loop, with check_true the 2-norm of every residual
+  // against its right-hand side's (the pair in tmp_pq, tmp_rz), and V.h_sc holds the systems' last state.  What only one system does -- graph replay, several
+  // ranks, the probe, timed launches, partials summed inside the step -- is keyed on the view.
+  int pcg_run(PcgView& V, int prec, int nsetup, bool check_true, bool* setup_broke, std::string& err,
+              int probe_budget = 0, bool* abandoned = nullptr);
 
   // ---- diagnostic read-outs of the preconditioners (tests/test_gpu_preconditioners.py; one GPU only) ----
   // They run the set-up a PCG solve runs and then put back what it wrote of the solver's state: the DevScalars on
   // both sides.  Everything else they touch -- the level numbers for a lambda, d_Minv, the PCG vectors -- is
-  // rewritten by every pcg_attempt before it is read, and amg_setup is a function of the linearisation alone, so a
+  // rewritten by every solve before it is read, and amg_setup is a function of the linearisation alone, so a
   // solve or optimize() that follows is bit for bit the one without the read-out.
-  int diag_begin(double lambda, DevScalars& saved_d, DevScalars& saved_h, std::string& err);
-  int diag_end(const DevScalars& saved_d, const DevScalars& saved_h, std::string& err);
-  // amg_setup if stale, amg_prepare(lambda) -- as pcg_attempt -- and, unlike it, a failed pivot is SIM3OPT_ERR_STATE
+  // (a view's V.nsc scalars: the first nrhs not done, at lambda[k], the rest finished)
+  int diag_begin(PcgView& V, const double* lambda, int nrhs, DevScalars* saved_d, DevScalars* saved_h, std::string& err);
+  // (rc: what happened in between; returned unless it was fine and the restoring failed)
+  int diag_end(PcgView& V, const DevScalars* saved_d, const DevScalars* saved_h, int rc, std::string& err);
+  // amg_setup if stale, amg_prepare(lambda) -- as a solve -- and, unlike it, a failed pivot is SIM3OPT_ERR_STATE
   int amg_numbers(double lambda, std::string& err);                                      // engine_amg.hip
   int amg_level_readout(double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals, float* vals32,
                         double* W, double* diagH, double* Minv, double* P, std::string& err);  // engine_amg.hip
@@ -638,16 +681,13 @@ class Engine {
   // ---- ... and of the PCG's own operator (tests/test_gpu_pcg_operator.py) ----
   // the span table as the device holds it (a copy: nothing is written)
   int spmv_spans(int32_t* n_spans, int32_t* wrow, std::string& err);                      // engine_pcg.hip
-  // q = (H + lambda I) p with p.q and rvec.p: the SpMV launch of a PCG iteration and the sum of its partials; one
-  // system through spmv_raw (d_sc), several through the batch's launch (operator_apply_batch: d_bsc, batch buffers).
-  // The partials are added by k_final_sum2 / k_final_sum2_k: the FUNCTION a solve adds them with (sum_partials on the
-  // same arrays, count and block size), not the launch -- up to MAX_GRID partials k_pcg_step adds them in-step.  With
-  // rvec the K-system kernel takes a path pcg_batch never takes (its r.z comes from the cycle): diagnostic only.
-  // Vectors they stage in -- d_z, d_r, d_q, b_az, b_r, b_q -- are rewritten by every solve before it reads them.
+  // q = (H + lambda I) p with p.q and rvec.p: the SpMV launch of a PCG iteration (pcg_spmv) and the sum of its partials,
+  // on the one-system view or, nrhs > 1, on the batch's.  The partials are added by k_final_sum2: the FUNCTION a solve
+  // adds them with (sum_partials on the same arrays, count and block size), not always the launch -- up to MAX_GRID
+  // partials the one-system k_pcg_step adds them in-step.  With rvec the K-system launch takes a path a batched solve
+  // never takes (its r.z comes from the cycle): diagnostic only.  The vectors staged in are rewritten by every solve.
   int operator_apply(int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q, double* pq,
                      double* rp, std::string& err);                                      // engine_pcg.hip
-  int operator_apply_batch(int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,
-                           double* pq, double* rp, std::string& err);                    // engine_batch.hip
 
   // ---- the iteration frame of LM, Gauss-Newton and dogleg (engine.hip) ----
   int iter_begin(sim3opt_iter_stats& T, double& chi, std::string& err);  // stamp 0, chi2 (cached or not), linearise

@@ -1,5 +1,8 @@
 // engine_pcg.hip -- preconditioned CG on (H + lambda I) x = b (LinearSolverEigen::solve, kitti_surf.cpp:553-554, on graphs
-// too large to factor) and the halo exchange of its row-partitioned form
+// too large to factor) and the halo exchange of its row-partitioned form.  ONE driver, Engine::pcg_run, handed the
+// PcgView of the systems it works on: the engine's own vectors and scalars (pcg_attempt: one system, K = 1 of every
+// kernel) or the buffers of batch_alloc (pcg_batch: up to KB systems in lock-step, per system the same operations
+// in the same order, so its solutions are bit for bit those of sequential solves).
 #include "engine_impl.hpp"
 
 namespace sim3opt {
@@ -18,7 +21,8 @@ void Engine::jacobi(int lo, int hi, const int32_t* rowptr, double* vals, double 
 void Engine::norms2(const double* r, const double* b, double* part_a, double* part_b, double* out2) {
   const int gn = grid_for(7 * (int64_t)(r1 - r0), WG);
   hipLaunchKernelGGL(k_norms2, dim3(gn), dim3(WG), 0, stream, 7 * r0, 7 * r1, r, b, part_a, part_b);
-  hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, part_a, part_b, gn, out2);
+  hipLaunchKernelGGL(k_final_sum2<1>, dim3(1), dim3(WG), 0, stream, (const double*)part_a, (const double*)part_b, gn, 0,
+                     out2, 0);
 }
 
 // Partition of level l and its exchange plan (see LevelPart).
@@ -121,19 +125,30 @@ hipLaunchKernelGGL((k_spmv_span<CH, NTV, 0>), dim3(g), dim3(WG), 0, stream, nb, 
 #undef SPAN_CASE
 }
 
-int Engine::spmv_launch(double lambda, const double* z, const double* rv, std::string& err) {  // the PCG's SpMV: w = A z, w.z (and r.z)
-  hipEvent_t a = nullptr, b = nullptr;
-  if (opt.time_kernels) {
-    int rc = pool_get(a, b, err);
-    if (rc) return rc;
+// the PCG's SpMV on the first `live` systems of a view: w = A v, the partials of w.v (and rvec.v)
+int Engine::pcg_spmv(const PcgView& V, int live, const double* v, const double* rvec, bool timed, std::string& err) {
+  if (!V.batch) {
+    hipEvent_t a = nullptr, b = nullptr;
+    if (timed && opt.time_kernels) {
+      int rc = pool_get(a, b, err);
+      if (rc) return rc;
+    }
+    spmv_raw(V.lam[0], v, V.q, rvec, V.sc, a, b);
+    return SIM3OPT_OK;
   }
-  spmv_raw(lambda, z, d_q, rv, d_sc, a, b);
+  const BatchStrides bs{V.vs, V.ms, 0, 0, V.pstride};  // (the dampings travel in V.sc)
+  BATCH_DISPATCH(live, hipLaunchKernelGGL((k_spmv_span<8, true, 0, double, KS, false>), dim3(span_grid), dim3(WG), 0, stream,
+                     nb, d_wrow, d_rowptr, d_colidx, (const double*)d_vals, v, V.q, 0.0, V.part_a, rvec, V.part_b, V.sc,
+                     (const double*)nullptr, 1, (const int32_t*)nullptr, 1.0, bs, (const float*)nullptr));
   return SIM3OPT_OK;
 }
 
-// Preconditioned CG on (H + lambda I) x = b in the single-reduction form (k_pcg_step); the
-// result stays in d_x.  Two launches and one reduction point per iteration; the host only looks at
-// one small struct between chunks of iterations (see `chunk` in pcg_attempt).
+// k_final_sum2 leaves [w.z, r.z] of system s in sc[s].tmp_pq, tmp_rz: out2 = &sc->tmp_pq, this many doubles apart
+constexpr int SC_DOUBLES = (int)(sizeof(DevScalars) / sizeof(double));
+static_assert(sizeof(DevScalars) % sizeof(double) == 0 &&
+                  offsetof(DevScalars, tmp_rz) == offsetof(DevScalars, tmp_pq) + sizeof(double),
+              "DevScalars: tmp_pq and tmp_rz adjacent, the struct a whole number of doubles");
+
 int Engine::agree_on_fail(std::string& err) {  // multi-GPU: fail on any rank = fail on all
   hipLaunchKernelGGL(k_fail_to_double, dim3(1), dim3(1), 0, stream, d_sc);
   int rc = comm.allreduce(&d_sc->tmp_pq, 1, 1, stream, err);
@@ -222,23 +237,125 @@ int Engine::pcg(double lambda, int32_t* iters, double* rel_res, bool* ok, std::s
 // probe_budget > 0 (block-Jacobi tried first on a damping-dominated system): after 8 iterations the
 // reduction reached so far predicts the total; if that exceeds the budget -- or the budget runs out --
 // *abandoned is set and the caller solves again with the hierarchy
-int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res, bool* ok,
-                bool* chain_broke, std::string& err, int probe_budget, bool* abandoned) {
+// rhs, rel_tol: another right-hand side and tolerance than d_b and options.pcg_rel_tol (the columns of the inverse)
+int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res, bool* ok, bool* chain_broke,
+                        std::string& err, int probe_budget, bool* abandoned, const double* rhs, double rel_tol) {
+  PcgView& V = pv_one;
+  V.nsys = 1;
+  V.lam[0] = lambda;
+  V.tol[0] = rhs ? rel_tol : opt.pcg_rel_tol;
+  V.b = rhs ? rhs : d_b;
+  const DevScalars& h = *h_sc;
+  bool broke = false;
+  int rc = pcg_run(V, prec, 1, prec == 2, &broke, err, probe_budget, abandoned);
+  if (rc) return rc;
+  if (broke) {
+    if (opt.verbose)
+      std::fprintf(stderr, "sim3opt: %s set-up met a non-positive pivot (lambda %.3g): block-Jacobi for this solve\n",
+                   prec == 2 ? "multigrid" : "chain", lambda);
+    if (chain_broke) *chain_broke = true;
+    *ok = false;
+    *iters = 0;
+    *rel_res = 0.0;
+    return SIM3OPT_OK;
+  }
+  *iters = h.iter;
+  *rel_res = h.rel_res();
+  *ok = !h.fail;
+  if (abandoned && *abandoned) return SIM3OPT_OK;  // (the probe ran out of budget, or is predicted to)
+  last_true_rel = prec == 2 && !h.fail ? h.true_rel() : 0.0;
+  if (prec == 2 && !h.fail && opt.verbose)
+    std::fprintf(stderr, "sim3opt: multigrid PCG: %d iterations, ||r||_Minv ratio %.2e, ||r||_2 / ||b||_2 %.2e\n", h.iter,
+                 *rel_res, last_true_rel);
+  // stopped by the cap, not by the tolerance: an inexact step (sim3opt_iter_stats::pcg_capped); LM's gain
+  // ratio decides what becomes of it -- the exact solver it stands in for has no such state
+  last_capped = h.capped(V.tol[0]);
+  return SIM3OPT_OK;
+}
+
+// Solves (H + lams[s] I) x_s = b, s < nsys <= KB, together; x_s is left in b_x + s * b_vs.  *usable = false:
+// some system broke down or failed the true-residual check -- the caller then solves the trials one by one
+// (the sequential path has the fall-backs: plain cycle instead of the over-corrected one, block-Jacobi).
+// cols (columns of the inverse, engine_columns.hip): system s solves for ITS right-hand side cols->g + s * stride to
+// its own tolerance, all at lams[0] -- so ONE set-up (smoother inverses, FP32 diagonals, dense coarsest inverse: slot
+// 0, the caller has set the per-system strides of the batch's views to 0) serves them all, and the batches of a call
+// that follow the first (cols->setup false) run none.  The 2-norm check is the caller's, on the true residual.
+int Engine::pcg_batch(const double* lams, int nsys, int32_t* iters, double* rel_res, bool* capped, bool* usable,
+                      std::string& err, const BatchRhs* cols) {
+  *usable = false;
+  int rc = batch_alloc(err);
+  if (rc) return rc;
+  PcgView& V = pv_batch;
+  V.nsys = nsys;
+  for (int s = 0; s < KB; ++s) {
+    V.tol[s] = cols ? cols->tol[std::min(s, nsys - 1)] : opt.pcg_rel_tol;
+    V.lam[s] = lams[std::min(s, nsys - 1)];
+  }
+  V.b = cols ? cols->g : d_b;
+  V.bstride = cols ? cols->stride : 0;
+  bool broke = false;
+  rc = pcg_run(V, 2, cols ? (cols->setup ? 1 : 0) : nsys, !cols, &broke, err);
+  if (rc || broke) return rc;  // (a non-positive pivot of some set-up: not usable)
+  bool good = true;
+  for (int s = 0; s < nsys; ++s) {
+    const DevScalars& h = h_bsc[s];
+    const double true_rel = cols ? 0.0 : h.true_rel();
+    if (h.fail || true_rel > 1e-3) good = false;
+    iters[s] = h.iter;
+    rel_res[s] = h.rel_res();
+    capped[s] = h.capped(V.tol[s]);
+    if (opt.verbose)
+      std::fprintf(stderr, "sim3opt: batched multigrid PCG, system %d of %d: lambda %.6g, %d iterations, ||r||_Minv ratio %.2e, "
+                   "||r||_2 / ||b||_2 %.2e\n", s, nsys, lams[s], h.iter, rel_res[s], true_rel);
+  }
+  kt.n_batched_solves += nsys;
+  kt.n_batches += 1;
+  *usable = good;
+  return SIM3OPT_OK;
+}
+
+// the numbers of preconditioner `prec` at the dampings V.lam (a batch: for its first nsetup systems)
+int Engine::pcg_setup(PcgView& V, int prec, int nsetup, std::string& err) {
+  const int nloc = r1 - r0, nseg = (nloc + chain_seg - 1) / chain_seg;
+  if (prec == 2) {
+    if (amg_stale) {
+      int rc = amg_setup(err);
+      if (rc) return rc;
+    }
+    if (V.batch) batch_prepare(nsetup);
+    else amg_prepare(V.lam[0]);
+  } else if (prec == 1) {
+    hipLaunchKernelGGL(k_chain_factor, dim3(std::max(1, (nseg + 63) / 64)), dim3(64), 0, stream, r0, r1, chain_seg,
+                       d_rowptr, d_vals, d_sub_first, d_sub_cnt, V.lam[0], V.Minv, d_Gm, V.sc);
+  } else {
+    hipLaunchKernelGGL(k_jacobi, dim3(std::max(1, (nloc + WG - 1) / WG)), dim3(WG), 0, stream, r0, r1, d_rowptr,
+                       d_vals, V.lam[0], V.Minv, V.sc, 1.0, (const double*)nullptr, (const double*)nullptr);
+  }
+  return SIM3OPT_OK;
+}
+
+// The solve (see engine_impl.hpp).  prec: 0 block-Jacobi, 1 chain segments, 2 aggregation multigrid.
+int Engine::pcg_run(PcgView& V, int prec, int nsetup, bool check_true, bool* setup_broke, std::string& err,
+                    int probe_budget, bool* abandoned) {
   const bool use_chain = prec == 1, use_mg = prec == 2;
   const bool probe = probe_budget > 0;
-  double* const zin = use_mg ? d_az : d_z;  // preconditioned residual the PCG consumes
+  const int nsys = V.nsys;
+  DevScalars* const h0 = V.h_sc;  // (system 0: the one system, or the batch's first)
+  double* const zin = use_mg ? V.az : V.z;  // preconditioned residual the PCG consumes
   // r.z: from the SpMV's own pass over r -- or, with the multiplicative multigrid cycle, from the
   // cycle's last kernel, which holds r and writes z (the SpMV then skips its load of r)
-  const double* const spmv_r = use_mg && !amg_additive ? nullptr : d_r;
+  const double* const spmv_r = use_mg && !amg_additive ? nullptr : V.r;
   const int nloc = r1 - r0;
-  const int gj = std::max(1, (nloc + WG - 1) / WG);
   const int gv = grid_for((nloc + 8) / 9, 4);  // 36 block rows per workgroup pass
   const int gs = spmv_grid();
   const bool multi = comm.active();
   // [w.z, r.z] summed once by k_final_sum2 (multi-GPU: then all-reduced) instead of by every
-  // workgroup of the PCG step when the SpMV leaves more partials than a workgroup sums for free
-  const bool pre_sum = multi || gs > MAX_GRID;
-  const double* scal = pre_sum ? &d_sc->tmp_pq : nullptr;
+  // workgroup of the PCG step when the SpMV leaves more partials than a workgroup sums for free; a batch always
+  const bool pre_sum = V.batch || multi || gs > MAX_GRID;
+  const double* const part_d = pre_sum ? nullptr : V.part_a;
+  const double* const part_g = pre_sum ? nullptr : V.part_b;
+  const BatchStrides bs{V.vs, V.ms, 0, 0, V.pstride};
+  *setup_broke = false;
   // automatic cap: small systems may need ~n iterations for an (almost) exact step like the
   // reference's Cholesky (chains are ill-conditioned); large ones get a truncated-Newton budget
   // (round 3: a cap of 4000 for the multigrid path was tried for the one system in twenty of the
@@ -249,63 +366,63 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
   if (probe) max_it = std::min(max_it, probe_budget);
   const int nseg = (nloc + chain_seg - 1) / chain_seg;
   const int gc = grid_for(nseg, 4);  // chain apply: one wavefront per segment
-  const double* Minv_arg = use_chain ? nullptr : d_Minv;
+  const double* Minv_arg = use_chain ? nullptr : V.Minv;
   int rc = SIM3OPT_OK;
-  h_sc->rz[0] = h_sc->rz[1] = h_sc->alpha[0] = h_sc->alpha[1] = h_sc->rz0 = 0.0;
-  h_sc->iter = 0;
-  h_sc->max_iter = max_it;
-  h_sc->done = h_sc->stop = h_sc->fail = 0;
-  h_sc->tol2 = opt.pcg_rel_tol * opt.pcg_rel_tol;
-  h_sc->lambda = lambda;
-  // chi2 / scale / maxdiag live in the same struct: only the PCG fields are reset
-  HIPCHK(hipMemcpyAsync(&d_sc->rz[0], &h_sc->rz[0], offsetof(DevScalars, chi2), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(&d_sc->iter, &h_sc->iter, offsetof(DevScalars, tmp_pq) - offsetof(DevScalars, iter),
-                        hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(&d_sc->lambda, &h_sc->lambda, sizeof(double), hipMemcpyHostToDevice, stream));
-  if (use_mg) {
-    if (amg_stale) {
-      rc = amg_setup(err);
-      if (rc) return rc;
-    }
-    amg_prepare(lambda);
-  } else if (use_chain) {
-    hipLaunchKernelGGL(k_chain_factor, dim3(std::max(1, (nseg + 63) / 64)), dim3(64), 0, stream,
-                       r0, r1, chain_seg, d_rowptr, d_vals, d_sub_first, d_sub_cnt, lambda,
-                       d_Minv, d_Gm, d_sc);
-  } else {
-    hipLaunchKernelGGL(k_jacobi, dim3(gj), dim3(WG), 0, stream, r0, r1, d_rowptr, d_vals, lambda,
-                       d_Minv, d_sc, 1.0, (const double*)nullptr, (const double*)nullptr);
+  for (int s = 0; s < V.nsc; ++s) {
+    DevScalars& h = V.h_sc[s];
+    if (V.batch) std::memset(&h, 0, sizeof(DevScalars));
+    h.rz[0] = h.rz[1] = h.alpha[0] = h.alpha[1] = h.rz0 = 0.0;
+    h.iter = 0;
+    h.max_iter = max_it;
+    h.done = s < nsys ? 0 : 1;  // (an unused slot: finished from the start, its vectors stay zero)
+    h.stop = h.fail = 0;
+    h.tol2 = V.tol[s] * V.tol[s];
+    h.lambda = V.lam[s];
   }
-  hipLaunchKernelGGL(k_pcg_init, dim3(gv), dim3(WG), 0, stream, r0, r1, d_b, Minv_arg, d_x, d_r,
-                     d_z, d_p, d_s);
+  if (V.batch) {
+    HIPCHK(hipMemcpyAsync(V.sc, V.h_sc, sizeof(DevScalars) * V.nsc, hipMemcpyHostToDevice, stream));
+  } else {
+    // chi2 / scale / maxdiag live in the same struct: only the PCG fields are reset
+    HIPCHK(hipMemcpyAsync(&V.sc->rz[0], &h0->rz[0], offsetof(DevScalars, chi2), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(&V.sc->iter, &h0->iter, offsetof(DevScalars, tmp_pq) - offsetof(DevScalars, iter),
+                          hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(&V.sc->lambda, &h0->lambda, sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  rc = pcg_setup(V, prec, nsetup, err);
+  if (rc) return rc;
+  if (V.cv) V.cv->nsys = nsys;
+  if (V.bstride)
+    BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_pcg_init<KS, true>), dim3(gv), dim3(WG), 0, stream, r0, r1, V.b, Minv_arg,
+                       V.x, V.r, V.z, V.p, V.s, bs, V.bstride));
+  else
+    BATCH_DISPATCH(nsys, hipLaunchKernelGGL((k_pcg_init<KS, false>), dim3(gv), dim3(WG), 0, stream, r0, r1, V.b, Minv_arg,
+                       V.x, V.r, V.z, V.p, V.s, bs, (int64_t)0));
+  // z = M^-1 r beyond the block-Jacobi part the step has written; sc: launches after `done` return at once
+  auto apply_prec = [&](const DevScalars* sc) -> int {
+    if (use_chain)
+      hipLaunchKernelGGL(k_chain_apply, dim3(gc), dim3(WG), 0, stream, r0, r1, chain_seg, V.Minv, d_Gm, V.r, V.z, sc);
+    if (use_mg && V.batch) amg_cycle(*V.cv, 0, V.z, V.az);
+    else if (use_mg) return amg_apply(err);  // (one system: several ranks' exchanges are in there)
+    return SIM3OPT_OK;
+  };
   if (use_chain || use_mg) {
     if (multi) {
       rc = agree_on_fail(err);
       if (rc) return rc;
     }
-    rc = fetch_scalars(err);  // did the factorisation succeed?
+    rc = fetch_scalars(V, err);  // did the factorisation succeed?
     if (rc) return rc;
-    if (h_sc->fail) {
-      if (opt.verbose)
-        std::fprintf(stderr, "sim3opt: %s set-up met a non-positive pivot (lambda %.3g): block-Jacobi for this solve\n",
-                     use_mg ? "multigrid" : "chain", lambda);
-      if (chain_broke) *chain_broke = true;
-      *ok = false;
-      *iters = 0;
-      *rel_res = 0.0;
-      return SIM3OPT_OK;
-    }
-    if (use_chain)
-      hipLaunchKernelGGL(k_chain_apply, dim3(gc), dim3(WG), 0, stream, r0, r1, chain_seg, d_Minv,
-                         d_Gm, d_r, d_z, (const DevScalars*)nullptr);
-    else {
-      rc = amg_apply(err);
-      if (rc) return rc;
-    }
+    for (int s = 0; s < nsys; ++s)
+      if (V.h_sc[s].fail) {
+        *setup_broke = true;
+        return SIM3OPT_OK;
+      }
+    rc = apply_prec(nullptr);
+    if (rc) return rc;
   }
   HIPCHK(hipGetLastError());
   if (multi && !use_mg) {  // (the multigrid cycle gathers its own operands)
-    rc = exchange_rows(d_z, err);
+    rc = exchange_rows(V.z, err);
     if (rc) return rc;
   }
   // Iterations per look into DevScalars.  Without a rate -- the first chunk of a solve, pcg_check_every = 1, the
@@ -319,11 +436,28 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
   const bool predict = !multi && !probe && pce > 1;
   const int cap = use_mg ? (pce >= 4 ? std::min(pce, std::max(4, sched_cap_mg)) : pce) : pce;
   int it = 0, par = 0;
-  // Launch-bound regime (small graphs: two ~3 us kernels per iteration): replay a captured
+  int live = V.batch ? nsys : 1;  // systems the launches carry: [0, live)
+  // the launches of one iteration up to the step, the one that decides (launch number itn; < 0: captured)
+  auto iterate = [&](int parity, int itn, bool timed) -> int {
+    int rc2 = pcg_spmv(V, live, zin, spmv_r, timed, err);
+    if (rc2) return rc2;
+    if (pre_sum)  // [w.z, r.z] -> tmp_pq, tmp_rz (adjacent) of every system
+      BATCH_DISPATCH(live, hipLaunchKernelGGL((k_final_sum2<KS>), dim3(1), dim3(WG), 0, stream, (const double*)V.part_a,
+                         (const double*)V.part_b, gs, V.pstride, &V.sc->tmp_pq, SC_DOUBLES));
+    if (multi) {  // one 2-double all-reduce
+      rc2 = comm.allreduce(&V.sc->tmp_pq, 2, 0, stream, err);
+      if (rc2) return rc2;
+    }
+    BATCH_DISPATCH(live, hipLaunchKernelGGL((k_pcg_step<KS>), dim3(gv), dim3(WG), 0, stream, r0, r1, parity, itn, part_d,
+                       part_g, gs, V.pstride, Minv_arg, (const double*)zin, V.z, (const double*)V.q, V.p, V.s, V.x, V.r,
+                       V.sc, bs));
+    return SIM3OPT_OK;
+  };
+  // Launch-bound regime (small graphs: two ~3 us kernels per iteration; one system): replay a captured
   // hipGraph of PCG_GRAPH_ITERS iterations instead of enqueueing them one by one.  The first
   // iteration stays eager (it carries it == 0); captured steps read the counter, the damping and
   // the stopping state from DevScalars, so one instantiated graph serves every solve.
-  const bool graphed = !multi && !opt.time_kernels && opt.pcg_graph && max_it > PCG_GRAPH_ITERS && !probe;
+  const bool graphed = !V.batch && !multi && !opt.time_kernels && opt.pcg_graph && max_it > PCG_GRAPH_ITERS && !probe;
   if (graphed && (!pcg_graph || pcg_graph_kind != prec)) {
     if (pcg_graph) { (void)hipGraphExecDestroy(pcg_graph); pcg_graph = nullptr; }
     // a multigrid iteration is ~20 launches: shorter graphs waste fewer no-op launches after
@@ -331,18 +465,9 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
     graph_iters = use_mg ? 4 : PCG_GRAPH_ITERS;
     hipGraph_t gr = nullptr;
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    for (int c = 0; c < graph_iters; ++c) {
-      spmv_raw(lambda, zin, d_q, spmv_r, d_sc);
-      if (pre_sum)
-        hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gs,
-                           &d_sc->tmp_pq);
-      hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(WG), 0, stream, r0, r1, (1 + c) & 1, -1,
-                         scal, d_part_a, d_part_b, gs, Minv_arg,
-                         (const double*)zin, d_z, d_q, d_p, d_s, d_x, d_r, d_sc);
-      if (use_chain)
-        hipLaunchKernelGGL(k_chain_apply, dim3(gc), dim3(WG), 0, stream, r0, r1, chain_seg,
-                           d_Minv, d_Gm, d_r, d_z, (const DevScalars*)d_sc);
-      if (use_mg) (void)amg_apply(err);  // single GPU here: no collectives inside
+    for (int c = 0; c < graph_iters; ++c) {  // (single GPU here: no collectives inside)
+      (void)iterate((1 + c) & 1, -1, false);
+      (void)apply_prec(V.sc);
     }
     {  // (a failed launch inside the region must not leave the stream capturing)
       const hipError_t le = hipGetLastError();
@@ -365,16 +490,9 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
   // (Several ranks: the cycle's collectives and the exchange of z stay where they were.)
   const bool defer_prec = !multi && (use_chain || use_mg);
   bool prec_pending = false;
-  auto apply_prec = [&]() -> int {
-    if (use_chain)
-      hipLaunchKernelGGL(k_chain_apply, dim3(gc), dim3(WG), 0, stream, r0, r1, chain_seg,
-                         d_Minv, d_Gm, d_r, d_z, (const DevScalars*)d_sc);
-    if (use_mg) return amg_apply(err);
-    return SIM3OPT_OK;
-  };
   auto enqueue = [&](int count) -> int {
     if (prec_pending) {
-      int rc2 = apply_prec();
+      int rc2 = apply_prec(V.sc);
       if (rc2) return rc2;
       prec_pending = false;
     }
@@ -388,26 +506,16 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
       return SIM3OPT_OK;
     }
     for (int c = 0; c < count; ++c) {
-      int rc2 = spmv_launch(lambda, zin, spmv_r, err);
+      int rc2 = iterate(par, it, true);
       if (rc2) return rc2;
-      if (pre_sum)  // [w.z, r.z] -> tmp_pq, tmp_rz (adjacent)
-        hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gs,
-                           &d_sc->tmp_pq);
-      if (multi) {  // one 2-double all-reduce
-        rc2 = comm.allreduce(&d_sc->tmp_pq, 2, 0, stream, err);
-        if (rc2) return rc2;
-      }
-      hipLaunchKernelGGL(k_pcg_step, dim3(gv), dim3(WG), 0, stream, r0, r1, par, it, scal,
-                         d_part_a, d_part_b, gs, Minv_arg, (const double*)zin, d_z, d_q, d_p, d_s,
-                         d_x, d_r, d_sc);
       if (defer_prec && c + 1 == count) {
         prec_pending = true;
       } else {
-        rc2 = apply_prec();
+        rc2 = apply_prec(V.sc);
         if (rc2) return rc2;
       }
       if (multi && !use_mg) {  // the next SpMV gathers z from the neighbouring ranks
-        rc2 = exchange_rows(d_z, err);
+        rc2 = exchange_rows(V.z, err);
         if (rc2) return rc2;
       }
       par ^= 1;
@@ -417,27 +525,33 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
     HIPCHK(hipGetLastError());
     return SIM3OPT_OK;
   };
-  // a look with nothing queued behind it: h_sc is fresh and every recorded event complete
+  // the timed SpMV launches of the one-system solve (time_kernels: the event pool) are counted against the work
+  // counter of the looks
+  auto note_work = [&]() {
+    if (!V.batch && !opt.time_kernels) spmv_work_seen = h0->n_spmv_work;
+  };
+  // a look with nothing queued behind it: the scalars are fresh and every recorded event complete
   auto poll_sync = [&]() -> int {
-    int rc2 = fetch_scalars(err);
+    int rc2 = fetch_scalars(V, err);
     if (rc2) return rc2;
     sched_stats[2] += 1;
-    if (opt.time_kernels) return pool_drain(err);
-    spmv_work_seen = h_sc->n_spmv_work;
+    if (!V.batch && opt.time_kernels) return pool_drain(err);
+    note_work();
     return SIM3OPT_OK;
   };
   // The captured graph starts at par == 1.  An eager chunk of several iterations on that path is cut by one where
   // it would end at par == 0, so that whole graphs can be replayed again should the prediction grow (single
   // iterations next to the end are left alone: two of them restore the parity).
   auto keep_parity = [&](int n) { return graphed && it > 0 && n > 1 && n < graph_iters && ((par ^ (n & 1)) == 0) ? n - 1 : n; };
-  PcgRate rate;
-  int seen = 0;  // iterations that were enqueued before the look h_sc holds (seen < it: chunks still in the queue)
+  auto finished = [](const DevScalars& h) { return h.done || h.stop || h.fail; };
+  PcgRate rate[KB];
+  int seen = 0;  // iterations that were enqueued before the look V.h_sc holds (seen < it: chunks still in the queue)
   const int64_t enq0 = sched_stats[0];
   // The set-up's fetch above has just read the scalars and no step has run since: with a prediction to make up
   // for it the loop's first look is left out (it would only drain the queue the first cycle sits in).
   bool have = predict && (use_chain || use_mg);
-  long long work0 = have ? h_sc->n_spmv_work : -1;
-  if (have && !opt.time_kernels) spmv_work_seen = h_sc->n_spmv_work;
+  long long work0 = have ? h0->n_spmv_work : -1;
+  if (have) note_work();
   for (;;) {
     if (!have) {
       rc = poll_sync();
@@ -445,27 +559,48 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
       seen = it;
     }
     have = false;
-    if (work0 < 0) work0 = h_sc->n_spmv_work;
+    if (work0 < 0) work0 = h0->n_spmv_work;
+    // systems still iterating: [0, live).  The dampings of a batch ascend with the trial, so the systems finish from
+    // the tail as a rule; the launches that follow carry the first `live` systems only (per system the same
+    // operations whatever K is: the results do not depend on when the others finished)
+    live = 0;
+    for (int s = 0; s < nsys; ++s)
+      if (!finished(V.h_sc[s])) live = s + 1;
     if (opt.verbose >= 3)
-      std::fprintf(stderr, "  pcg look: enqueued %d, seen %d, iter %d, r.z %.6e of %.6e (tol2 %.3e), done %d\n", it, seen,
-                   h_sc->iter, std::fabs(h_sc->gam_last), h_sc->rz0, h_sc->tol2, h_sc->done);
-    if (h_sc->done || h_sc->stop || h_sc->fail || seen >= max_it) break;
-    if (probe && it >= 8 && h_sc->rz0 > 0.0) {
+      for (int s = 0; s < nsys; ++s) {
+        const DevScalars& h = V.h_sc[s];
+        char who[40] = "  pcg look:";
+        if (V.batch) std::snprintf(who, sizeof(who), "  batch look: system %d,", s);
+        std::fprintf(stderr, "%s enqueued %d, seen %d, iter %d, r.z %.6e of %.6e (tol2 %.3e), done %d\n", who, it, seen,
+                     h.iter, std::fabs(h.gam_last), h.rz0, h.tol2, h.done);
+      }
+    if (live == 0 || seen >= max_it) break;
+    if (probe && it >= 8 && h0->rz0 > 0.0) {
       // squared M^-1-norm reduction after `it` iterations -> iterations to the tolerance at that rate
-      const double ratio = std::fabs(h_sc->gam_last) / h_sc->rz0;
-      const double need = ratio > 0.0 && ratio < 1.0 ? it * std::log(h_sc->tol2) / std::log(ratio) : 1e30;
+      const double ratio = std::fabs(h0->gam_last) / h0->rz0;
+      const double need = ratio > 0.0 && ratio < 1.0 ? it * std::log(h0->tol2) / std::log(ratio) : 1e30;
       if (need > probe_budget) break;
     }
-    double rem = -1.0;  // iterations predicted to be needed beyond the `it` enqueued
+    // iterations predicted to be needed beyond the `it` enqueued, per system: a chunk ends where the first of the live
+    // systems is predicted to finish -- so that `live` shrinks then and not up to three K-system iterations later
+    double rem = -1.0;
     if (predict) {
-      rate.look(h_sc->iter, h_sc->rz0, h_sc->gam_last);
-      const double x = rate.remaining(h_sc->tol2 * h_sc->rz0);
-      if (x >= 0.0) rem = std::max(0.0, x - (double)(it - seen));
+      double xmin = DBL_MAX;
+      for (int s = 0; s < live; ++s) {
+        const DevScalars& h = V.h_sc[s];
+        if (finished(h)) continue;
+        rate[s].look(h.iter, h.rz0, h.gam_last);
+        const double x = rate[s].remaining(h.tol2 * h.rz0);
+        xmin = x < 0.0 ? -1.0 : std::min(xmin, x);
+        if (x < 0.0) break;
+      }
+      if (xmin >= 0.0) rem = std::max(0.0, xmin - (double)(it - seen));
     }
     int todo = graphed && it == 0 ? 1 : std::min(sched_chunk(rem, chunk, cap), max_it - it);
     if (seen < it && (todo <= 0 || rem == 0.0)) continue;  // all that is predicted is in the queue: wait for it
     if (graphed && it > 0 && par == 1 && todo >= graph_iters) todo -= todo % graph_iters;
     todo = keep_parity(todo);
+    if (V.batch) V.cv->nsys = live;
     rc = enqueue(todo);
     if (rc) return rc;
     // more than this chunk predicted: the look at it goes into a pinned slot and is waited for with the next
@@ -474,103 +609,266 @@ int Engine::pcg_attempt(double lambda, int prec, int32_t* iters, double* rel_res
     if (graphed && par == 1 && ahead >= graph_iters) ahead -= ahead % graph_iters;
     ahead = keep_parity(ahead);
     if (ahead >= 2) {
-      rc = poll_async(d_sc, 1, err);
+      rc = poll_async(V.sc, V.nsc, err);
       if (rc) return rc;
       seen = it;
       rc = enqueue(ahead);
       if (rc) return rc;
-      rc = poll_wait(h_sc, 1, err);
+      rc = poll_wait(V.h_sc, V.nsc, err);
       if (rc) return rc;
-      if (!opt.time_kernels) spmv_work_seen = h_sc->n_spmv_work;
+      note_work();
       have = true;
     }
   }
-  // iterations enqueued that found the solve finished (h_sc: the last look of this solve)
+  // iterations enqueued that found the solve finished (V.h_sc: the last look of this solve; a batch: K-system
+  // iterations that found every system finished)
   auto count_idle = [&]() {
-    sched_stats[1] += std::max<int64_t>(0, (sched_stats[0] - enq0) - (int64_t)(h_sc->n_spmv_work - work0));
+    sched_stats[1] += std::max<int64_t>(0, (sched_stats[0] - enq0) - (int64_t)(h0->n_spmv_work - work0));
   };
   // stopped on a look that had a chunk queued behind it: the SpMV events are read once the stream has been waited for
-  bool drain_late = opt.time_kernels && seen < it;
-  if (probe && abandoned && !h_sc->done && !h_sc->fail) {  // (ran out of budget or predicted to)
+  bool drain_late = !V.batch && opt.time_kernels && seen < it;
+  if (probe && abandoned && !h0->done && !h0->fail) {  // (ran out of budget or predicted to)
     *abandoned = true;
     count_idle();
-    kt.n_pcg_vec += h_sc->iter;
-    *iters = h_sc->iter;
-    *rel_res = h_sc->rz0 > 0 ? std::sqrt(std::fabs(h_sc->gam_last) / h_sc->rz0) : 0.0;
-    *ok = true;
+    kt.n_pcg_vec += h0->iter;
     return SIM3OPT_OK;
   }
-  if (drain_late && !(use_mg && !h_sc->fail)) {
+  // The stopping test is in the M^-1 norm.  A multigrid cycle is symmetric by construction but
+  // positive definite only within limits (over-correction, inexact coarse solves): should it
+  // ever lose definiteness, r.z can vanish while r has not.  So the 2-norm of the (recursive)
+  // residual is checked against ||b|| once per solve: two more small launches per system and one read-back.
+  bool checked[KB] = {false, false, false, false}, any_checked = false;
+  for (int s = 0; s < nsys; ++s) any_checked |= checked[s] = check_true && !V.h_sc[s].fail;
+  if (drain_late && !any_checked) {
     HIPCHK(hipStreamSynchronize(stream));
     rc = pool_drain(err);
     if (rc) return rc;
     drain_late = false;
   }
   if (multi) {  // every rank updates its replica of all estimates
-    rc = comm.allgatherv(d_x, offs, stream, err);  // (the whole step: every replica updates every estimate)
+    rc = comm.allgatherv(V.x, offs, stream, err);  // (the whole step: every replica updates every estimate)
     if (rc) return rc;
     rc = agree_on_fail(err);
     if (rc) return rc;
-    rc = fetch_scalars(err);
+    rc = fetch_scalars(V, err);
     if (rc) return rc;
   }
-  last_true_rel = 0.0;
-  if (use_mg && !h_sc->fail) {
-    // The stopping test is in the M^-1 norm.  A multigrid cycle is symmetric by construction but
-    // positive definite only within limits (over-correction, inexact coarse solves): should it
-    // ever lose definiteness, r.z can vanish while r has not.  So the 2-norm of the (recursive)
-    // residual is checked against ||b|| once per solve: two more small launches and one read-back.
-    const int gn = grid_for(7 * (int64_t)nloc, WG);
-    hipLaunchKernelGGL(k_norms2, dim3(gn), dim3(WG), 0, stream, 7 * r0, 7 * r1, d_r, d_b, d_part_a, d_part_b);
-    hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gn, &d_sc->tmp_pq);
+  if (any_checked || V.batch) {  // (a batch: this look always, checked or not)
+    for (int s = 0; s < nsys; ++s)
+      if (checked[s])
+        norms2(V.r + (size_t)s * V.vs, V.b + (size_t)s * V.bstride, V.part_a, V.part_b, &V.sc[s].tmp_pq);
     HIPCHK(hipGetLastError());
     if (multi) {
-      rc = comm.allreduce(&d_sc->tmp_pq, 2, 0, stream, err);
+      rc = comm.allreduce(&V.sc->tmp_pq, 2, 0, stream, err);
       if (rc) return rc;
     }
-    rc = fetch_scalars(err);
+    rc = fetch_scalars(V, err);
     if (rc) return rc;
     if (drain_late) {
       rc = pool_drain(err);
       if (rc) return rc;
     }
-    last_true_rel = h_sc->tmp_rz > 0 ? std::sqrt(h_sc->tmp_pq / h_sc->tmp_rz) : 0.0;
-    if (opt.verbose)
-      std::fprintf(stderr, "sim3opt: multigrid PCG: %d iterations, ||r||_Minv ratio %.2e, ||r||_2 / ||b||_2 %.2e\n",
-                   h_sc->iter, h_sc->rz0 > 0 ? std::sqrt(std::fabs(h_sc->gam_last) / h_sc->rz0) : 0.0, last_true_rel);
   }
   count_idle();
-  kt.n_pcg_vec += h_sc->iter;
-  *iters = h_sc->iter;
-  // r.z seen by the last executed step, i.e. of the residual BEFORE that step's update
-  *rel_res = h_sc->rz0 > 0 ? std::sqrt(std::fabs(h_sc->gam_last) / h_sc->rz0) : 0.0;
-  *ok = !h_sc->fail;
-  // stopped by the cap, not by the tolerance: an inexact step (sim3opt_iter_stats::pcg_capped); LM's gain
-  // ratio decides what becomes of it -- the exact solver it stands in for has no such state
-  last_capped = !h_sc->fail && h_sc->iter >= max_it && *rel_res > opt.pcg_rel_tol;
+  int it_max = 0;
+  for (int s = 0; s < nsys; ++s) it_max = std::max(it_max, (int)V.h_sc[s].iter);
+  kt.n_pcg_vec += it_max;
+  return SIM3OPT_OK;
+}
+
+// ---- several right-hand sides at once: the rejected trials of one LM iteration (OptimizationAlgorithmLevenberg::solve,
+// reached from kitti_surf.cpp:675) solve (H + lambda_k I) x_k = b for a known sequence lambda_k; after the first
+// rejection the next ones are solved together -- one pass over the blocks for K vectors, K vectors per coarse launch --
+// and evaluated in g2o's order (lm_trial_solve decides and hands them out).  The batch's buffers, the two views of them
+// (pv_batch for pcg_run, cv_batch for the cycle of engine_amg.hip) and its per-system set-up ----
+// buffers of the batched solve, allocated at its first use (single GPU, multigrid path)
+int Engine::batch_alloc(std::string& err) {
+  if (batch_ready) return SIM3OPT_OK;
+  const int nl = (int)amg.size();
+  auto alloc = [&](double*& p, size_t count) -> int {
+    HIPCHK(dev_malloc((void**)&p, sizeof(double) * std::max<size_t>(count, 1)));
+    batch_owned.push_back(p);
+    HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * std::max<size_t>(count, 1), stream));
+    return SIM3OPT_OK;
+  };
+  // (schedule only -- the results do not depend on it: which levels run one system per grid slice)
+  if (const char* ev = std::getenv("SIM3OPT_BATCH_SLICE_BLOCKS")) b_slice_blocks = std::atoll(ev);
+  b_vs = pad64(n);
+  double** v0[] = {&b_x, &b_r, &b_z, &b_p, &b_q, &b_s, &b_az};
+  for (double** v : v0) {
+    int rc = alloc(*v, (size_t)KB * b_vs);
+    if (rc) return rc;
+  }
+  // what the cycle (engine_amg.hip) works on for a batch: KB systems per level
+  CycleView& V = cv_batch;
+  V = CycleView();
+  V.batch = true;
+  V.lv.assign(nl, CycleLevel());
+  for (int l = 0; l < nl; ++l) {
+    CycleLevel& B = V.lv[l];
+    const AmgLevel& L = amg[l];
+    B.vs = l == 0 ? b_vs : pad64(7 * (int64_t)L.nb);
+    B.ms = (int64_t)49 * L.nb;
+    int rc = alloc(B.Minv, (size_t)KB * B.ms);
+    if (rc) return rc;
+    if (l == 0) {
+      B.r = b_r; B.x = b_z; B.t = b_az;
+    } else {
+      if ((rc = alloc(B.r, (size_t)KB * B.vs))) return rc;
+      if ((rc = alloc(B.x, (size_t)KB * B.vs))) return rc;
+      if ((rc = alloc(B.t, (size_t)KB * B.vs))) return rc;
+      HIPCHK(dev_malloc((void**)&B.diag32, sizeof(float) * (size_t)KB * B.ms));
+      batch_owned.push_back(B.diag32);
+      HIPCHK(hipMemsetAsync(B.diag32, 0, sizeof(float) * (size_t)KB * B.ms, stream));
+    }
+  }
+  const size_t nc = (size_t)7 * amg[nl - 1].nb;
+  b_as = (int64_t)(nc * nc);
+  int rc = alloc(b_Ainv, (size_t)KB * b_as);
+  if (rc) return rc;
+  if ((rc = alloc(b_diag64, (size_t)KB * 49 * amg[nl - 1].nb))) return rc;
+  if ((rc = alloc(b_part_a, (size_t)KB * SPAN_GRID_MAX))) return rc;
+  if ((rc = alloc(b_part_b, (size_t)KB * SPAN_GRID_MAX))) return rc;
+  HIPCHK(dev_malloc((void**)&d_bsc, sizeof(DevScalars) * KB));
+  batch_owned.push_back(d_bsc);
+  HIPCHK(hipMemsetAsync(d_bsc, 0, sizeof(DevScalars) * KB, stream));
+  HIPCHK(host_malloc((void**)&h_bsc, sizeof(DevScalars) * KB));
+  V.sc = d_bsc;
+  V.Ainv = b_Ainv;
+  V.as = b_as;
+  V.rz_part = b_part_b;
+  V.part = SPAN_GRID_MAX;
+  // ... and what the PCG (engine_pcg.hip) works on
+  PcgView& P = pv_batch;
+  P = PcgView();
+  P.batch = true;
+  P.nsc = KB;
+  P.x = b_x; P.r = b_r; P.z = b_z; P.p = b_p; P.q = b_q; P.s = b_s; P.az = b_az;
+  P.vs = b_vs;
+  P.Minv = V.lv[0].Minv;
+  P.ms = V.lv[0].ms;
+  P.sc = d_bsc;
+  P.h_sc = h_bsc;
+  P.part_a = b_part_a;
+  P.part_b = b_part_b;
+  P.pstride = SPAN_GRID_MAX;
+  P.cv = &cv_batch;
+  batch_ready = true;
+  return SIM3OPT_OK;
+}
+
+void Engine::batch_release() {
+  for (void* p : batch_owned)
+    if (p) dev_free(p);
+  batch_owned.clear();
+  if (h_bsc) host_free(h_bsc);
+  h_bsc = nullptr;
+  d_bsc = nullptr;
+  cv_batch = CycleView();
+  pv_batch = PcgView();
+  batch_ready = false;
+}
+
+void Engine::batch_prepare(int nsetup) {
+  const int nl = (int)amg.size();
+  for (int s = 0; s < nsetup; ++s) {
+    for (int l = 0; l < nl; ++l) {
+      const AmgLevel& L = amg[l];
+      const CycleLevel& B = cv_batch.lv[l];
+      jacobi(0, L.nb, L.rowptr, L.vals, pv_batch.lam[s], B.Minv + (size_t)s * B.ms, amg_omega, L.diagH, L.W, nullptr,
+             d_bsc + s, l == nl - 1 ? b_diag64 + (size_t)s * 49 * L.nb : nullptr,
+             l > 0 ? B.diag32 + (size_t)s * B.ms : nullptr);
+    }
+    dense_inverse(b_diag64 + (size_t)s * 49 * amg[nl - 1].nb, b_Ainv + (size_t)s * b_as, d_bsc + s);
+  }
+}
+
+// The solve of LM trial q at damping lambda; ni is the factor the next rejection applies.  After a rejection g2o's
+// rule fixes the dampings of the next trials (lambda *= ni, ni *= 2 per rejection), so the systems of the trials
+// that may follow are solved TOGETHER -- one pass over the blocks for all of them -- and handed to the trials one
+// after the other, evaluated exactly as before; a trial that is accepted leaves the rest unused.
+// Only systems the hierarchy would solve anyway: a damping-dominated one (lambda >= the block-Jacobi gate,
+// adaptive_prec) is cheaper on its own.
+// ... and only while this iteration's solves behave: a batch runs until its LAST system is done, every iteration
+// at the price of all of them, and one failing system sends the whole batch to the sequential path's fall-backs --
+// in the as-written arithmetic (solves of hundreds of iterations, break-downs, a capped one) that made the
+// reference_arithmetic leg 1.7x SLOWER; there the trials stay sequential.
+int Engine::lm_trial_solve(int q, double lambda, double ni, const double** x, int32_t* iters, double* rel_res,
+                           bool* ok, std::string& err) {
+  TrialBatch& B = trial_batch;
+  bool from_batch = q > 0 && B.next < B.n && B.lam[B.next] == lambda;
+  if (!from_batch) {
+    B.n = B.next = 0;
+    const bool calm = B.prev_ok && !B.prev_capped && B.prev_pit > 0 && B.prev_pit <= 100;
+    const int cap = q >= 1 && calm ? std::min(batch_capacity(), opt.max_trials - q) : 0;
+    if (cap >= 2) {
+      double gate = DBL_MAX;
+      if (adaptive_prec && !trace_stale && mean_diag > 0.0) gate = bj_gate >= 0.0 ? bj_gate : 0.05 * mean_diag;
+      int nsys = 0;
+      double l = lambda, nu = ni;
+      while (nsys < cap && l < gate && std::isfinite(l)) {
+        B.lam[nsys++] = l;
+        l *= nu;
+        nu *= 2.0;
+      }
+      if (nsys >= 2) {
+        bool usable = false;
+        int rc = pcg_batch(B.lam, nsys, B.iters, B.rel, B.capped, &usable, err);
+        if (rc) return rc;
+        if (usable) {
+          B.n = nsys;
+          from_batch = true;
+        }
+      }
+    }
+  }
+  if (from_batch) {
+    const int s = B.next++;
+    *x = b_x + (size_t)s * b_vs;
+    *iters = B.iters[s];
+    *rel_res = B.rel[s];
+    *ok = true;
+    last_capped = B.capped[s];
+  } else {
+    *x = d_x;
+    int rc = pcg(lambda, iters, rel_res, ok, err);
+    if (rc) return rc;
+  }
+  B.prev_ok = *ok;
+  B.prev_capped = last_capped;
+  B.prev_pit = *iters;
   return SIM3OPT_OK;
 }
 
 // ---- diagnostic read-outs (see engine_impl.hpp) ----
-int Engine::diag_begin(double lambda, DevScalars& saved_d, DevScalars& saved_h, std::string& err) {
+int Engine::diag_begin(PcgView& V, const double* lambda, int nrhs, DevScalars* saved_d, DevScalars* saved_h,
+                       std::string& err) {
   HIPCHK(hipStreamSynchronize(stream));
-  saved_h = *h_sc;
-  HIPCHK(hipMemcpy(&saved_d, d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
-  // the PCG fields as pcg_attempt sets them: not done (level-0 launches test it), no failure yet, this damping
-  DevScalars s = saved_d;
-  s.rz[0] = s.rz[1] = s.alpha[0] = s.alpha[1] = s.rz0 = 0.0;
-  s.iter = 0;
-  s.done = s.stop = s.fail = 0;
-  s.lambda = lambda;
-  HIPCHK(hipMemcpy(d_sc, &s, sizeof(DevScalars), hipMemcpyHostToDevice));
+  std::memcpy(saved_h, V.h_sc, sizeof(DevScalars) * V.nsc);
+  HIPCHK(hipMemcpy(saved_d, V.sc, sizeof(DevScalars) * V.nsc, hipMemcpyDeviceToHost));
+  // the PCG fields as a solve sets them: the first nrhs not done (level-0 launches test it), no failure yet, their damping
+  DevScalars s[KB];
+  for (int k = 0; k < V.nsc; ++k) {
+    s[k] = saved_d[k];
+    s[k].rz[0] = s[k].rz[1] = s[k].alpha[0] = s[k].alpha[1] = s[k].rz0 = 0.0;
+    s[k].iter = 0;
+    s[k].done = k < nrhs ? 0 : 1;
+    s[k].stop = s[k].fail = 0;
+    s[k].lambda = lambda[std::min(k, nrhs - 1)];
+  }
+  HIPCHK(hipMemcpy(V.sc, s, sizeof(DevScalars) * V.nsc, hipMemcpyHostToDevice));
   return SIM3OPT_OK;
 }
 
-int Engine::diag_end(const DevScalars& saved_d, const DevScalars& saved_h, std::string& err) {
-  HIPCHK(hipStreamSynchronize(stream));
-  HIPCHK(hipMemcpy(d_sc, &saved_d, sizeof(DevScalars), hipMemcpyHostToDevice));
-  *h_sc = saved_h;
-  return SIM3OPT_OK;
+int Engine::diag_end(PcgView& V, const DevScalars* saved_d, const DevScalars* saved_h, int rc, std::string& err) {
+  const bool put_back = hipStreamSynchronize(stream) == hipSuccess &&
+                        hipMemcpy(V.sc, saved_d, sizeof(DevScalars) * V.nsc, hipMemcpyHostToDevice) == hipSuccess;
+  std::memcpy(V.h_sc, saved_h, sizeof(DevScalars) * V.nsc);
+  if (rc == SIM3OPT_OK && !put_back) {
+    err = "restoring the solver's scalars failed";
+    rc = SIM3OPT_ERR_HIP;
+  }
+  return rc;
 }
 
 int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r, double* z, std::string& err) {
@@ -590,24 +888,14 @@ int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r
   const int gv = grid_for((nloc + 8) / 9, 4);
   const int nseg = (nloc + chain_seg - 1) / chain_seg;
   DevScalars sd, sh;
-  int rc = diag_begin(lambda, sd, sh, err);
+  int rc = diag_begin(pv_one, &lambda, 1, &sd, &sh, err);
   if (rc) return rc;
   auto body = [&]() -> int {
-    if (prec == 2) {
-      if (amg_stale) {
-        int rc2 = amg_setup(err);
-        if (rc2) return rc2;
-      }
-      amg_prepare(lambda);
-    } else if (prec == 1) {
-      hipLaunchKernelGGL(k_chain_factor, dim3(std::max(1, (nseg + 63) / 64)), dim3(64), 0, stream, r0, r1, chain_seg,
-                         d_rowptr, d_vals, d_sub_first, d_sub_cnt, lambda, d_Minv, d_Gm, d_sc);
-    } else {
-      hipLaunchKernelGGL(k_jacobi, dim3(std::max(1, (nloc + WG - 1) / WG)), dim3(WG), 0, stream, r0, r1, d_rowptr,
-                         d_vals, lambda, d_Minv, d_sc, 1.0, (const double*)nullptr, (const double*)nullptr);
-    }
+    pv_one.lam[0] = lambda;
+    int rc2 = pcg_setup(pv_one, prec, 1, err);
+    if (rc2) return rc2;
     HIPCHK(hipGetLastError());
-    int rc2 = fetch_scalars(err);
+    rc2 = fetch_scalars(err);
     if (rc2) return rc2;
     if (h_sc->fail) {
       err = "precond_apply: the set-up met a non-positive pivot";
@@ -616,8 +904,9 @@ int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r
     for (int32_t q = 0; q < nrhs; ++q) {
       // r -> d_r and d_z = Minv_0 r, the arithmetic k_pcg_step leaves them with (d_q: staging, a solve rewrites it)
       HIPCHK(hipMemcpyAsync(d_q, r + (size_t)q * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(k_pcg_init, dim3(gv), dim3(WG), 0, stream, r0, r1, (const double*)d_q,
-                         prec == 1 ? (const double*)nullptr : (const double*)d_Minv, d_x, d_r, d_z, d_p, d_s);
+      hipLaunchKernelGGL((k_pcg_init<1, false>), dim3(gv), dim3(WG), 0, stream, r0, r1, (const double*)d_q,
+                         prec == 1 ? (const double*)nullptr : (const double*)d_Minv, d_x, d_r, d_z, d_p, d_s,
+                         BatchStrides{0, 0, 0, 0, 0}, (int64_t)0);
       const double* res = d_z;
       if (prec == 1) {
         hipLaunchKernelGGL(k_chain_apply, dim3(grid_for(nseg, 4)), dim3(WG), 0, stream, r0, r1, chain_seg, d_Minv, d_Gm,
@@ -633,14 +922,7 @@ int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r
     }
     return SIM3OPT_OK;
   };
-  rc = body();
-  std::string err2;
-  const int rc_end = diag_end(sd, sh, err2);
-  if (rc == SIM3OPT_OK && rc_end) {
-    err = err2;
-    rc = rc_end;
-  }
-  return rc;
+  return diag_end(pv_one, &sd, &sh, body(), err);
 }
 
 int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, const double* r, double* z,
@@ -670,38 +952,37 @@ int Engine::operator_apply(int32_t nrhs, const double* lambda, const double* p, 
     err = "operator_apply: several systems need the batch buffers of a multigrid graph";
     return SIM3OPT_ERR_STATE;
   }
-  DevScalars sd, sh;
-  int rc = diag_begin(lambda[0], sd, sh, err);
+  PcgView& V = nrhs > 1 ? pv_batch : pv_one;
+  int rc = nrhs > 1 ? batch_alloc(err) : SIM3OPT_OK;
+  if (rc) return rc;
+  DevScalars sd[KB], sh[KB];
+  rc = diag_begin(V, lambda, nrhs, sd, sh, err);
   if (rc) return rc;
   auto body = [&]() -> int {
-    if (nrhs > 1) return operator_apply_batch(nrhs, lambda, p, rvec, q, pq, rp, err);
-    // p -> d_z (what the PCG hands its SpMV), rvec -> d_r; the damping travels in d_sc as in pcg_attempt
+    // p -> what a solve hands its SpMV (d_z; a batch: b_az), rvec -> r; the dampings travel in the scalars as in a solve
+    double* const in = V.batch ? V.az : V.z;
     const size_t bytes = sizeof(double) * (size_t)n;
-    HIPCHK(hipMemcpyAsync(d_z, p, bytes, hipMemcpyHostToDevice, stream));
-    if (rvec) HIPCHK(hipMemcpyAsync(d_r, rvec, bytes, hipMemcpyHostToDevice, stream));
-    const int gs = spmv_grid();
-    spmv_raw(lambda[0], d_z, d_q, rvec ? d_r : nullptr, d_sc);
-    // (k_pcg_step adds the partials by sum_partials in every workgroup, or reads the pair k_final_sum2 left when there
-    // are more than MAX_GRID of them: the same FUNCTION on the same arrays, count and block size, hence the same value
-    // -- one launch serves both; the in-step summation itself is exercised by the iterates of sim3opt_solve only)
-    hipLaunchKernelGGL(k_final_sum2, dim3(1), dim3(WG), 0, stream, d_part_a, d_part_b, gs, &d_sc->tmp_pq);
+    for (int k = 0; k < nrhs; ++k) {
+      V.lam[k] = lambda[k];
+      HIPCHK(hipMemcpyAsync(in + (size_t)k * V.vs, p + (size_t)k * n, bytes, hipMemcpyHostToDevice, stream));
+      if (rvec) HIPCHK(hipMemcpyAsync(V.r + (size_t)k * V.vs, rvec + (size_t)k * n, bytes, hipMemcpyHostToDevice, stream));
+    }
+    int rc2 = pcg_spmv(V, nrhs, in, rvec ? V.r : nullptr, false, err);
+    if (rc2) return rc2;
+    BATCH_DISPATCH(nrhs, hipLaunchKernelGGL((k_final_sum2<KS>), dim3(1), dim3(WG), 0, stream, (const double*)V.part_a,
+                       (const double*)V.part_b, spmv_grid(), V.pstride, &V.sc->tmp_pq, SC_DOUBLES));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipMemcpy(q, d_q, bytes, hipMemcpyDeviceToHost));
-    double two[2];
-    HIPCHK(hipMemcpy(two, &d_sc->tmp_pq, sizeof(two), hipMemcpyDeviceToHost));
-    pq[0] = two[0];
-    if (rp) rp[0] = two[1];
+    DevScalars s[KB];
+    HIPCHK(hipMemcpy(s, V.sc, sizeof(DevScalars) * V.nsc, hipMemcpyDeviceToHost));
+    for (int k = 0; k < nrhs; ++k) {
+      HIPCHK(hipMemcpy(q + (size_t)k * n, V.q + (size_t)k * V.vs, bytes, hipMemcpyDeviceToHost));
+      pq[k] = s[k].tmp_pq;
+      if (rp) rp[k] = s[k].tmp_rz;
+    }
     return SIM3OPT_OK;
   };
-  rc = body();
-  std::string err2;
-  const int rc_end = diag_end(sd, sh, err2);
-  if (rc == SIM3OPT_OK && rc_end) {
-    err = err2;
-    rc = rc_end;
-  }
-  return rc;
+  return diag_end(V, sd, sh, body(), err);
 }
 
 int engine_spmv_spans(Engine* e, int32_t* n_spans, int32_t* wrow, std::string& err) {

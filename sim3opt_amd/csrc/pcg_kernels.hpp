@@ -1,5 +1,6 @@
-// pcg_kernels.hpp -- device side of the linear solve, non-template part (included by engine_pcg.hip ONLY,
-// inside namespace sim3opt): the single-reduction PCG step, the block-Jacobi inverses, the chain-segment
+// pcg_kernels.hpp -- device side of the linear solve (included by engine_pcg.hip ONLY, inside namespace sim3opt): the
+// single-reduction PCG step, its first residual and the two-value sums as templates on the number K of systems solved
+// together (K = 1 is the one-system solve; vectors of system s at base + s * stride, BatchStrides), the block-Jacobi inverses, the chain-segment
 // preconditioner, the halo exchange of the row-partitioned path, fixed-order two-value sums and the HBM read
 // calibration kernels.  The block-CSR SpMV itself is a template: spmv_kernel.hpp.  Stands in for
 // LinearSolverEigen::solve (kitti_surf.cpp:553-554) on graphs where a factorisation is not cheap;
@@ -9,16 +10,20 @@
 // PCG kernels.  Vector kernels map 63 lanes of a wavefront onto 9 block rows x 7 so a block
 // row's 7 entries sit in one wavefront (z = Minv r by shuffles) and addresses stay contiguous.
 // ------------------------------------------------------------------------------------------
-// two sums in one launch (multi-GPU PCG: [w.z, r.z] land in adjacent doubles for one all-reduce)
-__global__ __launch_bounds__(WG) void k_final_sum2(const double* __restrict__ pa,
-                                                   const double* __restrict__ pb, int n,
-                                                   double* __restrict__ out2) {
+// two sums in one launch per system: [w.z, r.z] of system s land in the adjacent doubles out2 + s * ostride (in doubles;
+// sc[s].tmp_pq / tmp_rz with out2 = &sc->tmp_pq and ostride = sizeof(DevScalars) / 8; multi-GPU: one all-reduce)
+template <int K>
+__global__ __launch_bounds__(WG) void k_final_sum2(const double* __restrict__ pa, const double* __restrict__ pb, int n,
+                                                   int pstride, double* __restrict__ out2, int ostride) {
   __shared__ double sh[4];
-  const double a = sum_partials(pa, n, sh);
-  const double b = sum_partials(pb, n, sh);
-  if (threadIdx.x == 0) {
-    out2[0] = a;
-    out2[1] = b;
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    const double a = sum_partials(pa + (size_t)s * pstride, n, sh);
+    const double b = sum_partials(pb + (size_t)s * pstride, n, sh);
+    if (threadIdx.x == 0) {
+      out2[(size_t)s * ostride] = a;
+      out2[(size_t)s * ostride + 1] = b;
+    }
   }
 }
 
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(WG) void k_jacobi(int r0, int r1, const int32_t* __
       for (int r = 0; r < 7; ++r) {
         a[r][c] += lambda * w[7 * c + r];
         if (diag64_out || diag32_out) {
-          // (one of several systems solved together, batch_kernels.hpp: the damped block goes to the system's
+          // (one of several systems solved together, Engine::batch_prepare: the damped block goes to the system's
           // own arrays, [row][49] column-major; the shared level arrays stay as they are)
           if (diag64_out) diag64_out[(size_t)49 * row + 7 * c + r] = a[r][c];
           if (diag32_out) diag32_out[(size_t)49 * row + 7 * c + r] = (float)a[r][c];
@@ -99,12 +104,15 @@ __global__ __launch_bounds__(WG) void k_jacobi(int r0, int r1, const int32_t* __
     for (int c = 0; c < 7; ++c) dst[7 * r + c] = omega * a[r][c];
 }
 
-// x = 0, r = b, z = Minv b (block-Jacobi; the chain preconditioner runs separately), p = s = 0
+// Per system s < K (vectors at base + s * bs.vec, Minv at + s * bs.minv): x = 0, r = b, z = Minv b (block-Jacobi; the
+// chain preconditioner, Minv == nullptr, runs separately), p = s = 0.  b is shared -- or, OWNB (the columns of the
+// inverse, engine_columns.hip), system s has its own right-hand side b + s * bstride.
+template <int K, bool OWNB = false>
 __global__ __launch_bounds__(WG) void k_pcg_init(int r0, int r1, const double* __restrict__ b,
-                                                 const double* __restrict__ Minv,
-                                                 double* __restrict__ x, double* __restrict__ r,
-                                                 double* __restrict__ z, double* __restrict__ p,
-                                                 double* __restrict__ sv) {
+                                                 const double* __restrict__ Minv, double* __restrict__ x,
+                                                 double* __restrict__ r, double* __restrict__ z,
+                                                 double* __restrict__ p, double* __restrict__ sv,
+                                                 BatchStrides bs, int64_t bstride) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int sub = lane / 7, rr = lane % 7, base = lane - rr;
@@ -112,21 +120,26 @@ __global__ __launch_bounds__(WG) void k_pcg_init(int r0, int r1, const double* _
     const int row = row0 + sub;
     const bool act = lane < 63 && row < r1;
     const size_t j = (size_t)7 * row + rr;
-    const double rv = act ? b[j] : 0.0;
-    if (act) {
-      x[j] = 0.0;
-      r[j] = rv;
-      p[j] = 0.0;
-      sv[j] = 0.0;
-    }
-    if (Minv) {
-      double zv = 0.0;
+    double rv = act ? b[j] : 0.0;
 #pragma unroll
-      for (int cc = 0; cc < 7; ++cc) {
-        const double rc = __shfl(rv, base + cc);
-        if (act) zv += Minv[(size_t)49 * row + 7 * rr + cc] * rc;
+    for (int s = 0; s < K; ++s) {
+      const size_t o = (size_t)s * bs.vec;
+      if (OWNB && s > 0) rv = act ? b[(size_t)s * bstride + j] : 0.0;
+      if (act) {
+        x[o + j] = 0.0;
+        r[o + j] = rv;
+        p[o + j] = 0.0;
+        sv[o + j] = 0.0;
       }
-      if (act) z[j] = zv;
+      if (Minv) {
+        double zv = 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 7; ++cc) {
+          const double rc = __shfl(rv, base + cc);
+          if (act) zv += Minv[(size_t)s * bs.minv + (size_t)49 * row + 7 * rr + cc] * rc;
+        }
+        if (act) z[o + j] = zv;
+      }
     }
   }
 }
@@ -280,43 +293,63 @@ __global__ __launch_bounds__(WG) void k_chain_apply(int r0, int r1, int seg,
 //   p = z + beta p,  s = w + beta s (= A p),  x += alpha p,  r -= alpha s,  z = Minv r
 // Workgroup 0 commits gamma / alpha for the next launch (ping-pong by parity, so no workgroup
 // reads what another one writes in the same launch) and the stopping decision.
+// K systems in lock-step: every system has its own scalars sc[s], its vectors at base + s * bs.vec and its Minv at
+// + s * bs.minv; a finished system is left alone, one that converges earlier just stops being updated.  delta and
+// gamma are read from sc[s].tmp_pq / tmp_rz (k_final_sum2 has summed them) or, part_d != nullptr (K = 1 only), summed
+// here from the SpMV's npart partials at part + s * pstride.  it >= 0: the launch number (0 = first iteration of every system);
+// it < 0: a captured (replayed) launch, never the first iteration.
+template <int K>
 __global__ __launch_bounds__(WG) void k_pcg_step(int r0, int r1, int par, int it,
-                                                 const double* __restrict__ scal,
                                                  const double* __restrict__ part_d,
-                                                 const double* __restrict__ part_g, int npart,
+                                                 const double* __restrict__ part_g, int npart, int pstride,
                                                  const double* __restrict__ Minv,
                                                  const double* zin, double* zout,
                                                  const double* __restrict__ w,
                                                  double* __restrict__ p, double* __restrict__ sv,
                                                  double* __restrict__ x, double* __restrict__ r,
-                                                 DevScalars* sc) {
+                                                 DevScalars* sc, BatchStrides bs) {
   __shared__ double sh[4];
-  if (sc->done) return;
-  const double delta = scal ? scal[0] : sum_partials(part_d, npart, sh);
-  const double gamma = scal ? scal[1] : sum_partials(part_g, npart, sh);
-  const bool first = it == 0;  // it < 0: a captured (replayed) launch, never the first iteration
-  const double gamma0 = first ? gamma : sc->rz0;
+  double alpha[K], beta[K], gam[K];
+  bool live[K];
   const bool commit = blockIdx.x == 0 && threadIdx.x == 0;
-  if (!(gamma == gamma) || gamma < 0.0 || gamma <= sc->tol2 * gamma0 || (first && gamma == 0.0)) {
-    if (commit) {  // converged (x is final) or broken down; every workgroup sees the same gamma
-      if (!(gamma == gamma) || gamma < 0.0) sc->fail = 1;
-      if (first) sc->rz0 = gamma;
-      sc->rz[par ^ 1] = gamma;
-      sc->gam_last = gamma;
-      sc->done = 1;
+  const bool first = it == 0;
+  // (K > 1 never sums here: the sums would move every system's alpha, beta and gamma from scalar to vector registers,
+  // 78 of them for K = 4 -- one occupancy step)
+  const bool sum_here = K == 1 && part_d;
+  bool any = false;
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    live[s] = false;
+    alpha[s] = beta[s] = gam[s] = 0.0;
+    if (sc[s].done) continue;
+    const double delta = sum_here ? sum_partials(part_d + (size_t)s * pstride, npart, sh) : sc[s].tmp_pq;
+    const double gamma = sum_here ? sum_partials(part_g + (size_t)s * pstride, npart, sh) : sc[s].tmp_rz;
+    const double gamma0 = first ? gamma : sc[s].rz0;
+    if (!(gamma == gamma) || gamma < 0.0 || gamma <= sc[s].tol2 * gamma0 || (first && gamma == 0.0)) {
+      if (commit) {  // converged (x is final) or broken down; every workgroup sees the same gamma
+        if (!(gamma == gamma) || gamma < 0.0) sc[s].fail = 1;
+        if (first) sc[s].rz0 = gamma;
+        sc[s].rz[par ^ 1] = gamma;
+        sc[s].gam_last = gamma;
+        sc[s].done = 1;
+      }
+      continue;
     }
-    return;
-  }
-  const double beta = first ? 0.0 : gamma / sc->rz[par];
-  const double denom = first ? delta : delta - beta * gamma / sc->alpha[par];
-  if (!(denom > 0.0) || !(denom < DBL_MAX)) {  // not positive definite (g2o: Cholesky fails)
-    if (commit) {
-      sc->fail = 1;
-      sc->done = 1;
+    beta[s] = first ? 0.0 : gamma / sc[s].rz[par];
+    const double denom = first ? delta : delta - beta[s] * gamma / sc[s].alpha[par];
+    if (!(denom > 0.0) || !(denom < DBL_MAX)) {  // not positive definite (g2o: Cholesky fails)
+      if (commit) {
+        sc[s].fail = 1;
+        sc[s].done = 1;
+      }
+      continue;
     }
-    return;
+    alpha[s] = gamma / denom;
+    gam[s] = gamma;
+    live[s] = true;
+    any = true;
   }
-  const double alpha = gamma / denom;
+  if (!any) return;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int sub = lane / 7, rr = lane % 7, base = lane - rr;
@@ -324,34 +357,44 @@ __global__ __launch_bounds__(WG) void k_pcg_step(int r0, int r1, int par, int it
     const int row = row0 + sub;
     const bool act = lane < 63 && row < r1;
     const size_t j = (size_t)7 * row + rr;
-    double rv = 0.0;
-    if (act) {
-      const double pn = zin[j] + beta * p[j];
-      const double sn = w[j] + beta * sv[j];
-      p[j] = pn;
-      sv[j] = sn;
-      x[j] += alpha * pn;
-      rv = r[j] - alpha * sn;
-      r[j] = rv;
-    }
-    if (Minv) {
-      double zv = 0.0;
 #pragma unroll
-      for (int cc = 0; cc < 7; ++cc) {
-        const double rc = __shfl(rv, base + cc);
-        if (act) zv += Minv[(size_t)49 * row + 7 * rr + cc] * rc;
+    for (int s = 0; s < K; ++s) {
+      if (!live[s]) continue;  // (uniform over the grid)
+      const size_t o = (size_t)s * bs.vec;
+      double rv = 0.0;
+      if (act) {
+        const double pn = zin[o + j] + beta[s] * p[o + j];
+        const double sn = w[o + j] + beta[s] * sv[o + j];
+        p[o + j] = pn;
+        sv[o + j] = sn;
+        x[o + j] += alpha[s] * pn;
+        rv = r[o + j] - alpha[s] * sn;
+        r[o + j] = rv;
       }
-      if (act) zout[j] = zv;
+      if (Minv) {
+        double zv = 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 7; ++cc) {
+          const double rc = __shfl(rv, base + cc);
+          if (act) zv += Minv[(size_t)s * bs.minv + (size_t)49 * row + 7 * rr + cc] * rc;
+        }
+        if (act) zout[o + j] = zv;
+      }
     }
   }
   if (commit) {
-    if (first) sc->rz0 = gamma;
-    sc->rz[par ^ 1] = gamma;
-    sc->gam_last = gamma;
-    sc->alpha[par ^ 1] = alpha;
-    const int itn = (it < 0 ? sc->iter : it) + 1;  // only this thread ever writes sc->iter
-    sc->iter = itn;
-    if (itn >= sc->max_iter) sc->stop = 1;
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      if (!live[s]) continue;
+      const double gamma = sum_here ? gam[s] : sc[s].tmp_rz;
+      if (first) sc[s].rz0 = gamma;
+      sc[s].rz[par ^ 1] = gamma;
+      sc[s].gam_last = gamma;
+      sc[s].alpha[par ^ 1] = alpha[s];
+      const int itn = (it < 0 ? sc[s].iter : it) + 1;  // only this thread ever writes sc[s].iter
+      sc[s].iter = itn;
+      if (itn >= sc[s].max_iter) sc[s].stop = 1;
+    }
   }
 }
 

@@ -1,6 +1,6 @@
 // spmv_kernel.hpp -- the software-pipelined 7x7 block-CSR SpMV with its multigrid epilogues (a template:
-// instantiated by engine_pcg.hip for the PCG's own product, by engine_amg.hip for the cycle's matrix passes (one and
-// K right-hand sides) and by engine_batch.hip for the K-system product -- ONE kernel source: the one-system kernel is K = 1; measured
+// instantiated by engine_pcg.hip for the PCG's own product, of one and of K systems, and by engine_amg.hip for the
+// cycle's matrix passes (one and K right-hand sides) -- ONE kernel source: the one-system kernel is K = 1; measured
 // on the driver's command: 47.1-47.2 LM it/s against 46.6-46.9 with a separate one-system kernel).
 // LinearSolverEigen's role, kitti_surf.cpp:553-554; SURVEY.md 8(a) row a9.
 #pragma once
@@ -31,7 +31,7 @@
 #endif
 constexpr bool FASTPATH = SIM3OPT_SPMV_FASTPATH != 0;
 
-// K > 1 (engine_batch.hip: the rejected trials of one LM iteration, solved together): the block stream, the
+// K > 1 (Engine::pcg_batch: the rejected trials of one LM iteration, solved together): the block stream, the
 // column indices and the row bookkeeping are shared, everything that depends on the vector is an array over the
 // systems; vectors of system s live at base + s * stride (BatchStrides).  Level 0 adds the damping as lambda_s x
 // at the row end; on a coarse level (DIAGK) the damping sits in the diagonal block, so system s takes ITS

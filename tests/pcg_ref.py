@@ -1,6 +1,6 @@
 """Plain numpy restatement of the PCG's own operator and recurrence -- the block-CSR product q = (H + lambda I) p of
 k_spmv_span MODE 0 (spmv_kernel.hpp) and the single-reduction iteration of k_pcg_init / k_pcg_step (pcg_kernels.hpp;
-their K-system twins in batch_kernels.hpp) -- written from the comments of those files, with no product code.
+templates on the number K of systems) -- written from the comments of those files, with no product code.
 dtype-generic like amg_ref.py: np.longdouble is the reference the device is compared with, np.float64 the noise gauge
 of the iterates (tests/test_gpu_pcg_operator.py).
 

@@ -695,7 +695,7 @@ def test_config3_manhattan_full_size_properties():
 @pytest.mark.parametrize("graph,slice_blocks", [("manhattan", None), ("manhattan", 0), ("kitti", None)])
 def test_batched_rejected_trials_equal_sequential_solves(monkeypatch, graph, slice_blocks):
     """After a rejected LM trial the dampings of the next trials are known (g2o: lambda *= nu, nu *= 2), so their
-    systems are solved together -- one pass over the blocks for up to four vectors (engine_batch.hip) -- and the
+    systems are solved together -- one pass over the blocks for up to four vectors (Engine::pcg_batch) -- and the
     trials evaluated in g2o's order.  Same trial counts, same lambda, same chi2, same estimates as solving them
     one after the other (options.pcg_batch = 1): bit for bit -- per system the batched kernels perform the
     one-system kernels' operations in the same order.  delta = 1e-9: LM reaches the noise floor of the

@@ -1,8 +1,9 @@
-"""GPU tests (-m gpu) of the PCG loops' SCHEDULE: how many iterations the host enqueues between two looks at the
-solver's scalars, and whether a look drains the queue (engine_pcg.hip, engine_batch.hip).  The stopping iteration is
-decided on the device, so the schedule must not show in any result: every case is compared, bit for bit, with
-pcg_check_every = 1 -- one iteration per look, no prediction -- and the read-out sim3opt_pcg_schedule_stats says
-whether the schedule does what it is for: few iterations enqueued after `done`, few looks that drain the queue.
+"""GPU tests (-m gpu) of the PCG loop's SCHEDULE: how many iterations the host enqueues between two looks at the
+solver's scalars, and whether a look drains the queue (Engine::pcg_run, engine_pcg.hip: one system or a batch).  The
+stopping iteration is decided on the device, so the schedule must not show in any result: every case is compared, bit
+for bit, with pcg_check_every = 1 -- one iteration per look, no prediction -- and the read-out
+sim3opt_pcg_schedule_stats says whether the schedule does what it is for: few iterations enqueued after `done`, few
+looks that drain the queue.
 
 Graphs and options as in test_gpu_preconditioners.py; dampings relative to max diag(H): 1e-7, 1e-3, 1.
 """
@@ -122,6 +123,35 @@ def test_batched_solve_is_scheduled_the_same_way():
     # the default run did predict: solves of twenty and more iterations cannot all have gone by without one look
     # that had the next chunk queued behind it, and the chunks were not the anchor's
     assert r[5]["overlapped_polls"] > 0 and r[5]["sync_polls"] < a[5]["sync_polls"]
+
+
+def test_batch_view_of_one_system_equals_batch_view_of_four():
+    """The two widths of the batch's view against each other through the one driver: the columns of the inverse of three
+    vertices (21 columns) on the smallest multigrid case, solved four to a batch (five batches of four and a last one of
+    ONE system: every launch of it carries live == 1, the K = 1 kernels on the batch's buffers) and one to a batch
+    (pcg_batch = 1: 21 batches of one).  A column's bits do not depend on its batch partners
+    (test_gpu_covariance_columns.py asserts that for one block), so every returned block and the PCG iterations summed
+    over the columns are equal, bit for bit.  The column call puts kernel_times() back as it found it, so the batch
+    counts are read from its own stats."""
+    name, prec, opts = CASES[0]
+    assert (name, prec, opts) == ("m400", 2, dict(amg_coarsest=16))
+    pairs, lam, out = [(250, 250), (11, 11), (120, 120)], 1e-2, []
+    for width in (4, 1):
+        G = mk(graph_of(name), preconditioner=prec, cov_solver=1, pcg_batch=width, **opts)
+        assert G.preconditioner_in_use() == prec
+        kt0 = G.kernel_times()
+        Z = G.covariances(pairs, lam)
+        st, kt = G.covariance_columns_stats(), G.kernel_times()
+        assert (int(kt.n_batches), int(kt.n_batched_solves)) == (int(kt0.n_batches), int(kt0.n_batched_solves))
+        print(f"[schedule] columns, {width} to a batch: {st}")
+        assert st["columns"] == 21 and st["vertices"] == 3
+        assert 21 % width == (1 if width == 4 else 0)  # width 4: the last batch is one system
+        assert st["batches"] == -(-21 // width)  # (the first passes; a refinement solve is not counted as a batch)
+        out.append((Z, st["pcg_iters"], st["refinements"], st["max_rel_residual"]))
+        G.close()
+    assert np.abs(out[0][0]).max() > 1e-3 and out[0][1] >= 21
+    assert np.array_equal(out[0][0], out[1][0])
+    assert out[0][1:] == out[1][1:]
 
 
 @pytest.mark.parametrize("variant", ["graph", "eager", "timed"])
