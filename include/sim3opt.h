@@ -355,6 +355,36 @@ int sim3opt_sim3_edge_jacobian(const double meas[8], const double s0[8], const d
                                const sim3opt_options* o, double e[7], double J[98]);
 /* runs the linearisation kernels once on the current estimates     BlockSolver::buildSystem */
 int sim3opt_linearize(sim3opt_graph* g);
+/* ---- read-outs of the LM set-up and update kernels, for tests ----
+ * Contract of both: nothing in the solver uses them; they run the launch code of sim3opt_linearize / of an LM trial on
+ * the current estimates, copy device buffers to the host and leave the estimates, every solver scalar, the cached chi2,
+ * the statistics and sim3opt_get_kernel_times -- hence every later sim3opt_optimize -- bit for bit what they are
+ * without the call.  One GPU: SIM3OPT_ERR_STATE on a partitioned graph (a rank holds its rows' share only) and before
+ * sim3opt_initialize; SIM3OPT_ERR_ARG for a NULL pointer that is not marked optional; the message is in
+ * sim3opt_last_error.  (sim3opt_version is unchanged: diagnostics are not part of the versioned interface.) */
+/* Diagnostic.  Sizes of the arrays below: the edges the linearisation runs on (at least one free endpoint) and the
+ * incidences (free endpoints of edges) of all block rows. */
+int sim3opt_debug_linearization_dims(sim3opt_graph* g, int32_t* n_active, int32_t* n_incidences);
+/* Diagnostic.  Linearises as sim3opt_linearize does, in either Jacobian mode, with the linearisation kernel in an
+ * instantiation that also stores what its Gram phase consumed; sim3opt_get_system afterwards returns what
+ * sim3opt_linearize produces, bit for bit.  J (n_active x 15 x 7): per active edge the 14 Jacobian columns (de/dd0,
+ * then de/dd1; 7 residual rows each) and e, as they lie in LDS; w (n_active): the robust weight the phase used;
+ * active (n_active): the edges' indices; scratch (n_incidences x 35): per incidence the upper triangle of its
+ * diagonal contribution (column-major: (0,0) (0,1) (1,1) (0,2) ...) and its 7 entries of b; incptr (block rows + 1),
+ * inc0 / inc1 / slot01 / slot10 (edges each; -1: a fixed endpoint): the incidence slots and off-diagonal blocks an
+ * edge owns; *trace and *maxdiag: sum and largest magnitude of the scalar diagonal of H (lambda_0's input). */
+int sim3opt_debug_linearization(sim3opt_graph* g, double* J, double* w, int32_t* active, double* scratch,
+                                int32_t* incptr, int32_t* inc0, int32_t* inc1, int32_t* slot01, int32_t* slot10,
+                                double* trace, double* maxdiag);
+/* Diagnostic.  What an LM trial makes of a caller's step x (7 per block row, any numbers) at damping lambda: the
+ * estimates k_oplus produces (states_out, 8 per vertex) and the backup it takes (backup_out), the robustified chi2
+ * there (k_chi2) and scale = x . (lambda x + b) (k_scale), both summed by k_final_sum_two; then the estimates are
+ * restored from the backup.  Needs a linearisation (b).  with_fail != 0 presents the exact solver's failure token:
+ * nothing may move (SIM3OPT_ERR_STATE unless the exact solver is in use).  grid = 0: the workgroup counts of a trial;
+ * 1 .. 2048: that many workgroups, hence partial sums, for both k_chi2 and k_scale.  The four outputs may be NULL,
+ * not all of them. */
+int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32_t with_fail, int32_t grid,
+                         double* states_out, double* backup_out, double* chi2, double* scale);
 /* dimensions of the block-CSR system: free block rows, stored 7x7 blocks */
 int sim3opt_system_dims(const sim3opt_graph* g, int32_t* n_block_rows, int64_t* n_blocks);
 /* the block-CSR pattern alone (host only, no GPU needed, may be called before initialize): two

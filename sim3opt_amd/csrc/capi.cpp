@@ -628,6 +628,37 @@ int sim3opt_linearize(sim3opt_graph* g) {
   return engine_linearize(g->engine, g->err);
 }
 
+int sim3opt_debug_linearization_dims(sim3opt_graph* g, int32_t* n_active, int32_t* n_incidences) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!n_active || !n_incidences) return fail(g, SIM3OPT_ERR_ARG, "debug_linearization_dims: null argument");
+  if (!g->initialized || g->dirty)
+    return fail(g, SIM3OPT_ERR_STATE, "debug_linearization_dims: call sim3opt_initialize first");
+  engine_debug_linearization_dims(g->engine, n_active, n_incidences);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_debug_linearization(sim3opt_graph* g, double* J, double* w, int32_t* active, double* scratch,
+                                int32_t* incptr, int32_t* inc0, int32_t* inc1, int32_t* slot01, int32_t* slot10,
+                                double* trace, double* maxdiag) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!J || !w || !active || !scratch || !incptr || !inc0 || !inc1 || !slot01 || !slot10 || !trace || !maxdiag)
+    return fail(g, SIM3OPT_ERR_ARG, "debug_linearization: null argument");
+  if (!g->initialized || g->dirty)
+    return fail(g, SIM3OPT_ERR_STATE, "debug_linearization: call sim3opt_initialize first");
+  return engine_debug_linearization(g->engine, J, w, active, scratch, incptr, inc0, inc1, slot01, slot10, trace,
+                                    maxdiag, g->err);
+}
+
+int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32_t with_fail, int32_t grid,
+                         double* states_out, double* backup_out, double* chi2, double* scale) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!x) return fail(g, SIM3OPT_ERR_ARG, "debug_update: null step");
+  if (!states_out && !backup_out && !chi2 && !scale) return fail(g, SIM3OPT_ERR_ARG, "debug_update: every output is null");
+  if (!std::isfinite(lambda)) return fail(g, SIM3OPT_ERR_ARG, "debug_update: lambda is not finite");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_update: call sim3opt_initialize first");
+  return engine_debug_update(g->engine, x, lambda, with_fail != 0, grid, states_out, backup_out, chi2, scale, g->err);
+}
+
 int sim3opt_system_dims(const sim3opt_graph* g, int32_t* n_block_rows, int64_t* n_blocks) {
   if (!g || !g->initialized) return SIM3OPT_ERR_STATE;
   if (n_block_rows) *n_block_rows = g->structure.nb;

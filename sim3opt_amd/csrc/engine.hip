@@ -339,8 +339,9 @@ int Engine::pool_drain(std::string& err) {
 // ---- building blocks ----
 // scale_parts > 0: d_part_b holds that many partial sums of the trial's scale (k_scale): summed in the
 // same launch as chi2's
-int Engine::chi2(double* out, std::string& err, hipEvent_t before_fetch, int scale_parts) {
-  const int g = grid_for(e_hi - e_lo, WG);
+// grid > 0 (sim3opt_debug_update only): that many workgroups instead of the rule's
+int Engine::chi2(double* out, std::string& err, hipEvent_t before_fetch, int scale_parts, int grid) {
+  const int g = grid > 0 ? grid : grid_for(e_hi - e_lo, WG);
   if (has_kernel) hipLaunchKernelGGL(k_chi2<true>, dim3(g), dim3(WG), 0, stream, edge_args(), d_part_a);
   else hipLaunchKernelGGL(k_chi2<false>, dim3(g), dim3(WG), 0, stream, edge_args(), d_part_a);
   // (exact solver on one GPU: small systems, where the copy of the scalar block is a visible share of a trial)
@@ -394,6 +395,30 @@ int Engine::check_foreign_ranges(std::string& err) {
   return SIM3OPT_OK;
 }
 
+// the eight instantiations of the linearisation (DUMP: their read-out twins, lm_kernels.hpp)
+template <bool DUMP>
+static void launch_linearize(bool analytic, bool has_info, bool has_kernel, int g, hipStream_t stream, const LinArgs& A) {
+  if (analytic) {
+    if (has_info && has_kernel)
+      hipLaunchKernelGGL((k_linearize_analytic<true, true, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+    else if (has_info)
+      hipLaunchKernelGGL((k_linearize_analytic<true, false, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+    else if (has_kernel)
+      hipLaunchKernelGGL((k_linearize_analytic<false, true, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+    else
+      hipLaunchKernelGGL((k_linearize_analytic<false, false, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+  } else {
+    if (has_info && has_kernel)
+      hipLaunchKernelGGL((k_linearize_numeric<true, true, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+    else if (has_info)
+      hipLaunchKernelGGL((k_linearize_numeric<true, false, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+    else if (has_kernel)
+      hipLaunchKernelGGL((k_linearize_numeric<false, true, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+    else
+      hipLaunchKernelGGL((k_linearize_numeric<false, false, DUMP>), dim3(g), dim3(WG), 0, stream, A);
+  }
+}
+
 int Engine::linearize(std::string& err) {
   const sim3::Opts mo = mopts();
   const bool analytic = opt.jacobians == 1;  // closed form: no perturbation table
@@ -409,24 +434,9 @@ int Engine::linearize(std::string& err) {
             (const Sim3*)d_ptab, opt.dof_mask, d_sc};
   const int g = (n_active + EPB - 1) / EPB;
   if (g == 0) HIPCHK(hipMemsetAsync(&d_sc->maxdiag_bits, 0, sizeof(unsigned long long), stream));
-  if (g > 0 && analytic) {
-    if (has_info && has_kernel)
-      hipLaunchKernelGGL((k_linearize_analytic<true, true>), dim3(g), dim3(WG), 0, stream, A);
-    else if (has_info)
-      hipLaunchKernelGGL((k_linearize_analytic<true, false>), dim3(g), dim3(WG), 0, stream, A);
-    else if (has_kernel)
-      hipLaunchKernelGGL((k_linearize_analytic<false, true>), dim3(g), dim3(WG), 0, stream, A);
-    else
-      hipLaunchKernelGGL((k_linearize_analytic<false, false>), dim3(g), dim3(WG), 0, stream, A);
-  } else if (g > 0) {
-    if (has_info && has_kernel)
-      hipLaunchKernelGGL((k_linearize_numeric<true, true>), dim3(g), dim3(WG), 0, stream, A);
-    else if (has_info)
-      hipLaunchKernelGGL((k_linearize_numeric<true, false>), dim3(g), dim3(WG), 0, stream, A);
-    else if (has_kernel)
-      hipLaunchKernelGGL((k_linearize_numeric<false, true>), dim3(g), dim3(WG), 0, stream, A);
-    else
-      hipLaunchKernelGGL((k_linearize_numeric<false, false>), dim3(g), dim3(WG), 0, stream, A);
+  if (g > 0) {
+    if (lin_dump) launch_linearize<true>(analytic, has_info, has_kernel, g, stream, A);  // (sim3opt_debug_linearization)
+    else launch_linearize<false>(analytic, has_info, has_kernel, g, stream, A);
   }
   const int gdr = grid_for(r1 - r0, 4);
   hipLaunchKernelGGL(k_diag_reduce, dim3(gdr), dim3(WG), 0, stream, r0, r1,
@@ -719,6 +729,133 @@ int engine_linearize(Engine* e, std::string& err) {
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));
   return e->check_foreign_ranges(err);
+}
+
+// ---- diagnostic read-outs of the LM set-up and update kernels (include/sim3opt.h, "Diagnostic.") ----
+void engine_debug_linearization_dims(const Engine* e, int32_t* n_active, int32_t* n_incidences) {
+  if (n_active) *n_active = e->n_active;
+  if (n_incidences) *n_incidences = e->st.incptr[e->nb];
+}
+
+int engine_debug_linearization(Engine* e, double* J, double* w, int32_t* active, double* scratch, int32_t* incptr,
+                               int32_t* inc0, int32_t* inc1, int32_t* slot01, int32_t* slot10, double* trace,
+                               double* maxdiag, std::string& err) {
+  if (e->comm.active()) {
+    err = "debug_linearization: a partitioned graph holds this rank's share only (one GPU, please)";
+    return SIM3OPT_ERR_STATE;
+  }
+  const size_t na = (size_t)e->n_active, ninc = (size_t)e->st.incptr[e->nb], m = (size_t)e->ne;
+  double* d_dump = nullptr;
+  HIPCHK(dev_malloc((void**)&d_dump, sizeof(double) * 106 * std::max<size_t>(na, 1)));
+  const LinDump dump{d_dump, d_dump + 105 * std::max<size_t>(na, 1)};
+  const sim3opt_kernel_times kt0 = e->kt;
+  int rc = SIM3OPT_OK;
+  hipError_t le = hipStreamSynchronize(e->stream);  // (the symbol is written outside the stream)
+  if (le == hipSuccess) le = hipMemcpyToSymbol(HIP_SYMBOL(d_lin_dump), &dump, sizeof(LinDump));
+  if (le == hipSuccess) {
+    e->lin_dump = true;
+    rc = e->linearize(err);  // the launches of sim3opt_linearize, the linearisation kernel in its DUMP instantiation
+    e->lin_dump = false;
+    e->kt = kt0;
+  }
+  if (le == hipSuccess && rc == SIM3OPT_OK) le = hipStreamSynchronize(e->stream);
+  if (le == hipSuccess && rc == SIM3OPT_OK && na) {
+    le = hipMemcpy(J, dump.J, sizeof(double) * 105 * na, hipMemcpyDeviceToHost);
+    if (le == hipSuccess) le = hipMemcpy(w, dump.w, sizeof(double) * na, hipMemcpyDeviceToHost);
+  }
+  dev_free(d_dump);
+  if (rc) return rc;
+  if (le == hipSuccess && ninc) le = hipMemcpy(scratch, e->d_scratch, sizeof(double) * 35 * ninc, hipMemcpyDeviceToHost);
+  unsigned long long bits = 0;
+  if (le == hipSuccess) le = hipMemcpy(trace, &e->d_sc->trace, sizeof(double), hipMemcpyDeviceToHost);
+  if (le == hipSuccess) le = hipMemcpy(&bits, &e->d_sc->maxdiag_bits, sizeof(bits), hipMemcpyDeviceToHost);
+  if (le != hipSuccess) {
+    err = std::string("debug_linearization: ") + hipGetErrorString(le);
+    return SIM3OPT_ERR_HIP;
+  }
+  std::memcpy(maxdiag, &bits, sizeof(double));
+  // the index arrays as uploaded (one rank: the structure's own)
+  if (na) std::memcpy(active, e->st.active.data(), sizeof(int32_t) * na);
+  std::memcpy(incptr, e->st.incptr.data(), sizeof(int32_t) * ((size_t)e->nb + 1));
+  if (m) {
+    std::memcpy(inc0, e->st.inc0.data(), sizeof(int32_t) * m);
+    std::memcpy(inc1, e->st.inc1.data(), sizeof(int32_t) * m);
+    std::memcpy(slot01, e->st.slot01.data(), sizeof(int32_t) * m);
+    std::memcpy(slot10, e->st.slot10.data(), sizeof(int32_t) * m);
+  }
+  return SIM3OPT_OK;
+}
+
+int engine_debug_update(Engine* e, const double* x, double lambda, bool with_fail, int32_t grid, double* states_out,
+                        double* backup_out, double* chi2, double* scale, std::string& err) {
+  if (e->comm.active()) {
+    err = "debug_update: a partitioned graph holds this rank's share only (one GPU, please)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (!e->linearized) {
+    err = "debug_update: call sim3opt_linearize (or optimize) first: the scale needs b";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (with_fail && !e->use_direct) {
+    err = "debug_update: with_fail needs the exact solver (only its failure token reaches k_oplus)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (grid < 0 || grid > MAX_GRID) {
+    err = "debug_update: grid out of range";
+    return SIM3OPT_ERR_ARG;
+  }
+  // everything a trial's launches overwrite that a later call could see
+  HIPCHK(hipStreamSynchronize(e->stream));
+  DevScalars dev0;
+  const DevScalars host0 = *e->h_sc;
+  const sim3opt_kernel_times kt0 = e->kt;
+  const bool known0 = e->chi_known;
+  const double cache0 = e->chi_cache;
+  int64_t sched0[4];
+  for (int i = 0; i < 4; ++i) sched0[i] = e->sched_stats[i];
+  HIPCHK(hipMemcpy(&dev0, e->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
+  double* d_step = nullptr;
+  HIPCHK(dev_malloc((void**)&d_step, sizeof(double) * std::max<size_t>((size_t)e->n, 1)));
+  int rc = SIM3OPT_OK;
+  double chi = 0.0;
+  hipError_t le = hipMemcpy(d_step, x, sizeof(double) * (size_t)e->n, hipMemcpyHostToDevice);
+  if (le == hipSuccess && with_fail) {
+    const int32_t token = e->fail_token;  // what the factorisation of the current solve stores on a bad pivot
+    le = hipMemcpy(&e->d_sc->fail, &token, sizeof(int32_t), hipMemcpyHostToDevice);
+  }
+  if (le == hipSuccess) {  // the launches of an LM trial after its solve (Engine::optimize)
+    e->apply_step(d_step, true);
+    const int ge = grid > 0 ? grid : grid_for(7 * (int64_t)(e->r1 - e->r0), WG);
+    hipLaunchKernelGGL(k_scale, dim3(ge), dim3(WG), 0, e->stream, 7 * e->r0, 7 * e->r1, (const double*)d_step,
+                       (const double*)e->d_b, lambda, e->d_part_b);
+    le = hipGetLastError();
+    if (le == hipSuccess) rc = e->chi2(&chi, err, nullptr, ge, grid);
+  }
+  const double sc = e->h_sc->scale;
+  if (le == hipSuccess && rc == SIM3OPT_OK) le = hipStreamSynchronize(e->stream);
+  if (le == hipSuccess && rc == SIM3OPT_OK && states_out)
+    le = hipMemcpy(states_out, e->d_states, sizeof(Sim3) * (size_t)e->nv, hipMemcpyDeviceToHost);
+  if (le == hipSuccess && rc == SIM3OPT_OK && backup_out)
+    le = hipMemcpy(backup_out, e->d_backup, sizeof(Sim3) * (size_t)e->nv, hipMemcpyDeviceToHost);
+  if (le == hipSuccess) {  // (the backup was taken whatever followed it)
+    e->pop_states();
+    le = hipStreamSynchronize(e->stream);
+  }
+  if (le == hipSuccess) le = hipMemcpy(e->d_sc, &dev0, sizeof(DevScalars), hipMemcpyHostToDevice);
+  dev_free(d_step);
+  *e->h_sc = host0;
+  e->kt = kt0;
+  e->chi_known = known0;
+  e->chi_cache = cache0;
+  for (int i = 0; i < 4; ++i) e->sched_stats[i] = sched0[i];
+  if (rc) return rc;
+  if (le != hipSuccess) {
+    err = std::string("debug_update: ") + hipGetErrorString(le);
+    return SIM3OPT_ERR_HIP;
+  }
+  if (chi2) *chi2 = chi;
+  if (scale) *scale = sc;
+  return SIM3OPT_OK;
 }
 
 int engine_get_system(Engine* e, int32_t* rowptr, int32_t* colidx, double* values, double* b,

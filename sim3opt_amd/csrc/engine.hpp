@@ -67,6 +67,13 @@ int engine_amg_level_numbers(Engine* e, double lambda, int32_t level, int32_t* r
 int engine_amg_coarsest_inverse(Engine* e, double lambda, double* Ainv, std::string& err);
 int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, const double* r, double* z,
                          std::string& err);
+// diagnostic read-outs of the LM set-up and update kernels (one GPU; the solver's state is left as it was)
+void engine_debug_linearization_dims(const Engine* e, int32_t* n_active, int32_t* n_incidences);
+int engine_debug_linearization(Engine* e, double* J, double* w, int32_t* active, double* scratch, int32_t* incptr,
+                               int32_t* inc0, int32_t* inc1, int32_t* slot01, int32_t* slot10, double* trace,
+                               double* maxdiag, std::string& err);
+int engine_debug_update(Engine* e, const double* x, double lambda, bool with_fail, int32_t grid, double* states_out,
+                        double* backup_out, double* chi2, double* scale, std::string& err);
 // diagnostic read-outs of the PCG's operator (engine_pcg.hip)
 int engine_spmv_spans(Engine* e, int32_t* n_spans, int32_t* wrow, std::string& err);
 int engine_operator_apply(Engine* e, int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,

@@ -614,7 +614,7 @@ class Engine {
   // ---- building blocks ----
   // scale_parts > 0: d_part_b holds that many partial sums of the trial's scale (k_scale): summed in the
   // same launch as chi2's
-  int chi2(double* out, std::string& err, hipEvent_t before_fetch = nullptr, int scale_parts = 0);
+  int chi2(double* out, std::string& err, hipEvent_t before_fetch = nullptr, int scale_parts = 0, int grid = 0);
 
   // the perturbation table of the numeric Jacobians, re-evaluated when delta or the arithmetic options change
   Sim3* d_ptab = nullptr;
@@ -693,6 +693,7 @@ class Engine {
   int iter_begin(sim3opt_iter_stats& T, double& chi, std::string& err);  // stamp 0, chi2 (cached or not), linearise
   void iter_end(sim3opt_iter_stats& T, double chi, std::vector<sim3opt_iter_stats>& stats);  // cache chi, record T
   bool direct_rejected() const;  // after the caller's fetch: the exact factorisation met a non-positive pivot
+  bool lin_dump = false;  // linearize() launches the DUMP instantiation (sim3opt_debug_linearization sets d_lin_dump first)
   void apply_step(const double* x, bool push);  // k_oplus; push: the old estimates into d_backup first
   void pop_states();                            // k_copy_states from d_backup
 

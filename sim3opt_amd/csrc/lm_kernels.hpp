@@ -210,14 +210,29 @@ __global__ __launch_bounds__(64) void k_perturbation_table(double delta, sim3::O
   tab[t] = sim3::exp(xi, opts);
 }
 
+// sim3opt_debug_linearization: where the DUMP instantiations of the linearisation kernels leave what the Gram phase
+// consumed, per ACTIVE edge (position in LinArgs::active): J = the 15 x 7 array of s_J (14 columns, then e), w = the
+// robust weight.  Set (hipMemcpyToSymbol) before such a launch; the hot instantiations never read it.
+struct LinDump {
+  double* J;  // 105 per active edge
+  double* w;  // 1 per active edge
+};
+__device__ LinDump d_lin_dump;
+
 // The Gram phase of both linearisation kernels, entered after the Jacobian columns (J[0..13]) and e (J[14]) of
 // this half-wavefront's edge are in LDS: Omega (J | e), the robust weight w = rho'(e^T Omega e) (uniform over the
 // half-wavefront), the 119 Gram tasks, the plain stores.
 // (Every thread of the workgroup calls it: it holds the workgroup barriers.)
-template <bool HAS_INFO, bool HAS_KERNEL>
+// DUMP (diagnostic read-out only): J and w also go to d_lin_dump, slot `ai`; everything else, stores included, is
+// the hot instantiation's.
+template <bool HAS_INFO, bool HAS_KERNEL, bool DUMP = false>
 __device__ __forceinline__ void linearize_gram_store(const LinArgs& A, int edge, bool valid, int l,
-                                                     double (*J)[7], double (*O)[7], double (*G)[15]) {
+                                                     double (*J)[7], double (*O)[7], double (*G)[15], int ai = 0) {
   __syncthreads();
+  if (DUMP) {
+    if (valid)
+      for (int t = l; t < 105; t += 32) d_lin_dump.J[(size_t)105 * ai + t] = J[t / 7][t % 7];
+  }
   if (HAS_INFO) {
     if (valid) {
       const double* Om = A.info + (size_t)49 * edge;  // column-major
@@ -240,6 +255,9 @@ __device__ __forceinline__ void linearize_gram_store(const LinArgs& A, int edge,
       for (int r = 0; r < 7; ++r) chi += J[14][r] * OJ[14][r];
       robustify(A.kkind[edge], A.kdelta[edge], chi, rho, w);
     }
+  }
+  if (DUMP) {
+    if (valid && l == 0) d_lin_dump.w[ai] = w;
   }
   if (valid) {
     for (int t = l; t < 119; t += 32) {
@@ -274,7 +292,7 @@ __device__ __forceinline__ void linearize_gram_store(const LinArgs& A, int edge,
   }
 }
 
-template <bool HAS_INFO, bool HAS_KERNEL>
+template <bool HAS_INFO, bool HAS_KERNEL, bool DUMP = false>
 __global__ __launch_bounds__(WG) void k_linearize_numeric(LinArgs A) {
   __shared__ double s_in[EPB][24];
   __shared__ double s_J[EPB][15][7];                    // 14 Jacobian columns, column 14 = e
@@ -318,7 +336,7 @@ __global__ __launch_bounds__(WG) void k_linearize_numeric(LinArgs A) {
       s_J[es][l >> 1][r] = ((A.dof_mask >> ((l % 14) >> 1)) & 1) ? scalar * (e[r] - other) : 0.0;
     if (valid && l == 28) s_J[es][14][r] = e[r];
   }
-  linearize_gram_store<HAS_INFO, HAS_KERNEL>(A, edge, valid, l, s_J[es], HAS_INFO ? s_O[es] : s_J[es], s_G[es]);
+  linearize_gram_store<HAS_INFO, HAS_KERNEL, DUMP>(A, edge, valid, l, s_J[es], HAS_INFO ? s_O[es] : s_J[es], s_G[es], ai);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -333,7 +351,7 @@ __global__ __launch_bounds__(WG) void k_linearize_numeric(LinArgs A) {
 //   The node table is dead once summed: it shares LDS with the Jacobian / Gram arrays (the sums sit past it,
 //   where only the Gram array overlaps them, and that is written after they are read).
 // ------------------------------------------------------------------------------------------
-template <bool HAS_INFO, bool HAS_KERNEL>
+template <bool HAS_INFO, bool HAS_KERNEL, bool DUMP = false>
 __global__ __launch_bounds__(WG) void k_linearize_analytic(LinArgs A) {
   constexpr int NJ = EPB * 15 * 7, NO = HAS_INFO ? NJ : 7, NG = EPB * 14 * 15;
   constexpr int NS = sim3::JAC_SUMS + 13;  // per edge: the J_l blocks, then exp(e)
@@ -403,7 +421,7 @@ __global__ __launch_bounds__(WG) void k_linearize_analytic(LinArgs A) {
 #pragma unroll
     for (int r = 0; r < 7; ++r) s_J[es][l][r] = col[r];
   }
-  linearize_gram_store<HAS_INFO, HAS_KERNEL>(A, edge, valid, l, s_J[es], HAS_INFO ? s_O[es] : s_J[es], s_G[es]);
+  linearize_gram_store<HAS_INFO, HAS_KERNEL, DUMP>(A, edge, valid, l, s_J[es], HAS_INFO ? s_O[es] : s_J[es], s_G[es], ai);
 }
 
 // sim3opt_edge_jacobians: one lane per edge, the functions k_linearize_analytic runs, summed in the same order

@@ -203,6 +203,9 @@ SYMBOLS = {
     "sim3opt_edge_jacobians": (C.c_int, [_vp, _dp, _dp]),
     "sim3opt_sim3_edge_jacobian": (C.c_int, [_dp, _dp, _dp, C.POINTER(Options), _dp, _dp]),
     "sim3opt_linearize": (C.c_int, [_vp]),
+    "sim3opt_debug_linearization_dims": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_debug_linearization": (C.c_int, [_vp, _dp, _dp, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp, _dp]),
+    "sim3opt_debug_update": (C.c_int, [_vp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "sim3opt_system_dims": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64)]),
     "sim3opt_system_pattern": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64), _ip, _ip]),
     "sim3opt_get_system": (C.c_int, [_vp, _ip, _ip, _dp, _dp]),
@@ -659,6 +662,41 @@ class Graph:
 
     def linearize(self):
         self._chk(self._L.sim3opt_linearize(self._g))
+
+    def debug_linearization(self):
+        """Diagnostic: linearises (the DUMP instantiation of the linearisation kernel) and returns a dict: J
+        (n_active, 15, 7) = the 14 Jacobian columns and e as the Gram phase read them, w (n_active,), active, scratch
+        (n_incidences, 35), incptr, inc0, inc1, slot01, slot10, trace, maxdiag.  get_system() afterwards is the
+        system of linearize()."""
+        na, ni = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_debug_linearization_dims(self._g, C.byref(na), C.byref(ni)))
+        na, ni, m = na.value, ni.value, self.num_edges
+        nb, _ = self.system_dims()
+        d = dict(J=np.empty((na, 15, 7)), w=np.empty(na), active=np.empty(na, dtype=np.int32),
+                 scratch=np.empty((ni, 35)), incptr=np.empty(nb + 1, dtype=np.int32))
+        for k in ("inc0", "inc1", "slot01", "slot10"):
+            d[k] = np.empty(m, dtype=np.int32)
+        tr, mx = C.c_double(), C.c_double()
+        self._chk(self._L.sim3opt_debug_linearization(
+            self._g, _p(d["J"], _dp), _p(d["w"], _dp), _p(d["active"], _ip), _p(d["scratch"], _dp),
+            _p(d["incptr"], _ip), _p(d["inc0"], _ip), _p(d["inc1"], _ip), _p(d["slot01"], _ip), _p(d["slot10"], _ip),
+            C.byref(tr), C.byref(mx)))
+        d["trace"], d["maxdiag"] = tr.value, mx.value
+        return d
+
+    def debug_update(self, x, lam=0.0, fail=False, grid=0):
+        """Diagnostic: (states, backup, chi2, scale) of an LM trial with the step x (7 per block row) at damping lam;
+        the estimates are restored.  fail: with the exact solver's failure token set; grid: workgroups (= partial sums)
+        of the chi2 and scale reductions, 0 = a trial's own."""
+        nb, _ = self.system_dims()
+        xs = _f64(x).reshape(-1)
+        assert xs.shape[0] == 7 * nb
+        nv = self.num_vertices
+        st, bk = np.empty((nv, 8)), np.empty((nv, 8))
+        chi, sc = C.c_double(), C.c_double()
+        self._chk(self._L.sim3opt_debug_update(self._g, _p(xs, _dp), float(lam), int(bool(fail)), int(grid),
+                                               _p(st, _dp), _p(bk, _dp), C.byref(chi), C.byref(sc)))
+        return st, bk, chi.value, sc.value
 
     def system_dims(self):
         nb, nnzb = C.c_int32(), C.c_int64()
