@@ -385,6 +385,32 @@ int sim3opt_debug_linearization(sim3opt_graph* g, double* J, double* w, int32_t*
  * not all of them. */
 int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32_t with_fail, int32_t grid,
                          double* states_out, double* backup_out, double* chi2, double* scale);
+/* ---- read-out of the exact block Cholesky, its solve and the selected inversion, for tests ----
+ * Same contract as the read-outs above: nothing in the solver uses it; it runs the launches that exist (k_ldl_gather,
+ * k_ldl, k_selinv_pivots, k_selinv) and copies their buffers out; the system H / b, every solver scalar (the LM's fail
+ * word and its token included), the cached chi2, the statistics and sim3opt_get_kernel_times are bit for bit what they
+ * are without the call.  Refused with SIM3OPT_ERR_STATE before sim3opt_initialize, on a partitioned graph, for
+ * context 0 where the LM solves by PCG, and without a linearisation unless vals and b are both given; with
+ * SIM3OPT_ERR_ARG for a NULL output that the call would fill, another context, with_selinv on context 0, a lambda
+ * that is negative or not finite.  (sim3opt_version is unchanged.) */
+/* Diagnostic.  Sizes: block columns, blocks of L (and Z) of the context's plan, blocks of the system.  Context 1 is
+ * built here at first use, as sim3opt_marginals builds it. */
+int sim3opt_debug_factor_dims(sim3opt_graph* g, int32_t context, int32_t* n_block_rows, int64_t* n_blocks_L,
+                              int64_t* n_blocks);
+/* Diagnostic.  context 0: the LM solver's factorisation; 1: the marginals' (plan of sim3opt_direct_plan with the limit
+ * of sim3opt_marginal_plan, lists of the latter).  (H + lambda I) = L L^T from the last linearisation, or from vals
+ * (n_blocks x 49, layout and order of sim3opt_get_system) and / or b (7 per block row) where not NULL: they go to
+ * scratch device buffers, and afterwards the context gathers the real system again.  Outputs, in the plan's numbering,
+ * blocks column-major: Aperm (n_blocks_L x 49; the gathered blocks, no damping), bp (7 nb), L (n_blocks_L x 49), Dinv
+ * (nb x 49; L(j,j)^-1), y (7 nb; L y = bp), *fail_word (non-zero: a pivot that is not positive and finite); with_solve
+ * also xp (7 nb; L^T xp = y) and x (7 nb, by block rows of the system); with_selinv (context 1) also Z (n_blocks_L x 49,
+ * (H + lambda I)^-1 on the pattern of L) and *singular (a pivot below 1e-13 max |H_dd|; with injected vals the
+ * largest scalar diagonal entry of their diagonal blocks).  bord / brow (n_blocks_L each, may be NULL): per column the
+ * order in which the backward solve and the selected inversion take its blocks, and those blocks' rows. */
+int sim3opt_debug_factor(sim3opt_graph* g, int32_t context, double lambda, const double* vals, const double* b,
+                         int32_t with_solve, int32_t with_selinv, double* Aperm, double* bp, double* L, double* Dinv,
+                         double* y, double* xp, double* x, int32_t* fail_word, double* Z, int32_t* singular,
+                         int32_t* bord, int32_t* brow);
 /* dimensions of the block-CSR system: free block rows, stored 7x7 blocks */
 int sim3opt_system_dims(const sim3opt_graph* g, int32_t* n_block_rows, int64_t* n_blocks);
 /* the block-CSR pattern alone (host only, no GPU needed, may be called before initialize): two

@@ -659,6 +659,27 @@ int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32
   return engine_debug_update(g->engine, x, lambda, with_fail != 0, grid, states_out, backup_out, chi2, scale, g->err);
 }
 
+int sim3opt_debug_factor_dims(sim3opt_graph* g, int32_t context, int32_t* n_block_rows, int64_t* n_blocks_L,
+                              int64_t* n_blocks) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!n_block_rows || !n_blocks_L || !n_blocks) return fail(g, SIM3OPT_ERR_ARG, "debug_factor_dims: null argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_factor_dims: call sim3opt_initialize first");
+  return engine_debug_factor_dims(g->engine, context, n_block_rows, n_blocks_L, n_blocks, g->err);
+}
+
+int sim3opt_debug_factor(sim3opt_graph* g, int32_t context, double lambda, const double* vals, const double* b,
+                         int32_t with_solve, int32_t with_selinv, double* Aperm, double* bp, double* L, double* Dinv,
+                         double* y, double* xp, double* x, int32_t* fail_word, double* Z, int32_t* singular,
+                         int32_t* bord, int32_t* brow) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!Aperm || !bp || !L || !Dinv || !y || !fail_word || (with_solve && (!xp || !x)) ||
+      (with_selinv && (!Z || !singular)))
+    return fail(g, SIM3OPT_ERR_ARG, "debug_factor: null argument");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_factor: call sim3opt_initialize first");
+  return engine_debug_factor(g->engine, context, lambda, vals, b, with_solve != 0, with_selinv != 0, Aperm, bp, L, Dinv,
+                             y, xp, x, fail_word, Z, singular, bord, brow, g->err);
+}
+
 int sim3opt_system_dims(const sim3opt_graph* g, int32_t* n_block_rows, int64_t* n_blocks) {
   if (!g || !g->initialized) return SIM3OPT_ERR_STATE;
   if (n_block_rows) *n_block_rows = g->structure.nb;

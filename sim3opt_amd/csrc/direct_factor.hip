@@ -170,6 +170,25 @@ void BlockLdl::cov_pairs(const int32_t* pa, const int32_t* pb, const int32_t* pl
     hipLaunchKernelGGL(k_cov_pairs, dim3((np + COV_NW - 1) / COV_NW), dim3(WG), 0, stream, C, pa, pb, plen, np, out);
 }
 
+hipError_t BlockLdl::debug_read(double* Aperm, double* bp, double* L, double* Dinv, double* y, double* xp,
+                                double* Z) const {
+  const LdlArgs& A = d_->A;
+  const size_t nL = (size_t)plan_.nL, nb = (size_t)plan_.nb;
+  hipError_t e = hipSuccess;
+  auto get = [&](double* dst, const double* src, size_t count) {
+    if (e == hipSuccess && dst && src && count) e = hipMemcpy(dst, src, sizeof(double) * count, hipMemcpyDeviceToHost);
+  };
+  get(Aperm, A.Aperm, 49 * nL); get(bp, A.bp, 7 * nb); get(L, A.L, 49 * nL); get(Dinv, A.Dinv, 49 * nb);
+  get(y, A.y, 7 * nb); get(xp, A.xp, 7 * nb); get(Z, d_->S.Z, 49 * nL);
+  return e;
+}
+
+void BlockLdl::debug_forget() {
+  LdlArgs& A = d_->A;
+  A.vals = nullptr; A.b = nullptr; A.x = nullptr; A.fail = nullptr;
+  d_->S.maxdiag_bits = nullptr; d_->S.singular = nullptr;
+}
+
 void BlockLdl::release() {
   for (void* p : owned_) dev_free(p);
   owned_.clear();

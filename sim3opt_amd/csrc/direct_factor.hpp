@@ -54,6 +54,12 @@ class BlockLdl {
   // out[p] = sum_t W[pa[p] + t]^T W[pb[p] + t], t < plen[p] ascending (device arrays of np)
   void cov_pairs(const int32_t* pa, const int32_t* pb, const int32_t* plen, int32_t np, double* W, int32_t wblocks,
                  double* out, hipStream_t stream);
+  // Diagnostic (sim3opt_debug_factor): host copies of the buffers as the last gather / factor / selinv left them; the
+  // caller has synchronised.  A NULL pointer is skipped; Z only with the selected inversion's plan.
+  hipError_t debug_read(double* Aperm, double* bp, double* L, double* Dinv, double* y, double* xp, double* Z) const;
+  // ... and when the caller's scratch buffers go: the argument blocks forget every per-call pointer (values, b, x,
+  // fail word, max |H_dd|, singular flag), so that a launch without a new gather / factor / selinv cannot reach them
+  void debug_forget();
   void release();  // frees everything (the caller has synchronised) and forgets the plan
 
  private:

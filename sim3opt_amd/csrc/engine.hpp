@@ -74,6 +74,12 @@ int engine_debug_linearization(Engine* e, double* J, double* w, int32_t* active,
                                double* maxdiag, std::string& err);
 int engine_debug_update(Engine* e, const double* x, double lambda, bool with_fail, int32_t grid, double* states_out,
                         double* backup_out, double* chi2, double* scale, std::string& err);
+// diagnostic read-out of the exact block Cholesky, its solve and the selected inversion (engine_direct.hip)
+int engine_debug_factor_dims(Engine* e, int32_t context, int32_t* nb, int64_t* nL, int64_t* nnzb, std::string& err);
+int engine_debug_factor(Engine* e, int32_t context, double lambda, const double* vals, const double* b, bool with_solve,
+                        bool with_selinv, double* Aperm, double* bp, double* L, double* Dinv, double* y, double* xp,
+                        double* x, int32_t* fail, double* Z, int32_t* singular, int32_t* bord, int32_t* brow,
+                        std::string& err);
 // diagnostic read-outs of the PCG's operator (engine_pcg.hip)
 int engine_spmv_spans(Engine* e, int32_t* n_spans, int32_t* wrow, std::string& err);
 int engine_operator_apply(Engine* e, int32_t nrhs, const double* lambda, const double* p, const double* rvec, double* q,

@@ -342,6 +342,137 @@ int Engine::gate_edges(double lambda, int32_t n, const int32_t* v0, const int32_
   return SIM3OPT_OK;
 }
 
+// ---- diagnostic read-out of the factorisation (include/sim3opt.h, sim3opt_debug_factor) ----
+// The launches are BlockLdl's own -- gather, factor, selinv -- on scratch copies of injected values, with a fail word,
+// a singular flag, an x and a max |H_dd| of the call's own: d_vals, d_b, d_x, the DevScalars, fail_token, the cached
+// chi2, kt and the schedule counters are never written.  What the call does overwrite is the context's Aperm / bp (put
+// back by a gather of the real system after injected values) and its L, Dinv, y, xp, Z, which every user recomputes
+// before reading them.
+int Engine::debug_factor(int32_t context, double lambda, const double* vals, const double* b, bool with_solve,
+                         bool with_selinv, double* Aperm, double* bp, double* L, double* Dinv, double* y, double* xp,
+                         double* x, int32_t* fail, double* Z, int32_t* singular, int32_t* bord, int32_t* brow,
+                         std::string& err) {
+  const std::string pre = "debug_factor: ";
+  if (comm.active()) {
+    err = pre + "a partitioned graph holds this rank's share only (one GPU, please)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (context != 0 && context != 1) {
+    err = pre + "context must be 0 (the LM's solver) or 1 (the marginals')";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (context == 0 && with_selinv) {
+    err = pre + "the selected inversion belongs to context 1 (the LM's factor has no plan for it)";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (!(lambda >= 0.0) || !(lambda < DBL_MAX)) {
+    err = pre + "lambda must be finite and >= 0";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (context == 0 && !use_direct) {
+    err = pre + "context 0 needs the exact solver (this graph's LM solves by PCG)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if ((!vals || !b) && !linearized) {
+    err = pre + "call sim3opt_linearize (or optimize) first, or inject both vals and b";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (context == 1 && !marg_factor.ready()) {
+    int rc = marginal_init(err);
+    if (rc) return rc;
+  }
+  BlockLdl& F = context == 0 ? lm_factor : marg_factor;
+  const DirectPlan& P = F.plan();
+  HIPCHK(hipStreamSynchronize(stream));
+  // scratch: [vals | b | x | max |H_dd| bits | fail, singular]
+  const size_t nv = vals ? (size_t)49 * nnzb : 0, nbv = b ? (size_t)n : 0, nx = (size_t)n;
+  double* d_buf = nullptr;
+  HIPCHK(dev_malloc((void**)&d_buf, sizeof(double) * (nv + nbv + nx + 2)));
+  double *d_v = d_buf, *d_bb = d_buf + nv, *d_xs = d_bb + nbv;
+  unsigned long long* d_bits = reinterpret_cast<unsigned long long*>(d_xs + nx);
+  int32_t* d_flags = reinterpret_cast<int32_t*>(d_bits + 1);
+  hipError_t e = hipMemsetAsync(d_xs, 0, sizeof(double) * (nx + 2), stream);
+  if (e == hipSuccess && vals) e = hipMemcpyAsync(d_v, vals, sizeof(double) * nv, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && b) e = hipMemcpyAsync(d_bb, b, sizeof(double) * nbv, hipMemcpyHostToDevice, stream);
+  const unsigned long long* bits_src = &d_sc->maxdiag_bits;
+  unsigned long long hbits = 0;
+  if (e == hipSuccess && with_selinv && vals) {
+    // max |H_dd| of the injected diagonal blocks (the first block of a row), as k_diag_reduce would report it
+    double m = 0.0;
+    for (int32_t i = 0; i < nb; ++i)
+      for (int d = 0; d < 7; ++d) m = std::max(m, std::fabs(vals[(size_t)49 * st.rowptr[i] + 8 * d]));
+    std::memcpy(&hbits, &m, sizeof(double));
+    e = hipMemcpyAsync(d_bits, &hbits, sizeof(hbits), hipMemcpyHostToDevice, stream);
+    bits_src = d_bits;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (the uploads read the caller's and this frame's memory)
+  if (e == hipSuccess) {
+    F.gather(vals ? d_v : d_vals, b ? d_bb : d_b, stream);
+    e = F.factor(lambda, d_flags, 1, with_solve ? d_xs : nullptr, stream);
+  }
+  if (e == hipSuccess && with_selinv) {
+    F.selinv(bits_src, d_flags + 1, stream, true);
+    e = hipGetLastError();
+  }
+  int32_t hflags[2] = {0, 0};
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e == hipSuccess) e = F.debug_read(Aperm, bp, L, Dinv, y, with_solve ? xp : nullptr, with_selinv ? Z : nullptr);
+  if (e == hipSuccess && with_solve) e = hipMemcpy(x, d_xs, sizeof(double) * nx, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost);
+  // the argument blocks point into the scratch buffer: forget that before it goes (every user sets the pointers
+  // again -- gather, factor, selinv -- before it launches) ...
+  const hipError_t es = hipStreamSynchronize(stream);
+  F.debug_forget();
+  // ... and the context starts every later trial from the real system's blocks again
+  if ((vals || b) && linearized && es == hipSuccess) {
+    F.gather(d_vals, d_b, stream);
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+  }
+  dev_free(d_buf);
+  if (e != hipSuccess) {
+    err = pre + hipGetErrorString(e);
+    return SIM3OPT_ERR_HIP;
+  }
+  *fail = hflags[0];
+  if (with_selinv) *singular = hflags[1];
+  if (bord) std::memcpy(bord, P.bord.data(), sizeof(int32_t) * P.bord.size());
+  if (brow) std::memcpy(brow, P.brow.data(), sizeof(int32_t) * P.brow.size());
+  return SIM3OPT_OK;
+}
+
+int engine_debug_factor_dims(Engine* e, int32_t context, int32_t* nb, int64_t* nL, int64_t* nnzb, std::string& err) {
+  if (e->comm.active()) {
+    err = "debug_factor_dims: a partitioned graph holds this rank's share only (one GPU, please)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (context != 0 && context != 1) {
+    err = "debug_factor_dims: context must be 0 (the LM's solver) or 1 (the marginals')";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (context == 0 && !e->use_direct) {
+    err = "debug_factor_dims: context 0 needs the exact solver (this graph's LM solves by PCG)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (context == 1 && !e->marg_factor.ready()) {
+    int rc = e->marginal_init(err);
+    if (rc) return rc;
+  }
+  const DirectPlan& P = (context == 0 ? e->lm_factor : e->marg_factor).plan();
+  *nb = P.nb;
+  *nL = P.nL;
+  *nnzb = e->nnzb;
+  return SIM3OPT_OK;
+}
+
+int engine_debug_factor(Engine* e, int32_t context, double lambda, const double* vals, const double* b, bool with_solve,
+                        bool with_selinv, double* Aperm, double* bp, double* L, double* Dinv, double* y, double* xp,
+                        double* x, int32_t* fail, double* Z, int32_t* singular, int32_t* bord, int32_t* brow,
+                        std::string& err) {
+  return e->debug_factor(context, lambda, vals, b, with_solve, with_selinv, Aperm, bp, L, Dinv, y, xp, x, fail, Z,
+                         singular, bord, brow, err);
+}
+
 int engine_marginals(Engine* e, double lambda, int32_t n, const int32_t* row_a, const int32_t* row_b, double* cov,
                      std::string& err) {
   return e->marginals(lambda, n, row_a, row_b, cov, err);

@@ -543,6 +543,12 @@ class Engine {
   // caller together with the trial's chi2: no extra round trip).
   int direct_solve(double lambda, std::string& err);
 
+  // Diagnostic (sim3opt_debug_factor): gather, factor and, when asked, the selected inversion of context 0 (lm_factor)
+  // or 1 (marg_factor) on the last linearisation or on injected values, read out; see include/sim3opt.h
+  int debug_factor(int32_t context, double lambda, const double* vals, const double* b, bool with_solve,
+                   bool with_selinv, double* Aperm, double* bp, double* L, double* Dinv, double* y, double* xp, double* x,
+                   int32_t* fail, double* Z, int32_t* singular, int32_t* bord, int32_t* brow, std::string& err);
+
   // ---- marginal covariances: blocks of (H + lambda I)^-1 by a selected inversion (selinv.cpp,
   // selinv_kernels.hpp) ----
   // A context of its own -- plan, factor, flag -- whatever linear solver the LM uses, built at the first

@@ -206,6 +206,9 @@ SYMBOLS = {
     "sim3opt_debug_linearization_dims": (C.c_int, [_vp, _ip, _ip]),
     "sim3opt_debug_linearization": (C.c_int, [_vp, _dp, _dp, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp, _dp]),
     "sim3opt_debug_update": (C.c_int, [_vp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "sim3opt_debug_factor_dims": (C.c_int, [_vp, C.c_int32, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sim3opt_debug_factor": (C.c_int, [_vp, C.c_int32, C.c_double, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
+                                       _dp, _dp, _dp, _ip, _dp, _ip, _ip, _ip]),
     "sim3opt_system_dims": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64)]),
     "sim3opt_system_pattern": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64), _ip, _ip]),
     "sim3opt_get_system": (C.c_int, [_vp, _ip, _ip, _dp, _dp]),
@@ -697,6 +700,40 @@ class Graph:
         self._chk(self._L.sim3opt_debug_update(self._g, _p(xs, _dp), float(lam), int(bool(fail)), int(grid),
                                                _p(st, _dp), _p(bk, _dp), C.byref(chi), C.byref(sc)))
         return st, bk, chi.value, sc.value
+
+    def debug_factor(self, context=0, lam=0.0, vals=None, b=None, solve=True, selinv=False):
+        """Diagnostic: the exact block Cholesky of context 0 (the LM's solver) or 1 (the marginals') on the last
+        linearisation, or on injected vals (nnzb, 7, 7) [k, r, c] / b (7 nb), read out as a dict in the plan's
+        numbering, blocks [s, r, c]: Aperm, bp, L, Dinv, y, fail, bord, brow; with solve xp and x (by block rows of
+        the system); with selinv (context 1) Z and singular."""
+        nb, nL, nz = C.c_int32(), C.c_int64(), C.c_int64()
+        self._chk(self._L.sim3opt_debug_factor_dims(self._g, int(context), C.byref(nb), C.byref(nL), C.byref(nz)))
+        nb, nL, nz = nb.value, nL.value, nz.value
+        v = bb = None
+        if vals is not None:
+            v = _f64(np.asarray(vals).reshape(nz, 7, 7).transpose(0, 2, 1)).reshape(-1)
+        if b is not None:
+            bb = _f64(b).reshape(-1)
+            assert bb.shape[0] == 7 * nb
+        d = dict(Aperm=np.empty((nL, 49)), bp=np.empty((nb, 7)), L=np.empty((nL, 49)), Dinv=np.empty((nb, 49)),
+                 y=np.empty((nb, 7)), xp=np.empty((nb, 7)), x=np.empty((nb, 7)), Z=np.empty((nL if selinv else 0, 49)),
+                 bord=np.empty(nL, dtype=np.int32), brow=np.empty(nL, dtype=np.int32))
+        fw, sg = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_debug_factor(
+            self._g, int(context), float(lam), _p(v, _dp), _p(bb, _dp), int(bool(solve)), int(bool(selinv)),
+            _p(d["Aperm"], _dp), _p(d["bp"], _dp), _p(d["L"], _dp), _p(d["Dinv"], _dp), _p(d["y"], _dp),
+            _p(d["xp"], _dp), _p(d["x"], _dp), C.byref(fw), _p(d["Z"], _dp) if selinv else None, C.byref(sg),
+            _p(d["bord"], _ip), _p(d["brow"], _ip)))
+        for k in ("Aperm", "L", "Dinv", "Z"):
+            d[k] = d[k].reshape(-1, 7, 7).transpose(0, 2, 1).copy()
+        if not solve:
+            del d["xp"], d["x"]
+        if not selinv:
+            del d["Z"]
+        else:
+            d["singular"] = sg.value
+        d["fail"] = fw.value
+        return d
 
     def system_dims(self):
         nb, nnzb = C.c_int32(), C.c_int64()
