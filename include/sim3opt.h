@@ -665,6 +665,12 @@ int sim3opt_local_rows(const sim3opt_graph* g, int32_t* begin, int32_t* end);
  * Called automatically when the last sim3opt_graph / sim3opt_ba handle of the process is destroyed;
  * call it yourself before allocating large device buffers of your own next to a live handle. */
 void sim3opt_release_device_cache(void);
+/* Diagnostic.  out = {blocks, bytes} of device memory the library has handed to its handles and calls and not got
+ * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch of the process, on all devices; bytes as the block
+ * cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
+ * that creates no handle and initialises none is what "this call keeps no device memory" means
+ * (tests/test_gpu_device_memory.py). */
+void sim3opt_device_memory_in_use(int64_t out[2]);
 
 /* ---- reference-format I/O (host C++; the callers either side of the path) ---- */
 /* Builds the graph of testDirectSim3Optimization                   kitti_surf.cpp:562-670

@@ -1,9 +1,13 @@
-"""Compares the gfx950 code of named kernels between two device assembly listings (parent and head of a change that
+"""Compares the gfx950 code of named kernels (or, with --all, of every kernel) between two device assembly listings (parent and head of a change that
 must leave the hot path alone): per kernel the instruction stream (local labels renumbered by order of appearance, so
 that a function's place in the file does not show) and the resource figures of its .amdhsa_kernel block.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -S --offload-device-only <unit>.hip -o <listing>.s
     python scripts/compare_kernel_code.py parent.s head.s k_linearize_numeric k_diag_reduce ...
+    python scripts/compare_kernel_code.py --all parent.s head.s
+
+--all compares every kernel found in either listing, the read-out twins `k<a, b, true>` included, under its full
+demangled name: for a change that must leave the whole unit's device code alone.
 
 Prints a markdown table; exit status 1 if a kernel differs or is missing on either side."""
 import hashlib
@@ -57,16 +61,23 @@ def short(name):
 
 
 def main():
-    a, b, want = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args = [x for x in sys.argv[1:] if x != "--all"]
+    everything = len(args) < len(sys.argv) - 1
+    a, b, want = args[0], args[1], args[2:]
     (ba, ma, ta), (bb, mb, tb) = kernels(a), kernels(b)
+    # (only what has a .amdhsa_kernel block is a kernel: device functions that were not inlined are left out)
+    ba = {s: c for s, c in ba.items() if s in ma}
+    bb = {s: c for s, c in bb.items() if s in mb}
     names = demangle(sorted(set(ba) | set(bb)))
-    sa = {short(names[s]): s for s in ba}
-    sb = {short(names[s]): s for s in bb}
+    label = (lambda nm: nm.replace("sim3opt::", "").replace("void ", "")) if everything else short
+    sa = {label(names[s]): s for s in ba}
+    sb = {label(names[s]): s for s in bb}
     bad = 0
     print("| kernel | parent VGPR / SGPR / scratch / LDS / occupancy / code bytes | head | instruction stream |")
     print("|---|---|---|---|")
     for nm in sorted(set(sa) | set(sb)):
-        if not any(nm == w or nm.startswith(w + "<") for w in want) or re.search(r"<\w+, \w+, true>$", nm):
+        if not everything and (not any(nm == w or nm.startswith(w + "<") for w in want)
+                               or re.search(r"<\w+, \w+, true>$", nm)):
             continue
         if nm not in sa or nm not in sb:
             print(f"| `{nm}` | {'missing' if nm not in sa else ''} | {'missing' if nm not in sb else ''} | - |")

@@ -48,15 +48,6 @@
 
 namespace sim3opt_bundle {
 
-#define BA_HIPCHK(call)                                                     \
-  do {                                                                      \
-    hipError_t e_ = (call);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);              \
-      return SIM3OPT_ERR_HIP;                                               \
-    }                                                                       \
-  } while (0)
-
 constexpr int WG = 256;
 
 struct Cam {  // T_w2c: unit quaternion (x y z w) and translation; 8th double pads to 64 bytes
@@ -513,7 +504,8 @@ struct Problem {
   // device
   bool ready = false;
   hipStream_t stream = nullptr;
-  std::vector<void*> owned;
+  sim3opt::DevArena mem;  // every device block of initialize() (the library's block cache: an out-of-memory hipMalloc
+                          // elsewhere flushes it)
   Cam *d_cams = nullptr, *d_cams_bk = nullptr;
   double *d_pts = nullptr, *d_pts_bk = nullptr, *d_uv = nullptr, *d_lin = nullptr, *d_Z = nullptr;
   double *d_Hinv = nullptr, *d_bp = nullptr, *d_pdmax = nullptr, *d_cdmax = nullptr;
@@ -533,9 +525,7 @@ struct Problem {
   void release() {
     if (stream) (void)hipStreamSynchronize(stream);
     direct.release();
-    for (void* p : owned)
-      if (p) sim3opt::dev_free(p);  // (the library's block cache: an out-of-memory hipMalloc elsewhere flushes it)
-    owned.clear();
+    mem.release();
     if (h_sc) (void)hipHostFree(h_sc);
     h_sc = nullptr;
     if (stream) (void)hipStreamDestroy(stream);
@@ -546,19 +536,10 @@ struct Problem {
   int np() const { return (int)(pts.size() / 3); }
   int no() const { return (int)oc.size(); }
 
+  // (synchronous copies and memsets on the null stream: initialize() ends with a device-wide synchronisation)
   template <typename T>
-  int up(T*& d, const std::vector<T>& h) {
-    BA_HIPCHK(sim3opt::dev_malloc((void**)&d, sizeof(T) * std::max<size_t>(h.size(), 1)));
-    owned.push_back(d);
-    if (!h.empty()) BA_HIPCHK(hipMemcpy(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    return SIM3OPT_OK;
-  }
-  int alloc(double*& d, size_t n) {
-    BA_HIPCHK(sim3opt::dev_malloc((void**)&d, sizeof(double) * std::max<size_t>(n, 1)));
-    owned.push_back(d);
-    BA_HIPCHK(hipMemset(d, 0, sizeof(double) * std::max<size_t>(n, 1)));
-    return SIM3OPT_OK;
-  }
+  hipError_t up(T*& d, const std::vector<T>& h) { return mem.upload(d, h, nullptr, nullptr); }
+  hipError_t alloc(double*& d, size_t n) { return mem.alloc(d, n, nullptr); }
 
   int initialize() {
     release();
@@ -569,7 +550,7 @@ struct Problem {
     }
     if (opt.device >= 0) {
       if (opt.device >= ndev) { err = "device ordinal out of range"; return SIM3OPT_ERR_ARG; }
-      BA_HIPCHK(hipSetDevice(opt.device));
+      HIPCHK(hipSetDevice(opt.device));
     }
     const int NC = nc(), NP = np(), NO = no();
     if (NC < 1 || NP < 1 || NO < 1) { err = "empty problem"; return SIM3OPT_ERR_STATE; }
@@ -620,20 +601,18 @@ struct Problem {
     }
     for (int c = 0; c < NC; ++c) rptr[c + 1] = std::max(rptr[c + 1], rptr[c]);
     nblk = (int32_t)brow.size();
-    BA_HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    int rc;
-#define BCHK(call) do { rc = (call); if (rc) return rc; } while (0)
-    BCHK(up(d_cams, cams));
-    BA_HIPCHK(sim3opt::dev_malloc((void**)&d_cams_bk, sizeof(Cam) * NC)); owned.push_back(d_cams_bk);
-    BCHK(up(d_pts, pts));
-    BCHK(alloc(d_pts_bk, 3 * (size_t)NP));
-    BCHK(up(d_uv, uv));
-    BCHK(up(d_oc, oc)); BCHK(up(d_op, op));
-    BCHK(up(d_pptr, pptr)); BCHK(up(d_pobs, pobs)); BCHK(up(d_cptr, cptr)); BCHK(up(d_cobs, cobs));
-    BCHK(up(d_brow, brow)); BCHK(up(d_bcol, bcol)); BCHK(up(d_sptr, sptr)); BCHK(up(d_sa, sa)); BCHK(up(d_sb, sb));
-    BCHK(up(d_rptr, rptr));
+    HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIPCHK(up(d_cams, cams));
+    HIPCHK(mem.raw(d_cams_bk, (size_t)NC));
+    HIPCHK(up(d_pts, pts));
+    HIPCHK(alloc(d_pts_bk, 3 * (size_t)NP));
+    HIPCHK(up(d_uv, uv));
+    HIPCHK(up(d_oc, oc)); HIPCHK(up(d_op, op));
+    HIPCHK(up(d_pptr, pptr)); HIPCHK(up(d_pobs, pobs)); HIPCHK(up(d_cptr, cptr)); HIPCHK(up(d_cobs, cobs));
+    HIPCHK(up(d_brow, brow)); HIPCHK(up(d_bcol, bcol)); HIPCHK(up(d_sptr, sptr)); HIPCHK(up(d_sa, sa)); HIPCHK(up(d_sb, sb));
+    HIPCHK(up(d_rptr, rptr));
     cam_fixed.resize(NC, 0);
-    BCHK(up(d_fixed, cam_fixed));
+    HIPCHK(up(d_fixed, cam_fixed));
     // the reduced camera system's factorisation plan (nested dissection, level schedule: direct.hpp)
     if (opt.linear_solver != 0) {
       int64_t max_pairs = 8000000;
@@ -645,7 +624,7 @@ struct Problem {
       const int32_t subtree = std::max(16, NC / 6);
       std::string why;
       if (direct.build_plan(NC, rptr.data(), bcol.data(), max_pairs, subtree, "SIM3OPT_BA", false, why)) {
-        BA_HIPCHK(direct.upload(stream));  // (synchronised below)
+        HIPCHK(direct.upload(stream));  // (synchronised below)
         const sim3opt::DirectPlan& P = direct.plan();
         if (opt.verbose)
           std::fprintf(stderr, "sim3opt ba: exact block Cholesky of the reduced system: %d cameras, %lld blocks in L, "
@@ -658,22 +637,20 @@ struct Problem {
         std::fprintf(stderr, "sim3opt ba: no exact factorisation (%s): PCG\n", why.c_str());
       }
     }
-    BCHK(alloc(d_lin, 20 * (size_t)NO)); BCHK(alloc(d_Z, 18 * (size_t)NO));
-    BCHK(alloc(d_Hinv, 9 * (size_t)NP)); BCHK(alloc(d_bp, 3 * (size_t)NP)); BCHK(alloc(d_pdmax, NP));
-    BCHK(alloc(d_cdmax, 7 * (size_t)NC));
-    BCHK(alloc(d_S, 49 * (size_t)nblk)); BCHK(alloc(d_g, 7 * (size_t)NC)); BCHK(alloc(d_bc, 7 * (size_t)NC));
-    BCHK(alloc(d_xc, 7 * (size_t)NC)); BCHK(alloc(d_xp, 3 * (size_t)NP));
-    BCHK(alloc(d_r, 7 * (size_t)NC)); BCHK(alloc(d_z, 7 * (size_t)NC)); BCHK(alloc(d_p, 7 * (size_t)NC));
-    BCHK(alloc(d_q, 7 * (size_t)NC)); BCHK(alloc(d_Dinv, 49 * (size_t)NC));
+    HIPCHK(alloc(d_lin, 20 * (size_t)NO)); HIPCHK(alloc(d_Z, 18 * (size_t)NO));
+    HIPCHK(alloc(d_Hinv, 9 * (size_t)NP)); HIPCHK(alloc(d_bp, 3 * (size_t)NP)); HIPCHK(alloc(d_pdmax, NP));
+    HIPCHK(alloc(d_cdmax, 7 * (size_t)NC));
+    HIPCHK(alloc(d_S, 49 * (size_t)nblk)); HIPCHK(alloc(d_g, 7 * (size_t)NC)); HIPCHK(alloc(d_bc, 7 * (size_t)NC));
+    HIPCHK(alloc(d_xc, 7 * (size_t)NC)); HIPCHK(alloc(d_xp, 3 * (size_t)NP));
+    HIPCHK(alloc(d_r, 7 * (size_t)NC)); HIPCHK(alloc(d_z, 7 * (size_t)NC)); HIPCHK(alloc(d_p, 7 * (size_t)NC));
+    HIPCHK(alloc(d_q, 7 * (size_t)NC)); HIPCHK(alloc(d_Dinv, 49 * (size_t)NC));
     grid_chi = std::max(1, std::min(1024, (NO + WG - 1) / WG));
-    BCHK(alloc(d_pa, 1024)); BCHK(alloc(d_pb, 1024)); BCHK(alloc(d_pc, 1024));
-#undef BCHK
-    BA_HIPCHK(sim3opt::dev_malloc((void**)&d_sc, sizeof(Scal))); owned.push_back(d_sc);
-    BA_HIPCHK(hipMemset(d_sc, 0, sizeof(Scal)));
-    BA_HIPCHK(hipHostMalloc((void**)&h_sc, sizeof(Scal)));
+    HIPCHK(alloc(d_pa, 1024)); HIPCHK(alloc(d_pb, 1024)); HIPCHK(alloc(d_pc, 1024));
+    HIPCHK(mem.alloc(d_sc, 1, nullptr));
+    HIPCHK(hipHostMalloc((void**)&h_sc, sizeof(Scal)));
     // the uploads and memsets above ran on the null stream, the kernels run on a non-blocking one:
     // order them (engine.hip ends its init the same way)
-    BA_HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipDeviceSynchronize());
     ready = true;
     return SIM3OPT_OK;
   }
@@ -683,8 +660,8 @@ struct Problem {
                    1.0 / (opt.pixel_noise * opt.pixel_noise), opt.huber_delta};
   }
   int fetch() {
-    BA_HIPCHK(hipMemcpyAsync(h_sc, d_sc, sizeof(Scal), hipMemcpyDeviceToHost, stream));
-    BA_HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpyAsync(h_sc, d_sc, sizeof(Scal), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
     return SIM3OPT_OK;
   }
   int chi2(double* out) {
@@ -692,7 +669,7 @@ struct Problem {
     hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(WG), 0, stream, (const double*)d_pa, grid_chi,
                        (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)nullptr, 0,
                        (const double*)nullptr, 0, d_sc);
-    BA_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     int rc = fetch();
     if (rc) return rc;
     *out = h_sc->chi2;
@@ -706,13 +683,13 @@ struct Problem {
     hipLaunchKernelGGL(k_ba_obs, dim3(gobs()), dim3(WG), 0, stream, oargs(), d_lin);
   }
   int backup() {
-    BA_HIPCHK(hipMemcpyAsync(d_cams_bk, d_cams, sizeof(Cam) * nc(), hipMemcpyDeviceToDevice, stream));
-    BA_HIPCHK(hipMemcpyAsync(d_pts_bk, d_pts, sizeof(double) * 3 * np(), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_cams_bk, d_cams, sizeof(Cam) * nc(), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_pts_bk, d_pts, sizeof(double) * 3 * np(), hipMemcpyDeviceToDevice, stream));
     return SIM3OPT_OK;
   }
   int restore() {
-    BA_HIPCHK(hipMemcpyAsync(d_cams, d_cams_bk, sizeof(Cam) * nc(), hipMemcpyDeviceToDevice, stream));
-    BA_HIPCHK(hipMemcpyAsync(d_pts, d_pts_bk, sizeof(double) * 3 * np(), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_cams, d_cams_bk, sizeof(Cam) * nc(), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_pts, d_pts_bk, sizeof(double) * 3 * np(), hipMemcpyDeviceToDevice, stream));
     return SIM3OPT_OK;
   }
   // H_pp^-1, b_p, Z, then S, g, b_c and the undamped diagonals, for the damping `lambda`
@@ -733,14 +710,14 @@ struct Problem {
   // `fail`, so a pcg_rel left by an earlier k_ba_pcg launch (a read-out may ask for one) must not reach the statistics.
   int clear_solver_flags() {
     static_assert(offsetof(Scal, pcg_rel) == offsetof(Scal, pcg_iters) + 2 * sizeof(int32_t), "Scal layout");
-    BA_HIPCHK(hipMemsetAsync(&d_sc->pcg_iters, 0, 2 * sizeof(int32_t) + sizeof(double), stream));
+    HIPCHK(hipMemsetAsync(&d_sc->pcg_iters, 0, 2 * sizeof(int32_t) + sizeof(double), stream));
     return SIM3OPT_OK;
   }
   // S dx_c = g: the exact block Cholesky, or the one-workgroup PCG with the given cap (0: automatic) and tolerance
   int launch_solve(bool exact, int pcg_max_iters, double pcg_rel_tol) {
     if (exact) {
       direct.gather(d_S, d_g, stream);
-      BA_HIPCHK(direct.factor(0.0, &d_sc->fail, 1, d_xc, stream));  // lambda 0: S carries the damping already
+      HIPCHK(direct.factor(0.0, &d_sc->fail, 1, d_xc, stream));  // lambda 0: S carries the damping already
     } else {
       hipLaunchKernelGGL(k_ba_pcg, dim3(1), dim3(1024), 0, stream, nc(), d_rptr, d_bcol, d_S, d_g, d_xc, d_r,
                          d_z, d_p, d_q, d_Dinv, pcg_max_iters > 0 ? pcg_max_iters : 20 * nc() + 100,
@@ -793,7 +770,7 @@ struct Problem {
             // computeLambdaInit: tau * max diagonal entry of the (undamped) Hessian over all vertices
             launch_reduced(1.0);
             launch_maxdiag();
-            BA_HIPCHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
             rc = fetch();
             if (rc) return rc;
             maxdiag = h_sc->maxdiag;
@@ -809,7 +786,7 @@ struct Problem {
         launch_backsub();
         launch_update();
         launch_trial_sums(lambda);
-        BA_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         rc = fetch();
         if (rc) return rc;
         T.pcg_iters += h_sc->pcg_iters;
@@ -835,9 +812,9 @@ struct Problem {
                      it, currentChi, damp.lambda, qmax, T.pcg_iters, T.pcg_rel_res);
       if (damp.terminate(qmax, opt.max_trials, rho)) ok = false;
     }
-    BA_HIPCHK(hipStreamSynchronize(stream));
-    BA_HIPCHK(hipMemcpy(cams.data(), d_cams, sizeof(Cam) * NC, hipMemcpyDeviceToHost));
-    BA_HIPCHK(hipMemcpy(pts.data(), d_pts, sizeof(double) * 3 * NP, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(cams.data(), d_cams, sizeof(Cam) * NC, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pts.data(), d_pts, sizeof(double) * 3 * NP, hipMemcpyDeviceToHost));
     return iters;
   }
 
@@ -845,13 +822,13 @@ struct Problem {
   // optimize() rewrites before it reads it, and the estimate is restored from the trial's backup buffers. ----
   int down(void* dst, const void* src, size_t bytes) {
     if (!dst || !bytes) return SIM3OPT_OK;
-    BA_HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-    BA_HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
     return SIM3OPT_OK;
   }
   int read_lin(double* lin) {
     launch_linearize();
-    BA_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return down(lin, d_lin, sizeof(double) * 20 * no());
   }
   int read_reduced(double lambda, double* S, double* g, double* bc, double* Hinv, double* bp, double* Z,
@@ -859,7 +836,7 @@ struct Problem {
     launch_linearize();
     launch_reduced(lambda);
     launch_maxdiag();
-    BA_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     int rc = fetch();
     if (rc) return rc;
     if (maxdiag) *maxdiag = h_sc->maxdiag;
@@ -879,7 +856,7 @@ struct Problem {
     rc = launch_solve(exact, pcg_max_iters, pcg_rel_tol);
     if (rc) return rc;
     launch_backsub();
-    BA_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     rc = fetch();
     if (rc) return rc;
     if (iters) *iters = h_sc->pcg_iters;
@@ -896,13 +873,13 @@ struct Problem {
     launch_reduced(lambda);  // b_c, b_p of the scale term
     int rc = backup();
     if (rc) return rc;
-    BA_HIPCHK(hipMemcpyAsync(d_xc, dxc, sizeof(double) * 7 * NC, hipMemcpyHostToDevice, stream));
-    BA_HIPCHK(hipMemcpyAsync(d_xp, dxp, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_xc, dxc, sizeof(double) * 7 * NC, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_xp, dxp, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, stream));
     const int32_t flags[2] = {0, with_fail ? 1 : 0};  // pcg_iters, fail
-    BA_HIPCHK(hipMemcpyAsync(&d_sc->pcg_iters, flags, sizeof(flags), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(&d_sc->pcg_iters, flags, sizeof(flags), hipMemcpyHostToDevice, stream));
     launch_update();
     launch_trial_sums(lambda);
-    BA_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     rc = fetch();
     if (rc) return rc;
     if (chi2_out) *chi2_out = h_sc->chi2;
@@ -918,7 +895,7 @@ struct Problem {
     if (rc) return rc;
     rc = clear_solver_flags();
     if (rc) return rc;
-    BA_HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipStreamSynchronize(stream));
     return SIM3OPT_OK;
   }
 };

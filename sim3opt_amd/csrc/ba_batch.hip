@@ -42,15 +42,6 @@
 
 namespace sim3opt_bundle {
 
-#define BB_HIPCHK(call)                                                     \
-  do {                                                                      \
-    hipError_t e_ = (call);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);              \
-      return SIM3OPT_ERR_HIP;                                               \
-    }                                                                       \
-  } while (0)
-
 constexpr int WGB = 256;                    // threads of a workgroup (four wavefronts)
 constexpr int NWAVE = WGB / 64;
 constexpr int SCR_PER_POINT = 56;           // doubles of scratch per point, see the S_* offsets
@@ -431,6 +422,7 @@ struct Batch {
   bool have_run = false;
   // device
   hipStream_t stream = nullptr;
+  sim3opt::DevArena mem;  // the four blocks below
   int32_t* d_ptr = nullptr;
   double *d_in = nullptr, *d_scr = nullptr, *d_out = nullptr;
   int64_t cap_n = 0, cap_total = 0, cap_iters = 0;
@@ -442,8 +434,7 @@ struct Batch {
 
   void release() {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)d_ptr, (void*)d_in, (void*)d_scr, (void*)d_out})
-      if (p) sim3opt::dev_free(p);
+    mem.release();
     d_ptr = nullptr;
     d_in = d_scr = d_out = nullptr;
     if (stream) (void)hipStreamDestroy(stream);
@@ -467,17 +458,17 @@ struct Batch {
     }
     if (opt.device >= 0) {
       if (opt.device >= ndev) { err = "device ordinal out of range"; return SIM3OPT_ERR_ARG; }
-      BB_HIPCHK(hipSetDevice(opt.device));
+      HIPCHK(hipSetDevice(opt.device));
     }
     const int32_t N = n();
     const size_t T = (size_t)total();
     if (N != cap_n || (int64_t)T != cap_total || opt.max_iters != cap_iters) {
       release();
-      BB_HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      BB_HIPCHK(sim3opt::dev_malloc((void**)&d_ptr, sizeof(int32_t) * ((size_t)N + 1)));
-      BB_HIPCHK(sim3opt::dev_malloc((void**)&d_in, sizeof(double) * in_doubles()));
-      BB_HIPCHK(sim3opt::dev_malloc((void**)&d_scr, sizeof(double) * SCR_PER_POINT * T));
-      BB_HIPCHK(sim3opt::dev_malloc((void**)&d_out, sizeof(double) * out_doubles()));
+      HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+      HIPCHK(mem.raw(d_ptr, (size_t)N + 1));
+      HIPCHK(mem.raw(d_in, in_doubles()));
+      HIPCHK(mem.raw(d_scr, SCR_PER_POINT * T));
+      HIPCHK(mem.raw(d_out, out_doubles()));
       cap_n = N; cap_total = (int64_t)T; cap_iters = opt.max_iters;
     }
     // device layout of d_in: cam0 | cam1 | points | uv0 | uv1; of d_out: points | cam1 | stats | summary | edge chi2
@@ -487,13 +478,13 @@ struct Batch {
     double* d_uv0 = d_pin + 3 * T;
     double* d_uv1 = d_uv0 + 2 * T;
     if (!static_uploaded) {
-      BB_HIPCHK(hipMemcpyAsync(d_ptr, ptr.data(), sizeof(int32_t) * ((size_t)N + 1), hipMemcpyHostToDevice, stream));
-      BB_HIPCHK(hipMemcpyAsync(d_cam0, cam0.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, stream));
-      BB_HIPCHK(hipMemcpyAsync(d_uv0, uv0.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
-      BB_HIPCHK(hipMemcpyAsync(d_uv1, uv1.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_ptr, ptr.data(), sizeof(int32_t) * ((size_t)N + 1), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_cam0, cam0.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_uv0, uv0.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_uv1, uv1.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
     }
-    BB_HIPCHK(hipMemcpyAsync(d_cam1, cam1.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, stream));
-    BB_HIPCHK(hipMemcpyAsync(d_pin, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_cam1, cam1.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_pin, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, stream));
     // (the copies read pageable memory: each has left the host buffer when its call returns)
     static_uploaded = true;
 
@@ -512,12 +503,12 @@ struct Batch {
     A.outlier_chi2 = opt.outlier_chi2;
     A.max_iters = opt.max_iters; A.max_trials = opt.max_trials;
     // the statistics of iterations a problem does not reach read as zeros
-    BB_HIPCHK(hipMemsetAsync(A.stats, 0, sizeof(double) * STAT_DOUBLES * opt.max_iters * N, stream));
+    HIPCHK(hipMemsetAsync(A.stats, 0, sizeof(double) * STAT_DOUBLES * opt.max_iters * N, stream));
     hipLaunchKernelGGL(k_ba_two_view, dim3(N), dim3(WGB), 0, stream, A);  // the one launch of the batch
-    BB_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     std::vector<double> out(out_doubles());
-    BB_HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, stream));
-    BB_HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
     const double* o = out.data();
     pts.assign(o, o + 3 * T); o += 3 * T;
     cam1.assign(o, o + 7 * (size_t)N); o += 7 * (size_t)N;

@@ -254,6 +254,10 @@ void sim3opt_destroy(sim3opt_graph* g) {
 
 void sim3opt_release_device_cache(void) { sim3opt::dev_cache_release(); }
 
+void sim3opt_device_memory_in_use(int64_t out[2]) {
+  if (out) sim3opt::dev_in_use(out);
+}
+
 int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
   if (!g || !o) return fail(g, SIM3OPT_ERR_ARG, "set_options: null argument");
   if (!(o->fd_delta > 0) || !(o->exp_eps > 0) || o->max_trials < 1 || !(o->pcg_rel_tol >= 0) ||

@@ -1,5 +1,6 @@
 // comm.cpp -- RCCL (dlopen) and host-staged callback transports (see comm.hpp).
 #include "comm.hpp"
+#include "devmem.hpp"  // HIPCHK
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -74,15 +75,6 @@ bool load_rccl(std::string& err) {
     if (r_ != ncclSuccess) {                                                   \
       err = std::string(#call) + ": " + g_api.GetErrorString(r_);              \
       return SIM3OPT_ERR_COMM;                                                 \
-    }                                                                          \
-  } while (0)
-
-#define HIPCHK(call)                                                           \
-  do {                                                                         \
-    hipError_t e_ = (call);                                                    \
-    if (e_ != hipSuccess) {                                                    \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);                 \
-      return SIM3OPT_ERR_HIP;                                                  \
     }                                                                          \
   } while (0)
 

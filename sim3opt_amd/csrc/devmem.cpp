@@ -107,6 +107,14 @@ void dev_free(void* p) {
   }
 }
 
+void dev_in_use(int64_t out[2]) {
+  Cache& c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  out[0] = (int64_t)c.live.size();
+  out[1] = 0;
+  for (const auto& kv : c.live) out[1] += (int64_t)kv.second.second;
+}
+
 int handle_count(int delta) {
   static std::mutex mu;
   static int n = 0;

@@ -50,22 +50,12 @@ bool BlockLdl::build_plan(int32_t nb, const int32_t* rowptr, const int32_t* coli
 
 hipError_t BlockLdl::upload(hipStream_t stream, StagedUploads* staged) {
   hipError_t e = hipSuccess;
+  // (after the first failure nothing more is allocated; the blocks so far go with release())
   auto up = [&](const int32_t*& dptr, const std::vector<int32_t>& h) {
-    int32_t* p = nullptr;
-    if (e == hipSuccess) e = dev_malloc((void**)&p, sizeof(int32_t) * std::max<size_t>(h.size(), 1));
-    if (e != hipSuccess) return;
-    owned_.push_back(p);
-    dptr = p;
-    if (!h.empty())
-      e = staged ? staged->put(p, h.data(), sizeof(int32_t) * h.size(), stream)
-                 : hipMemcpyAsync(p, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = mem_.upload(dptr, h, stream, staged);
   };
   auto alloc = [&](double*& dptr, size_t count) {
-    count = std::max<size_t>(count, 1);
-    if (e == hipSuccess) e = dev_malloc((void**)&dptr, sizeof(double) * count);
-    if (e != hipSuccess) return;
-    owned_.push_back(dptr);
-    e = hipMemset(dptr, 0, sizeof(double) * count);
+    if (e == hipSuccess) e = mem_.alloc(dptr, count, nullptr);
   };
   const DirectPlan& P = plan_;
   LdlArgs& A = d_->A;
@@ -127,9 +117,8 @@ hipError_t BlockLdl::factor(double lambda, int32_t* fail, int32_t token, double*
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !x || !A.dbg) return e;
   long long h[256];
-  e = hipStreamSynchronize(stream);
-  if (e == hipSuccess) e = hipMemcpy(h, A.dbg, sizeof(h), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+  if ((e = hipMemcpy(h, A.dbg, sizeof(h), hipMemcpyDeviceToHost)) != hipSuccess) return e;
   std::fprintf(stderr, "sim3opt: %s_TRACE: top group stamps [us from start] (level start / after A+B per round / "
                "... / down start / end):", knobs_.c_str());
   for (long long i = 0; i < h[255] && i < 255; ++i) std::fprintf(stderr, " %.1f", (h[i] - h[0]) * 0.01);
@@ -190,8 +179,7 @@ void BlockLdl::debug_forget() {
 }
 
 void BlockLdl::release() {
-  for (void* p : owned_) dev_free(p);
-  owned_.clear();
+  mem_.release();
   *d_ = Dev{};
   plan_ = DirectPlan();
   sel_ = SelinvPlan();

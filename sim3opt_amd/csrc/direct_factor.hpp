@@ -71,7 +71,7 @@ class BlockLdl {
   std::vector<int32_t> parent_, depth_;
   struct Dev;               // the kernels' argument blocks: device copies of the plan, the buffers
   std::unique_ptr<Dev> d_;
-  std::vector<void*> owned_;
+  DevArena mem_;  // every device block of upload()
 };
 
 // Lane sums over the factor's 7x7 block layout (lane l < 49: entry l, column-major), shared with ba.hip's PCG.

@@ -30,24 +30,9 @@ void Engine::release() {
 void Engine::release_under_device() {
   // cached blocks are handed out again without the device-wide wait a hipFree implies
   if (stream) (void)hipStreamSynchronize(stream);
-  void* ptrs[] = {d_states, d_backup, d_meas, d_ev0, d_ev1, d_hidx, d_active, d_info, d_kdelta,
-                  d_kkind, d_rowptr, d_colidx, d_incptr, d_wrow, d_slot01, d_slot10, d_inc0, d_inc1,
-                  d_b, d_Minv, d_x, d_r, d_z, d_p, d_q, d_s, d_part_a, d_part_b, d_sc,
-                  d_sub_first, d_sub_cnt, d_Gm, d_ptab, d_dl};
-  for (void* p : ptrs)
-    if (p) dev_free(p);
-  for (const RangedArray& a : ranged)
-    if (a.alloc) dev_free(a.alloc);
+  mem.release();
   ranged.clear();
   d_vals = d_scratch = nullptr;
-  for (void* p : amg_owned)
-    if (p) dev_free(p);
-  amg_owned.clear();
-  for (LevelPart& lp : parts) {
-    void* q[] = {lp.d_send, lp.d_recv, lp.d_sbuf, lp.d_rbuf};
-    for (void* p : q)
-      if (p) dev_free(p);
-  }
   parts.clear();
   n_sharded = 0;
   batch_release();
@@ -131,19 +116,19 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
   HIPCHK(event_acquire(&ev_a));
   HIPCHK(event_acquire(&ev_b));
   for (hipEvent_t& e : ev_ph) HIPCHK(event_acquire(&e));
-  HIPCHK(upload(staged, stream, d_states, g.states));
-  HIPCHK(dev_malloc((void**)&d_backup, sizeof(Sim3) * (size_t)nv));
-  HIPCHK(upload(staged, stream, d_meas, g.meas));
-  HIPCHK(upload(staged, stream, d_ev0, g.ev0));
-  HIPCHK(upload(staged, stream, d_ev1, g.ev1));
-  HIPCHK(upload(staged, stream, d_hidx, s.hidx));
-  HIPCHK(upload(staged, stream, d_active, l_active));
-  if (has_info) HIPCHK(upload(staged, stream, d_info, g.info));
-  if (has_kernel) HIPCHK(upload(staged, stream, d_kdelta, g.kdelta));
-  if (has_kernel) HIPCHK(upload(staged, stream, d_kkind, g.kkind));
-  HIPCHK(upload(staged, stream, d_rowptr, s.rowptr));
-  HIPCHK(upload(staged, stream, d_colidx, s.colidx));
-  HIPCHK(upload(staged, stream, d_incptr, s.incptr));
+  HIPCHK(upload(d_states, g.states));
+  HIPCHK(mem.raw(d_backup, (size_t)nv));
+  HIPCHK(upload(d_meas, g.meas));
+  HIPCHK(upload(d_ev0, g.ev0));
+  HIPCHK(upload(d_ev1, g.ev1));
+  HIPCHK(upload(d_hidx, s.hidx));
+  HIPCHK(upload(d_active, l_active));
+  if (has_info) HIPCHK(upload(d_info, g.info));
+  if (has_kernel) HIPCHK(upload(d_kdelta, g.kdelta));
+  if (has_kernel) HIPCHK(upload(d_kkind, g.kkind));
+  HIPCHK(upload(d_rowptr, s.rowptr));
+  HIPCHK(upload(d_colidx, s.colidx));
+  HIPCHK(upload(d_incptr, s.incptr));
   {  // span SpMV: contiguous row span per wavefront, balanced by stored blocks
     const int nloc = r1 - r0;
     // 3x the resident set (256 CUs x 8 workgroups of 4 wavefronts): shorter spans make the
@@ -160,12 +145,12 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
     std::vector<int32_t> wrow(nw + 1);
     partition_rows(nloc, s.rowptr.data() + r0, nw, wrow.data());
     for (int32_t& w : wrow) w += r0;
-    HIPCHK(upload(staged, stream, d_wrow, wrow));
+    HIPCHK(upload(d_wrow, wrow));
   }
-  HIPCHK(upload(staged, stream, d_slot01, l_s01));
-  HIPCHK(upload(staged, stream, d_slot10, l_s10));
-  HIPCHK(upload(staged, stream, d_inc0, l_i0));
-  HIPCHK(upload(staged, stream, d_inc1, l_i1));
+  HIPCHK(upload(d_slot01, l_s01));
+  HIPCHK(upload(d_slot10, l_s10));
+  HIPCHK(upload(d_inc0, l_i0));
+  HIPCHK(upload(d_inc1, l_i1));
   // H and the assembly scratch: this rank's rows only (alloc_ranged; one rank: everything)
   {
     int rc = alloc_ranged(d_vals, 49 * (int64_t)s.rowptr[r0], 49 * (int64_t)s.rowptr[r1], 49 * (int64_t)nnzb, err);
@@ -173,7 +158,7 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
     rc = alloc_ranged(d_scratch, 35 * (int64_t)s.incptr[r0], 35 * (int64_t)s.incptr[r1], 35 * (int64_t)s.incptr[nb], err);
     if (rc) return rc;
   }
-  HIPCHK(dev_malloc((void**)&d_Minv, sizeof(double) * 49 * (size_t)nb));
+  HIPCHK(mem.raw(d_Minv, 49 * (size_t)nb));
   // preconditioner choice: chain segments for chain-like graphs (few blocks per row)
   // automatic: chain segments only when almost every edge is a chain link (KITTI with one loop:
   // 3963 PCG iterations per 30 LM iterations instead of 621642); with many loops the low-rank
@@ -218,9 +203,9 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
           if (sf[i] < 0) sf[i] = k;
           ++scnt[i];
         }
-    HIPCHK(upload(staged, stream, d_sub_first, sf));
-    HIPCHK(upload(staged, stream, d_sub_cnt, scnt));
-    HIPCHK(dev_malloc((void**)&d_Gm, sizeof(double) * 49 * (size_t)nb));
+    HIPCHK(upload(d_sub_first, sf));
+    HIPCHK(upload(d_sub_cnt, scnt));
+    HIPCHK(mem.raw(d_Gm, 49 * (size_t)nb));
   }
   double** vecs[] = {&d_b, &d_x, &d_r, &d_z, &d_p, &d_q, &d_s};
   for (double** v : vecs) {
@@ -228,13 +213,11 @@ int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
     int64_t padded = 0;
     (void)allgather_equal_plan(offs.data(), comm.world, nullptr, &padded);
     const size_t n_alloc = std::max<size_t>((size_t)n, (size_t)padded);
-    HIPCHK(dev_malloc((void**)v, sizeof(double) * n_alloc));
-    HIPCHK(hipMemset(*v, 0, sizeof(double) * n_alloc));
+    HIPCHK(mem.alloc(*v, n_alloc, nullptr));
   }
-  HIPCHK(dev_malloc((void**)&d_part_a, sizeof(double) * SPAN_GRID_MAX));
-  HIPCHK(dev_malloc((void**)&d_part_b, sizeof(double) * SPAN_GRID_MAX));
-  HIPCHK(dev_malloc((void**)&d_sc, sizeof(DevScalars)));
-  HIPCHK(hipMemset(d_sc, 0, sizeof(DevScalars)));
+  HIPCHK(mem.raw(d_part_a, SPAN_GRID_MAX));
+  HIPCHK(mem.raw(d_part_b, SPAN_GRID_MAX));
+  HIPCHK(mem.alloc(d_sc, 1, nullptr));
   HIPCHK(host_malloc((void**)&h_sc, sizeof(DevScalars)));
   HIPCHK(host_malloc((void**)&h_ring, sizeof(DevScalars) * KB));
   HIPCHK(event_acquire(&ring_ev));
@@ -370,8 +353,8 @@ int Engine::chi2(double* out, std::string& err, hipEvent_t before_fetch, int sca
 // debug_full_arrays: nothing outside this rank's ranges may have been written (reads show as NaN in the results)
 int Engine::check_foreign_ranges(std::string& err) {
   if (!opt.debug_full_arrays || ranged.empty()) return SIM3OPT_OK;
-  unsigned long long* d_cnt = nullptr;
-  HIPCHK(dev_malloc((void**)&d_cnt, sizeof(unsigned long long) * ranged.size()));
+  DevBuf<unsigned long long> d_cnt;
+  HIPCHK(d_cnt.alloc(ranged.size()));
   HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * ranged.size(), stream));
   for (size_t i = 0; i < ranged.size(); ++i) {
     const RangedArray& a = ranged[i];
@@ -381,11 +364,9 @@ int Engine::check_foreign_ranges(std::string& err) {
     if (tail) hipLaunchKernelGGL(k_count_unpoisoned, dim3(1024), dim3(WG), 0, stream, reinterpret_cast<const uint32_t*>(base + tail0), tail, d_cnt + i);
   }
   std::vector<unsigned long long> h(ranged.size(), 0);
-  hipError_t e1 = hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, stream);
-  hipError_t e2 = hipStreamSynchronize(stream);
-  dev_free(d_cnt);
+  const hipError_t e1 = hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, stream);
+  HIPCHK(hipStreamSynchronize(stream));  // (whatever the copy said: the launches above are behind it before d_cnt goes)
   HIPCHK(e1);
-  HIPCHK(e2);
   for (size_t i = 0; i < h.size(); ++i)
     if (h[i]) {
       err = "debug_full_arrays: " + std::to_string(h[i]) + " words outside this rank's range of ranged array " +
@@ -422,7 +403,7 @@ static void launch_linearize(bool analytic, bool has_info, bool has_kernel, int 
 int Engine::linearize(std::string& err) {
   const sim3::Opts mo = mopts();
   const bool analytic = opt.jacobians == 1;  // closed form: no perturbation table
-  if (!analytic && !d_ptab) HIPCHK(dev_malloc((void**)&d_ptab, 14 * sizeof(Sim3)));
+  if (!analytic && !d_ptab) HIPCHK(mem.raw(d_ptab, 14));
   if (!analytic && (ptab_delta != opt.fd_delta || ptab_opts.eps != mo.eps ||
                     ptab_opts.small_rot_half != mo.small_rot_half || ptab_opts.fix_small_b != mo.fix_small_b)) {
     hipLaunchKernelGGL(k_perturbation_table, dim3(1), dim3(64), 0, stream, opt.fd_delta, mo, d_ptab);
@@ -644,43 +625,32 @@ int engine_set_states(Engine* e, const Sim3* in, std::string& err) {
 }
 
 int engine_edge_errors(Engine* e, double* out, std::string& err) {
-  double* d_out = nullptr;
-  HIPCHK(dev_malloc((void**)&d_out, sizeof(double) * 7 * std::max<size_t>((size_t)e->ne, 1)));
+  DevBuf<double> d_out;
+  HIPCHK(d_out.alloc(7 * std::max<size_t>((size_t)e->ne, 1)));
   EdgeArgs ea = e->edge_args();
   ea.e_lo = 0;
   ea.e_hi = e->ne;
-  hipLaunchKernelGGL(k_edge_errors, dim3(grid_for(e->ne, WG)), dim3(WG), 0, e->stream, ea, d_out);
-  hipError_t le = hipGetLastError();
-  if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
-  if (le == hipSuccess)
-    le = hipMemcpy(out, d_out, sizeof(double) * 7 * (size_t)e->ne, hipMemcpyDeviceToHost);
-  dev_free(d_out);
-  if (le != hipSuccess) {
-    err = std::string("edge_errors: ") + hipGetErrorString(le);
-    return SIM3OPT_ERR_HIP;
-  }
+  hipLaunchKernelGGL(k_edge_errors, dim3(grid_for(e->ne, WG)), dim3(WG), 0, e->stream, ea, d_out.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(out, d_out, sizeof(double) * 7 * (size_t)e->ne, hipMemcpyDeviceToHost));
   return SIM3OPT_OK;
 }
 
 int engine_edge_chi2(Engine* e, double* chi2, double* rho, double* weight, std::string& err) {
   const size_t m = (size_t)e->ne;
-  double* d_out = nullptr;
-  HIPCHK(dev_malloc((void**)&d_out, sizeof(double) * 3 * std::max<size_t>(m, 1)));
+  DevBuf<double> d_out;
+  HIPCHK(d_out.alloc(3 * std::max<size_t>(m, 1)));
   EdgeArgs ea = e->edge_args();  // (replicated states: every rank evaluates every edge)
   ea.e_lo = 0;
   ea.e_hi = e->ne;
   hipLaunchKernelGGL(k_edge_chi2, dim3(grid_for(e->ne, WG)), dim3(WG), 0, e->stream, ea,
-                     chi2 ? d_out : nullptr, rho ? d_out + m : nullptr, weight ? d_out + 2 * m : nullptr);
-  hipError_t le = hipGetLastError();
-  if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
-  if (le == hipSuccess && chi2) le = hipMemcpy(chi2, d_out, sizeof(double) * m, hipMemcpyDeviceToHost);
-  if (le == hipSuccess && rho) le = hipMemcpy(rho, d_out + m, sizeof(double) * m, hipMemcpyDeviceToHost);
-  if (le == hipSuccess && weight) le = hipMemcpy(weight, d_out + 2 * m, sizeof(double) * m, hipMemcpyDeviceToHost);
-  dev_free(d_out);
-  if (le != hipSuccess) {
-    err = std::string("edge_chi2: ") + hipGetErrorString(le);
-    return SIM3OPT_ERR_HIP;
-  }
+                     chi2 ? d_out.get() : nullptr, rho ? d_out + m : nullptr, weight ? d_out + 2 * m : nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (chi2) HIPCHK(hipMemcpy(chi2, d_out, sizeof(double) * m, hipMemcpyDeviceToHost));
+  if (rho) HIPCHK(hipMemcpy(rho, d_out + m, sizeof(double) * m, hipMemcpyDeviceToHost));
+  if (weight) HIPCHK(hipMemcpy(weight, d_out + 2 * m, sizeof(double) * m, hipMemcpyDeviceToHost));
   return SIM3OPT_OK;
 }
 
@@ -691,8 +661,8 @@ int engine_set_kernels(Engine* e, const HostGraph& g, std::string& err) {
     return SIM3OPT_ERR_STATE;
   }
   HIPCHK(hipStreamSynchronize(e->stream));  // (a launch in flight may still read the old arrays)
-  if (!e->d_kdelta) HIPCHK(dev_malloc((void**)&e->d_kdelta, sizeof(double) * std::max<size_t>(m, 1)));
-  if (!e->d_kkind) HIPCHK(dev_malloc((void**)&e->d_kkind, sizeof(uint8_t) * std::max<size_t>(m, 1)));
+  if (!e->d_kdelta) HIPCHK(e->mem.raw(e->d_kdelta, m));
+  if (!e->d_kkind) HIPCHK(e->mem.raw(e->d_kkind, m));
   if (m) {
     HIPCHK(hipMemcpy(e->d_kdelta, g.kdelta.data(), sizeof(double) * m, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_kkind, g.kkind.data(), sizeof(uint8_t) * m, hipMemcpyHostToDevice));
@@ -705,22 +675,17 @@ int engine_set_kernels(Engine* e, const HostGraph& g, std::string& err) {
 
 int engine_edge_jacobians(Engine* e, double* e_out, double* J_out, std::string& err) {
   const size_t m = (size_t)e->ne;
-  double* d_out = nullptr;
-  HIPCHK(dev_malloc((void**)&d_out, sizeof(double) * 105 * std::max<size_t>(m, 1)));
+  DevBuf<double> d_out;
+  HIPCHK(d_out.alloc(105 * std::max<size_t>(m, 1)));
   EdgeArgs ea = e->edge_args();
   ea.e_lo = 0;
   ea.e_hi = e->ne;
   hipLaunchKernelGGL(k_edge_jacobians, dim3(grid_for(e->ne, WG)), dim3(WG), 0, e->stream, ea, e->opt.dof_mask,
-                     d_out, d_out + 7 * m);
-  hipError_t le = hipGetLastError();
-  if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
-  if (le == hipSuccess) le = hipMemcpy(e_out, d_out, sizeof(double) * 7 * m, hipMemcpyDeviceToHost);
-  if (le == hipSuccess) le = hipMemcpy(J_out, d_out + 7 * m, sizeof(double) * 98 * m, hipMemcpyDeviceToHost);
-  dev_free(d_out);
-  if (le != hipSuccess) {
-    err = std::string("edge_jacobians: ") + hipGetErrorString(le);
-    return SIM3OPT_ERR_HIP;
-  }
+                     d_out.get(), d_out + 7 * m);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(e_out, d_out, sizeof(double) * 7 * m, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(J_out, d_out + 7 * m, sizeof(double) * 98 * m, hipMemcpyDeviceToHost));
   return SIM3OPT_OK;
 }
 
@@ -745,34 +710,27 @@ int engine_debug_linearization(Engine* e, double* J, double* w, int32_t* active,
     return SIM3OPT_ERR_STATE;
   }
   const size_t na = (size_t)e->n_active, ninc = (size_t)e->st.incptr[e->nb], m = (size_t)e->ne;
-  double* d_dump = nullptr;
-  HIPCHK(dev_malloc((void**)&d_dump, sizeof(double) * 106 * std::max<size_t>(na, 1)));
+  DevBuf<double> d_dump;
+  HIPCHK(d_dump.alloc(106 * std::max<size_t>(na, 1)));
   const LinDump dump{d_dump, d_dump + 105 * std::max<size_t>(na, 1)};
+  HIPCHK(hipStreamSynchronize(e->stream));  // (the symbol is written outside the stream)
+  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(d_lin_dump), &dump, sizeof(LinDump)));
   const sim3opt_kernel_times kt0 = e->kt;
-  int rc = SIM3OPT_OK;
-  hipError_t le = hipStreamSynchronize(e->stream);  // (the symbol is written outside the stream)
-  if (le == hipSuccess) le = hipMemcpyToSymbol(HIP_SYMBOL(d_lin_dump), &dump, sizeof(LinDump));
-  if (le == hipSuccess) {
-    e->lin_dump = true;
-    rc = e->linearize(err);  // the launches of sim3opt_linearize, the linearisation kernel in its DUMP instantiation
-    e->lin_dump = false;
-    e->kt = kt0;
-  }
-  if (le == hipSuccess && rc == SIM3OPT_OK) le = hipStreamSynchronize(e->stream);
-  if (le == hipSuccess && rc == SIM3OPT_OK && na) {
-    le = hipMemcpy(J, dump.J, sizeof(double) * 105 * na, hipMemcpyDeviceToHost);
-    if (le == hipSuccess) le = hipMemcpy(w, dump.w, sizeof(double) * na, hipMemcpyDeviceToHost);
-  }
-  dev_free(d_dump);
+  e->lin_dump = true;
+  const int rc = e->linearize(err);  // the launches of sim3opt_linearize, the linearisation kernel in its DUMP instantiation
+  e->lin_dump = false;
+  e->kt = kt0;
+  const hipError_t es = hipStreamSynchronize(e->stream);  // (whatever it said: its launches are done before d_dump goes)
   if (rc) return rc;
-  if (le == hipSuccess && ninc) le = hipMemcpy(scratch, e->d_scratch, sizeof(double) * 35 * ninc, hipMemcpyDeviceToHost);
-  unsigned long long bits = 0;
-  if (le == hipSuccess) le = hipMemcpy(trace, &e->d_sc->trace, sizeof(double), hipMemcpyDeviceToHost);
-  if (le == hipSuccess) le = hipMemcpy(&bits, &e->d_sc->maxdiag_bits, sizeof(bits), hipMemcpyDeviceToHost);
-  if (le != hipSuccess) {
-    err = std::string("debug_linearization: ") + hipGetErrorString(le);
-    return SIM3OPT_ERR_HIP;
+  HIPCHK(es);
+  if (na) {
+    HIPCHK(hipMemcpy(J, dump.J, sizeof(double) * 105 * na, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(w, dump.w, sizeof(double) * na, hipMemcpyDeviceToHost));
   }
+  if (ninc) HIPCHK(hipMemcpy(scratch, e->d_scratch, sizeof(double) * 35 * ninc, hipMemcpyDeviceToHost));
+  unsigned long long bits = 0;
+  HIPCHK(hipMemcpy(trace, &e->d_sc->trace, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&bits, &e->d_sc->maxdiag_bits, sizeof(bits), hipMemcpyDeviceToHost));
   std::memcpy(maxdiag, &bits, sizeof(double));
   // the index arrays as uploaded (one rank: the structure's own)
   if (na) std::memcpy(active, e->st.active.data(), sizeof(int32_t) * na);
@@ -805,54 +763,38 @@ int engine_debug_update(Engine* e, const double* x, double lambda, bool with_fai
     return SIM3OPT_ERR_ARG;
   }
   // everything a trial's launches overwrite that a later call could see
-  HIPCHK(hipStreamSynchronize(e->stream));
-  DevScalars dev0;
-  const DevScalars host0 = *e->h_sc;
-  const sim3opt_kernel_times kt0 = e->kt;
-  const bool known0 = e->chi_known;
-  const double cache0 = e->chi_cache;
-  int64_t sched0[4];
-  for (int i = 0; i < 4; ++i) sched0[i] = e->sched_stats[i];
-  HIPCHK(hipMemcpy(&dev0, e->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
-  double* d_step = nullptr;
-  HIPCHK(dev_malloc((void**)&d_step, sizeof(double) * std::max<size_t>((size_t)e->n, 1)));
-  int rc = SIM3OPT_OK;
-  double chi = 0.0;
-  hipError_t le = hipMemcpy(d_step, x, sizeof(double) * (size_t)e->n, hipMemcpyHostToDevice);
-  if (le == hipSuccess && with_fail) {
-    const int32_t token = e->fail_token;  // what the factorisation of the current solve stores on a bad pivot
-    le = hipMemcpy(&e->d_sc->fail, &token, sizeof(int32_t), hipMemcpyHostToDevice);
-  }
-  if (le == hipSuccess) {  // the launches of an LM trial after its solve (Engine::optimize)
+  SolverSnapshot snap;
+  int rc = snap.take(*e, err);
+  if (rc) return rc;
+  DevBuf<double> d_step;  // (outlives the put-back's synchronisation)
+  double chi = 0.0, sc = 0.0;
+  bool pushed = false;
+  auto body = [&]() -> int {
+    HIPCHK(d_step.alloc(std::max<size_t>((size_t)e->n, 1)));
+    HIPCHK(hipMemcpy(d_step, x, sizeof(double) * (size_t)e->n, hipMemcpyHostToDevice));
+    if (with_fail) {
+      const int32_t token = e->fail_token;  // what the factorisation of the current solve stores on a bad pivot
+      HIPCHK(hipMemcpy(&e->d_sc->fail, &token, sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    // the launches of an LM trial after its solve (Engine::optimize)
+    pushed = true;
     e->apply_step(d_step, true);
     const int ge = grid > 0 ? grid : grid_for(7 * (int64_t)(e->r1 - e->r0), WG);
     hipLaunchKernelGGL(k_scale, dim3(ge), dim3(WG), 0, e->stream, 7 * e->r0, 7 * e->r1, (const double*)d_step,
                        (const double*)e->d_b, lambda, e->d_part_b);
-    le = hipGetLastError();
-    if (le == hipSuccess) rc = e->chi2(&chi, err, nullptr, ge, grid);
-  }
-  const double sc = e->h_sc->scale;
-  if (le == hipSuccess && rc == SIM3OPT_OK) le = hipStreamSynchronize(e->stream);
-  if (le == hipSuccess && rc == SIM3OPT_OK && states_out)
-    le = hipMemcpy(states_out, e->d_states, sizeof(Sim3) * (size_t)e->nv, hipMemcpyDeviceToHost);
-  if (le == hipSuccess && rc == SIM3OPT_OK && backup_out)
-    le = hipMemcpy(backup_out, e->d_backup, sizeof(Sim3) * (size_t)e->nv, hipMemcpyDeviceToHost);
-  if (le == hipSuccess) {  // (the backup was taken whatever followed it)
-    e->pop_states();
-    le = hipStreamSynchronize(e->stream);
-  }
-  if (le == hipSuccess) le = hipMemcpy(e->d_sc, &dev0, sizeof(DevScalars), hipMemcpyHostToDevice);
-  dev_free(d_step);
-  *e->h_sc = host0;
-  e->kt = kt0;
-  e->chi_known = known0;
-  e->chi_cache = cache0;
-  for (int i = 0; i < 4; ++i) e->sched_stats[i] = sched0[i];
+    HIPCHK(hipGetLastError());
+    const int rc2 = e->chi2(&chi, err, nullptr, ge, grid);
+    if (rc2) return rc2;
+    sc = e->h_sc->scale;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (states_out) HIPCHK(hipMemcpy(states_out, e->d_states, sizeof(Sim3) * (size_t)e->nv, hipMemcpyDeviceToHost));
+    if (backup_out) HIPCHK(hipMemcpy(backup_out, e->d_backup, sizeof(Sim3) * (size_t)e->nv, hipMemcpyDeviceToHost));
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  if (pushed) e->pop_states();  // (the backup was taken whatever followed it)
+  rc = snap.put_back(rc, err);
   if (rc) return rc;
-  if (le != hipSuccess) {
-    err = std::string("debug_update: ") + hipGetErrorString(le);
-    return SIM3OPT_ERR_HIP;
-  }
   if (chi2) *chi2 = chi;
   if (scale) *scale = sc;
   return SIM3OPT_OK;

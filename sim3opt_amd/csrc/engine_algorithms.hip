@@ -90,8 +90,7 @@ int Engine::dogleg_dots(std::string& err) {
 
 int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
   if (!d_dl) {
-    HIPCHK(dev_malloc((void**)&d_dl, sizeof(double) * (4 * MAX_GRID + DL_OUT + 8)));
-    HIPCHK(hipMemset(d_dl, 0, sizeof(double) * (4 * MAX_GRID + DL_OUT + 8)));
+    HIPCHK(mem.alloc(d_dl, 4 * MAX_GRID + DL_OUT + 8, nullptr));
   }
   if (!h_dl) HIPCHK(host_malloc((void**)&h_dl, sizeof(double) * 8));
   // (the span SpMV's launch state -- row spans d_wrow, partial buffers -- is built by init() for every linear

@@ -84,9 +84,9 @@ int Engine::amg_bind(const Structure& s, std::string& err) {
   // (padded like the PCG vectors: the multi-GPU all-gather runs in place with equal counts)
   int64_t padded = 0;
   (void)allgather_equal_plan(offs.data(), comm.world, nullptr, &padded);
-  AMGCHK(amg_alloc(d_az, std::max<size_t>((size_t)n, (size_t)padded), err));
-  AMGCHK(amg_alloc(d_P, (size_t)49 * nb, err));
-  AMGCHK(amg_up(d_row2v, s.row2vertex, err));
+  HIPCHK(mem.alloc(d_az, std::max<size_t>((size_t)n, (size_t)padded), nullptr));
+  HIPCHK(mem.alloc(d_P, (size_t)49 * nb, nullptr));
+  HIPCHK(upload(d_row2v, s.row2vertex));
   L0.t = d_az;
   L0.lo = r0; L0.hi = r1;
   // Which coarse levels are partitioned like level 0 (multi-rank runs): those with more rows than
@@ -110,8 +110,8 @@ int Engine::amg_bind(const Structure& s, std::string& err) {
     if (l > 0) {
       L.nb = h.nb; L.nnzb = h.nnzb;
       L.lo = 0; L.hi = L.nb;
-      AMGCHK(amg_up(L.rowptr, h.rowptr, err));
-      AMGCHK(amg_up(L.colidx, h.colidx, err));
+      HIPCHK(upload(L.rowptr, h.rowptr));
+      HIPCHK(upload(L.colidx, h.colidx));
       if (sharded(l)) {
         AMGCHK(level_part_init(l, L.nb, h.rowptr.data(), h.colidx.data(), h.row_begin, err));
         L.lo = parts[l].lo; L.hi = parts[l].hi;
@@ -122,15 +122,15 @@ int Engine::amg_bind(const Structure& s, std::string& err) {
       std::vector<int32_t> wrow(L.span_grid * 4 + 1);
       partition_rows(nloc, h.rowptr.data() + L.lo, L.span_grid * 4, wrow.data());
       for (int32_t& w : wrow) w += L.lo;
-      AMGCHK(amg_up(L.wrow, wrow, err));
+      HIPCHK(upload(L.wrow, wrow));
       // (a partitioned level's blocks: this rank's rows only -- alloc_ranged; replicated levels: all)
       AMGCHK(alloc_ranged(L.vals, 49 * (int64_t)h.rowptr[L.lo], 49 * (int64_t)h.rowptr[L.hi], 49 * (int64_t)L.nnzb, err));
-      AMGCHK(amg_alloc(L.diagH, (size_t)49 * L.nb, err));
-      AMGCHK(amg_alloc(L.W, (size_t)49 * L.nb, err));
-      AMGCHK(amg_alloc(L.Minv, (size_t)49 * L.nb, err));
-      AMGCHK(amg_alloc(L.r, (size_t)7 * L.nb, err));
-      AMGCHK(amg_alloc(L.x, (size_t)7 * L.nb, err));
-      AMGCHK(amg_alloc(L.t, (size_t)7 * L.nb, err));
+      HIPCHK(mem.alloc(L.diagH, (size_t)49 * L.nb, nullptr));
+      HIPCHK(mem.alloc(L.W, (size_t)49 * L.nb, nullptr));
+      HIPCHK(mem.alloc(L.Minv, (size_t)49 * L.nb, nullptr));
+      HIPCHK(mem.alloc(L.r, (size_t)7 * L.nb, nullptr));
+      HIPCHK(mem.alloc(L.x, (size_t)7 * L.nb, nullptr));
+      HIPCHK(mem.alloc(L.t, (size_t)7 * L.nb, nullptr));
     }
     if (amg_fp32) {
       // whole pairs of blocks (f32_pair_index); of a partitioned level the pairs that hold this rank's rows' blocks
@@ -140,18 +140,18 @@ int Engine::amg_bind(const Structure& s, std::string& err) {
       AMGCHK(alloc_ranged(L.vals32, 98 * (b0 / 2), 98 * ((b1 + 1) / 2), n32, err));
     }
     if (l + 1 < nl) {
-      AMGCHK(amg_up(L.agg, h.agg, err));
-      AMGCHK(amg_up(L.mptr, h.mptr, err));
-      AMGCHK(amg_up(L.mem, h.mem, err));
-      AMGCHK(amg_up(L.gptr, h.gptr, err));
-      AMGCHK(amg_up(L.gblk, h.gblk, err));
-      AMGCHK(amg_up(L.grow, h.grow, err));
+      HIPCHK(upload(L.agg, h.agg));
+      HIPCHK(upload(L.mptr, h.mptr));
+      HIPCHK(upload(L.mem, h.mem));
+      HIPCHK(upload(L.gptr, h.gptr));
+      HIPCHK(upload(L.gblk, h.gblk));
+      HIPCHK(upload(L.grow, h.grow));
     }
   }
   const size_t nc = (size_t)7 * amg[nl - 1].nb;
-  AMGCHK(amg_alloc(d_Ainv, nc * nc, err));
-  AMGCHK(amg_alloc(d_Ainv2, nc * nc, err));
-  AMGCHK(amg_alloc(d_piv, 2 * 28 * 28, err));  // pivot-block inverses handed from step to step
+  HIPCHK(mem.alloc(d_Ainv, nc * nc, nullptr));
+  HIPCHK(mem.alloc(d_Ainv2, nc * nc, nullptr));
+  HIPCHK(mem.alloc(d_piv, 2 * 28 * 28, nullptr));  // pivot-block inverses handed from step to step
 #undef AMGCHK
   // rows of level l + 1 whose Galerkin blocks / restricted residuals this rank forms from level l: the
   // aggregates of its own rows when level l is partitioned, all of them otherwise -- and where a partitioned
@@ -511,19 +511,23 @@ int Engine::amg_numbers(double lambda, std::string& err) {
     err = "amg read-out: this graph was not initialised with the multigrid preconditioner";
     return SIM3OPT_ERR_STATE;
   }
-  DevScalars sd, sh;
-  int rc = diag_begin(pv_one, &lambda, 1, &sd, &sh, err);
+  SolverSnapshot snap;
+  int rc = snap.take(*this, err);
   if (rc) return rc;
-  if (amg_stale) rc = amg_setup(err);
-  if (rc == SIM3OPT_OK) {
+  auto body = [&]() -> int {
+    int rc2 = diag_begin(pv_one, &lambda, 1, &snap.d_one, err);
+    if (rc2) return rc2;
+    if (amg_stale && (rc2 = amg_setup(err))) return rc2;
     amg_prepare(lambda);
-    rc = fetch_scalars(err);
-    if (rc == SIM3OPT_OK && h_sc->fail) {
+    rc2 = fetch_scalars(err);
+    if (rc2) return rc2;
+    if (h_sc->fail) {
       err = "amg read-out: the set-up met a non-positive pivot";
-      rc = SIM3OPT_ERR_STATE;
+      return SIM3OPT_ERR_STATE;
     }
-  }
-  return diag_end(pv_one, &sd, &sh, rc, err);
+    return SIM3OPT_OK;
+  };
+  return snap.put_back(body(), err);
 }
 
 int Engine::amg_level_readout(double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals,

@@ -19,20 +19,13 @@ int Engine::cols_alloc(std::string& err) {
   if (c_g) return SIM3OPT_OK;
   c_vs = pad64(n);
   double** v0[] = {&c_g, &c_y, &c_r, &c_d};
-  for (double** v : v0) {
-    HIPCHK(dev_malloc((void**)v, sizeof(double) * (size_t)KB * c_vs));
-    cols_owned.push_back(*v);
-    HIPCHK(hipMemsetAsync(*v, 0, sizeof(double) * (size_t)KB * c_vs, stream));
-  }
-  HIPCHK(dev_malloc((void**)&c_nrm, sizeof(double) * 2 * KB));
-  cols_owned.push_back(c_nrm);
+  for (double** v : v0) HIPCHK(cols_mem.alloc(*v, (size_t)KB * c_vs, stream));
+  HIPCHK(cols_mem.raw(c_nrm, 2 * KB));
   return SIM3OPT_OK;
 }
 
 void Engine::cols_release() {
-  for (void* p : cols_owned)
-    if (p) dev_free(p);
-  cols_owned.clear();
+  cols_mem.release();
   c_g = c_y = c_r = c_d = c_nrm = nullptr;
 }
 
@@ -103,45 +96,37 @@ int Engine::inverse_columns(double lambda, int32_t nvert, const int32_t* vertice
           "exactly -- cov_solver = 0 is the path for it";
     return SIM3OPT_ERR_STATE;
   }
+  const sim3opt_kernel_times kt0 = kt;  // (not one of the optimiser's linearisations: the counters stay)
   int rc = linearize(err);  // H at the current estimates (b is rewritten with the values it has)
+  kt = kt0;
   if (rc) return rc;
   if (nvert == 0) return SIM3OPT_OK;
   rc = cols_alloc(err);
   if (rc) return rc;
   const int width = cols_batch_width();
   if (width > 0 && (rc = batch_alloc(err))) return rc;
-  // ---- what the solves write of the solver's state, saved: the scalars on both sides, the batch's, the counters ----
-  HIPCHK(hipStreamSynchronize(stream));
-  DevScalars sd, sh = *h_sc, sbd[KB], sbh[KB];
-  HIPCHK(hipMemcpy(&sd, d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
+  SolverSnapshot snap;  // (after batch_alloc: the batch's scalars are in it)
+  if ((rc = snap.take(*this, err))) return rc;
+  // one set-up for all systems of a batch: slot 0 of the smoother inverses, the FP32 diagonals and the dense inverse --
+  // a mode of this call, not solver state: the strides go to zero here and come back below
   std::vector<int64_t> ms_saved;
-  int64_t as_saved = 0;
+  const int64_t as_saved = cv_batch.as;
   if (width > 0) {
-    HIPCHK(hipMemcpy(sbd, d_bsc, sizeof(sbd), hipMemcpyDeviceToHost));
-    std::memcpy(sbh, h_bsc, sizeof(sbh));
-    // one set-up for all systems of a batch: slot 0 of the smoother inverses, the FP32 diagonals and the dense inverse
     for (CycleLevel& B : cv_batch.lv) {
       ms_saved.push_back(B.ms);
       B.ms = 0;
     }
-    as_saved = cv_batch.as;
     cv_batch.as = 0;
     pv_batch.ms = 0;
   }
-  const sim3opt_kernel_times kt_saved = kt;
-  int64_t sched_saved[4];
-  std::memcpy(sched_saved, sched_stats, sizeof(sched_saved));
-  const long long work_saved = spmv_work_seen;
-  const double true_rel_saved = last_true_rel;
-  const bool capped_saved = last_capped;
 
   const int32_t nblk = first[nvert];
-  int32_t* d_rows = nullptr;
-  double* d_blocks = nullptr;
+  DevBuf<int32_t> d_rows;  // (they go after the put-back's synchronisation)
+  DevBuf<double> d_blocks;
   std::vector<double> out((size_t)49 * std::max(nblk, 1));
   auto body = [&]() -> int {
-    HIPCHK(dev_malloc((void**)&d_rows, sizeof(int32_t) * (size_t)std::max(nblk, 1)));
-    HIPCHK(dev_malloc((void**)&d_blocks, sizeof(double) * 49 * (size_t)std::max(nblk, 1)));
+    HIPCHK(d_rows.alloc((size_t)std::max(nblk, 1)));
+    HIPCHK(d_blocks.alloc(49 * (size_t)std::max(nblk, 1)));
     HIPCHK(hipMemcpyAsync(d_rows, blk_row, sizeof(int32_t) * (size_t)nblk, hipMemcpyHostToDevice, stream));
     const double ctol = opt.cov_rel_tol;
     double first_pass = 0.01;
@@ -237,7 +222,7 @@ int Engine::inverse_columns(double lambda, int32_t nvert, const int32_t* vertice
         if (cnt > 0)
           hipLaunchKernelGGL(k_cols_gather, dim3(grid_for(7 * (int64_t)cnt, WG)), dim3(WG), 0, stream, first[v], cnt,
                              (int32_t)((c0 + s) % 7), (const int32_t*)d_rows, (const double*)(c_y + (size_t)s * c_vs),
-                             d_blocks);
+                             d_blocks.get());
       }
       HIPCHK(hipGetLastError());
     }
@@ -245,28 +230,11 @@ int Engine::inverse_columns(double lambda, int32_t nvert, const int32_t* vertice
     HIPCHK(hipStreamSynchronize(stream));
     return SIM3OPT_OK;
   };
-  rc = body();
-  // ---- ... and put back ----
-  bool restored = hipStreamSynchronize(stream) == hipSuccess;
-  restored = restored && hipMemcpy(d_sc, &sd, sizeof(DevScalars), hipMemcpyHostToDevice) == hipSuccess;
-  *h_sc = sh;
+  rc = snap.put_back(body(), err);
   if (width > 0) {
-    restored = restored && hipMemcpy(d_bsc, sbd, sizeof(sbd), hipMemcpyHostToDevice) == hipSuccess;
-    std::memcpy(h_bsc, sbh, sizeof(sbh));
     for (size_t l = 0; l < cv_batch.lv.size(); ++l) cv_batch.lv[l].ms = ms_saved[l];
     cv_batch.as = as_saved;
     pv_batch.ms = ms_saved[0];
-  }
-  kt = kt_saved;
-  std::memcpy(sched_stats, sched_saved, sizeof(sched_saved));
-  spmv_work_seen = work_saved;
-  last_true_rel = true_rel_saved;
-  last_capped = capped_saved;
-  if (d_rows) dev_free(d_rows);
-  if (d_blocks) dev_free(d_blocks);
-  if (rc == SIM3OPT_OK && !restored) {
-    err = pre + "restoring the solver's scalars failed";
-    rc = SIM3OPT_ERR_HIP;
   }
   if (rc) return rc;
   col_counts[0] = nvert;

@@ -216,7 +216,9 @@ int Engine::cov_blocks(const char* who, bool any_pair, bool fixed_zero, double l
   cov_stats[3] = n_on;
   cov_stats[4] = n_off > 0 ? wblocks * 392 : 0;
   cov_stats[5] = n_on > 0 ? 1 : 0;
+  const sim3opt_kernel_times kt0 = kt;  // (not one of the optimiser's linearisations: the counters stay)
   int rc = linearize(err);  // H (and b, unused) at the current estimates
+  kt = kt0;
   if (rc) return rc;
   int32_t* flags = marg_factor.selinv_flags();  // the factor's fail word, the singular flag
   HIPCHK(hipMemsetAsync(flags, 0, 2 * sizeof(int32_t), stream));
@@ -225,37 +227,35 @@ int Engine::cov_blocks(const char* who, bool any_pair, bool fixed_zero, double l
   marg_factor.selinv(&d_sc->maxdiag_bits, flags + 1, stream, n_on > 0);
   HIPCHK(hipGetLastError());
   const int32_t n_out = n_on + n_off;
-  int32_t* d_idx = nullptr;
-  double *d_out = nullptr, *d_W = nullptr;
   int32_t hflags[2] = {0, 0};
   std::vector<double> out((size_t)49 * std::max(n_out, 1));
-  hipError_t e = dev_malloc((void**)&d_idx, sizeof(int32_t) * std::max<size_t>(idx.size(), 1));
-  if (e == hipSuccess) e = dev_malloc((void**)&d_out, sizeof(double) * 49 * (size_t)std::max(n_out, 1));
-  if (e == hipSuccess && n_off > 0) e = dev_malloc((void**)&d_W, sizeof(double) * 49 * (size_t)wblocks);
-  if (e == hipSuccess && !idx.empty())
-    e = hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && n_on > 0) {
-    marg_factor.pick(d_idx, d_idx + n_on, n_on, d_out, stream);
-    e = hipGetLastError();
-  }
-  for (const Chunk& c : chunks) {
-    if (e != hipSuccess) break;
-    marg_factor.cov_paths(d_idx + c.iv, d_idx + c.iv + c.nv, c.nv, d_W, (int32_t)wblocks, stream);
-    marg_factor.cov_pairs(d_idx + c.ip, d_idx + c.ip + c.np, d_idx + c.ip + 2 * c.np, c.np, d_W, (int32_t)wblocks,
-                          d_out + (size_t)49 * (n_on + c.p0), stream);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && n_out > 0)
-    e = hipMemcpyAsync(out.data(), d_out, sizeof(double) * 49 * n_out, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (d_idx) dev_free(d_idx);
-  if (d_out) dev_free(d_out);
-  if (d_W) dev_free(d_W);
-  if (e != hipSuccess) {
-    err = pre + hipGetErrorString(e);
-    return SIM3OPT_ERR_HIP;
-  }
+  DevBuf<int32_t> d_idx;
+  DevBuf<double> d_out, d_W;
+  // (the launches above and below are on the stream: whatever ends this, they are done before the three blocks go)
+  auto body = [&]() -> int {
+    HIPCHK(d_idx.alloc(std::max<size_t>(idx.size(), 1)));
+    HIPCHK(d_out.alloc(49 * (size_t)std::max(n_out, 1)));
+    if (n_off > 0) HIPCHK(d_W.alloc(49 * (size_t)wblocks));
+    if (!idx.empty())
+      HIPCHK(hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, stream));
+    if (n_on > 0) {
+      marg_factor.pick(d_idx, d_idx + n_on, n_on, d_out, stream);
+      HIPCHK(hipGetLastError());
+    }
+    for (const Chunk& c : chunks) {
+      marg_factor.cov_paths(d_idx + c.iv, d_idx + c.iv + c.nv, c.nv, d_W, (int32_t)wblocks, stream);
+      marg_factor.cov_pairs(d_idx + c.ip, d_idx + c.ip + c.np, d_idx + c.ip + 2 * c.np, c.np, d_W, (int32_t)wblocks,
+                            d_out + (size_t)49 * (n_on + c.p0), stream);
+      HIPCHK(hipGetLastError());
+    }
+    if (n_out > 0) HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * 49 * n_out, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, stream));
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  const hipError_t es = hipStreamSynchronize(stream);
+  if (rc) return rc;
+  HIPCHK(es);
   const int32_t fail = hflags[0], singular = hflags[1];
   bool finite = true;
   for (size_t k = 0; k < (size_t)49 * n_out && finite; ++k) finite = std::isfinite(out[k]);
@@ -304,33 +304,31 @@ int Engine::gate_edges(double lambda, int32_t n, const int32_t* v0, const int32_
   if (rc || n == 0) return rc;
   const size_t m = (size_t)n;
   // one device buffer: measurements (8 m), Sigma (147 m), Omega^-1 (49 m), then e (7 m), S (49 m), d2 (m)
-  double* d_buf = nullptr;
-  int32_t* d_v = nullptr;
-  hipError_t e = dev_malloc((void**)&d_buf, sizeof(double) * 261 * m);
-  if (e == hipSuccess) e = dev_malloc((void**)&d_v, sizeof(int32_t) * 2 * m);
-  double *d_meas_c = d_buf, *d_sigma = d_buf + 8 * m, *d_oi = d_buf + 155 * m, *d_e = d_buf + 204 * m,
-         *d_S = d_buf + 211 * m, *d_d2 = d_buf + 260 * m;
-  static_assert(sizeof(Sim3) == 8 * sizeof(double), "Sim3 is eight doubles");
+  DevBuf<double> d_buf;
+  DevBuf<int32_t> d_v;
   std::vector<double> res(57 * m);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_sigma, sigma.data(), sizeof(double) * 147 * m, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_oi, infoinv, sizeof(double) * 49 * m, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_meas_c, meas, sizeof(Sim3) * m, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_v, v0, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_v + m, v1, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
+  auto body = [&]() -> int {
+    HIPCHK(d_buf.alloc(261 * m));
+    HIPCHK(d_v.alloc(2 * m));
+    double *d_meas_c = d_buf, *d_sigma = d_buf + 8 * m, *d_oi = d_buf + 155 * m, *d_e = d_buf + 204 * m,
+           *d_S = d_buf + 211 * m, *d_d2 = d_buf + 260 * m;
+    static_assert(sizeof(Sim3) == 8 * sizeof(double), "Sim3 is eight doubles");
+    HIPCHK(hipMemcpyAsync(d_sigma, sigma.data(), sizeof(double) * 147 * m, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_oi, infoinv, sizeof(double) * 49 * m, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_meas_c, meas, sizeof(Sim3) * m, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_v, v0, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_v + m, v1, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream));
     GateArgs G{n, d_v, d_v + m, reinterpret_cast<const Sim3*>(d_meas_c), d_sigma, d_oi, d_states, mopts(),
                opt.jacobians, opt.dof_mask, opt.fd_delta, d_e, d_S, d_d2};
     hipLaunchKernelGGL(k_gate_edges, dim3((n + WG - 1) / WG), dim3(WG), 0, stream, G);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_e, sizeof(double) * 57 * m, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (d_buf) dev_free(d_buf);
-  if (d_v) dev_free(d_v);
-  if (e != hipSuccess) {
-    err = std::string("gate_edges: ") + hipGetErrorString(e);
-    return SIM3OPT_ERR_HIP;
-  }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(res.data(), d_e, sizeof(double) * 57 * m, hipMemcpyDeviceToHost, stream));
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  const hipError_t es = hipStreamSynchronize(stream);  // (the copies and the launch are done before the blocks go)
+  if (rc) return rc;
+  HIPCHK(es);
   for (size_t k = 0; k < 57 * m; ++k)
     if (!std::isfinite(res[k])) {
       err = "gate_edges: the innovation covariance J Sigma J^T + Omega^-1 of a candidate is not positive definite";
@@ -386,39 +384,41 @@ int Engine::debug_factor(int32_t context, double lambda, const double* vals, con
   HIPCHK(hipStreamSynchronize(stream));
   // scratch: [vals | b | x | max |H_dd| bits | fail, singular]
   const size_t nv = vals ? (size_t)49 * nnzb : 0, nbv = b ? (size_t)n : 0, nx = (size_t)n;
-  double* d_buf = nullptr;
-  HIPCHK(dev_malloc((void**)&d_buf, sizeof(double) * (nv + nbv + nx + 2)));
+  DevBuf<double> d_buf;  // (declared before the body: it outlives debug_forget and the gather of the real system)
+  HIPCHK(d_buf.alloc(nv + nbv + nx + 2));
   double *d_v = d_buf, *d_bb = d_buf + nv, *d_xs = d_bb + nbv;
   unsigned long long* d_bits = reinterpret_cast<unsigned long long*>(d_xs + nx);
   int32_t* d_flags = reinterpret_cast<int32_t*>(d_bits + 1);
-  hipError_t e = hipMemsetAsync(d_xs, 0, sizeof(double) * (nx + 2), stream);
-  if (e == hipSuccess && vals) e = hipMemcpyAsync(d_v, vals, sizeof(double) * nv, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && b) e = hipMemcpyAsync(d_bb, b, sizeof(double) * nbv, hipMemcpyHostToDevice, stream);
-  const unsigned long long* bits_src = &d_sc->maxdiag_bits;
-  unsigned long long hbits = 0;
-  if (e == hipSuccess && with_selinv && vals) {
-    // max |H_dd| of the injected diagonal blocks (the first block of a row), as k_diag_reduce would report it
-    double m = 0.0;
-    for (int32_t i = 0; i < nb; ++i)
-      for (int d = 0; d < 7; ++d) m = std::max(m, std::fabs(vals[(size_t)49 * st.rowptr[i] + 8 * d]));
-    std::memcpy(&hbits, &m, sizeof(double));
-    e = hipMemcpyAsync(d_bits, &hbits, sizeof(hbits), hipMemcpyHostToDevice, stream);
-    bits_src = d_bits;
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (the uploads read the caller's and this frame's memory)
-  if (e == hipSuccess) {
-    F.gather(vals ? d_v : d_vals, b ? d_bb : d_b, stream);
-    e = F.factor(lambda, d_flags, 1, with_solve ? d_xs : nullptr, stream);
-  }
-  if (e == hipSuccess && with_selinv) {
-    F.selinv(bits_src, d_flags + 1, stream, true);
-    e = hipGetLastError();
-  }
   int32_t hflags[2] = {0, 0};
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e == hipSuccess) e = F.debug_read(Aperm, bp, L, Dinv, y, with_solve ? xp : nullptr, with_selinv ? Z : nullptr);
-  if (e == hipSuccess && with_solve) e = hipMemcpy(x, d_xs, sizeof(double) * nx, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost);
+  unsigned long long hbits = 0;
+  auto body = [&]() -> int {
+    HIPCHK(hipMemsetAsync(d_xs, 0, sizeof(double) * (nx + 2), stream));
+    if (vals) HIPCHK(hipMemcpyAsync(d_v, vals, sizeof(double) * nv, hipMemcpyHostToDevice, stream));
+    if (b) HIPCHK(hipMemcpyAsync(d_bb, b, sizeof(double) * nbv, hipMemcpyHostToDevice, stream));
+    const unsigned long long* bits_src = &d_sc->maxdiag_bits;
+    if (with_selinv && vals) {
+      // max |H_dd| of the injected diagonal blocks (the first block of a row), as k_diag_reduce would report it
+      double m = 0.0;
+      for (int32_t i = 0; i < nb; ++i)
+        for (int d = 0; d < 7; ++d) m = std::max(m, std::fabs(vals[(size_t)49 * st.rowptr[i] + 8 * d]));
+      std::memcpy(&hbits, &m, sizeof(double));
+      HIPCHK(hipMemcpyAsync(d_bits, &hbits, sizeof(hbits), hipMemcpyHostToDevice, stream));
+      bits_src = d_bits;
+    }
+    HIPCHK(hipStreamSynchronize(stream));  // (the uploads read the caller's and this frame's memory)
+    F.gather(vals ? d_v : d_vals, b ? d_bb : d_b, stream);
+    HIPCHK(F.factor(lambda, d_flags, 1, with_solve ? d_xs : nullptr, stream));
+    if (with_selinv) {
+      F.selinv(bits_src, d_flags + 1, stream, true);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(F.debug_read(Aperm, bp, L, Dinv, y, with_solve ? xp : nullptr, with_selinv ? Z : nullptr));
+    if (with_solve) HIPCHK(hipMemcpy(x, d_xs, sizeof(double) * nx, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hflags, d_flags, sizeof(hflags), hipMemcpyDeviceToHost));
+    return SIM3OPT_OK;
+  };
+  int rc = body();
   // the argument blocks point into the scratch buffer: forget that before it goes (every user sets the pointers
   // again -- gather, factor, selinv -- before it launches) ...
   const hipError_t es = hipStreamSynchronize(stream);
@@ -427,13 +427,9 @@ int Engine::debug_factor(int32_t context, double lambda, const double* vals, con
   if ((vals || b) && linearized && es == hipSuccess) {
     F.gather(d_vals, d_b, stream);
     const hipError_t e2 = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = e2;
+    if (rc == SIM3OPT_OK) HIPCHK(e2);
   }
-  dev_free(d_buf);
-  if (e != hipSuccess) {
-    err = pre + hipGetErrorString(e);
-    return SIM3OPT_ERR_HIP;
-  }
+  if (rc) return rc;
   *fail = hflags[0];
   if (with_selinv) *singular = hflags[1];
   if (bord) std::memcpy(bord, P.bord.data(), sizeof(int32_t) * P.bord.size());

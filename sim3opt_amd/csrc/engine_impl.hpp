@@ -60,15 +60,6 @@ namespace sim3opt {
 
 using sim3::Sim3;
 
-#define HIPCHK(call)                                                        \
-  do {                                                                      \
-    hipError_t e_ = (call);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);              \
-      return SIM3OPT_ERR_HIP;                                               \
-    }                                                                       \
-  } while (0)
-
 #ifndef SIM3OPT_COARSE_CH
 #define SIM3OPT_COARSE_CH 8     // blocks per pipeline step of the coarse levels' passes (one-system cycle; tuning: 16)
 #endif
@@ -162,16 +153,6 @@ struct EdgeArgs;  // lm_kernels.hpp
 // ------------------------------------------------------------------------------------------
 // Engine
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static hipError_t upload(StagedUploads& staged, hipStream_t stream, T*& dptr, const std::vector<T>& h) {
-  const size_t bytes = sizeof(T) * std::max<size_t>(h.size(), 1);
-  hipError_t e = dev_malloc((void**)&dptr, bytes);
-  if (e != hipSuccess) return e;
-  // (small arrays: staged in pinned memory and enqueued; init synchronises once at its end)
-  if (!h.empty()) e = staged.put(dptr, h.data(), sizeof(T) * h.size(), stream);
-  return e;
-}
-
 static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
 static inline int grid_for(int64_t items, int per_block) {
   const int64_t g = (items + per_block - 1) / per_block;
@@ -186,6 +167,12 @@ class Engine {
   int64_t nnzb = 0;
   bool has_info = false, has_kernel = false;
   hipStream_t stream = nullptr;
+  // every device block of init() and of what it calls (the hierarchy, the exchange plans, the ranged arrays), and the
+  // few allocated at their first use (d_ptab, d_dl, the kernels' arrays): given back by release_under_device()
+  DevArena mem;
+  // (small arrays: staged in pinned memory and enqueued; init synchronises once at its end)
+  template <typename T>
+  hipError_t upload(T*& dptr, const std::vector<T>& h) { return mem.upload(dptr, h, stream, &staged); }
   // graph
   Sim3 *d_states = nullptr, *d_backup = nullptr, *d_meas = nullptr;
   int32_t *d_ev0 = nullptr, *d_ev1 = nullptr, *d_hidx = nullptr, *d_active = nullptr;
@@ -203,7 +190,7 @@ class Engine {
   // options.debug_full_arrays: the whole array, everything outside the range filled with 0xFF bytes (NaN as
   // float and as double); check_foreign_ranges() finds a write there, a read shows up as NaN in the results --
   // the test of the ranges (tests/test_distributed_gpu.py).  One rank: lo = 0, hi = total.
-  struct RangedArray { void* alloc; size_t elem; int64_t total, lo, hi; };
+  struct RangedArray { void* alloc; size_t elem; int64_t total, lo, hi; };  // (alloc: a block of `mem`)
   std::vector<RangedArray> ranged;
   template <typename T>
   int alloc_ranged(T*& virt, int64_t lo, int64_t hi, int64_t total, std::string& err) {
@@ -212,13 +199,12 @@ class Engine {
     hi = std::max(lo, std::min(hi, total));
     T* p = nullptr;
     if (opt.debug_full_arrays) {
-      HIPCHK(dev_malloc((void**)&p, sizeof(T) * (size_t)total));
+      HIPCHK(mem.raw(p, (size_t)total));
       HIPCHK(hipMemset(p, 0xFF, sizeof(T) * (size_t)total));
       if (hi > lo) HIPCHK(hipMemset(p + lo, 0, sizeof(T) * (size_t)(hi - lo)));
       virt = p;
     } else {
-      HIPCHK(dev_malloc((void**)&p, sizeof(T) * (size_t)std::max<int64_t>(hi - lo, 1)));
-      HIPCHK(hipMemset(p, 0, sizeof(T) * (size_t)std::max<int64_t>(hi - lo, 1)));
+      HIPCHK(mem.alloc(p, (size_t)(hi - lo), nullptr));
       virt = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) - sizeof(T) * (size_t)lo);
     }
     ranged.push_back({p, sizeof(T), total, lo, hi});
@@ -254,7 +240,6 @@ class Engine {
   // spans (per rank) of a level's vectors / block values: set where a partitioned level meets a replicated one
   std::vector<std::vector<int64_t>> lvl_offs, lvl_blk_offs;
   std::vector<AmgLevel> amg;
-  std::vector<void*> amg_owned;
   double *d_P = nullptr, *d_Ainv = nullptr, *d_Ainv2 = nullptr, *d_piv = nullptr, *d_az = nullptr;
   int32_t* d_row2v = nullptr;
   bool use_amg = false, amg_stale = true;
@@ -324,7 +309,7 @@ class Engine {
   PcgView pv_one;    // d_x ... d_az, d_sc / h_sc, d_b (init)
   PcgView pv_batch;  // b_x ... b_az, d_bsc / h_bsc (batch_alloc)
   // ---- several right-hand sides at once (engine_pcg.hip): the rejected trials of an LM iteration ----
-  std::vector<void*> batch_owned;
+  DevArena batch_mem;
   double *b_x = nullptr, *b_r = nullptr, *b_z = nullptr, *b_p = nullptr, *b_q = nullptr, *b_s = nullptr, *b_az = nullptr;
   double *b_Ainv = nullptr, *b_diag64 = nullptr, *b_part_a = nullptr, *b_part_b = nullptr;
   int64_t b_vs = 0, b_as = 0;
@@ -480,20 +465,6 @@ class Engine {
   int pool_drain(std::string& err);
 
   // ---- aggregation multigrid ----
-  template <typename T>
-  int amg_up(T*& dptr, const std::vector<T>& h, std::string& err) {
-    HIPCHK(dev_malloc((void**)&dptr, sizeof(T) * std::max<size_t>(h.size(), 1)));
-    amg_owned.push_back(dptr);
-    if (!h.empty()) HIPCHK(staged.put(dptr, h.data(), sizeof(T) * h.size(), stream));
-    return SIM3OPT_OK;
-  }
-  int amg_alloc(double*& dptr, size_t count, std::string& err) {
-    HIPCHK(dev_malloc((void**)&dptr, sizeof(double) * std::max<size_t>(count, 1)));
-    amg_owned.push_back(dptr);
-    HIPCHK(hipMemset(dptr, 0, sizeof(double) * std::max<size_t>(count, 1)));
-    return SIM3OPT_OK;
-  }
-
   // structure of the hierarchy (once per initialize); leaves use_amg false when the graph does
   // not coarsen (block-Jacobi is used then)
   std::vector<AmgLevelHost> amg_host;  // kept between amg_init and amg_bind
@@ -576,8 +547,8 @@ class Engine {
   // (H + lambda I) y = e_{7 b + c}, by the PCG the graph was initialised with -- on a multigrid graph up to KB columns
   // per pass over the blocks (pcg_batch with per-system right-hand sides and ONE set-up), else one at a time
   // (pcg_attempt) -- each checked on the device by its TRUE residual in the 2-norm against options.cov_rel_tol and
-  // refined at most twice.  The solver's state is put back as the diagnostic read-outs do.
-  std::vector<void*> cols_owned;
+  // refined at most twice.  The solver's state is put back as the diagnostic read-outs do (SolverSnapshot).
+  DevArena cols_mem;
   double *c_g = nullptr, *c_y = nullptr, *c_r = nullptr, *c_d = nullptr;  // KB right-hand sides, solutions, residuals, refinement right-hand sides
   double* c_nrm = nullptr;  // [||r||^2, ||g||^2] per system
   int64_t c_vs = 0;
@@ -669,14 +640,13 @@ class Engine {
               int probe_budget = 0, bool* abandoned = nullptr);
 
   // ---- diagnostic read-outs of the preconditioners (tests/test_gpu_preconditioners.py; one GPU only) ----
-  // They run the set-up a PCG solve runs and then put back what it wrote of the solver's state: the DevScalars on
-  // both sides.  Everything else they touch -- the level numbers for a lambda, d_Minv, the PCG vectors -- is
-  // rewritten by every solve before it is read, and amg_setup is a function of the linearisation alone, so a
-  // solve or optimize() that follows is bit for bit the one without the read-out.
-  // (a view's V.nsc scalars: the first nrhs not done, at lambda[k], the rest finished)
-  int diag_begin(PcgView& V, const double* lambda, int nrhs, DevScalars* saved_d, DevScalars* saved_h, std::string& err);
-  // (rc: what happened in between; returned unless it was fine and the restoring failed)
-  int diag_end(PcgView& V, const DevScalars* saved_d, const DevScalars* saved_h, int rc, std::string& err);
+  // They run the set-up a PCG solve runs between SolverSnapshot::take and put_back (below).  Everything else they
+  // touch -- the level numbers for a lambda, d_Minv, the PCG vectors -- is rewritten by every solve before it is
+  // read, and amg_setup is a function of the linearisation alone, so a solve or optimize() that follows is bit for
+  // bit the one without the read-out.
+  // the PCG fields of a view's V.nsc scalars as a solve sets them: the first nrhs not done, at lambda[k], the rest
+  // finished (after a take(): `from` is the snapshot's device copy of them)
+  int diag_begin(PcgView& V, const double* lambda, int nrhs, const DevScalars* from, std::string& err);
   // amg_setup if stale, amg_prepare(lambda) -- as a solve -- and, unlike it, a failed pivot is SIM3OPT_ERR_STATE
   int amg_numbers(double lambda, std::string& err);                                      // engine_amg.hip
   int amg_level_readout(double lambda, int32_t level, int32_t* rowptr, int32_t* colidx, double* vals, float* vals32,
@@ -718,6 +688,24 @@ class Engine {
   std::vector<sim3opt_tr_stats> tr_stats;  // per iteration of the last dogleg run
   double* d_dl = nullptr;  // dogleg: 4 x MAX_GRID dot partials, then the 8 scalars (DL_OUT)
   double* h_dl = nullptr;  // pinned copy of the scalars
+};
+
+// What a read-out that runs the solver's own launches puts back, so that the next solve or optimize() is the one
+// without it: the one-system scalars on the device and in h_sc, the batch's KB scalars on both sides once the batch
+// exists, and the host's counters and caches -- kt, sched_stats, spmv_work_seen, last_true_rel, last_capped, chi_known,
+// chi_cache.  (engine_pcg.hip)
+struct SolverSnapshot {
+  int take(Engine& e, std::string& err);  // synchronises the stream first
+  // rc: what happened in between; returned unless it was fine and the restoring failed
+  int put_back(int rc, std::string& err);
+  Engine* eng = nullptr;
+  bool batch = false;
+  DevScalars d_one, h_one, d_batch[KB], h_batch[KB];
+  sim3opt_kernel_times kt;
+  int64_t sched[4];
+  long long work_seen;
+  double true_rel, chi_cache;
+  bool capped, chi_known;
 };
 
 }  // namespace sim3opt

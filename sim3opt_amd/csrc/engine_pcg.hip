@@ -74,10 +74,10 @@ int Engine::level_part_init(int l, int32_t nb_l, const int32_t* rowptr_l, const 
     lp.send_offs[r] = 7 * (int64_t)sseg[r];
     lp.recv_offs[r] = 7 * (int64_t)rseg[r];
   }
-  HIPCHK(upload(staged, stream, lp.d_send, srows));
-  HIPCHK(upload(staged, stream, lp.d_recv, rrows));
-  HIPCHK(dev_malloc((void**)&lp.d_sbuf, sizeof(double) * 7 * std::max<size_t>(srows.size(), 1)));
-  HIPCHK(dev_malloc((void**)&lp.d_rbuf, sizeof(double) * 7 * std::max<size_t>(rrows.size(), 1)));
+  HIPCHK(upload(lp.d_send, srows));
+  HIPCHK(upload(lp.d_recv, rrows));
+  HIPCHK(mem.raw(lp.d_sbuf, 7 * std::max<size_t>(srows.size(), 1)));
+  HIPCHK(mem.raw(lp.d_rbuf, 7 * std::max<size_t>(rrows.size(), 1)));
   return SIM3OPT_OK;
 }
 
@@ -685,20 +685,11 @@ int Engine::pcg_run(PcgView& V, int prec, int nsetup, bool check_true, bool* set
 int Engine::batch_alloc(std::string& err) {
   if (batch_ready) return SIM3OPT_OK;
   const int nl = (int)amg.size();
-  auto alloc = [&](double*& p, size_t count) -> int {
-    HIPCHK(dev_malloc((void**)&p, sizeof(double) * std::max<size_t>(count, 1)));
-    batch_owned.push_back(p);
-    HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * std::max<size_t>(count, 1), stream));
-    return SIM3OPT_OK;
-  };
   // (schedule only -- the results do not depend on it: which levels run one system per grid slice)
   if (const char* ev = std::getenv("SIM3OPT_BATCH_SLICE_BLOCKS")) b_slice_blocks = std::atoll(ev);
   b_vs = pad64(n);
   double** v0[] = {&b_x, &b_r, &b_z, &b_p, &b_q, &b_s, &b_az};
-  for (double** v : v0) {
-    int rc = alloc(*v, (size_t)KB * b_vs);
-    if (rc) return rc;
-  }
+  for (double** v : v0) HIPCHK(batch_mem.alloc(*v, (size_t)KB * b_vs, stream));
   // what the cycle (engine_amg.hip) works on for a batch: KB systems per level
   CycleView& V = cv_batch;
   V = CycleView();
@@ -709,29 +700,23 @@ int Engine::batch_alloc(std::string& err) {
     const AmgLevel& L = amg[l];
     B.vs = l == 0 ? b_vs : pad64(7 * (int64_t)L.nb);
     B.ms = (int64_t)49 * L.nb;
-    int rc = alloc(B.Minv, (size_t)KB * B.ms);
-    if (rc) return rc;
+    HIPCHK(batch_mem.alloc(B.Minv, (size_t)KB * B.ms, stream));
     if (l == 0) {
       B.r = b_r; B.x = b_z; B.t = b_az;
     } else {
-      if ((rc = alloc(B.r, (size_t)KB * B.vs))) return rc;
-      if ((rc = alloc(B.x, (size_t)KB * B.vs))) return rc;
-      if ((rc = alloc(B.t, (size_t)KB * B.vs))) return rc;
-      HIPCHK(dev_malloc((void**)&B.diag32, sizeof(float) * (size_t)KB * B.ms));
-      batch_owned.push_back(B.diag32);
-      HIPCHK(hipMemsetAsync(B.diag32, 0, sizeof(float) * (size_t)KB * B.ms, stream));
+      HIPCHK(batch_mem.alloc(B.r, (size_t)KB * B.vs, stream));
+      HIPCHK(batch_mem.alloc(B.x, (size_t)KB * B.vs, stream));
+      HIPCHK(batch_mem.alloc(B.t, (size_t)KB * B.vs, stream));
+      HIPCHK(batch_mem.alloc(B.diag32, (size_t)KB * B.ms, stream));
     }
   }
   const size_t nc = (size_t)7 * amg[nl - 1].nb;
   b_as = (int64_t)(nc * nc);
-  int rc = alloc(b_Ainv, (size_t)KB * b_as);
-  if (rc) return rc;
-  if ((rc = alloc(b_diag64, (size_t)KB * 49 * amg[nl - 1].nb))) return rc;
-  if ((rc = alloc(b_part_a, (size_t)KB * SPAN_GRID_MAX))) return rc;
-  if ((rc = alloc(b_part_b, (size_t)KB * SPAN_GRID_MAX))) return rc;
-  HIPCHK(dev_malloc((void**)&d_bsc, sizeof(DevScalars) * KB));
-  batch_owned.push_back(d_bsc);
-  HIPCHK(hipMemsetAsync(d_bsc, 0, sizeof(DevScalars) * KB, stream));
+  HIPCHK(batch_mem.alloc(b_Ainv, (size_t)KB * b_as, stream));
+  HIPCHK(batch_mem.alloc(b_diag64, (size_t)KB * 49 * amg[nl - 1].nb, stream));
+  HIPCHK(batch_mem.alloc(b_part_a, (size_t)KB * SPAN_GRID_MAX, stream));
+  HIPCHK(batch_mem.alloc(b_part_b, (size_t)KB * SPAN_GRID_MAX, stream));
+  HIPCHK(batch_mem.alloc(d_bsc, (size_t)KB, stream));
   HIPCHK(host_malloc((void**)&h_bsc, sizeof(DevScalars) * KB));
   V.sc = d_bsc;
   V.Ainv = b_Ainv;
@@ -758,9 +743,7 @@ int Engine::batch_alloc(std::string& err) {
 }
 
 void Engine::batch_release() {
-  for (void* p : batch_owned)
-    if (p) dev_free(p);
-  batch_owned.clear();
+  batch_mem.release();
   if (h_bsc) host_free(h_bsc);
   h_bsc = nullptr;
   d_bsc = nullptr;
@@ -841,15 +824,54 @@ int Engine::lm_trial_solve(int q, double lambda, double ni, const double** x, in
 }
 
 // ---- diagnostic read-outs (see engine_impl.hpp) ----
-int Engine::diag_begin(PcgView& V, const double* lambda, int nrhs, DevScalars* saved_d, DevScalars* saved_h,
-                       std::string& err) {
-  HIPCHK(hipStreamSynchronize(stream));
-  std::memcpy(saved_h, V.h_sc, sizeof(DevScalars) * V.nsc);
-  HIPCHK(hipMemcpy(saved_d, V.sc, sizeof(DevScalars) * V.nsc, hipMemcpyDeviceToHost));
-  // the PCG fields as a solve sets them: the first nrhs not done (level-0 launches test it), no failure yet, their damping
+int SolverSnapshot::take(Engine& e, std::string& err) {
+  eng = &e;
+  HIPCHK(hipStreamSynchronize(e.stream));
+  h_one = *e.h_sc;
+  HIPCHK(hipMemcpy(&d_one, e.d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
+  batch = e.batch_ready;
+  if (batch) {
+    std::memcpy(h_batch, e.h_bsc, sizeof(h_batch));
+    HIPCHK(hipMemcpy(d_batch, e.d_bsc, sizeof(d_batch), hipMemcpyDeviceToHost));
+  }
+  kt = e.kt;
+  std::memcpy(sched, e.sched_stats, sizeof(sched));
+  work_seen = e.spmv_work_seen;
+  true_rel = e.last_true_rel;
+  capped = e.last_capped;
+  chi_known = e.chi_known;
+  chi_cache = e.chi_cache;
+  return SIM3OPT_OK;
+}
+
+int SolverSnapshot::put_back(int rc, std::string& err) {
+  Engine& e = *eng;
+  bool ok = hipStreamSynchronize(e.stream) == hipSuccess;
+  ok = ok && hipMemcpy(e.d_sc, &d_one, sizeof(DevScalars), hipMemcpyHostToDevice) == hipSuccess;
+  *e.h_sc = h_one;
+  if (batch) {
+    ok = ok && hipMemcpy(e.d_bsc, d_batch, sizeof(d_batch), hipMemcpyHostToDevice) == hipSuccess;
+    std::memcpy(e.h_bsc, h_batch, sizeof(h_batch));
+  }
+  e.kt = kt;
+  std::memcpy(e.sched_stats, sched, sizeof(sched));
+  e.spmv_work_seen = work_seen;
+  e.last_true_rel = true_rel;
+  e.last_capped = capped;
+  e.chi_known = chi_known;
+  e.chi_cache = chi_cache;
+  if (rc == SIM3OPT_OK && !ok) {
+    err = "restoring the solver's scalars failed";
+    rc = SIM3OPT_ERR_HIP;
+  }
+  return rc;
+}
+
+int Engine::diag_begin(PcgView& V, const double* lambda, int nrhs, const DevScalars* from, std::string& err) {
+  // no system done among the first nrhs (level-0 launches test it), no failure yet, their damping
   DevScalars s[KB];
   for (int k = 0; k < V.nsc; ++k) {
-    s[k] = saved_d[k];
+    s[k] = from[k];
     s[k].rz[0] = s[k].rz[1] = s[k].alpha[0] = s[k].alpha[1] = s[k].rz0 = 0.0;
     s[k].iter = 0;
     s[k].done = k < nrhs ? 0 : 1;
@@ -858,17 +880,6 @@ int Engine::diag_begin(PcgView& V, const double* lambda, int nrhs, DevScalars* s
   }
   HIPCHK(hipMemcpy(V.sc, s, sizeof(DevScalars) * V.nsc, hipMemcpyHostToDevice));
   return SIM3OPT_OK;
-}
-
-int Engine::diag_end(PcgView& V, const DevScalars* saved_d, const DevScalars* saved_h, int rc, std::string& err) {
-  const bool put_back = hipStreamSynchronize(stream) == hipSuccess &&
-                        hipMemcpy(V.sc, saved_d, sizeof(DevScalars) * V.nsc, hipMemcpyHostToDevice) == hipSuccess;
-  std::memcpy(V.h_sc, saved_h, sizeof(DevScalars) * V.nsc);
-  if (rc == SIM3OPT_OK && !put_back) {
-    err = "restoring the solver's scalars failed";
-    rc = SIM3OPT_ERR_HIP;
-  }
-  return rc;
 }
 
 int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r, double* z, std::string& err) {
@@ -887,12 +898,14 @@ int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r
   const int nloc = r1 - r0;
   const int gv = grid_for((nloc + 8) / 9, 4);
   const int nseg = (nloc + chain_seg - 1) / chain_seg;
-  DevScalars sd, sh;
-  int rc = diag_begin(pv_one, &lambda, 1, &sd, &sh, err);
+  SolverSnapshot snap;
+  int rc = snap.take(*this, err);
   if (rc) return rc;
   auto body = [&]() -> int {
+    int rc2 = diag_begin(pv_one, &lambda, 1, &snap.d_one, err);
+    if (rc2) return rc2;
     pv_one.lam[0] = lambda;
-    int rc2 = pcg_setup(pv_one, prec, 1, err);
+    rc2 = pcg_setup(pv_one, prec, 1, err);
     if (rc2) return rc2;
     HIPCHK(hipGetLastError());
     rc2 = fetch_scalars(err);
@@ -922,7 +935,7 @@ int Engine::precond_apply(int prec, double lambda, int32_t nrhs, const double* r
     }
     return SIM3OPT_OK;
   };
-  return diag_end(pv_one, &sd, &sh, body(), err);
+  return snap.put_back(body(), err);
 }
 
 int engine_precond_apply(Engine* e, int32_t prec, double lambda, int32_t nrhs, const double* r, double* z,
@@ -955,10 +968,12 @@ int Engine::operator_apply(int32_t nrhs, const double* lambda, const double* p, 
   PcgView& V = nrhs > 1 ? pv_batch : pv_one;
   int rc = nrhs > 1 ? batch_alloc(err) : SIM3OPT_OK;
   if (rc) return rc;
-  DevScalars sd[KB], sh[KB];
-  rc = diag_begin(V, lambda, nrhs, sd, sh, err);
+  SolverSnapshot snap;  // (after batch_alloc: the batch's scalars are in it)
+  rc = snap.take(*this, err);
   if (rc) return rc;
   auto body = [&]() -> int {
+    int rc2 = diag_begin(V, lambda, nrhs, V.batch ? snap.d_batch : &snap.d_one, err);
+    if (rc2) return rc2;
     // p -> what a solve hands its SpMV (d_z; a batch: b_az), rvec -> r; the dampings travel in the scalars as in a solve
     double* const in = V.batch ? V.az : V.z;
     const size_t bytes = sizeof(double) * (size_t)n;
@@ -967,7 +982,7 @@ int Engine::operator_apply(int32_t nrhs, const double* lambda, const double* p, 
       HIPCHK(hipMemcpyAsync(in + (size_t)k * V.vs, p + (size_t)k * n, bytes, hipMemcpyHostToDevice, stream));
       if (rvec) HIPCHK(hipMemcpyAsync(V.r + (size_t)k * V.vs, rvec + (size_t)k * n, bytes, hipMemcpyHostToDevice, stream));
     }
-    int rc2 = pcg_spmv(V, nrhs, in, rvec ? V.r : nullptr, false, err);
+    rc2 = pcg_spmv(V, nrhs, in, rvec ? V.r : nullptr, false, err);
     if (rc2) return rc2;
     BATCH_DISPATCH(nrhs, hipLaunchKernelGGL((k_final_sum2<KS>), dim3(1), dim3(WG), 0, stream, (const double*)V.part_a,
                        (const double*)V.part_b, spmv_grid(), V.pstride, &V.sc->tmp_pq, SC_DOUBLES));
@@ -982,7 +997,7 @@ int Engine::operator_apply(int32_t nrhs, const double* lambda, const double* p, 
     }
     return SIM3OPT_OK;
   };
-  return diag_end(V, sd, sh, body(), err);
+  return snap.put_back(body(), err);
 }
 
 int engine_spmv_spans(Engine* e, int32_t* n_spans, int32_t* wrow, std::string& err) {

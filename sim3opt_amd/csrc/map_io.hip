@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "devmem.hpp"
 #include "sim3_math.hpp"
 
 namespace {
@@ -97,31 +98,26 @@ extern "C" int sim3opt_reanchor_points(int32_t n_frames, const double* old_Rt,
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SIM3OPT_ERR_NO_DEVICE;
   if (device >= 0 && hipSetDevice(device) != hipSuccess) return SIM3OPT_ERR_HIP;
-  int32_t *d_last = nullptr, *d_of = nullptr;
-  double *d_rt = nullptr, *d_pts = nullptr;
-  sim3::Sim3* d_st = nullptr;
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  chk(hipMalloc((void**)&d_last, sizeof(int32_t) * (size_t)n_points));
-  chk(hipMalloc((void**)&d_of, sizeof(int32_t) * (size_t)(n_obs > 0 ? n_obs : 1)));
-  chk(hipMalloc((void**)&d_rt, sizeof(double) * 12 * (size_t)n_frames));
-  chk(hipMalloc((void**)&d_st, sizeof(sim3::Sim3) * (size_t)n_frames));
-  chk(hipMalloc((void**)&d_pts, sizeof(double) * 3 * (size_t)n_points));
-  if (e == hipSuccess) {
-    chk(hipMemcpy(d_last, last.data(), sizeof(int32_t) * (size_t)n_points, hipMemcpyHostToDevice));
-    if (n_obs) chk(hipMemcpy(d_of, obs_frame, sizeof(int32_t) * (size_t)n_obs, hipMemcpyHostToDevice));
-    chk(hipMemcpy(d_rt, old_Rt, sizeof(double) * 12 * (size_t)n_frames, hipMemcpyHostToDevice));
-    chk(hipMemcpy(d_st, new_states, sizeof(double) * 8 * (size_t)n_frames, hipMemcpyHostToDevice));
-    chk(hipMemcpy(d_pts, points, sizeof(double) * 3 * (size_t)n_points, hipMemcpyHostToDevice));
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_reanchor, dim3((n_points + 255) / 256), dim3(256), 0, 0, n_points, d_last,
-                       d_of, d_rt, d_st, d_pts);
-    chk(hipGetLastError());
-    chk(hipMemcpy(points, d_pts, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost));
-  }
-  (void)hipFree(d_last); (void)hipFree(d_of); (void)hipFree(d_rt); (void)hipFree(d_st); (void)hipFree(d_pts);
-  return e == hipSuccess ? SIM3OPT_OK : SIM3OPT_ERR_HIP;
+  sim3opt::DevBuf<int32_t> d_last, d_of;
+  sim3opt::DevBuf<double> d_rt, d_pts;
+  sim3opt::DevBuf<sim3::Sim3> d_st;
+  std::string err;  // (this call reports a code only)
+  HIPCHK(d_last.alloc((size_t)n_points));
+  HIPCHK(d_of.alloc((size_t)(n_obs > 0 ? n_obs : 1)));
+  HIPCHK(d_rt.alloc(12 * (size_t)n_frames));
+  HIPCHK(d_st.alloc((size_t)n_frames));
+  HIPCHK(d_pts.alloc(3 * (size_t)n_points));
+  HIPCHK(hipMemcpy(d_last, last.data(), sizeof(int32_t) * (size_t)n_points, hipMemcpyHostToDevice));
+  if (n_obs) HIPCHK(hipMemcpy(d_of, obs_frame, sizeof(int32_t) * (size_t)n_obs, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_rt, old_Rt, sizeof(double) * 12 * (size_t)n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_st, new_states, sizeof(double) * 8 * (size_t)n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_pts, points, sizeof(double) * 3 * (size_t)n_points, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_reanchor, dim3((n_points + 255) / 256), dim3(256), 0, 0, n_points, d_last.get(), d_of.get(),
+                     d_rt.get(), d_st.get(), d_pts.get());
+  HIPCHK(hipGetLastError());
+  // (a copy on the null stream: the launch is done when it returns, before the blocks go)
+  HIPCHK(hipMemcpy(points, d_pts, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost));
+  return SIM3OPT_OK;
 }
 
 extern "C" int sim3opt_write_g2o(sim3opt_graph* g, const char* path) {

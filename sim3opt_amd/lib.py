@@ -253,6 +253,7 @@ SYMBOLS = {
     "sim3opt_load_kitti_direct": (C.c_int, [_vp, C.c_char_p, C.c_int32]),
     "sim3opt_load_kitti_gt_loops": (C.c_int, [_vp, C.c_char_p]),
     "sim3opt_release_device_cache": (None, []),
+    "sim3opt_device_memory_in_use": (None, [C.POINTER(C.c_int64)]),
     "sim3opt_write_poses": (C.c_int, [_vp, C.c_char_p, _ip]),
     "sim3opt_stepwise_scale_init": (C.c_int, [_vp, _dp]),
     "sim3opt_read_keyframe_bin": (C.c_int, [C.c_char_p, _ip, _dp, _dp, _ip, C.POINTER(C.c_uint32), _dp,
@@ -367,6 +368,14 @@ class Sim3OptError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"sim3opt error {code}: {msg}")
         self.code = code
+
+
+def device_memory_in_use():
+    """(blocks, bytes) of device memory the library's handles and calls of this process hold right now
+    (sim3opt_device_memory_in_use): a call that keeps no device memory leaves both as they were."""
+    o = (C.c_int64 * 2)()
+    load().sim3opt_device_memory_in_use(o)
+    return int(o[0]), int(o[1])
 
 
 def default_options(**kw):
