@@ -17,7 +17,7 @@ EIGEN_INC ?= -Itests/mock_eigen
 all: $(LIB) oracle/liboracle_sim3.so
 
 $(LIB): $(SRCS) $(HDRS)
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-result -o $@ $(SRCS) -ldl
+	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-result -pthread -o $@ $(SRCS) -ldl
 
 oracle/liboracle_sim3.so: oracle/sim3_oracle.c oracle/sim3_oracle.h
 	$(MAKE) -C oracle liboracle_sim3.so

@@ -16,6 +16,10 @@
  *
  * All computation runs on the GPU (HIP, gfx950).  There is no CPU fallback: if no
  * HIP device is usable, sim3opt_initialize returns SIM3OPT_ERR_NO_DEVICE.
+ *
+ * Several GPUs: one process per GPU with a communicator handed in (sim3opt_comm_init,
+ * sim3opt_comm_init_callbacks), or one single-threaded caller and the ranks inside the library
+ * (sim3opt_set_devices, sim3opt_rank_count, sim3opt_local_rows_of_rank, sim3opt_device_bytes_of_rank).
  */
 #ifndef SIM3OPT_H
 #define SIM3OPT_H
@@ -35,7 +39,7 @@ enum {
   SIM3OPT_ERR_NO_DEVICE = -3,  /* no usable HIP device                               */
   SIM3OPT_ERR_HIP = -4,        /* a HIP runtime call failed                          */
   SIM3OPT_ERR_IO = -5,         /* file could not be read / parsed                    */
-  SIM3OPT_ERR_COMM = -6        /* RCCL communicator failure                          */
+  SIM3OPT_ERR_COMM = -6        /* communicator failure (RCCL, or a rank of the process) */
 };
 
 /* Robust kernels of an edge (g2o RobustKernel*, robust_kernel_impl.cpp).  rho(e2) and w = rho'(e2) at
@@ -658,6 +662,32 @@ int sim3opt_halo_plan(sim3opt_graph* g, int32_t world, int32_t rank, int32_t* n_
                       int32_t* send_rows, int32_t* send_seg, int32_t* recv_rows, int32_t* recv_seg);
 /* block-row range [begin, end) this graph's rank owns (valid after initialize) */
 int sim3opt_local_rows(const sim3opt_graph* g, int32_t* begin, int32_t* end);
+
+/* ---- one process drives N devices (the caller stays single-threaded) ----
+ * sim3opt_set_devices gives the handle n ranks (1..8) INSIDE the library: a worker thread per rank, bound to
+ * devices[r], with its own engine; the ranks exchange through each other's device memory (peer access over xGMI
+ * between distinct devices, enabled here; a pair without it: sim3opt_initialize returns SIM3OPT_ERR_COMM and names
+ * the pair).  An ordinal may repeat: N ranks on one GPU, the same kernels.  Call between create and initialize;
+ * collective_timeout_s <= 0: 120 s.  SIM3OPT_ERR_ARG: n out of range, NULL, an ordinal below 0 or beyond the device
+ * count; SIM3OPT_ERR_STATE: after initialize, or after sim3opt_comm_init* on this handle (and sim3opt_comm_init*
+ * after this call).  n == 1 only selects the device: the plain one-rank graph.
+ *
+ * With n > 1 the handle stays ONE object and every entry is called once, from one thread:
+ *   - what a partitioned graph serves runs on all ranks and returns rank 0's answer (all ranks hold a replica of
+ *     every estimate and return identical results): initialize, optimize, chi2, get / set vertex(es), the stats,
+ *     set_edge_kernels, edge_chi2 / edge_errors, linearize, amg_in_use, preconditioner_in_use, linear_solver_in_use,
+ *     kernel_times, comm_times;
+ *   - what a partitioned graph refuses stays SIM3OPT_ERR_STATE: marginals, covariances, gate_edges, solve, the
+ *     operator, preconditioner and factor read-outs;
+ *   - sim3opt_local_rows / sim3opt_device_bytes answer for rank 0, their _of_rank siblings for any rank.
+ * A rank that fails, or waits longer than the timeout for its peers (its message names the collective's sequence
+ * number), releases the others with SIM3OPT_ERR_COMM; the handle then answers SIM3OPT_ERR_STATE until it is
+ * destroyed.  Nothing in here ends the process.  (INTEGRATION.md has the table, DESIGN.md section 7 the protocol.) */
+int sim3opt_set_devices(sim3opt_graph* g, int32_t n, const int32_t* devices, double collective_timeout_s);
+/* ranks this handle drives: n of sim3opt_set_devices, else 1 */
+int sim3opt_rank_count(const sim3opt_graph* g);
+int sim3opt_local_rows_of_rank(const sim3opt_graph* g, int32_t rank, int32_t* begin, int32_t* end);
+int sim3opt_device_bytes_of_rank(const sim3opt_graph* g, int32_t rank, int64_t bytes[2]);
 
 /* Returns the device blocks the library keeps for re-use (graphs that are re-initialised after growing
  * by an edge find their predecessor's buffers, csrc/devmem.cpp; at most 1 GB) to the HIP runtime, together

@@ -644,6 +644,13 @@ class SparseOptimizer {  // g2o::SparseOptimizer (kitti_surf.cpp:552, 558, 620, 
     auto it = verts_.find(id);
     return it == verts_.end() ? nullptr : it->second.get();
   }
+  // Not g2o: one rank of the row-partitioned solver per listed HIP device ordinal (1 to 8, repeats allowed), driven by
+  // the library's own threads; this optimizer stays one object, called from one thread (sim3opt_set_devices).  Before
+  // initializeOptimization(); false when the library refuses the list.
+  bool setDevices(const std::vector<int>& devices) {
+    std::vector<int32_t> d(devices.begin(), devices.end());
+    return sim3opt_set_devices(g_, (int32_t)d.size(), d.data(), 0.0) == SIM3OPT_OK;
+  }
   bool initializeOptimization() { return sim3opt_initialize(g_) == SIM3OPT_OK; }
   int optimize(int iterations) { return sim3opt_optimize(g_, iterations); }
   void computeActiveErrors() {}

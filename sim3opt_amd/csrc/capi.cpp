@@ -19,6 +19,7 @@
 #include "direct.hpp"
 #include "engine.hpp"
 #include "graph.hpp"
+#include "rank_group.hpp"
 #include "robust.hpp"
 #include "sim3_jac.hpp"
 
@@ -37,7 +38,14 @@ struct sim3opt_graph {
   std::string err;
   Comm comm;        // handed to the engine at initialize
   bool comm_set = false;
+  bool comm_called = false;  // sim3opt_comm_init* was called: the ranks come from outside (no sim3opt_set_devices)
+  // sim3opt_set_devices: with n > 1 the ranks live in here, one engine each, and `engine` is rank 0's (not owned)
+  bool devices_set = false;
+  int32_t device_one = -1;  // n == 1: the ordinal it chose
+  std::unique_ptr<RankGroup> group;
   ~sim3opt_graph() {
+    if (group) engine = nullptr;  // (the group releases the engines, each under its own device)
+    group.reset();
     if (engine) engine_destroy(engine);
   }
 };
@@ -74,11 +82,45 @@ bool is_identity77(const double* m) {
   return true;
 }
 
+// An engine call f(engine, rank, err) of a public entry: on the handle's one engine, or, on a handle with several
+// ranks, on every rank's worker (all == false: on rank 0's only -- read-outs of what every rank holds a replica of,
+// which run no collective).  Returns the lowest failing rank's code with its message in the handle, else rank 0's.
+template <class F>
+int on_ranks(sim3opt_graph* g, F f, bool all = true) {
+  if (!g->group) return f(g->engine, 0, g->err);
+  return g->group->run([&](RankCtx& c) { return f(c.engine, (int)c.rank, c.err); }, g->err, all);
+}
+
+// after a rank failed or timed out inside a collective the ranks are out of step for good
+bool finished(const sim3opt_graph* g) { return g && g->group && g->group->broken(); }
+const char* const FINISHED = "a rank failed or timed out: the handle is finished (sim3opt_destroy is what is left)";
+#define REFUSE_FINISHED(g) \
+  if (finished(g)) return fail(g, SIM3OPT_ERR_STATE, FINISHED)
+// entries that serve one rank only (as on a graph partitioned over processes)
+#define REFUSE_RANKS(g, who) \
+  if ((g)->group) return fail(g, SIM3OPT_ERR_STATE, who ": one rank only (the graph is partitioned over ranks)")
+
 // pulls the current estimates back into the host container (so get/set work either side of
 // initialize, like g2o's vertex objects)
 int sync_host_states(sim3opt_graph* g) {
   if (!g->initialized) return SIM3OPT_OK;
-  return engine_get_states(g->engine, g->host.states.data(), g->err);
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_get_states(e, g->host.states.data(), err); },
+                  false);
+}
+
+int push_host_states(sim3opt_graph* g) {
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_set_states(e, g->host.states.data(), err); });
+}
+
+// (no HIP call in f: the workers are idle between two commands)
+template <class F>
+void for_engines(sim3opt_graph* g, F f) {
+  if (!g->group) {
+    if (g->engine) f(g->engine);
+    return;
+  }
+  for (int32_t r = 0; r < g->group->size(); ++r)
+    if (g->group->ctx(r).engine) f(g->group->ctx(r).engine);
 }
 
 // a kind / delta pair as sim3opt_add_edge and sim3opt_set_edge_kernels accept it
@@ -260,6 +302,7 @@ void sim3opt_device_memory_in_use(int64_t out[2]) {
 
 int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
   if (!g || !o) return fail(g, SIM3OPT_ERR_ARG, "set_options: null argument");
+  REFUSE_FINISHED(g);
   if (!(o->fd_delta > 0) || !(o->exp_eps > 0) || o->max_trials < 1 || !(o->pcg_rel_tol >= 0) ||
       !(o->tau > 0) || o->pcg_check_every < 0 || o->amg_virtual_ranks < 0 || o->pcg_batch < 0 ||
       o->direct_max_pairs < 0 || !(o->amg_omega > 0) || !(o->amg_over[0] > 0) || !(o->amg_over[1] > 0))
@@ -294,7 +337,8 @@ int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
   const bool span_as_reported = g->engine && span_request > 0 && o->span_grid == engine_span_grid(g->engine);
   g->opt = *o;
   if (span_as_reported) g->opt.span_grid = span_request;
-  if (g->engine) engine_set_options(g->engine, g->opt);
+  if (g->devices_set && !g->group) g->opt.device = g->device_one;  // (sim3opt_set_devices chose it)
+  for_engines(g, [&](Engine* e) { engine_set_options(e, g->opt); });  // (an engine keeps its own device)
   return SIM3OPT_OK;
 }
 
@@ -310,6 +354,7 @@ const char* sim3opt_last_error(const sim3opt_graph* g) { return g ? g->err.c_str
 int sim3opt_add_vertex(sim3opt_graph* g, int32_t id, const double state[8], int32_t fixed) {
   try {
   if (!g || !state) return fail(g, SIM3OPT_ERR_ARG, "add_vertex: null argument");
+  REFUSE_FINISHED(g);
   if (g->initialized) g->dirty = true;  // needs initializeOptimization() again, like g2o
   if (!state_ok(state)) return fail(g, SIM3OPT_ERR_ARG, "add_vertex: non-finite state or scale <= 0");
   HostGraph& h = g->host;
@@ -349,6 +394,7 @@ int sim3opt_add_edge(sim3opt_graph* g, int32_t id_v0, int32_t id_v1, const doubl
                      const double* info77, int32_t kernel, double kernel_delta) {
   try {
   if (!g || !meas) return fail(g, SIM3OPT_ERR_ARG, "add_edge: null argument");
+  REFUSE_FINISHED(g);
   if (g->initialized) g->dirty = true;
   return add_edge_impl(g, id_v0, id_v1, meas, info77, kernel, kernel_delta);
   } catch (...) {  // (std::bad_alloc, std::length_error ...: nothing crosses the C boundary)
@@ -362,6 +408,7 @@ int sim3opt_add_edges(sim3opt_graph* g, int32_t m, const int32_t* id_v0, const i
   try {
   if (!g || m < 0 || (m > 0 && (!id_v0 || !id_v1 || !meas)))
     return fail(g, SIM3OPT_ERR_ARG, "add_edges: bad argument");
+  REFUSE_FINISHED(g);
   if (g->initialized) g->dirty = true;
   HostGraph& h = g->host;
   h.ev0.reserve(h.ev0.size() + m);
@@ -383,6 +430,7 @@ int sim3opt_set_edge_kernels(sim3opt_graph* g, int32_t n, const int32_t* edges, 
   try {
   if (!g) return SIM3OPT_ERR_ARG;
   if (n < 0 || (n > 0 && (!kinds || !deltas))) return fail(g, SIM3OPT_ERR_ARG, "set_edge_kernels: bad argument");
+  REFUSE_FINISHED(g);
   HostGraph& h = g->host;
   const int32_t m = h.ne();
   bool any = false;
@@ -401,7 +449,8 @@ int sim3opt_set_edge_kernels(sim3opt_graph* g, int32_t n, const int32_t* edges, 
     h.kdelta[k] = kinds[i] == SIM3OPT_KERNEL_NONE ? 0.0 : deltas[i];
   }
   // an initialised graph takes the new kernels at once; a changed one gets them at its next initialize
-  if (g->initialized && !g->dirty) return engine_set_kernels(g->engine, h, g->err);
+  if (g->initialized && !g->dirty)
+    return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_set_kernels(e, h, err); });
   return SIM3OPT_OK;
   } catch (...) {  // (std::bad_alloc, std::length_error ...: nothing crosses the C boundary)
     return fail(g, SIM3OPT_ERR_ARG, "set_edge_kernels: out of host memory or internal error");
@@ -443,6 +492,7 @@ int sim3opt_get_edge(const sim3opt_graph* g, int32_t k, int32_t* id_v0, int32_t*
 int sim3opt_initialize(sim3opt_graph* g) {
   try {
   if (!g) return SIM3OPT_ERR_ARG;
+  REFUSE_FINISHED(g);
   const bool trace = std::getenv("SIM3OPT_INIT_TRACE") != nullptr;
   auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = now();
@@ -450,10 +500,21 @@ int sim3opt_initialize(sim3opt_graph* g) {
   if (g->initialized) {  // g2o allows re-initialisation: rebuild from the current estimates
     int rc = sync_host_states(g);
     if (rc) return rc;
+    if (g->group) {  // every rank keeps its communicator (and its mailboxes) for the next engine
+      g->engine = nullptr;
+      rc = g->group->run([](RankCtx& c) {
+        engine_take_comm(c.engine, &c.comm);
+        engine_destroy(c.engine);
+        c.engine = nullptr;
+        return (int)SIM3OPT_OK;
+      }, g->err);
+      if (rc) return rc;
+    } else {
     engine_take_comm(g->engine, &g->comm);  // a multi-GPU graph stays partitioned after re-init
     g->comm_set = g->comm.world > 1 || g->comm.force;
     engine_destroy(g->engine);
     g->engine = nullptr;
+    }
     g->initialized = false;
     g->dirty = false;
   }
@@ -463,13 +524,28 @@ int sim3opt_initialize(sim3opt_graph* g) {
     // (contiguous rank spans are then slabs of the graph: few cut edges, a small halo); one rank
     // keeps g2o's insertion order (options.row_order overrides: tests, measurements).
     apply_env_overrides(g->opt);
-    const bool local = g->opt.row_order >= 0 ? g->opt.row_order == 1 : (g->comm_set && g->comm.world > 1);
+    const bool local = g->opt.row_order >= 0 ? g->opt.row_order == 1 : (g->group || (g->comm_set && g->comm.world > 1));
     std::vector<int32_t> order;
     if (local) locality_order(g->host, order);
     if (!build_structure(g->host, g->structure, g->err, local ? &order : nullptr)) return SIM3OPT_ERR_STATE;
   }
   t2 = now();
   int status = SIM3OPT_OK;
+  if (g->group) {  // the host graph and the structure are shared, read-only; every rank builds its own share
+    status = g->group->run([&](RankCtx& c) {
+      if (!c.connected) {
+        const int rc = comm_local_connect(c.comm, c.err);
+        if (rc) return rc;
+        c.connected = true;
+      }
+      sim3opt_options o = g->opt;
+      o.device = c.device;
+      int st = SIM3OPT_OK;
+      c.engine = engine_create(g->host, g->structure, o, &c.comm, c.err, st);
+      return c.engine ? (int)SIM3OPT_OK : st;
+    }, g->err);
+    g->engine = status == SIM3OPT_OK ? g->group->ctx(0).engine : nullptr;
+  } else
   g->engine = engine_create(g->host, g->structure, g->opt, g->comm_set ? &g->comm : nullptr,
                             g->err, status);
   if (trace)
@@ -487,6 +563,7 @@ int sim3opt_initialize(sim3opt_graph* g) {
 int sim3opt_optimize(sim3opt_graph* g, int32_t max_iters) {
   try {
   if (!g) return 0;
+  if (finished(g)) { g->err = FINISHED; return 0; }
   if (!g->initialized) {
     // g2o: optimize() on an uninitialised / empty problem returns -1
     if (g->host.ne() == 0 || g->host.nv() == 0) { g->err = "optimize: nothing to optimise"; return -1; }
@@ -496,6 +573,16 @@ int sim3opt_optimize(sim3opt_graph* g, int32_t max_iters) {
   if (max_iters <= 0) return 0;
   if (g->dirty) { g->err = "optimize: graph changed, call sim3opt_initialize again"; return 0; }
   g->last_algorithm = g->opt.algorithm;
+  if (g->group) {
+    const int rc = g->group->run([&](RankCtx& c) {
+      const int it = engine_optimize(c.engine, max_iters, c.stats, c.err);
+      engine_trust_region_stats(c.engine, c.tr_stats);
+      return it;
+    }, g->err);
+    g->stats = g->group->ctx(0).stats;
+    g->tr_stats = g->group->ctx(0).tr_stats;
+    return rc < 0 ? 0 : rc;
+  }
   const int rc = engine_optimize(g->engine, max_iters, g->stats, g->err);
   engine_trust_region_stats(g->engine, g->tr_stats);
   return rc < 0 ? 0 : rc;
@@ -506,6 +593,7 @@ int sim3opt_optimize(sim3opt_graph* g, int32_t max_iters) {
 
 int sim3opt_get_vertex(sim3opt_graph* g, int32_t id, double state[8]) {
   if (!g || !state) return fail(g, SIM3OPT_ERR_ARG, "get_vertex: null argument");
+  REFUSE_FINISHED(g);
   auto it = g->host.id2idx.find(id);
   if (it == g->host.id2idx.end()) return fail(g, SIM3OPT_ERR_ARG, "get_vertex: unknown id");
   int rc = sync_host_states(g);
@@ -516,18 +604,20 @@ int sim3opt_get_vertex(sim3opt_graph* g, int32_t id, double state[8]) {
 
 int sim3opt_set_vertex(sim3opt_graph* g, int32_t id, const double state[8]) {
   if (!g || !state) return fail(g, SIM3OPT_ERR_ARG, "set_vertex: null argument");
+  REFUSE_FINISHED(g);
   auto it = g->host.id2idx.find(id);
   if (it == g->host.id2idx.end()) return fail(g, SIM3OPT_ERR_ARG, "set_vertex: unknown id");
   if (!state_ok(state)) return fail(g, SIM3OPT_ERR_ARG, "set_vertex: non-finite state or scale <= 0");
   int rc = sync_host_states(g);
   if (rc) return rc;
   g->host.states[it->second] = to_sim3(state);
-  if (g->initialized) return engine_set_states(g->engine, g->host.states.data(), g->err);
+  if (g->initialized) return push_host_states(g);
   return SIM3OPT_OK;
 }
 
 int sim3opt_get_vertices(sim3opt_graph* g, double* states) {
   if (!g || !states) return fail(g, SIM3OPT_ERR_ARG, "get_vertices: null argument");
+  REFUSE_FINISHED(g);
   int rc = sync_host_states(g);
   if (rc) return rc;
   for (size_t k = 0; k < g->host.states.size(); ++k) from_sim3(g->host.states[k], states + 8 * k);
@@ -536,17 +626,22 @@ int sim3opt_get_vertices(sim3opt_graph* g, double* states) {
 
 int sim3opt_set_vertices(sim3opt_graph* g, const double* states) {
   if (!g || !states) return fail(g, SIM3OPT_ERR_ARG, "set_vertices: null argument");
+  REFUSE_FINISHED(g);
   for (size_t k = 0; k < g->host.states.size(); ++k)
     if (!state_ok(states + 8 * k)) return fail(g, SIM3OPT_ERR_ARG, "set_vertices: bad state");
   for (size_t k = 0; k < g->host.states.size(); ++k) g->host.states[k] = to_sim3(states + 8 * k);
-  if (g->initialized) return engine_set_states(g->engine, g->host.states.data(), g->err);
+  if (g->initialized) return push_host_states(g);
   return SIM3OPT_OK;
 }
 
 int sim3opt_chi2(sim3opt_graph* g, double* chi2) {
   if (!g || !chi2) return fail(g, SIM3OPT_ERR_ARG, "chi2: null argument");
+  REFUSE_FINISHED(g);
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "chi2: call sim3opt_initialize first");
-  return engine_chi2(g->engine, chi2, g->err);
+  return on_ranks(g, [&](Engine* e, int rank, std::string& err) {
+    double other = 0.0;  // (every rank computes the same sum)
+    return engine_chi2(e, rank == 0 ? chi2 : &other, err);
+  });
 }
 
 int32_t sim3opt_num_iterations(const sim3opt_graph* g) { return g ? (int32_t)g->stats.size() : 0; }
@@ -573,33 +668,40 @@ int sim3opt_get_kernel_times(sim3opt_graph* g, sim3opt_kernel_times* out) {
 
 int sim3opt_get_comm_times(sim3opt_graph* g, sim3opt_comm_times* out) {
   if (!g || !out) return SIM3OPT_ERR_ARG;
+  REFUSE_FINISHED(g);
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "comm_times: not initialized");
-  return engine_comm_times(g->engine, out);
+  return on_ranks(g, [&](Engine* e, int, std::string&) { return engine_comm_times(e, out); }, false);
 }
 
 int sim3opt_reset_kernel_times(sim3opt_graph* g) {
   if (!g) return SIM3OPT_ERR_ARG;
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "kernel_times: not initialized");
-  return engine_kernel_times(g->engine, nullptr, true);
+  for_engines(g, [](Engine* e) { (void)engine_kernel_times(e, nullptr, true); });
+  return SIM3OPT_OK;
 }
 
 int sim3opt_pcg_schedule_stats(sim3opt_graph* g, int64_t out[4], int32_t reset) {
   if (!g) return SIM3OPT_ERR_ARG;
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "pcg_schedule_stats: not initialized");
   engine_pcg_schedule_stats(g->engine, out, reset != 0);
+  if (g->group && reset)
+    for (int32_t r = 1; r < g->group->size(); ++r) engine_pcg_schedule_stats(g->group->ctx(r).engine, nullptr, true);
   return SIM3OPT_OK;
 }
 
 int sim3opt_edge_errors(sim3opt_graph* g, double* e_out) {
   if (!g || !e_out) return fail(g, SIM3OPT_ERR_ARG, "edge_errors: null argument");
+  REFUSE_FINISHED(g);
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "edge_errors: call sim3opt_initialize first");
-  return engine_edge_errors(g->engine, e_out, g->err);
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_edge_errors(e, e_out, err); }, false);
 }
 
 int sim3opt_edge_chi2(sim3opt_graph* g, double* chi2, double* rho, double* weight) {
   if (!g) return SIM3OPT_ERR_ARG;
+  REFUSE_FINISHED(g);
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "edge_chi2: call sim3opt_initialize first");
-  return engine_edge_chi2(g->engine, chi2, rho, weight, g->err);
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_edge_chi2(e, chi2, rho, weight, err); },
+                  false);
 }
 
 int sim3opt_edge_jacobians(sim3opt_graph* g, double* e_out, double* J_out) {
@@ -608,7 +710,9 @@ int sim3opt_edge_jacobians(sim3opt_graph* g, double* e_out, double* J_out) {
     return fail(g, SIM3OPT_ERR_ARG, "edge_jacobians: needs fix_small_angle_b = 1 (closed form of the exact map)");
   if (!g->initialized || g->dirty)
     return fail(g, SIM3OPT_ERR_STATE, "edge_jacobians: call sim3opt_initialize first");
-  return engine_edge_jacobians(g->engine, e_out, J_out, g->err);
+  REFUSE_FINISHED(g);
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_edge_jacobians(e, e_out, J_out, err); },
+                  false);
 }
 
 int sim3opt_sim3_edge_jacobian(const double meas[8], const double s0[8], const double s1[8],
@@ -628,8 +732,9 @@ int sim3opt_sim3_edge_jacobian(const double meas[8], const double s0[8], const d
 
 int sim3opt_linearize(sim3opt_graph* g) {
   if (!g) return SIM3OPT_ERR_ARG;
+  REFUSE_FINISHED(g);
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "linearize: call sim3opt_initialize first");
-  return engine_linearize(g->engine, g->err);
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_linearize(e, err); });
 }
 
 int sim3opt_debug_linearization_dims(sim3opt_graph* g, int32_t* n_active, int32_t* n_incidences) {
@@ -649,6 +754,7 @@ int sim3opt_debug_linearization(sim3opt_graph* g, double* J, double* w, int32_t*
     return fail(g, SIM3OPT_ERR_ARG, "debug_linearization: null argument");
   if (!g->initialized || g->dirty)
     return fail(g, SIM3OPT_ERR_STATE, "debug_linearization: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "debug_linearization");
   return engine_debug_linearization(g->engine, J, w, active, scratch, incptr, inc0, inc1, slot01, slot10, trace,
                                     maxdiag, g->err);
 }
@@ -660,6 +766,7 @@ int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32
   if (!states_out && !backup_out && !chi2 && !scale) return fail(g, SIM3OPT_ERR_ARG, "debug_update: every output is null");
   if (!std::isfinite(lambda)) return fail(g, SIM3OPT_ERR_ARG, "debug_update: lambda is not finite");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_update: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "debug_update");
   return engine_debug_update(g->engine, x, lambda, with_fail != 0, grid, states_out, backup_out, chi2, scale, g->err);
 }
 
@@ -668,6 +775,7 @@ int sim3opt_debug_factor_dims(sim3opt_graph* g, int32_t context, int32_t* n_bloc
   if (!g) return SIM3OPT_ERR_ARG;
   if (!n_block_rows || !n_blocks_L || !n_blocks) return fail(g, SIM3OPT_ERR_ARG, "debug_factor_dims: null argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_factor_dims: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "debug_factor_dims");
   return engine_debug_factor_dims(g->engine, context, n_block_rows, n_blocks_L, n_blocks, g->err);
 }
 
@@ -680,6 +788,7 @@ int sim3opt_debug_factor(sim3opt_graph* g, int32_t context, double lambda, const
       (with_selinv && (!Z || !singular)))
     return fail(g, SIM3OPT_ERR_ARG, "debug_factor: null argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_factor: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "debug_factor");
   return engine_debug_factor(g->engine, context, lambda, vals, b, with_solve != 0, with_selinv != 0, Aperm, bp, L, Dinv,
                              y, xp, x, fail_word, Z, singular, bord, brow, g->err);
 }
@@ -710,19 +819,24 @@ int sim3opt_system_pattern(sim3opt_graph* g, int32_t* n_block_rows, int64_t* n_b
 int sim3opt_get_system(sim3opt_graph* g, int32_t* rowptr, int32_t* colidx, double* values,
                        double* b) {
   if (!g) return SIM3OPT_ERR_ARG;
+  REFUSE_FINISHED(g);
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "get_system: call sim3opt_initialize first");
-  return engine_get_system(g->engine, rowptr, colidx, values, b, g->err);
+  // (rank 0's rows, as a rank of a graph partitioned over processes answers)
+  return on_ranks(g, [&](Engine* e, int, std::string& err) { return engine_get_system(e, rowptr, colidx, values, b, err); },
+                  false);
 }
 
 int sim3opt_solve(sim3opt_graph* g, double lambda, double* x, int32_t* iters, double* rel_res) {
   if (!g) return SIM3OPT_ERR_ARG;
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "solve: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "solve");
   return engine_solve(g->engine, lambda, x, iters, rel_res, g->err);
 }
 
 int sim3opt_bench_spmv(sim3opt_graph* g, int32_t reps, double* ms_mean) {
   if (!g || !ms_mean || reps < 1) return fail(g, SIM3OPT_ERR_ARG, "bench_spmv: bad argument");
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "bench_spmv: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "bench_spmv");
   return engine_bench_spmv(g->engine, reps, ms_mean, g->err);
 }
 
@@ -787,6 +901,7 @@ int sim3opt_marginals(sim3opt_graph* g, double lambda, int32_t n, const int32_t*
   try {
   if (!g || n < 0 || (n > 0 && (!id_a || !id_b || !cov))) return fail(g, SIM3OPT_ERR_ARG, "marginals: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "marginals: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "marginals");
   std::vector<int32_t> ra(std::max(n, 1)), rb(std::max(n, 1));
   for (int32_t q = 0; q < n; ++q) {
     const auto a = g->host.id2idx.find(id_a[q]), b = g->host.id2idx.find(id_b[q]);
@@ -817,6 +932,7 @@ int sim3opt_covariances(sim3opt_graph* g, double lambda, int32_t n, const int32_
   try {
   if (!g || n < 0 || (n > 0 && (!id_a || !id_b || !cov))) return fail(g, SIM3OPT_ERR_ARG, "covariances: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "covariances: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "covariances");
   std::vector<int32_t> ra(std::max(n, 1)), rb(std::max(n, 1));
   for (int32_t q = 0; q < n; ++q) {
     const auto a = g->host.id2idx.find(id_a[q]), b = g->host.id2idx.find(id_b[q]);
@@ -878,6 +994,7 @@ int sim3opt_gate_edges(sim3opt_graph* g, double lambda, int32_t n, const int32_t
   if (!g || n < 0 || (n > 0 && (!id_v0 || !id_v1 || !meas || !e || !S || !d2)))
     return fail(g, SIM3OPT_ERR_ARG, "gate_edges: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "gate_edges: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "gate_edges");
   const size_t m = (size_t)std::max(n, 1);
   std::vector<int32_t> v0(m), v1(m), r0(m), r1(m);
   std::vector<sim3::Sim3> cm(m);
@@ -943,6 +1060,7 @@ int sim3opt_marginal_covariances(sim3opt_graph* g, double lambda, double* cov) {
   try {
   if (!g || !cov) return fail(g, SIM3OPT_ERR_ARG, "marginal_covariances: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "marginal_covariances: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "marginal_covariances");
   std::vector<int32_t> rows;  // free vertices in insertion order
   for (int32_t v = 0; v < g->host.nv(); ++v)
     if (g->structure.hidx[v] >= 0) rows.push_back(g->structure.hidx[v]);
@@ -1056,6 +1174,7 @@ int sim3opt_amg_level_numbers(sim3opt_graph* g, double lambda, int32_t level, in
   if (!g) return SIM3OPT_ERR_ARG;
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "amg_level_numbers: call sim3opt_initialize first");
   if (!std::isfinite(lambda) || lambda < 0.0) return fail(g, SIM3OPT_ERR_ARG, "amg_level_numbers: bad lambda");
+  REFUSE_RANKS(g, "amg_level_numbers");
   return engine_amg_level_numbers(g->engine, lambda, level, rowptr, colidx, values, values32, W, diagH, Minv, P, g->err);
 }
 
@@ -1063,6 +1182,7 @@ int sim3opt_amg_coarsest_inverse(sim3opt_graph* g, double lambda, double* Ainv) 
   if (!g || !Ainv) return fail(g, SIM3OPT_ERR_ARG, "amg_coarsest_inverse: null argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "amg_coarsest_inverse: call sim3opt_initialize first");
   if (!std::isfinite(lambda) || lambda < 0.0) return fail(g, SIM3OPT_ERR_ARG, "amg_coarsest_inverse: bad lambda");
+  REFUSE_RANKS(g, "amg_coarsest_inverse");
   return engine_amg_coarsest_inverse(g->engine, lambda, Ainv, g->err);
 }
 
@@ -1071,12 +1191,14 @@ int sim3opt_preconditioner_apply(sim3opt_graph* g, int32_t prec, double lambda, 
   if (!g || !r || !z || nrhs < 1 || prec < 0 || prec > 2 || !std::isfinite(lambda) || lambda < 0.0)
     return fail(g, SIM3OPT_ERR_ARG, "preconditioner_apply: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "preconditioner_apply: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "preconditioner_apply");
   return engine_precond_apply(g->engine, prec, lambda, nrhs, r, z, g->err);
 }
 
 int sim3opt_spmv_spans(sim3opt_graph* g, int32_t* n_spans, int32_t* wrow) {
   if (!g || !n_spans) return fail(g, SIM3OPT_ERR_ARG, "spmv_spans: bad argument");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "spmv_spans: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "spmv_spans");
   return engine_spmv_spans(g->engine, n_spans, wrow, g->err);
 }
 
@@ -1094,6 +1216,7 @@ int sim3opt_operator_apply(sim3opt_graph* g, int32_t nrhs, const double* lambda,
   for (int32_t s = 0; s < nrhs; ++s)
     if (!std::isfinite(lambda[s]) || lambda[s] < 0.0) return fail(g, SIM3OPT_ERR_ARG, "operator_apply: bad lambda");
   if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "operator_apply: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "operator_apply");
   return engine_operator_apply(g->engine, nrhs, lambda, p, rvec, q, pq, rp, g->err);
 }
 
@@ -1132,6 +1255,7 @@ int sim3opt_partition_plan(sim3opt_graph* g, int32_t world, int32_t locality, in
 int sim3opt_bench_stream(sim3opt_graph* g, int32_t mode, int32_t reps, double* ms_mean) {
   if (!g || !ms_mean || reps < 1 || mode < 0 || mode > 2) return fail(g, SIM3OPT_ERR_ARG, "bench_stream: bad argument");
   if (!g->initialized) return fail(g, SIM3OPT_ERR_STATE, "bench_stream: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "bench_stream");
   return engine_bench_stream(g->engine, mode, reps, ms_mean, g->err);
 }
 
@@ -1181,6 +1305,8 @@ int sim3opt_comm_unique_id(uint8_t id_out[128]) {
 int sim3opt_comm_init(sim3opt_graph* g, int32_t rank, int32_t world, const uint8_t unique_id[128]) {
   if (!g || world < 1 || rank < 0 || rank >= world) return fail(g, SIM3OPT_ERR_ARG, "comm_init: bad rank/world");
   if (g->initialized) return fail(g, SIM3OPT_ERR_STATE, "comm_init: call before sim3opt_initialize");
+  if (g->devices_set) return fail(g, SIM3OPT_ERR_STATE, "comm_init: sim3opt_set_devices has given the handle its ranks");
+  g->comm_called = true;
   // options.force_collectives: build the communicator and run every collective even with one rank
   // (self-test of the RCCL transport on a single-GPU machine)
   apply_env_overrides(g->opt);
@@ -1202,6 +1328,9 @@ int sim3opt_comm_init_callbacks(sim3opt_graph* g, int32_t rank, int32_t world,
   if (!g || world < 1 || rank < 0 || rank >= world || !allreduce || !allgatherv)
     return fail(g, SIM3OPT_ERR_ARG, "comm_init_callbacks: bad argument");
   if (g->initialized) return fail(g, SIM3OPT_ERR_STATE, "comm_init_callbacks: call before sim3opt_initialize");
+  if (g->devices_set)
+    return fail(g, SIM3OPT_ERR_STATE, "comm_init_callbacks: sim3opt_set_devices has given the handle its ranks");
+  g->comm_called = true;
   g->comm.release();
   g->comm.rank = rank;
   g->comm.world = world;
@@ -1247,6 +1376,50 @@ int sim3opt_comm_set_alltoallv(sim3opt_graph* g, sim3opt_alltoallv_fn alltoallv)
 int sim3opt_local_rows(const sim3opt_graph* g, int32_t* begin, int32_t* end) {
   if (!g || !g->initialized) return SIM3OPT_ERR_STATE;
   engine_local_rows(g->engine, begin, end);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_set_devices(sim3opt_graph* g, int32_t n, const int32_t* devices, double collective_timeout_s) {
+  try {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (n < 1 || n > 8 || !devices) return fail(g, SIM3OPT_ERR_ARG, "set_devices: 1 to 8 device ordinals, please");
+  if (g->initialized) return fail(g, SIM3OPT_ERR_STATE, "set_devices: call before sim3opt_initialize");
+  if (g->comm_called) return fail(g, SIM3OPT_ERR_STATE, "set_devices: sim3opt_comm_init* has given the handle its ranks");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(g, SIM3OPT_ERR_NO_DEVICE, "set_devices: no usable HIP device");
+  for (int32_t r = 0; r < n; ++r)
+    if (devices[r] < 0 || devices[r] >= ndev) return fail(g, SIM3OPT_ERR_ARG, "set_devices: device ordinal out of range");
+  g->group.reset();  // (a second call replaces the first)
+  g->devices_set = true;
+  if (n == 1) {  // the plain one-rank graph on that device
+    g->device_one = g->opt.device = devices[0];
+    return SIM3OPT_OK;
+  }
+  g->group.reset(new RankGroup(n, devices, collective_timeout_s));
+  return SIM3OPT_OK;
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "set_devices: out of host memory or internal error");
+  }
+}
+
+int sim3opt_rank_count(const sim3opt_graph* g) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  return g->group ? g->group->size() : 1;  // (ranks THIS handle drives; a rank of a multi-process run is one)
+}
+
+int sim3opt_local_rows_of_rank(const sim3opt_graph* g, int32_t rank, int32_t* begin, int32_t* end) {
+  if (!g || !g->initialized) return SIM3OPT_ERR_STATE;
+  if (rank < 0 || rank >= (g->group ? g->group->size() : 1)) return SIM3OPT_ERR_ARG;
+  engine_local_rows(g->group ? g->group->ctx(rank).engine : g->engine, begin, end);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_device_bytes_of_rank(const sim3opt_graph* g, int32_t rank, int64_t bytes[2]) {
+  if (!g || !bytes) return SIM3OPT_ERR_ARG;
+  if (!g->initialized) return SIM3OPT_ERR_STATE;
+  if (rank < 0 || rank >= (g->group ? g->group->size() : 1)) return SIM3OPT_ERR_ARG;
+  engine_device_bytes(g->group ? g->group->ctx(rank).engine : g->engine, bytes);
   return SIM3OPT_OK;
 }
 

@@ -1,4 +1,4 @@
-// comm.cpp -- RCCL (dlopen) and host-staged callback transports (see comm.hpp).
+// comm.cpp -- RCCL (dlopen) and host-staged callback transports (see comm.hpp); the in-process one is comm_local.hip.
 #include "comm.hpp"
 #include "devmem.hpp"  // HIPCHK
 
@@ -184,6 +184,7 @@ int Comm::exchange(const double* sbuf, const std::vector<int64_t>& soffs, double
 
 int Comm::exchange_impl(const double* sbuf, const std::vector<int64_t>& soffs, double* rbuf,
                         const std::vector<int64_t>& roffs, hipStream_t stream, std::string& err) {
+  if (kind == 3) return comm_local_exchange(*this, sbuf, soffs, rbuf, roffs, stream, err);
   if (kind == 1) {
     NCCLCHK(g_api.GroupStart());
     for (int p = 0; p < world; ++p) {
@@ -227,6 +228,7 @@ int Comm::exchange_impl(const double* sbuf, const std::vector<int64_t>& soffs, d
 
 int Comm::allreduce_impl(double* dptr, int n, int op, hipStream_t stream, std::string& err) {
   if (!active()) return SIM3OPT_OK;
+  if (kind == 3) return comm_local_allreduce(*this, dptr, n, op, stream, err);
   if (kind == 1) {
     NCCLCHK(g_api.AllReduce(dptr, dptr, (size_t)n, ncclFloat64, op == 1 ? ncclMax : ncclSum,
                             (ncclComm_t)nccl, stream));
@@ -248,6 +250,7 @@ int Comm::allreduce_impl(double* dptr, int n, int op, hipStream_t stream, std::s
 int Comm::allgatherv_impl(double* dvec, const std::vector<int64_t>& offs, hipStream_t stream,
                           std::string& err) {
   if (!active()) return SIM3OPT_OK;
+  if (kind == 3) return comm_local_allgatherv(*this, dvec, offs, stream, err);
   if (kind == 1) {
     // equal spans (the engine's partition; buffers are padded to world x count): ONE in-place
     // ncclAllGather -- rank r's segment already sits at recvbuff + r * count
@@ -292,6 +295,8 @@ int Comm::allgatherv_impl(double* dvec, const std::vector<int64_t>& offs, hipStr
 }
 
 void Comm::release() {
+  if (kind == 3) comm_local_release(*this);
+  local = nullptr;
   if (kind == 1 && nccl && g_api.CommDestroy) (void)g_api.CommDestroy((ncclComm_t)nccl);
   nccl = nullptr;
   if (h_stage) (void)hipHostFree(h_stage);

@@ -1,10 +1,12 @@
-// comm.hpp -- collectives of the row-partitioned multi-GPU path (one process per GPU).
+// comm.hpp -- collectives of the row-partitioned multi-GPU path (one process per GPU, or the ranks of one process).
 //
-// Two transports behind one interface:
+// Three transports behind one interface:
 //   RCCL      in-place ncclAllReduce / ncclAllGather on the engine's HIP stream (xGMI); librccl is
 //             dlopen'ed at sim3opt_comm_init so that libsim3opt.so loads on machines without it
 //   callbacks host-staged: the engine copies the operands to pinned host memory and calls the
 //             user's functions (MPI, torch.distributed/gloo, ...).  Used by the 2-process tests.
+//   local     the ranks are threads of this process (sim3opt_set_devices, rank_group.hpp): each rank's kernel
+//             stores into its peers' device mailboxes, a host barrier orders the ranks (comm_local.hip)
 // The reference has no communication at all; this is new work.
 #pragma once
 
@@ -15,12 +17,30 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "rank_barrier.hpp"
 
 namespace sim3opt {
 
+// What the ranks of one process share (kind 3); owned by their RankGroup, outlives every Comm that points to it.
+// A rank writes its own LocalRank only, and only where a barrier separates the write from the peers' reads.
+struct LocalRank {
+  double* mbox[2] = {nullptr, nullptr};  // device mailboxes, even and odd collectives; the same capacity on every rank
+  int64_t cap = 0;                       // ... in doubles
+  int64_t need[2] = {0, 0};              // capacity this rank's exchange asks for (by parity, like the mailboxes)
+  uint64_t seq = 0;                      // collectives so far: barrier waits, identical on every rank
+  int32_t device = 0;
+};
+struct LocalGroup {
+  int32_t world = 1;
+  double timeout_s = 120.0;
+  RankBarrier barrier;
+  LocalRank ranks[8];
+};
+
 struct Comm {
   int32_t rank = 0, world = 1;
-  int kind = 0;  // 0 none, 1 RCCL, 2 callbacks
+  int kind = 0;  // 0 none, 1 RCCL, 2 callbacks, 3 local (ranks of this process)
+  LocalGroup* local = nullptr;  // kind 3 (not owned)
   void* nccl = nullptr;  // ncclComm_t
   sim3opt_allreduce_fn cb_allreduce = nullptr;
   sim3opt_allgatherv_fn cb_allgatherv = nullptr;
@@ -52,7 +72,7 @@ struct Comm {
   // neighbour exchange: sbuf[soffs[p] .. soffs[p+1]) goes to rank p, rbuf[roffs[p] .. roffs[p+1]) comes from
   // rank p (doubles; both plans come from the same symmetric pattern, so the two sides agree on every
   // count).  RCCL: one group of ncclSend / ncclRecv pairs; callbacks: the optional alltoallv callback.
-  bool can_exchange() const { return kind == 1 || (kind == 2 && cb_alltoallv != nullptr); }
+  bool can_exchange() const { return kind == 1 || kind == 3 || (kind == 2 && cb_alltoallv != nullptr); }
   int exchange(const double* sbuf, const std::vector<int64_t>& soffs, double* rbuf,
                const std::vector<int64_t>& roffs, hipStream_t stream, std::string& err);
   void release();
@@ -81,5 +101,16 @@ inline bool allgather_equal_plan(const int64_t* offs, int32_t world, int64_t* co
 
 int comm_unique_id(uint8_t id_out[128], std::string& err);
 int comm_init_rccl(Comm& c, int32_t rank, int32_t world, const uint8_t id[128], std::string& err);
+
+// kind 3 (comm_local.hip).  comm_init_local makes c rank `rank` of the group; comm_local_connect, called by every rank's
+// own thread under its own device, enables peer access to the other ranks' devices (SIM3OPT_ERR_COMM names a pair
+// without it).  The collectives are in place on device memory and ordered on `stream`, like the other transports'.
+void comm_init_local(Comm& c, LocalGroup* group, int32_t rank);
+int comm_local_connect(Comm& c, std::string& err);
+int comm_local_allreduce(Comm& c, double* dptr, int n, int op, hipStream_t stream, std::string& err);
+int comm_local_allgatherv(Comm& c, double* dvec, const std::vector<int64_t>& offs, hipStream_t stream, std::string& err);
+int comm_local_exchange(Comm& c, const double* sbuf, const std::vector<int64_t>& soffs, double* rbuf,
+                        const std::vector<int64_t>& roffs, hipStream_t stream, std::string& err);
+void comm_local_release(Comm& c);  // gives this rank's mailboxes back (its own thread, after every rank has gone quiet)
 
 }  // namespace sim3opt

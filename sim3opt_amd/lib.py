@@ -247,6 +247,10 @@ SYMBOLS = {
     "sim3opt_device_bytes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "sim3opt_halo_plan": (C.c_int, [_vp, C.c_int32, C.c_int32, _ip, _ip, _ip, _ip, _ip, _ip]),
     "sim3opt_local_rows": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_set_devices": (C.c_int, [_vp, C.c_int32, _ip, C.c_double]),
+    "sim3opt_rank_count": (C.c_int, [_vp]),
+    "sim3opt_local_rows_of_rank": (C.c_int, [_vp, C.c_int32, _ip, _ip]),
+    "sim3opt_device_bytes_of_rank": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
     "sim3opt_partition_plan": (C.c_int, [_vp, C.c_int32, C.c_int32, _ip, _ip, _ip, C.POINTER(C.c_int64)]),
     "sim3opt_partition_rows": (C.c_int, [C.c_int32, _ip, C.c_int32, _ip]),
     "sim3opt_partition_rows_equal": (C.c_int, [C.c_int32, C.c_int32, _ip]),
@@ -575,6 +579,28 @@ class Graph:
         a, b = C.c_int32(), C.c_int32()
         self._chk(self._L.sim3opt_local_rows(self._g, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_devices(self, devices, timeout_s=0.0):
+        """One rank per entry of `devices` (1 to 8 HIP ordinals, repeats allowed), run by the library's own worker
+        threads: this object stays one graph, called from one thread.  Between construction and initialize();
+        timeout_s <= 0: a rank waits 120 s for its peers in a collective before it gives the group up."""
+        d = _i32(list(devices))
+        self._chk(self._L.sim3opt_set_devices(self._g, int(d.size), _p(d, _ip) if d.size else None, float(timeout_s)))
+
+    def rank_count(self):
+        """Ranks this graph drives: len(devices) of set_devices, else 1."""
+        return int(self._L.sim3opt_rank_count(self._g))
+
+    def local_rows_of_rank(self, rank):
+        a, b = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_local_rows_of_rank(self._g, int(rank), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def device_bytes_of_rank(self, rank):
+        """device_bytes() of one rank of a set_devices graph."""
+        b = (C.c_int64 * 2)()
+        self._chk(self._L.sim3opt_device_bytes_of_rank(self._g, int(rank), b))
+        return int(b[0]), int(b[1])
 
     # ---- optimisation ----
     def initialize(self):
