@@ -696,8 +696,8 @@ int sim3opt_device_bytes_of_rank(const sim3opt_graph* g, int32_t rank, int64_t b
  * call it yourself before allocating large device buffers of your own next to a live handle. */
 void sim3opt_release_device_cache(void);
 /* Diagnostic.  out = {blocks, bytes} of device memory the library has handed to its handles and calls and not got
- * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch of the process, on all devices; bytes as the block
- * cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
+ * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch of the process, on all
+ * devices; bytes as the block cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
  * that creates no handle and initialises none is what "this call keeps no device memory" means
  * (tests/test_gpu_device_memory.py). */
 void sim3opt_device_memory_in_use(int64_t out[2]);
@@ -895,6 +895,88 @@ int sim3opt_ba_batch_get_lambda_init(const sim3opt_ba_batch* b, double* lambda_i
  * SIM3OPT_ERR_STATE before the first optimize. */
 int sim3opt_ba_batch_get_chi2(const sim3opt_ba_batch* b, double* active_before, double* active_after,
                               double* edge_chi2, int32_t* n_outlier_edges);
+
+/* ---- batched PnP RANSAC: the loop detector's start pose, every candidate in one launch ----
+ * cv::solvePnPRansac(surfPoints[0], points2, K, dist, rvec, tvec, false, 100, 3, 10, noArray(), CV_ITERATIVE)
+ * (kittiDetector.h:1300-1301), which the detector calls once per accepted loop candidate before BAOptimize (:1325)
+ * and whose result is line 3 of a loopConstraints.txt record: camera 1 (T_w2c of camera 0's frame) from camera 0's
+ * 3-D points and camera 1's pixels.  Its poses are the cam1 the batched two-view refinement above starts from.
+ * PARITY UNPINNED: the reference stores the outputs of its PnP runs, not their inputs, and OpenCV's sampling is not
+ * reproducible.  What is OpenCV's here: the order of the steps and the inlier criterion, squared reprojection error
+ * <= reproj_error^2.  What is not: hypotheses are closed-form P3P solutions of three points, chosen by a fourth
+ * (OpenCV: EPnP); all `iterations` hypotheses are evaluated (OpenCV stops early on its confidence estimate); the
+ * sampler is counter-based -- draw j of hypothesis h is splitmix64 of seed + (4 h + j + 1) * 0x9E3779B97F4A7C15
+ * modulo n - j, stepped over the earlier picks -- so a seed gives the same samples everywhere; the final refit is a
+ * Levenberg-Marquardt on camera 1 over the best hypothesis's inliers (OpenCV: CV_ITERATIVE).  Device pipeline:
+ * sim3opt_amd/csrc/pnp_batch.hip, one workgroup per problem, one launch.  A problem's result does not depend on the
+ * other problems of the batch or on its place among them.  No CPU fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_pnp_batch sim3opt_pnp_batch;
+
+typedef struct sim3opt_pnp_batch_options {
+  double reproj_error;      /* inlier: squared error <= reproj_error^2 [px]      default 3.0    :1301 reprojectionError     */
+  double tau;               /* refit: lambda_0 = tau * max diag(H)              default 1e-5                                */
+  uint64_t seed;            /* of the sampler                                   default 0                                   */
+  int32_t iterations;       /* hypotheses per problem, 1..4096                  default 100    :1301 iterationsCount        */
+  int32_t min_inliers;      /* fewer final inliers: status 3                    default 10     :1301 minInliersCount        */
+  int32_t min_points;       /* fewer points: status 1, nothing run; >= 4        default 9      :1282 point_count > 8        */
+  int32_t refine_iters;     /* LM iterations of the refit, 0 = no refit         default 10                                  */
+  int32_t max_trials;       /* LM trials per iteration                          default 5                                   */
+  int32_t device;           /* HIP device ordinal, -1 = current                 default -1                                  */
+} sim3opt_pnp_batch_options;
+
+#define SIM3OPT_PNP_OK 0            /* a pose from at least min_inliers inliers                                  */
+#define SIM3OPT_PNP_FEW_POINTS 1    /* fewer than min_points points: nothing run, the pose is the identity       */
+#define SIM3OPT_PNP_NO_HYPOTHESIS 2 /* no sample gave a pose: the pose is the identity                           */
+#define SIM3OPT_PNP_FEW_INLIERS 3   /* fewer than min_inliers final inliers: the pose is returned all the same    */
+
+void sim3opt_pnp_batch_options_default(sim3opt_pnp_batch_options* o);
+sim3opt_pnp_batch* sim3opt_pnp_batch_create(void);
+void sim3opt_pnp_batch_destroy(sim3opt_pnp_batch* b);
+const char* sim3opt_pnp_batch_last_error(const sim3opt_pnp_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: iterations outside 1..4096, reproj_error <= 0, tau <= 0, min_points < 4,
+ * min_inliers < 0, refine_iters < 0, max_trials < 1, a non-finite value. */
+int sim3opt_pnp_batch_set_options(sim3opt_pnp_batch* b, const sim3opt_pnp_batch_options* o);
+/* The arguments of the call at :1300 for n_problems candidates at once: point_ptr (n_problems + 1, ragged,
+ * point_ptr[0] = 0), points (total x 3 in camera 0's frame: surfPoints[0]), uv1 (total x 2: points2), focal / cx / cy
+ * of K (the reference's distortion is zero).  SIM3OPT_ERR_ARG with nothing changed: n_problems < 1, a problem with no
+ * point, a non-monotone point_ptr, a non-finite number, focal <= 0, a NULL array.  A problem with fewer than
+ * min_points points is accepted and ends with status 1. */
+int sim3opt_pnp_batch_set_problems(sim3opt_pnp_batch* b, int32_t n_problems, const int32_t* point_ptr,
+                                   const double* points, const double* uv1, double focal, double cx, double cy);
+int sim3opt_pnp_batch_dims(const sim3opt_pnp_batch* b, int32_t* n_problems, int32_t* total_points);
+/* Every problem, ONE kernel launch for the batch.  Returns the number of problems with status 0, or a negative
+ * SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no problems set); one problem's failure is its status, never the batch's. */
+int sim3opt_pnp_batch_solve(sim3opt_pnp_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  cam1: n x 7 [qx qy qz qw tx ty tz] of T_w2c, the
+ * layout the batched two-view refinement takes as its cam1 (rvec, tvec of :1300 as a quaternion). */
+int sim3opt_pnp_batch_get_poses(const sim3opt_pnp_batch* b, double* cam1);
+/* mask (total, 1 = inlier of the returned pose) and / or n_inliers (n); either may be NULL */
+int sim3opt_pnp_batch_get_inliers(const sim3opt_pnp_batch* b, uint8_t* mask, int32_t* n_inliers);
+/* Per problem (n each, each may be NULL): status (SIM3OPT_PNP_*), the index of the best hypothesis (-1: none), its
+ * inlier count and the sum of its inliers' squared errors, the RMS error [px] of the final inliers, the LM
+ * iterations the refit ran. */
+int sim3opt_pnp_batch_get_summary(const sim3opt_pnp_batch* b, int32_t* status, int32_t* best_hypothesis,
+                                  int32_t* n_inliers_hypothesis, double* cost_hypothesis, double* rms_px,
+                                  int32_t* refine_iterations);
+/* Diagnostics.  Each leaves the results of the last solve as they were.
+ * What the last solve computed for `problem`, H = options.iterations hypotheses: sample (H x 4 point indices),
+ * n_solutions (P3P solutions with positive depths), valid, pose (H x 7; the identity where not valid), count and cost
+ * of the scoring (0 where not valid).  Each may be NULL.  SIM3OPT_ERR_STATE before the first solve. */
+int sim3opt_pnp_batch_debug_hypotheses(sim3opt_pnp_batch* b, int32_t problem, int32_t* sample, int32_t* n_solutions,
+                                       int32_t* valid, double* pose, int32_t* count, double* cost);
+/* P (1..4096) supplied poses per problem (poses: n x P x 7, any numbers) through the scoring code of k_pnp_ransac:
+ * count and cost (n x P each, one may be NULL). */
+int sim3opt_pnp_batch_debug_score(sim3opt_pnp_batch* b, int32_t P, const double* poses, int32_t* count, double* cost);
+/* The refit of k_pnp_ransac from a supplied pose per problem (poses: n x 7, finite) on a supplied inlier set (mask:
+ * total): pose_out (n x 7), the LM iterations run (n), chi2 (n x 2: the masked points' sum of squared errors before and
+ * after) and trials (n x refine_iters, 0 for iterations not run).  The outputs may be NULL. */
+int sim3opt_pnp_batch_debug_refine(sim3opt_pnp_batch* b, const double* poses, const uint8_t* mask, double* pose_out,
+                                   int32_t* iterations, double* chi2, int32_t* trials);
+/* Host, doubles.  "compute scale change" of :1305-1311 for n_problems candidates: ratio[k] = the element at index
+ * floor(0.5 n) of problem k's sorted depth1 over the same element of its sorted depth0 (sloop, the second number of a
+ * loopConstraints.txt record's line 3).  SIM3OPT_ERR_ARG: as for point_ptr above, a NULL array, a non-finite depth. */
+int sim3opt_median_depth_ratio(int32_t n_problems, const int32_t* point_ptr, const double* depth0,
+                               const double* depth1, double* ratio);
 
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933

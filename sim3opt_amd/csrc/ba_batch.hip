@@ -69,79 +69,6 @@ struct TwoViewArgs {
   int32_t max_iters, max_trials;
 };
 
-// Sum of v[q] over the workgroup, left in v[q] of every thread with the same bits: xor butterfly over the
-// wavefront (a + b and b + a are the same double), then the wavefronts' partials in the order 0, 1, 2, 3.
-template <int N>
-__device__ __forceinline__ void wg_sum(double (&v)[N], double* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    double x = v[q];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    v[q] = x;
-  }
-  __syncthreads();  // the readers of the previous sum are done with red
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) red[wave * N + q] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < N; ++q) v[q] = ((red[q] + red[N + q]) + red[2 * N + q]) + red[3 * N + q];
-}
-
-__device__ __forceinline__ double wg_max(double x, double* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-  __syncthreads();
-  if (lane == 0) red[wave] = x;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-// upper triangle of a symmetric 6x6, row by row
-__device__ __forceinline__ constexpr int tri6(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
-
-// S dx = g by Cholesky (S symmetric, upper triangle given); false on a non-positive pivot
-__device__ __forceinline__ bool chol6_solve(const double Su[21], const double g[6], double x[6]) {
-  double L[6][6];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = Su[tri6(j, j)];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-    if (!(d > 0.0)) ok = false;
-    const double l = sqrt(d);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double s = Su[tri6(j, i)];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
-      L[i][j] = s / l;
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double s = g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-    y[i] = s / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * x[k];
-    x[i] = s / L[i][i];
-  }
-  return ok;
-}
-
 // e, e2 = e^T Omega e, the Huber rho of one observation
 __device__ __forceinline__ double two_view_rho(const TwoViewArgs& A, const double q[4], const double t[3],
                                                const double* p, const double* uv, double& e2) {

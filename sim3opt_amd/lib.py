@@ -141,6 +141,21 @@ class BaBatchOptions(C.Structure):
     ]
 
 
+class PnpBatchOptions(C.Structure):
+    """sim3opt_pnp_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("reproj_error", C.c_double),
+        ("tau", C.c_double),
+        ("seed", C.c_uint64),
+        ("iterations", C.c_int32),
+        ("min_inliers", C.c_int32),
+        ("min_points", C.c_int32),
+        ("refine_iters", C.c_int32),
+        ("max_trials", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -304,6 +319,21 @@ SYMBOLS = {
     "sim3opt_ba_batch_get_stats": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(IterStats)]),
     "sim3opt_ba_batch_get_lambda_init": (C.c_int, [_vp, _dp]),
     "sim3opt_ba_batch_get_chi2": (C.c_int, [_vp, _dp, _dp, _dp, _ip]),
+    "sim3opt_pnp_batch_options_default": (None, [C.POINTER(PnpBatchOptions)]),
+    "sim3opt_pnp_batch_create": (_vp, []),
+    "sim3opt_pnp_batch_destroy": (None, [_vp]),
+    "sim3opt_pnp_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_pnp_batch_set_options": (C.c_int, [_vp, C.POINTER(PnpBatchOptions)]),
+    "sim3opt_pnp_batch_set_problems": (C.c_int, [_vp, C.c_int32, _ip, _dp, _dp, C.c_double, C.c_double, C.c_double]),
+    "sim3opt_pnp_batch_dims": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_pnp_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_pnp_batch_get_poses": (C.c_int, [_vp, _dp]),
+    "sim3opt_pnp_batch_get_inliers": (C.c_int, [_vp, _up, _ip]),
+    "sim3opt_pnp_batch_get_summary": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp, _ip]),
+    "sim3opt_pnp_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
+    "sim3opt_pnp_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
+    "sim3opt_pnp_batch_debug_refine": (C.c_int, [_vp, _dp, _up, _dp, _ip, _dp, _ip]),
+    "sim3opt_median_depth_ratio": (C.c_int, [C.c_int32, _ip, _dp, _dp, _dp]),
 }
 
 _lib = None
@@ -1454,6 +1484,151 @@ class TwoViewBatch:
         self._chk(self._L.sim3opt_ba_batch_get_chi2(self._b, _p(ab, _dp), _p(aa, _dp), _p(ec, _dp), _p(no, _ip)),
                   "ba_batch_get_chi2")
         return dict(active_before=ab, active_after=aa, edge_chi2=ec, n_outlier_edges=no)
+
+
+PNP_OK, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS, PNP_FEW_INLIERS = 0, 1, 2, 3
+
+
+class PnpBatch:
+    """sim3opt_pnp_batch*: the loop detector's start pose (cv::solvePnPRansac, kittiDetector.h:1300-1301) of a whole
+    batch of loop candidates in one kernel launch -- P3P hypotheses from a reproducible sampler, every one scored,
+    an LM refit over the best one's inliers.  Problem k owns the points point_ptr[k]:point_ptr[k+1] of the flat
+    arrays; poses() is the cam1 TwoViewBatch.set_problems takes."""
+
+    def __init__(self, **options):
+        self._L = load()
+        self._b = self._L.sim3opt_pnp_batch_create()
+        if not self._b:
+            raise MemoryError("sim3opt_pnp_batch_create")
+        self._opt = PnpBatchOptions()
+        self._L.sim3opt_pnp_batch_options_default(C.byref(self._opt))
+        if options:
+            self.set_options(**options)
+
+    def close(self):
+        if self._b:
+            self._L.sim3opt_pnp_batch_destroy(self._b)
+            self._b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != OK:
+            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_pnp_batch_last_error(self._b).decode()}")
+
+    def set_options(self, **kw):
+        """The defaults with `kw` over them (as TwoViewBatch.set_options)."""
+        o = PnpBatchOptions()
+        self._L.sim3opt_pnp_batch_options_default(C.byref(o))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        self._chk(self._L.sim3opt_pnp_batch_set_options(self._b, C.byref(o)), "pnp_batch_set_options")
+        self._opt = o
+
+    def options(self):
+        return {k: getattr(self._opt, k) for k, _ in PnpBatchOptions._fields_}
+
+    def set_problems(self, point_ptr, points, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        ptr = _i32(point_ptr).reshape(-1)
+        pts, a = _f64(points).reshape(-1, 3), _f64(uv1).reshape(-1, 2)
+        n = ptr.shape[0] - 1
+        if n >= 1 and not (pts.shape[0] == a.shape[0] and pts.shape[0] >= ptr.max()):
+            raise ValueError("point and observation arrays shorter than point_ptr says")
+        self._chk(self._L.sim3opt_pnp_batch_set_problems(self._b, n, _p(ptr, _ip), _p(pts, _dp), _p(a, _dp), focal, cx,
+                                                         cy), "pnp_batch_set_problems")
+
+    def dims(self):
+        """(problems, points of all problems)"""
+        a, b = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_pnp_batch_dims(self._b, C.byref(a), C.byref(b)), "pnp_batch_dims")
+        return a.value, b.value
+
+    def solve(self):
+        """Problems with status 0 (one launch); raises when the library reports an error."""
+        n = self._L.sim3opt_pnp_batch_solve(self._b)
+        if n < 0:
+            self._chk(n, "pnp_batch_solve")
+        return n
+
+    def poses(self):
+        """cam1 (n, 7) [qx qy qz qw tx ty tz]"""
+        out = np.empty((self.dims()[0], 7))
+        self._chk(self._L.sim3opt_pnp_batch_get_poses(self._b, _p(out, _dp)), "pnp_batch_get_poses")
+        return out
+
+    def inliers(self):
+        """(mask (total,) uint8, n_inliers (n,))"""
+        n, t = self.dims()
+        m, c = np.empty(t, dtype=np.uint8), np.empty(n, dtype=np.int32)
+        self._chk(self._L.sim3opt_pnp_batch_get_inliers(self._b, _p(m, _up), _p(c, _ip)), "pnp_batch_get_inliers")
+        return m, c
+
+    def summary(self):
+        """dict of (n,) arrays: status, best_hypothesis, n_inliers_hypothesis, cost_hypothesis, rms_px,
+        refine_iterations"""
+        n = self.dims()[0]
+        i = lambda: np.empty(n, dtype=np.int32)
+        st, bh, nh, ch, rm, ri = i(), i(), i(), np.empty(n), np.empty(n), i()
+        self._chk(self._L.sim3opt_pnp_batch_get_summary(self._b, _p(st, _ip), _p(bh, _ip), _p(nh, _ip), _p(ch, _dp),
+                                                        _p(rm, _dp), _p(ri, _ip)), "pnp_batch_get_summary")
+        return dict(status=st, best_hypothesis=bh, n_inliers_hypothesis=nh, cost_hypothesis=ch, rms_px=rm,
+                    refine_iterations=ri)
+
+    def debug_hypotheses(self, problem):
+        """What the last solve computed for `problem`: dict of sample (H, 4), n_solutions, valid, count (H,), pose
+        (H, 7), cost (H,)."""
+        H = self._opt.iterations
+        i = lambda *s: np.empty(s, dtype=np.int32)
+        sm, ns, va, po, co, cs = i(H, 4), i(H), i(H), np.empty((H, 7)), i(H), np.empty(H)
+        self._chk(self._L.sim3opt_pnp_batch_debug_hypotheses(self._b, int(problem), _p(sm, _ip), _p(ns, _ip),
+                                                             _p(va, _ip), _p(po, _dp), _p(co, _ip), _p(cs, _dp)),
+                  "pnp_batch_debug_hypotheses")
+        return dict(sample=sm, n_solutions=ns, valid=va, pose=po, count=co, cost=cs)
+
+    def debug_score(self, poses):
+        """poses (n, P, 7) through the kernel's scoring: (count (n, P) int32, cost (n, P))"""
+        n = self.dims()[0]
+        q = _f64(poses).reshape(n, -1, 7)
+        P = q.shape[1]
+        co, cs = np.empty((n, P), dtype=np.int32), np.empty((n, P))
+        self._chk(self._L.sim3opt_pnp_batch_debug_score(self._b, P, _p(q, _dp), _p(co, _ip), _p(cs, _dp)),
+                  "pnp_batch_debug_score")
+        return co, cs
+
+    def debug_refine(self, poses, mask):
+        """The kernel's refit from poses (n, 7) on mask (total,): dict of pose (n, 7), iterations (n,), chi2 (n, 2:
+        before, after), trials (n, refine_iters)."""
+        n, t = self.dims()
+        q = _f64(poses).reshape(-1)
+        m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        if q.shape[0] != 7 * n or m.shape[0] != t:
+            raise ValueError("poses holds 7 numbers per problem, mask one entry per point")
+        po, it, ch = np.empty((n, 7)), np.empty(n, dtype=np.int32), np.empty((n, 2))
+        tr = np.zeros((n, self._opt.refine_iters), dtype=np.int32)
+        self._chk(self._L.sim3opt_pnp_batch_debug_refine(self._b, _p(q, _dp), _p(m, _up), _p(po, _dp), _p(it, _ip),
+                                                         _p(ch, _dp), _p(tr, _ip)), "pnp_batch_debug_refine")
+        return dict(pose=po, iterations=it, chi2=ch, trials=tr)
+
+
+def median_depth_ratio(point_ptr, depth0, depth1):
+    """sim3opt_median_depth_ratio: per problem, the element at index floor(0.5 n) of the sorted depth1 over that of the
+    sorted depth0 (kittiDetector.h:1305-1311).  Host only."""
+    ptr = _i32(point_ptr).reshape(-1)
+    a, b = _f64(depth0).reshape(-1), _f64(depth1).reshape(-1)
+    n = ptr.shape[0] - 1
+    if n >= 1 and not (a.shape[0] == b.shape[0] and a.shape[0] >= ptr.max()):
+        raise ValueError("depth arrays shorter than point_ptr says")
+    out = np.empty(max(n, 0))
+    rc = load().sim3opt_median_depth_ratio(n, _p(ptr, _ip), _p(a, _dp), _p(b, _dp), _p(out, _dp))
+    if rc != OK:
+        raise Sim3OptError(rc, "median_depth_ratio")
+    return out
 
 
 def align_trajectory(query_xyz, train_xyz, with_scale=True):
