@@ -696,7 +696,7 @@ int sim3opt_device_bytes_of_rank(const sim3opt_graph* g, int32_t rank, int64_t b
  * call it yourself before allocating large device buffers of your own next to a live handle. */
 void sim3opt_release_device_cache(void);
 /* Diagnostic.  out = {blocks, bytes} of device memory the library has handed to its handles and calls and not got
- * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch of the process, on all
+ * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch of the process, on all
  * devices; bytes as the block cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
  * that creates no handle and initialises none is what "this call keeps no device memory" means
  * (tests/test_gpu_device_memory.py). */
@@ -977,6 +977,93 @@ int sim3opt_pnp_batch_debug_refine(sim3opt_pnp_batch* b, const double* poses, co
  * loopConstraints.txt record's line 3).  SIM3OPT_ERR_ARG: as for point_ptr above, a NULL array, a non-finite depth. */
 int sim3opt_median_depth_ratio(int32_t n_problems, const int32_t* point_ptr, const double* depth0,
                                const double* depth1, double* ratio);
+
+/* ---- batched descriptor matching and map-depth lookup: what the three blocks above consume, every candidate at once ----
+ * The front of computeConstraints: matcher.match / knnMatch(.., 2) with the ratio test, the 1/10 image-border filter,
+ * the skew filter and the uniqueness pass (kittiDetector.h:1085-1160), then the depth of every kept match in both
+ * keyframes as the mean over the K = 6 map-point observations nearest in the image (cv::ml::KNearest, :1229-1279) and
+ * surfPoints[0] = depth K^-1 (u, v, 1)^T.  match_ptr / points0 / uv1 are the point_ptr / points / uv1 of
+ * sim3opt_pnp_batch_set_problems, uv0 / uv1 / points0 what sim3opt_ba_batch_set_problems takes, depth0 / depth1 what
+ * sim3opt_median_depth_ratio takes.
+ * PARITY UNPINNED: the reference stores neither descriptors nor matches, and its FlannBasedMatcher is an approximate
+ * search over randomised trees.  Here the search is exact and deterministic.  The filters, their constants, the
+ * uniqueness rule, K = 6 and the mean are the reference's.
+ * Definition.  d2(i, j) = sum_k (a_ik - b_jk)^2 in FP32 (the difference form: near-duplicate descriptors do not
+ * cancel), distance = sqrtf(d2).  The nearest train descriptor has the smallest d2, the lower index on equal d2; the
+ * second nearest likewise among the rest.  ratio > 0 keeps a query iff n_train >= 2 and (d_1 == 0 && d_2 > 0) or
+ * d_2 / d_1 > ratio (a float division of the two distances).  Border: both keypoints' x in [border_ratio w,
+ * (1 - border_ratio) w] and y likewise with h; skew: |y1 - y0| < skew_y h and |x1 - x0| < skew_x w; all in double on
+ * the float pixels.  Uniqueness: among kept queries with one train index the smallest d2 survives, the lower query
+ * index on equal d2.  Survivors are listed by ascending query index.  Depth of a match on side c (side 0: the query
+ * keypoint, frame0's observations): the min(K, n_obs) observations with the smallest FP32 squared pixel distance
+ * fl(fl(dx dx) + fl(dy dy)), the lower index on equal distance; their obs_depth summed in double in that order, divided
+ * by their number and rounded to float.  points0 = depth0 ((u - cx) / f, (v - cy) / f, 1) in double.
+ * Device pipeline: sim3opt_amd/csrc/match_batch.hip; the launches of a solve do not depend on the number of pairs, and
+ * a pair's result does not depend on the other pairs or its place among them.  No CPU fallback:
+ * SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_match_batch sim3opt_match_batch;
+
+typedef struct sim3opt_match_batch_options {
+  double ratio;         /* ratio test of USE_KNN_MATCH, 0 = off (the reference's build)   default 0      :1097 thresh        */
+  double border_ratio;  /* keypoints this share of the image from its edge or closer go   default 0.1    :1101 boundaryRatio */
+  double skew_x;        /* |x1 - x0| < skew_x * image_width                               default 1/3    :1106 skewThreshX   */
+  double skew_y;        /* |y1 - y0| < skew_y * image_height                              default 1/4    :1106 skewThreshY   */
+  int32_t knn_k;        /* observations a depth is the mean of, 1..16                     default 6      :1238 K             */
+  int32_t device;       /* HIP device ordinal, -1 = current                               default -1                         */
+} sim3opt_match_batch_options;
+
+#define SIM3OPT_MATCH_OK 0            /* matched (possibly with no match left)                                   */
+#define SIM3OPT_MATCH_NO_KEYPOINTS 1  /* one of the two frames has no keypoint: no matches                        */
+#define SIM3OPT_MATCH_NO_MAP 2        /* one of the two frames has no map-point observation: no matches           */
+
+void sim3opt_match_batch_options_default(sim3opt_match_batch_options* o);
+sim3opt_match_batch* sim3opt_match_batch_create(void);
+void sim3opt_match_batch_destroy(sim3opt_match_batch* b);
+const char* sim3opt_match_batch_last_error(const sim3opt_match_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: a negative or non-finite threshold, knn_k outside 1..16. */
+int sim3opt_match_batch_set_options(sim3opt_match_batch* b, const sim3opt_match_batch_options* o);
+/* n_frames ragged frames: frame f owns the keypoints kp_ptr[f]:kp_ptr[f+1] of kp (x 2, pixels) and desc (x 64) and the
+ * observations obs_ptr[f]:obs_ptr[f+1] of obs_uv (x 2) and obs_depth (z of the map point in that camera's frame); a
+ * frame may have none of either.  SIM3OPT_ERR_ARG with nothing changed: n_frames < 1, a NULL array, a pointer array
+ * that does not start at 0 or decreases, a non-finite number, focal <= 0, a non-positive image size.  A successful call
+ * drops the pairs and the results of the last solve. */
+int sim3opt_match_batch_set_frames(sim3opt_match_batch* b, int32_t n_frames, const int32_t* kp_ptr,
+                                   const int32_t* obs_ptr, const float* kp, const float* desc, const float* obs_uv,
+                                   const float* obs_depth, double focal, double cx, double cy, int32_t image_width,
+                                   int32_t image_height);
+/* pairs: n_pairs x 2 (frame0 = the query side, frame1); a frame may be in any number of pairs, and in both places of
+ * one.  SIM3OPT_ERR_STATE before set_frames; SIM3OPT_ERR_ARG with nothing changed: n_pairs < 1, NULL, a frame index
+ * out of range.  A successful call drops the results of the last solve; the frames stay on the device. */
+int sim3opt_match_batch_set_pairs(sim3opt_match_batch* b, int32_t n_pairs, const int32_t* pairs);
+/* Each may be NULL.  tiles[4]: the lanes of a wavefront, the queries of a workgroup of k_match_nn, the train descriptors
+ * and the observations staged in LDS at a time: the sizes at which the kernels take another path. */
+int sim3opt_match_batch_dims(const sim3opt_match_batch* b, int32_t* n_frames, int32_t* n_pairs,
+                             int32_t* total_keypoints, int32_t* total_observations, int32_t tiles[4]);
+/* Every pair; the same launches whatever their number.  Returns the number of pairs with status 0, or a negative
+ * SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no frames or no pairs set); one pair's failure is its status, never the batch's. */
+int sim3opt_match_batch_solve(sim3opt_match_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  match_ptr: n_pairs + 1. */
+int sim3opt_match_batch_get_match_ptr(const sim3opt_match_batch* b, int32_t* match_ptr);
+/* Per match (total = match_ptr[n_pairs]), each may be NULL: query_idx and train_idx within their frames, distance,
+ * uv0 and uv1 (x 2), depth0 and depth1, points0 (x 3). */
+int sim3opt_match_batch_get_matches(const sim3opt_match_batch* b, int32_t* query_idx, int32_t* train_idx,
+                                    float* distance, double* uv0, double* uv1, double* depth0, double* depth1,
+                                    double* points0);
+/* Per pair (n_pairs each, each may be NULL): status (SIM3OPT_MATCH_*) and the queries left after each stage: with a
+ * nearest neighbour, after the ratio test, after border and skew, after uniqueness (= the pair's matches). */
+int sim3opt_match_batch_get_summary(const sim3opt_match_batch* b, int32_t* status, int32_t* n_nearest,
+                                    int32_t* n_after_ratio, int32_t* n_after_filters, int32_t* n_after_unique);
+/* Diagnostics.  Each leaves the results of the last solve as they were.
+ * What k_match_nn wrote for every query of `pair` in the last solve (n_query each, each may be NULL); second_idx = -1
+ * and second_d2 = +inf with one train keypoint.  SIM3OPT_ERR_STATE before the first solve and for a pair whose status
+ * is not 0 (nothing was computed for it). */
+int sim3opt_match_batch_debug_nn(sim3opt_match_batch* b, int32_t pair, int32_t* best_idx, float* best_d2,
+                                 int32_t* second_idx, float* second_d2);
+/* n supplied pixels (uv: n x 2, finite) through the K-nearest code of k_match_depth on the observations of `frame`:
+ * depth (n) and the chosen observations in (distance, index) order (neighbours: n x knn_k, -1 padded).  Needs frames
+ * (SIM3OPT_ERR_STATE) with at least one observation in `frame` (SIM3OPT_ERR_ARG), no solve. */
+int sim3opt_match_batch_debug_depth(sim3opt_match_batch* b, int32_t n, int32_t frame, const float* uv, double* depth,
+                                    int32_t* neighbours);
 
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933

@@ -156,6 +156,18 @@ class PnpBatchOptions(C.Structure):
     ]
 
 
+class MatchBatchOptions(C.Structure):
+    """sim3opt_match_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("ratio", C.c_double),
+        ("border_ratio", C.c_double),
+        ("skew_x", C.c_double),
+        ("skew_y", C.c_double),
+        ("knn_k", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -180,6 +192,7 @@ class CommTimes(C.Structure):
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _up = C.POINTER(C.c_uint8)
+_fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 SYMBOLS = {
     "sim3opt_version": (C.c_int, []),
@@ -333,6 +346,21 @@ SYMBOLS = {
     "sim3opt_pnp_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
     "sim3opt_pnp_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
     "sim3opt_pnp_batch_debug_refine": (C.c_int, [_vp, _dp, _up, _dp, _ip, _dp, _ip]),
+    "sim3opt_match_batch_options_default": (None, [C.POINTER(MatchBatchOptions)]),
+    "sim3opt_match_batch_create": (_vp, []),
+    "sim3opt_match_batch_destroy": (None, [_vp]),
+    "sim3opt_match_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_match_batch_set_options": (C.c_int, [_vp, C.POINTER(MatchBatchOptions)]),
+    "sim3opt_match_batch_set_frames": (C.c_int, [_vp, C.c_int32, _ip, _ip, _fp, _fp, _fp, _fp, C.c_double, C.c_double,
+                                                 C.c_double, C.c_int32, C.c_int32]),
+    "sim3opt_match_batch_set_pairs": (C.c_int, [_vp, C.c_int32, _ip]),
+    "sim3opt_match_batch_dims": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_match_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_match_batch_get_match_ptr": (C.c_int, [_vp, _ip]),
+    "sim3opt_match_batch_get_matches": (C.c_int, [_vp, _ip, _ip, _fp, _dp, _dp, _dp, _dp, _dp]),
+    "sim3opt_match_batch_get_summary": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_match_batch_debug_nn": (C.c_int, [_vp, C.c_int32, _ip, _fp, _ip, _fp]),
+    "sim3opt_match_batch_debug_depth": (C.c_int, [_vp, C.c_int32, C.c_int32, _fp, _dp, _ip]),
     "sim3opt_median_depth_ratio": (C.c_int, [C.c_int32, _ip, _dp, _dp, _dp]),
 }
 
@@ -1629,6 +1657,145 @@ def median_depth_ratio(point_ptr, depth0, depth1):
     if rc != OK:
         raise Sim3OptError(rc, "median_depth_ratio")
     return out
+
+
+MATCH_OK, MATCH_NO_KEYPOINTS, MATCH_NO_MAP = 0, 1, 2
+KITTI_WIDTH, KITTI_HEIGHT = 1241, 376  # (KITTI-00's images)
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class MatchBatch:
+    """sim3opt_match_batch*: descriptor matching with the reference's filters (kittiDetector.h:1085-1160) and the
+    map-depth lookup (:1229-1279) of a whole batch of loop candidates.  Frames are handed over once, pairs name them;
+    match_ptr() / matches() are the point_ptr, points, uv0 / uv1 and depths PnpBatch, TwoViewBatch and
+    median_depth_ratio take."""
+
+    def __init__(self, **options):
+        self._L = load()
+        self._b = self._L.sim3opt_match_batch_create()
+        if not self._b:
+            raise MemoryError("sim3opt_match_batch_create")
+        self._opt = MatchBatchOptions()
+        self._n_kp = self._pairs = None
+        self._L.sim3opt_match_batch_options_default(C.byref(self._opt))
+        if options:
+            self.set_options(**options)
+
+    def close(self):
+        if self._b:
+            self._L.sim3opt_match_batch_destroy(self._b)
+            self._b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != OK:
+            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_match_batch_last_error(self._b).decode()}")
+
+    def set_options(self, **kw):
+        """The defaults with `kw` over them (as PnpBatch.set_options)."""
+        o = MatchBatchOptions()
+        self._L.sim3opt_match_batch_options_default(C.byref(o))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        self._chk(self._L.sim3opt_match_batch_set_options(self._b, C.byref(o)), "match_batch_set_options")
+        self._opt = o
+
+    def options(self):
+        return {k: getattr(self._opt, k) for k, _ in MatchBatchOptions._fields_}
+
+    def set_frames(self, kp_ptr, obs_ptr, kp, desc, obs_uv, obs_depth, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY,
+                   image_width=KITTI_WIDTH, image_height=KITTI_HEIGHT):
+        kpp, obp = _i32(kp_ptr).reshape(-1), _i32(obs_ptr).reshape(-1)
+        k, d = _f32(kp).reshape(-1, 2), _f32(desc).reshape(-1, 64)
+        ou, od = _f32(obs_uv).reshape(-1, 2), _f32(obs_depth).reshape(-1)
+        n = kpp.shape[0] - 1
+        if obp.shape[0] != n + 1:
+            raise ValueError("kp_ptr and obs_ptr hold one entry per frame and one more")
+        if n >= 1 and not (k.shape[0] == d.shape[0] and k.shape[0] >= kpp.max() and ou.shape[0] == od.shape[0]
+                           and ou.shape[0] >= obp.max()):
+            raise ValueError("keypoint or observation arrays shorter than their pointer arrays say")
+        self._chk(self._L.sim3opt_match_batch_set_frames(self._b, n, _p(kpp, _ip), _p(obp, _ip), _p(k, _fp), _p(d, _fp),
+                                                         _p(ou, _fp), _p(od, _fp), focal, cx, cy, int(image_width),
+                                                         int(image_height)), "match_batch_set_frames")
+        self._n_kp, self._pairs = np.diff(kpp), None  # (what debug_nn sizes its arrays by; the pairs went with the frames)
+
+    def set_pairs(self, pairs):
+        p = _i32(pairs).reshape(-1, 2)
+        self._chk(self._L.sim3opt_match_batch_set_pairs(self._b, p.shape[0], _p(p, _ip)), "match_batch_set_pairs")
+        self._pairs = p.copy()
+
+    def dims(self):
+        """dict: n_frames, n_pairs, total_keypoints, total_observations and the kernels' tile sizes wavefront,
+        query_tile, train_tile, obs_chunk"""
+        v = [C.c_int32() for _ in range(4)]
+        t = (C.c_int32 * 4)()
+        self._chk(self._L.sim3opt_match_batch_dims(self._b, *(C.byref(x) for x in v), t), "match_batch_dims")
+        return dict(n_frames=v[0].value, n_pairs=v[1].value, total_keypoints=v[2].value,
+                    total_observations=v[3].value, wavefront=t[0], query_tile=t[1], train_tile=t[2], obs_chunk=t[3])
+
+    def solve(self):
+        """Pairs with status 0; raises when the library reports an error."""
+        n = self._L.sim3opt_match_batch_solve(self._b)
+        if n < 0:
+            self._chk(n, "match_batch_solve")
+        return n
+
+    def match_ptr(self):
+        out = np.empty(self.dims()["n_pairs"] + 1, dtype=np.int32)
+        self._chk(self._L.sim3opt_match_batch_get_match_ptr(self._b, _p(out, _ip)), "match_batch_get_match_ptr")
+        return out
+
+    def matches(self):
+        """dict of per-match arrays: query_idx, train_idx (int32), distance (float32), uv0, uv1 (M, 2), depth0,
+        depth1 (M,), points0 (M, 3)"""
+        M = int(self.match_ptr()[-1])
+        q, t = np.empty(M, dtype=np.int32), np.empty(M, dtype=np.int32)
+        d = np.empty(M, dtype=np.float32)
+        u0, u1, z0, z1, pt = np.empty((M, 2)), np.empty((M, 2)), np.empty(M), np.empty(M), np.empty((M, 3))
+        self._chk(self._L.sim3opt_match_batch_get_matches(self._b, _p(q, _ip), _p(t, _ip), _p(d, _fp), _p(u0, _dp),
+                                                          _p(u1, _dp), _p(z0, _dp), _p(z1, _dp), _p(pt, _dp)),
+                  "match_batch_get_matches")
+        return dict(query_idx=q, train_idx=t, distance=d, uv0=u0, uv1=u1, depth0=z0, depth1=z1, points0=pt)
+
+    def summary(self):
+        """dict of (n_pairs,) arrays: status, n_nearest, n_after_ratio, n_after_filters, n_after_unique"""
+        n = self.dims()["n_pairs"]
+        a = [np.empty(n, dtype=np.int32) for _ in range(5)]
+        self._chk(self._L.sim3opt_match_batch_get_summary(self._b, *(_p(x, _ip) for x in a)), "match_batch_get_summary")
+        return dict(zip(("status", "n_nearest", "n_after_ratio", "n_after_filters", "n_after_unique"), a))
+
+    def debug_nn(self, pair):
+        """What k_match_nn wrote for every query of `pair` (the keypoints of its frame0): dict of best_idx, best_d2,
+        second_idx, second_d2."""
+        if self._pairs is None or not 0 <= int(pair) < self._pairs.shape[0]:
+            n_query = 0  # (the library says what is wrong: no pairs, no solve, no such pair)
+        else:
+            n_query = int(self._n_kp[self._pairs[int(pair), 0]])
+        bi, si = np.empty(n_query, dtype=np.int32), np.empty(n_query, dtype=np.int32)
+        bd, sd = np.empty(n_query, dtype=np.float32), np.empty(n_query, dtype=np.float32)
+        self._chk(self._L.sim3opt_match_batch_debug_nn(self._b, int(pair), _p(bi, _ip), _p(bd, _fp), _p(si, _ip),
+                                                       _p(sd, _fp)), "match_batch_debug_nn")
+        return dict(best_idx=bi, best_d2=bd, second_idx=si, second_d2=sd)
+
+    def debug_depth(self, frame, uv):
+        """Pixels uv (n, 2) through the kernel's K-nearest code on `frame`'s observations: (depth (n,), neighbours
+        (n, knn_k) int32, -1 padded)."""
+        q = _f32(uv).reshape(-1, 2)
+        n = q.shape[0]
+        z, nb = np.empty(n), np.empty((n, self._opt.knn_k), dtype=np.int32)
+        self._chk(self._L.sim3opt_match_batch_debug_depth(self._b, n, int(frame), _p(q, _fp), _p(z, _dp), _p(nb, _ip)),
+                  "match_batch_debug_depth")
+        return z, nb
 
 
 def align_trajectory(query_xyz, train_xyz, with_scale=True):
