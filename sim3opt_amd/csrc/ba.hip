@@ -42,7 +42,7 @@
 
 #include "../../include/sim3opt.h"
 #include "ba_math.hpp"
-#include "devmem.hpp"
+#include "handle_device.hpp"
 #include "direct_factor.hpp"
 #include "lm_damping.hpp"
 
@@ -543,15 +543,7 @@ struct Problem {
 
   int initialize() {
     release();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-      err = "no usable HIP device (libsim3opt has no CPU fallback)";
-      return SIM3OPT_ERR_NO_DEVICE;
-    }
-    if (opt.device >= 0) {
-      if (opt.device >= ndev) { err = "device ordinal out of range"; return SIM3OPT_ERR_ARG; }
-      HIPCHK(hipSetDevice(opt.device));
-    }
+    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
     const int NC = nc(), NP = np(), NO = no();
     if (NC < 1 || NP < 1 || NO < 1) { err = "empty problem"; return SIM3OPT_ERR_STATE; }
     // observation lists per point / per camera, ascending observation index
@@ -924,20 +916,9 @@ void sim3opt_ba_options_default(sim3opt_ba_options* o) {
   o->verbose = 0;
 }
 
-sim3opt_ba* sim3opt_ba_create(void) {
-  sim3opt_ba* b = new (std::nothrow) sim3opt_ba();
-  if (b) {
-    sim3opt_ba_options_default(&b->opt);
-    sim3opt::handle_count(+1);
-  }
-  return b;
-}
+sim3opt_ba* sim3opt_ba_create(void) { return sim3opt::handle_create<sim3opt_ba>(sim3opt_ba_options_default); }
 
-void sim3opt_ba_destroy(sim3opt_ba* b) {
-  if (!b) return;
-  delete b;
-  if (sim3opt::handle_count(-1) == 0) sim3opt::dev_cache_release();
-}
+void sim3opt_ba_destroy(sim3opt_ba* b) { sim3opt::handle_destroy(b); }
 
 const char* sim3opt_ba_last_error(const sim3opt_ba* b) { return b ? b->err.c_str() : "null problem"; }
 
@@ -963,18 +944,16 @@ int sim3opt_ba_set_problem(sim3opt_ba* b, int32_t n_cams, const double* cam_qt, 
     if (b) b->err = "ba_set_problem: bad argument";
     return SIM3OPT_ERR_ARG;
   }
-  try {
+  return sim3opt::guarded(b, "ba_set_problem", sim3opt::NO_MEMORY, [&]() -> int {
   for (int32_t o = 0; o < n_obs; ++o)
     if (obs_cam[o] < 0 || obs_cam[o] >= n_cams || obs_point[o] < 0 || obs_point[o] >= n_points) {
       b->err = "ba_set_problem: observation index out of range";  // (the reference asserts, :140-143)
       return SIM3OPT_ERR_ARG;
     }
-  for (size_t i = 0; i < 7 * (size_t)n_cams; ++i)
-    if (!std::isfinite(cam_qt[i])) { b->err = "ba_set_problem: non-finite camera"; return SIM3OPT_ERR_ARG; }
-  for (size_t i = 0; i < 3 * (size_t)n_points; ++i)
-    if (!std::isfinite(points[i])) { b->err = "ba_set_problem: non-finite point"; return SIM3OPT_ERR_ARG; }
-  for (size_t i = 0; i < 2 * (size_t)n_obs; ++i)
-    if (!std::isfinite(obs_uv[i])) { b->err = "ba_set_problem: non-finite observation"; return SIM3OPT_ERR_ARG; }
+  using sim3opt::all_finite;
+  if (!all_finite(cam_qt, 7 * (size_t)n_cams)) { b->err = "ba_set_problem: non-finite camera"; return SIM3OPT_ERR_ARG; }
+  if (!all_finite(points, 3 * (size_t)n_points)) { b->err = "ba_set_problem: non-finite point"; return SIM3OPT_ERR_ARG; }
+  if (!all_finite(obs_uv, 2 * (size_t)n_obs)) { b->err = "ba_set_problem: non-finite observation"; return SIM3OPT_ERR_ARG; }
   b->release();
   b->cams.resize(n_cams);
   for (int32_t c = 0; c < n_cams; ++c) {
@@ -993,22 +972,18 @@ int sim3opt_ba_set_problem(sim3opt_ba* b, int32_t n_cams, const double* cam_qt, 
   b->cam_fixed.assign(n_cams, 0);
   b->stats.clear();
   return SIM3OPT_OK;
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_set_problem: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_set_fixed_cameras(sim3opt_ba* b, const uint8_t* fixed) {
   if (!b || !fixed) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_set_fixed_cameras", sim3opt::NO_MEMORY, [&]() -> int {
   if (b->nc() < 1) { b->err = "ba_set_fixed_cameras: no problem set"; return SIM3OPT_ERR_STATE; }
   b->cam_fixed.assign(fixed, fixed + b->nc());
   for (auto& f : b->cam_fixed) f = f ? 1 : 0;
   b->release();  // the next call re-uploads
   return SIM3OPT_OK;
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_set_fixed_cameras: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 // The BAL file as ba_demo reads it (bal_example.cpp:104-189): "<cams> <points> <observations>", one
@@ -1081,12 +1056,10 @@ int sim3opt_ba_dims(const sim3opt_ba* b, int32_t* n_cams, int32_t* n_points, int
 
 int sim3opt_ba_chi2(sim3opt_ba* b, double* chi2) {
   if (!b || !chi2) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_chi2", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
   if (!b->ready) { int rc = b->initialize(); if (rc) return rc; }
   return b->chi2(chi2);
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_chi2: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 // ---- diagnostic read-outs (include/sim3opt.h, "Diagnostic."): nothing in the solver uses them ----
@@ -1102,7 +1075,7 @@ int ba_debug_enter(sim3opt_ba* b, const char* what) {
 
 int sim3opt_ba_debug_pattern(sim3opt_ba* b, int32_t* n_blocks, int32_t* rptr, int32_t* bcol) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_debug_pattern", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
   int rc = ba_debug_enter(b, "ba_debug_pattern");
   if (rc) return rc;
   if (!n_blocks || (!rptr != !bcol)) { b->err = "ba_debug_pattern: NULL output"; return SIM3OPT_ERR_ARG; }
@@ -1112,27 +1085,23 @@ int sim3opt_ba_debug_pattern(sim3opt_ba* b, int32_t* n_blocks, int32_t* rptr, in
       (rc = b->down(bcol, b->d_bcol, sizeof(int32_t) * b->nblk)))
     return rc;
   return SIM3OPT_OK;
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_debug_pattern: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_debug_linearization(sim3opt_ba* b, double* lin) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_debug_linearization", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
   int rc = ba_debug_enter(b, "ba_debug_linearization");
   if (rc) return rc;
   if (!lin) { b->err = "ba_debug_linearization: NULL output"; return SIM3OPT_ERR_ARG; }
   return b->read_lin(lin);
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_debug_linearization: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_debug_reduced(sim3opt_ba* b, double lambda, double* S, double* g, double* b_c, double* Hpp_inv,
                              double* b_p, double* Z, double* point_maxdiag, double* cam_maxdiag, double* maxdiag) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_debug_reduced", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
   int rc = ba_debug_enter(b, "ba_debug_reduced");
   if (rc) return rc;
   if (!std::isfinite(lambda)) { b->err = "ba_debug_reduced: lambda is not finite"; return SIM3OPT_ERR_ARG; }
@@ -1141,15 +1110,13 @@ int sim3opt_ba_debug_reduced(sim3opt_ba* b, double lambda, double* S, double* g,
     return SIM3OPT_ERR_ARG;
   }
   return b->read_reduced(lambda, S, g, b_c, Hpp_inv, b_p, Z, point_maxdiag, cam_maxdiag, maxdiag);
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_debug_reduced: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_debug_step(sim3opt_ba* b, double lambda, int32_t solver, int32_t pcg_max_iters, double pcg_rel_tol,
                           double* dx_c, double* dx_p, int32_t* pcg_iters, double* pcg_rel, int32_t* fail) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_debug_step", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
   int rc = ba_debug_enter(b, "ba_debug_step");
   if (rc) return rc;
   if (!std::isfinite(lambda) || solver < 0 || solver > 1 || pcg_max_iters < 0 || !(pcg_rel_tol >= 0)) {
@@ -1163,24 +1130,20 @@ int sim3opt_ba_debug_step(sim3opt_ba* b, double lambda, int32_t solver, int32_t 
     return SIM3OPT_ERR_STATE;
   }
   return b->read_step(lambda, solver == 1, pcg_max_iters, pcg_rel_tol, dx_c, dx_p, pcg_iters, pcg_rel, fail);
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_debug_step: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_debug_update(sim3opt_ba* b, const double* dx_c, const double* dx_p, double lambda, int32_t with_fail,
                             double* cam_qt, double* points, double* chi2, double* scale) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "ba_debug_update", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
   int rc = ba_debug_enter(b, "ba_debug_update");
   if (rc) return rc;
   if (!dx_c || !dx_p) { b->err = "ba_debug_update: NULL step"; return SIM3OPT_ERR_ARG; }
   if (!cam_qt && !points && !chi2 && !scale) { b->err = "ba_debug_update: every output is NULL"; return SIM3OPT_ERR_ARG; }
   if (!std::isfinite(lambda)) { b->err = "ba_debug_update: lambda is not finite"; return SIM3OPT_ERR_ARG; }
   return b->read_update(dx_c, dx_p, lambda, with_fail != 0, cam_qt, points, chi2, scale);
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_debug_update: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_optimize(sim3opt_ba* b, int32_t max_iters) {

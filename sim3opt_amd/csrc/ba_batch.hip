@@ -31,13 +31,12 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/sim3opt.h"
 #include "ba_math.hpp"
-#include "devmem.hpp"
+#include "handle_device.hpp"
 #include "lm_damping.hpp"
 
 namespace sim3opt_bundle {
@@ -336,9 +335,8 @@ __global__ __launch_bounds__(WGB) void k_ba_two_view(TwoViewArgs A) {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct Batch {
+struct Batch : sim3opt::BatchHandle {
   sim3opt_ba_batch_options opt;
-  std::string err;
   // the problems, as set; cam1 and pts hold the current estimate
   std::vector<int32_t> ptr;
   std::vector<double> cam0_given, cam0, cam1, pts, uv0, uv1;
@@ -346,28 +344,22 @@ struct Batch {
   // the last run
   std::vector<double> stats, summary, edge_chi2;
   int32_t stats_stride = 0;  // max_iters of the last run
-  bool have_run = false;
   // device
-  hipStream_t stream = nullptr;
-  sim3opt::DevArena mem;  // the four blocks below
-  int32_t* d_ptr = nullptr;
-  double *d_in = nullptr, *d_scr = nullptr, *d_out = nullptr;
-  int64_t cap_n = 0, cap_total = 0, cap_iters = 0;
-  bool static_uploaded = false;
+  sim3opt::DevArena mem;  // the four blocks of dev
+  struct Dev {
+    int32_t* ptr;
+    double *in, *scr, *out;
+    int64_t cap_n, cap_total, cap_iters;  // what the blocks were sized for
+    bool static_uploaded;
+  } dev{};
 
   ~Batch() { release(); }
   int32_t n() const { return ptr.empty() ? 0 : (int32_t)ptr.size() - 1; }
   int64_t total() const { return ptr.empty() ? 0 : ptr.back(); }
 
   void release() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    mem.release();
-    d_ptr = nullptr;
-    d_in = d_scr = d_out = nullptr;
-    if (stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
-    cap_n = cap_total = cap_iters = 0;
-    static_uploaded = false;
+    close_stream(mem);
+    dev = Dev{};
   }
 
   size_t in_doubles() const { return 14 * (size_t)n() + 7 * (size_t)total(); }
@@ -378,34 +370,26 @@ struct Batch {
   int optimize() {
     err.clear();
     if (n() < 1) { err = "ba_batch_optimize: no problems set"; return SIM3OPT_ERR_STATE; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-      err = "no usable HIP device (libsim3opt has no CPU fallback)";
-      return SIM3OPT_ERR_NO_DEVICE;
-    }
-    if (opt.device >= 0) {
-      if (opt.device >= ndev) { err = "device ordinal out of range"; return SIM3OPT_ERR_ARG; }
-      HIPCHK(hipSetDevice(opt.device));
-    }
+    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
     const int32_t N = n();
     const size_t T = (size_t)total();
-    if (N != cap_n || (int64_t)T != cap_total || opt.max_iters != cap_iters) {
+    if (N != dev.cap_n || (int64_t)T != dev.cap_total || opt.max_iters != dev.cap_iters) {
       release();
-      HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      HIPCHK(mem.raw(d_ptr, (size_t)N + 1));
-      HIPCHK(mem.raw(d_in, in_doubles()));
-      HIPCHK(mem.raw(d_scr, SCR_PER_POINT * T));
-      HIPCHK(mem.raw(d_out, out_doubles()));
-      cap_n = N; cap_total = (int64_t)T; cap_iters = opt.max_iters;
+      if (int rc = open_stream()) return rc;
+      HIPCHK(mem.raw(dev.ptr, (size_t)N + 1));
+      HIPCHK(mem.raw(dev.in, in_doubles()));
+      HIPCHK(mem.raw(dev.scr, SCR_PER_POINT * T));
+      HIPCHK(mem.raw(dev.out, out_doubles()));
+      dev.cap_n = N; dev.cap_total = (int64_t)T; dev.cap_iters = opt.max_iters;
     }
-    // device layout of d_in: cam0 | cam1 | points | uv0 | uv1; of d_out: points | cam1 | stats | summary | edge chi2
-    double* d_cam0 = d_in;
+    // device layout of dev.in: cam0 | cam1 | points | uv0 | uv1; of dev.out: points | cam1 | stats | summary | edge chi2
+    double* d_cam0 = dev.in;
     double* d_cam1 = d_cam0 + 7 * (size_t)N;
     double* d_pin = d_cam1 + 7 * (size_t)N;
     double* d_uv0 = d_pin + 3 * T;
     double* d_uv1 = d_uv0 + 2 * T;
-    if (!static_uploaded) {
-      HIPCHK(hipMemcpyAsync(d_ptr, ptr.data(), sizeof(int32_t) * ((size_t)N + 1), hipMemcpyHostToDevice, stream));
+    if (!dev.static_uploaded) {
+      HIPCHK(hipMemcpyAsync(dev.ptr, ptr.data(), sizeof(int32_t) * ((size_t)N + 1), hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(d_cam0, cam0.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(d_uv0, uv0.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(d_uv1, uv1.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
@@ -413,12 +397,12 @@ struct Batch {
     HIPCHK(hipMemcpyAsync(d_cam1, cam1.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_pin, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, stream));
     // (the copies read pageable memory: each has left the host buffer when its call returns)
-    static_uploaded = true;
+    dev.static_uploaded = true;
 
     TwoViewArgs A;
-    A.ptr = d_ptr; A.cam0 = d_cam0; A.cam1 = d_cam1; A.pts_in = d_pin; A.uv0 = d_uv0; A.uv1 = d_uv1;
-    A.scr = d_scr;
-    A.pts = d_out;
+    A.ptr = dev.ptr; A.cam0 = d_cam0; A.cam1 = d_cam1; A.pts_in = d_pin; A.uv0 = d_uv0; A.uv1 = d_uv1;
+    A.scr = dev.scr;
+    A.pts = dev.out;
     A.cam_out = A.pts + 3 * T;
     A.stats = A.cam_out + 7 * (size_t)N;
     A.summary = A.stats + (size_t)STAT_DOUBLES * opt.max_iters * N;
@@ -433,8 +417,8 @@ struct Batch {
     HIPCHK(hipMemsetAsync(A.stats, 0, sizeof(double) * STAT_DOUBLES * opt.max_iters * N, stream));
     hipLaunchKernelGGL(k_ba_two_view, dim3(N), dim3(WGB), 0, stream, A);  // the one launch of the batch
     HIPCHK(hipGetLastError());
-    std::vector<double> out(out_doubles());
-    HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, stream));
+    std::vector<double> out;
+    HIPCHK(sim3opt::read_back(out, dev.out, out_doubles(), stream));
     HIPCHK(hipStreamSynchronize(stream));
     const double* o = out.data();
     pts.assign(o, o + 3 * T); o += 3 * T;
@@ -470,19 +454,10 @@ void sim3opt_ba_batch_options_default(sim3opt_ba_batch_options* o) {
 }
 
 sim3opt_ba_batch* sim3opt_ba_batch_create(void) {
-  sim3opt_ba_batch* b = new (std::nothrow) sim3opt_ba_batch();
-  if (b) {
-    sim3opt_ba_batch_options_default(&b->opt);
-    sim3opt::handle_count(+1);
-  }
-  return b;
+  return sim3opt::handle_create<sim3opt_ba_batch>(sim3opt_ba_batch_options_default);
 }
 
-void sim3opt_ba_batch_destroy(sim3opt_ba_batch* b) {
-  if (!b) return;
-  delete b;
-  if (sim3opt::handle_count(-1) == 0) sim3opt::dev_cache_release();
-}
+void sim3opt_ba_batch_destroy(sim3opt_ba_batch* b) { sim3opt::handle_destroy(b); }
 
 const char* sim3opt_ba_batch_last_error(const sim3opt_ba_batch* b) { return b ? b->err.c_str() : "null batch"; }
 
@@ -508,26 +483,17 @@ int sim3opt_ba_batch_set_problems(sim3opt_ba_batch* b, int32_t n_problems, const
     b->err = "ba_batch_set_problems: bad argument";
     return SIM3OPT_ERR_ARG;
   }
-  try {
-  if (point_ptr[0] != 0) { b->err = "ba_batch_set_problems: point_ptr[0] must be 0"; return SIM3OPT_ERR_ARG; }
-  for (int32_t k = 0; k < n_problems; ++k)
-    if (point_ptr[k + 1] <= point_ptr[k]) {
-      b->err = "ba_batch_set_problems: problem " + std::to_string(k) +
-               (point_ptr[k + 1] == point_ptr[k] ? " has no point" : ": point_ptr is not monotone");
-      return SIM3OPT_ERR_ARG;
-    }
+  return sim3opt::guarded(b, "ba_batch_set_problems", sim3opt::NO_MEMORY, [&]() -> int {
+  using sim3opt::all_finite;
+  const std::string e = sim3opt::check_point_ptr(n_problems, point_ptr);
+  if (!e.empty()) { b->err = "ba_batch_set_problems: " + e; return SIM3OPT_ERR_ARG; }
   const size_t T = (size_t)point_ptr[n_problems];
-  auto finite = [](const double* v, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-      if (!std::isfinite(v[i])) return false;
-    return true;
-  };
-  if (!finite(cam0, 7 * (size_t)n_problems) || !finite(cam1, 7 * (size_t)n_problems)) {
+  if (!all_finite(cam0, 7 * (size_t)n_problems) || !all_finite(cam1, 7 * (size_t)n_problems)) {
     b->err = "ba_batch_set_problems: non-finite camera";
     return SIM3OPT_ERR_ARG;
   }
-  if (!finite(points, 3 * T)) { b->err = "ba_batch_set_problems: non-finite point"; return SIM3OPT_ERR_ARG; }
-  if (!finite(uv0, 2 * T) || !finite(uv1, 2 * T)) {
+  if (!all_finite(points, 3 * T)) { b->err = "ba_batch_set_problems: non-finite point"; return SIM3OPT_ERR_ARG; }
+  if (!all_finite(uv0, 2 * T) || !all_finite(uv1, 2 * T)) {
     b->err = "ba_batch_set_problems: non-finite observation";
     return SIM3OPT_ERR_ARG;
   }
@@ -550,11 +516,9 @@ int sim3opt_ba_batch_set_problems(sim3opt_ba_batch* b, int32_t n_problems, const
   b->f = focal; b->cx = cx; b->cy = cy;
   b->stats.clear(); b->summary.clear(); b->edge_chi2.clear();
   b->have_run = false;
-  b->static_uploaded = false;
+  b->dev.static_uploaded = false;
   return SIM3OPT_OK;
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_batch_set_problems: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_ba_batch_dims(const sim3opt_ba_batch* b, int32_t* n_problems, int32_t* total_points) {
@@ -566,11 +530,7 @@ int sim3opt_ba_batch_dims(const sim3opt_ba_batch* b, int32_t* n_problems, int32_
 
 int sim3opt_ba_batch_optimize(sim3opt_ba_batch* b) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
-    return b->optimize();
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "ba_batch_optimize: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "ba_batch_optimize", sim3opt::NO_MEMORY_OR_INTERNAL, [&] { return b->optimize(); });
 }
 
 int sim3opt_ba_batch_get_cameras(const sim3opt_ba_batch* b, double* cam0, double* cam1) {

@@ -19,6 +19,7 @@
 #include "direct.hpp"
 #include "engine.hpp"
 #include "graph.hpp"
+#include "handle_device.hpp"
 #include "rank_group.hpp"
 #include "robust.hpp"
 #include "sim3_jac.hpp"
@@ -279,20 +280,9 @@ static void apply_env_overrides(sim3opt_options& o) {
     if (std::atof(ev) > 0.0 && std::atof(ev) <= 1e-2) o.cov_rel_tol = std::atof(ev);
 }
 
-sim3opt_graph* sim3opt_create(void) {
-  sim3opt_graph* g = new (std::nothrow) sim3opt_graph();
-  if (g) {
-    sim3opt_options_default(&g->opt);
-    sim3opt::handle_count(+1);
-  }
-  return g;
-}
+sim3opt_graph* sim3opt_create(void) { return sim3opt::handle_create<sim3opt_graph>(sim3opt_options_default); }
 
-void sim3opt_destroy(sim3opt_graph* g) {
-  if (!g) return;
-  delete g;
-  if (sim3opt::handle_count(-1) == 0) sim3opt::dev_cache_release();  // the last handle of the process
-}
+void sim3opt_destroy(sim3opt_graph* g) { sim3opt::handle_destroy(g); }
 
 void sim3opt_release_device_cache(void) { sim3opt::dev_cache_release(); }
 

@@ -31,8 +31,8 @@ void dev_free(void* p);
 void dev_cache_release();  // gives every cached block back to the driver
 // {blocks, bytes (as rounded)} dev_malloc has handed out and not got back, process-wide (sim3opt_device_memory_in_use)
 void dev_in_use(int64_t out[2]);
-// live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch handles of the process (delta = +1 / -1; returns the new count):
-// the cache is released when the last one goes (sim3opt_release_device_cache does it on request)
+// live handles of the process, of every type handle_device.hpp's handle_create makes (delta = +1 / -1; returns the new
+// count): the cache is released when the last one goes (sim3opt_release_device_cache does it on request)
 int handle_count(int delta);
 
 // The same idea for what else an engine creates and destroys around every re-initialisation (round 3: 2.9 of

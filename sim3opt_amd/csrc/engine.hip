@@ -1,6 +1,7 @@
 // engine.hip -- initialisation, linearisation, chi2, the iteration frame and the LM trial loop (g2o: SparseOptimizer::
 // optimize -> OptimizationAlgorithmLevenberg::solve, kitti_surf.cpp:674-675); the C++ interface capi.cpp calls
 #include "engine_impl.hpp"
+#include "handle_device.hpp"
 #include "lm_damping.hpp"
 #include "robust.hpp"
 #include "sim3_jac.hpp"
@@ -58,18 +59,7 @@ void Engine::release_under_device() {
 }
 
 int Engine::init(const HostGraph& g, const Structure& s, std::string& err) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    err = "no usable HIP device (libsim3opt has no CPU fallback)";
-    return SIM3OPT_ERR_NO_DEVICE;
-  }
-  if (opt.device >= 0) {
-    if (opt.device >= ndev) {
-      err = "device ordinal out of range";
-      return SIM3OPT_ERR_ARG;
-    }
-    HIPCHK(hipSetDevice(opt.device));
-  }
+  if (int rc = select_device(opt.device, err)) return rc;
   HIPCHK(hipGetDevice(&device_used));
   if (const char* ev = std::getenv("SIM3OPT_SPMV")) {
     int a = 0, b = 0;

@@ -26,12 +26,11 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/sim3opt.h"
-#include "devmem.hpp"
+#include "handle_device.hpp"
 #include "match_host.hpp"
 
 namespace sim3opt_match {
@@ -323,9 +322,8 @@ __global__ __launch_bounds__(WG) void k_match_depth_probe(const float2* ouv, con
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct Batch {
+struct Batch : sim3opt::BatchHandle {
   sim3opt_match_batch_options opt;
-  std::string err;
   // the frames and pairs, as set
   std::vector<int32_t> kp_ptr, obs_ptr, pairs;
   std::vector<float> kp, desc, obs_uv, obs_depth;
@@ -336,20 +334,24 @@ struct Batch {
   std::vector<int32_t> match_ptr, counts, m_query, m_train;
   std::vector<float> m_dist;
   std::vector<double> m_uv0, m_uv1, m_depth0, m_depth1, m_pts;
-  bool have_run = false;
   // device
-  hipStream_t stream = nullptr;
-  sim3opt::DevArena frame_mem, pair_mem;  // the frames' blocks; the pairs' plan and the blocks of a solve
-  float *d_kp = nullptr, *d_desc = nullptr, *d_obs_uv = nullptr, *d_obs_depth = nullptr;
-  int32_t *d_kp_ptr = nullptr, *d_obs_ptr = nullptr, *d_pairs = nullptr, *d_qptr = nullptr, *d_tptr = nullptr;
-  Tile* d_tiles = nullptr;
-  int32_t *d_best_idx = nullptr, *d_second_idx = nullptr, *d_counts = nullptr, *d_match_ptr = nullptr;
-  float *d_best_d2 = nullptr, *d_second_d2 = nullptr, *d_m_dist = nullptr;
-  uint8_t* d_pass = nullptr;
-  unsigned long long* d_vote = nullptr;
-  int32_t *d_m_query = nullptr, *d_m_train = nullptr;
-  double* d_m_dbl = nullptr;  // uv0 (2), uv1 (2), depth0, depth1, points0 (3): nine blocks of Q doubles
-  bool frames_up = false, pairs_up = false;
+  sim3opt::DevArena frame_mem, pair_mem;  // the blocks of devf; of devp
+  struct DevFrames {  // the frames, as set
+    float *kp, *desc, *obs_uv, *obs_depth;
+    int32_t *kp_ptr, *obs_ptr;
+    bool up;
+  } devf{};
+  struct DevPairs {  // the pairs' plan and the blocks of a solve
+    int32_t *pairs, *qptr, *tptr;
+    Tile* tiles;
+    int32_t *best_idx, *second_idx, *counts, *match_ptr;
+    float *best_d2, *second_d2, *m_dist;
+    uint8_t* pass;
+    unsigned long long* vote;
+    int32_t *m_query, *m_train;
+    double* m_dbl;  // uv0 (2), uv1 (2), depth0, depth1, points0 (3): nine blocks of Q doubles
+    bool up;
+  } devp{};
 
   ~Batch() { release(); }
   int32_t n_frames() const { return kp_ptr.empty() ? 0 : (int32_t)kp_ptr.size() - 1; }
@@ -359,75 +361,55 @@ struct Batch {
 
   // the pairs' blocks alone: the frames stay on the device when only the candidate list changes
   void release_pairs() {
-    if (stream) (void)hipStreamSynchronize(stream);
+    wait();
     pair_mem.release();
-    d_pairs = d_qptr = d_tptr = nullptr;
-    d_tiles = nullptr;
-    d_best_idx = d_second_idx = d_counts = d_match_ptr = nullptr;
-    d_best_d2 = d_second_d2 = d_m_dist = nullptr;
-    d_pass = nullptr;
-    d_vote = nullptr;
-    d_m_query = d_m_train = nullptr;
-    d_m_dbl = nullptr;
-    pairs_up = false;
+    devp = DevPairs{};
   }
 
   void release() {
-    release_pairs();
-    frame_mem.release();
-    d_kp = d_desc = d_obs_uv = d_obs_depth = nullptr;
-    d_kp_ptr = d_obs_ptr = nullptr;
-    if (stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
-    frames_up = false;
+    close_stream(pair_mem, frame_mem);
+    devp = DevPairs{};
+    devf = DevFrames{};
   }
 
   // the device and the frames on it (need_pairs: and the pairs, their plan and the blocks of a solve)
   int ensure_device(const char* who, bool need_pairs) {
     if (n_frames() < 1) { err = std::string(who) + ": no frames set"; return SIM3OPT_ERR_STATE; }
     if (need_pairs && n_pairs() < 1) { err = std::string(who) + ": no pairs set"; return SIM3OPT_ERR_STATE; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-      err = "no usable HIP device (libsim3opt has no CPU fallback)";
-      return SIM3OPT_ERR_NO_DEVICE;
-    }
-    if (opt.device >= 0) {
-      if (opt.device >= ndev) { err = "device ordinal out of range"; return SIM3OPT_ERR_ARG; }
-      HIPCHK(hipSetDevice(opt.device));
-    }
-    if (!frames_up) {
+    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
+    if (!devf.up) {
       release();
-      HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      HIPCHK(frame_mem.upload(d_kp_ptr, kp_ptr, stream, nullptr));
-      HIPCHK(frame_mem.upload(d_obs_ptr, obs_ptr, stream, nullptr));
-      HIPCHK(frame_mem.upload(d_kp, kp, stream, nullptr));
-      HIPCHK(frame_mem.upload(d_desc, desc, stream, nullptr));
-      HIPCHK(frame_mem.upload(d_obs_uv, obs_uv, stream, nullptr));
-      HIPCHK(frame_mem.upload(d_obs_depth, obs_depth, stream, nullptr));
+      if (int rc = open_stream()) return rc;
+      HIPCHK(frame_mem.upload(devf.kp_ptr, kp_ptr, stream, nullptr));
+      HIPCHK(frame_mem.upload(devf.obs_ptr, obs_ptr, stream, nullptr));
+      HIPCHK(frame_mem.upload(devf.kp, kp, stream, nullptr));
+      HIPCHK(frame_mem.upload(devf.desc, desc, stream, nullptr));
+      HIPCHK(frame_mem.upload(devf.obs_uv, obs_uv, stream, nullptr));
+      HIPCHK(frame_mem.upload(devf.obs_depth, obs_depth, stream, nullptr));
       HIPCHK(hipStreamSynchronize(stream));
-      frames_up = true;
+      devf.up = true;
     }
-    if (need_pairs && !pairs_up) {
+    if (need_pairs && !devp.up) {
       release_pairs();
       const size_t N = (size_t)n_pairs(), q = Q();
-      HIPCHK(pair_mem.upload(d_pairs, pairs, stream, nullptr));
-      HIPCHK(pair_mem.upload(d_qptr, plan.qptr, stream, nullptr));
-      HIPCHK(pair_mem.upload(d_tptr, plan.tptr, stream, nullptr));
-      HIPCHK(pair_mem.upload(d_tiles, plan.tiles, stream, nullptr));
-      HIPCHK(pair_mem.raw(d_best_idx, q));
-      HIPCHK(pair_mem.raw(d_second_idx, q));
-      HIPCHK(pair_mem.raw(d_best_d2, q));
-      HIPCHK(pair_mem.raw(d_second_d2, q));
-      HIPCHK(pair_mem.raw(d_pass, q));
-      HIPCHK(pair_mem.raw(d_vote, T()));
-      HIPCHK(pair_mem.raw(d_counts, 4 * N));
-      HIPCHK(pair_mem.raw(d_match_ptr, N + 1));
-      HIPCHK(pair_mem.raw(d_m_query, q));
-      HIPCHK(pair_mem.raw(d_m_train, q));
-      HIPCHK(pair_mem.raw(d_m_dist, q));
-      HIPCHK(pair_mem.raw(d_m_dbl, 9 * q));
+      HIPCHK(pair_mem.upload(devp.pairs, pairs, stream, nullptr));
+      HIPCHK(pair_mem.upload(devp.qptr, plan.qptr, stream, nullptr));
+      HIPCHK(pair_mem.upload(devp.tptr, plan.tptr, stream, nullptr));
+      HIPCHK(pair_mem.upload(devp.tiles, plan.tiles, stream, nullptr));
+      HIPCHK(pair_mem.raw(devp.best_idx, q));
+      HIPCHK(pair_mem.raw(devp.second_idx, q));
+      HIPCHK(pair_mem.raw(devp.best_d2, q));
+      HIPCHK(pair_mem.raw(devp.second_d2, q));
+      HIPCHK(pair_mem.raw(devp.pass, q));
+      HIPCHK(pair_mem.raw(devp.vote, T()));
+      HIPCHK(pair_mem.raw(devp.counts, 4 * N));
+      HIPCHK(pair_mem.raw(devp.match_ptr, N + 1));
+      HIPCHK(pair_mem.raw(devp.m_query, q));
+      HIPCHK(pair_mem.raw(devp.m_train, q));
+      HIPCHK(pair_mem.raw(devp.m_dist, q));
+      HIPCHK(pair_mem.raw(devp.m_dbl, 9 * q));
       HIPCHK(hipStreamSynchronize(stream));
-      pairs_up = true;
+      devp.up = true;
     }
     return SIM3OPT_OK;
   }
@@ -435,16 +417,16 @@ struct Batch {
   MatchArgs args() const {
     MatchArgs A{};
     const size_t q = Q();
-    A.kp = reinterpret_cast<const float2*>(d_kp); A.desc = d_desc;
-    A.obs_uv = reinterpret_cast<const float2*>(d_obs_uv); A.obs_depth = d_obs_depth;
-    A.kp_ptr = d_kp_ptr; A.obs_ptr = d_obs_ptr;
-    A.pairs = d_pairs; A.qptr = d_qptr; A.tptr = d_tptr; A.tiles = d_tiles;
-    A.best_idx = d_best_idx; A.second_idx = d_second_idx; A.best_d2 = d_best_d2; A.second_d2 = d_second_d2;
-    A.pass = d_pass; A.vote = d_vote; A.counts = d_counts; A.match_ptr = d_match_ptr;
-    A.m_query = d_m_query; A.m_train = d_m_train; A.m_dist = d_m_dist;
-    if (d_m_dbl) {
-      A.m_uv0 = d_m_dbl; A.m_uv1 = d_m_dbl + 2 * q; A.m_depth0 = d_m_dbl + 4 * q; A.m_depth1 = d_m_dbl + 5 * q;
-      A.m_pts = d_m_dbl + 6 * q;
+    A.kp = reinterpret_cast<const float2*>(devf.kp); A.desc = devf.desc;
+    A.obs_uv = reinterpret_cast<const float2*>(devf.obs_uv); A.obs_depth = devf.obs_depth;
+    A.kp_ptr = devf.kp_ptr; A.obs_ptr = devf.obs_ptr;
+    A.pairs = devp.pairs; A.qptr = devp.qptr; A.tptr = devp.tptr; A.tiles = devp.tiles;
+    A.best_idx = devp.best_idx; A.second_idx = devp.second_idx; A.best_d2 = devp.best_d2; A.second_d2 = devp.second_d2;
+    A.pass = devp.pass; A.vote = devp.vote; A.counts = devp.counts; A.match_ptr = devp.match_ptr;
+    A.m_query = devp.m_query; A.m_train = devp.m_train; A.m_dist = devp.m_dist;
+    if (devp.m_dbl) {
+      A.m_uv0 = devp.m_dbl; A.m_uv1 = devp.m_dbl + 2 * q; A.m_depth0 = devp.m_dbl + 4 * q; A.m_depth1 = devp.m_dbl + 5 * q;
+      A.m_pts = devp.m_dbl + 6 * q;
     }
     A.ratio = opt.ratio; A.use_ratio = opt.ratio > 0;
     A.x_lo = opt.border_ratio * width; A.x_hi = (1 - opt.border_ratio) * width;
@@ -461,37 +443,32 @@ struct Batch {
     if (rc != SIM3OPT_OK) return rc;
     const size_t N = (size_t)n_pairs(), n_tiles = plan.tiles.size();
     const MatchArgs A = args();
-    HIPCHK(hipMemsetAsync(d_vote, 0xFF, sizeof(unsigned long long) * std::max<size_t>(T(), 1), stream));
-    HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * 4 * N, stream));
+    HIPCHK(hipMemsetAsync(devp.vote, 0xFF, sizeof(unsigned long long) * std::max<size_t>(T(), 1), stream));
+    HIPCHK(hipMemsetAsync(devp.counts, 0, sizeof(int32_t) * 4 * N, stream));
     if (n_tiles) hipLaunchKernelGGL(k_match_nn, dim3((unsigned)n_tiles), dim3(WG), 0, stream, A);
     hipLaunchKernelGGL(k_match_count, dim3((unsigned)N), dim3(WG), 0, stream, A);
     hipLaunchKernelGGL(k_match_scan, dim3(1), dim3(WG), 0, stream, A);
     hipLaunchKernelGGL(k_match_compact, dim3((unsigned)N), dim3(WG), 0, stream, A);
     if (n_tiles) hipLaunchKernelGGL(k_match_depth, dim3((unsigned)n_tiles, 2), dim3(WG), 0, stream, A);
     HIPCHK(hipGetLastError());
-    std::vector<int32_t> mp(N + 1), cn(4 * N);
-    HIPCHK(hipMemcpyAsync(mp.data(), d_match_ptr, sizeof(int32_t) * (N + 1), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(cn.data(), d_counts, sizeof(int32_t) * 4 * N, hipMemcpyDeviceToHost, stream));
+    std::vector<int32_t> mp, cn;
+    HIPCHK(sim3opt::read_back(mp, devp.match_ptr, N + 1, stream));
+    HIPCHK(sim3opt::read_back(cn, devp.counts, 4 * N, stream));
     HIPCHK(hipStreamSynchronize(stream));
     const size_t M = (size_t)mp[N];
     if (M > Q()) { err = "match_batch_solve: internal error (more matches than queries)"; return SIM3OPT_ERR_HIP; }
-    std::vector<int32_t> mq(M), mt(M);
-    std::vector<float> md(M);
-    std::vector<double> u0(2 * M), u1(2 * M), z0(M), z1(M), pt(3 * M);
-    if (M) {
-      const auto get = [&](void* dst, const void* src, size_t bytes) {
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
-      };
-      HIPCHK(get(mq.data(), A.m_query, sizeof(int32_t) * M));
-      HIPCHK(get(mt.data(), A.m_train, sizeof(int32_t) * M));
-      HIPCHK(get(md.data(), A.m_dist, sizeof(float) * M));
-      HIPCHK(get(u0.data(), A.m_uv0, sizeof(double) * 2 * M));
-      HIPCHK(get(u1.data(), A.m_uv1, sizeof(double) * 2 * M));
-      HIPCHK(get(z0.data(), A.m_depth0, sizeof(double) * M));
-      HIPCHK(get(z1.data(), A.m_depth1, sizeof(double) * M));
-      HIPCHK(get(pt.data(), A.m_pts, sizeof(double) * 3 * M));
-      HIPCHK(hipStreamSynchronize(stream));
-    }
+    std::vector<int32_t> mq, mt;
+    std::vector<float> md;
+    std::vector<double> u0, u1, z0, z1, pt;
+    HIPCHK(sim3opt::read_back(mq, A.m_query, M, stream));
+    HIPCHK(sim3opt::read_back(mt, A.m_train, M, stream));
+    HIPCHK(sim3opt::read_back(md, A.m_dist, M, stream));
+    HIPCHK(sim3opt::read_back(u0, A.m_uv0, 2 * M, stream));
+    HIPCHK(sim3opt::read_back(u1, A.m_uv1, 2 * M, stream));
+    HIPCHK(sim3opt::read_back(z0, A.m_depth0, M, stream));
+    HIPCHK(sim3opt::read_back(z1, A.m_depth1, M, stream));
+    HIPCHK(sim3opt::read_back(pt, A.m_pts, 3 * M, stream));
+    if (M) HIPCHK(hipStreamSynchronize(stream));  // (no match: nothing was enqueued)
     match_ptr.swap(mp); counts.swap(cn); m_query.swap(mq); m_train.swap(mt); m_dist.swap(md);
     m_uv0.swap(u0); m_uv1.swap(u1); m_depth0.swap(z0); m_depth1.swap(z1); m_pts.swap(pt);
     have_run = true;
@@ -503,7 +480,7 @@ struct Batch {
   int debug_nn(int32_t pair, int32_t* best_idx, float* best_d2, int32_t* second_idx, float* second_d2) {
     err.clear();
     if (!have_run) { err = "match_batch_debug_nn: no solve yet"; return SIM3OPT_ERR_STATE; }
-    if (!pairs_up) {  // (options.device changed: the getters still hold the last results, the device holds nothing)
+    if (!devp.up) {  // (options.device changed: the getters still hold the last results, the device holds nothing)
       err = "match_batch_debug_nn: the device blocks of the last solve were released; solve again";
       return SIM3OPT_ERR_STATE;
     }
@@ -513,12 +490,12 @@ struct Batch {
       return SIM3OPT_ERR_STATE;
     }
     const size_t lo = (size_t)plan.qptr[pair], n = (size_t)plan.qptr[pair + 1] - lo;
-    std::vector<int32_t> bi(n), si(n);
-    std::vector<float> bd(n), sd(n);
-    HIPCHK(hipMemcpyAsync(bi.data(), d_best_idx + lo, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(si.data(), d_second_idx + lo, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(bd.data(), d_best_d2 + lo, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(sd.data(), d_second_d2 + lo, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
+    std::vector<int32_t> bi, si;
+    std::vector<float> bd, sd;
+    HIPCHK(sim3opt::read_back(bi, devp.best_idx + lo, n, stream));
+    HIPCHK(sim3opt::read_back(si, devp.second_idx + lo, n, stream));
+    HIPCHK(sim3opt::read_back(bd, devp.best_d2 + lo, n, stream));
+    HIPCHK(sim3opt::read_back(sd, devp.second_d2 + lo, n, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (best_idx) std::memcpy(best_idx, bi.data(), sizeof(int32_t) * n);
     if (second_idx) std::memcpy(second_idx, si.data(), sizeof(int32_t) * n);
@@ -544,13 +521,13 @@ struct Batch {
     HIPCHK(dnb.alloc(K * n));
     HIPCHK(hipMemcpyAsync(duv.get(), uv, sizeof(float) * 2 * n, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_match_depth_probe, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, stream,
-                       reinterpret_cast<const float2*>(d_obs_uv) + o_lo, d_obs_depth + o_lo, n_obs, opt.knn_k,
+                       reinterpret_cast<const float2*>(devf.obs_uv) + o_lo, devf.obs_depth + o_lo, n_obs, opt.knn_k,
                        reinterpret_cast<const float2*>(duv.get()), n, dz.get(), dnb.get());
     HIPCHK(hipGetLastError());
-    std::vector<double> hz((size_t)n);
-    std::vector<int32_t> hn(K * n);
-    HIPCHK(hipMemcpyAsync(hz.data(), dz.get(), sizeof(double) * n, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hn.data(), dnb.get(), sizeof(int32_t) * K * n, hipMemcpyDeviceToHost, stream));
+    std::vector<double> hz;
+    std::vector<int32_t> hn;
+    HIPCHK(sim3opt::read_back(hz, dz.get(), (size_t)n, stream));
+    HIPCHK(sim3opt::read_back(hn, dnb.get(), K * n, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (depth) std::memcpy(depth, hz.data(), sizeof(double) * n);
     if (neighbours) std::memcpy(neighbours, hn.data(), sizeof(int32_t) * K * n);
@@ -578,19 +555,10 @@ void sim3opt_match_batch_options_default(sim3opt_match_batch_options* o) {
 }
 
 sim3opt_match_batch* sim3opt_match_batch_create(void) {
-  sim3opt_match_batch* b = new (std::nothrow) sim3opt_match_batch();
-  if (b) {
-    sim3opt_match_batch_options_default(&b->opt);
-    sim3opt::handle_count(+1);
-  }
-  return b;
+  return sim3opt::handle_create<sim3opt_match_batch>(sim3opt_match_batch_options_default);
 }
 
-void sim3opt_match_batch_destroy(sim3opt_match_batch* b) {
-  if (!b) return;
-  delete b;
-  if (sim3opt::handle_count(-1) == 0) sim3opt::dev_cache_release();
-}
+void sim3opt_match_batch_destroy(sim3opt_match_batch* b) { sim3opt::handle_destroy(b); }
 
 const char* sim3opt_match_batch_last_error(const sim3opt_match_batch* b) { return b ? b->err.c_str() : "null batch"; }
 
@@ -608,7 +576,7 @@ int sim3opt_match_batch_set_frames(sim3opt_match_batch* b, int32_t n_frames, con
                                    const float* obs_depth, double focal, double cx, double cy, int32_t image_width,
                                    int32_t image_height) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
+  return sim3opt::guarded(b, "match_batch_set_frames", sim3opt::NO_MEMORY, [&]() -> int {
     const std::string e = sim3opt_match::validate_frames(n_frames, kp_ptr, obs_ptr, kp, desc, obs_uv, obs_depth, focal,
                                                          cx, cy, image_width, image_height);
     if (!e.empty()) { b->err = "match_batch_set_frames: " + e; return SIM3OPT_ERR_ARG; }
@@ -622,17 +590,15 @@ int sim3opt_match_batch_set_frames(sim3opt_match_batch* b, int32_t n_frames, con
     b->pairs.clear();
     b->plan = sim3opt_match::Plan();
     b->have_run = false;
-    b->frames_up = b->pairs_up = false;
+    b->devf.up = b->devp.up = false;
     return SIM3OPT_OK;
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "match_batch_set_frames: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_match_batch_set_pairs(sim3opt_match_batch* b, int32_t n_pairs, const int32_t* pairs) {
   if (!b) return SIM3OPT_ERR_ARG;
   if (b->n_frames() < 1) { b->err = "match_batch_set_pairs: no frames set"; return SIM3OPT_ERR_STATE; }
-  try {
+  return sim3opt::guarded(b, "match_batch_set_pairs", sim3opt::NO_MEMORY, [&]() -> int {
     std::string e = sim3opt_match::validate_pairs(b->n_frames(), n_pairs, pairs);
     sim3opt_match::Plan plan;
     if (e.empty()) e = sim3opt_match::build_plan(b->kp_ptr.data(), b->obs_ptr.data(), n_pairs, pairs, plan);
@@ -641,11 +607,9 @@ int sim3opt_match_batch_set_pairs(sim3opt_match_batch* b, int32_t n_pairs, const
     b->pairs.swap(p);
     b->plan = std::move(plan);
     b->have_run = false;
-    b->pairs_up = false;  // (the frames stay where they are)
+    b->devp.up = false;  // (the frames stay where they are)
     return SIM3OPT_OK;
-  } catch (...) {
-    b->err = "match_batch_set_pairs: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_match_batch_dims(const sim3opt_match_batch* b, int32_t* n_frames, int32_t* n_pairs,
@@ -664,11 +628,7 @@ int sim3opt_match_batch_dims(const sim3opt_match_batch* b, int32_t* n_frames, in
 
 int sim3opt_match_batch_solve(sim3opt_match_batch* b) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
-    return b->solve();
-  } catch (...) {
-    b->err = "match_batch_solve: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "match_batch_solve", sim3opt::NO_MEMORY_OR_INTERNAL, [&] { return b->solve(); });
 }
 
 int sim3opt_match_batch_get_match_ptr(const sim3opt_match_batch* b, int32_t* match_ptr) {
@@ -714,24 +674,18 @@ int sim3opt_match_batch_get_summary(const sim3opt_match_batch* b, int32_t* statu
 int sim3opt_match_batch_debug_nn(sim3opt_match_batch* b, int32_t pair, int32_t* best_idx, float* best_d2,
                                  int32_t* second_idx, float* second_d2) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
-    return b->debug_nn(pair, best_idx, best_d2, second_idx, second_d2);
-  } catch (...) {
-    b->err = "match_batch_debug_nn: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "match_batch_debug_nn", sim3opt::NO_MEMORY,
+                          [&] { return b->debug_nn(pair, best_idx, best_d2, second_idx, second_d2); });
 }
 
 int sim3opt_match_batch_debug_depth(sim3opt_match_batch* b, int32_t n, int32_t frame, const float* uv, double* depth,
                                     int32_t* neighbours) {
   if (!b) return SIM3OPT_ERR_ARG;
-  if (n < 1 || !uv || (!depth && !neighbours) || !sim3opt_match::all_finite(uv, 2 * (size_t)n)) {
+  if (n < 1 || !uv || (!depth && !neighbours) || !sim3opt::all_finite(uv, 2 * (size_t)n)) {
     b->err = "match_batch_debug_depth: bad argument"; return SIM3OPT_ERR_ARG;
   }
-  try {
-    return b->debug_depth(n, frame, uv, depth, neighbours);
-  } catch (...) {
-    b->err = "match_batch_debug_depth: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "match_batch_debug_depth", sim3opt::NO_MEMORY,
+                          [&] { return b->debug_depth(n, frame, uv, depth, neighbours); });
 }
 
 }  // extern "C"

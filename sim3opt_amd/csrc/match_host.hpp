@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "handle_host.hpp"
 
 namespace sim3opt_match {
 
@@ -31,19 +32,8 @@ struct Plan {
   std::vector<Tile> tiles;
 };
 
-inline bool all_finite(const float* v, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
-// "" when ptr (n + 1 entries) starts at 0 and never decreases
-inline std::string check_ptr(const char* name, int32_t n, const int32_t* ptr) {
-  if (ptr[0] != 0) return std::string(name) + "[0] must be 0";
-  for (int32_t k = 0; k < n; ++k)
-    if (ptr[k + 1] < ptr[k]) return std::string(name) + " is not monotone at frame " + std::to_string(k);
-  return "";
-}
+using sim3opt::all_finite;
+using sim3opt::check_frame_ptr;
 
 inline std::string validate_options(const sim3opt_match_batch_options& o) {
   const double v[4] = {o.ratio, o.border_ratio, o.skew_x, o.skew_y};
@@ -61,8 +51,8 @@ inline std::string validate_frames(int32_t n_frames, const int32_t* kp_ptr, cons
   if (!(focal > 0) || !std::isfinite(focal) || !std::isfinite(cx) || !std::isfinite(cy))
     return "focal <= 0 or a non-finite intrinsic";
   if (image_width < 1 || image_height < 1) return "a non-positive image size";
-  std::string e = check_ptr("kp_ptr", n_frames, kp_ptr);
-  if (e.empty()) e = check_ptr("obs_ptr", n_frames, obs_ptr);
+  std::string e = check_frame_ptr("kp_ptr", n_frames, kp_ptr);
+  if (e.empty()) e = check_frame_ptr("obs_ptr", n_frames, obs_ptr);
   if (!e.empty()) return e;
   const size_t nk = (size_t)kp_ptr[n_frames], no = (size_t)obs_ptr[n_frames];
   if (nk > (size_t)INT32_MAX / DESC) return "too many keypoints";

@@ -31,13 +31,12 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/sim3opt.h"
 #include "ba_math.hpp"
-#include "devmem.hpp"
+#include "handle_device.hpp"
 #include "lm_damping.hpp"
 #include "pnp_math.hpp"
 
@@ -460,9 +459,8 @@ __global__ __launch_bounds__(WG) void k_pnp_refine(PnpArgs A, const double* pose
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct Batch {
+struct Batch : sim3opt::BatchHandle {
   sim3opt_pnp_batch_options opt;
-  std::string err;
   // the problems, as set
   std::vector<int32_t> ptr;
   std::vector<double> pts, uv;
@@ -472,74 +470,58 @@ struct Batch {
   std::vector<int32_t> out_i;
   std::vector<uint8_t> mask;
   int32_t solved_H = 0;
-  bool have_run = false;
   // device
-  hipStream_t stream = nullptr;
-  sim3opt::DevArena mem;  // the blocks below
-  int32_t* d_ptr = nullptr;
-  double *d_in = nullptr, *d_hyp_pose = nullptr, *d_hyp_cost = nullptr, *d_out_d = nullptr;
-  int32_t *d_hyp_int = nullptr, *d_out_i = nullptr;
-  uint8_t* d_mask = nullptr;
-  int64_t cap_n = 0, cap_total = 0, cap_H = 0;
-  bool uploaded = false;
+  sim3opt::DevArena mem;  // the eight blocks of dev
+  struct Dev {
+    int32_t* ptr;
+    double *in, *hyp_pose, *hyp_cost, *out_d;
+    int32_t *hyp_int, *out_i;
+    uint8_t* mask;
+    int64_t cap_n, cap_total, cap_H;  // what the blocks were sized for
+    bool uploaded;
+  } dev{};
 
   ~Batch() { release(); }
   int32_t n() const { return ptr.empty() ? 0 : (int32_t)ptr.size() - 1; }
   int64_t total() const { return ptr.empty() ? 0 : ptr.back(); }
 
   void release() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    mem.release();
-    d_ptr = nullptr;
-    d_in = d_hyp_pose = d_hyp_cost = d_out_d = nullptr;
-    d_hyp_int = d_out_i = nullptr;
-    d_mask = nullptr;
-    if (stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
-    cap_n = cap_total = cap_H = 0;
-    uploaded = false;
+    close_stream(mem);
+    dev = Dev{};
   }
 
   // the device, the handle's blocks (sized by the problems and options.iterations) and the problems on the device
   int ensure_device(const char* who) {
     if (n() < 1) { err = std::string(who) + ": no problems set"; return SIM3OPT_ERR_STATE; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-      err = "no usable HIP device (libsim3opt has no CPU fallback)";
-      return SIM3OPT_ERR_NO_DEVICE;
-    }
-    if (opt.device >= 0) {
-      if (opt.device >= ndev) { err = "device ordinal out of range"; return SIM3OPT_ERR_ARG; }
-      HIPCHK(hipSetDevice(opt.device));
-    }
+    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
     const size_t N = (size_t)n(), T = (size_t)total(), H = (size_t)opt.iterations;
-    if ((int64_t)N != cap_n || (int64_t)T != cap_total || (int64_t)H != cap_H) {
+    if ((int64_t)N != dev.cap_n || (int64_t)T != dev.cap_total || (int64_t)H != dev.cap_H) {
       release();
-      HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      HIPCHK(mem.raw(d_ptr, N + 1));
-      HIPCHK(mem.raw(d_in, 5 * T));
-      HIPCHK(mem.raw(d_hyp_pose, 7 * N * H));
-      HIPCHK(mem.raw(d_hyp_cost, N * H));
-      HIPCHK(mem.raw(d_hyp_int, HYP_INTS * N * H));
-      HIPCHK(mem.raw(d_out_d, OUT_DOUBLES * N));
-      HIPCHK(mem.raw(d_out_i, OUT_INTS * N));
-      HIPCHK(mem.raw(d_mask, T));
-      cap_n = (int64_t)N; cap_total = (int64_t)T; cap_H = (int64_t)H;
+      if (int rc = open_stream()) return rc;
+      HIPCHK(mem.raw(dev.ptr, N + 1));
+      HIPCHK(mem.raw(dev.in, 5 * T));
+      HIPCHK(mem.raw(dev.hyp_pose, 7 * N * H));
+      HIPCHK(mem.raw(dev.hyp_cost, N * H));
+      HIPCHK(mem.raw(dev.hyp_int, HYP_INTS * N * H));
+      HIPCHK(mem.raw(dev.out_d, OUT_DOUBLES * N));
+      HIPCHK(mem.raw(dev.out_i, OUT_INTS * N));
+      HIPCHK(mem.raw(dev.mask, T));
+      dev.cap_n = (int64_t)N; dev.cap_total = (int64_t)T; dev.cap_H = (int64_t)H;
     }
-    if (!uploaded) {
-      HIPCHK(hipMemcpyAsync(d_ptr, ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(d_in, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(d_in + 3 * T, uv.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
-      uploaded = true;
+    if (!dev.uploaded) {
+      HIPCHK(hipMemcpyAsync(dev.ptr, ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(dev.in, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(dev.in + 3 * T, uv.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
+      dev.uploaded = true;
     }
     return SIM3OPT_OK;
   }
 
   PnpArgs args() const {
     PnpArgs A{};
-    A.ptr = d_ptr; A.pts = d_in; A.uv = d_in + 3 * (size_t)total();
-    A.hyp_pose = d_hyp_pose; A.hyp_cost = d_hyp_cost; A.hyp_int = d_hyp_int;
-    A.out_d = d_out_d; A.out_i = d_out_i; A.mask = d_mask;
+    A.ptr = dev.ptr; A.pts = dev.in; A.uv = dev.in + 3 * (size_t)total();
+    A.hyp_pose = dev.hyp_pose; A.hyp_cost = dev.hyp_cost; A.hyp_int = dev.hyp_int;
+    A.out_d = dev.out_d; A.out_i = dev.out_i; A.mask = dev.mask;
     A.f = f; A.cx = cx; A.cy = cy;
     A.thr2 = opt.reproj_error * opt.reproj_error;
     A.tau = opt.tau; A.seed = opt.seed;
@@ -554,17 +536,17 @@ struct Batch {
     if (rc != SIM3OPT_OK) return rc;
     const size_t N = (size_t)n(), T = (size_t)total(), H = (size_t)opt.iterations;
     // hypotheses of a problem that runs none (status 1) read as zeros
-    HIPCHK(hipMemsetAsync(d_hyp_pose, 0, sizeof(double) * 7 * N * H, stream));
-    HIPCHK(hipMemsetAsync(d_hyp_cost, 0, sizeof(double) * N * H, stream));
-    HIPCHK(hipMemsetAsync(d_hyp_int, 0, sizeof(int32_t) * HYP_INTS * N * H, stream));
+    HIPCHK(hipMemsetAsync(dev.hyp_pose, 0, sizeof(double) * 7 * N * H, stream));
+    HIPCHK(hipMemsetAsync(dev.hyp_cost, 0, sizeof(double) * N * H, stream));
+    HIPCHK(hipMemsetAsync(dev.hyp_int, 0, sizeof(int32_t) * HYP_INTS * N * H, stream));
     hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)N), dim3(WG), 0, stream, args());  // the one launch of the batch
     HIPCHK(hipGetLastError());
-    std::vector<double> od(OUT_DOUBLES * N);
-    std::vector<int32_t> oi(OUT_INTS * N);
-    std::vector<uint8_t> m(T);
-    HIPCHK(hipMemcpyAsync(od.data(), d_out_d, sizeof(double) * od.size(), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(oi.data(), d_out_i, sizeof(int32_t) * oi.size(), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(m.data(), d_mask, m.size(), hipMemcpyDeviceToHost, stream));
+    std::vector<double> od;
+    std::vector<int32_t> oi;
+    std::vector<uint8_t> m;
+    HIPCHK(sim3opt::read_back(od, dev.out_d, OUT_DOUBLES * N, stream));
+    HIPCHK(sim3opt::read_back(oi, dev.out_i, OUT_INTS * N, stream));
+    HIPCHK(sim3opt::read_back(m, dev.mask, T, stream));
     HIPCHK(hipStreamSynchronize(stream));
     out_d.swap(od); out_i.swap(oi); mask.swap(m);
     solved_H = opt.iterations;
@@ -579,18 +561,16 @@ struct Batch {
     err.clear();
     if (!have_run) { err = "pnp_batch_debug_hypotheses: no solve yet"; return SIM3OPT_ERR_STATE; }
     if (problem < 0 || problem >= n()) { err = "pnp_batch_debug_hypotheses: no such problem"; return SIM3OPT_ERR_ARG; }
-    if (solved_H != opt.iterations || cap_H != solved_H) {
+    if (solved_H != opt.iterations || dev.cap_H != solved_H) {
       err = "pnp_batch_debug_hypotheses: options.iterations changed since the solve";
       return SIM3OPT_ERR_STATE;
     }
     const size_t H = (size_t)solved_H;
-    std::vector<int32_t> hi(HYP_INTS * H);
-    std::vector<double> hp(7 * H), hc(H);
-    HIPCHK(hipMemcpyAsync(hi.data(), d_hyp_int + HYP_INTS * H * problem, sizeof(int32_t) * hi.size(),
-                          hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hp.data(), d_hyp_pose + 7 * H * problem, sizeof(double) * hp.size(), hipMemcpyDeviceToHost,
-                          stream));
-    HIPCHK(hipMemcpyAsync(hc.data(), d_hyp_cost + H * problem, sizeof(double) * H, hipMemcpyDeviceToHost, stream));
+    std::vector<int32_t> hi;
+    std::vector<double> hp, hc;
+    HIPCHK(sim3opt::read_back(hi, dev.hyp_int + HYP_INTS * H * problem, HYP_INTS * H, stream));
+    HIPCHK(sim3opt::read_back(hp, dev.hyp_pose + 7 * H * problem, 7 * H, stream));
+    HIPCHK(sim3opt::read_back(hc, dev.hyp_cost + H * problem, H, stream));
     HIPCHK(hipStreamSynchronize(stream));
     for (size_t h = 0; h < H; ++h) {
       if (sample)
@@ -619,10 +599,10 @@ struct Batch {
     A.H = P;
     hipLaunchKernelGGL(k_pnp_score, dim3((unsigned)N), dim3(WG), 0, stream, A, dp.get(), dn.get(), dc.get());
     HIPCHK(hipGetLastError());
-    std::vector<int32_t> hn(M);
-    std::vector<double> hc(M);
-    HIPCHK(hipMemcpyAsync(hn.data(), dn.get(), sizeof(int32_t) * M, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hc.data(), dc.get(), sizeof(double) * M, hipMemcpyDeviceToHost, stream));
+    std::vector<int32_t> hn;
+    std::vector<double> hc;
+    HIPCHK(sim3opt::read_back(hn, dn.get(), M, stream));
+    HIPCHK(sim3opt::read_back(hc, dc.get(), M, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (count) std::memcpy(count, hn.data(), sizeof(int32_t) * M);
     if (cost) std::memcpy(cost, hc.data(), sizeof(double) * M);
@@ -650,12 +630,12 @@ struct Batch {
     hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)N), dim3(WG), 0, stream, args(), dp.get(), dm.get(), dq.get(),
                        dit.get(), dchi.get(), dtr.get());
     HIPCHK(hipGetLastError());
-    std::vector<double> hq(7 * N), hchi(2 * N);
-    std::vector<int32_t> hit(N), htr(N * I);
-    HIPCHK(hipMemcpyAsync(hq.data(), dq.get(), sizeof(double) * 7 * N, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hchi.data(), dchi.get(), sizeof(double) * 2 * N, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hit.data(), dit.get(), sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
-    if (N * I) HIPCHK(hipMemcpyAsync(htr.data(), dtr.get(), sizeof(int32_t) * N * I, hipMemcpyDeviceToHost, stream));
+    std::vector<double> hq, hchi;
+    std::vector<int32_t> hit, htr;
+    HIPCHK(sim3opt::read_back(hq, dq.get(), 7 * N, stream));
+    HIPCHK(sim3opt::read_back(hchi, dchi.get(), 2 * N, stream));
+    HIPCHK(sim3opt::read_back(hit, dit.get(), N, stream));
+    HIPCHK(sim3opt::read_back(htr, dtr.get(), N * I, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (pose_out) std::memcpy(pose_out, hq.data(), sizeof(double) * 7 * N);
     if (chi2) std::memcpy(chi2, hchi.data(), sizeof(double) * 2 * N);
@@ -664,12 +644,6 @@ struct Batch {
     return SIM3OPT_OK;
   }
 };
-
-static bool all_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
 
 }  // namespace sim3opt_pnp
 
@@ -694,19 +668,10 @@ void sim3opt_pnp_batch_options_default(sim3opt_pnp_batch_options* o) {
 }
 
 sim3opt_pnp_batch* sim3opt_pnp_batch_create(void) {
-  sim3opt_pnp_batch* b = new (std::nothrow) sim3opt_pnp_batch();
-  if (b) {
-    sim3opt_pnp_batch_options_default(&b->opt);
-    sim3opt::handle_count(+1);
-  }
-  return b;
+  return sim3opt::handle_create<sim3opt_pnp_batch>(sim3opt_pnp_batch_options_default);
 }
 
-void sim3opt_pnp_batch_destroy(sim3opt_pnp_batch* b) {
-  if (!b) return;
-  delete b;
-  if (sim3opt::handle_count(-1) == 0) sim3opt::dev_cache_release();
-}
+void sim3opt_pnp_batch_destroy(sim3opt_pnp_batch* b) { sim3opt::handle_destroy(b); }
 
 const char* sim3opt_pnp_batch_last_error(const sim3opt_pnp_batch* b) { return b ? b->err.c_str() : "null batch"; }
 
@@ -731,17 +696,12 @@ int sim3opt_pnp_batch_set_problems(sim3opt_pnp_batch* b, int32_t n_problems, con
     b->err = "pnp_batch_set_problems: bad argument";
     return SIM3OPT_ERR_ARG;
   }
-  try {
-    if (point_ptr[0] != 0) { b->err = "pnp_batch_set_problems: point_ptr[0] must be 0"; return SIM3OPT_ERR_ARG; }
-    for (int32_t k = 0; k < n_problems; ++k)
-      if (point_ptr[k + 1] <= point_ptr[k]) {
-        b->err = "pnp_batch_set_problems: problem " + std::to_string(k) +
-                 (point_ptr[k + 1] == point_ptr[k] ? " has no point" : ": point_ptr is not monotone");
-        return SIM3OPT_ERR_ARG;
-      }
+  return sim3opt::guarded(b, "pnp_batch_set_problems", sim3opt::NO_MEMORY, [&]() -> int {
+    const std::string e = sim3opt::check_point_ptr(n_problems, point_ptr);
+    if (!e.empty()) { b->err = "pnp_batch_set_problems: " + e; return SIM3OPT_ERR_ARG; }
     const size_t T = (size_t)point_ptr[n_problems];
-    if (!sim3opt_pnp::all_finite(points, 3 * T)) { b->err = "pnp_batch_set_problems: non-finite point"; return SIM3OPT_ERR_ARG; }
-    if (!sim3opt_pnp::all_finite(uv1, 2 * T)) { b->err = "pnp_batch_set_problems: non-finite observation"; return SIM3OPT_ERR_ARG; }
+    if (!sim3opt::all_finite(points, 3 * T)) { b->err = "pnp_batch_set_problems: non-finite point"; return SIM3OPT_ERR_ARG; }
+    if (!sim3opt::all_finite(uv1, 2 * T)) { b->err = "pnp_batch_set_problems: non-finite observation"; return SIM3OPT_ERR_ARG; }
     std::vector<int32_t> ptr(point_ptr, point_ptr + n_problems + 1);
     std::vector<double> p(points, points + 3 * T), a(uv1, uv1 + 2 * T);
     // nothing failed: the handle changes now
@@ -749,11 +709,9 @@ int sim3opt_pnp_batch_set_problems(sim3opt_pnp_batch* b, int32_t n_problems, con
     b->f = focal; b->cx = cx; b->cy = cy;
     b->out_d.clear(); b->out_i.clear(); b->mask.clear();
     b->have_run = false;
-    b->uploaded = false;
+    b->dev.uploaded = false;
     return SIM3OPT_OK;
-  } catch (...) {  // nothing crosses the C boundary
-    b->err = "pnp_batch_set_problems: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  });
 }
 
 int sim3opt_pnp_batch_dims(const sim3opt_pnp_batch* b, int32_t* n_problems, int32_t* total_points) {
@@ -765,11 +723,7 @@ int sim3opt_pnp_batch_dims(const sim3opt_pnp_batch* b, int32_t* n_problems, int3
 
 int sim3opt_pnp_batch_solve(sim3opt_pnp_batch* b) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
-    return b->solve();
-  } catch (...) {
-    b->err = "pnp_batch_solve: out of host memory or internal error"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "pnp_batch_solve", sim3opt::NO_MEMORY_OR_INTERNAL, [&] { return b->solve(); });
 }
 
 int sim3opt_pnp_batch_get_poses(const sim3opt_pnp_batch* b, double* cam1) {
@@ -810,45 +764,35 @@ int sim3opt_pnp_batch_get_summary(const sim3opt_pnp_batch* b, int32_t* status, i
 int sim3opt_pnp_batch_debug_hypotheses(sim3opt_pnp_batch* b, int32_t problem, int32_t* sample, int32_t* n_solutions,
                                        int32_t* valid, double* pose, int32_t* count, double* cost) {
   if (!b) return SIM3OPT_ERR_ARG;
-  try {
-    return b->debug_hypotheses(problem, sample, n_solutions, valid, pose, count, cost);
-  } catch (...) {
-    b->err = "pnp_batch_debug_hypotheses: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "pnp_batch_debug_hypotheses", sim3opt::NO_MEMORY,
+                          [&] { return b->debug_hypotheses(problem, sample, n_solutions, valid, pose, count, cost); });
 }
 
 int sim3opt_pnp_batch_debug_score(sim3opt_pnp_batch* b, int32_t P, const double* poses, int32_t* count, double* cost) {
   if (!b) return SIM3OPT_ERR_ARG;
   if (P < 1 || P > 4096 || !poses || (!count && !cost)) { b->err = "pnp_batch_debug_score: bad argument"; return SIM3OPT_ERR_ARG; }
-  try {
-    return b->debug_score(P, poses, count, cost);
-  } catch (...) {
-    b->err = "pnp_batch_debug_score: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "pnp_batch_debug_score", sim3opt::NO_MEMORY,
+                          [&] { return b->debug_score(P, poses, count, cost); });
 }
 
 int sim3opt_pnp_batch_debug_refine(sim3opt_pnp_batch* b, const double* poses, const uint8_t* mask, double* pose_out,
                                    int32_t* iterations, double* chi2, int32_t* trials) {
   if (!b) return SIM3OPT_ERR_ARG;
   if (!poses || !mask) { b->err = "pnp_batch_debug_refine: bad argument"; return SIM3OPT_ERR_ARG; }
-  if (b->n() >= 1 && !sim3opt_pnp::all_finite(poses, 7 * (size_t)b->n())) {
+  if (b->n() >= 1 && !sim3opt::all_finite(poses, 7 * (size_t)b->n())) {
     b->err = "pnp_batch_debug_refine: non-finite pose"; return SIM3OPT_ERR_ARG;
   }
-  try {
-    return b->debug_refine(poses, mask, pose_out, iterations, chi2, trials);
-  } catch (...) {
-    b->err = "pnp_batch_debug_refine: out of host memory"; return SIM3OPT_ERR_ARG;
-  }
+  return sim3opt::guarded(b, "pnp_batch_debug_refine", sim3opt::NO_MEMORY,
+                          [&] { return b->debug_refine(poses, mask, pose_out, iterations, chi2, trials); });
 }
 
 int sim3opt_median_depth_ratio(int32_t n_problems, const int32_t* point_ptr, const double* depth0,
                                const double* depth1, double* ratio) {
-  if (n_problems < 1 || !point_ptr || !depth0 || !depth1 || !ratio || point_ptr[0] != 0) return SIM3OPT_ERR_ARG;
-  for (int32_t k = 0; k < n_problems; ++k)
-    if (point_ptr[k + 1] <= point_ptr[k]) return SIM3OPT_ERR_ARG;
-  const size_t T = (size_t)point_ptr[n_problems];
-  if (!sim3opt_pnp::all_finite(depth0, T) || !sim3opt_pnp::all_finite(depth1, T)) return SIM3OPT_ERR_ARG;
+  if (n_problems < 1 || !point_ptr || !depth0 || !depth1 || !ratio) return SIM3OPT_ERR_ARG;
   try {
+    if (!sim3opt::check_point_ptr(n_problems, point_ptr).empty()) return SIM3OPT_ERR_ARG;
+    const size_t T = (size_t)point_ptr[n_problems];
+    if (!sim3opt::all_finite(depth0, T) || !sim3opt::all_finite(depth1, T)) return SIM3OPT_ERR_ARG;
     std::vector<double> a, c;
     for (int32_t k = 0; k < n_problems; ++k) {
       const size_t lo = (size_t)point_ptr[k], n = (size_t)point_ptr[k + 1] - lo;

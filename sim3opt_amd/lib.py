@@ -1254,22 +1254,27 @@ def write_bal(path, Rw2c, tw2c, f_k1_k2, points, obs_cam, obs_point, obs_uv):
 KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
-class BundleAdjuster:
-    """sim3opt_ba*: the reference's ba_demo (bal_example.cpp:44-243) -- SE(3) cameras + points, Huber,
-    LM over the Schur complement -- on the GPU.  Mirrors the demo's flow: read a BAL file (or hand the
-    arrays over), optimize(maxIterations), write the camera poses."""
+class _Handle:
+    """What BundleAdjuster, TwoViewBatch, PnpBatch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
+    _prefix = _Options = None
 
     def __init__(self, **options):
         self._L = load()
-        self._b = self._L.sim3opt_ba_create()
+        self._b = self._fn("create")()
         if not self._b:
-            raise MemoryError("sim3opt_ba_create")
+            raise MemoryError(f"sim3opt_{self._prefix}_create")
+        self._opt = self._Options()
+        self._fn("options_default")(C.byref(self._opt))
         if options:
             self.set_options(**options)
 
+    def _fn(self, name):
+        return getattr(self._L, f"sim3opt_{self._prefix}_{name}")
+
     def close(self):
         if self._b:
-            self._L.sim3opt_ba_destroy(self._b)
+            self._fn("destroy")(self._b)
             self._b = None
 
     def __del__(self):
@@ -1280,16 +1285,34 @@ class BundleAdjuster:
 
     def _chk(self, rc, what):
         if rc != OK:
-            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_ba_last_error(self._b).decode()}")
+            raise Sim3OptError(rc, f"{what}: {self._fn('last_error')(self._b).decode()}")
+
+    def _count(self, n, what):
+        """What optimize() / solve() return: the count the library gives, or its error raised."""
+        if n < 0:
+            self._chk(n, what)
+        return n
 
     def set_options(self, **kw):
-        o = BaOptions()
-        self._L.sim3opt_ba_options_default(C.byref(o))
+        """The defaults with `kw` over them."""
+        o = self._Options()
+        self._fn("options_default")(C.byref(o))
         for k, v in kw.items():
             if not hasattr(o, k):
                 raise AttributeError(k)
             setattr(o, k, v)
-        self._chk(self._L.sim3opt_ba_set_options(self._b, C.byref(o)), "ba_set_options")
+        self._chk(self._fn("set_options")(self._b, C.byref(o)), f"{self._prefix}_set_options")
+        self._opt = o
+
+    def options(self):
+        return {k: getattr(self._opt, k) for k, _ in self._Options._fields_}
+
+
+class BundleAdjuster(_Handle):
+    """sim3opt_ba*: the reference's ba_demo (bal_example.cpp:44-243) -- SE(3) cameras + points, Huber,
+    LM over the Schur complement -- on the GPU.  Mirrors the demo's flow: read a BAL file (or hand the
+    arrays over), optimize(maxIterations), write the camera poses."""
+    _prefix, _Options = "ba", BaOptions
 
     def set_problem(self, cams, points, obs_cam, obs_point, obs_uv, focal=KITTI_FOCAL, cx=KITTI_CX,
                     cy=KITTI_CY):
@@ -1412,43 +1435,12 @@ class BundleAdjuster:
         return dict(cams=cams, points=pts, chi2=chi.value, scale=sc.value)
 
 
-class TwoViewBatch:
+class TwoViewBatch(_Handle):
     """sim3opt_ba_batch*: the loop detector's two-view refinement (BAOptimize, kittiDetector.h:845-954) of a whole
     batch of loop candidates in one kernel launch -- camera 0 fixed, camera 1 and the points refined, Huber, LM with
     the detector's settings (lambda_0 = 50, 5 trials, 10 iterations).  Problem k owns the points
     point_ptr[k]:point_ptr[k+1] of the flat arrays."""
-
-    def __init__(self, **options):
-        self._L = load()
-        self._b = self._L.sim3opt_ba_batch_create()
-        if not self._b:
-            raise MemoryError("sim3opt_ba_batch_create")
-        if options:
-            self.set_options(**options)
-
-    def close(self):
-        if self._b:
-            self._L.sim3opt_ba_batch_destroy(self._b)
-            self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != OK:
-            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_ba_batch_last_error(self._b).decode()}")
-
-    def set_options(self, **kw):
-        o = BaBatchOptions()
-        self._L.sim3opt_ba_batch_options_default(C.byref(o))
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise AttributeError(k)
-            setattr(o, k, v)
-        self._chk(self._L.sim3opt_ba_batch_set_options(self._b, C.byref(o)), "ba_batch_set_options")
+    _prefix, _Options = "ba_batch", BaBatchOptions
 
     def set_problems(self, point_ptr, cam0, cam1, points, uv0, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
         ptr = _i32(point_ptr).reshape(-1)
@@ -1471,10 +1463,7 @@ class TwoViewBatch:
 
     def optimize(self):
         """Problems optimised (one launch); raises when the library reports an error."""
-        n = self._L.sim3opt_ba_batch_optimize(self._b)
-        if n < 0:
-            self._chk(n, "ba_batch_optimize")
-        return n
+        return self._count(self._L.sim3opt_ba_batch_optimize(self._b), "ba_batch_optimize")
 
     def cameras(self):
         """(cam0 as given, cam1), n x 7 each"""
@@ -1517,50 +1506,12 @@ class TwoViewBatch:
 PNP_OK, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS, PNP_FEW_INLIERS = 0, 1, 2, 3
 
 
-class PnpBatch:
+class PnpBatch(_Handle):
     """sim3opt_pnp_batch*: the loop detector's start pose (cv::solvePnPRansac, kittiDetector.h:1300-1301) of a whole
     batch of loop candidates in one kernel launch -- P3P hypotheses from a reproducible sampler, every one scored,
     an LM refit over the best one's inliers.  Problem k owns the points point_ptr[k]:point_ptr[k+1] of the flat
     arrays; poses() is the cam1 TwoViewBatch.set_problems takes."""
-
-    def __init__(self, **options):
-        self._L = load()
-        self._b = self._L.sim3opt_pnp_batch_create()
-        if not self._b:
-            raise MemoryError("sim3opt_pnp_batch_create")
-        self._opt = PnpBatchOptions()
-        self._L.sim3opt_pnp_batch_options_default(C.byref(self._opt))
-        if options:
-            self.set_options(**options)
-
-    def close(self):
-        if self._b:
-            self._L.sim3opt_pnp_batch_destroy(self._b)
-            self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != OK:
-            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_pnp_batch_last_error(self._b).decode()}")
-
-    def set_options(self, **kw):
-        """The defaults with `kw` over them (as TwoViewBatch.set_options)."""
-        o = PnpBatchOptions()
-        self._L.sim3opt_pnp_batch_options_default(C.byref(o))
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise AttributeError(k)
-            setattr(o, k, v)
-        self._chk(self._L.sim3opt_pnp_batch_set_options(self._b, C.byref(o)), "pnp_batch_set_options")
-        self._opt = o
-
-    def options(self):
-        return {k: getattr(self._opt, k) for k, _ in PnpBatchOptions._fields_}
+    _prefix, _Options = "pnp_batch", PnpBatchOptions
 
     def set_problems(self, point_ptr, points, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
         ptr = _i32(point_ptr).reshape(-1)
@@ -1579,10 +1530,7 @@ class PnpBatch:
 
     def solve(self):
         """Problems with status 0 (one launch); raises when the library reports an error."""
-        n = self._L.sim3opt_pnp_batch_solve(self._b)
-        if n < 0:
-            self._chk(n, "pnp_batch_solve")
-        return n
+        return self._count(self._L.sim3opt_pnp_batch_solve(self._b), "pnp_batch_solve")
 
     def poses(self):
         """cam1 (n, 7) [qx qy qz qw tx ty tz]"""
@@ -1667,51 +1615,13 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class MatchBatch:
+class MatchBatch(_Handle):
     """sim3opt_match_batch*: descriptor matching with the reference's filters (kittiDetector.h:1085-1160) and the
     map-depth lookup (:1229-1279) of a whole batch of loop candidates.  Frames are handed over once, pairs name them;
     match_ptr() / matches() are the point_ptr, points, uv0 / uv1 and depths PnpBatch, TwoViewBatch and
     median_depth_ratio take."""
-
-    def __init__(self, **options):
-        self._L = load()
-        self._b = self._L.sim3opt_match_batch_create()
-        if not self._b:
-            raise MemoryError("sim3opt_match_batch_create")
-        self._opt = MatchBatchOptions()
-        self._n_kp = self._pairs = None
-        self._L.sim3opt_match_batch_options_default(C.byref(self._opt))
-        if options:
-            self.set_options(**options)
-
-    def close(self):
-        if self._b:
-            self._L.sim3opt_match_batch_destroy(self._b)
-            self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != OK:
-            raise Sim3OptError(rc, f"{what}: {self._L.sim3opt_match_batch_last_error(self._b).decode()}")
-
-    def set_options(self, **kw):
-        """The defaults with `kw` over them (as PnpBatch.set_options)."""
-        o = MatchBatchOptions()
-        self._L.sim3opt_match_batch_options_default(C.byref(o))
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise AttributeError(k)
-            setattr(o, k, v)
-        self._chk(self._L.sim3opt_match_batch_set_options(self._b, C.byref(o)), "match_batch_set_options")
-        self._opt = o
-
-    def options(self):
-        return {k: getattr(self._opt, k) for k, _ in MatchBatchOptions._fields_}
+    _prefix, _Options = "match_batch", MatchBatchOptions
+    _n_kp = _pairs = None  # set_frames / set_pairs: what debug_nn sizes its arrays by
 
     def set_frames(self, kp_ptr, obs_ptr, kp, desc, obs_uv, obs_depth, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY,
                    image_width=KITTI_WIDTH, image_height=KITTI_HEIGHT):
@@ -1745,10 +1655,7 @@ class MatchBatch:
 
     def solve(self):
         """Pairs with status 0; raises when the library reports an error."""
-        n = self._L.sim3opt_match_batch_solve(self._b)
-        if n < 0:
-            self._chk(n, "match_batch_solve")
-        return n
+        return self._count(self._L.sim3opt_match_batch_solve(self._b), "match_batch_solve")
 
     def match_ptr(self):
         out = np.empty(self.dims()["n_pairs"] + 1, dtype=np.int32)

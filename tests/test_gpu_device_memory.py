@@ -7,7 +7,8 @@ read-out at once, on one small graph per solver configuration:
   jacobi      pcg_cases tiny3, block-Jacobi PCG, covariances by columns one at a time
 
 1. no read-out keeps a block, whether it succeeds or refuses;
-2. a graph, a bundle adjuster and a two-view batch give back everything when they are destroyed;
+2. a graph, a bundle adjuster and the three batch handles give back everything when they are destroyed, and the batch
+   handles when a change of options.device releases them -- after which they solve again to the same bytes;
 3. optimize(3), every read-out, optimize(3) is bit for bit optimize(3), optimize(3): the per-family "change nothing" tests
    guard each family, this one their combination under the one SolverSnapshot."""
 import functools
@@ -20,7 +21,9 @@ from conftest import gpu_available
 from sim3opt_amd import lib as L
 import ba_cases as BC
 import factor_cases as FC
+import match_cases as MC
 import pcg_cases as PC
+import pnp_cases as PNC
 import two_view_cases as TC
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
@@ -191,6 +194,110 @@ def test_handles_give_everything_back():
     t.set_problems(**TC.batch_arrays(TC.ONE_ITERATION_CASES[:1]))
     assert t.optimize() == 1
     assert L.device_memory_in_use()[0] == start[0] + 4  # (its four blocks)
+    t.close()
+    assert L.device_memory_in_use() == start, "two-view batch"
+    pnp_batch_gives_everything_back(start)
+    match_batch_gives_everything_back(start)
+    two_view_batch_survives_a_release(start)
+
+
+def as_bytes(x):
+    """A getter's output -- an array, a tuple or a dict of them, a list of per-iteration dicts -- as comparable bytes."""
+    if isinstance(x, dict):
+        return tuple((k, as_bytes(v)) for k, v in sorted(x.items()))
+    if isinstance(x, (tuple, list)):
+        return tuple(as_bytes(v) for v in x)
+    return np.asarray(x).tobytes()
+
+
+def pnp_getters(b):
+    return as_bytes([b.poses(), b.inliers(), b.summary()])
+
+
+def pnp_batch_gives_everything_back(start):
+    two, three = PNC.batch_arrays(PNC.MANY_CASES[:2]), PNC.batch_arrays(PNC.MANY_CASES[:3])
+    b = L.PnpBatch()  # (device = -1; MANY_CASES hold the nine points the defaults ask for)
+    b.set_problems(**two)
+    b.solve()
+    first = pnp_getters(b)
+    assert L.device_memory_in_use()[0] == start[0] + 8  # pointers, input, three hypothesis blocks, two outputs, the mask
+    b.solve()
+    assert L.device_memory_in_use()[0] == start[0] + 8
+    b.set_problems(**three)  # another size: every block goes and comes again
+    b.solve()
+    assert L.device_memory_in_use()[0] == start[0] + 8
+    b.set_problems(**two)
+    b.solve()
+    assert pnp_getters(b) == first
+    b.set_options(device=0)  # the option changes: release()
+    assert L.device_memory_in_use() == start, "pnp batch, released by set_options"
+    assert pnp_getters(b) == first  # (the results of the last solve stay on the host)
+    b.solve()
+    assert L.device_memory_in_use()[0] == start[0] + 8
+    assert pnp_getters(b) == first
+    b.close()
+    assert L.device_memory_in_use() == start, "pnp batch"
+
+
+def match_getters(b):
+    return as_bytes([b.match_ptr(), b.matches(), b.summary()])
+
+
+def match_batch_gives_everything_back(start):
+    rng = np.random.default_rng(19)
+    w, h = MC.KITTI["image_width"], MC.KITTI["image_height"]
+    pool, homes = MC._pool(rng, 30, w, h)
+    frames = [MC._quantised_frame(rng, pool, homes, n_kp, n_obs, w, h) for n_kp, n_obs in ((40, 30), (37, 45))]
+    b = L.MatchBatch()  # (device = -1)
+    b.set_frames(**MC.frame_arrays(frames), **MC.KITTI)
+    b.set_pairs([(0, 1)])
+    assert b.solve() == 1 and b.match_ptr()[-1] > 0
+    first = match_getters(b)
+    nn = as_bytes(b.debug_nn(0))
+    assert L.device_memory_in_use()[0] == start[0] + 22  # 6 blocks of the frames, 16 of the pairs
+    b.solve()
+    assert L.device_memory_in_use()[0] == start[0] + 22
+    b.set_pairs([(0, 1), (1, 0)])  # another size: the pairs' blocks go at the next solve, the frames' stay
+    assert L.device_memory_in_use()[0] == start[0] + 22
+    assert b.solve() == 2
+    assert L.device_memory_in_use()[0] == start[0] + 22
+    b.debug_depth(0, frames[0]["kp"][:5])  # (the frames' blocks alone, and temporaries that go)
+    assert L.device_memory_in_use()[0] == start[0] + 22
+    b.set_pairs([(0, 1)])
+    b.solve()
+    assert match_getters(b) == first and as_bytes(b.debug_nn(0)) == nn
+    b.set_options(device=0)  # the option changes: release()
+    assert L.device_memory_in_use() == start, "match batch, released by set_options"
+    assert match_getters(b) == first  # (the results of the last solve stay on the host)
+    with pytest.raises(L.Sim3OptError, match="the device blocks of the last solve were released; solve again"):
+        b.debug_nn(0)
+    assert L.device_memory_in_use() == start
+    assert b.solve() == 1
+    assert L.device_memory_in_use()[0] == start[0] + 22
+    assert match_getters(b) == first and as_bytes(b.debug_nn(0)) == nn
+    b.close()
+    assert L.device_memory_in_use() == start, "match batch"
+
+
+def two_view_getters(t):
+    return as_bytes([t.cameras(), t.points(), t.num_iterations(), [t.stats(k) for k in range(t.dims()[0])],
+                     t.lambda_init(), t.chi2()])
+
+
+def two_view_batch_survives_a_release(start):
+    a = TC.batch_arrays(TC.ONE_ITERATION_CASES[1:3])
+    t = L.TwoViewBatch()  # (device = -1)
+    t.set_problems(**a)
+    assert t.optimize() == 2
+    first = two_view_getters(t)
+    assert L.device_memory_in_use()[0] == start[0] + 4
+    t.set_options(device=0)  # the option changes: release()
+    assert L.device_memory_in_use() == start, "two-view batch, released by set_options"
+    assert two_view_getters(t) == first  # (the results of the last run stay on the host)
+    t.set_problems(**a)  # (optimize() goes on from the estimate it left: the same start again)
+    assert t.optimize() == 2
+    assert L.device_memory_in_use()[0] == start[0] + 4
+    assert two_view_getters(t) == first
     t.close()
     assert L.device_memory_in_use() == start, "two-view batch"
 

@@ -88,3 +88,16 @@ def test_host_checks_and_tile_table_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     assert r.stdout.strip().endswith("match host ok"), r.stdout[-2000:]
+
+
+def test_handle_host_frame_under_asan_ubsan(tmp_path):
+    """csrc/handle_host.hpp -- all_finite, the two ragged-pointer checks with every message as an exact string, the guard
+    of the C boundary -- and match_host.hpp's use of it, stand-alone (tests/cxx/handle_host_driver.cpp)."""
+    exe = str(tmp_path / "handle_host_san")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror"] + SAN +
+                          [os.path.join(ROOT, "tests", "cxx", "handle_host_driver.cpp"), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert r.stdout.strip().endswith("handle host ok"), r.stdout[-2000:]
