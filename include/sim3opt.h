@@ -689,6 +689,43 @@ int sim3opt_rank_count(const sim3opt_graph* g);
 int sim3opt_local_rows_of_rank(const sim3opt_graph* g, int32_t rank, int32_t* begin, int32_t* end);
 int sim3opt_device_bytes_of_rank(const sim3opt_graph* g, int32_t rank, int64_t bytes[2]);
 
+/* ---- diagnostic read-outs of the in-process transport (tests/test_gpu_comm_operators.py compares them bit for bit
+ * with the numpy restatement tests/comm_ref.py) ----
+ * Each runs exactly ONE collective on operands the caller supplies: every rank's own communicator, on that rank's own
+ * stream, the same allreduce / allgatherv / exchange the engine calls during an optimisation.  They are for testing the
+ * transport at payloads an optimisation never sends; nothing in the product calls them.  `world` below is
+ * sim3opt_rank_count(g).  Rank r's operand is uploaded into a scratch device block of its own, at element offset
+ * `phase` (0 or 1) from a 16-byte aligned start, between guard doubles of a fixed bit pattern (at least 4 either side);
+ * the stream is synchronised, the block read back and every guard compared: one that changed is SIM3OPT_ERR_STATE, the
+ * message names the rank and the index relative to the operand, and the handle is finished (device memory was written
+ * that nobody owned).  The scratch blocks are returned before the call returns; the mailboxes may grow and stay with
+ * the handle, as in a run; the engine's vectors, scalars and estimates are not touched.  With options.time_kernels the
+ * collective is counted in sim3opt_get_comm_times like any other.
+ * Refusals are decided on the host for all ranks at once, before any rank enters the collective, and leave the handle as
+ * it was: SIM3OPT_ERR_STATE unless the handle is initialised and sim3opt_set_devices gave it more than one rank (and for a
+ * finished handle, as everywhere); SIM3OPT_ERR_ARG for a NULL pointer, a phase other than 0 / 1, an op other than 0 / 1,
+ * n < 0 (or beyond 2^30), offsets that decrease or start below 0, and exchange plans that disagree.  n = 0 and plans
+ * without a double are valid: the ranks meet at the barrier and nothing else changes.
+ * (sim3opt_version is unchanged: diagnostics are not part of the versioned interface.) */
+/* Diagnostic.  in and out: world x n doubles, row r is rank r's operand before and after.  op: 0 sum (a left fold in
+ * rank order, ((s0 + s1) + s2) + ..., no contraction), 1 max (a NaN wins, as numpy.maximum has it). */
+int sim3opt_comm_apply_allreduce(sim3opt_graph* g, int64_t n, int32_t op, int32_t phase, const double* in, double* out);
+/* Diagnostic.  offs[0 .. world], offs[0] = 0, never decreasing: rank r owns [offs[r], offs[r + 1]) of a vector of
+ * offs[world] doubles.  in and out: world x offs[world] doubles, row r is rank r's whole vector before and after (what
+ * it holds outside its own span before the call is replaced by the owners' spans). */
+int sim3opt_comm_apply_allgatherv(sim3opt_graph* g, const int64_t* offs, int32_t phase, const double* in, double* out);
+/* Diagnostic.  soffs and roffs: world rows of world + 1 offsets, row r is rank r's plan: it sends
+ * [soffs[r][p], soffs[r][p + 1]) of its send buffer (soffs[r][world] doubles) to rank p and receives rank p's segment
+ * into [roffs[r][p], roffs[r][p + 1]) of its receive buffer (roffs[r][world] doubles); rank p's count for q must be q's
+ * count from p.  A row may start above 0: what lies in front of the first segment is not part of the exchange.  send:
+ * the ranks' send buffers one after the other (checked to come back unchanged); recv: the ranks' receive buffers one
+ * after the other, read AND written: what no segment covers keeps the caller's numbers. */
+int sim3opt_comm_apply_exchange(sim3opt_graph* g, const int64_t* soffs, const int64_t* roffs, int32_t send_phase,
+                                int32_t recv_phase, const double* send, double* recv);
+/* Diagnostic.  out = {capacity of a mailbox in doubles, collectives so far (barrier waits: an exchange that grows the
+ * mailboxes counts 3)} of rank 0; both are the same on every rank.  Same SIM3OPT_ERR_STATE rule as above. */
+int sim3opt_comm_local_state(sim3opt_graph* g, int64_t out[2]);
+
 /* Returns the device blocks the library keeps for re-use (graphs that are re-initialised after growing
  * by an edge find their predecessor's buffers, csrc/devmem.cpp; at most 1 GB) to the HIP runtime, together
  * with the idle streams, events and pinned host blocks (<= 64 MB) it recycles the same way.

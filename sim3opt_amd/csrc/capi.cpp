@@ -15,6 +15,7 @@
 #include "amg.hpp"
 #include "col_plan.hpp"
 #include "comm.hpp"
+#include "comm_apply_host.hpp"
 #include "devmem.hpp"
 #include "direct.hpp"
 #include "engine.hpp"
@@ -1411,6 +1412,78 @@ int sim3opt_device_bytes_of_rank(const sim3opt_graph* g, int32_t rank, int64_t b
   if (rank < 0 || rank >= (g->group ? g->group->size() : 1)) return SIM3OPT_ERR_ARG;
   engine_device_bytes(g->group ? g->group->ctx(rank).engine : g->engine, bytes);
   return SIM3OPT_OK;
+}
+
+// ---- diagnostic read-outs of the in-process transport: everything is decided here, on the host and for all ranks at
+// once, before any rank enters the collective -- a refusal leaves the ranks in step and the handle as it was
+static int comm_apply_ready(sim3opt_graph* g, const char* who) {
+  REFUSE_FINISHED(g);
+  if (!g->group || !g->initialized) {
+    g->err = std::string(who) + ": needs an initialised handle that sim3opt_set_devices gave more than one rank";
+    return SIM3OPT_ERR_STATE;
+  }
+  return SIM3OPT_OK;
+}
+
+int sim3opt_comm_apply_allreduce(sim3opt_graph* g, int64_t n, int32_t op, int32_t phase, const double* in, double* out) {
+  try {
+  if (!g) return SIM3OPT_ERR_ARG;
+  int rc = comm_apply_ready(g, "comm_apply_allreduce");
+  if (rc) return rc;
+  const std::string bad = comm_check_allreduce(n, op, phase, in, out);
+  if (!bad.empty()) return fail(g, SIM3OPT_ERR_ARG, bad.c_str());
+  return on_ranks(g, [&](Engine* e, int rank, std::string& err) {
+    return engine_comm_apply_allreduce(e, (int32_t)n, op, phase, in + (int64_t)rank * n, out + (int64_t)rank * n, err);
+  });
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "comm_apply_allreduce: out of host memory or internal error");
+  }
+}
+
+int sim3opt_comm_apply_allgatherv(sim3opt_graph* g, const int64_t* offs, int32_t phase, const double* in, double* out) {
+  try {
+  if (!g) return SIM3OPT_ERR_ARG;
+  int rc = comm_apply_ready(g, "comm_apply_allgatherv");
+  if (rc) return rc;
+  const int32_t world = g->group->size();
+  const std::string bad = comm_check_allgatherv(offs, world, phase, in, out);
+  if (!bad.empty()) return fail(g, SIM3OPT_ERR_ARG, bad.c_str());
+  const int64_t total = offs[world];
+  return on_ranks(g, [&](Engine* e, int rank, std::string& err) {
+    return engine_comm_apply_allgatherv(e, offs, phase, in + (int64_t)rank * total, out + (int64_t)rank * total, err);
+  });
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "comm_apply_allgatherv: out of host memory or internal error");
+  }
+}
+
+int sim3opt_comm_apply_exchange(sim3opt_graph* g, const int64_t* soffs, const int64_t* roffs, int32_t send_phase,
+                                int32_t recv_phase, const double* send, double* recv) {
+  try {
+  if (!g) return SIM3OPT_ERR_ARG;
+  int rc = comm_apply_ready(g, "comm_apply_exchange");
+  if (rc) return rc;
+  const int32_t world = g->group->size();
+  std::vector<int64_t> sbase, rbase;  // where rank r's buffers start in send / recv
+  const std::string bad = comm_check_exchange(soffs, roffs, world, send_phase, recv_phase, send, recv, sbase, rbase);
+  if (!bad.empty()) return fail(g, SIM3OPT_ERR_ARG, bad.c_str());
+  return on_ranks(g, [&](Engine* e, int rank, std::string& err) {
+    return engine_comm_apply_exchange(e, soffs + (int64_t)rank * (world + 1), roffs + (int64_t)rank * (world + 1),
+                                      send_phase, recv_phase, send + sbase[rank], recv + rbase[rank], err);
+  });
+  } catch (...) {
+    return fail(g, SIM3OPT_ERR_ARG, "comm_apply_exchange: out of host memory or internal error");
+  }
+}
+
+int sim3opt_comm_local_state(sim3opt_graph* g, int64_t out[2]) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  int rc = comm_apply_ready(g, "comm_local_state");
+  if (rc) return rc;
+  if (!out) return fail(g, SIM3OPT_ERR_ARG, "comm_local_state: null argument");
+  // (the workers are idle between two commands: rank 0's record is read from here)
+  return engine_comm_local_state(g->engine, out) ? SIM3OPT_OK
+                                                 : fail(g, SIM3OPT_ERR_STATE, "comm_local_state: not the in-process transport");
 }
 
 }  // extern "C"

@@ -890,5 +890,119 @@ int engine_comm_times(Engine* e, sim3opt_comm_times* out) {
   return SIM3OPT_OK;
 }
 
+// ---- diagnostic read-outs of the in-process transport (sim3opt_comm_apply_*, tests/test_gpu_comm_operators.py) ----
+// One collective of this rank's own Comm on this rank's own stream, on an operand the caller supplies.  The operand
+// lives in a scratch block of its own between guard doubles: COMM_GUARD of them either side (plus `phase` more in
+// front, which puts the operand on an even or an odd double of a 16-byte aligned block), all of one bit pattern that
+// no copy and no fold produces.  After the collective the whole block comes back and every guard is compared.
+namespace {
+
+constexpr int64_t COMM_GUARD = 4;
+constexpr uint64_t COMM_GUARD_BITS = 0x7ff4c0dedbadf00dull;  // (a signalling-NaN payload)
+
+struct GuardedOperand {
+  DevBuf<double> dev;
+  std::vector<double> host;
+  int64_t n = 0, lead = 0;
+  double* ptr() const { return dev.get() + lead; }
+  int upload(const double* src, int64_t n_, int phase, hipStream_t stream, std::string& err) {
+    n = n_;
+    lead = COMM_GUARD + phase;
+    double guard;
+    std::memcpy(&guard, &COMM_GUARD_BITS, sizeof(double));
+    host.assign((size_t)(lead + n + COMM_GUARD), guard);
+    if (n) std::memcpy(host.data() + lead, src, sizeof(double) * (size_t)n);
+    HIPCHK(dev.alloc(host.size()));
+    HIPCHK(hipMemcpyAsync(dev.get(), host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, stream));
+    return SIM3OPT_OK;
+  }
+  // (the caller has synchronised the stream after the collective)
+  int download(double* dst, int rank, const char* what, std::string& err) {
+    HIPCHK(hipMemcpy(host.data(), dev.get(), sizeof(double) * host.size(), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < (int64_t)host.size(); ++i) {
+      if (i >= lead && i < lead + n) continue;
+      uint64_t bits;
+      std::memcpy(&bits, &host[(size_t)i], sizeof(bits));
+      if (bits != COMM_GUARD_BITS) {
+        err = std::string(what) + ": rank " + std::to_string(rank) + " wrote the guard double at index " +
+              std::to_string(i - lead) + " of its operand of " + std::to_string(n) + " doubles";
+        return SIM3OPT_ERR_STATE;
+      }
+    }
+    if (n) std::memcpy(dst, host.data() + lead, sizeof(double) * (size_t)n);
+    return SIM3OPT_OK;
+  }
+};
+
+// the stream is quiet and the timing pairs of the collective are folded in, as after the engine's own look at its scalars
+int comm_apply_finish(Engine* e, std::string& err) {
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (e->comm.timing && e->comm.ev_used) return e->comm.drain(err);
+  return SIM3OPT_OK;
+}
+
+// (a failed collective: whatever it queued on the scratch blocks is behind us before they go back to the cache)
+int comm_apply_failed(Engine* e, int rc) {
+  (void)hipStreamSynchronize(e->stream);
+  return rc;
+}
+
+}  // namespace
+
+int engine_comm_apply_allreduce(Engine* e, int32_t n, int32_t op, int32_t phase, const double* in, double* out,
+                                std::string& err) {
+  GuardedOperand a;
+  int rc = a.upload(in, n, phase, e->stream, err);
+  if (rc) return rc;
+  rc = e->comm.allreduce(a.ptr(), n, op, e->stream, err);
+  if (rc) return comm_apply_failed(e, rc);
+  rc = comm_apply_finish(e, err);
+  if (rc) return rc;
+  return a.download(out, e->comm.rank, "comm_apply_allreduce", err);
+}
+
+int engine_comm_apply_allgatherv(Engine* e, const int64_t* offs, int32_t phase, const double* in, double* out,
+                                 std::string& err) {
+  const std::vector<int64_t> o(offs, offs + e->comm.world + 1);
+  GuardedOperand a;
+  int rc = a.upload(in, o.back(), phase, e->stream, err);
+  if (rc) return rc;
+  rc = e->comm.allgatherv(a.ptr(), o, e->stream, err);
+  if (rc) return comm_apply_failed(e, rc);
+  rc = comm_apply_finish(e, err);
+  if (rc) return rc;
+  return a.download(out, e->comm.rank, "comm_apply_allgatherv", err);
+}
+
+int engine_comm_apply_exchange(Engine* e, const int64_t* soffs, const int64_t* roffs, int32_t send_phase,
+                               int32_t recv_phase, const double* send, double* recv, std::string& err) {
+  const std::vector<int64_t> so(soffs, soffs + e->comm.world + 1), ro(roffs, roffs + e->comm.world + 1);
+  GuardedOperand s, r;
+  int rc = s.upload(send, so.back(), send_phase, e->stream, err);
+  if (rc) return rc;
+  rc = r.upload(recv, ro.back(), recv_phase, e->stream, err);
+  if (rc) return rc;
+  rc = e->comm.exchange(s.ptr(), so, r.ptr(), ro, e->stream, err);
+  if (rc) return comm_apply_failed(e, rc);
+  rc = comm_apply_finish(e, err);
+  if (rc) return rc;
+  std::vector<double> sent((size_t)so.back());  // (the send buffer is an input: it must come back as it went)
+  rc = s.download(sent.data(), e->comm.rank, "comm_apply_exchange (send buffer)", err);
+  if (rc) return rc;
+  if (so.back() && std::memcmp(sent.data(), send, sizeof(double) * sent.size()) != 0) {
+    err = "comm_apply_exchange: rank " + std::to_string(e->comm.rank) + " changed its send buffer";
+    return SIM3OPT_ERR_STATE;
+  }
+  return r.download(recv, e->comm.rank, "comm_apply_exchange (receive buffer)", err);
+}
+
+bool engine_comm_local_state(const Engine* e, int64_t out[2]) {
+  if (e->comm.kind != 3 || !e->comm.local) return false;
+  const LocalRank& r0 = e->comm.local->ranks[0];
+  out[0] = r0.cap;
+  out[1] = (int64_t)r0.seq;
+  return true;
+}
+
 
 }  // namespace sim3opt

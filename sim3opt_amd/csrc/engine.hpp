@@ -94,6 +94,17 @@ void engine_amg_in_use(const Engine* e, int32_t* n_levels, int32_t* n_partitione
 void engine_device_bytes(const Engine* e, int64_t bytes[2]);
 int engine_kernel_times(Engine* e, sim3opt_kernel_times* out, bool reset);
 int engine_comm_times(Engine* e, sim3opt_comm_times* out);
+// diagnostic read-outs of the in-process transport: ONE collective of this rank's communicator on this rank's stream, on
+// this rank's operand in a guarded scratch block (phase 0 / 1: on an even / odd double of a 16-byte aligned block); a
+// guard that changed is SIM3OPT_ERR_STATE naming the rank and the index.  Every rank of the group calls the same one.
+int engine_comm_apply_allreduce(Engine* e, int32_t n, int32_t op, int32_t phase, const double* in, double* out,
+                                std::string& err);
+int engine_comm_apply_allgatherv(Engine* e, const int64_t* offs, int32_t phase, const double* in, double* out,
+                                 std::string& err);
+int engine_comm_apply_exchange(Engine* e, const int64_t* soffs, const int64_t* roffs, int32_t send_phase,
+                               int32_t recv_phase, const double* send, double* recv, std::string& err);
+// {mailbox capacity in doubles, collectives so far} of rank 0 (the same on every rank); false: not that transport
+bool engine_comm_local_state(const Engine* e, int64_t out[2]);
 // the PCG loops' schedule since the last reset: {iterations enqueued, of them after `done`, polls that synchronised
 // with an empty queue behind them, polls waited for with the next chunk queued}
 void engine_pcg_schedule_stats(Engine* e, int64_t out[4], bool reset);

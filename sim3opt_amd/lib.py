@@ -279,6 +279,11 @@ SYMBOLS = {
     "sim3opt_rank_count": (C.c_int, [_vp]),
     "sim3opt_local_rows_of_rank": (C.c_int, [_vp, C.c_int32, _ip, _ip]),
     "sim3opt_device_bytes_of_rank": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
+    "sim3opt_comm_apply_allreduce": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp]),
+    "sim3opt_comm_apply_allgatherv": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_int32, _dp, _dp]),
+    "sim3opt_comm_apply_exchange": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                              _dp, _dp]),
+    "sim3opt_comm_local_state": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "sim3opt_partition_plan": (C.c_int, [_vp, C.c_int32, C.c_int32, _ip, _ip, _ip, C.POINTER(C.c_int64)]),
     "sim3opt_partition_rows": (C.c_int, [C.c_int32, _ip, C.c_int32, _ip]),
     "sim3opt_partition_rows_equal": (C.c_int, [C.c_int32, C.c_int32, _ip]),
@@ -659,6 +664,55 @@ class Graph:
         b = (C.c_int64 * 2)()
         self._chk(self._L.sim3opt_device_bytes_of_rank(self._g, int(rank), b))
         return int(b[0]), int(b[1])
+
+    # ---- diagnostic read-outs of the in-process transport (a set_devices graph with more than one rank) ----
+    def comm_apply_allreduce(self, rows, op=0, phase=0):
+        """One all-reduce (op 0 sum, 1 max) of the ranks' operands: rows (world, n), row r is rank r's, placed on an even
+        (phase 0) or odd (phase 1) double of device memory; returns what every rank holds afterwards, (world, n)."""
+        a = _f64(rows)
+        if a.ndim != 2 or a.shape[0] != self.rank_count():
+            raise ValueError("rows must be (rank_count, n)")
+        out = np.empty_like(a)
+        self._chk(self._L.sim3opt_comm_apply_allreduce(self._g, int(a.shape[1]), int(op), int(phase), _p(a, _dp),
+                                                       _p(out, _dp)))
+        return out
+
+    def comm_apply_allgatherv(self, offs, rows, phase=0):
+        """One in-place all-gather of a vector split at offs (world + 1): rows (world, offs[-1]), row r is rank r's
+        whole vector before; returns the vectors afterwards."""
+        o = np.ascontiguousarray(offs, dtype=np.int64)
+        a = _f64(rows)
+        if o.shape != (self.rank_count() + 1,) or a.shape != (self.rank_count(), max(int(o[-1]), 0)):
+            raise ValueError("offs must be (rank_count + 1,), rows (rank_count, offs[-1])")
+        out = np.empty_like(a)
+        self._chk(self._L.sim3opt_comm_apply_allgatherv(self._g, _p(o, C.POINTER(C.c_int64)), int(phase), _p(a, _dp),
+                                                        _p(out, _dp)))
+        return out
+
+    def comm_apply_exchange(self, soffs, roffs, send, recv, send_phase=0, recv_phase=0):
+        """One neighbour exchange: soffs / roffs (world, world + 1) are the ranks' plans, send / recv lists of the
+        ranks' send buffers and pre-filled receive buffers; returns the list of the receive buffers afterwards."""
+        w = self.rank_count()
+        so = np.ascontiguousarray(soffs, dtype=np.int64)
+        ro = np.ascontiguousarray(roffs, dtype=np.int64)
+        if so.shape != (w, w + 1) or ro.shape != (w, w + 1) or len(send) != w or len(recv) != w:
+            raise ValueError("plans must be (rank_count, rank_count + 1), one buffer per rank")
+        for r in range(w):
+            if len(send[r]) != max(int(so[r, -1]), 0) or len(recv[r]) != max(int(ro[r, -1]), 0):
+                raise ValueError("rank %d: a buffer is as long as its plan's last offset" % r)
+        s = _f64(np.concatenate([_f64(x) for x in send] + [np.zeros(1)]))  # (never an empty array: a pointer is needed)
+        v = _f64(np.concatenate([_f64(x) for x in recv] + [np.zeros(1)])).copy()
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.sim3opt_comm_apply_exchange(self._g, _p(so, i64), _p(ro, i64), int(send_phase),
+                                                      int(recv_phase), _p(s, _dp), _p(v, _dp)))
+        cuts = np.cumsum([0] + [len(x) for x in recv])
+        return [v[cuts[r]:cuts[r + 1]].copy() for r in range(w)]
+
+    def comm_local_state(self):
+        """(capacity of a mailbox in doubles, collectives so far) of the in-process transport."""
+        o = (C.c_int64 * 2)()
+        self._chk(self._L.sim3opt_comm_local_state(self._g, o))
+        return int(o[0]), int(o[1])
 
     # ---- optimisation ----
     def initialize(self):
