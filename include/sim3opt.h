@@ -1015,6 +1015,107 @@ int sim3opt_pnp_batch_debug_refine(sim3opt_pnp_batch* b, const double* poses, co
 int sim3opt_median_depth_ratio(int32_t n_problems, const int32_t* point_ptr, const double* depth0,
                                const double* depth1, double* ratio);
 
+/* ---- batched essential-matrix RANSAC: the loop detector's two-view pose without depths, every candidate in one launch ----
+ * ExtractCameras(points1, points2, Rf2s, tfins, K) (kittiDetector.h:279-293, called at :1161-1185):
+ * cv::findEssentialMat(points1, points2, focal, pp, cv::RANSAC, 0.999, 1.0, mask), then cv::recoverPose(E, points1,
+ * points2, R, t, focal, pp, mask).  Its result is line 2 of a loopConstraints.txt record: the match count, the Euler
+ * angles of Rc12c2 and the unit translation.  It is the one pose of the chain that does not use the map's depths.
+ * PARITY UNPINNED: the reference stores the outputs of its runs, not the matched pixels they were given, and
+ * OpenCV's sampling is not reproducible.  What is OpenCV's here: the order of the steps, the inlier criterion after
+ * its normalisation by focal, the cheirality vote with its distance threshold and the narrowing of the mask.  What is
+ * not: a hypothesis is the five-point solution chosen by a sixth point (OpenCV scores every solution); all
+ * `iterations` hypotheses are evaluated (OpenCV stops early on its confidence 0.999); the sampler is counter-based;
+ * the pose candidates come from a closed form and a least-squares triangulation (OpenCV: SVD, DLT).
+ * Definition.
+ * Coordinates: x = ((u - cx) / f, (v - cy) / f, 1) in double for both views; x1^T E x0 = 0, view 0 is uv0 (points1,
+ * the first frame); the pose is Rc12c2, tc1inc2: X1 = R X0 + t, the convention of the PnP stage's cam1.
+ * Sampler: draw j (0..5) of hypothesis h is splitmix64(seed + (6 h + j + 1) * 0x9E3779B97F4A7C15) modulo n - j,
+ * stepped over the earlier picks in ascending order.  Points 0..4 make the hypothesis, point 5 chooses its solution.
+ * Hypothesis: Nister's five-point method (four-dimensional null space of the 5 x 9 epipolar system; det E = 0 and
+ * 2 E E^T E - tr(E E^T) E = 0 as a 10 x 20 matrix, eliminated with row pivoting; the degree-10 polynomial's real
+ * roots by a Sturm chain with a fixed bisection depth and a fixed number of Newton steps; every solution polished by a
+ * fixed number of Gauss-Newton steps on the ten cubics; up to ten E, each scaled to Frobenius norm 1).  Of the real
+ * solutions the one with the smallest Sampson error on the sixth point.  Invalid (E = 0 stored, skipped): a repeated
+ * point among the six (the same four coordinates), any pivot below its threshold (1e-12 in the 5 x 9 system and in
+ * the 10 x 20 matrix, 1e-14 for a leading coefficient of the Sturm chain), no real root, a non-finite number.
+ * Inlier: a0..2 = E x0, b0..1 = (E^T x1)_0..1, d = x1 . a, e2 = d^2 / (a0^2 + a1^2 + b0^2 + b1^2), every product and
+ * sum rounded on its own, left to right (no fused multiply-add); inlier iff e2 <= (threshold / focal)^2.
+ * Best: the largest inlier count, then the smallest cost (the sum of the inliers' e2), then the smallest index.
+ * Pose: t is the unit vector spanning E's left null space whose component of largest magnitude (the first such) is
+ * positive; Ra and Rb are the rotations with E = +s [t]x Ra and E = -s [t]x Rb, s > 0.  Candidates: 0 (Ra, t),
+ * 1 (Rb, t), 2 (Ra, -t), 3 (Rb, -t).  The depths (z0, z1) of a correspondence under (R, t) are the least-squares
+ * solution of z0 R x0 - z1 x1 = -t; an inlier of the best hypothesis votes for a candidate iff 0 < z0 < distance_threshold
+ * and 0 < z1 < distance_threshold.  The candidate with the most votes wins, the lower index on a tie; the final mask is
+ * the inliers that voted for it.
+ * Device pipeline: sim3opt_amd/csrc/essential_batch.hip, one workgroup per problem, one launch.  A problem's result
+ * does not depend on the other problems of the batch or on its place among them.  No CPU fallback:
+ * SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_essential_batch sim3opt_essential_batch;
+
+typedef struct sim3opt_essential_batch_options {
+  double threshold;           /* inlier: Sampson e2 <= (threshold / focal)^2 [px]  default 1.0   :290 findEssentialMat's threshold */
+  double distance_threshold;  /* a vote needs both depths below it, |t| = 1       default 50    :292 recoverPose [upstream-recall] */
+  uint64_t seed;              /* of the sampler                                   default 0                                        */
+  int32_t iterations;         /* hypotheses per problem, 1..4096                  default 1000  :290 maxIters [upstream-recall]    */
+  int32_t min_points;         /* fewer points: status 1, nothing run; >= 6        default 9     :1163 point_count > 8              */
+  int32_t device;             /* HIP device ordinal, -1 = current                 default -1                                       */
+} sim3opt_essential_batch_options;
+
+#define SIM3OPT_ESSENTIAL_OK 0            /* E, a pose and its inliers                                                    */
+#define SIM3OPT_ESSENTIAL_FEW_POINTS 1    /* fewer than min_points points: nothing run, identity rotation, zero t, E = 0   */
+#define SIM3OPT_ESSENTIAL_NO_HYPOTHESIS 2 /* no sample gave an E: likewise                                                */
+#define SIM3OPT_ESSENTIAL_NO_POSE 3       /* no inlier in front of both cameras under any candidate: candidate 0, E kept   */
+
+void sim3opt_essential_batch_options_default(sim3opt_essential_batch_options* o);
+sim3opt_essential_batch* sim3opt_essential_batch_create(void);
+void sim3opt_essential_batch_destroy(sim3opt_essential_batch* b);
+const char* sim3opt_essential_batch_last_error(const sim3opt_essential_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: iterations outside 1..4096, threshold <= 0, distance_threshold <= 0,
+ * min_points < 6, a non-finite value. */
+int sim3opt_essential_batch_set_options(sim3opt_essential_batch* b, const sim3opt_essential_batch_options* o);
+/* The arguments of the call at :1174 for n_problems candidates at once: point_ptr (n_problems + 1, ragged,
+ * point_ptr[0] = 0), uv0 and uv1 (total x 2: points1, points2) -- exactly the match_ptr, uv0, uv1 that
+ * sim3opt_match_batch_get_* return -- and focal / cx / cy of K.  SIM3OPT_ERR_ARG with nothing changed: n_problems < 1,
+ * a problem with no point, a non-monotone point_ptr, a non-finite number, focal <= 0, a NULL array.  A problem with
+ * fewer than min_points points is accepted and ends with status 1. */
+int sim3opt_essential_batch_set_problems(sim3opt_essential_batch* b, int32_t n_problems, const int32_t* point_ptr,
+                                         const double* uv0, const double* uv1, double focal, double cx, double cy);
+/* Each may be NULL.  tiles[2]: the points staged in LDS at most and the hypotheses of a chunk: the sizes at which
+ * the kernel takes another path. */
+int sim3opt_essential_batch_dims(const sim3opt_essential_batch* b, int32_t* n_problems, int32_t* total_points,
+                                 int32_t tiles[2]);
+/* Every problem, ONE kernel launch for the batch.  Returns the number of problems with status 0, or a negative
+ * SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no problems set); one problem's failure is its status, never the batch's. */
+int sim3opt_essential_batch_solve(sim3opt_essential_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  poses: n x 7 [qx qy qz qw tx ty tz] of Rc12c2 and
+ * tc1inc2, |t| = 1 (status 1 and 2: the identity and zero). */
+int sim3opt_essential_batch_get_poses(const sim3opt_essential_batch* b, double* poses);
+/* essentials: n x 9 row-major, Frobenius norm 1 (status 1 and 2: zero) */
+int sim3opt_essential_batch_get_essentials(const sim3opt_essential_batch* b, double* essentials);
+/* mask (total, 1 = inlier of the best hypothesis that voted for the winning candidate) and / or n_inliers (n) */
+int sim3opt_essential_batch_get_inliers(const sim3opt_essential_batch* b, uint8_t* mask, int32_t* n_inliers);
+/* Per problem (n each, votes n x 4; each may be NULL): status (SIM3OPT_ESSENTIAL_*), the index of the best hypothesis
+ * (-1: none), its inlier count and the sum of its inliers' e2, the winning candidate, its votes, all four vote counts. */
+int sim3opt_essential_batch_get_summary(const sim3opt_essential_batch* b, int32_t* status, int32_t* best_hypothesis,
+                                        int32_t* n_inliers_hypothesis, double* cost_hypothesis, int32_t* winner,
+                                        int32_t* votes_winner, int32_t* votes);
+/* Diagnostics.  Each leaves the results of the last solve as they were.
+ * What the last solve computed for `problem`, H = options.iterations hypotheses: sample (H x 6 point indices),
+ * n_solutions (real solutions with a finite E), valid, essential (H x 9; zero where not valid), count and cost of the
+ * scoring (0 where not valid).  Each may be NULL.  SIM3OPT_ERR_STATE before the first solve. */
+int sim3opt_essential_batch_debug_hypotheses(sim3opt_essential_batch* b, int32_t problem, int32_t* sample,
+                                             int32_t* n_solutions, int32_t* valid, double* essential, int32_t* count,
+                                             double* cost);
+/* P (1..4096) supplied matrices per problem (essentials: n x P x 9, finite) through the scoring code of
+ * k_essential_ransac: count and cost (n x P each, one may be NULL). */
+int sim3opt_essential_batch_debug_score(sim3opt_essential_batch* b, int32_t P, const double* essentials,
+                                        int32_t* count, double* cost);
+/* The pose step of k_essential_ransac on a supplied matrix per problem (essentials: n x 9, finite) and a supplied
+ * inlier set (mask: total): the four candidates (n x 4 x 7, in the order above), their votes (n x 4), the winner (n)
+ * and the mask narrowed to its voters (total).  The outputs may be NULL. */
+int sim3opt_essential_batch_debug_pose(sim3opt_essential_batch* b, const double* essentials, const uint8_t* mask,
+                                       double* candidates, int32_t* votes, int32_t* winner, uint8_t* mask_out);
+
 /* ---- batched descriptor matching and map-depth lookup: what the three blocks above consume, every candidate at once ----
  * The front of computeConstraints: matcher.match / knnMatch(.., 2) with the ratio test, the 1/10 image-border filter,
  * the skew filter and the uniqueness pass (kittiDetector.h:1085-1160), then the depth of every kept match in both

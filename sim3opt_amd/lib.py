@@ -156,6 +156,18 @@ class PnpBatchOptions(C.Structure):
     ]
 
 
+class EssentialBatchOptions(C.Structure):
+    """sim3opt_essential_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("threshold", C.c_double),
+        ("distance_threshold", C.c_double),
+        ("seed", C.c_uint64),
+        ("iterations", C.c_int32),
+        ("min_points", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class MatchBatchOptions(C.Structure):
     """sim3opt_match_batch_options (include/sim3opt.h), field for field."""
     _fields_ = [
@@ -351,6 +363,22 @@ SYMBOLS = {
     "sim3opt_pnp_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
     "sim3opt_pnp_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
     "sim3opt_pnp_batch_debug_refine": (C.c_int, [_vp, _dp, _up, _dp, _ip, _dp, _ip]),
+    "sim3opt_essential_batch_options_default": (None, [C.POINTER(EssentialBatchOptions)]),
+    "sim3opt_essential_batch_create": (_vp, []),
+    "sim3opt_essential_batch_destroy": (None, [_vp]),
+    "sim3opt_essential_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_essential_batch_set_options": (C.c_int, [_vp, C.POINTER(EssentialBatchOptions)]),
+    "sim3opt_essential_batch_set_problems": (C.c_int, [_vp, C.c_int32, _ip, _dp, _dp, C.c_double, C.c_double,
+                                                       C.c_double]),
+    "sim3opt_essential_batch_dims": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "sim3opt_essential_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_essential_batch_get_poses": (C.c_int, [_vp, _dp]),
+    "sim3opt_essential_batch_get_essentials": (C.c_int, [_vp, _dp]),
+    "sim3opt_essential_batch_get_inliers": (C.c_int, [_vp, _up, _ip]),
+    "sim3opt_essential_batch_get_summary": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _ip, _ip, _ip]),
+    "sim3opt_essential_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
+    "sim3opt_essential_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
+    "sim3opt_essential_batch_debug_pose": (C.c_int, [_vp, _dp, _up, _dp, _ip, _ip, _up]),
     "sim3opt_match_batch_options_default": (None, [C.POINTER(MatchBatchOptions)]),
     "sim3opt_match_batch_create": (_vp, []),
     "sim3opt_match_batch_destroy": (None, [_vp]),
@@ -1309,7 +1337,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -1659,6 +1687,111 @@ def median_depth_ratio(point_ptr, depth0, depth1):
     if rc != OK:
         raise Sim3OptError(rc, "median_depth_ratio")
     return out
+
+
+ESSENTIAL_OK, ESSENTIAL_FEW_POINTS, ESSENTIAL_NO_HYPOTHESIS, ESSENTIAL_NO_POSE = 0, 1, 2, 3
+
+
+class EssentialBatch(_Handle):
+    """sim3opt_essential_batch*: the loop detector's essential matrix and relative pose (ExtractCameras,
+    kittiDetector.h:279-293: cv::findEssentialMat + cv::recoverPose) of a whole batch of loop candidates in one kernel
+    launch -- five-point hypotheses from a reproducible sampler, every one scored by its Sampson inliers, the best
+    one's four pose candidates voted on by its inliers.  Problem k owns the correspondences
+    point_ptr[k]:point_ptr[k+1] of uv0 / uv1: exactly MatchBatch's match_ptr, uv0, uv1."""
+    _prefix, _Options = "essential_batch", EssentialBatchOptions
+
+    def set_problems(self, point_ptr, uv0, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        ptr = _i32(point_ptr).reshape(-1)
+        a, b = _f64(uv0).reshape(-1, 2), _f64(uv1).reshape(-1, 2)
+        n = ptr.shape[0] - 1
+        if n >= 1 and not (a.shape[0] == b.shape[0] and a.shape[0] >= ptr.max()):
+            raise ValueError("observation arrays shorter than point_ptr says")
+        self._chk(self._L.sim3opt_essential_batch_set_problems(self._b, n, _p(ptr, _ip), _p(a, _dp), _p(b, _dp), focal,
+                                                               cx, cy), "essential_batch_set_problems")
+
+    def dims(self):
+        """(problems, points of all problems)"""
+        a, b = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_essential_batch_dims(self._b, C.byref(a), C.byref(b), None), "essential_batch_dims")
+        return a.value, b.value
+
+    def tiles(self):
+        """(points staged in LDS at most, hypotheses of a chunk): the sizes at which the kernel takes another path"""
+        t = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.sim3opt_essential_batch_dims(self._b, None, None, _p(t, _ip)), "essential_batch_dims")
+        return int(t[0]), int(t[1])
+
+    def solve(self):
+        """Problems with status 0 (one launch); raises when the library reports an error."""
+        return self._count(self._L.sim3opt_essential_batch_solve(self._b), "essential_batch_solve")
+
+    def poses(self):
+        """(n, 7) [qx qy qz qw tx ty tz] of Rc12c2, tc1inc2 (X1 = R X0 + t), |t| = 1"""
+        out = np.empty((self.dims()[0], 7))
+        self._chk(self._L.sim3opt_essential_batch_get_poses(self._b, _p(out, _dp)), "essential_batch_get_poses")
+        return out
+
+    def essentials(self):
+        """(n, 3, 3), Frobenius norm 1: x1^T E x0 = 0 in normalised coordinates"""
+        out = np.empty((self.dims()[0], 3, 3))
+        self._chk(self._L.sim3opt_essential_batch_get_essentials(self._b, _p(out, _dp)),
+                  "essential_batch_get_essentials")
+        return out
+
+    def inliers(self):
+        """(mask (total,) uint8, n_inliers (n,)): the best hypothesis's inliers that voted for the winning candidate"""
+        n, t = self.dims()
+        m, c = np.empty(t, dtype=np.uint8), np.empty(n, dtype=np.int32)
+        self._chk(self._L.sim3opt_essential_batch_get_inliers(self._b, _p(m, _up), _p(c, _ip)),
+                  "essential_batch_get_inliers")
+        return m, c
+
+    def summary(self):
+        """dict of (n,) arrays: status, best_hypothesis, n_inliers_hypothesis, cost_hypothesis, winner, votes_winner,
+        and votes (n, 4)"""
+        n = self.dims()[0]
+        i = lambda *s: np.empty((n,) + s, dtype=np.int32)
+        st, bh, nh, ch, wi, vw, vo = i(), i(), i(), np.empty(n), i(), i(), i(4)
+        self._chk(self._L.sim3opt_essential_batch_get_summary(self._b, _p(st, _ip), _p(bh, _ip), _p(nh, _ip),
+                                                              _p(ch, _dp), _p(wi, _ip), _p(vw, _ip), _p(vo, _ip)),
+                  "essential_batch_get_summary")
+        return dict(status=st, best_hypothesis=bh, n_inliers_hypothesis=nh, cost_hypothesis=ch, winner=wi,
+                    votes_winner=vw, votes=vo)
+
+    def debug_hypotheses(self, problem):
+        """What the last solve computed for `problem`: dict of sample (H, 6), n_solutions, valid, count (H,), E
+        (H, 3, 3), cost (H,)."""
+        H = self._opt.iterations
+        i = lambda *s: np.empty(s, dtype=np.int32)
+        sm, ns, va, es, co, cs = i(H, 6), i(H), i(H), np.empty((H, 3, 3)), i(H), np.empty(H)
+        self._chk(self._L.sim3opt_essential_batch_debug_hypotheses(self._b, int(problem), _p(sm, _ip), _p(ns, _ip),
+                                                                   _p(va, _ip), _p(es, _dp), _p(co, _ip), _p(cs, _dp)),
+                  "essential_batch_debug_hypotheses")
+        return dict(sample=sm, n_solutions=ns, valid=va, E=es, count=co, cost=cs)
+
+    def debug_score(self, essentials):
+        """essentials (n, P, 3, 3) through the kernel's scoring: (count (n, P) int32, cost (n, P))"""
+        n = self.dims()[0]
+        e = _f64(essentials).reshape(n, -1, 9)
+        P = e.shape[1]
+        co, cs = np.empty((n, P), dtype=np.int32), np.empty((n, P))
+        self._chk(self._L.sim3opt_essential_batch_debug_score(self._b, P, _p(e, _dp), _p(co, _ip), _p(cs, _dp)),
+                  "essential_batch_debug_score")
+        return co, cs
+
+    def debug_pose(self, essentials, mask):
+        """The kernel's pose step on essentials (n, 3, 3) and mask (total,): dict of candidates (n, 4, 7), votes
+        (n, 4), winner (n,), mask (total,) narrowed to the winner's voters."""
+        n, t = self.dims()
+        e = _f64(essentials).reshape(-1)
+        m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        if e.shape[0] != 9 * n or m.shape[0] != t:
+            raise ValueError("essentials holds 9 numbers per problem, mask one entry per point")
+        ca, vo, wi = np.empty((n, 4, 7)), np.empty((n, 4), dtype=np.int32), np.empty(n, dtype=np.int32)
+        mo = np.empty(t, dtype=np.uint8)
+        self._chk(self._L.sim3opt_essential_batch_debug_pose(self._b, _p(e, _dp), _p(m, _up), _p(ca, _dp), _p(vo, _ip),
+                                                             _p(wi, _ip), _p(mo, _up)), "essential_batch_debug_pose")
+        return dict(candidates=ca, votes=vo, winner=wi, mask=mo)
 
 
 MATCH_OK, MATCH_NO_KEYPOINTS, MATCH_NO_MAP = 0, 1, 2
