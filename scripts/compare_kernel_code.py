@@ -5,9 +5,11 @@ that a function's place in the file does not show) and the resource figures of i
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -S --offload-device-only <unit>.hip -o <listing>.s
     python scripts/compare_kernel_code.py parent.s head.s k_linearize_numeric k_diag_reduce ...
     python scripts/compare_kernel_code.py --all parent.s head.s
+    python scripts/compare_kernel_code.py --all parent.s head.s 'k_new<Policy>=k_old'
 
 --all compares every kernel found in either listing, the read-out twins `k<a, b, true>` included, under its full
-demangled name: for a change that must leave the whole unit's device code alone.
+demangled name: for a change that must leave the whole unit's device code alone.  A further argument HEAD=PARENT pairs
+a kernel the change renamed: head's kernel whose name holds HEAD is compared with the parent's whose name holds PARENT.
 
 Prints a markdown table; exit status 1 if a kernel differs or is missing on either side."""
 import hashlib
@@ -72,6 +74,9 @@ def main():
     label = (lambda nm: nm.replace("sim3opt::", "").replace("void ", "")) if everything else short
     sa = {label(names[s]): s for s in ba}
     sb = {label(names[s]): s for s in bb}
+    for head, parent in (w.split("=") for w in want if "=" in w):
+        (h,), (p,) = [n for n in sb if head in n], [n for n in sa if parent in n]
+        sa[f"{p} -> {h}"], sb[f"{p} -> {h}"] = sa.pop(p), sb.pop(h)
     bad = 0
     print("| kernel | parent VGPR / SGPR / scratch / LDS / occupancy / code bytes | head | instruction stream |")
     print("|---|---|---|---|")

@@ -22,17 +22,16 @@
 //                at run time is a private array, so nothing of it goes to scratch.  16 lanes because a group must
 //                not straddle a wavefront and ten rows need ten lanes; CHUNK = 256 / 16, and its 16 work spaces
 //                (29.5 KiB) are what LDS has room for beside the points.
-//   scoring      one wavefront per hypothesis of the chunk, lanes over the points (staged in LDS when the problem has
-//                at most LDS_POINTS of them, else read from global memory), butterfly sums: inlier count (integer),
-//                sum of the inliers' Sampson errors; every wavefront keeps the best of the hypotheses it scored
-//   best         largest count, then smallest cost, then smallest index, over the four wavefronts
+//   scoring,     ransac_frame.hpp (score_chunk, best_of_waves) with EssScore: the Sampson error of the normalised
+//   best         correspondences, staged in LDS when the problem has at most LDS_POINTS of them
 //   pose, vote   thread t owns the points t, t + 256, ...: the four candidates redundantly per thread from the same
 //                bits, every inlier's vote under each, sums by wg_sum; the mask narrowed to the winner's voters
 // What this mapping leaves idle: the null space and the polynomials with their Sturm chain are the first lane's
 // alone (15 of 16 lanes wait), and the roots use ten lanes of 16; with 352 registers a lane there is one wavefront per
 // SIMD.  Spreading those serial phases over the group's lanes is the next thing to do for its time.
-// One launch per batch.  k_essential_score and k_essential_pose run the same scoring and pose code on supplied
-// matrices (sim3opt_essential_batch_debug_*).
+// One launch per batch.  k_ransac_score<EssScore> and k_essential_pose run the same scoring and pose code on supplied
+// matrices (sim3opt_essential_batch_debug_*).  The handle is the frame's RansacBatch; this file adds args() and the
+// pose step's debug entry.
 // Static LDS of k_essential_ransac: points 4 x 1072 x 8 = 34304, work spaces 16 x 236 x 8 = 30208 (a hypothesis's E
 // lies in its work space), validity 64, reduction 256, best 384: 65216 bytes, below the 64 KiB a workgroup may
 // declare statically.
@@ -50,13 +49,14 @@
 #include "ba_math.hpp"
 #include "essential_math.hpp"
 #include "handle_device.hpp"
+#include "ransac_frame.hpp"
 
 namespace sim3opt_essential {
 
 using sim3opt_bundle::wg_sum;
+using sim3opt_ransac::NWAVE;
+using sim3opt_ransac::WG;
 
-constexpr int WG = 256;  // threads of a workgroup (four wavefronts)
-constexpr int NWAVE = WG / 64;
 constexpr int GROUP = 16;             // lanes of a hypothesis group
 constexpr int CHUNK = WG / GROUP;     // hypotheses made, then scored, at a time
 constexpr int LDS_POINTS = 1072;      // KITTI-00's candidates have 219-1047 points: all of them are staged
@@ -115,60 +115,29 @@ __device__ __forceinline__ void stage_points(const PtsGlobal& G, int n, double* 
     G.get(i, s[i], s[LDS_POINTS + i], s[2 * LDS_POINTS + i], s[3 * LDS_POINTS + i]);
 }
 
-// One wavefront scores one E: lane l takes the points l, l + 64, ... in ascending order, then a butterfly; every
-// lane ends with the same count and the same bits of cost.
-template <class Pts>
-__device__ __forceinline__ void score_essential(const Pts& P, int n, const double* Es, double thr2, int& count,
-                                                double& cost) {
-  const int lane = threadIdx.x & 63;
-  double E[9];
+struct EssScore {  // the frame's scoring policy: an E counts the correspondences within thr2 of it (Sampson)
+  static constexpr int DOUBLES = 9, CHUNK = sim3opt_essential::CHUNK, LDS_POINTS = sim3opt_essential::LDS_POINTS,
+                       POINT_DOUBLES = 4;
+  using Args = EssArgs;
+  using Lds = PtsLds;
+  struct Prepared { double E[9]; };
+  const EssArgs& A;
+  static __device__ __forceinline__ PtsGlobal global(const EssArgs& A, int64_t p0) {
+    return PtsGlobal{A.uv0 + 2 * p0, A.uv1 + 2 * p0, A.f, A.cx, A.cy};
+  }
+  static __device__ __forceinline__ void stage(const PtsGlobal& G, int n, double* s) { stage_points(G, n, s); }
+  __device__ __forceinline__ void prepare(const double* Es, Prepared& p) const {
 #pragma unroll
-  for (int i = 0; i < 9; ++i) E[i] = Es[i];
-  int c = 0;
-  double s = 0.0;
-  for (int i = lane; i < n; i += 64) {
+    for (int i = 0; i < 9; ++i) p.E[i] = Es[i];
+  }
+  template <class Pts>
+  __device__ __forceinline__ bool inlier(const Prepared& p, const Pts& P, int i, double& e2) const {
     double x0, y0, x1, y1;
     P.get(i, x0, y0, x1, y1);
-    const double e2 = ess_sampson(E, x0, y0, x1, y1);
-    if (e2 <= thr2) { ++c; s += e2; }
+    e2 = ess_sampson(p.E, x0, y0, x1, y1);
+    return e2 <= A.thr2;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { c += __shfl_xor(c, off); s += __shfl_xor(s, off); }
-  count = c;
-  cost = s;
-}
-
-struct Best {  // of the hypotheses a wavefront has scored: the same in all its lanes
-  int count = -1, h = -1;
-  double cost = 0.0;
-  double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
-
-// The matrices s_E[stride k], k < m, of a chunk (s_valid[k] says which count): wavefront w scores k = w, w + 4, ...,
-// writes count and cost of matrix `first + k` and updates its best (larger count, then smaller cost; it goes through
-// its hypotheses in ascending order, so of equals the smallest index stays).
-template <class Pts>
-__device__ __forceinline__ void score_chunk(const Pts& P, int n, const double* s_E, int stride, const int* s_valid,
-                                            int m, int first, double thr2, int32_t* count_out, int count_stride,
-                                            double* cost_out, Best& best) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int k = wave; k < m; k += NWAVE) {
-    int c = 0;
-    double s = 0.0;
-    if (s_valid[k] != 0) {
-      score_essential(P, n, s_E + stride * k, thr2, c, s);
-      if (c > best.count || (c == best.count && s < best.cost)) {
-        best.count = c; best.cost = s; best.h = first + k;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) best.E[i] = s_E[stride * k + i];
-      }
-    }
-    if (lane == 0) {
-      count_out[(size_t)(first + k) * count_stride] = c;
-      cost_out[first + k] = s;
-    }
-  }
-}
 
 // recoverPose on the points a thread owns.  The inliers are those of E under thr2 (GIVEN = false) or mask_in's
 // (GIVEN = true); each votes for the candidates that put it in front of both cameras and nearer than dist.  Leaves
@@ -188,7 +157,7 @@ __device__ __forceinline__ void pose_vote(const EssArgs& A, int64_t p0, int n, c
 #pragma unroll
     for (int i = 0; i < 3; ++i) cand[c][4 + i] = c < 2 ? t[i] : tm[i];
   }
-  const PtsGlobal G{A.uv0 + 2 * p0, A.uv1 + 2 * p0, A.f, A.cx, A.cy};
+  const PtsGlobal G = EssScore::global(A, p0);
   double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // (counts are integers below 2^31: a double carries them exactly)
   for (int i = threadIdx.x; i < n; i += WG) {
     double x0, y0, x1, y1;
@@ -247,23 +216,24 @@ __global__ __launch_bounds__(WG) void k_essential_ransac(EssArgs A) {
   __shared__ int s_valid[CHUNK];
   __shared__ double red[NWAVE * 8];
   __shared__ double s_best[NWAVE * 12];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int prob = blockIdx.x;
   const int64_t p0 = A.ptr[prob];
   const int n = (int)(A.ptr[prob + 1] - p0);
-  const PtsGlobal G{A.uv0 + 2 * p0, A.uv1 + 2 * p0, A.f, A.cx, A.cy};
+  const PtsGlobal G = EssScore::global(A, p0);
   const double ident[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}, zeroE[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   const int novotes[4] = {0, 0, 0, 0};
 
   if (n < A.min_points) {  // (the whole workgroup: n is the problem's)
-    for (int i = tid; i < n; i += WG) A.mask[p0 + i] = 0;
+    sim3opt_ransac::clear_mask(A.mask, p0, n);
     write_result(A, prob, 1, -1, 0, 0.0, 0, novotes, ident, zeroE);
     return;
   }
   const bool staged = n <= LDS_POINTS;
   if (staged) stage_points(G, n, s_pts);
 
-  Best best;
+  const EssScore score{A};
+  sim3opt_ransac::Best<9> best;
   double* const hE = A.hyp_E + (size_t)prob * A.H * 9;
   double* const hc = A.hyp_cost + (size_t)prob * A.H;
   int32_t* const hi = A.hyp_int + (size_t)prob * A.H * HYP_INTS;
@@ -272,7 +242,7 @@ __global__ __launch_bounds__(WG) void k_essential_ransac(EssArgs A) {
     if (h < A.H) {  // (the same for the lanes of a group)
       const LaneGroup grp{tid % GROUP};
       int idx[6], nsol = 0;
-      ess_sample(A.seed, (uint32_t)h, n, idx);
+      sim3opt_ransac::ransac_sample<6>(A.seed, (uint32_t)h, n, idx);
       double q[6][4], E[9];
 #pragma unroll
       for (int j = 0; j < 6; ++j) G.get(idx[j], q[j][0], q[j][1], q[j][2], q[j][3]);
@@ -290,36 +260,20 @@ __global__ __launch_bounds__(WG) void k_essential_ransac(EssArgs A) {
     }
     __syncthreads();  // the chunk's matrices (and, the first time, the staged points) are in LDS
     const int m = min(CHUNK, A.H - first);
-    if (staged) score_chunk(PtsLds{s_pts}, n, s_ws + WS_E, WS_DOUBLES, s_valid, m, first, A.thr2, hi + 8, HYP_INTS, hc, best);
-    else score_chunk(G, n, s_ws + WS_E, WS_DOUBLES, s_valid, m, first, A.thr2, hi + 8, HYP_INTS, hc, best);
+    const double* const s_E = s_ws + WS_E;  // (a hypothesis's E lies in its work space)
+    if (staged) score_chunk(score, PtsLds{s_pts}, n, s_E, WS_DOUBLES, s_valid, m, first, hi + 8, HYP_INTS, hc, best);
+    else score_chunk(score, G, n, s_E, WS_DOUBLES, s_valid, m, first, hi + 8, HYP_INTS, hc, best);
     __syncthreads();  // ... before the next chunk overwrites them
   }
 
-  // ---- the best of the four wavefronts: count, then cost, then index ----
-  if (lane == 0) {
-    double* b = s_best + 12 * wave;
-    b[0] = (double)best.count; b[1] = best.cost; b[2] = (double)best.h;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) b[3 + i] = best.E[i];
-  }
-  __syncthreads();
-  int bw = 0;
-  for (int w = 1; w < NWAVE; ++w) {
-    const double* a = s_best + 12 * w;
-    const double* b = s_best + 12 * bw;
-    if (a[2] < 0.0) continue;
-    if (b[2] < 0.0 || a[0] > b[0] || (a[0] == b[0] && (a[1] < b[1] || (a[1] == b[1] && a[2] < b[2])))) bw = w;
-  }
-  const int n_hyp = (int)s_best[12 * bw], best_h = (int)s_best[12 * bw + 2];
-  const double cost_hyp = s_best[12 * bw + 1];
+  int n_hyp, best_h;
+  double cost_hyp, E[9], cand[4][7];
+  sim3opt_ransac::best_of_waves(best, s_best, n_hyp, best_h, cost_hyp, E);
   if (best_h < 0) {  // no valid hypothesis
-    for (int i = tid; i < n; i += WG) A.mask[p0 + i] = 0;
+    sim3opt_ransac::clear_mask(A.mask, p0, n);
     write_result(A, prob, 2, -1, 0, 0.0, 0, novotes, ident, zeroE);
     return;
   }
-  double E[9], cand[4][7];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) E[i] = s_best[12 * bw + 3 + i];
   int votes[4], winner, count;
   double cost;
   pose_vote<false>(A, p0, n, E, nullptr, A.mask, red, cand, votes, winner, count, cost);
@@ -331,35 +285,6 @@ __global__ __launch_bounds__(WG) void k_essential_ransac(EssArgs A) {
       for (int i = 0; i < 7; ++i) pose[i] = cand[c][i];
     }
   write_result(A, prob, votes[winner] > 0 ? 0 : 3, best_h, n_hyp, cost_hyp, winner, votes, pose, E);
-}
-
-// sim3opt_essential_batch_debug_score: P supplied matrices per problem through score_chunk
-__global__ __launch_bounds__(WG) void k_essential_score(EssArgs A, const double* essentials, int32_t* count,
-                                                        double* cost) {
-  __shared__ double s_pts[4 * LDS_POINTS];
-  __shared__ double s_E[9 * CHUNK];
-  __shared__ int s_valid[CHUNK];
-  const int tid = threadIdx.x, prob = blockIdx.x;
-  const int64_t p0 = A.ptr[prob];
-  const int n = (int)(A.ptr[prob + 1] - p0);
-  const PtsGlobal G{A.uv0 + 2 * p0, A.uv1 + 2 * p0, A.f, A.cx, A.cy};
-  const bool staged = n <= LDS_POINTS;
-  if (staged) stage_points(G, n, s_pts);
-  Best best;
-  for (int first = 0; first < A.H; first += CHUNK) {
-    if (tid < CHUNK && first + tid < A.H) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) s_E[9 * tid + i] = essentials[((size_t)prob * A.H + first + tid) * 9 + i];
-      s_valid[tid] = 1;
-    }
-    __syncthreads();
-    const int m = min(CHUNK, A.H - first);
-    int32_t* const co = count + (size_t)prob * A.H;
-    double* const cs = cost + (size_t)prob * A.H;
-    if (staged) score_chunk(PtsLds{s_pts}, n, s_E, 9, s_valid, m, first, A.thr2, co, 1, cs, best);
-    else score_chunk(G, n, s_E, 9, s_valid, m, first, A.thr2, co, 1, cs, best);
-    __syncthreads();
-  }
 }
 
 // sim3opt_essential_batch_debug_pose: pose_vote on a supplied matrix and a supplied inlier set per problem
@@ -390,68 +315,25 @@ __global__ __launch_bounds__(WG) void k_essential_pose(EssArgs A, const double* 
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct Batch : sim3opt::BatchHandle {
-  sim3opt_essential_batch_options opt;
-  // the problems, as set
-  std::vector<int32_t> ptr;
-  std::vector<double> uv0, uv1;
-  double f = 0, cx = 0, cy = 0;
-  // the last solve
-  std::vector<double> out_d;
-  std::vector<int32_t> out_i;
-  std::vector<uint8_t> mask;
-  int32_t solved_H = 0;
-  // device
-  sim3opt::DevArena mem;  // the eight blocks of dev
-  struct Dev {
-    int32_t* ptr;
-    double *in, *hyp_E, *hyp_cost, *out_d;
-    int32_t *hyp_int, *out_i;
-    uint8_t* mask;
-    int64_t cap_n, cap_total, cap_H;  // what the blocks were sized for
-    bool uploaded;
-  } dev{};
+struct Batch;
+struct EssTraits {  // what the frame's handle needs to know of this stage
+  using Options = sim3opt_essential_batch_options;
+  using Args = EssArgs;
+  using Score = EssScore;
+  static constexpr int IN0 = 2, IN1 = 2;  // uv0, uv1
+  static constexpr int SAMPLE = 6, MODEL = 9, HYP_INTS = sim3opt_essential::HYP_INTS,
+                       OUT_DOUBLES = sim3opt_essential::OUT_DOUBLES, OUT_INTS = sim3opt_essential::OUT_INTS;
+  static constexpr auto KERNEL = &k_essential_ransac;
+  static constexpr const char* PREFIX = "essential_batch";
+  static constexpr const char* IN0_NAME = "observation";
+  static int32_t n_inliers(const int32_t* o) { return o[4 + o[3]]; }  // the winner's votes
+};
 
-  ~Batch() { release(); }
-  int32_t n() const { return ptr.empty() ? 0 : (int32_t)ptr.size() - 1; }
-  int64_t total() const { return ptr.empty() ? 0 : ptr.back(); }
-
-  void release() {
-    close_stream(mem);
-    dev = Dev{};
-  }
-
-  // the device, the handle's blocks (sized by the problems and options.iterations) and the problems on the device
-  int ensure_device(const char* who) {
-    if (n() < 1) { err = std::string(who) + ": no problems set"; return SIM3OPT_ERR_STATE; }
-    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
-    const size_t N = (size_t)n(), T = (size_t)total(), H = (size_t)opt.iterations;
-    if ((int64_t)N != dev.cap_n || (int64_t)T != dev.cap_total || (int64_t)H != dev.cap_H) {
-      release();
-      if (int rc = open_stream()) return rc;
-      HIPCHK(mem.raw(dev.ptr, N + 1));
-      HIPCHK(mem.raw(dev.in, 4 * T));
-      HIPCHK(mem.raw(dev.hyp_E, 9 * N * H));
-      HIPCHK(mem.raw(dev.hyp_cost, N * H));
-      HIPCHK(mem.raw(dev.hyp_int, HYP_INTS * N * H));
-      HIPCHK(mem.raw(dev.out_d, OUT_DOUBLES * N));
-      HIPCHK(mem.raw(dev.out_i, OUT_INTS * N));
-      HIPCHK(mem.raw(dev.mask, T));
-      dev.cap_n = (int64_t)N; dev.cap_total = (int64_t)T; dev.cap_H = (int64_t)H;
-    }
-    if (!dev.uploaded) {
-      HIPCHK(hipMemcpyAsync(dev.ptr, ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(dev.in, uv0.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(dev.in + 2 * T, uv1.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
-      dev.uploaded = true;
-    }
-    return SIM3OPT_OK;
-  }
-
+struct Batch : sim3opt_ransac::RansacBatch<EssTraits, Batch> {
   EssArgs args() const {
     EssArgs A{};
     A.ptr = dev.ptr; A.uv0 = dev.in; A.uv1 = dev.in + 2 * (size_t)total();
-    A.hyp_E = dev.hyp_E; A.hyp_cost = dev.hyp_cost; A.hyp_int = dev.hyp_int;
+    A.hyp_E = dev.hyp_model; A.hyp_cost = dev.hyp_cost; A.hyp_int = dev.hyp_int;
     A.out_d = dev.out_d; A.out_i = dev.out_i; A.mask = dev.mask;
     A.f = f; A.cx = cx; A.cy = cy;
     const double thr = opt.threshold / f;  // OpenCV divides its threshold by the focal length
@@ -459,85 +341,6 @@ struct Batch : sim3opt::BatchHandle {
     A.dist = opt.distance_threshold; A.seed = opt.seed;
     A.H = opt.iterations; A.min_points = opt.min_points;
     return A;
-  }
-
-  int solve() {
-    err.clear();
-    const int rc = ensure_device("essential_batch_solve");
-    if (rc != SIM3OPT_OK) return rc;
-    const size_t N = (size_t)n(), T = (size_t)total(), H = (size_t)opt.iterations;
-    // hypotheses of a problem that runs none (status 1) read as zeros
-    HIPCHK(hipMemsetAsync(dev.hyp_E, 0, sizeof(double) * 9 * N * H, stream));
-    HIPCHK(hipMemsetAsync(dev.hyp_cost, 0, sizeof(double) * N * H, stream));
-    HIPCHK(hipMemsetAsync(dev.hyp_int, 0, sizeof(int32_t) * HYP_INTS * N * H, stream));
-    hipLaunchKernelGGL(k_essential_ransac, dim3((unsigned)N), dim3(WG), 0, stream, args());  // the one launch
-    HIPCHK(hipGetLastError());
-    std::vector<double> od;
-    std::vector<int32_t> oi;
-    std::vector<uint8_t> m;
-    HIPCHK(sim3opt::read_back(od, dev.out_d, OUT_DOUBLES * N, stream));
-    HIPCHK(sim3opt::read_back(oi, dev.out_i, OUT_INTS * N, stream));
-    HIPCHK(sim3opt::read_back(m, dev.mask, T, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    out_d.swap(od); out_i.swap(oi); mask.swap(m);
-    solved_H = opt.iterations;
-    have_run = true;
-    int ok = 0;
-    for (size_t k = 0; k < N; ++k) ok += out_i[OUT_INTS * k] == 0;
-    return ok;
-  }
-
-  int debug_hypotheses(int32_t problem, int32_t* sample, int32_t* n_solutions, int32_t* valid, double* essential,
-                       int32_t* count, double* cost) {
-    err.clear();
-    if (!have_run) { err = "essential_batch_debug_hypotheses: no solve yet"; return SIM3OPT_ERR_STATE; }
-    if (problem < 0 || problem >= n()) { err = "essential_batch_debug_hypotheses: no such problem"; return SIM3OPT_ERR_ARG; }
-    if (solved_H != opt.iterations || dev.cap_H != solved_H) {
-      err = "essential_batch_debug_hypotheses: options.iterations changed since the solve";
-      return SIM3OPT_ERR_STATE;
-    }
-    const size_t H = (size_t)solved_H;
-    std::vector<int32_t> hi;
-    std::vector<double> he, hc;
-    HIPCHK(sim3opt::read_back(hi, dev.hyp_int + HYP_INTS * H * problem, HYP_INTS * H, stream));
-    HIPCHK(sim3opt::read_back(he, dev.hyp_E + 9 * H * problem, 9 * H, stream));
-    HIPCHK(sim3opt::read_back(hc, dev.hyp_cost + H * problem, H, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t h = 0; h < H; ++h) {
-      if (sample)
-        for (int k = 0; k < 6; ++k) sample[6 * h + k] = hi[HYP_INTS * h + k];
-      if (n_solutions) n_solutions[h] = hi[HYP_INTS * h + 6];
-      if (valid) valid[h] = hi[HYP_INTS * h + 7];
-      if (count) count[h] = hi[HYP_INTS * h + 8];
-    }
-    if (essential) std::memcpy(essential, he.data(), sizeof(double) * he.size());
-    if (cost) std::memcpy(cost, hc.data(), sizeof(double) * H);
-    return SIM3OPT_OK;
-  }
-
-  int debug_score(int32_t P, const double* essentials, int32_t* count, double* cost) {
-    err.clear();
-    const int rc = ensure_device("essential_batch_debug_score");
-    if (rc != SIM3OPT_OK) return rc;
-    const size_t N = (size_t)n(), M = N * (size_t)P;
-    sim3opt::DevBuf<double> de, dc;
-    sim3opt::DevBuf<int32_t> dn;
-    HIPCHK(de.alloc(9 * M));
-    HIPCHK(dc.alloc(M));
-    HIPCHK(dn.alloc(M));
-    HIPCHK(hipMemcpyAsync(de.get(), essentials, sizeof(double) * 9 * M, hipMemcpyHostToDevice, stream));
-    EssArgs A = args();
-    A.H = P;
-    hipLaunchKernelGGL(k_essential_score, dim3((unsigned)N), dim3(WG), 0, stream, A, de.get(), dn.get(), dc.get());
-    HIPCHK(hipGetLastError());
-    std::vector<int32_t> hn;
-    std::vector<double> hc;
-    HIPCHK(sim3opt::read_back(hn, dn.get(), M, stream));
-    HIPCHK(sim3opt::read_back(hc, dc.get(), M, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (count) std::memcpy(count, hn.data(), sizeof(int32_t) * M);
-    if (cost) std::memcpy(cost, hc.data(), sizeof(double) * M);
-    return SIM3OPT_OK;
   }
 
   int debug_pose(const double* essentials, const uint8_t* msk, double* candidates, int32_t* votes, int32_t* winner,
@@ -619,39 +422,14 @@ int sim3opt_essential_batch_set_options(sim3opt_essential_batch* b, const sim3op
 
 int sim3opt_essential_batch_set_problems(sim3opt_essential_batch* b, int32_t n_problems, const int32_t* point_ptr,
                                          const double* uv0, const double* uv1, double focal, double cx, double cy) {
-  if (!b) return SIM3OPT_ERR_ARG;
-  if (n_problems < 1 || !point_ptr || !uv0 || !uv1 || !(focal > 0) || !std::isfinite(focal) || !std::isfinite(cx) ||
-      !std::isfinite(cy)) {
-    b->err = "essential_batch_set_problems: bad argument";
-    return SIM3OPT_ERR_ARG;
-  }
-  return sim3opt::guarded(b, "essential_batch_set_problems", sim3opt::NO_MEMORY, [&]() -> int {
-    const std::string e = sim3opt::check_point_ptr(n_problems, point_ptr);
-    if (!e.empty()) { b->err = "essential_batch_set_problems: " + e; return SIM3OPT_ERR_ARG; }
-    const size_t T = (size_t)point_ptr[n_problems];
-    if (!sim3opt::all_finite(uv0, 2 * T) || !sim3opt::all_finite(uv1, 2 * T)) {
-      b->err = "essential_batch_set_problems: non-finite observation";
-      return SIM3OPT_ERR_ARG;
-    }
-    std::vector<int32_t> ptr(point_ptr, point_ptr + n_problems + 1);
-    std::vector<double> a(uv0, uv0 + 2 * T), c(uv1, uv1 + 2 * T);
-    // nothing failed: the handle changes now
-    b->ptr.swap(ptr); b->uv0.swap(a); b->uv1.swap(c);
-    b->f = focal; b->cx = cx; b->cy = cy;
-    b->out_d.clear(); b->out_i.clear(); b->mask.clear();
-    b->have_run = false;
-    b->dev.uploaded = false;
-    return SIM3OPT_OK;
-  });
+  return b ? b->set_problems(n_problems, point_ptr, uv0, uv1, focal, cx, cy) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_essential_batch_dims(const sim3opt_essential_batch* b, int32_t* n_problems, int32_t* total_points,
                                  int32_t tiles[2]) {
   if (!b) return SIM3OPT_ERR_ARG;
-  if (n_problems) *n_problems = b->n();
-  if (total_points) *total_points = (int32_t)b->total();
   if (tiles) { tiles[0] = sim3opt_essential::LDS_POINTS; tiles[1] = sim3opt_essential::CHUNK; }
-  return SIM3OPT_OK;
+  return b->dims(n_problems, total_points);
 }
 
 int sim3opt_essential_batch_solve(sim3opt_essential_batch* b) {
@@ -660,11 +438,7 @@ int sim3opt_essential_batch_solve(sim3opt_essential_batch* b) {
 }
 
 int sim3opt_essential_batch_get_poses(const sim3opt_essential_batch* b, double* poses) {
-  if (!b || !poses) return SIM3OPT_ERR_ARG;
-  if (!b->have_run) return SIM3OPT_ERR_STATE;
-  for (int32_t k = 0; k < b->n(); ++k)
-    std::memcpy(poses + 7 * (size_t)k, b->out_d.data() + (size_t)sim3opt_essential::OUT_DOUBLES * k, sizeof(double) * 7);
-  return SIM3OPT_OK;
+  return b ? b->get_poses(poses) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_essential_batch_get_essentials(const sim3opt_essential_batch* b, double* essentials) {
@@ -677,15 +451,7 @@ int sim3opt_essential_batch_get_essentials(const sim3opt_essential_batch* b, dou
 }
 
 int sim3opt_essential_batch_get_inliers(const sim3opt_essential_batch* b, uint8_t* mask, int32_t* n_inliers) {
-  if (!b || (!mask && !n_inliers)) return SIM3OPT_ERR_ARG;
-  if (!b->have_run) return SIM3OPT_ERR_STATE;
-  if (mask && !b->mask.empty()) std::memcpy(mask, b->mask.data(), b->mask.size());
-  if (n_inliers)
-    for (int32_t k = 0; k < b->n(); ++k) {
-      const int32_t* o = b->out_i.data() + (size_t)sim3opt_essential::OUT_INTS * k;
-      n_inliers[k] = o[4 + o[3]];
-    }
-  return SIM3OPT_OK;
+  return b ? b->get_inliers(mask, n_inliers) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_essential_batch_get_summary(const sim3opt_essential_batch* b, int32_t* status, int32_t* best_hypothesis,

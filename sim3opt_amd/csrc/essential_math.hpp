@@ -1,6 +1,6 @@
-// essential_math.hpp -- the per-hypothesis arithmetic of the batched essential-matrix RANSAC (essential_batch.hip): the
-// counter-based sampler, Nister's five-point method, the Sampson error, and the pose candidates of an essential
-// matrix with the depths they are voted on.  Host and device: tests/cxx/essential_math_driver.cpp runs the same
+// essential_math.hpp -- the per-hypothesis arithmetic of the batched essential-matrix RANSAC (essential_batch.hip):
+// Nister's five-point method, the Sampson error, and the pose candidates of an essential matrix with the depths they
+// are voted on (the sampler: ransac_sample.hpp).  Host and device: tests/cxx/essential_math_driver.cpp runs the same
 // statements on the CPU against tests/essential_ref.py.
 //
 // Five points, the formulation.  Rows kron(x1, x0) of the five correspondences leave a four-dimensional null space
@@ -40,8 +40,6 @@
 
 namespace sim3opt_essential {
 
-using sim3opt_pnp::splitmix64;
-
 constexpr int WS_DOUBLES = 236;           // the 10 x 20 matrix and the 4 x 9 basis; the layout is WS_* below
 constexpr int BISECTIONS = 40;            // halvings of the Cauchy interval per root
 constexpr int NEWTON = 6;                 // Newton steps on the degree-10 polynomial per root
@@ -50,25 +48,6 @@ constexpr double POLISH_DONE = 1e-20;     // the polish has arrived when |r|^2 b
 constexpr double NULL_PIVOT_MIN = 1e-12;  // pivot of the 5 x 9 system (its entries are at most about 1)
 constexpr double ELIM_PIVOT_MIN = 1e-12;  // pivot of the 10 x 20 matrix (built from an orthonormal basis)
 constexpr double STURM_LEAD_MIN = 1e-14;  // leading coefficient of a member of the chain scaled to max |c| = 1
-
-// The sample of hypothesis h: six distinct indices below n (n >= 6) in exactly six draws, the PnP stage's rule.
-SIM3OPT_ESS_HD void ess_sample(uint64_t seed, uint32_t h, int n, int idx[6]) {
-  int sorted[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const uint64_t r = splitmix64(seed + (uint64_t)(6 * (uint64_t)h + j + 1) * 0x9E3779B97F4A7C15ull);
-    int i = (int)(r % (uint64_t)(n - j));
-#pragma unroll
-    for (int k = 0; k < j; ++k)
-      if (sorted[k] <= i) ++i;
-    idx[j] = i;
-    int v = i;
-#pragma unroll
-    for (int k = 0; k < j; ++k)
-      if (sorted[k] > v) { const int s = sorted[k]; sorted[k] = v; v = s; }
-    sorted[j] = v;
-  }
-}
 
 // Sampson's squared error of (x0, y0, 1) <-> (x1, y1, 1) under E (row-major), x1^T E x0 = 0.  Plain IEEE arithmetic,
 // every operation rounded on its own in the order written (no fused multiply-add), as pnp_sqerr: a restatement gets

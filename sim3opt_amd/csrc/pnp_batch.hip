@@ -14,15 +14,15 @@
 // and no waits on other workgroups; every loop is bounded by the options; a problem's result depends on its own data
 // and the options only.
 //   hypotheses   in chunks of 256: thread t makes hypothesis base + t (pnp_math.hpp) and leaves its pose in LDS
-//   scoring      one wavefront per hypothesis of the chunk, lanes over the points (staged in LDS when the problem has
-//                at most LDS_POINTS of them, else read from global memory), butterfly sums: inlier count (integer),
-//                sum of the inliers' squared errors; every wavefront keeps the best of the hypotheses it scored
-//   best         largest count, then smallest cost, then smallest index, over the four wavefronts
+//   scoring,     ransac_frame.hpp (score_chunk, best_of_waves) with PnpScore: the squared reprojection error of the
+//   best         points in front of the camera, staged in LDS when the problem has at most LDS_POINTS of them
 //   refit        LM on camera 1 over the best hypothesis's inliers: thread t owns the points t, t + 256, ...; sums by
 //                wg_sum, 6x6 Cholesky and the damping rule (lm_damping.hpp) redundantly per thread, as ba_batch.hip
 //   final count  inlier mask, count and RMS at the refitted pose
 // One launch per batch: no step needs anything from another problem, so there is no reason for a second.
-// k_pnp_score and k_pnp_refine run the same scoring and refit code on supplied poses (sim3opt_pnp_batch_debug_*).
+// k_ransac_score<PnpScore> and k_pnp_refine run the same scoring and refit code on supplied poses
+// (sim3opt_pnp_batch_debug_*).  The handle is the frame's RansacBatch; this file adds args() and the refit's debug
+// entry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +39,7 @@
 #include "handle_device.hpp"
 #include "lm_damping.hpp"
 #include "pnp_math.hpp"
+#include "ransac_frame.hpp"
 
 namespace sim3opt_pnp {
 
@@ -49,9 +50,9 @@ using sim3opt_bundle::chol6_solve;
 using sim3opt_bundle::R_to_quat;
 using sim3opt_bundle::tri6;
 using sim3opt_bundle::wg_sum;
+using sim3opt_ransac::NWAVE;
+using sim3opt_ransac::WG;
 
-constexpr int WG = 256;             // threads of a workgroup (four wavefronts)
-constexpr int NWAVE = WG / 64;
 // Points of a problem staged in LDS for the scoring: 5 doubles each, 45 KiB at the cap; with the chunk's poses
 // (14 KiB) and the reduction slots the workgroup stays below the 64 KiB a workgroup may declare statically, so two
 // workgroups share a CU's 160 KiB.  KITTI-00's candidates have 219-1047 points: all of them are staged.
@@ -93,7 +94,9 @@ struct PtsLds {  // ... and staged: five rows of LDS_POINTS (consecutive lanes, 
   }
 };
 
-__device__ __forceinline__ void stage_points(const double* p, const double* uv, int n, double* s) {
+__device__ __forceinline__ void stage_points(const PtsGlobal& G, int n, double* s) {
+  const double* const p = G.p;
+  const double* const uv = G.uv;
   for (int i = threadIdx.x; i < n; i += WG) {
     s[i] = p[3 * (size_t)i]; s[LDS_POINTS + i] = p[3 * (size_t)i + 1]; s[2 * LDS_POINTS + i] = p[3 * (size_t)i + 2];
     s[3 * LDS_POINTS + i] = uv[2 * (size_t)i]; s[4 * LDS_POINTS + i] = uv[2 * (size_t)i + 1];
@@ -108,60 +111,28 @@ __device__ __forceinline__ bool pnp_inlier(const double R[9], const double t[3],
   return z > 0.0 && e2 <= thr2;
 }
 
-// One wavefront scores one pose: lane l takes the points l, l + 64, ... in ascending order, then a butterfly; every
-// lane ends with the same count and the same bits of cost.
-template <class Pts>
-__device__ __forceinline__ void score_pose(const Pts& P, int n, const double* pose, double f, double cx, double cy,
-                                           double thr2, int& count, double& cost) {
-  const int lane = threadIdx.x & 63;
-  double R[9];
-  const double q[4] = {pose[0], pose[1], pose[2], pose[3]}, t[3] = {pose[4], pose[5], pose[6]};
-  pnp_quat_to_R(q, R);
-  int c = 0;
-  double s = 0.0;
-  for (int i = lane; i < n; i += 64) {
-    double X[3], u, v, e2;
+struct PnpScore {  // the frame's scoring policy: a pose [q t] counts the points pnp_inlier admits
+  static constexpr int DOUBLES = 7, CHUNK = WG, LDS_POINTS = sim3opt_pnp::LDS_POINTS, POINT_DOUBLES = 5;
+  using Args = PnpArgs;
+  using Lds = PtsLds;
+  struct Prepared { double R[9], t[3]; };
+  const PnpArgs& A;
+  static __device__ __forceinline__ PtsGlobal global(const PnpArgs& A, int64_t p0) {
+    return PtsGlobal{A.pts + 3 * p0, A.uv + 2 * p0};
+  }
+  static __device__ __forceinline__ void stage(const PtsGlobal& G, int n, double* s) { stage_points(G, n, s); }
+  __device__ __forceinline__ void prepare(const double* pose, Prepared& p) const {
+    const double q[4] = {pose[0], pose[1], pose[2], pose[3]};
+    pnp_quat_to_R(q, p.R);
+    p.t[0] = pose[4]; p.t[1] = pose[5]; p.t[2] = pose[6];
+  }
+  template <class Pts>
+  __device__ __forceinline__ bool inlier(const Prepared& p, const Pts& P, int i, double& e2) const {
+    double X[3], u, v;
     P.get(i, X, u, v);
-    if (pnp_inlier(R, t, X, u, v, f, cx, cy, thr2, e2)) { ++c; s += e2; }
+    return pnp_inlier(p.R, p.t, X, u, v, A.f, A.cx, A.cy, A.thr2, e2);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { c += __shfl_xor(c, off); s += __shfl_xor(s, off); }
-  count = c;
-  cost = s;
-}
-
-struct Best {  // of the hypotheses a wavefront has scored: the same in all its lanes
-  int count = -1, h = -1;
-  double cost = 0.0;
-  double pose[7] = {0, 0, 0, 1, 0, 0, 0};
 };
-
-// The poses s_pose[7 k], k < m, of a chunk (s_valid[k] says which count): wavefront w scores k = w, w + 4, ...,
-// writes count and cost of pose `first + k` and updates its best (larger count, then smaller cost; it goes through
-// its hypotheses in ascending order, so of equals the smallest index stays).
-template <class Pts>
-__device__ __forceinline__ void score_chunk(const Pts& P, int n, const double* s_pose, const int* s_valid, int m,
-                                            int first, const PnpArgs& A, int32_t* count_out, int count_stride,
-                                            double* cost_out, Best& best) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int k = wave; k < m; k += NWAVE) {
-    int c = 0;
-    double s = 0.0;
-    const bool valid = s_valid[k] != 0;
-    if (valid) {
-      score_pose(P, n, s_pose + 7 * k, A.f, A.cx, A.cy, A.thr2, c, s);
-      if (c > best.count || (c == best.count && s < best.cost)) {
-        best.count = c; best.cost = s; best.h = first + k;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) best.pose[i] = s_pose[7 * k + i];
-      }
-    }
-    if (lane == 0) {
-      count_out[(size_t)(first + k) * count_stride] = c;
-      cost_out[first + k] = s;
-    }
-  }
-}
 
 // The inliers of (q, t) among the points a thread owns -> mask; count and sum of squared errors over the workgroup
 __device__ __forceinline__ void mark_inliers(const PnpArgs& A, int64_t p0, int n, const double q[4], const double t[3],
@@ -301,23 +272,25 @@ __global__ __launch_bounds__(WG) void k_pnp_ransac(PnpArgs A) {
   __shared__ int s_valid[WG];
   __shared__ double red[NWAVE * 32];
   __shared__ double s_best[NWAVE * 10];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int prob = blockIdx.x;
   const int64_t p0 = A.ptr[prob];
   const int n = (int)(A.ptr[prob + 1] - p0);
-  const double* const P = A.pts + 3 * p0;
-  const double* const UV = A.uv + 2 * p0;
+  const PtsGlobal G = PnpScore::global(A, p0);
+  const double* const P = G.p;
+  const double* const UV = G.uv;
   double q[4] = {0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
 
   if (n < A.min_points) {  // (the whole workgroup: n is the problem's)
-    for (int i = tid; i < n; i += WG) A.mask[p0 + i] = 0;
+    sim3opt_ransac::clear_mask(A.mask, p0, n);
     write_result(A, prob, 1, -1, 0, 0.0, 0, 0.0, 0, q, t);
     return;
   }
   const bool staged = n <= LDS_POINTS;
-  if (staged) stage_points(P, UV, n, s_pts);
+  if (staged) stage_points(G, n, s_pts);
 
-  Best best;
+  const PnpScore score{A};
+  sim3opt_ransac::Best<7> best;
   double* const hp = A.hyp_pose + (size_t)prob * A.H * 7;
   double* const hc = A.hyp_cost + (size_t)prob * A.H;
   int32_t* const hi = A.hyp_int + (size_t)prob * A.H * HYP_INTS;
@@ -325,7 +298,7 @@ __global__ __launch_bounds__(WG) void k_pnp_ransac(PnpArgs A) {
     const int h = first + tid;
     if (h < A.H) {
       int idx[4], nsol = 0;
-      pnp_sample(A.seed, (uint32_t)h, n, idx);
+      sim3opt_ransac::ransac_sample<4>(A.seed, (uint32_t)h, n, idx);
       double X[4][3], uv[4][2], R[9], tt[3], pose[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -357,37 +330,23 @@ __global__ __launch_bounds__(WG) void k_pnp_ransac(PnpArgs A) {
     }
     __syncthreads();  // the chunk's poses (and, the first time, the staged points) are in LDS
     const int m = min(WG, A.H - first);
-    if (staged) score_chunk(PtsLds{s_pts}, n, s_pose, s_valid, m, first, A, hi + 6, HYP_INTS, hc, best);
-    else score_chunk(PtsGlobal{P, UV}, n, s_pose, s_valid, m, first, A, hi + 6, HYP_INTS, hc, best);
+    if (staged) score_chunk(score, PtsLds{s_pts}, n, s_pose, 7, s_valid, m, first, hi + 6, HYP_INTS, hc, best);
+    else score_chunk(score, G, n, s_pose, 7, s_valid, m, first, hi + 6, HYP_INTS, hc, best);
     __syncthreads();  // ... before the next chunk overwrites them
   }
 
-  // ---- the best of the four wavefronts: count, then cost, then index ----
-  if (lane == 0) {
-    double* b = s_best + 10 * wave;
-    b[0] = (double)best.count; b[1] = best.cost; b[2] = (double)best.h;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) b[3 + i] = best.pose[i];
-  }
-  __syncthreads();
-  int bw = 0;
-  for (int w = 1; w < NWAVE; ++w) {
-    const double* a = s_best + 10 * w;
-    const double* b = s_best + 10 * bw;
-    if (a[2] < 0.0) continue;
-    if (b[2] < 0.0 || a[0] > b[0] || (a[0] == b[0] && (a[1] < b[1] || (a[1] == b[1] && a[2] < b[2])))) bw = w;
-  }
-  const int n_hyp = (int)s_best[10 * bw], best_h = (int)s_best[10 * bw + 2];
-  const double cost_hyp = s_best[10 * bw + 1];
+  int n_hyp, best_h;
+  double cost_hyp, pose[7];
+  sim3opt_ransac::best_of_waves(best, s_best, n_hyp, best_h, cost_hyp, pose);
   if (best_h < 0) {  // no valid hypothesis
-    for (int i = tid; i < n; i += WG) A.mask[p0 + i] = 0;
+    sim3opt_ransac::clear_mask(A.mask, p0, n);
     write_result(A, prob, 2, -1, 0, 0.0, 0, 0.0, 0, q, t);
     return;
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = s_best[10 * bw + 3 + i];
+  for (int i = 0; i < 4; ++i) q[i] = pose[i];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = s_best[10 * bw + 7 + i];
+  for (int i = 0; i < 3; ++i) t[i] = pose[4 + i];
 
   int count, iters = 0;
   double cost, chi0, chi1;
@@ -398,35 +357,6 @@ __global__ __launch_bounds__(WG) void k_pnp_ransac(PnpArgs A) {
   }
   const double rms = count > 0 ? sqrt(cost / (double)count) : 0.0;
   write_result(A, prob, count < A.min_inliers ? 3 : 0, best_h, n_hyp, cost_hyp, count, rms, iters, q, t);
-}
-
-// sim3opt_pnp_batch_debug_score: P supplied poses per problem through score_chunk
-__global__ __launch_bounds__(WG) void k_pnp_score(PnpArgs A, const double* poses, int32_t* count, double* cost) {
-  __shared__ double s_pts[5 * LDS_POINTS];
-  __shared__ double s_pose[7 * WG];
-  __shared__ int s_valid[WG];
-  const int tid = threadIdx.x, prob = blockIdx.x;
-  const int64_t p0 = A.ptr[prob];
-  const int n = (int)(A.ptr[prob + 1] - p0);
-  const double* const P = A.pts + 3 * p0;
-  const double* const UV = A.uv + 2 * p0;
-  const bool staged = n <= LDS_POINTS;
-  if (staged) stage_points(P, UV, n, s_pts);
-  Best best;
-  for (int first = 0; first < A.H; first += WG) {
-    if (first + tid < A.H) {
-#pragma unroll
-      for (int i = 0; i < 7; ++i) s_pose[7 * tid + i] = poses[((size_t)prob * A.H + first + tid) * 7 + i];
-      s_valid[tid] = 1;
-    }
-    __syncthreads();
-    const int m = min(WG, A.H - first);
-    int32_t* const co = count + (size_t)prob * A.H;
-    double* const cs = cost + (size_t)prob * A.H;
-    if (staged) score_chunk(PtsLds{s_pts}, n, s_pose, s_valid, m, first, A, co, 1, cs, best);
-    else score_chunk(PtsGlobal{P, UV}, n, s_pose, s_valid, m, first, A, co, 1, cs, best);
-    __syncthreads();
-  }
 }
 
 // sim3opt_pnp_batch_debug_refine: pnp_refit from a supplied pose on a supplied mask
@@ -459,68 +389,25 @@ __global__ __launch_bounds__(WG) void k_pnp_refine(PnpArgs A, const double* pose
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct Batch : sim3opt::BatchHandle {
-  sim3opt_pnp_batch_options opt;
-  // the problems, as set
-  std::vector<int32_t> ptr;
-  std::vector<double> pts, uv;
-  double f = 0, cx = 0, cy = 0;
-  // the last solve
-  std::vector<double> out_d;
-  std::vector<int32_t> out_i;
-  std::vector<uint8_t> mask;
-  int32_t solved_H = 0;
-  // device
-  sim3opt::DevArena mem;  // the eight blocks of dev
-  struct Dev {
-    int32_t* ptr;
-    double *in, *hyp_pose, *hyp_cost, *out_d;
-    int32_t *hyp_int, *out_i;
-    uint8_t* mask;
-    int64_t cap_n, cap_total, cap_H;  // what the blocks were sized for
-    bool uploaded;
-  } dev{};
+struct Batch;
+struct PnpTraits {  // what the frame's handle needs to know of this stage
+  using Options = sim3opt_pnp_batch_options;
+  using Args = PnpArgs;
+  using Score = PnpScore;
+  static constexpr int IN0 = 3, IN1 = 2;  // points, uv1
+  static constexpr int SAMPLE = 4, MODEL = 7, HYP_INTS = sim3opt_pnp::HYP_INTS, OUT_DOUBLES = sim3opt_pnp::OUT_DOUBLES,
+                       OUT_INTS = sim3opt_pnp::OUT_INTS;
+  static constexpr auto KERNEL = &k_pnp_ransac;
+  static constexpr const char* PREFIX = "pnp_batch";
+  static constexpr const char* IN0_NAME = "point";
+  static int32_t n_inliers(const int32_t* o) { return o[3]; }
+};
 
-  ~Batch() { release(); }
-  int32_t n() const { return ptr.empty() ? 0 : (int32_t)ptr.size() - 1; }
-  int64_t total() const { return ptr.empty() ? 0 : ptr.back(); }
-
-  void release() {
-    close_stream(mem);
-    dev = Dev{};
-  }
-
-  // the device, the handle's blocks (sized by the problems and options.iterations) and the problems on the device
-  int ensure_device(const char* who) {
-    if (n() < 1) { err = std::string(who) + ": no problems set"; return SIM3OPT_ERR_STATE; }
-    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
-    const size_t N = (size_t)n(), T = (size_t)total(), H = (size_t)opt.iterations;
-    if ((int64_t)N != dev.cap_n || (int64_t)T != dev.cap_total || (int64_t)H != dev.cap_H) {
-      release();
-      if (int rc = open_stream()) return rc;
-      HIPCHK(mem.raw(dev.ptr, N + 1));
-      HIPCHK(mem.raw(dev.in, 5 * T));
-      HIPCHK(mem.raw(dev.hyp_pose, 7 * N * H));
-      HIPCHK(mem.raw(dev.hyp_cost, N * H));
-      HIPCHK(mem.raw(dev.hyp_int, HYP_INTS * N * H));
-      HIPCHK(mem.raw(dev.out_d, OUT_DOUBLES * N));
-      HIPCHK(mem.raw(dev.out_i, OUT_INTS * N));
-      HIPCHK(mem.raw(dev.mask, T));
-      dev.cap_n = (int64_t)N; dev.cap_total = (int64_t)T; dev.cap_H = (int64_t)H;
-    }
-    if (!dev.uploaded) {
-      HIPCHK(hipMemcpyAsync(dev.ptr, ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(dev.in, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, stream));
-      HIPCHK(hipMemcpyAsync(dev.in + 3 * T, uv.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, stream));
-      dev.uploaded = true;
-    }
-    return SIM3OPT_OK;
-  }
-
+struct Batch : sim3opt_ransac::RansacBatch<PnpTraits, Batch> {
   PnpArgs args() const {
     PnpArgs A{};
     A.ptr = dev.ptr; A.pts = dev.in; A.uv = dev.in + 3 * (size_t)total();
-    A.hyp_pose = dev.hyp_pose; A.hyp_cost = dev.hyp_cost; A.hyp_int = dev.hyp_int;
+    A.hyp_pose = dev.hyp_model; A.hyp_cost = dev.hyp_cost; A.hyp_int = dev.hyp_int;
     A.out_d = dev.out_d; A.out_i = dev.out_i; A.mask = dev.mask;
     A.f = f; A.cx = cx; A.cy = cy;
     A.thr2 = opt.reproj_error * opt.reproj_error;
@@ -528,85 +415,6 @@ struct Batch : sim3opt::BatchHandle {
     A.H = opt.iterations; A.min_points = opt.min_points; A.min_inliers = opt.min_inliers;
     A.refine_iters = opt.refine_iters; A.max_trials = opt.max_trials;
     return A;
-  }
-
-  int solve() {
-    err.clear();
-    const int rc = ensure_device("pnp_batch_solve");
-    if (rc != SIM3OPT_OK) return rc;
-    const size_t N = (size_t)n(), T = (size_t)total(), H = (size_t)opt.iterations;
-    // hypotheses of a problem that runs none (status 1) read as zeros
-    HIPCHK(hipMemsetAsync(dev.hyp_pose, 0, sizeof(double) * 7 * N * H, stream));
-    HIPCHK(hipMemsetAsync(dev.hyp_cost, 0, sizeof(double) * N * H, stream));
-    HIPCHK(hipMemsetAsync(dev.hyp_int, 0, sizeof(int32_t) * HYP_INTS * N * H, stream));
-    hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)N), dim3(WG), 0, stream, args());  // the one launch of the batch
-    HIPCHK(hipGetLastError());
-    std::vector<double> od;
-    std::vector<int32_t> oi;
-    std::vector<uint8_t> m;
-    HIPCHK(sim3opt::read_back(od, dev.out_d, OUT_DOUBLES * N, stream));
-    HIPCHK(sim3opt::read_back(oi, dev.out_i, OUT_INTS * N, stream));
-    HIPCHK(sim3opt::read_back(m, dev.mask, T, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    out_d.swap(od); out_i.swap(oi); mask.swap(m);
-    solved_H = opt.iterations;
-    have_run = true;
-    int ok = 0;
-    for (size_t k = 0; k < N; ++k) ok += out_i[OUT_INTS * k] == 0;
-    return ok;
-  }
-
-  int debug_hypotheses(int32_t problem, int32_t* sample, int32_t* n_solutions, int32_t* valid, double* pose,
-                       int32_t* count, double* cost) {
-    err.clear();
-    if (!have_run) { err = "pnp_batch_debug_hypotheses: no solve yet"; return SIM3OPT_ERR_STATE; }
-    if (problem < 0 || problem >= n()) { err = "pnp_batch_debug_hypotheses: no such problem"; return SIM3OPT_ERR_ARG; }
-    if (solved_H != opt.iterations || dev.cap_H != solved_H) {
-      err = "pnp_batch_debug_hypotheses: options.iterations changed since the solve";
-      return SIM3OPT_ERR_STATE;
-    }
-    const size_t H = (size_t)solved_H;
-    std::vector<int32_t> hi;
-    std::vector<double> hp, hc;
-    HIPCHK(sim3opt::read_back(hi, dev.hyp_int + HYP_INTS * H * problem, HYP_INTS * H, stream));
-    HIPCHK(sim3opt::read_back(hp, dev.hyp_pose + 7 * H * problem, 7 * H, stream));
-    HIPCHK(sim3opt::read_back(hc, dev.hyp_cost + H * problem, H, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t h = 0; h < H; ++h) {
-      if (sample)
-        for (int k = 0; k < 4; ++k) sample[4 * h + k] = hi[HYP_INTS * h + k];
-      if (n_solutions) n_solutions[h] = hi[HYP_INTS * h + 4];
-      if (valid) valid[h] = hi[HYP_INTS * h + 5];
-      if (count) count[h] = hi[HYP_INTS * h + 6];
-    }
-    if (pose) std::memcpy(pose, hp.data(), sizeof(double) * hp.size());
-    if (cost) std::memcpy(cost, hc.data(), sizeof(double) * H);
-    return SIM3OPT_OK;
-  }
-
-  int debug_score(int32_t P, const double* poses, int32_t* count, double* cost) {
-    err.clear();
-    const int rc = ensure_device("pnp_batch_debug_score");
-    if (rc != SIM3OPT_OK) return rc;
-    const size_t N = (size_t)n(), M = N * (size_t)P;
-    sim3opt::DevBuf<double> dp, dc;
-    sim3opt::DevBuf<int32_t> dn;
-    HIPCHK(dp.alloc(7 * M));
-    HIPCHK(dc.alloc(M));
-    HIPCHK(dn.alloc(M));
-    HIPCHK(hipMemcpyAsync(dp.get(), poses, sizeof(double) * 7 * M, hipMemcpyHostToDevice, stream));
-    PnpArgs A = args();
-    A.H = P;
-    hipLaunchKernelGGL(k_pnp_score, dim3((unsigned)N), dim3(WG), 0, stream, A, dp.get(), dn.get(), dc.get());
-    HIPCHK(hipGetLastError());
-    std::vector<int32_t> hn;
-    std::vector<double> hc;
-    HIPCHK(sim3opt::read_back(hn, dn.get(), M, stream));
-    HIPCHK(sim3opt::read_back(hc, dc.get(), M, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (count) std::memcpy(count, hn.data(), sizeof(int32_t) * M);
-    if (cost) std::memcpy(cost, hc.data(), sizeof(double) * M);
-    return SIM3OPT_OK;
   }
 
   int debug_refine(const double* poses, const uint8_t* msk, double* pose_out, int32_t* iterations, double* chi2,
@@ -690,35 +498,11 @@ int sim3opt_pnp_batch_set_options(sim3opt_pnp_batch* b, const sim3opt_pnp_batch_
 
 int sim3opt_pnp_batch_set_problems(sim3opt_pnp_batch* b, int32_t n_problems, const int32_t* point_ptr,
                                    const double* points, const double* uv1, double focal, double cx, double cy) {
-  if (!b) return SIM3OPT_ERR_ARG;
-  if (n_problems < 1 || !point_ptr || !points || !uv1 || !(focal > 0) || !std::isfinite(focal) ||
-      !std::isfinite(cx) || !std::isfinite(cy)) {
-    b->err = "pnp_batch_set_problems: bad argument";
-    return SIM3OPT_ERR_ARG;
-  }
-  return sim3opt::guarded(b, "pnp_batch_set_problems", sim3opt::NO_MEMORY, [&]() -> int {
-    const std::string e = sim3opt::check_point_ptr(n_problems, point_ptr);
-    if (!e.empty()) { b->err = "pnp_batch_set_problems: " + e; return SIM3OPT_ERR_ARG; }
-    const size_t T = (size_t)point_ptr[n_problems];
-    if (!sim3opt::all_finite(points, 3 * T)) { b->err = "pnp_batch_set_problems: non-finite point"; return SIM3OPT_ERR_ARG; }
-    if (!sim3opt::all_finite(uv1, 2 * T)) { b->err = "pnp_batch_set_problems: non-finite observation"; return SIM3OPT_ERR_ARG; }
-    std::vector<int32_t> ptr(point_ptr, point_ptr + n_problems + 1);
-    std::vector<double> p(points, points + 3 * T), a(uv1, uv1 + 2 * T);
-    // nothing failed: the handle changes now
-    b->ptr.swap(ptr); b->pts.swap(p); b->uv.swap(a);
-    b->f = focal; b->cx = cx; b->cy = cy;
-    b->out_d.clear(); b->out_i.clear(); b->mask.clear();
-    b->have_run = false;
-    b->dev.uploaded = false;
-    return SIM3OPT_OK;
-  });
+  return b ? b->set_problems(n_problems, point_ptr, points, uv1, focal, cx, cy) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_pnp_batch_dims(const sim3opt_pnp_batch* b, int32_t* n_problems, int32_t* total_points) {
-  if (!b) return SIM3OPT_ERR_ARG;
-  if (n_problems) *n_problems = b->n();
-  if (total_points) *total_points = (int32_t)b->total();
-  return SIM3OPT_OK;
+  return b ? b->dims(n_problems, total_points) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_pnp_batch_solve(sim3opt_pnp_batch* b) {
@@ -727,20 +511,11 @@ int sim3opt_pnp_batch_solve(sim3opt_pnp_batch* b) {
 }
 
 int sim3opt_pnp_batch_get_poses(const sim3opt_pnp_batch* b, double* cam1) {
-  if (!b || !cam1) return SIM3OPT_ERR_ARG;
-  if (!b->have_run) return SIM3OPT_ERR_STATE;
-  for (int32_t k = 0; k < b->n(); ++k)
-    std::memcpy(cam1 + 7 * (size_t)k, b->out_d.data() + (size_t)sim3opt_pnp::OUT_DOUBLES * k, sizeof(double) * 7);
-  return SIM3OPT_OK;
+  return b ? b->get_poses(cam1) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_pnp_batch_get_inliers(const sim3opt_pnp_batch* b, uint8_t* mask, int32_t* n_inliers) {
-  if (!b || (!mask && !n_inliers)) return SIM3OPT_ERR_ARG;
-  if (!b->have_run) return SIM3OPT_ERR_STATE;
-  if (mask && !b->mask.empty()) std::memcpy(mask, b->mask.data(), b->mask.size());
-  if (n_inliers)
-    for (int32_t k = 0; k < b->n(); ++k) n_inliers[k] = b->out_i[(size_t)sim3opt_pnp::OUT_INTS * k + 3];
-  return SIM3OPT_OK;
+  return b ? b->get_inliers(mask, n_inliers) : SIM3OPT_ERR_ARG;
 }
 
 int sim3opt_pnp_batch_get_summary(const sim3opt_pnp_batch* b, int32_t* status, int32_t* best_hypothesis,

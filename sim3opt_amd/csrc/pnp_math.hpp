@@ -1,5 +1,5 @@
-// pnp_math.hpp -- the per-hypothesis arithmetic of the batched PnP RANSAC (pnp_batch.hip): the counter-based
-// sampler, a closed-form quartic, the three-point pose (P3P) and the squared reprojection error.  Host and device:
+// pnp_math.hpp -- the per-hypothesis arithmetic of the batched PnP RANSAC (pnp_batch.hip): a closed-form quartic, the
+// three-point pose (P3P) and the squared reprojection error (the sampler: ransac_sample.hpp).  Host and device:
 // tests/cxx/pnp_math_driver.cpp runs the same statements on the CPU against tests/pnp_ref.py.
 //
 // P3P, the formulation: with unit bearings j1 j2 j3 of the three pixels, depths s1, s2 = u s1, s3 = v s1 and the
@@ -15,46 +15,14 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIP__)
-#include <hip/hip_runtime.h>
-#define SIM3OPT_PNP_HD __host__ __device__ __forceinline__
-#else
-#define SIM3OPT_PNP_HD inline
-#endif
+#include "ransac_sample.hpp"
+
+#define SIM3OPT_PNP_HD SIM3OPT_RANSAC_HD
 
 namespace sim3opt_pnp {
 
 constexpr int QUARTIC_POLISH = 3;  // Newton steps on every root of the quartic
 constexpr int CUBIC_POLISH = 2;    // ... and on the resolvent cubic's root
-
-SIM3OPT_PNP_HD uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// The sample of hypothesis h: four distinct indices below n (n >= 4) in exactly four draws.  Draw j picks among the
-// n - j indices not yet taken: its number is stepped over the earlier picks in ascending order.  The key holds the
-// seed and h only.
-SIM3OPT_PNP_HD void pnp_sample(uint64_t seed, uint32_t h, int n, int idx[4]) {
-  int sorted[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint64_t r = splitmix64(seed + (uint64_t)(4 * (uint64_t)h + j + 1) * 0x9E3779B97F4A7C15ull);
-    int i = (int)(r % (uint64_t)(n - j));
-#pragma unroll
-    for (int k = 0; k < j; ++k)
-      if (sorted[k] <= i) ++i;
-    idx[j] = i;
-    // insert into the ascending list
-    int v = i;
-#pragma unroll
-    for (int k = 0; k < j; ++k)
-      if (sorted[k] > v) { const int s = sorted[k]; sorted[k] = v; v = s; }
-    sorted[j] = v;
-  }
-}
 
 // largest real root of m^3 + B m^2 + C m + D
 SIM3OPT_PNP_HD double cubic_largest_root(double B, double C, double D) {

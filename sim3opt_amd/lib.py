@@ -1585,47 +1585,80 @@ class TwoViewBatch(_Handle):
         return dict(active_before=ab, active_after=aa, edge_chi2=ec, n_outlier_edges=no)
 
 
-PNP_OK, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS, PNP_FEW_INLIERS = 0, 1, 2, 3
+class _RansacBatch(_Handle):
+    """What PnpBatch and EssentialBatch share (csrc/ransac_frame.hpp): a batch of problems, each owning the rows
+    point_ptr[k]:point_ptr[k+1] of two flat arrays; one launch makes `iterations` hypotheses per problem from samples
+    of _sample points, scores every one and keeps the best model (of shape _model, under the key _key)."""
+    _sample = _model = _key = None
+    _dims_extra = ()  # what the stage's dims takes after the two counts
 
-
-class PnpBatch(_Handle):
-    """sim3opt_pnp_batch*: the loop detector's start pose (cv::solvePnPRansac, kittiDetector.h:1300-1301) of a whole
-    batch of loop candidates in one kernel launch -- P3P hypotheses from a reproducible sampler, every one scored,
-    an LM refit over the best one's inliers.  Problem k owns the points point_ptr[k]:point_ptr[k+1] of the flat
-    arrays; poses() is the cam1 TwoViewBatch.set_problems takes."""
-    _prefix, _Options = "pnp_batch", PnpBatchOptions
-
-    def set_problems(self, point_ptr, points, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+    def _set_problems(self, point_ptr, a, b, focal, cx, cy, what):
         ptr = _i32(point_ptr).reshape(-1)
-        pts, a = _f64(points).reshape(-1, 3), _f64(uv1).reshape(-1, 2)
         n = ptr.shape[0] - 1
-        if n >= 1 and not (pts.shape[0] == a.shape[0] and pts.shape[0] >= ptr.max()):
-            raise ValueError("point and observation arrays shorter than point_ptr says")
-        self._chk(self._L.sim3opt_pnp_batch_set_problems(self._b, n, _p(ptr, _ip), _p(pts, _dp), _p(a, _dp), focal, cx,
-                                                         cy), "pnp_batch_set_problems")
+        if n >= 1 and not (a.shape[0] == b.shape[0] and a.shape[0] >= ptr.max()):
+            raise ValueError(f"{what} arrays shorter than point_ptr says")
+        self._chk(self._fn("set_problems")(self._b, n, _p(ptr, _ip), _p(a, _dp), _p(b, _dp), focal, cx, cy),
+                  f"{self._prefix}_set_problems")
 
     def dims(self):
         """(problems, points of all problems)"""
         a, b = C.c_int32(), C.c_int32()
-        self._chk(self._L.sim3opt_pnp_batch_dims(self._b, C.byref(a), C.byref(b)), "pnp_batch_dims")
+        self._chk(self._fn("dims")(self._b, C.byref(a), C.byref(b), *self._dims_extra), f"{self._prefix}_dims")
         return a.value, b.value
 
     def solve(self):
         """Problems with status 0 (one launch); raises when the library reports an error."""
-        return self._count(self._L.sim3opt_pnp_batch_solve(self._b), "pnp_batch_solve")
+        return self._count(self._fn("solve")(self._b), f"{self._prefix}_solve")
 
     def poses(self):
-        """cam1 (n, 7) [qx qy qz qw tx ty tz]"""
+        """(n, 7) [qx qy qz qw tx ty tz]"""
         out = np.empty((self.dims()[0], 7))
-        self._chk(self._L.sim3opt_pnp_batch_get_poses(self._b, _p(out, _dp)), "pnp_batch_get_poses")
+        self._chk(self._fn("get_poses")(self._b, _p(out, _dp)), f"{self._prefix}_get_poses")
         return out
 
     def inliers(self):
         """(mask (total,) uint8, n_inliers (n,))"""
         n, t = self.dims()
         m, c = np.empty(t, dtype=np.uint8), np.empty(n, dtype=np.int32)
-        self._chk(self._L.sim3opt_pnp_batch_get_inliers(self._b, _p(m, _up), _p(c, _ip)), "pnp_batch_get_inliers")
+        self._chk(self._fn("get_inliers")(self._b, _p(m, _up), _p(c, _ip)), f"{self._prefix}_get_inliers")
         return m, c
+
+    def debug_hypotheses(self, problem):
+        """What the last solve computed for `problem`: dict of sample (H, _sample), n_solutions, valid, count (H,), the
+        models (H, *_model) under _key, cost (H,)."""
+        H = self._opt.iterations
+        i = lambda *s: np.empty(s, dtype=np.int32)
+        sm, ns, va, mo, co, cs = i(H, self._sample), i(H), i(H), np.empty((H,) + self._model), i(H), np.empty(H)
+        self._chk(self._fn("debug_hypotheses")(self._b, int(problem), _p(sm, _ip), _p(ns, _ip), _p(va, _ip),
+                                               _p(mo, _dp), _p(co, _ip), _p(cs, _dp)),
+                  f"{self._prefix}_debug_hypotheses")
+        return {"sample": sm, "n_solutions": ns, "valid": va, self._key: mo, "count": co, "cost": cs}
+
+    def debug_score(self, models):
+        """models (n, P, *_model) through the kernel's scoring: (count (n, P) int32, cost (n, P))"""
+        n = self.dims()[0]
+        q = _f64(models).reshape(n, -1, int(np.prod(self._model)))
+        P = q.shape[1]
+        co, cs = np.empty((n, P), dtype=np.int32), np.empty((n, P))
+        self._chk(self._fn("debug_score")(self._b, P, _p(q, _dp), _p(co, _ip), _p(cs, _dp)),
+                  f"{self._prefix}_debug_score")
+        return co, cs
+
+
+PNP_OK, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS, PNP_FEW_INLIERS = 0, 1, 2, 3
+
+
+class PnpBatch(_RansacBatch):
+    """sim3opt_pnp_batch*: the loop detector's start pose (cv::solvePnPRansac, kittiDetector.h:1300-1301) of a whole
+    batch of loop candidates in one kernel launch -- P3P hypotheses from a reproducible sampler, every one scored,
+    an LM refit over the best one's inliers.  Problem k owns the points point_ptr[k]:point_ptr[k+1] of the flat
+    arrays; poses() is the cam1 TwoViewBatch.set_problems takes."""
+    _prefix, _Options = "pnp_batch", PnpBatchOptions
+    _sample, _model, _key = 4, (7,), "pose"  # (poses() is cam1)
+
+    def set_problems(self, point_ptr, points, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        self._set_problems(point_ptr, _f64(points).reshape(-1, 3), _f64(uv1).reshape(-1, 2), focal, cx, cy,
+                           "point and observation")
 
     def summary(self):
         """dict of (n,) arrays: status, best_hypothesis, n_inliers_hypothesis, cost_hypothesis, rms_px,
@@ -1637,27 +1670,6 @@ class PnpBatch(_Handle):
                                                         _p(rm, _dp), _p(ri, _ip)), "pnp_batch_get_summary")
         return dict(status=st, best_hypothesis=bh, n_inliers_hypothesis=nh, cost_hypothesis=ch, rms_px=rm,
                     refine_iterations=ri)
-
-    def debug_hypotheses(self, problem):
-        """What the last solve computed for `problem`: dict of sample (H, 4), n_solutions, valid, count (H,), pose
-        (H, 7), cost (H,)."""
-        H = self._opt.iterations
-        i = lambda *s: np.empty(s, dtype=np.int32)
-        sm, ns, va, po, co, cs = i(H, 4), i(H), i(H), np.empty((H, 7)), i(H), np.empty(H)
-        self._chk(self._L.sim3opt_pnp_batch_debug_hypotheses(self._b, int(problem), _p(sm, _ip), _p(ns, _ip),
-                                                             _p(va, _ip), _p(po, _dp), _p(co, _ip), _p(cs, _dp)),
-                  "pnp_batch_debug_hypotheses")
-        return dict(sample=sm, n_solutions=ns, valid=va, pose=po, count=co, cost=cs)
-
-    def debug_score(self, poses):
-        """poses (n, P, 7) through the kernel's scoring: (count (n, P) int32, cost (n, P))"""
-        n = self.dims()[0]
-        q = _f64(poses).reshape(n, -1, 7)
-        P = q.shape[1]
-        co, cs = np.empty((n, P), dtype=np.int32), np.empty((n, P))
-        self._chk(self._L.sim3opt_pnp_batch_debug_score(self._b, P, _p(q, _dp), _p(co, _ip), _p(cs, _dp)),
-                  "pnp_batch_debug_score")
-        return co, cs
 
     def debug_refine(self, poses, mask):
         """The kernel's refit from poses (n, 7) on mask (total,): dict of pose (n, 7), iterations (n,), chi2 (n, 2:
@@ -1692,28 +1704,19 @@ def median_depth_ratio(point_ptr, depth0, depth1):
 ESSENTIAL_OK, ESSENTIAL_FEW_POINTS, ESSENTIAL_NO_HYPOTHESIS, ESSENTIAL_NO_POSE = 0, 1, 2, 3
 
 
-class EssentialBatch(_Handle):
+class EssentialBatch(_RansacBatch):
     """sim3opt_essential_batch*: the loop detector's essential matrix and relative pose (ExtractCameras,
     kittiDetector.h:279-293: cv::findEssentialMat + cv::recoverPose) of a whole batch of loop candidates in one kernel
     launch -- five-point hypotheses from a reproducible sampler, every one scored by its Sampson inliers, the best
     one's four pose candidates voted on by its inliers.  Problem k owns the correspondences
     point_ptr[k]:point_ptr[k+1] of uv0 / uv1: exactly MatchBatch's match_ptr, uv0, uv1."""
     _prefix, _Options = "essential_batch", EssentialBatchOptions
+    # (poses() is Rc12c2, tc1inc2 (X1 = R X0 + t) with |t| = 1; inliers() are those of the best hypothesis that voted
+    # for the winning candidate)
+    _sample, _model, _key, _dims_extra = 6, (3, 3), "E", (None,)
 
     def set_problems(self, point_ptr, uv0, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
-        ptr = _i32(point_ptr).reshape(-1)
-        a, b = _f64(uv0).reshape(-1, 2), _f64(uv1).reshape(-1, 2)
-        n = ptr.shape[0] - 1
-        if n >= 1 and not (a.shape[0] == b.shape[0] and a.shape[0] >= ptr.max()):
-            raise ValueError("observation arrays shorter than point_ptr says")
-        self._chk(self._L.sim3opt_essential_batch_set_problems(self._b, n, _p(ptr, _ip), _p(a, _dp), _p(b, _dp), focal,
-                                                               cx, cy), "essential_batch_set_problems")
-
-    def dims(self):
-        """(problems, points of all problems)"""
-        a, b = C.c_int32(), C.c_int32()
-        self._chk(self._L.sim3opt_essential_batch_dims(self._b, C.byref(a), C.byref(b), None), "essential_batch_dims")
-        return a.value, b.value
+        self._set_problems(point_ptr, _f64(uv0).reshape(-1, 2), _f64(uv1).reshape(-1, 2), focal, cx, cy, "observation")
 
     def tiles(self):
         """(points staged in LDS at most, hypotheses of a chunk): the sizes at which the kernel takes another path"""
@@ -1721,30 +1724,12 @@ class EssentialBatch(_Handle):
         self._chk(self._L.sim3opt_essential_batch_dims(self._b, None, None, _p(t, _ip)), "essential_batch_dims")
         return int(t[0]), int(t[1])
 
-    def solve(self):
-        """Problems with status 0 (one launch); raises when the library reports an error."""
-        return self._count(self._L.sim3opt_essential_batch_solve(self._b), "essential_batch_solve")
-
-    def poses(self):
-        """(n, 7) [qx qy qz qw tx ty tz] of Rc12c2, tc1inc2 (X1 = R X0 + t), |t| = 1"""
-        out = np.empty((self.dims()[0], 7))
-        self._chk(self._L.sim3opt_essential_batch_get_poses(self._b, _p(out, _dp)), "essential_batch_get_poses")
-        return out
-
     def essentials(self):
         """(n, 3, 3), Frobenius norm 1: x1^T E x0 = 0 in normalised coordinates"""
         out = np.empty((self.dims()[0], 3, 3))
         self._chk(self._L.sim3opt_essential_batch_get_essentials(self._b, _p(out, _dp)),
                   "essential_batch_get_essentials")
         return out
-
-    def inliers(self):
-        """(mask (total,) uint8, n_inliers (n,)): the best hypothesis's inliers that voted for the winning candidate"""
-        n, t = self.dims()
-        m, c = np.empty(t, dtype=np.uint8), np.empty(n, dtype=np.int32)
-        self._chk(self._L.sim3opt_essential_batch_get_inliers(self._b, _p(m, _up), _p(c, _ip)),
-                  "essential_batch_get_inliers")
-        return m, c
 
     def summary(self):
         """dict of (n,) arrays: status, best_hypothesis, n_inliers_hypothesis, cost_hypothesis, winner, votes_winner,
@@ -1757,27 +1742,6 @@ class EssentialBatch(_Handle):
                   "essential_batch_get_summary")
         return dict(status=st, best_hypothesis=bh, n_inliers_hypothesis=nh, cost_hypothesis=ch, winner=wi,
                     votes_winner=vw, votes=vo)
-
-    def debug_hypotheses(self, problem):
-        """What the last solve computed for `problem`: dict of sample (H, 6), n_solutions, valid, count (H,), E
-        (H, 3, 3), cost (H,)."""
-        H = self._opt.iterations
-        i = lambda *s: np.empty(s, dtype=np.int32)
-        sm, ns, va, es, co, cs = i(H, 6), i(H), i(H), np.empty((H, 3, 3)), i(H), np.empty(H)
-        self._chk(self._L.sim3opt_essential_batch_debug_hypotheses(self._b, int(problem), _p(sm, _ip), _p(ns, _ip),
-                                                                   _p(va, _ip), _p(es, _dp), _p(co, _ip), _p(cs, _dp)),
-                  "essential_batch_debug_hypotheses")
-        return dict(sample=sm, n_solutions=ns, valid=va, E=es, count=co, cost=cs)
-
-    def debug_score(self, essentials):
-        """essentials (n, P, 3, 3) through the kernel's scoring: (count (n, P) int32, cost (n, P))"""
-        n = self.dims()[0]
-        e = _f64(essentials).reshape(n, -1, 9)
-        P = e.shape[1]
-        co, cs = np.empty((n, P), dtype=np.int32), np.empty((n, P))
-        self._chk(self._L.sim3opt_essential_batch_debug_score(self._b, P, _p(e, _dp), _p(co, _ip), _p(cs, _dp)),
-                  "essential_batch_debug_score")
-        return co, cs
 
     def debug_pose(self, essentials, mask):
         """The kernel's pose step on essentials (n, 3, 3) and mask (total,): dict of candidates (n, 4, 7), votes

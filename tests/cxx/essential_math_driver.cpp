@@ -35,7 +35,7 @@ int main(int argc, char** argv) {
     std::vector<double> ws(E5::WS_DOUBLES);
     for (int h = 0; h < H; ++h) {
       int idx[6], nsol = 0;
-      E5::ess_sample(seed, (uint32_t)h, n, idx);
+      sim3opt_ransac::ransac_sample<6>(seed, (uint32_t)h, n, idx);
       double q[6][4], E[9];
       for (int k = 0; k < 6; ++k)
         for (int c = 0; c < 4; ++c) q[k][c] = (p[4 * (size_t)idx[k] + c] - ((c & 1) ? cy : cx)) / f;

@@ -23,7 +23,7 @@ int main(int argc, char** argv) {
   std::fclose(fp);
   for (int h = 0; h < H; ++h) {
     int idx[4], nsol = 0;
-    sim3opt_pnp::pnp_sample(seed, (uint32_t)h, n, idx);
+    sim3opt_ransac::ransac_sample<4>(seed, (uint32_t)h, n, idx);
     double X[4][3], uv[4][2], R[9], t[3];
     for (int k = 0; k < 4; ++k) {
       for (int c = 0; c < 3; ++c) X[k][c] = p[5 * (size_t)idx[k] + c];
