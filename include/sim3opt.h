@@ -389,6 +389,40 @@ int sim3opt_debug_linearization(sim3opt_graph* g, double* J, double* w, int32_t*
  * not all of them. */
 int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32_t with_fail, int32_t grid,
                          double* states_out, double* backup_out, double* chi2, double* scale);
+/* ---- read-outs of the dogleg's kernels and of the column kernels of the inverse, for tests ----
+ * Same contract as the read-outs above (sim3opt_version unchanged): they run the launch code of a dogleg iteration
+ * after its solve / the vector kernels of a column solve on the caller's data and leave the estimates, every solver
+ * vector and scalar, the cached chi2, the statistics and sim3opt_get_kernel_times bit for bit what they are without
+ * the call.  SIM3OPT_ERR_STATE on a partitioned graph, before sim3opt_initialize, without a linearisation, and for
+ * with_fail unless the exact solver is in use; SIM3OPT_ERR_ARG for a NULL input, a grid outside 0 .. 2048, a range or
+ * an index out of bounds. */
+/* Diagnostic.  h_gn (7 per block row, any numbers) goes where the solve leaves its solution.  scalars[6]: b.b, b^T H b,
+ * g.g, b.g, (Hb).g, g^T H g for g = h_gn, as k_dl_dots, k_dl_sum and k_dl_final leave them and the host reads them;
+ * the SpMVs' partial count is options.span_grid as sim3opt_initialize clamped it (sim3opt_get_options).  grid = 0:
+ * k_dl_dots' own workgroup count, 1 .. 2048: that many (= partial sums per dot); [j0, j1) the entries the four dots run
+ * over (0 <= j0 <= j1 <= 7 x block rows; both 0: all of them; the two quadratic forms always cover every row).
+ * states_out / backup_out (8 per vertex): the estimates after k_dogleg_oplus with h_dl = ca b + cg h_gn and the backup
+ * it takes; then the estimates are restored.  with_fail != 0 presents the exact solver's failure token: nothing may
+ * move.  The three outputs may be NULL, not all of them. */
+int sim3opt_debug_dogleg(sim3opt_graph* g, const double* h_gn, double ca, double cg, int32_t with_fail, int32_t grid,
+                         int64_t j0, int64_t j1, double* scalars, double* states_out, double* backup_out);
+/* The dogleg's step rule on the host (no GPU needed; the function sim3opt_optimize calls per trial): from the six
+ * scalars above and the trust radius delta, model = {alpha, ||h_sd||, ||h_gn||} and trial = {ca, cg, ||h_dl||,
+ * linearGain} of h_dl = ca b + cg h_gn, *step = SIM3OPT_STEP_*.  SIM3OPT_ERR_ARG for a NULL pointer. */
+int sim3opt_dogleg_rule(const double scalars[6], double delta, double model[3], double trial[4], int32_t* step);
+/* Diagnostic.  One of the vector kernels of the columns of the inverse (options.cov_solver) on the caller's data, at a
+ * vector length 1 <= n <= 7 x block rows, staged in the buffers a column solve uses: systems lie vs = 7 x block rows
+ * rounded up to a multiple of 64 doubles apart.  Also refused (SIM3OPT_ERR_STATE) where the columns are: on a graph
+ * that factorises exactly.  grid = 0: the workgroups a solve launches, 1 .. 2048: that many.  `out` is read and written:
+ * on entry what the kernel's output buffer holds before the launch.
+ *   kernel 0, k_cols_rhs<K>: K = 1 .. 4 systems, at[K] their unit entries (< 0: none; must be < n); out: K x vs.
+ *   kernel 1, k_cols_residual: r = a - b on system `system` (0 .. 3); a, b: n each; out: vs (r and what follows it).
+ *   kernel 2, k_cols_axpy: y += a on system `system`; out: vs, on entry y.
+ *   kernel 3, k_cols_gather: column `col` (0 .. 6) of blocks first .. first + count - 1 of out (n_blocks x 49) from
+ *     a = y (n) at the block rows rows[first .. first + count) (7 rows[k] + 7 <= n; rows has first + count entries). */
+int sim3opt_debug_column_vectors(sim3opt_graph* g, int32_t kernel, int32_t grid, int64_t n, int32_t K, const int64_t* at,
+                                 int32_t system, const double* a, const double* b, int32_t first, int32_t count,
+                                 int32_t col, const int32_t* rows, int32_t n_blocks, double* out);
 /* ---- read-out of the exact block Cholesky, its solve and the selected inversion, for tests ----
  * Same contract as the read-outs above: nothing in the solver uses it; it runs the launches that exist (k_ldl_gather,
  * k_ldl, k_selinv_pivots, k_selinv) and copies their buffers out; the system H / b, every solver scalar (the LM's fail

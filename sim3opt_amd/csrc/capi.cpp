@@ -761,6 +761,36 @@ int sim3opt_debug_update(sim3opt_graph* g, const double* x, double lambda, int32
   return engine_debug_update(g->engine, x, lambda, with_fail != 0, grid, states_out, backup_out, chi2, scale, g->err);
 }
 
+int sim3opt_debug_dogleg(sim3opt_graph* g, const double* h_gn, double ca, double cg, int32_t with_fail, int32_t grid,
+                         int64_t j0, int64_t j1, double* scalars, double* states_out, double* backup_out) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!h_gn) return fail(g, SIM3OPT_ERR_ARG, "debug_dogleg: null h_gn");
+  if (!scalars && !states_out && !backup_out) return fail(g, SIM3OPT_ERR_ARG, "debug_dogleg: every output is null");
+  if (!std::isfinite(ca) || !std::isfinite(cg)) return fail(g, SIM3OPT_ERR_ARG, "debug_dogleg: a coefficient is not finite");
+  if (!g->initialized || g->dirty) return fail(g, SIM3OPT_ERR_STATE, "debug_dogleg: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "debug_dogleg");
+  return engine_debug_dogleg(g->engine, h_gn, ca, cg, with_fail != 0, grid, j0, j1, scalars, states_out, backup_out,
+                             g->err);
+}
+
+int sim3opt_dogleg_rule(const double scalars[6], double delta, double model[3], double trial[4], int32_t* step) {
+  if (!scalars || !model || !trial || !step) return SIM3OPT_ERR_ARG;
+  engine_dogleg_rule(scalars, delta, model, trial, step);
+  return SIM3OPT_OK;
+}
+
+int sim3opt_debug_column_vectors(sim3opt_graph* g, int32_t kernel, int32_t grid, int64_t n, int32_t K, const int64_t* at,
+                                 int32_t system, const double* a, const double* b, int32_t first, int32_t count,
+                                 int32_t col, const int32_t* rows, int32_t n_blocks, double* out) {
+  if (!g) return SIM3OPT_ERR_ARG;
+  if (!out) return fail(g, SIM3OPT_ERR_ARG, "debug_column_vectors: null output");
+  if (!g->initialized || g->dirty)
+    return fail(g, SIM3OPT_ERR_STATE, "debug_column_vectors: call sim3opt_initialize first");
+  REFUSE_RANKS(g, "debug_column_vectors");
+  return engine_debug_column_vectors(g->engine, kernel, grid, n, K, at, system, a, b, first, count, col, rows, n_blocks,
+                                     out, g->err);
+}
+
 int sim3opt_debug_factor_dims(sim3opt_graph* g, int32_t context, int32_t* n_block_rows, int64_t* n_blocks_L,
                               int64_t* n_blocks) {
   if (!g) return SIM3OPT_ERR_ARG;

@@ -74,6 +74,15 @@ int engine_debug_linearization(Engine* e, double* J, double* w, int32_t* active,
                                double* maxdiag, std::string& err);
 int engine_debug_update(Engine* e, const double* x, double lambda, bool with_fail, int32_t grid, double* states_out,
                         double* backup_out, double* chi2, double* scale, std::string& err);
+// diagnostic read-outs of the dogleg's launches (engine_algorithms.hip) and of the column kernels (engine_columns.hip)
+int engine_debug_dogleg(Engine* e, const double* h_gn, double ca, double cg, bool with_fail, int32_t grid, int64_t j0,
+                        int64_t j1, double* scalars, double* states_out, double* backup_out, std::string& err);
+int engine_debug_column_vectors(Engine* e, int32_t op, int32_t grid, int64_t n, int32_t K, const int64_t* at,
+                                int32_t sys, const double* a, const double* b, int32_t first, int32_t count,
+                                int32_t col, const int32_t* rows, int32_t n_blocks, double* out, std::string& err);
+// the dogleg's step rule (dogleg_rule.hpp; host only, no engine): scalars in the order of DL_*; model = {alpha, norm_sd,
+// norm_gn}, trial = {ca, cg, norm_dl, linearGain}, *step = SIM3OPT_STEP_*
+void engine_dogleg_rule(const double scalars[6], double delta, double model[3], double trial[4], int32_t* step);
 // diagnostic read-out of the exact block Cholesky, its solve and the selected inversion (engine_direct.hip)
 int engine_debug_factor_dims(Engine* e, int32_t context, int32_t* nb, int64_t* nL, int64_t* nnzb, std::string& err);
 int engine_debug_factor(Engine* e, int32_t context, double lambda, const double* vals, const double* b, bool with_solve,

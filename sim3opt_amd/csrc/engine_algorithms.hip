@@ -2,6 +2,7 @@
 // and OptimizationAlgorithmDogleg behind SparseOptimizer::setAlgorithm), on the engine's linearisation, solvers and
 // chi2.  Engine::optimize hands options.algorithm = 1 / 2 here.  The rules are written out in DESIGN.md 5h.
 #include "engine_impl.hpp"
+#include "dogleg_rule.hpp"
 
 namespace sim3opt {
 
@@ -70,7 +71,7 @@ int Engine::optimize_gauss_newton(int32_t max_iters, std::vector<sim3opt_iter_st
 // d_dl[DL_OUT + DL_*] <- b.b, b^T H b, g.g, b.g, (Hb).g, g^T H g for b = d_b, g = h_gn = d_x.  Both vectors are whole on
 // every rank here (b all-gathered after the linearisation, h_gn by the PCG), so the SpMVs of this rank's rows need
 // no further exchange; the scalars of the ranks' rows are summed by one all-reduce.
-int Engine::dogleg_dots(std::string& err) {
+int Engine::dogleg_dots(std::string& err, int grid, int64_t j0, int64_t j1) {
   const int gs = spmv_grid();
   double* out = d_dl + 4 * MAX_GRID + DL_OUT;
   // q = H b (lambda = 0): its v.q partials are b^T H b
@@ -78,8 +79,12 @@ int Engine::dogleg_dots(std::string& err) {
   hipLaunchKernelGGL(k_dl_sum, dim3(1), dim3(WG), 0, stream, (const double*)d_part_a, gs, out + DL_BHB);
   // H h_gn into the PCG's (now unused) direction vector: its v.q partials are h_gn^T H h_gn
   spmv_raw(0.0, d_x, d_p, nullptr, nullptr);
-  const int gd = grid_for(7 * (int64_t)(r1 - r0), WG);
-  hipLaunchKernelGGL(k_dl_dots, dim3(gd), dim3(WG), 0, stream, 7 * r0, 7 * r1, (const double*)d_b,
+  if (j1 < 0) {  // this rank's rows
+    j0 = 7 * (int64_t)r0;
+    j1 = 7 * (int64_t)r1;
+  }
+  const int gd = grid > 0 ? grid : grid_for(7 * (int64_t)(r1 - r0), WG);
+  hipLaunchKernelGGL(k_dl_dots, dim3(gd), dim3(WG), 0, stream, (int)j0, (int)j1, (const double*)d_b,
                      (const double*)d_x, (const double*)d_q, d_dl);
   hipLaunchKernelGGL(k_dl_final, dim3(1), dim3(WG), 0, stream, (const double*)d_dl, gd, (const double*)d_part_a, gs,
                      out);
@@ -88,7 +93,8 @@ int Engine::dogleg_dots(std::string& err) {
   return SIM3OPT_OK;
 }
 
-int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
+// the dogleg's buffers, allocated at their first use (an optimize() with options.algorithm = 2, or the read-out)
+int Engine::dogleg_alloc(std::string& err) {
   if (!d_dl) {
     HIPCHK(mem.alloc(d_dl, 4 * MAX_GRID + DL_OUT + 8, nullptr));
   }
@@ -99,6 +105,104 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
     err = "dogleg: the SpMV's launch state is missing";
     return SIM3OPT_ERR_STATE;
   }
+  return SIM3OPT_OK;
+}
+
+// one trial's update: backup <- S, S <- exp(ca b + cg h_gn) S on the free vertices (k_dogleg_oplus)
+void Engine::dogleg_step(double ca, double cg) {
+  hipLaunchKernelGGL(k_dogleg_oplus, dim3((nv + WG - 1) / WG), dim3(WG), 0, stream, nv, (const int32_t*)d_hidx,
+                     (const double*)d_b, (const double*)d_x, ca, cg, d_states, mopts(),
+                     use_direct ? (const DevScalars*)d_sc : nullptr, d_backup, fail_token);
+}
+
+// ---- diagnostic read-out of the dogleg's launches (include/sim3opt.h, "Diagnostic."; tests/test_gpu_dogleg_operators.py)
+int Engine::debug_dogleg(const double* h_gn, double ca, double cg, bool with_fail, int32_t grid, int64_t j0, int64_t j1,
+                         double* scalars, double* states_out, double* backup_out, std::string& err) {
+  if (comm.active()) {
+    err = "debug_dogleg: a partitioned graph holds this rank's share only (one GPU, please)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (!linearized) {
+    err = "debug_dogleg: call sim3opt_linearize (or optimize) first: the model needs H and b";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (with_fail && !use_direct) {
+    err = "debug_dogleg: with_fail needs the exact solver (only its failure token reaches k_dogleg_oplus)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (grid < 0 || grid > MAX_GRID) {
+    err = "debug_dogleg: grid out of range";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (j0 < 0 || j0 > j1 || j1 > (int64_t)n) {
+    err = "debug_dogleg: entry range out of bounds (0 <= j0 <= j1 <= 7 x block rows)";
+    return SIM3OPT_ERR_ARG;
+  }
+  int rc = dogleg_alloc(err);
+  if (rc) return rc;
+  // everything these launches overwrite that a later call could see
+  SolverSnapshot snap;
+  rc = snap.take(*this, err, true);
+  if (rc) return rc;
+  const bool whole = j0 == 0 && j1 == 0;
+  bool pushed = false;
+  double six[6] = {0, 0, 0, 0, 0, 0};
+  auto body = [&]() -> int {
+    // h_gn where the solve leaves its solution
+    HIPCHK(hipMemcpy(d_x, h_gn, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    if (with_fail) {
+      const int32_t token = fail_token;  // what the factorisation of the current solve stores on a bad pivot
+      HIPCHK(hipMemcpy(&d_sc->fail, &token, sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    if (scalars) {  // the launches and the read of an iteration after its solve (optimize_dogleg)
+      const int rc2 = whole ? dogleg_dots(err, grid) : dogleg_dots(err, grid, j0, j1);
+      if (rc2) return rc2;
+      HIPCHK(hipMemcpyAsync(h_dl, d_dl + 4 * MAX_GRID + DL_OUT, sizeof(double) * 6, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      for (int k = 0; k < 6; ++k) six[k] = h_dl[k];
+    }
+    if (states_out || backup_out) {  // ... and of a trial
+      pushed = true;
+      dogleg_step(ca, cg);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(stream));
+      if (states_out) HIPCHK(hipMemcpy(states_out, d_states, sizeof(Sim3) * (size_t)nv, hipMemcpyDeviceToHost));
+      if (backup_out) HIPCHK(hipMemcpy(backup_out, d_backup, sizeof(Sim3) * (size_t)nv, hipMemcpyDeviceToHost));
+    }
+    return SIM3OPT_OK;
+  };
+  rc = body();
+  if (pushed) pop_states();  // (the backup was taken whatever followed it)
+  rc = snap.put_back(rc, err);
+  if (rc) return rc;
+  if (scalars)
+    for (int k = 0; k < 6; ++k) scalars[k] = six[k];
+  return SIM3OPT_OK;
+}
+
+int engine_debug_dogleg(Engine* e, const double* h_gn, double ca, double cg, bool with_fail, int32_t grid, int64_t j0,
+                        int64_t j1, double* scalars, double* states_out, double* backup_out, std::string& err) {
+  return e->debug_dogleg(h_gn, ca, cg, with_fail, grid, j0, j1, scalars, states_out, backup_out, err);
+}
+
+// the step rule on the host (sim3opt_dogleg_rule): the functions optimize_dogleg calls, in this translation unit
+void engine_dogleg_rule(const double scalars[6], double delta, double model[3], double trial[4], int32_t* step) {
+  const DoglegScalars S{scalars[DL_BB], scalars[DL_BHB], scalars[DL_GG], scalars[DL_BG], scalars[DL_HBG], scalars[DL_GHG]};
+  const DoglegModel M = dogleg_model(S);
+  const DoglegTrial D = dogleg_trial(S, M, delta);
+  model[0] = M.alpha;
+  model[1] = M.norm_sd;
+  model[2] = M.norm_gn;
+  trial[0] = D.ca;
+  trial[1] = D.cg;
+  trial[2] = D.norm_dl;
+  trial[3] = D.linear_gain;
+  *step = D.step;
+}
+
+int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& stats, std::string& err) {
+  const int rc0 = dogleg_alloc(err);
+  if (rc0) return rc0;
   const double* d_out = d_dl + 4 * MAX_GRID + DL_OUT;
   // g2o's state at iteration 0 of a (non-online) optimize()
   double delta = opt.dl_delta_init, lam_c = opt.dl_lambda_init;
@@ -165,48 +269,22 @@ int Engine::optimize_dogleg(int32_t max_iters, std::vector<sim3opt_iter_stats>& 
       return fail_iteration(it, T, currentChi, stats,
                             "optimize: dogleg: the damped linear solve still failed at lambda 1e3", err);
     }
-    const double bb = h_dl[DL_BB], bHb = h_dl[DL_BHB], gg = h_dl[DL_GG], bg = h_dl[DL_BG], hbg = h_dl[DL_HBG],
-                 gHg = h_dl[DL_GHG];
-    const double alpha = bb / bHb;  // h_sd = alpha b
-    const double hsd_norm = std::fabs(alpha) * std::sqrt(bb), hgn_norm = std::sqrt(gg);
-    R.alpha = alpha;
-    R.norm_sd = hsd_norm;
-    R.norm_gn = hgn_norm;
+    const DoglegScalars S{h_dl[DL_BB], h_dl[DL_BHB], h_dl[DL_GG], h_dl[DL_BG], h_dl[DL_HBG], h_dl[DL_GHG]};
+    const DoglegModel M = dogleg_model(S);  // h_sd = alpha b
+    R.alpha = M.alpha;
+    R.norm_sd = M.norm_sd;
+    R.norm_gn = M.norm_gn;
     int tries = 0;
     bool good = false;
     double rho = 0.0;
     do {
       ++tries;
       if (phase_timing) HIPCHK(hipEventRecord(ev_ph[1], stream));
-      double ca = 0.0, cg = 0.0;  // h_dl = ca b + cg h_gn
-      if (hgn_norm < delta) {
-        cg = 1.0;
-        R.step = SIM3OPT_STEP_GN;
-      } else if (hsd_norm > delta) {
-        ca = delta / hsd_norm * alpha;
-        R.step = SIM3OPT_STEP_SD;
-      } else {
-        // h_sd + beta (h_gn - h_sd), ||.|| = delta; g2o's two numerically stable forms of the root
-        const double hsd2 = alpha * alpha * bb;
-        const double c = alpha * bg - hsd2;                  // h_sd . (h_gn - h_sd)
-        const double bma2 = gg - 2.0 * alpha * bg + hsd2;    // ||h_gn - h_sd||^2
-        const double d2 = delta * delta - hsd2;
-        double beta;
-        if (c <= 0.0) beta = (-c + std::sqrt(c * c + bma2 * d2)) / bma2;
-        else beta = d2 / (c + std::sqrt(c * c + bma2 * d2));
-        ca = (1.0 - beta) * alpha;
-        cg = beta;
-        R.step = SIM3OPT_STEP_DL;
-      }
-      // ||h_dl||^2, b.h_dl and h_dl^T H h_dl as quadratic forms in (ca, cg)
-      const double dl2 = ca * ca * bb + 2.0 * ca * cg * bg + cg * cg * gg;
-      const double bh = ca * bb + cg * bg;
-      const double hHh = ca * ca * bHb + 2.0 * ca * cg * hbg + cg * cg * gHg;
-      double linearGain = 2.0 * bh - hHh;
-      R.norm_dl = std::sqrt(std::max(0.0, dl2));
-      hipLaunchKernelGGL(k_dogleg_oplus, dim3((nv + WG - 1) / WG), dim3(WG), 0, stream, nv, (const int32_t*)d_hidx,
-                         (const double*)d_b, (const double*)d_x, ca, cg, d_states, mopts(),
-                         use_direct ? (const DevScalars*)d_sc : nullptr, d_backup, fail_token);
+      const DoglegTrial D = dogleg_trial(S, M, delta);  // h_dl = ca b + cg h_gn (dogleg_rule.hpp)
+      double linearGain = D.linear_gain;
+      R.step = D.step;
+      R.norm_dl = D.norm_dl;
+      dogleg_step(D.ca, D.cg);
       HIPCHK(hipGetLastError());
       double newChi = 0.0;
       rc = chi2(&newChi, err, phase_timing ? ev_ph[3] : nullptr);

@@ -303,6 +303,122 @@ int Engine::cov_blocks_columns(const std::string& pre, bool fixed_zero, double l
   return SIM3OPT_OK;
 }
 
+// ---- diagnostic read-out of the four kernels above (include/sim3opt.h, "Diagnostic."; tests/test_gpu_column_vectors.py) ----
+// One kernel per call, on the caller's data staged in the c_* buffers a column solve uses, at a length nvec <= 7 nb of
+// the caller's choice (the kernels take any length; a solve passes 7 nb).  `out` is read and written: what it holds on
+// entry is what the kernel's output buffer holds before the launch.  Every index the kernels dereference is checked
+// here first.
+int Engine::debug_column_vectors(int32_t op, int32_t grid, int64_t nvec, int32_t K, const int64_t* at, int32_t sys,
+                                 const double* a, const double* b, int32_t first, int32_t count, int32_t col,
+                                 const int32_t* rows, int32_t n_blocks, double* out, std::string& err) {
+  const std::string pre = "debug_column_vectors: ";
+  if (comm.world > 1) {
+    err = pre + "one GPU only (the graph is partitioned over ranks)";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (use_direct) {
+    err = pre + "the column kernels belong to a graph initialised on the PCG path (linear_solver = 0); this one "
+          "factorises exactly";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (!linearized) {
+    err = pre + "call sim3opt_linearize (or optimize) first";
+    return SIM3OPT_ERR_STATE;
+  }
+  if (grid < 0 || grid > MAX_GRID) {
+    err = pre + "grid out of range";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (op < 0 || op > 3 || !out) {
+    err = pre + "unknown kernel or null output";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (nvec < 1 || nvec > (int64_t)n) {
+    err = pre + "vector length out of range (1 .. 7 x block rows)";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (op == 0) {
+    if (K < 1 || K > KB || !at) {
+      err = pre + "k_cols_rhs takes 1 .. 4 systems and their unit entries";
+      return SIM3OPT_ERR_ARG;
+    }
+    for (int s = 0; s < K; ++s)
+      if (at[s] >= nvec) {
+        err = pre + "unit entry past the end of the vector";
+        return SIM3OPT_ERR_ARG;
+      }
+  } else if (sys < 0 || sys >= KB || !a || (op == 1 && !b)) {
+    err = pre + "system index out of range or null input";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (op == 3) {
+    if (first < 0 || count < 0 || n_blocks < 1 || (int64_t)first + count > n_blocks || col < 0 || col > 6 || !rows) {
+      err = pre + "k_cols_gather: blocks [first, first + count) must lie in the output, col in 0 .. 6";
+      return SIM3OPT_ERR_ARG;
+    }
+    for (int32_t k = first; k < first + count; ++k)
+      if (rows[k] < 0 || (int64_t)7 * rows[k] + 7 > nvec) {
+        err = pre + "k_cols_gather: a row past the end of the vector";
+        return SIM3OPT_ERR_ARG;
+      }
+  }
+  int rc = cols_alloc(err);
+  if (rc) return rc;
+  SolverSnapshot snap;
+  if ((rc = snap.take(*this, err))) return rc;
+  DevBuf<int32_t> d_rows;  // (they go after the put-back's synchronisation)
+  DevBuf<double> d_blocks;
+  auto body = [&]() -> int {
+    const int ge = grid > 0 ? grid : grid_for(nvec / 2, WG);
+    const size_t vb = sizeof(double) * (size_t)nvec, sb = sizeof(double) * (size_t)c_vs, o = (size_t)sys * c_vs;
+    if (op == 0) {
+      HIPCHK(hipMemcpy(c_g, out, sb * K, hipMemcpyHostToDevice));
+      ColUnits u;
+      for (int s = 0; s < KB; ++s) u.at[s] = s < K ? at[s] : -1;
+      BATCH_DISPATCH(K, hipLaunchKernelGGL((k_cols_rhs<KS>), dim3(ge), dim3(WG), 0, stream, nvec, c_vs, c_g, u));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(stream));
+      HIPCHK(hipMemcpy(out, c_g, sb * K, hipMemcpyDeviceToHost));
+    } else if (op == 1) {  // (q staged in c_d, which no kernel of this call reads otherwise; a column solve passes d_q)
+      HIPCHK(hipMemcpy(c_g + o, a, vb, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(c_d + o, b, vb, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(c_r + o, out, sb, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(k_cols_residual, dim3(ge), dim3(WG), 0, stream, nvec, (const double*)(c_g + o),
+                         (const double*)(c_d + o), c_r + o);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(stream));
+      HIPCHK(hipMemcpy(out, c_r + o, sb, hipMemcpyDeviceToHost));
+    } else if (op == 2) {
+      HIPCHK(hipMemcpy(c_d + o, a, vb, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(c_y + o, out, sb, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(k_cols_axpy, dim3(ge), dim3(WG), 0, stream, nvec, (const double*)(c_d + o), c_y + o);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(stream));
+      HIPCHK(hipMemcpy(out, c_y + o, sb, hipMemcpyDeviceToHost));
+    } else {
+      HIPCHK(d_rows.alloc((size_t)n_blocks));
+      HIPCHK(d_blocks.alloc(49 * (size_t)n_blocks));
+      HIPCHK(hipMemcpy(d_rows, rows, sizeof(int32_t) * (size_t)(first + count), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_blocks, out, sizeof(double) * 49 * (size_t)n_blocks, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(c_y + o, a, vb, hipMemcpyHostToDevice));
+      if (count > 0)
+        hipLaunchKernelGGL(k_cols_gather, dim3(grid > 0 ? grid : grid_for(7 * (int64_t)count, WG)), dim3(WG), 0, stream,
+                           first, count, col, (const int32_t*)d_rows, (const double*)(c_y + o), d_blocks.get());
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(stream));
+      HIPCHK(hipMemcpy(out, d_blocks, sizeof(double) * 49 * (size_t)n_blocks, hipMemcpyDeviceToHost));
+    }
+    return SIM3OPT_OK;
+  };
+  return snap.put_back(body(), err);
+}
+
+int engine_debug_column_vectors(Engine* e, int32_t op, int32_t grid, int64_t n, int32_t K, const int64_t* at,
+                                int32_t sys, const double* a, const double* b, int32_t first, int32_t count,
+                                int32_t col, const int32_t* rows, int32_t n_blocks, double* out, std::string& err) {
+  return e->debug_column_vectors(op, grid, n, K, at, sys, a, b, first, count, col, rows, n_blocks, out, err);
+}
+
 void engine_covariance_columns_stats(const Engine* e, int64_t counts[5], double res[2], int32_t* failed_vertex) {
   for (int k = 0; k < 5; ++k) counts[k] = e->col_counts[k];
   res[0] = e->col_res[0];

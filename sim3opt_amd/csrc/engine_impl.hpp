@@ -684,22 +684,37 @@ class Engine {
                      const char* why, std::string& err);
   // the six per-iteration scalars of the dogleg model from b (d_b) and h_gn (d_x): two SpMVs with lambda = 0 and
   // one fused dot kernel, all-reduced over the ranks; left on the device in d_dl (no host round trip here)
-  int dogleg_dots(std::string& err);
+  // grid > 0: that many workgroups (= partials per dot) for k_dl_dots instead of the rule's; j1 >= 0: its entries
+  // [j0, j1) instead of this rank's rows' (both for sim3opt_debug_dogleg only)
+  int dogleg_dots(std::string& err, int grid = 0, int64_t j0 = 0, int64_t j1 = -1);
+  int dogleg_alloc(std::string& err);       // d_dl / h_dl at their first use; refuses without the SpMV's launch state
+  void dogleg_step(double ca, double cg);   // k_dogleg_oplus: backup <- S, S <- exp(ca b + cg h_gn) S
+  // Diagnostic (sim3opt_debug_dogleg): the launches of a dogleg iteration after its solve on a caller's h_gn
+  int debug_dogleg(const double* h_gn, double ca, double cg, bool with_fail, int32_t grid, int64_t j0, int64_t j1,
+                   double* scalars, double* states_out, double* backup_out, std::string& err);
+  // Diagnostic (sim3opt_debug_column_vectors): one of the four column kernels on a caller's data (engine_columns.hip)
+  int debug_column_vectors(int32_t op, int32_t grid, int64_t nvec, int32_t K, const int64_t* at, int32_t sys,
+                           const double* a, const double* b, int32_t first, int32_t count, int32_t col,
+                           const int32_t* rows, int32_t n_blocks, double* out, std::string& err);
   std::vector<sim3opt_tr_stats> tr_stats;  // per iteration of the last dogleg run
-  double* d_dl = nullptr;  // dogleg: 4 x MAX_GRID dot partials, then the 8 scalars (DL_OUT)
+  double* d_dl = nullptr;  // dogleg: 4 x MAX_GRID dot partials, then the 8 scalars (DL_OUT), DL_DOUBLES in all
   double* h_dl = nullptr;  // pinned copy of the scalars
 };
+constexpr size_t DL_DOUBLES = 4 * MAX_GRID + 16;
 
 // What a read-out that runs the solver's own launches puts back, so that the next solve or optimize() is the one
 // without it: the one-system scalars on the device and in h_sc, the batch's KB scalars on both sides once the batch
 // exists, and the host's counters and caches -- kt, sched_stats, spmv_work_seen, last_true_rel, last_capped, chi_known,
-// chi_cache.  (engine_pcg.hip)
+// chi_cache.  With `vectors` also what the dogleg's launches write outside the scalars: d_x, d_p, d_q, the SpMV's
+// partials d_part_a and, once allocated, d_dl (a solve rewrites the first four before it reads them; the read-out
+// that stages a caller's h_gn in d_x puts them back all the same).  (engine_pcg.hip)
 struct SolverSnapshot {
-  int take(Engine& e, std::string& err);  // synchronises the stream first
+  int take(Engine& e, std::string& err, bool vectors = false);  // synchronises the stream first
+  DevBuf<double> vec;  // the saved vectors, in the order above
   // rc: what happened in between; returned unless it was fine and the restoring failed
   int put_back(int rc, std::string& err);
   Engine* eng = nullptr;
-  bool batch = false;
+  bool batch = false, has_dl = false;
   DevScalars d_one, h_one, d_batch[KB], h_batch[KB];
   sim3opt_kernel_times kt;
   int64_t sched[4];

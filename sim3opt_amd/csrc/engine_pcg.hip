@@ -824,9 +824,22 @@ int Engine::lm_trial_solve(int q, double lambda, double ni, const double** x, in
 }
 
 // ---- diagnostic read-outs (see engine_impl.hpp) ----
-int SolverSnapshot::take(Engine& e, std::string& err) {
+int SolverSnapshot::take(Engine& e, std::string& err, bool vectors) {
   eng = &e;
   HIPCHK(hipStreamSynchronize(e.stream));
+  if (vectors) {
+    const size_t nn = (size_t)e.n;
+    HIPCHK(vec.alloc(3 * nn + SPAN_GRID_MAX + DL_DOUBLES));
+    const size_t vb = sizeof(double) * nn;
+    HIPCHK(hipMemcpy(vec, e.d_x, vb, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(vec + nn, e.d_p, vb, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(vec + 2 * nn, e.d_q, vb, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(vec + 3 * nn, e.d_part_a, sizeof(double) * SPAN_GRID_MAX, hipMemcpyDeviceToDevice));
+    if (e.d_dl)
+      HIPCHK(hipMemcpy(vec + 3 * nn + SPAN_GRID_MAX, e.d_dl, sizeof(double) * DL_DOUBLES, hipMemcpyDeviceToDevice));
+    has_dl = e.d_dl != nullptr;
+    HIPCHK(hipDeviceSynchronize());  // (device-to-device copies may return before they are done)
+  }
   h_one = *e.h_sc;
   HIPCHK(hipMemcpy(&d_one, e.d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
   batch = e.batch_ready;
@@ -852,6 +865,17 @@ int SolverSnapshot::put_back(int rc, std::string& err) {
   if (batch) {
     ok = ok && hipMemcpy(e.d_bsc, d_batch, sizeof(d_batch), hipMemcpyHostToDevice) == hipSuccess;
     std::memcpy(e.h_bsc, h_batch, sizeof(h_batch));
+  }
+  if (vec.get()) {
+    const size_t nn = (size_t)e.n, vb = sizeof(double) * nn;
+    ok = ok && hipMemcpy(e.d_x, vec, vb, hipMemcpyDeviceToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(e.d_p, vec + nn, vb, hipMemcpyDeviceToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(e.d_q, vec + 2 * nn, vb, hipMemcpyDeviceToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(e.d_part_a, vec + 3 * nn, sizeof(double) * SPAN_GRID_MAX, hipMemcpyDeviceToDevice) == hipSuccess;
+    if (has_dl)
+      ok = ok && hipMemcpy(e.d_dl, vec + 3 * nn + SPAN_GRID_MAX, sizeof(double) * DL_DOUBLES, hipMemcpyDeviceToDevice) ==
+                     hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;  // (device-to-device copies may return before they are done)
   }
   e.kt = kt;
   std::memcpy(e.sched_stats, sched, sizeof(sched));

@@ -246,6 +246,12 @@ SYMBOLS = {
     "sim3opt_debug_linearization_dims": (C.c_int, [_vp, _ip, _ip]),
     "sim3opt_debug_linearization": (C.c_int, [_vp, _dp, _dp, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp, _dp]),
     "sim3opt_debug_update": (C.c_int, [_vp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "sim3opt_debug_dogleg": (C.c_int, [_vp, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                       _dp, _dp, _dp]),
+    "sim3opt_dogleg_rule": (C.c_int, [_dp, C.c_double, _dp, _dp, _ip]),
+    "sim3opt_debug_column_vectors": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64),
+                                               C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _ip, C.c_int32,
+                                               _dp]),
     "sim3opt_debug_factor_dims": (C.c_int, [_vp, C.c_int32, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sim3opt_debug_factor": (C.c_int, [_vp, C.c_int32, C.c_double, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
                                        _dp, _dp, _dp, _ip, _dp, _ip, _ip, _ip]),
@@ -876,6 +882,62 @@ class Graph:
                                                _p(st, _dp), _p(bk, _dp), C.byref(chi), C.byref(sc)))
         return st, bk, chi.value, sc.value
 
+    def debug_dogleg(self, h_gn, ca=0.0, cg=1.0, fail=False, grid=0, j0=0, j1=0, scalars=True, states=True):
+        """Diagnostic: the launches of a dogleg iteration after its solve, on a caller's h_gn (7 per block row).  Returns
+        (scalars, states, backup): the six scalars b.b, b^T H b, g.g, b.g, (Hb).g, g^T H g (None without `scalars`) and
+        the estimates / the backup after k_dogleg_oplus with h_dl = ca b + cg h_gn (None without `states`); the
+        estimates are restored.  grid: workgroups of k_dl_dots (0: its own); [j0, j1): the entries its dots run over
+        (both 0: all); fail: with the exact solver's failure token set."""
+        nb, _ = self.system_dims()
+        xs = _f64(h_gn).reshape(-1) if h_gn is not None else None
+        assert xs is None or xs.shape[0] == 7 * nb
+        nv = self.num_vertices
+        sc = np.empty(6) if scalars else None
+        st = np.empty((nv, 8)) if states else None
+        bk = np.empty((nv, 8)) if states else None
+        self._chk(self._L.sim3opt_debug_dogleg(self._g, _p(xs, _dp), float(ca), float(cg), int(bool(fail)), int(grid),
+                                               int(j0), int(j1), _p(sc, _dp), _p(st, _dp), _p(bk, _dp)))
+        return sc, st, bk
+
+    def column_vector_stride(self):
+        """Doubles between the systems' vectors of a column solve: 7 x block rows, rounded up to a multiple of 64."""
+        nb, _ = self.system_dims()
+        return (7 * nb + 63) // 64 * 64
+
+    def debug_column_vectors(self, kernel, n, out, grid=0, at=None, system=0, a=None, b=None, first=0, count=0, col=0,
+                             rows=None):
+        """Diagnostic: one vector kernel of the columns of the inverse on the caller's data at vector length n; returns
+        the output buffer after the launch, `out` being what it held before (never modified).  kernel "rhs": at (K,)
+        unit entries, out (K, vs); "residual": a - b on system `system`, out (vs,); "axpy": y += a, out (vs,) holding y;
+        "gather": column col of blocks first .. first + count - 1 of out (n_blocks, 49) from a = y at block rows
+        rows[first .. first + count).  vs = column_vector_stride(); grid: workgroups, 0 = a solve's."""
+        op = ("rhs", "residual", "axpy", "gather").index(kernel) if isinstance(kernel, str) else int(kernel)
+        o = _f64(out).copy() if out is not None else None
+        vs = self.column_vector_stride()
+        K = 0
+        at64 = None
+        if at is not None:
+            at64 = np.ascontiguousarray(at, dtype=np.int64).reshape(-1)
+            K = at64.shape[0]
+        if o is not None:
+            if op == 0:
+                assert o.shape == (K, vs)
+            elif op in (1, 2):
+                assert o.shape == (vs,)
+            elif op == 3:
+                assert o.ndim == 2 and o.shape[1] == 49
+        av = _f64(a).reshape(-1) if a is not None else None
+        bv = _f64(b).reshape(-1) if b is not None else None
+        assert av is None or av.shape[0] == n
+        assert bv is None or bv.shape[0] == n
+        rw = _i32(rows).reshape(-1) if rows is not None else None
+        assert rw is None or rw.shape[0] >= first + count
+        nblk = o.shape[0] if (o is not None and op == 3) else 0
+        self._chk(self._L.sim3opt_debug_column_vectors(
+            self._g, op, int(grid), int(n), K, _p(at64, C.POINTER(C.c_int64)), int(system), _p(av, _dp), _p(bv, _dp),
+            int(first), int(count), int(col), _p(rw, _ip), int(nblk), _p(o, _dp)))
+        return o
+
     def debug_factor(self, context=0, lam=0.0, vals=None, b=None, solve=True, selinv=False):
         """Diagnostic: the exact block Cholesky of context 0 (the LM's solver) or 1 (the marginals') on the last
         linearisation, or on injected vals (nnzb, 7, 7) [k, r, c] / b (7 nb), read out as a dict in the plan's
@@ -1279,6 +1341,20 @@ def edge_jacobian_host(meas, s0, s1, **opts):
     if rc != OK:
         raise Sim3OptError(rc, "sim3_edge_jacobian: bad state (non-finite, scale <= 0) or fix_small_angle_b != 1")
     return e, J
+
+
+def dogleg_rule(scalars, delta):
+    """sim3opt_dogleg_rule: the dogleg's step rule on the host, the function optimize() calls per trial.  scalars = (b.b,
+    b^T H b, g.g, b.g, (Hb).g, g^T H g) for g = h_gn; returns a dict of alpha, norm_sd, norm_gn, ca, cg, norm_dl,
+    linear_gain and step (1 steepest descent, 2 Gauss-Newton, 3 dogleg) for h_dl = ca b + cg h_gn."""
+    s = _f64(scalars).reshape(-1)
+    assert s.shape == (6,)
+    m, t, st = np.empty(3), np.empty(4), C.c_int32()
+    rc = load().sim3opt_dogleg_rule(_p(s, _dp), float(delta), _p(m, _dp), _p(t, _dp), C.byref(st))
+    if rc != OK:
+        raise Sim3OptError(rc, "dogleg_rule: null argument")
+    return dict(alpha=float(m[0]), norm_sd=float(m[1]), norm_gn=float(m[2]), ca=float(t[0]), cg=float(t[1]),
+                norm_dl=float(t[2]), linear_gain=float(t[3]), step=int(st.value))
 
 
 def read_keyframe_bin(path):

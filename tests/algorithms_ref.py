@@ -110,3 +110,61 @@ def dogleg(OG, iters, opt, delta_init=1e4, max_trials=100, lambda_init=1e-7, lam
         if not good:
             break
     return len(out), out
+
+
+# ---------------------------------------------------------------------------------------------- the dogleg's operators
+# Restatements for tests/test_gpu_dogleg_operators.py and tests/test_dogleg_rule.py (dtype-generic, np.longdouble the
+# reference): the six scalars of an iteration with their magnitudes, and the step rule of DESIGN.md 5h.
+LD = np.longdouble
+
+
+def dogleg_scalars(rowptr, colidx, blocks, b, g, j0=None, j1=None, dt=LD):
+    """(values, magnitudes), six each in the device's order: b.b, b^T H b, g.g, b.g, (Hb).g, g^T H g.  The four dots
+    of k_dl_dots (b.b, g.g, b.g, (Hb).g) run over the entries [j0, j1), the two quadratic forms over every row; a
+    magnitude is the same sum with every term replaced by its absolute value (sum |v_i| |H_ij| |w_j|)."""
+    import pcg_ref as P
+    b, g = np.asarray(b, dtype=dt), np.asarray(g, dtype=dt)
+    j0 = 0 if j0 is None else j0
+    j1 = b.shape[0] if j1 is None else j1
+    (Hb, Hg), (Mb, Mg) = P.bcsr_apply(rowptr, colidx, blocks, 0.0, np.stack([b, g]), dt)
+    r = slice(j0, j1)
+    ab, ag = np.abs(b), np.abs(g)
+    val = [(b[r] * b[r]).sum(), (b * Hb).sum(), (g[r] * g[r]).sum(), (b[r] * g[r]).sum(), (Hb[r] * g[r]).sum(),
+           (g * Hg).sum()]
+    mag = [(b[r] * b[r]).sum(), (ab * Mb).sum(), (g[r] * g[r]).sum(), (ab[r] * ag[r]).sum(), (Mb[r] * ag[r]).sum(),
+           (ag * Mg).sum()]
+    return np.array(val, dtype=dt), np.array(mag, dtype=dt)
+
+
+def dogleg_rule(s, delta, dt=LD):
+    """The step rule of DESIGN.md 5h, item 4, from the six scalars: dict(alpha, norm_sd, norm_gn, step, ca, cg, beta,
+    c, bma2, d2) for h_dl = ca b + cg h_gn (beta, c, bma2, d2: None unless a dogleg step)."""
+    bb, bHb, gg, bg = (dt(x) for x in s[:4])
+    delta = dt(delta)
+    alpha = bb / bHb
+    nsd, ngn = abs(alpha) * np.sqrt(bb), np.sqrt(gg)
+    out = dict(alpha=alpha, norm_sd=nsd, norm_gn=ngn, beta=None, c=None, bma2=None, d2=None)
+    if ngn < delta:
+        out.update(step=STEP_GN, ca=dt(0), cg=dt(1))
+    elif nsd > delta:
+        out.update(step=STEP_SD, ca=delta / nsd * alpha, cg=dt(0))
+    else:
+        hsd2 = alpha * alpha * bb
+        c = alpha * bg - hsd2
+        bma2 = gg - 2 * alpha * bg + hsd2
+        d2 = delta * delta - hsd2
+        root = np.sqrt(c * c + bma2 * d2)
+        beta = (-c + root) / bma2 if c <= 0 else d2 / (c + root)
+        out.update(step=STEP_DL, ca=(1 - beta) * alpha, cg=beta, beta=beta, c=c, bma2=bma2, d2=d2)
+    return out
+
+
+def dogleg_step_model(s, ca, cg, dt=LD):
+    """(||h_dl||^2, linearGain = 2 b.h - h^T H h) of h = ca b + cg h_gn with their magnitudes, from the six scalars."""
+    bb, bHb, gg, bg, hbg, gHg = (dt(x) for x in s)
+    ca, cg = dt(ca), dt(cg)
+    dl2 = ca * ca * bb + 2 * ca * cg * bg + cg * cg * gg
+    dl2_mag = ca * ca * bb + 2 * abs(ca * cg * bg) + cg * cg * gg
+    gain = 2 * (ca * bb + cg * bg) - (ca * ca * bHb + 2 * ca * cg * hbg + cg * cg * gHg)
+    gain_mag = 2 * (abs(ca) * bb + abs(cg * bg)) + ca * ca * abs(bHb) + 2 * abs(ca * cg * hbg) + cg * cg * abs(gHg)
+    return dl2, dl2_mag, gain, gain_mag
