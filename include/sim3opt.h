@@ -966,6 +966,28 @@ int sim3opt_ba_batch_get_lambda_init(const sim3opt_ba_batch* b, double* lambda_i
  * SIM3OPT_ERR_STATE before the first optimize. */
 int sim3opt_ba_batch_get_chi2(const sim3opt_ba_batch* b, double* active_before, double* active_after,
                               double* edge_chi2, int32_t* n_outlier_edges);
+/* Diagnostic read-out of ONE LM trial of every problem, in one launch, at the current estimate (the start before
+ * the first optimize, else its result): the linearisation (pass L), the elimination of the points at the caller's
+ * damping lambda[k] (pass S; n values, any finite number, negative allowed), the 6x6 Cholesky, and the back-
+ * substitution with the trial's chi2 (pass U) -- the device functions sim3opt_ba_batch_optimize runs, not copies of
+ * them.  With dx_c (n x 6, [omega, upsilon]; may be NULL) pass U uses that camera step instead of the Cholesky's, which
+ * is still reported.  Nothing in the solver uses this call and it changes nothing: the estimates, the results of the
+ * last optimize and the handle's device blocks stay; its own device memory is gone when it returns.
+ *   point_rows   (SIM3OPT_BA_BATCH_TRIAL_POINT_ROWS x total, row r of point g at [r * total + g]) the kernel's scratch:
+ *                rows 0-5 H_pp (undamped; xx xy xz yy yz zz), 6-8 b_p, 9-20 A_1 (2 x 6 row-major), 21-26 B_1 (2 x 3),
+ *                27-28 es_1, 29-34 H_pp^-1 (damped; as H_pp), 35-52 Z (6 x 3 row-major), 53-55 the trial point
+ *   problem_rows (n x SIM3OPT_BA_BATCH_TRIAL_PROBLEM_DOUBLES) 0-20 sum A_1^T A_1 (upper triangle, row by row), 21-26
+ *                b_c, 27 the robust chi2, 28 activeChi2, 29 computeLambdaInit's max diag(H) (whatever
+ *                user_lambda_init is), 30-50 - sum Z Y^T, 51-56 - sum Z b_p, 57-77 the damped S, 78-83 g, 84-89 dx_c
+ *                of the Cholesky, 90 fail (1: a non-positive pivot), 91-97 the trial camera 1, 98 the trial's robust
+ *                chi2, 99 x.(lambda x + b) over the points and the camera
+ * A failed trial does what the LM loop does: pass U is skipped, the trial camera is the current one, its chi2 DBL_MAX,
+ * the scale and the trial points 0.  Either output may be NULL, not both.  SIM3OPT_ERR_STATE: no problems set.
+ * SIM3OPT_ERR_ARG with a message: lambda NULL, both outputs NULL, a non-finite lambda or dx_c. */
+#define SIM3OPT_BA_BATCH_TRIAL_POINT_ROWS 56
+#define SIM3OPT_BA_BATCH_TRIAL_PROBLEM_DOUBLES 100
+int sim3opt_ba_batch_debug_trial(sim3opt_ba_batch* b, const double* lambda, const double* dx_c, double* point_rows,
+                                 double* problem_rows);
 
 /* ---- batched PnP RANSAC: the loop detector's start pose, every candidate in one launch ----
  * cv::solvePnPRansac(surfPoints[0], points2, K, dist, rvec, tvec, false, 100, 3, 10, noArray(), CV_ITERATIVE)

@@ -24,6 +24,10 @@
 //                   pass U: dx_p = H_pp^-1 b_p - Z^T dx_c, trial points; sums: robust chi2 of the trial, x.(lambda x + b)
 //                   LmDamping::update (lm_damping.hpp) accepts (the thread copies its trial points) or rejects
 //   at the end      pass F: e->chi2() of every observation, activeChi2, the count above outlier_chi2 (:947-953)
+//
+// The passes are device functions (two_view_pass_L / _S / _U, two_view_reduced_solve, two_view_maxdiag), inlined into
+// k_ba_two_view and into k_ba_two_view_trial, the read-out of ONE trial at a caller's lambda
+// (sim3opt_ba_batch_debug_trial): what a test reads is what the LM loop runs.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -43,12 +47,17 @@ namespace sim3opt_bundle {
 
 constexpr int WGB = 256;                    // threads of a workgroup (four wavefronts)
 constexpr int NWAVE = WGB / 64;
-constexpr int SCR_PER_POINT = 56;           // doubles of scratch per point, see the S_* offsets
+constexpr int SCR_PER_POINT = SIM3OPT_BA_BATCH_TRIAL_POINT_ROWS;  // doubles of scratch per point, see the S_* offsets
 constexpr int STAT_DOUBLES = 5;             // chi2_before, chi2_after, lambda, rho, trials
 constexpr int SUMMARY_DOUBLES = 5;          // iterations run, activeChi2 before / after, outlier edges, lambda_0
 // scratch rows (row r of point g at scr[r * total + g]: consecutive threads, consecutive addresses)
 constexpr int S_HPP = 0, S_BP = 6, S_A1 = 9, S_B1 = 21, S_ES1 = 27, S_HINV = 29, S_Z = 35, S_TRIAL = 53;
-static_assert(S_TRIAL + 3 == SCR_PER_POINT, "scratch layout");
+static_assert(S_TRIAL + 3 == SCR_PER_POINT && SCR_PER_POINT == 56, "scratch layout");
+// the read-out's row of a problem (sim3opt.h, sim3opt_ba_batch_debug_trial)
+constexpr int T_ATA = 0, T_BC = 21, T_CHI = 27, T_ACTIVE = 28, T_MAXDIAG = 29, T_ZY = 30, T_ZB = 51, T_S = 57, T_G = 78,
+              T_DXC = 84, T_FAIL = 90, T_CAM = 91, T_CHI_NEW = 98, T_SCALE = 99;
+constexpr int TRIAL_DOUBLES = SIM3OPT_BA_BATCH_TRIAL_PROBLEM_DOUBLES;
+static_assert(T_SCALE + 1 == TRIAL_DOUBLES && TRIAL_DOUBLES == 100, "read-out layout");
 
 struct TwoViewArgs {
   const int32_t* ptr;     // n_problems + 1
@@ -78,6 +87,198 @@ __device__ __forceinline__ double two_view_rho(const TwoViewArgs& A, const doubl
   return rho;
 }
 
+// ---- pass L: linearise at the estimate A.pts, (c1q, c1t).  The thread's points are p0 + tid, p0 + tid + 256, ...
+// below p0 + n.  acc, summed over the workgroup: 0..20 sum A1^T A1 (upper), 21..26 b_c, 27 robust chi2, 28 activeChi2;
+// dmax: the largest diagonal entry of H_pp among THIS thread's points ----
+__device__ __forceinline__ void two_view_pass_L(const TwoViewArgs& A, int tid, int64_t p0, int n, const double c0q[4],
+                                                const double c0t[3], const double c1q[4], const double c1t[3],
+                                                double (&acc)[29], double& dmax, double* red) {
+  const int64_t T = A.total;
+  double* const scr = A.scr;
+  const double* const pts = A.pts;
+#pragma unroll
+  for (int q = 0; q < 29; ++q) acc[q] = 0.0;
+  dmax = 0.0;
+  for (int i = tid; i < n; i += WGB) {
+    const int64_t g = p0 + i;
+    const double p[3] = {pts[3 * g], pts[3 * g + 1], pts[3 * g + 2]};
+    double R[9], X[3], e[2], rho, w, Jc[12], Jp[6];
+    // camera 0 is fixed: its observation reaches H_pp and b_p only
+    ba_project_residual(c0q, c0t, p, A.uv0[2 * g], A.uv0[2 * g + 1], A.f, A.cx, A.cy, R, X, e);
+    double e2 = A.omega * (e[0] * e[0] + e[1] * e[1]);
+    ba_huber(e2, A.huber, rho, w);
+    acc[27] += rho;
+    acc[28] += e2;
+    double sw = sqrt(w * A.omega);
+    ba_jacobians(R, X, A.f, Jc, Jp);
+    double B[6], es[2] = {sw * e[0], sw * e[1]};
+#pragma unroll
+    for (int q = 0; q < 6; ++q) B[q] = sw * Jp[q];
+    double H[6], b[3];
+    H[0] = B[0] * B[0] + B[3] * B[3];
+    H[1] = B[0] * B[1] + B[3] * B[4];
+    H[2] = B[0] * B[2] + B[3] * B[5];
+    H[3] = B[1] * B[1] + B[4] * B[4];
+    H[4] = B[1] * B[2] + B[4] * B[5];
+    H[5] = B[2] * B[2] + B[5] * B[5];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] = -(B[c] * es[0] + B[3 + c] * es[1]);
+    // camera 1
+    ba_project_residual(c1q, c1t, p, A.uv1[2 * g], A.uv1[2 * g + 1], A.f, A.cx, A.cy, R, X, e);
+    e2 = A.omega * (e[0] * e[0] + e[1] * e[1]);
+    ba_huber(e2, A.huber, rho, w);
+    acc[27] += rho;
+    acc[28] += e2;
+    sw = sqrt(w * A.omega);
+    ba_jacobians(R, X, A.f, Jc, Jp);
+    double A1[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) A1[q] = sw * Jc[q];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) B[q] = sw * Jp[q];
+    es[0] = sw * e[0];
+    es[1] = sw * e[1];
+    H[0] += B[0] * B[0] + B[3] * B[3];
+    H[1] += B[0] * B[1] + B[3] * B[4];
+    H[2] += B[0] * B[2] + B[3] * B[5];
+    H[3] += B[1] * B[1] + B[4] * B[4];
+    H[4] += B[1] * B[2] + B[4] * B[5];
+    H[5] += B[2] * B[2] + B[5] * B[5];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] -= B[c] * es[0] + B[3 + c] * es[1];
+    dmax = fmax(dmax, fmax(H[0], fmax(H[3], H[5])));
+#pragma unroll
+    for (int q = 0; q < 6; ++q) scr[(S_HPP + q) * T + g] = H[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) scr[(S_BP + q) * T + g] = b[q];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) scr[(S_A1 + q) * T + g] = A1[q];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) scr[(S_B1 + q) * T + g] = B[q];
+    scr[(S_ES1 + 0) * T + g] = es[0];
+    scr[(S_ES1 + 1) * T + g] = es[1];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+      for (int c = r; c < 6; ++c) acc[tri6(r, c)] += A1[r] * A1[c] + A1[6 + r] * A1[6 + c];
+      acc[21 + r] -= A1[r] * es[0] + A1[6 + r] * es[1];
+    }
+  }
+  wg_sum(acc, red);
+}
+
+// computeLambdaInit's maximum: the largest diagonal entry of the (undamped) Hessian over the free vertices
+__device__ __forceinline__ double two_view_maxdiag(double dmax, const double (&acc)[29], double* red) {
+  double maxdiag = wg_max(dmax, red);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) maxdiag = fmax(maxdiag, acc[tri6(r, r)]);
+  return maxdiag;
+}
+
+// ---- pass S: eliminate the points at damping lambda, sum the reduced camera system.  sg, summed over the
+// workgroup: 0..20 - sum Z Y^T (upper), 21..26 - sum Z b_p ----
+__device__ __forceinline__ void two_view_pass_S(const TwoViewArgs& A, int tid, int64_t p0, int n, double lambda,
+                                                double (&sg)[27], double* red) {
+  const int64_t T = A.total;
+  double* const scr = A.scr;
+#pragma unroll
+  for (int q = 0; q < 27; ++q) sg[q] = 0.0;
+  for (int i = tid; i < n; i += WGB) {
+    const int64_t g = p0 + i;
+    double H[6], b[3], A1[12], B[6], Hi[9];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) H[q] = scr[(S_HPP + q) * T + g];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) b[q] = scr[(S_BP + q) * T + g];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) A1[q] = scr[(S_A1 + q) * T + g];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) B[q] = scr[(S_B1 + q) * T + g];
+    ba_sym3_inverse(H[0] + lambda, H[1], H[2], H[3] + lambda, H[4], H[5] + lambda, Hi);
+    scr[(S_HINV + 0) * T + g] = Hi[0]; scr[(S_HINV + 1) * T + g] = Hi[1]; scr[(S_HINV + 2) * T + g] = Hi[2];
+    scr[(S_HINV + 3) * T + g] = Hi[4]; scr[(S_HINV + 4) * T + g] = Hi[5]; scr[(S_HINV + 5) * T + g] = Hi[8];
+    double Y[18], Z[18];  // Y = A1^T B1, Z = Y H_pp^-1, 6x3 row-major
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      Y[3 * r] = A1[r] * B[0] + A1[6 + r] * B[3];
+      Y[3 * r + 1] = A1[r] * B[1] + A1[6 + r] * B[4];
+      Y[3 * r + 2] = A1[r] * B[2] + A1[6 + r] * B[5];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        Z[3 * r + c] = Y[3 * r] * Hi[c] + Y[3 * r + 1] * Hi[3 + c] + Y[3 * r + 2] * Hi[6 + c];
+        scr[(S_Z + 3 * r + c) * T + g] = Z[3 * r + c];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+      for (int c = r; c < 6; ++c)
+        sg[tri6(r, c)] -= Z[3 * r] * Y[3 * c] + Z[3 * r + 1] * Y[3 * c + 1] + Z[3 * r + 2] * Y[3 * c + 2];
+      sg[21 + r] -= Z[3 * r] * b[0] + Z[3 * r + 1] * b[1] + Z[3 * r + 2] * b[2];
+    }
+  }
+  wg_sum(sg, red);
+}
+
+// S = lambda I + sum A_1^T A_1 - sum Z Y^T, g = b_c - sum Z b_p, dx_c = S^-1 g by the 6x6 Cholesky; returns `fail`:
+// a non-positive pivot, the trial is rejected
+__device__ __forceinline__ bool two_view_reduced_solve(const double (&acc)[29], const double (&sg)[27], double lambda,
+                                                       double (&Su)[21], double (&gv)[6], double (&dxc)[6]) {
+#pragma unroll
+  for (int q = 0; q < 21; ++q) Su[q] = acc[q] + sg[q];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    Su[tri6(r, r)] += lambda;
+    gv[r] = acc[21 + r] + sg[21 + r];
+  }
+  return !chol6_solve(Su, gv, dxc);
+}
+
+// ---- pass U: back-substitute the camera step dxc, the trial points to the scratch; the trial's robust chi2 with
+// camera 1 at (nq, nt), and scale = x.(lambda x + b) over the points and the camera (b_c = acc[21..26]) ----
+__device__ __forceinline__ void two_view_pass_U(const TwoViewArgs& A, int tid, int64_t p0, int n, double lambda,
+                                                const double (&dxc)[6], const double (&acc)[29], const double c0q[4],
+                                                const double c0t[3], const double nq[4], const double nt[3],
+                                                double& tempChi, double& scale, double* red) {
+  const int64_t T = A.total;
+  double* const scr = A.scr;
+  const double* const pts = A.pts;
+  double tr[2] = {0.0, 0.0};
+  for (int i = tid; i < n; i += WGB) {
+    const int64_t g = p0 + i;
+    double b[3], h[6], d[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) b[q] = scr[(S_BP + q) * T + g];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) h[q] = scr[(S_HINV + q) * T + g];
+    d[0] = h[0] * b[0] + h[1] * b[1] + h[2] * b[2];
+    d[1] = h[1] * b[0] + h[3] * b[1] + h[4] * b[2];
+    d[2] = h[2] * b[0] + h[4] * b[1] + h[5] * b[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) s += scr[(S_Z + 3 * r + c) * T + g] * dxc[r];
+      d[c] -= s;
+    }
+    double pn[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      tr[1] += d[c] * (lambda * d[c] + b[c]);
+      pn[c] = pts[3 * g + c] + d[c];
+      scr[(S_TRIAL + c) * T + g] = pn[c];
+    }
+    double e2;
+    tr[0] += two_view_rho(A, c0q, c0t, pn, A.uv0 + 2 * g, e2);
+    tr[0] += two_view_rho(A, nq, nt, pn, A.uv1 + 2 * g, e2);
+  }
+  wg_sum(tr, red);
+  tempChi = tr[0];
+  scale = tr[1];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) scale += dxc[r] * (lambda * dxc[r] + acc[21 + r]);
+}
+
 __global__ __launch_bounds__(WGB) void k_ba_two_view(TwoViewArgs A) {
   __shared__ double red[NWAVE * 32];
   const int tid = threadIdx.x;
@@ -104,88 +305,15 @@ __global__ __launch_bounds__(WGB) void k_ba_two_view(TwoViewArgs A) {
   int iters = 0;
   double active_before = 0.0, lambda0 = 0.0;
   for (int it = 0; it < A.max_iters && go; ++it) {
-    // ---- pass L: linearise at the estimate ----
-    double acc[29];  // 0..20 sum A1^T A1 (upper), 21..26 b_c, 27 robust chi2, 28 activeChi2
-#pragma unroll
-    for (int q = 0; q < 29; ++q) acc[q] = 0.0;
-    double dmax = 0.0;
-    for (int i = tid; i < n; i += WGB) {
-      const int64_t g = p0 + i;
-      const double p[3] = {pts[3 * g], pts[3 * g + 1], pts[3 * g + 2]};
-      double R[9], X[3], e[2], rho, w, Jc[12], Jp[6];
-      // camera 0 is fixed: its observation reaches H_pp and b_p only
-      ba_project_residual(c0q, c0t, p, A.uv0[2 * g], A.uv0[2 * g + 1], A.f, A.cx, A.cy, R, X, e);
-      double e2 = A.omega * (e[0] * e[0] + e[1] * e[1]);
-      ba_huber(e2, A.huber, rho, w);
-      acc[27] += rho;
-      acc[28] += e2;
-      double sw = sqrt(w * A.omega);
-      ba_jacobians(R, X, A.f, Jc, Jp);
-      double B[6], es[2] = {sw * e[0], sw * e[1]};
-#pragma unroll
-      for (int q = 0; q < 6; ++q) B[q] = sw * Jp[q];
-      double H[6], b[3];
-      H[0] = B[0] * B[0] + B[3] * B[3];
-      H[1] = B[0] * B[1] + B[3] * B[4];
-      H[2] = B[0] * B[2] + B[3] * B[5];
-      H[3] = B[1] * B[1] + B[4] * B[4];
-      H[4] = B[1] * B[2] + B[4] * B[5];
-      H[5] = B[2] * B[2] + B[5] * B[5];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) b[c] = -(B[c] * es[0] + B[3 + c] * es[1]);
-      // camera 1
-      ba_project_residual(c1q, c1t, p, A.uv1[2 * g], A.uv1[2 * g + 1], A.f, A.cx, A.cy, R, X, e);
-      e2 = A.omega * (e[0] * e[0] + e[1] * e[1]);
-      ba_huber(e2, A.huber, rho, w);
-      acc[27] += rho;
-      acc[28] += e2;
-      sw = sqrt(w * A.omega);
-      ba_jacobians(R, X, A.f, Jc, Jp);
-      double A1[12];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) A1[q] = sw * Jc[q];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) B[q] = sw * Jp[q];
-      es[0] = sw * e[0];
-      es[1] = sw * e[1];
-      H[0] += B[0] * B[0] + B[3] * B[3];
-      H[1] += B[0] * B[1] + B[3] * B[4];
-      H[2] += B[0] * B[2] + B[3] * B[5];
-      H[3] += B[1] * B[1] + B[4] * B[4];
-      H[4] += B[1] * B[2] + B[4] * B[5];
-      H[5] += B[2] * B[2] + B[5] * B[5];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) b[c] -= B[c] * es[0] + B[3 + c] * es[1];
-      dmax = fmax(dmax, fmax(H[0], fmax(H[3], H[5])));
-#pragma unroll
-      for (int q = 0; q < 6; ++q) scr[(S_HPP + q) * T + g] = H[q];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) scr[(S_BP + q) * T + g] = b[q];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) scr[(S_A1 + q) * T + g] = A1[q];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) scr[(S_B1 + q) * T + g] = B[q];
-      scr[(S_ES1 + 0) * T + g] = es[0];
-      scr[(S_ES1 + 1) * T + g] = es[1];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-#pragma unroll
-        for (int c = r; c < 6; ++c) acc[tri6(r, c)] += A1[r] * A1[c] + A1[6 + r] * A1[6 + c];
-        acc[21 + r] -= A1[r] * es[0] + A1[6 + r] * es[1];
-      }
-    }
-    wg_sum(acc, red);
+    double acc[29], dmax;
+    two_view_pass_L(A, tid, p0, n, c0q, c0t, c1q, c1t, acc, dmax, red);
     double currentChi = acc[27];
     const double chi2_before = currentChi;
     if (it == 0) {
       active_before = acc[28];
       double maxdiag = 0.0;
-      if (!(A.user_lambda_init > 0)) {
-        // computeLambdaInit: tau * max diagonal entry of the (undamped) Hessian over the free vertices
-        maxdiag = wg_max(dmax, red);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) maxdiag = fmax(maxdiag, acc[tri6(r, r)]);
-      }
+      // computeLambdaInit: tau * max diagonal entry of the (undamped) Hessian over the free vertices
+      if (!(A.user_lambda_init > 0)) maxdiag = two_view_maxdiag(dmax, acc, red);
       damp.start(A.user_lambda_init, A.tau, maxdiag);
       lambda0 = damp.lambda;
     }
@@ -194,94 +322,15 @@ __global__ __launch_bounds__(WGB) void k_ba_two_view(TwoViewArgs A) {
     int qmax = 0;
     do {
       const double lambda = damp.lambda;
-      // ---- pass S: eliminate the points, sum the reduced camera system ----
-      double sg[27];  // 0..20 - sum Z Y^T (upper), 21..26 - sum Z b_p
-#pragma unroll
-      for (int q = 0; q < 27; ++q) sg[q] = 0.0;
-      for (int i = tid; i < n; i += WGB) {
-        const int64_t g = p0 + i;
-        double H[6], b[3], A1[12], B[6], Hi[9];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) H[q] = scr[(S_HPP + q) * T + g];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) b[q] = scr[(S_BP + q) * T + g];
-#pragma unroll
-        for (int q = 0; q < 12; ++q) A1[q] = scr[(S_A1 + q) * T + g];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) B[q] = scr[(S_B1 + q) * T + g];
-        ba_sym3_inverse(H[0] + lambda, H[1], H[2], H[3] + lambda, H[4], H[5] + lambda, Hi);
-        scr[(S_HINV + 0) * T + g] = Hi[0]; scr[(S_HINV + 1) * T + g] = Hi[1]; scr[(S_HINV + 2) * T + g] = Hi[2];
-        scr[(S_HINV + 3) * T + g] = Hi[4]; scr[(S_HINV + 4) * T + g] = Hi[5]; scr[(S_HINV + 5) * T + g] = Hi[8];
-        double Y[18], Z[18];  // Y = A1^T B1, Z = Y H_pp^-1, 6x3 row-major
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          Y[3 * r] = A1[r] * B[0] + A1[6 + r] * B[3];
-          Y[3 * r + 1] = A1[r] * B[1] + A1[6 + r] * B[4];
-          Y[3 * r + 2] = A1[r] * B[2] + A1[6 + r] * B[5];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            Z[3 * r + c] = Y[3 * r] * Hi[c] + Y[3 * r + 1] * Hi[3 + c] + Y[3 * r + 2] * Hi[6 + c];
-            scr[(S_Z + 3 * r + c) * T + g] = Z[3 * r + c];
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-#pragma unroll
-          for (int c = r; c < 6; ++c)
-            sg[tri6(r, c)] -= Z[3 * r] * Y[3 * c] + Z[3 * r + 1] * Y[3 * c + 1] + Z[3 * r + 2] * Y[3 * c + 2];
-          sg[21 + r] -= Z[3 * r] * b[0] + Z[3 * r + 1] * b[1] + Z[3 * r + 2] * b[2];
-        }
-      }
-      wg_sum(sg, red);
-      double Su[21], gv[6], dxc[6];
-#pragma unroll
-      for (int q = 0; q < 21; ++q) Su[q] = acc[q] + sg[q];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        Su[tri6(r, r)] += lambda;
-        gv[r] = acc[21 + r] + sg[21 + r];
-      }
-      const bool fail = !chol6_solve(Su, gv, dxc);  // a non-positive pivot: the trial is rejected
+      double sg[27], Su[21], gv[6], dxc[6];
+      two_view_pass_S(A, tid, p0, n, lambda, sg, red);
+      const bool fail = two_view_reduced_solve(acc, sg, lambda, Su, gv, dxc);
 
       double tempChi = DBL_MAX, scale = 0.0;
       double nq[4] = {c1q[0], c1q[1], c1q[2], c1q[3]}, nt[3] = {c1t[0], c1t[1], c1t[2]};
       if (!fail) {
         ba_se3_oplus(dxc, nq, nt);
-        // ---- pass U: back-substitute, the trial estimate, its robust chi2 and x.(lambda x + b) ----
-        double tr[2] = {0.0, 0.0};
-        for (int i = tid; i < n; i += WGB) {
-          const int64_t g = p0 + i;
-          double b[3], h[6], d[3];
-#pragma unroll
-          for (int q = 0; q < 3; ++q) b[q] = scr[(S_BP + q) * T + g];
-#pragma unroll
-          for (int q = 0; q < 6; ++q) h[q] = scr[(S_HINV + q) * T + g];
-          d[0] = h[0] * b[0] + h[1] * b[1] + h[2] * b[2];
-          d[1] = h[1] * b[0] + h[3] * b[1] + h[4] * b[2];
-          d[2] = h[2] * b[0] + h[4] * b[1] + h[5] * b[2];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            double s = 0.0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) s += scr[(S_Z + 3 * r + c) * T + g] * dxc[r];
-            d[c] -= s;
-          }
-          double pn[3];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            tr[1] += d[c] * (lambda * d[c] + b[c]);
-            pn[c] = pts[3 * g + c] + d[c];
-            scr[(S_TRIAL + c) * T + g] = pn[c];
-          }
-          double e2;
-          tr[0] += two_view_rho(A, c0q, c0t, pn, A.uv0 + 2 * g, e2);
-          tr[0] += two_view_rho(A, nq, nt, pn, A.uv1 + 2 * g, e2);
-        }
-        wg_sum(tr, red);
-        tempChi = tr[0];
-        scale = tr[1];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) scale += dxc[r] * (lambda * dxc[r] + acc[21 + r]);
+        two_view_pass_U(A, tid, p0, n, lambda, dxc, acc, c0q, c0t, nq, nt, tempChi, scale, red);
       }
       if (damp.update(currentChi, tempChi, scale, 1.0 / 3.0, 2.0 / 3.0, rho)) {
         currentChi = tempChi;
@@ -289,7 +338,9 @@ __global__ __launch_bounds__(WGB) void k_ba_two_view(TwoViewArgs A) {
         for (int i = 0; i < 4; ++i) c1q[i] = nq[i];
 #pragma unroll
         for (int i = 0; i < 3; ++i) c1t[i] = nt[i];
-        for (int i = tid; i < n; i += WGB) {
+        // A failed trial skipped pass U and has no trial points: the estimate stays.  (The rule does accept one when
+        // the current chi2 is not finite, DBL_MAX being less than +inf; the rows would be whatever the scratch held.)
+        for (int i = tid; i < n && !fail; i += WGB) {
           const int64_t g = p0 + i;
 #pragma unroll
           for (int c = 0; c < 3; ++c) pts[3 * g + c] = scr[(S_TRIAL + c) * T + g];
@@ -332,6 +383,57 @@ __global__ __launch_bounds__(WGB) void k_ba_two_view(TwoViewArgs A) {
   }
 }
 
+// The read-out of one trial (sim3opt_ba_batch_debug_trial): passes L, S, the Cholesky and U of k_ba_two_view, once,
+// at the estimate A.pts (read only) and A.cam1, at the caller's lam[problem]; pass U with the caller's camera step
+// when dx_c is given.  The scratch is the per-point half of the read-out, `out` the per-problem half (T_* offsets).
+// Of A it reads ptr, cam0, cam1, pts, uv0, uv1, scr, total and the camera / kernel constants.
+__global__ __launch_bounds__(WGB) void k_ba_two_view_trial(TwoViewArgs A, const double* lam, const double* dx_c,
+                                                           double* out) {
+  __shared__ double red[NWAVE * 32];
+  const int tid = threadIdx.x;
+  const int prob = blockIdx.x;
+  const int64_t p0 = A.ptr[prob];
+  const int n = (int)(A.ptr[prob + 1] - p0);
+
+  double c0q[4], c0t[3], c1q[4], c1t[3];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { c0q[i] = A.cam0[7 * (size_t)prob + i]; c1q[i] = A.cam1[7 * (size_t)prob + i]; }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { c0t[i] = A.cam0[7 * (size_t)prob + 4 + i]; c1t[i] = A.cam1[7 * (size_t)prob + 4 + i]; }
+
+  double acc[29], dmax;
+  two_view_pass_L(A, tid, p0, n, c0q, c0t, c1q, c1t, acc, dmax, red);
+  const double maxdiag = two_view_maxdiag(dmax, acc, red);
+  const double lambda = lam[prob];
+  double sg[27], Su[21], gv[6], dxc[6], step[6];
+  two_view_pass_S(A, tid, p0, n, lambda, sg, red);
+  const bool fail = two_view_reduced_solve(acc, sg, lambda, Su, gv, dxc);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) step[r] = dx_c ? dx_c[6 * (size_t)prob + r] : dxc[r];
+  double tempChi = DBL_MAX, scale = 0.0;
+  double nq[4] = {c1q[0], c1q[1], c1q[2], c1q[3]}, nt[3] = {c1t[0], c1t[1], c1t[2]};
+  if (!fail) {
+    ba_se3_oplus(step, nq, nt);
+    two_view_pass_U(A, tid, p0, n, lambda, step, acc, c0q, c0t, nq, nt, tempChi, scale, red);
+  }
+  if (tid == 0) {
+    double* o = out + (size_t)prob * TRIAL_DOUBLES;
+#pragma unroll
+    for (int q = 0; q < 21; ++q) { o[T_ATA + q] = acc[q]; o[T_ZY + q] = sg[q]; o[T_S + q] = Su[q]; }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      o[T_BC + r] = acc[21 + r]; o[T_ZB + r] = sg[21 + r]; o[T_G + r] = gv[r]; o[T_DXC + r] = dxc[r];
+    }
+    o[T_CHI] = acc[27]; o[T_ACTIVE] = acc[28]; o[T_MAXDIAG] = maxdiag;
+    o[T_FAIL] = fail ? 1.0 : 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[T_CAM + i] = nq[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[T_CAM + 4 + i] = nt[i];
+    o[T_CHI_NEW] = tempChi; o[T_SCALE] = scale;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -365,6 +467,16 @@ struct Batch : sim3opt::BatchHandle {
   size_t in_doubles() const { return 14 * (size_t)n() + 7 * (size_t)total(); }
   size_t out_doubles() const {
     return (7 + SUMMARY_DOUBLES + (size_t)STAT_DOUBLES * opt.max_iters) * n() + 5 * (size_t)total();
+  }
+
+  // the camera and kernel constants of a launch
+  void constants(TwoViewArgs& A) const {
+    A.total = total();
+    A.f = f; A.cx = cx; A.cy = cy;
+    A.omega = 1.0 / (opt.pixel_noise * opt.pixel_noise);
+    A.huber = opt.huber_delta; A.tau = opt.tau; A.user_lambda_init = opt.user_lambda_init;
+    A.outlier_chi2 = opt.outlier_chi2;
+    A.max_iters = opt.max_iters; A.max_trials = opt.max_trials;
   }
 
   int optimize() {
@@ -407,12 +519,7 @@ struct Batch : sim3opt::BatchHandle {
     A.stats = A.cam_out + 7 * (size_t)N;
     A.summary = A.stats + (size_t)STAT_DOUBLES * opt.max_iters * N;
     A.edge_chi2 = A.summary + (size_t)SUMMARY_DOUBLES * N;
-    A.total = (int64_t)T;
-    A.f = f; A.cx = cx; A.cy = cy;
-    A.omega = 1.0 / (opt.pixel_noise * opt.pixel_noise);
-    A.huber = opt.huber_delta; A.tau = opt.tau; A.user_lambda_init = opt.user_lambda_init;
-    A.outlier_chi2 = opt.outlier_chi2;
-    A.max_iters = opt.max_iters; A.max_trials = opt.max_trials;
+    constants(A);
     // the statistics of iterations a problem does not reach read as zeros
     HIPCHK(hipMemsetAsync(A.stats, 0, sizeof(double) * STAT_DOUBLES * opt.max_iters * N, stream));
     hipLaunchKernelGGL(k_ba_two_view, dim3(N), dim3(WGB), 0, stream, A);  // the one launch of the batch
@@ -429,6 +536,66 @@ struct Batch : sim3opt::BatchHandle {
     stats_stride = opt.max_iters;
     have_run = true;
     return N;
+  }
+
+  // sim3opt_ba_batch_debug_trial: one trial of every problem at the current estimate, in blocks of its own that are
+  // gone when it returns.  Nothing of the handle is written: not the estimate, not the last run, not `dev`.
+  int debug_trial(const double* lam, const double* dx_c, double* point_rows, double* problem_rows) {
+    err.clear();
+    if (n() < 1) { err = "ba_batch_debug_trial: no problems set"; return SIM3OPT_ERR_STATE; }
+    const size_t N = (size_t)n(), T = (size_t)total();
+    if (!sim3opt::all_finite(lam, N)) { err = "ba_batch_debug_trial: non-finite lambda"; return SIM3OPT_ERR_ARG; }
+    if (dx_c && !sim3opt::all_finite(dx_c, 6 * N)) {
+      err = "ba_batch_debug_trial: non-finite camera step";
+      return SIM3OPT_ERR_ARG;
+    }
+    if (int rc = sim3opt::select_device(opt.device, err)) return rc;
+    // d_in: cam0 | cam1 | points | uv0 | uv1 | lam | dx_c.  (Declared before the stream's lease: on every path the
+    // lease's synchronisation comes first, then the blocks go.)
+    sim3opt::DevBuf<int32_t> d_ptr;
+    sim3opt::DevBuf<double> d_in, d_scr, d_out;
+    hipStream_t s = nullptr;  // (the handle's own may not exist yet, and is not this call's to create)
+    HIPCHK(sim3opt::stream_acquire(&s));
+    struct Lease {
+      hipStream_t s;
+      ~Lease() { (void)hipStreamSynchronize(s); sim3opt::stream_release(s); }
+    } lease{s};
+    HIPCHK(d_ptr.alloc(N + 1));
+    HIPCHK(d_in.alloc(in_doubles() + 7 * N));
+    HIPCHK(d_scr.alloc(SCR_PER_POINT * T));
+    HIPCHK(d_out.alloc(TRIAL_DOUBLES * N));
+    double* d_cam0 = d_in.get();
+    double* d_cam1 = d_cam0 + 7 * N;
+    double* d_pts = d_cam1 + 7 * N;
+    double* d_uv0 = d_pts + 3 * T;
+    double* d_uv1 = d_uv0 + 2 * T;
+    double* d_lam = d_uv1 + 2 * T;
+    double* d_dxc = d_lam + N;
+    HIPCHK(hipMemcpyAsync(d_ptr.get(), ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_cam0, cam0.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_cam1, cam1.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_pts, pts.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_uv0, uv0.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_uv1, uv1.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_lam, lam, sizeof(double) * N, hipMemcpyHostToDevice, s));
+    if (dx_c) HIPCHK(hipMemcpyAsync(d_dxc, dx_c, sizeof(double) * 6 * N, hipMemcpyHostToDevice, s));
+    // a failed trial skips pass U: its trial rows read as zeros
+    HIPCHK(hipMemsetAsync(d_scr.get(), 0, sizeof(double) * SCR_PER_POINT * T, s));
+    TwoViewArgs A{};
+    A.ptr = d_ptr.get(); A.cam0 = d_cam0; A.cam1 = d_cam1; A.pts_in = d_pts; A.uv0 = d_uv0; A.uv1 = d_uv1;
+    A.scr = d_scr.get();
+    A.pts = d_pts;
+    constants(A);
+    hipLaunchKernelGGL(k_ba_two_view_trial, dim3((unsigned)N), dim3(WGB), 0, s, A, (const double*)d_lam,
+                       dx_c ? (const double*)d_dxc : (const double*)nullptr, d_out.get());
+    HIPCHK(hipGetLastError());
+    std::vector<double> h_scr, h_out;
+    if (point_rows) HIPCHK(sim3opt::read_back(h_scr, (const double*)d_scr.get(), SCR_PER_POINT * T, s));
+    if (problem_rows) HIPCHK(sim3opt::read_back(h_out, (const double*)d_out.get(), TRIAL_DOUBLES * N, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (point_rows) std::memcpy(point_rows, h_scr.data(), sizeof(double) * h_scr.size());
+    if (problem_rows) std::memcpy(problem_rows, h_out.data(), sizeof(double) * h_out.size());
+    return SIM3OPT_OK;
   }
 };
 
@@ -531,6 +698,17 @@ int sim3opt_ba_batch_dims(const sim3opt_ba_batch* b, int32_t* n_problems, int32_
 int sim3opt_ba_batch_optimize(sim3opt_ba_batch* b) {
   if (!b) return SIM3OPT_ERR_ARG;
   return sim3opt::guarded(b, "ba_batch_optimize", sim3opt::NO_MEMORY_OR_INTERNAL, [&] { return b->optimize(); });
+}
+
+int sim3opt_ba_batch_debug_trial(sim3opt_ba_batch* b, const double* lambda, const double* dx_c, double* point_rows,
+                                 double* problem_rows) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  if (!lambda || (!point_rows && !problem_rows)) {
+    b->err = "ba_batch_debug_trial: bad argument";
+    return SIM3OPT_ERR_ARG;
+  }
+  return sim3opt::guarded(b, "ba_batch_debug_trial", sim3opt::NO_MEMORY_OR_INTERNAL,
+                          [&] { return b->debug_trial(lambda, dx_c, point_rows, problem_rows); });
 }
 
 int sim3opt_ba_batch_get_cameras(const sim3opt_ba_batch* b, double* cam0, double* cam1) {

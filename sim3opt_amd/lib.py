@@ -349,6 +349,7 @@ SYMBOLS = {
                                                 C.c_double]),
     "sim3opt_ba_batch_dims": (C.c_int, [_vp, _ip, _ip]),
     "sim3opt_ba_batch_optimize": (C.c_int, [_vp]),
+    "sim3opt_ba_batch_debug_trial": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "sim3opt_ba_batch_get_cameras": (C.c_int, [_vp, _dp, _dp]),
     "sim3opt_ba_batch_get_points": (C.c_int, [_vp, _dp]),
     "sim3opt_ba_batch_num_iterations": (C.c_int32, [_vp, C.c_int32]),
@@ -424,8 +425,13 @@ def hip_runtime_path():
     return None
 
 
-def load():
-    """Loads libsim3opt.so and binds every declared symbol (raises if one is missing)."""
+MISSING_SYMBOLS = []  # what load(tolerant=True) found missing
+
+
+def load(tolerant=False):
+    """Loads libsim3opt.so and binds every declared symbol (raises if one is missing).  tolerant: for a comparison with
+    an older build named by SIM3OPT_LIB, an export it lacks is left unbound and listed in MISSING_SYMBOLS; it holds
+    for the process, since the library is loaded once."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -447,6 +453,9 @@ def load():
         if os.environ.get("SIM3OPT_VERBOSE_LOAD"):
             print(f"sim3opt: {LIB_PATH} loaded; HIP runtime mapped: {hip_runtime_path()}", file=sys.stderr)
         for name, (res, args) in SYMBOLS.items():
+            if tolerant and not hasattr(L, name):
+                MISSING_SYMBOLS.append(name)
+                continue
             fn = getattr(L, name)  # AttributeError if the export is missing
             fn.restype = res
             fn.argtypes = args
@@ -1659,6 +1668,42 @@ class TwoViewBatch(_Handle):
         self._chk(self._L.sim3opt_ba_batch_get_chi2(self._b, _p(ab, _dp), _p(aa, _dp), _p(ec, _dp), _p(no, _ip)),
                   "ba_batch_get_chi2")
         return dict(active_before=ab, active_after=aa, edge_chi2=ec, n_outlier_edges=no)
+
+    # ---- diagnostic read-out (sim3opt_ba_batch_debug_trial): nothing in the solver uses it, and an optimize() after
+    # it computes bit for bit what it computes without it ----
+    # name -> (first row, rows) of the per-point scratch; name -> (first, count) of a problem's row
+    TRIAL_POINT_ROWS = dict(H_pp=(0, 6), b_p=(6, 3), A1=(9, 12), B1=(21, 6), es1=(27, 2), Hpp_inv=(29, 6), Z=(35, 18),
+                            trial_points=(53, 3))
+    TRIAL_PROBLEM_ROWS = dict(AtA=(0, 21), b_c=(21, 6), chi2=(27, 1), active_chi2=(28, 1), maxdiag=(29, 1),
+                              ZY=(30, 21), Zb=(51, 6), S=(57, 21), g=(78, 6), dx_c=(84, 6), fail=(90, 1), cam=(91, 7),
+                              chi2_new=(98, 1), scale=(99, 1))
+
+    def debug_trial(self, lam, dx_c=None):
+        """One LM trial of every problem at the current estimate, damping lam (one per problem, or one for all); with
+        dx_c (n x 6) the back-substitution and the trial estimate use that camera step.  dict, per point: H_pp (t, 6:
+        xx xy xz yy yz zz, undamped), b_p (t, 3), A1 (t, 2, 6), B1 (t, 2, 3), es1 (t, 2), Hpp_inv (t, 6), Z (t, 6, 3),
+        trial_points (t, 3); per problem: AtA, ZY = -sum Z Y^T, S (n, 21: upper triangles row by row), b_c, Zb =
+        -sum Z b_p, g, dx_c (n, 6), chi2, active_chi2, maxdiag, chi2_new, scale (n), fail (n, bool), cam (n, 7)."""
+        n, t = self.dims()
+        lam = np.ascontiguousarray(np.broadcast_to(_f64(lam).reshape(-1), (n,)) if np.size(lam) == 1 else
+                                   _f64(lam).reshape(-1))
+        if lam.shape[0] != n:
+            raise ValueError("one lambda per problem")
+        step = None
+        if dx_c is not None:
+            step = _f64(dx_c).reshape(-1)
+            if step.shape[0] != 6 * n:
+                raise ValueError("dx_c holds 6 numbers per problem")
+        rows, prob = np.empty((56, max(t, 1))), np.empty((max(n, 1), 100))
+        self._chk(self._L.sim3opt_ba_batch_debug_trial(self._b, _p(lam, _dp), _p(step, _dp), _p(rows, _dp),
+                                                       _p(prob, _dp)), "ba_batch_debug_trial")
+        shape = dict(A1=(t, 2, 6), B1=(t, 2, 3), Z=(t, 6, 3))
+        out = {k: np.ascontiguousarray(rows[a:a + c].T).reshape(shape.get(k, (t, c)))
+               for k, (a, c) in self.TRIAL_POINT_ROWS.items()}
+        for k, (a, c) in self.TRIAL_PROBLEM_ROWS.items():
+            out[k] = prob[:, a].copy() if c == 1 else prob[:, a:a + c].copy()
+        out["fail"] = out["fail"] != 0
+        return out
 
 
 class _RansacBatch(_Handle):

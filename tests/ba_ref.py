@@ -382,6 +382,194 @@ def scale_terms(x, b, lam, dt):
     return x * (dt(lam) * x + b), np.abs(x) * (abs(dt(lam)) * np.abs(x) + np.abs(b))
 
 
+# ---------------------------------------------------------------------------------------------- the two-view trial
+# One LM trial of sim3opt_amd/csrc/ba_batch.hip (k_ba_two_view: a workgroup per problem, camera 0 fixed) for a whole
+# ragged batch at once.  The per-point arrays are the kernel's scratch rows; a problem's sums run over an index list
+# into them, so that the slips of an index (TWO_VIEW_MUTATIONS) can be stated on the list.
+#   wave3_drop ......... wg_sum without the fourth wavefront's partial: the points i with i % 256 >= 192 leave every sum
+#   p256_as_0 .......... the 256-thread stride reads point i - 256 for point i = 256
+#   prev_offset ........ problem k's point i read at problem k - 1's offset (scr[r total + ptr[k - 1] + i])
+#   damp_none .......... H_pp inverted without lambda;  damp_offdiag: lambda on every entry of H_pp
+#   no_cam0 ............ camera 0's observation missing from H_pp and b_p;  cam0_in_AtA: present in sum A_1^T A_1
+#   huber_swapped ...... sqrt(w omega) of one view's observation used for the other view's
+#   g_no_Zbp ........... g = b_c;  backsub_ZT: Z read as 3 x 6;  scale_no_cam: x.(lambda x + b) over the points only
+#   hinv_other_lambda .. the H_pp^-1 rows of the trial before, at lambda / 2, left in the scratch: Z and the sums are
+#                        this trial's, the back-substitution reads the stale inverse
+#   maxdiag_no_cam ..... computeLambdaInit's maximum over the points only, the camera's diagonal left out
+#   maxdiag_wave3 ...... wg_max without the fourth wavefront's maximum
+#   V_half, quat_jl_swap as above
+TWO_VIEW_MUTATIONS = ("wave3_drop", "p256_as_0", "prev_offset", "damp_none", "damp_offdiag", "no_cam0", "cam0_in_AtA",
+                      "huber_swapped", "g_no_Zbp", "backsub_ZT", "scale_no_cam", "hinv_other_lambda", "maxdiag_no_cam",
+                      "maxdiag_wave3", "V_half", "quat_jl_swap")
+
+
+class TwoViewBatch:
+    """The batch as one problem `P` of this file: cameras 2 k (fixed) and 2 k + 1 of problem k, observations 2 g (camera
+    0's) and 2 g + 1 (camera 1's) of point g; ptr as sim3opt_ba_batch_set_problems takes it."""
+
+    def __init__(self, ptr, cam0, cam1, points, uv0, uv1, f, cx, cy, huber=3.0, pixel_noise=1.0):
+        self.ptr = np.asarray(ptr, dtype=np.int64)
+        n, cnt = self.ptr.shape[0] - 1, np.diff(self.ptr)
+        self.cams = np.stack([np.asarray(cam0).reshape(n, 7), np.asarray(cam1).reshape(n, 7)], axis=1).reshape(2 * n, 7)
+        self.points = np.asarray(points).reshape(-1, 3)
+        self.uv = np.stack([np.asarray(uv0).reshape(-1, 2), np.asarray(uv1).reshape(-1, 2)], axis=1).reshape(-1, 2)
+        self.problem_of = np.repeat(np.arange(n), cnt)
+        self.oc = np.stack([2 * self.problem_of, 2 * self.problem_of + 1], axis=1).ravel()
+        self.op = np.repeat(np.arange(self.points.shape[0]), 2)
+        self.fixed = np.tile([True, False], n)
+        self.f, self.cx, self.cy, self.huber, self.omega = f, cx, cy, huber, 1.0 / (pixel_noise * pixel_noise)
+
+    def index_lists(self, mut=None):
+        """Per problem: the points its sums read."""
+        out = []
+        for k in range(self.ptr.shape[0] - 1):
+            i = np.arange(self.ptr[k + 1] - self.ptr[k])
+            idx = self.ptr[k] + i
+            if mut == "wave3_drop":
+                idx = idx[i % 256 < 192]
+            elif mut == "p256_as_0" and idx.shape[0] > 256:
+                idx[256] = idx[0]
+            elif mut == "prev_offset" and k > 0:
+                idx = np.minimum(self.ptr[k - 1] + i, self.ptr[-1] - 1)
+            out.append(idx)
+        return out
+
+
+def active_terms(P, cams, points, dt):
+    """e^T Omega e of every observation: the terms of g2o's activeChi2 (no robust kernel)."""
+    _, _, e = residual(P, cams, points, dt)
+    return dt(P.omega) * (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1])
+
+
+def lambda_init_maxdiag(hpp_diag, cam_diag):
+    """computeLambdaInit's maximum over the free vertices: the diagonals of the (undamped) H_pp of the points and of
+    sum A^T A of the free cameras."""
+    return max(np.max(hpp_diag), np.max(cam_diag))
+
+
+def two_view_rows(P, lam_point, dt, mut=None):
+    """The per-point rows of pass L and pass S at the estimate P.cams, P.points: dict of H (T, 3, 3, undamped), b_p,
+    bp_mag, A1 (T, 2, 6), B1 (T, 2, 3), es1 (T, 2), A0 (camera 0's A, which the kernel never forms), H0 and bp0
+    (camera 0's share of H and b_p), Hinv (T, 3, 3), Y, Z, Z_mag (T, 6, 3), rho, e2 (T, 2).  lam_point (T,): the
+    damping of every point's problem."""
+    Jc, Jp, e = jacobians(P, P.cams, P.points, dt)
+    e2 = dt(P.omega) * (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1])
+    rho, w, _ = huber(e2, P.huber, dt)
+    if mut == "huber_swapped":
+        w = w.reshape(-1, 2)[:, ::-1].reshape(-1)
+    sw = np.sqrt(w * dt(P.omega))[:, None]
+    lin = np.concatenate([sw * Jc.reshape(-1, 12), sw * Jp.reshape(-1, 6), sw * e], axis=1)
+    T = P.points.shape[0]
+    lin_h = lin.copy()
+    if mut == "no_cam0":
+        lin_h[0::2] = 0
+    H, bp, bp_mag, _ = point_blocks(lin_h, P.op, T, dt)
+    A, B, es = split_lin(lin, dt)
+    A0, B0, es0, A1, B1 = A[0::2], B[0::2], es[0::2], A[1::2], B[1::2]
+    # camera 0's share of H_pp and b_p, which the kernel keeps in registers only: (value, magnitude) each
+    H0 = (np.einsum("nri,nrj->nij", B0, B0), np.einsum("nri,nrj->nij", np.abs(B0), np.abs(B0)))
+    bp0 = (-np.einsum("nri,nr->ni", B0, es0), np.einsum("nri,nr->ni", np.abs(B0), np.abs(es0)))
+    lam = np.asarray(lam_point, dtype=dt)[:, None, None]
+    damp = np.ones((3, 3), dtype=dt) if mut == "damp_offdiag" else np.eye(3, dtype=dt)
+
+    def inverse(l):  # (the kernel stores six entries: its inverse is symmetric)
+        X = R.accurate_inverse(H + (0 if mut == "damp_none" else l * damp), dt)
+        return (X + X.transpose(0, 2, 1)) / 2
+
+    Hinv = inverse(lam)
+    Y = np.einsum("nri,nrj->nij", A1, B1)
+    Z = Y @ Hinv
+    Z_mag = np.einsum("nri,nrj->nij", np.abs(A1), np.abs(B1)) @ np.abs(Hinv)
+    if mut == "hinv_other_lambda":
+        Hinv = inverse(lam / 2)
+    return dict(H=H, b_p=bp, bp_mag=bp_mag, H0=H0, bp0=bp0, A1=A1, B1=B1, es1=es[1::2], A0=A0, Hinv=Hinv, Y=Y, Z=Z,
+                Z_mag=Z_mag, rho=rho.reshape(-1, 2), e2=e2.reshape(-1, 2))
+
+
+def two_view_sums(rows, idx, lam, dt, mut=None):
+    """One problem's sums over the points idx of per-point rows (the reference's, or the device's own A1, B1, es1, Z,
+    b_p in dt): AtA = sum A_1^T A_1, b_c = -sum A_1^T es_1, ZY = -sum Z Y^T, Zb = -sum Z b_p, the damped S = lam I +
+    AtA + ZY as one 6 x 6 block, g = b_c + Zb, each with its magnitude `<name>_mag`; n = len(idx)."""
+    g = lambda k: np.asarray(rows[k], dtype=dt)[idx]
+    A, B, es, Z, bp = g("A1"), g("B1"), g("es1"), g("Z"), g("b_p")
+    Y = np.einsum("nri,nrj->nij", A, B)
+    out = dict(AtA=np.einsum("nri,nrj->ij", A, A), AtA_mag=np.einsum("nri,nrj->ij", np.abs(A), np.abs(A)),
+               b_c=-np.einsum("nri,nr->i", A, es), b_c_mag=np.einsum("nri,nr->i", np.abs(A), np.abs(es)),
+               ZY=-np.einsum("nik,njk->ij", Z, Y), ZY_mag=np.einsum("nik,njk->ij", np.abs(Z), np.abs(Y)),
+               Zb=-np.einsum("nik,nk->i", Z, bp), Zb_mag=np.einsum("nik,nk->i", np.abs(Z), np.abs(bp)), n=len(idx))
+    if mut == "cam0_in_AtA":
+        A0 = g("A0")
+        out["AtA"] = out["AtA"] + np.einsum("nri,nrj->ij", A0, A0)
+    I6 = np.eye(6, dtype=dt)
+    out["S"] = out["AtA"] + out["ZY"] + dt(lam) * I6
+    out["S_mag"] = out["AtA_mag"] + out["ZY_mag"] + abs(dt(lam)) * I6
+    out["g"] = out["b_c"].copy() if mut == "g_no_Zbp" else out["b_c"] + out["Zb"]
+    out["g_mag"] = out["b_c_mag"] + out["Zb_mag"]
+    return out
+
+
+def two_view_backsub(rows, step_point, dt, mut=None):
+    """(dx_p, magnitude) of every point: H_pp^-1 b_p - Z^T dx_c, dx_c (T, 6) the step of the point's camera 1."""
+    g = lambda k: np.asarray(rows[k], dtype=dt)
+    Hi, bp, Z, x = g("Hinv"), g("b_p"), g("Z"), np.asarray(step_point, dtype=dt)
+    if mut == "backsub_ZT":
+        Z = Z.reshape(-1, 3, 6).transpose(0, 2, 1)
+    return (np.einsum("pij,pj->pi", Hi, bp) - np.einsum("nrc,nr->nc", Z, x),
+            np.einsum("pij,pj->pi", np.abs(Hi), np.abs(bp)) + np.einsum("nrc,nr->nc", np.abs(Z), np.abs(x)))
+
+
+def two_view_scale(dxp, bp, step, bc, lam, dt, mut=None):
+    """(x.(lam x + b), its magnitude, the number of terms) of one problem: its points, then camera 1's six."""
+    x, b = [np.asarray(dxp, dtype=dt).ravel()], [np.asarray(bp, dtype=dt).ravel()]
+    if mut != "scale_no_cam":
+        x.append(np.asarray(step, dtype=dt).ravel())
+        b.append(np.asarray(bc, dtype=dt).ravel())
+    t, mag = scale_terms(np.concatenate(x), np.concatenate(b), lam, dt)
+    return t.sum(), mag.sum(), t.shape[0]
+
+
+def two_view_trial(P, lam, dt, dx_c=None, mut=None):
+    """The whole read-out of sim3opt_ba_batch_debug_trial from the estimate, in dt: dict of the rows (two_view_rows, and
+    trial_points), and per problem (lists / arrays over k) the sums (two_view_sums), chi2, active, maxdiag, dx_c (the
+    solve of S, g), cams (the trial camera 1 after the step dx_c[k] if given, else the solve's), branch, small, chi2_new
+    and scale.  lam (n,).  No trial fails here: S must be positive definite."""
+    n = P.ptr.shape[0] - 1
+    lam = np.asarray(lam, dtype=dt)
+    rows = two_view_rows(P, lam[P.problem_of], dt, mut)
+    lists = P.index_lists(mut)
+    sums = [two_view_sums(rows, lists[k], lam[k], dt, mut) for k in range(n)]
+    out = dict(rows=rows, sums=sums)
+    out["chi2"] = np.array([rows["rho"][i].sum() for i in lists], dtype=dt)
+    out["active"] = np.array([rows["e2"][i].sum() for i in lists], dtype=dt)
+    def maxdiag(i, s):
+        hpp, cam = rows["H"][i].diagonal(0, 1, 2), s["AtA"].diagonal()
+        if mut == "maxdiag_wave3":
+            hpp = np.concatenate([hpp[np.arange(hpp.shape[0]) % 256 < 192], np.zeros((1, 3), dtype=dt)])
+        return lambda_init_maxdiag(hpp, np.zeros(6, dtype=dt) if mut == "maxdiag_no_cam" else cam)
+
+    out["maxdiag"] = np.array([maxdiag(i, s) for i, s in zip(lists, sums)], dtype=dt)
+    out["dx_c"] = np.stack([np.linalg.solve(s["S"].astype(np.float64), s["g"].astype(np.float64)).astype(dt)
+                            if dt is np.float64 else refined6(s["S"], s["g"]) for s in sums])
+    step = out["dx_c"] if dx_c is None else np.asarray(dx_c, dtype=dt).reshape(n, 6)
+    dxp, _ = two_view_backsub(rows, step[P.problem_of], dt, mut)
+    full = np.zeros((2 * n, 6), dtype=dt)
+    full[1::2] = step
+    up = update(P.cams, P.points, full, dxp, P.fixed, dt, mut)
+    rows["trial_points"] = up["points"]
+    out["cams"], out["branch"], out["small"] = up["cams"][1::2], up["branch"][1::2], up["small"][1::2]
+    rho_new = rho_terms(P, up["cams"], up["points"], dt)[0].reshape(-1, 2)
+    out["chi2_new"] = np.array([rho_new[i].sum() for i in lists], dtype=dt)
+    out["scale"] = np.array([two_view_scale(dxp[i], rows["b_p"][i], step[k], sums[k]["b_c"], lam[k], dt, mut)[0]
+                             for k, i in enumerate(lists)], dtype=dt)
+    return out
+
+
+def refined6(S, g):
+    """x = S^-1 g of one small dense system in long double: a float64 inverse, refined."""
+    S, g = np.asarray(S, dtype=LD), np.asarray(g, dtype=LD)
+    return R.refined_solve(S, np.linalg.inv(S.astype(np.float64)), g, steps=5)
+
+
 # ---------------------------------------------------------------------------------------------- the PCG
 def bcsr_matvec(rptr, bcol, S, p):
     """q = S p on the padded block-CSR (blocks [k, r, c])."""

@@ -134,6 +134,40 @@ def test_restatement_agrees_with_the_oracle(name):
         assert R.relerr(cg["x"][-1], dxc.ravel()) < 1e-8
 
 
+@pytest.mark.parametrize("case", [(65, 24), (257, 19), (65, 24, "z+")])
+def test_two_view_trial_agrees_with_the_oracle(case):
+    """What the two-view trial adds to this file, against oracle/ba_oracle.py's two-camera Problem with camera 0 fixed:
+    chi2 and activeChi2, computeLambdaInit's maximum, the damped S as one 6 x 6 block (the Schur complement of the
+    oracle's H + lambda I) with g, the step, the trial estimate with its chi2, and the scale term."""
+    import two_view_cases as TC
+    c = TC.make_case(*case)
+    P = TC.oracle_problem(c, TC.DEFAULTS)
+    B = TC.ref_batch(TC.arrays_of([c]))
+    H, b, chi = P.system()
+    lam = 50.0
+    e = P.residuals()
+    Hl = (H + lam * sp.identity(H.shape[0])).toarray()[6:, 6:]
+    rhs = b[6:]
+    A, Bm, D = Hl[:6, :6], Hl[:6, 6:], Hl[6:, 6:]
+    dx = np.concatenate([np.zeros(6), np.linalg.solve(Hl, rhs)])
+    cn, pn = P.apply(P.cams, P.points, dx)
+    for dt in (np.float64, LD):
+        t = BR.two_view_trial(B, np.array([lam]), dt)
+        s = t["sums"][0]
+        assert abs(float(t["chi2"][0]) - chi) <= 1e-12 * chi
+        assert abs(float(t["active"][0]) - float(P.omega * (e * e).sum())) <= 1e-12 * float(t["active"][0])
+        assert abs(float(t["maxdiag"][0]) - np.abs(H.diagonal()[6:]).max()) <= 1e-12 * float(t["maxdiag"][0])
+        assert R.relerr(s["S"], A - Bm @ np.linalg.solve(D, Bm.T)) < 1e-10
+        assert R.relerr(s["g"], rhs[:6] - Bm @ np.linalg.solve(D, rhs[6:])) < 1e-9
+        assert R.relerr(s["b_c"], rhs[:6]) < 1e-12 and R.relerr(t["rows"]["b_p"].ravel(), rhs[6:]) < 1e-12
+        assert R.relerr(s["AtA"], H.toarray()[6:12, 6:12]) < 1e-12
+        assert R.relerr(t["dx_c"][0], dx[6:12]) < 1e-8
+        assert R.relerr(t["cams"][0], cn[1]) < 1e-9 and R.relerr(t["rows"]["trial_points"], pn) < 1e-9
+        assert abs(float(t["chi2_new"][0]) - P.chi2(cn, pn)) <= 1e-7 * chi
+        assert abs(float(t["scale"][0]) - float(dx[6:] @ (lam * dx[6:] + rhs))) <= 1e-8 * abs(float(t["scale"][0]))
+        assert t["branch"][0] == BR.quat_branch(c["cam1"][None])[0] == (TC.GAUGE_BRANCH[case[2]] if len(case) > 2 else 3)
+
+
 def test_update_matches_the_oracle_on_every_branch():
     P = C.problem("branches")
     nc = P.cams.shape[0]

@@ -193,6 +193,7 @@ def test_handles_give_everything_back():
     t = L.TwoViewBatch()
     t.set_problems(**TC.batch_arrays(TC.ONE_ITERATION_CASES[:1]))
     assert t.optimize() == 1
+    assert not t.debug_trial(50.0)["fail"].any()  # (the read-out's blocks are gone when it returns)
     assert L.device_memory_in_use()[0] == start[0] + 4  # (its four blocks)
     t.close()
     assert L.device_memory_in_use() == start, "two-view batch"

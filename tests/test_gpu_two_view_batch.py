@@ -116,6 +116,87 @@ def test_whole_run_matches_oracle():
     assert (snap["lambda_init"] == 50.0).all()
 
 
+def test_whole_run_on_every_quaternion_branch():
+    """BRANCH_CASES: case (65, 24) in worlds moved so that camera 1 stays on the x, y, z or trace branch of Eigen's
+    matrix -> quaternion rule through the whole run (tests/test_two_view_batch.py shows it for the oracle) and camera 0
+    is far from the identity: the same comparisons as any whole run, and the final chi2 is the device's own for the
+    base case to 1e-7 relative -- the refinement does not depend on the gauge."""
+    import ba_ref as BR
+    cases = TC.BRANCH_CASES + (TC.BRANCH_BASE,)
+    a = TC.batch_arrays(cases)
+    snap = snapshot(run_batch(cases, a))
+    base = problem_of(snap, a["point_ptr"], len(cases) - 1)[2][-1, 1]
+    for k, case in enumerate(TC.BRANCH_CASES):
+        check_whole_run(snap, a["point_ptr"], k, case)
+        want = TC.GAUGE_BRANCH[case[2]]
+        assert list(BR.quat_branch(np.stack([a["cam1"][k], snap["cam1"][k]]))) == [want, want], case
+        chi = problem_of(snap, a["point_ptr"], k)[2][-1, 1]
+        assert abs(chi - base) <= 1e-7 * base, (case, chi, base)
+
+
+def test_second_optimize_continues_from_the_first():
+    """optimize() with max_iters = 4, then again with max_iters = 6 and no set_problems in between: "another call
+    continues from them" (include/sim3opt.h).  Against the oracle's optimize(4) followed by optimize(6) on the same
+    Problem, each restarting at lambda_0 = 50 and ni = 2 (tests/test_two_view_batch.py: that pair of traces is stable),
+    with check_whole_run's tolerances for either call."""
+    cases = TC.CONTINUED_CASES
+    a = TC.batch_arrays(cases)
+    b = L.TwoViewBatch()
+    b.set_problems(**a)
+    for call, iters in enumerate(TC.CONTINUED_ITERS):
+        b.set_options(max_iters=iters)
+        assert b.optimize() == len(cases)
+        snap = snapshot(b)
+        for k, case in enumerate(cases):
+            ref = TC.continued_reference(*case)[call]
+            cam1, pts, st, n_it, ab, aa, ec, _, lam0 = problem_of(snap, a["point_ptr"], k)
+            tr = ref["trace"]
+            assert int(n_it[0]) == len(tr) == iters and lam0[0] == 50.0
+            assert [int(t) for t in st[:, 4]] == [t["trials"] for t in tr], (case, call)
+            for i, t in enumerate(tr):
+                assert abs(st[i, 1] - t["chi2"]) <= 1e-7 * t["chi2"], (case, call, i)
+                assert abs(st[i, 2] - t["lam"]) <= 1e-5 * t["lam"], (case, call, i)
+            tol0 = 1e-12 if call == 0 else 1e-7  # (the second call starts from the first's result, not from the input)
+            assert abs(st[0, 0] - ref["chi2_before"]) <= tol0 * ref["chi2_before"]
+            assert TC.quat_dist(cam1[:4], ref["cam1"][:4]) < 1e-8 and np.abs(cam1[4:] - ref["cam1"][4:]).max() < 1e-7
+            assert np.abs(pts - ref["points"]).max() < 1e-6, (case, call)
+            assert abs(ab[0] - ref["active_before"]) <= 1e-7 * ref["active_before"]
+            assert abs(aa[0] - ref["active_after"]) <= 1e-7 * ref["active_after"]
+            assert (np.abs(ec - ref["edge_chi2"]) <= 1e-7 * ref["edge_chi2"]).all(), (case, call)
+    b.close()
+
+
+def test_problem_whose_sums_are_not_finite_beside_healthy_ones():
+    """A 12-point problem one of whose points has X_z = 0 exactly in camera 1 (two_view_cases.degenerate_case), between
+    two healthy problems.  Its projection divides by zero: the robust chi2 of the start is +inf, every entry of the
+    reduced system is NaN, the Cholesky reports a non-positive pivot and the trial's chi2 is DBL_MAX.
+    lm_damping.hpp's statements (run on the host in tests/test_two_view_batch.py) then give rho = +inf, the failed
+    trial counted as accepted with nothing to accept, lambda / 3, and no reason to stop: 10 iterations of one trial.
+    The kernel returns (every loop is bounded), camera and points come back bit-identical to the start, and the
+    neighbours give the bytes they give alone.  (oracle/ba_oracle.py solves the non-finite system by LU, gets a NaN
+    chi2 and rejects: also 10 x 1 trial, with lambda growing instead; DESIGN.md.)"""
+    import test_two_view_batch as TH
+    bad = TC.degenerate_case()
+    healthy = [TC.make_case(*TC.WHOLE_RUN_CASES[3]), TC.make_case(*TC.WHOLE_RUN_CASES[0])]
+    a = TC.arrays_of([healthy[0], bad, healthy[1]])
+    b = L.TwoViewBatch()
+    b.set_problems(**a)
+    start = (b.cameras()[1], b.points())
+    assert b.optimize() == 3
+    snap, ptr = snapshot(b), a["point_ptr"]
+    for k, c in ((0, healthy[0]), (2, healthy[1])):
+        one = TC.arrays_of([c])
+        alone = snapshot(run_batch((None,), one))
+        assert same_bits(problem_of(alone, one["point_ptr"], 0), problem_of(snap, ptr, k)), k
+    cam1, pts, st, n_it = problem_of(snap, ptr, 1)[:4]
+    iters, trials, lam_ratio = TH.DAMPING_INF_FAIL
+    assert int(n_it[0]) == iters and [int(t) for t in st[:, 4]] == trials
+    assert (st[:, 0] == np.inf).all() and (st[:, 1] == np.finfo(np.float64).max).all() and (st[:, 3] == np.inf).all()
+    assert abs(st[-1, 2] - 50.0 * lam_ratio) <= 1e-14 * 50.0 * lam_ratio
+    assert np.array_equal(cam1, start[0][1]) and np.array_equal(pts, start[1][int(ptr[1]):int(ptr[2])])
+    b.close()
+
+
 def test_problems_are_independent_of_the_batch():
     """Each problem solved alone, and the batch in reversed order: the same bits as in the batch."""
     a, snap = default_run()
