@@ -117,9 +117,5 @@ bool engine_comm_local_state(const Engine* e, int64_t out[2]);
 // the PCG loops' schedule since the last reset: {iterations enqueued, of them after `done`, polls that synchronised
 // with an empty queue behind them, polls waited for with the next chunk queued}
 void engine_pcg_schedule_stats(Engine* e, int64_t out[4], bool reset);
-#ifdef SIM3OPT_BENCH_HOOKS
-int engine_bench_spmv_symmetric(Engine* e, int32_t reps, double out[4], std::string& err);
-int engine_bench_spmv_rowlane(Engine* e, int32_t reps, int32_t rows_per_group, double out[8], std::string& err);
-#endif
 
 }  // namespace sim3opt

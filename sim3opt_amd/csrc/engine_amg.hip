@@ -328,12 +328,12 @@ void Engine::spmv_mode(const CycleView& V, int level, int mode, const double* v,
   if (!V.batch) {
     // one system: the damped diagonal sits in the level's own blocks (k_jacobi wrote it)
     if (amg_fp32) {
-      if (level == 0) PASS_FINE(SIM3OPT_F32_CH, float, 1, L.vals32); else PASS_COARSE(SIM3OPT_COARSE_CH, float, 1, false, 1, L.vals32);
+      if (level == 0) PASS_FINE(F32_CH, float, 1, L.vals32); else PASS_COARSE(COARSE_CH, float, 1, false, 1, L.vals32);
     } else {
       if (level == 0) PASS_FINE(8, double, 1, L.vals); else PASS_COARSE(8, double, 1, false, 1, L.vals);
     }
   } else if (level == 0) {
-    BATCH_DISPATCH(V.nsys, PASS_FINE(SIM3OPT_F32_CH, float, KS, L.vals32));
+    BATCH_DISPATCH(V.nsys, PASS_FINE(F32_CH, float, KS, L.vals32));
   } else if (L.nnzb <= b_slice_blocks) {
     // a level whose blocks stay in cache (levels >= 2 of config 3) runs one system per grid slice: its passes
     // are launch-latency-bound, four times the wavefronts cost what one set costs, while one wavefront

@@ -60,12 +60,8 @@ namespace sim3opt {
 
 using sim3::Sim3;
 
-#ifndef SIM3OPT_COARSE_CH
-#define SIM3OPT_COARSE_CH 8     // blocks per pipeline step of the coarse levels' passes (one-system cycle; tuning: 16)
-#endif
-#ifndef SIM3OPT_F32_CH
-#define SIM3OPT_F32_CH 8        // blocks per pipeline step of the level-0 FP32 passes (tuning: 16)
-#endif
+constexpr int COARSE_CH = 8;    // blocks per pipeline step of the coarse levels' passes (one-system cycle; tuning: 16)
+constexpr int F32_CH = 8;       // blocks per pipeline step of the level-0 FP32 passes (tuning: 16)
 constexpr int WG = 256;         // 4 wavefronts of 64
 constexpr int KB = 4;            // most right-hand sides one PCG solves together (the batch's view)
 constexpr int CHAIN_SEG_MAX = 256;  // rows per segment of the chain preconditioner (LDS of k_chain_apply)

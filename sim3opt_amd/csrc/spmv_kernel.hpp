@@ -26,10 +26,6 @@
 // VT = float: the multigrid preconditioner's matrix passes stream an FP32 copy of the blocks (half
 // the bytes; vectors, accumulation and the smoother inverses stay FP64) -- the PCG's own SpMV
 // (MODE 0) always reads the FP64 blocks.
-#ifndef SIM3OPT_SPMV_FASTPATH
-#define SIM3OPT_SPMV_FASTPATH 1
-#endif
-constexpr bool FASTPATH = SIM3OPT_SPMV_FASTPATH != 0;
 
 // K > 1 (Engine::pcg_batch: the rejected trials of one LM iteration, solved together): the block stream, the
 // column indices and the row bookkeeping are shared, everything that depends on the vector is an array over the
@@ -46,14 +42,8 @@ struct BatchStrides {
   int part;      // between their arrays of partial sums
 };
 
-#ifndef SIM3OPT_BATCH_WAVES
-#define SIM3OPT_BATCH_WAVES 0  // tuning: force this many wavefronts per SIMD (0: the compiler's choice)
-#endif
 template <int CH, bool NT, int MODE, typename VT = double, int K = 1, bool DIAGK = false>
 __global__ __launch_bounds__(WG)
-#if SIM3OPT_BATCH_WAVES > 0
-__attribute__((amdgpu_waves_per_eu(SIM3OPT_BATCH_WAVES, SIM3OPT_BATCH_WAVES)))
-#endif
 void k_spmv_span(int nb, const int32_t* __restrict__ wrow,
                                                   const int32_t* __restrict__ rowptr,
                                                   const int32_t* __restrict__ colidx,
@@ -75,22 +65,17 @@ void k_spmv_span(int nb, const int32_t* __restrict__ wrow,
   // chunk, one ds_read_b64 per block and system (seven distinct words: broadcasts, no bank conflicts) -- half the LDS
   // instructions of the two ds_bpermute_b32 a 64-bit shuffle costs, the same values in the same order (bit-identical).
   // End of round 4, A/B on one box: 47.2 -> 49.3 LM it/s on the driver's command, the burst iteration 136 -> 128 ms.
-  // (0: the shuffles, kept for A/B)
-#ifndef SIM3OPT_X_LDS
-#define SIM3OPT_X_LDS 1
-#endif
-  // (not for the FP64 pass over several systems: measured 260 -> 279 us for four; the one-system FP64 pass is neutral)
-  constexpr bool XLDS = SIM3OPT_X_LDS != 0 && !(sizeof(VT) == 8 && K > 1);
+  // The FP64 pass over several systems keeps the shuffles: the LDS copy measured 260 -> 279 us for four systems (the
+  // one-system FP64 pass is neutral).  Each path is the only one some instantiation runs;
+  // test_gpu_pcg_operator.py::test_systems_of_a_batch_equal_the_one_system_launches holds the two to each other,
+  // bit for bit.
+  constexpr bool XLDS = !(sizeof(VT) == 8 && K > 1);
   constexpr int NGX = (CH + 7) / 8;
   __shared__ double xl[XLDS ? 4 : 1][XLDS ? K : 1][XLDS ? NGX : 1][64];
   double (*xw)[NGX][64] = xl[XLDS ? (threadIdx.x >> 6) : 0];
   // ... and the row epilogue's sums over the seven columns likewise: lane (r, c) writes its term to slot 8 r + c, lane r
   // reads its row back (three ds_read_b128 + one b64) and adds c = 0 ... 6 in that order -- the order of the six
   // 64-bit shuffles it replaces (twelve ds_bpermute_b32), bit-identical
-#ifndef SIM3OPT_ROWEND_LDS
-#define SIM3OPT_ROWEND_LDS 1  // (0: the shuffles, kept for A/B)
-#endif
-  constexpr bool RLDS = XLDS && SIM3OPT_ROWEND_LDS != 0;
   __shared__ __attribute__((aligned(16))) double rl[XLDS ? 4 : 1][64];
   double* const rw = rl[XLDS ? (threadIdx.x >> 6) : 0];
   if (MODE == 2 || MODE == 0) {  // (arrival counter of the barrier-free partial sums below)
@@ -181,7 +166,7 @@ void k_spmv_span(int nb, const int32_t* __restrict__ wrow,
   // (row sums are valid in lanes 0..6)
   typedef double d2_t __attribute__((ext_vector_type(2)));
   auto colsum = [&](double v) -> double {  // sum over c of the terms of lanes (r, c); valid in lanes 0..6
-    if (RLDS) {
+    if (XLDS) {
       wave_lds_sync();
       rw[8 * r + c49] = v;
       wave_lds_sync();
@@ -214,7 +199,7 @@ void k_spmv_span(int nb, const int32_t* __restrict__ wrow,
           if (lane < 7) qs[(size_t)7 * row + lane] = d;
         } else {
           double dc;  // d_c for lane (r, c)
-          if (RLDS) {
+          if (XLDS) {
             if (lane < 7) rw[56 + lane] = d;
             wave_lds_sync();
             dc = rw[56 + c49];
@@ -310,7 +295,7 @@ void k_spmv_span(int nb, const int32_t* __restrict__ wrow,
       // passes, the level-0 FP32 passes unchanged).  A third path for interior chunks WITH a row boundary
       // (no validity tests) raised the register count and lost more than it won
       // (profiles/r3_negative_results.log)
-      const bool interior = FASTPATH && k >= kbeg && k + CH <= kend;
+      const bool interior = k >= kbeg && k + CH <= kend;
       auto next_row = [&](int u) {  // row `row` is complete; block u of this chunk starts the next one
         row_end(row);
         ++row;

@@ -11,10 +11,9 @@ import sys
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (SIM3OPT_LIB: another build of the same library, e.g. the host-sanitizer build of scripts/host_asan_suite.sh)
+# (SIM3OPT_LIB: another build of the same library, e.g. the host-sanitizer build of scripts/host_asan_suite.sh or an
+# experiment build, `python -m sim3opt_amd.build --flags "..." --out PATH`, which never writes the product library)
 LIB_PATH = os.environ.get("SIM3OPT_LIB") or os.path.join(_HERE, "libsim3opt.so")
-# (a tuning script that A/Bs two builds sets sim3opt_amd.lib.LIB_PATH before the first load(); no
-# environment variable redirects the dlopen)
 
 OK, ERR_ARG, ERR_STATE, ERR_NO_DEVICE, ERR_HIP, ERR_IO, ERR_COMM = 0, -1, -2, -3, -4, -5, -6
 # robust kernels of an edge (include/sim3opt.h lists rho and rho' of each)
@@ -407,12 +406,6 @@ SYMBOLS = {
 _lib = None
 
 
-OPTIONAL_SYMBOLS = {
-    "sim3opt_bench_spmv_symmetric": (C.c_int, [_vp, C.c_int32, _dp]),
-    "sim3opt_bench_spmv_rowlane": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),
-}
-
-
 def hip_runtime_path():
     """Path of the libamdhip64 this process has mapped (the one libsim3opt.so is bound to), or None."""
     try:
@@ -459,11 +452,6 @@ def load(tolerant=False):
             fn = getattr(L, name)  # AttributeError if the export is missing
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in OPTIONAL_SYMBOLS.items():  # a SIM3OPT_BENCH_HOOKS build only
-            fn = getattr(L, name, None)
-            if fn is not None:
-                fn.restype = res
-                fn.argtypes = args
         _lib = L
     return _lib
 
@@ -1287,19 +1275,6 @@ class Graph:
         ms = C.c_double()
         self._chk(self._L.sim3opt_bench_spmv(self._g, int(reps), C.byref(ms)))
         return ms.value
-
-    def bench_spmv_symmetric(self, reps=20):
-        """Prototype of the two-phase upper-triangle SpMV: (ms phase 1, ms phase 2, max rel difference to
-        the product SpMV, bytes of its stream)."""
-        out = np.zeros(4)
-        self._chk(self._L.sim3opt_bench_spmv_symmetric(self._g, int(reps), _p(out, _dp)))
-        return tuple(float(v) for v in out)
-
-    def bench_spmv_rowlane(self, reps=20, rows_per_group=2):
-        """Prototype of the row-per-lane FP32 passes (a SIM3OPT_BENCH_HOOKS build): 8 numbers, see sim3opt_bench.h."""
-        out = np.zeros(8)
-        self._chk(self._L.sim3opt_bench_spmv_rowlane(self._g, int(reps), int(rows_per_group), _p(out, _dp)))
-        return tuple(float(v) for v in out)
 
     def bench_stream(self, mode, reps=20):
         ms = C.c_double()

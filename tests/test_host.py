@@ -5,6 +5,7 @@ the row partition.  No compute call is made here -- without a GPU the library mu
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -19,8 +20,8 @@ I8 = [0, 0, 0, 1, 0, 0, 0, 1.0]
 def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "sim3opt.h")).read()
     bench = open(os.path.join(ROOT, "include", "sim3opt_bench.h")).read()
-    # (what only a SIM3OPT_BENCH_HOOKS build exports -- measurement prototypes -- is not part of the product)
-    bench = re.sub(r"#ifdef SIM3OPT_BENCH_HOOKS.*?#endif", "", bench, flags=re.S)
+    # one build configuration: no declaration depends on a build mode
+    assert "SIM3OPT_BENCH_HOOKS" not in hdr + bench
     # the drop-in interface carries no measurement hooks (they live in sim3opt_bench.h)
     assert "sim3opt_bench_" not in hdr and set(re.findall(r"\b(sim3opt_[a-z0-9_]+)\s*\(", bench)) == {
         "sim3opt_bench_spmv", "sim3opt_bench_stream"}
@@ -31,6 +32,40 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert getattr(lib, name) is not None
     assert lib.sim3opt_version() >= 100
+    # ... and the library exports nothing beyond them: its unmangled sim3opt_* functions ARE the declared set
+    nm = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {f[2] for f in (ln.split() for ln in nm.splitlines())
+                if len(f) == 3 and f[1] in "Tt" and re.fullmatch(r"sim3opt_[a-z0-9_]+", f[2])}
+    assert exported == declared, exported ^ declared
+
+
+def test_build_is_the_product_whatever_the_environment_holds(monkeypatch, tmp_path):
+    """command() is a function of its arguments: variables that once selected another build change nothing, and an
+    experiment build cannot land on the product library.  Nothing is compiled."""
+    import importlib
+
+    from sim3opt_amd import build as B
+
+    for name in ("SIM3OPT_BENCH_HOOKS", "SIM3OPT_EXTRA_FLAGS"):
+        monkeypatch.delenv(name, raising=False)
+    clean = importlib.reload(B).command()
+    monkeypatch.setenv("SIM3OPT_BENCH_HOOKS", "1")
+    monkeypatch.setenv("SIM3OPT_EXTRA_FLAGS", "-DX=1")
+    B = importlib.reload(B)
+    assert B.command() == clean and "-DX=1" not in clean
+    # every translation unit of csrc/SOURCES, no other source, into the product library
+    listed = open(os.path.join(B.CSRC, "SOURCES")).read().split()
+    assert [a for a in clean if a.endswith((".hip", ".cpp", ".c", ".cc"))] == [os.path.join(B.CSRC, s) for s in listed]
+    assert clean[clean.index("-o") + 1] == B.LIB and "--offload-arch=gfx950" in clean
+    # ... with the flags of the Makefile's recipe, in its order
+    recipe = re.search(r"^\t\$\(HIPCC\) (.*) -o \$@ \$\(SRCS\) (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M)
+    assert clean[1:clean.index("-o")] == recipe.group(1).split() and clean[-1:] == recipe.group(2).split()
+    with pytest.raises(ValueError):
+        B.command(extra_flags=["-DX=1"], out=B.LIB)
+    out = str(tmp_path / "libexperiment.so")
+    exp = B.command(extra_flags=["-DX=1"], out=out)
+    assert "-DX=1" in exp and exp[exp.index("-o") + 1] == out and B.LIB not in exp
+    assert [a for a in exp if a not in ("-DX=1", out)] == [a for a in clean if a != B.LIB]
 
 
 def test_options_struct_matches_header_defaults():
