@@ -6,7 +6,8 @@
 #                           tests/cxx/two_view_conformance (the two-view refinement helper),
 #                           tests/cxx/pnp_conformance (the PnP RANSAC helper feeding it),
 #                           tests/cxx/match_conformance (the matching helper feeding that),
-#                           tests/cxx/essential_conformance (the essential-matrix RANSAC helper)
+#                           tests/cxx/essential_conformance (the essential-matrix RANSAC helper),
+#                           tests/cxx/homography_conformance (the homography MLESAC helper)
 #   make LIB=/some/where/libsim3opt.so   builds the library elsewhere (used by the tests)
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC  := sim3opt_amd/csrc
@@ -32,7 +33,8 @@ example: $(LIB) examples/direct_pgo.cpp include/sim3opt_g2o.hpp
 conformance: $(LIB) tests/cxx/shim_conformance.cpp tests/cxx/ba_shim_conformance.cpp tests/cxx/two_view_conformance.cpp \
              tests/cxx/pnp_conformance.cpp include/sim3opt_g2o.hpp include/sim3opt_g2o_ba.hpp include/sim3opt_two_view.hpp \
              include/sim3opt_pnp.hpp tests/cxx/match_conformance.cpp include/sim3opt_match.hpp \
-             tests/cxx/essential_conformance.cpp include/sim3opt_essential.hpp
+             tests/cxx/essential_conformance.cpp include/sim3opt_essential.hpp \
+             tests/cxx/homography_conformance.cpp include/sim3opt_homography.hpp
 	g++ -std=c++17 -Wall -DSIM3OPT_G2O_NAMES -Iinclude $(EIGEN_INC) tests/cxx/shim_conformance.cpp \
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/shim_conformance
 	g++ -std=c++17 -Wall -DSIM3OPT_G2O_BA_NAMES -Iinclude $(EIGEN_INC) tests/cxx/ba_shim_conformance.cpp \
@@ -45,10 +47,12 @@ conformance: $(LIB) tests/cxx/shim_conformance.cpp tests/cxx/ba_shim_conformance
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/match_conformance
 	g++ -std=c++17 -Wall -Iinclude tests/cxx/essential_conformance.cpp \
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/essential_conformance
+	g++ -std=c++17 -Wall -Iinclude tests/cxx/homography_conformance.cpp \
+	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/homography_conformance
 
 clean:
 	rm -f sim3opt_amd/libsim3opt.so oracle/liboracle_sim3.so examples/direct_pgo tests/cxx/shim_conformance \
 	    tests/cxx/ba_shim_conformance tests/cxx/two_view_conformance tests/cxx/pnp_conformance tests/cxx/match_conformance \
-	    tests/cxx/essential_conformance
+	    tests/cxx/essential_conformance tests/cxx/homography_conformance
 
 .PHONY: all example conformance clean

@@ -1172,6 +1172,128 @@ int sim3opt_essential_batch_debug_score(sim3opt_essential_batch* b, int32_t P, c
 int sim3opt_essential_batch_debug_pose(sim3opt_essential_batch* b, const double* essentials, const uint8_t* mask,
                                        double* candidates, int32_t* votes, int32_t* winner, uint8_t* mask_out);
 
+/* ---- batched homography MLESAC and decomposition: the loop detector's planar two-view pose, every candidate in one launch ----
+ * HomographyInit::Compute(vMatches, 5.0, se3) (kittiDetector.h:1387-1443, the USE_KLEIN record line; HomographyInit.cc,
+ * MEstimator.h): 300 MLESAC trials of a four-point homography, the inliers of the best one, five Tukey-reweighted
+ * refinement rounds on them, the Faugeras-Lustman decomposition into eight (R, t, n, d), two visibility tests and a
+ * Sampson tie-break.  It is the estimator that works where the five-point one degenerates: facades, the road surface,
+ * revisits with little parallax.
+ * PARITY UNPINNED: the reference cannot be built here (TooN and libCVD are absent) and its rand() sampling is not
+ * reproducible.  What is the reference's: every step and formula below from the error on, in its order, with its
+ * constants.  What is not: the sampler is counter-based; the linear algebra (TooN's SVD of the 8 x 9 system, its WLS, its
+ * 3 x 3 SVD) is a closed form, a Cholesky factorisation and a Jacobi eigen-solver; equal scores are ordered by the
+ * decomposition's number (std::sort leaves that open); the camera is the pinhole (the reference: ATANCamera); the
+ * least-squares branch the call site reaches at exactly nine points is not here (status 1 below min_points = 10).
+ * Definition.
+ * Coordinates: v2CamPlane = ((u - cx) / f, (v - cy) / f) in double for both views, m2PixelProjectionJac = f I; view 0 is
+ * uv0 (First); second ~ H first; the pose is se3SecondFromFirst: X1 = R X0 + t.
+ * Sampler: draw j (0..3) of hypothesis h is splitmix64(seed + (4 h + j + 1) * 0x9E3779B97F4A7C15) modulo n - j, stepped
+ * over the earlier picks in ascending order.
+ * Hypothesis (:65-115): the homography of the four correspondences, H = B adj(A) with A (B) the map from the standard
+ * projective basis to the four points of view 0 (1) -- the null vector of the reference's 8 x 9 system up to sign --
+ * scaled to Frobenius norm 1.  Invalid (the identity stored, skipped): twice the area of a triangle of three of the four
+ * points at most 1e-9 in either view (collinear or repeated points), a non-finite entry.
+ * Error (:14-33): p = H (x0, y0, 1), e = f ((x1, y1) - (p0, p1) / p2), e2 = |e|^2 in px^2, every product and sum
+ * rounded on its own, left to right (no fused multiply-add).  MLESAC: the cost of a hypothesis is the sum over all
+ * points of min(e2, max_pixel_error^2) (a non-finite e2 costs the cap).  Best: the smallest cost, then the smallest index.
+ * Inliers (:44-47): e2 < max_pixel_error^2 under the best H; the set is fixed from here on; fewer than 4: status 3.
+ * Refinement (:120-177), refine_rounds times: the inliers' e and 2 x 9 Jacobians at H; sigma^2 = (4.6851 * 1.4826 *
+ * (1 + 5 / (2 m - 6)) * sqrt(median))^2 with the median the element of rank floor(m / 2) (from 0) of the m squared
+ * errors in ascending order, exactly; weights (1 - e2 / sigma^2)^2, 0 where e2 > sigma^2; (I + J^T W J) update =
+ * J^T W e summed in a fixed order and solved by Cholesky; H += update.
+ * Decomposition (:232-339): H = U diag(d1 >= d2 >= d3) V^T (V and d^2 from eight cyclic Jacobi sweeps on H^T H,
+ * U = H V diag(1 / d); every column of V signed so that its component of largest magnitude, the first such, is
+ * positive -- the reference leaves that to TooN's SVD, and with it which of the eight is which), s = det U det V.  Only d1 != d2 != d3 exactly (the reference's case 1); anything else, or a
+ * non-finite number: status 4.  Decomposition k = 0..3 has d = s d2 and Eq. 13-14, k = 4..7 d = -s d2 and Eq. 15-16,
+ * with the signs (e1, e3) = (+, +), (-, +), (+, -), (-, -) within each four; R = s U Rp V^T, t = U tp, n = V np.
+ * Choice (:363-435): first count, per decomposition, of inliers with (H row 2 . (x0, y0, 1)) / d > 0; the four with
+ * the largest counts stay (equal counts: the smaller k first); second count: ((x0, y0, 1) . n) / d > 0; two stay.
+ * dRatio = score[1] / score[0] of the negated counts; dRatio < 0.9 takes the first; otherwise (0 / 0 included) the sums
+ * over ALL points of Sampson's error of second^T [t]x R first, each capped at 4 max_pixel_error^2, decide with <=.
+ * H and -H give the same pose: decomposition k of H is decomposition (k & 4) | (3 - (k & 3)) of -H.
+ * Device pipeline: sim3opt_amd/csrc/homography_batch.hip, one workgroup per problem, one launch.  A problem's result
+ * does not depend on the other problems of the batch or on its place among them.  No CPU fallback:
+ * SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_homography_batch sim3opt_homography_batch;
+
+typedef struct sim3opt_homography_batch_options {
+  double max_pixel_error;  /* inlier: e2 < max_pixel_error^2 [px]; MLESAC's cap       default 5.0   :1414 dMaxPixelError        */
+  uint64_t seed;           /* of the sampler                                           default 0                                 */
+  int32_t iterations;      /* hypotheses per problem, 1..4096                          default 300   HomographyInit.cc:195       */
+  int32_t refine_rounds;   /* Tukey-reweighted rounds on the inliers, 0..8             default 5     HomographyInit.cc:48        */
+  int32_t min_points;      /* fewer points: status 1, nothing run; >= 4                default 10    HomographyInit.cc:182       */
+  int32_t device;          /* HIP device ordinal, -1 = current                         default -1                                */
+} sim3opt_homography_batch_options;
+
+#define SIM3OPT_HOMOGRAPHY_OK 0            /* H, a pose and its inliers                                                     */
+#define SIM3OPT_HOMOGRAPHY_FEW_POINTS 1    /* fewer than min_points points: nothing run, identity rotation, zero t, H = 0    */
+#define SIM3OPT_HOMOGRAPHY_NO_HYPOTHESIS 2 /* no sample gave an H: likewise                                                 */
+#define SIM3OPT_HOMOGRAPHY_NO_INLIERS 3    /* fewer than 4 inliers of the best H: identity pose, both H the MLESAC one       */
+#define SIM3OPT_HOMOGRAPHY_DEGENERATE 4    /* not the decomposition's case 1, or a non-finite number: identity pose, H kept  */
+
+void sim3opt_homography_batch_options_default(sim3opt_homography_batch_options* o);
+sim3opt_homography_batch* sim3opt_homography_batch_create(void);
+void sim3opt_homography_batch_destroy(sim3opt_homography_batch* b);
+const char* sim3opt_homography_batch_last_error(const sim3opt_homography_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: iterations outside 1..4096, max_pixel_error <= 0 or not finite, refine_rounds
+ * outside 0..8, min_points < 4. */
+int sim3opt_homography_batch_set_options(sim3opt_homography_batch* b, const sim3opt_homography_batch_options* o);
+/* vMatches of the call at :1414 (built at :1393-1409) for n_problems candidates at once: point_ptr (n_problems + 1,
+ * ragged, point_ptr[0] = 0), uv0 and uv1 (total x 2) -- exactly the match_ptr, uv0, uv1 that
+ * sim3opt_match_batch_get_* return -- and focal / cx / cy.  SIM3OPT_ERR_ARG with nothing changed: n_problems < 1, a
+ * problem with no point, a non-monotone point_ptr, a non-finite number, focal <= 0, a NULL array.  A problem with fewer
+ * than min_points points is accepted and ends with status 1. */
+int sim3opt_homography_batch_set_problems(sim3opt_homography_batch* b, int32_t n_problems, const int32_t* point_ptr,
+                                          const double* uv0, const double* uv1, double focal, double cx, double cy);
+/* Each may be NULL.  tiles[2]: the points staged in LDS at most and the hypotheses of a chunk: the sizes at which
+ * the kernel takes another path. */
+int sim3opt_homography_batch_dims(const sim3opt_homography_batch* b, int32_t* n_problems, int32_t* total_points,
+                                  int32_t tiles[2]);
+/* Compute (:35-63) of every problem, ONE kernel launch for the batch.  Returns the number of problems with status 0, or
+ * a negative SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no problems set); one problem's failure is its status, never the batch's. */
+int sim3opt_homography_batch_solve(sim3opt_homography_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  poses: n x 7 [qx qy qz qw tx ty tz] of
+ * se3SecondFromFirst (:61), t as computed, not normalised (:1431 normalises it; status 1..4: the identity and zero). */
+int sim3opt_homography_batch_get_poses(const sim3opt_homography_batch* b, double* poses);
+/* n x 9 row-major each, one may be NULL: the best MLESAC hypothesis (:179-230, Frobenius norm 1) and mm3BestHomography
+ * after the refinement rounds (:48-49) */
+int sim3opt_homography_batch_get_homographies(const sim3opt_homography_batch* b, double* mlesac, double* refined);
+/* mask (total, 1 = in mvHomographyInliers, :44-47) and / or n_inliers (n) */
+int sim3opt_homography_batch_get_inliers(const sim3opt_homography_batch* b, uint8_t* mask, int32_t* n_inliers);
+/* Per problem (each may be NULL): status (SIM3OPT_HOMOGRAPHY_*), the index of the best hypothesis (-1: none) and its
+ * cost (dBestError, :224-228), the inlier count, sigma^2 of every round (n x 8, zero beyond refine_rounds; :161), the
+ * first counts (n x 8; :366-378), the four decompositions kept (n x 4) and their second counts (n x 4; :383-395), the
+ * chosen decomposition (0..7), whether the ambiguity branch ran (:404-433) and its two Sampson sums (n x 2, zero if
+ * not). */
+int sim3opt_homography_batch_get_summary(const sim3opt_homography_batch* b, int32_t* status, int32_t* best_hypothesis,
+                                         double* cost_hypothesis, int32_t* n_inliers, double* sigma2,
+                                         int32_t* counts_first, int32_t* kept, int32_t* counts_second,
+                                         int32_t* choice, int32_t* ambiguous, double* sampson);
+/* Diagnostics.  Each leaves the results of the last solve as they were.
+ * What the last solve computed for `problem`, H = options.iterations hypotheses (:195-229): sample (H x 4 point
+ * indices), n_solutions (1 where valid), valid, homography (H x 9; the identity where not valid), count (n where
+ * valid) and cost of the scoring (0 where not valid).  Each may be NULL.  SIM3OPT_ERR_STATE before the first solve. */
+int sim3opt_homography_batch_debug_hypotheses(sim3opt_homography_batch* b, int32_t problem, int32_t* sample,
+                                              int32_t* n_solutions, int32_t* valid, double* homography,
+                                              int32_t* count, double* cost);
+/* P (1..4096) supplied matrices per problem (homographies: n x P x 9, finite) through the scoring code of
+ * k_homography_ransac (MLESACScore, :23-33): count (= the problem's points) and cost (n x P each, one may be NULL). */
+int sim3opt_homography_batch_debug_score(sim3opt_homography_batch* b, int32_t P, const double* homographies,
+                                         int32_t* count, double* cost);
+/* RefineHomographyWithInliers (:120-177), refine_rounds times, from a supplied matrix per problem (homographies:
+ * n x 9, finite) on a supplied inlier set (mask: total): sigma^2 (n x refine_rounds) and H (n x refine_rounds x 9)
+ * after every round; zero for a problem whose set has fewer than four points.  One output may be NULL. */
+int sim3opt_homography_batch_debug_refine(sim3opt_homography_batch* b, const double* homographies,
+                                          const uint8_t* mask, double* sigma2, double* refined);
+/* DecomposeHomography and ChooseBestDecomposition (:232-435) of a supplied matrix per problem (homographies: n x 9,
+ * finite) on a supplied inlier set (mask: total): the eight decompositions (n x 8 x 16: R row-major, t, n, d; zero with
+ * status 4), status (0 or 4), and what sim3opt_homography_batch_get_summary returns of the choice, then the poses
+ * (n x 7).  The outputs may be NULL. */
+int sim3opt_homography_batch_debug_decompose(sim3opt_homography_batch* b, const double* homographies,
+                                             const uint8_t* mask, double* decompositions, int32_t* status,
+                                             int32_t* counts_first, int32_t* kept, int32_t* counts_second,
+                                             int32_t* choice, int32_t* ambiguous, double* sampson, double* poses);
+
 /* ---- batched descriptor matching and map-depth lookup: what the three blocks above consume, every candidate at once ----
  * The front of computeConstraints: matcher.match / knnMatch(.., 2) with the ratio test, the 1/10 image-border filter,
  * the skew filter and the uniqueness pass (kittiDetector.h:1085-1160), then the depth of every kept match in both

@@ -167,6 +167,18 @@ class EssentialBatchOptions(C.Structure):
     ]
 
 
+class HomographyBatchOptions(C.Structure):
+    """sim3opt_homography_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("max_pixel_error", C.c_double),
+        ("seed", C.c_uint64),
+        ("iterations", C.c_int32),
+        ("refine_rounds", C.c_int32),
+        ("min_points", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class MatchBatchOptions(C.Structure):
     """sim3opt_match_batch_options (include/sim3opt.h), field for field."""
     _fields_ = [
@@ -385,6 +397,24 @@ SYMBOLS = {
     "sim3opt_essential_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
     "sim3opt_essential_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
     "sim3opt_essential_batch_debug_pose": (C.c_int, [_vp, _dp, _up, _dp, _ip, _ip, _up]),
+    "sim3opt_homography_batch_options_default": (None, [C.POINTER(HomographyBatchOptions)]),
+    "sim3opt_homography_batch_create": (_vp, []),
+    "sim3opt_homography_batch_destroy": (None, [_vp]),
+    "sim3opt_homography_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_homography_batch_set_options": (C.c_int, [_vp, C.POINTER(HomographyBatchOptions)]),
+    "sim3opt_homography_batch_set_problems": (C.c_int, [_vp, C.c_int32, _ip, _dp, _dp, C.c_double, C.c_double,
+                                                        C.c_double]),
+    "sim3opt_homography_batch_dims": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "sim3opt_homography_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_homography_batch_get_poses": (C.c_int, [_vp, _dp]),
+    "sim3opt_homography_batch_get_homographies": (C.c_int, [_vp, _dp, _dp]),
+    "sim3opt_homography_batch_get_inliers": (C.c_int, [_vp, _up, _ip]),
+    "sim3opt_homography_batch_get_summary": (C.c_int, [_vp, _ip, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _dp]),
+    "sim3opt_homography_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
+    "sim3opt_homography_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
+    "sim3opt_homography_batch_debug_refine": (C.c_int, [_vp, _dp, _up, _dp, _dp]),
+    "sim3opt_homography_batch_debug_decompose": (C.c_int, [_vp, _dp, _up, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _dp,
+                                                           _dp]),
     "sim3opt_match_batch_options_default": (None, [C.POINTER(MatchBatchOptions)]),
     "sim3opt_match_batch_create": (_vp, []),
     "sim3opt_match_batch_destroy": (None, [_vp]),
@@ -1397,7 +1427,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -1682,7 +1712,7 @@ class TwoViewBatch(_Handle):
 
 
 class _RansacBatch(_Handle):
-    """What PnpBatch and EssentialBatch share (csrc/ransac_frame.hpp): a batch of problems, each owning the rows
+    """What PnpBatch, EssentialBatch and HomographyBatch share (csrc/ransac_frame.hpp): a batch of problems, each owning the rows
     point_ptr[k]:point_ptr[k+1] of two flat arrays; one launch makes `iterations` hypotheses per problem from samples
     of _sample points, scores every one and keeps the best model (of shape _model, under the key _key)."""
     _sample = _model = _key = None
@@ -1852,6 +1882,85 @@ class EssentialBatch(_RansacBatch):
         self._chk(self._L.sim3opt_essential_batch_debug_pose(self._b, _p(e, _dp), _p(m, _up), _p(ca, _dp), _p(vo, _ip),
                                                              _p(wi, _ip), _p(mo, _up)), "essential_batch_debug_pose")
         return dict(candidates=ca, votes=vo, winner=wi, mask=mo)
+
+
+HOMOGRAPHY_OK, HOMOGRAPHY_FEW_POINTS, HOMOGRAPHY_NO_HYPOTHESIS, HOMOGRAPHY_NO_INLIERS, HOMOGRAPHY_DEGENERATE = 0, 1, 2, 3, 4
+HOMOGRAPHY_MAX_ROUNDS = 8
+
+
+class HomographyBatch(_RansacBatch):
+    """sim3opt_homography_batch*: the loop detector's planar relative pose (HomographyInit::Compute,
+    kittiDetector.h:1387-1443; HomographyInit.cc) of a whole batch of loop candidates in one kernel launch -- four-point
+    homographies from a reproducible sampler scored by MLESAC, the best one refined on its inliers by Tukey-reweighted
+    rounds, decomposed into eight (R, t, n, d) and chosen by the visibility tests and the Sampson tie-break.  Problem k
+    owns the correspondences point_ptr[k]:point_ptr[k+1] of uv0 / uv1: exactly MatchBatch's match_ptr, uv0, uv1."""
+    _prefix, _Options = "homography_batch", HomographyBatchOptions
+    # (poses() is se3SecondFromFirst (X1 = R X0 + t), t not normalised; inliers() are mvHomographyInliers)
+    _sample, _model, _key, _dims_extra = 4, (3, 3), "H", (None,)
+
+    def set_problems(self, point_ptr, uv0, uv1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        self._set_problems(point_ptr, _f64(uv0).reshape(-1, 2), _f64(uv1).reshape(-1, 2), focal, cx, cy, "observation")
+
+    def tiles(self):
+        """(points staged in LDS at most, hypotheses of a chunk): the sizes at which the kernel takes another path"""
+        t = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.sim3opt_homography_batch_dims(self._b, None, None, _p(t, _ip)), "homography_batch_dims")
+        return int(t[0]), int(t[1])
+
+    def homographies(self):
+        """(mlesac (n, 3, 3) of Frobenius norm 1, refined (n, 3, 3)): second ~ H first in camera-plane coordinates"""
+        n = self.dims()[0]
+        a, b = np.empty((n, 3, 3)), np.empty((n, 3, 3))
+        self._chk(self._L.sim3opt_homography_batch_get_homographies(self._b, _p(a, _dp), _p(b, _dp)),
+                  "homography_batch_get_homographies")
+        return a, b
+
+    def summary(self):
+        """dict of (n,) arrays: status, best_hypothesis, cost_hypothesis, n_inliers, choice, ambiguous, and sigma2
+        (n, refine_rounds), counts_first (n, 8), kept (n, 4), counts_second (n, 4), sampson (n, 2)"""
+        n = self.dims()[0]
+        i = lambda *s: np.empty((n,) + s, dtype=np.int32)
+        st, bh, ch, ni, sg = i(), i(), np.empty(n), i(), np.empty((n, HOMOGRAPHY_MAX_ROUNDS))
+        c1, ke, c2, cho, am, sa = i(8), i(4), i(4), i(), i(), np.empty((n, 2))
+        self._chk(self._L.sim3opt_homography_batch_get_summary(
+            self._b, _p(st, _ip), _p(bh, _ip), _p(ch, _dp), _p(ni, _ip), _p(sg, _dp), _p(c1, _ip), _p(ke, _ip),
+            _p(c2, _ip), _p(cho, _ip), _p(am, _ip), _p(sa, _dp)), "homography_batch_get_summary")
+        return dict(status=st, best_hypothesis=bh, cost_hypothesis=ch, n_inliers=ni,
+                    sigma2=sg[:, :self._opt.refine_rounds].copy(), counts_first=c1, kept=ke, counts_second=c2,
+                    choice=cho, ambiguous=am, sampson=sa)
+
+    def _h_and_mask(self, homographies, mask):
+        n, t = self.dims()
+        h = _f64(homographies).reshape(-1)
+        m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        if h.shape[0] != 9 * n or m.shape[0] != t:
+            raise ValueError("homographies holds 9 numbers per problem, mask one entry per point")
+        return n, h, m
+
+    def debug_refine(self, homographies, mask):
+        """The kernel's refinement rounds from homographies (n, 3, 3) on mask (total,): dict of sigma2
+        (n, refine_rounds) and H (n, refine_rounds, 3, 3) after every round."""
+        n, h, m = self._h_and_mask(homographies, mask)
+        r = self._opt.refine_rounds
+        sg, hr = np.zeros((n, r)), np.zeros((n, r, 3, 3))
+        self._chk(self._L.sim3opt_homography_batch_debug_refine(self._b, _p(h, _dp), _p(m, _up), _p(sg, _dp),
+                                                                _p(hr, _dp)), "homography_batch_debug_refine")
+        return dict(sigma2=sg, H=hr)
+
+    def debug_decompose(self, homographies, mask):
+        """The kernel's decomposition and choice of homographies (n, 3, 3) on mask (total,): dict of R (n, 8, 3, 3),
+        t, normal (n, 8, 3), d (n, 8), status, choice, ambiguous (n,), counts_first (n, 8), kept, counts_second (n, 4),
+        sampson (n, 2), pose (n, 7)."""
+        n, h, m = self._h_and_mask(homographies, mask)
+        i = lambda *s: np.empty((n,) + s, dtype=np.int32)
+        de, st, c1, ke, c2, cho, am = np.empty((n, 8, 16)), i(), i(8), i(4), i(4), i(), i()
+        sa, po = np.empty((n, 2)), np.empty((n, 7))
+        self._chk(self._L.sim3opt_homography_batch_debug_decompose(
+            self._b, _p(h, _dp), _p(m, _up), _p(de, _dp), _p(st, _ip), _p(c1, _ip), _p(ke, _ip), _p(c2, _ip),
+            _p(cho, _ip), _p(am, _ip), _p(sa, _dp), _p(po, _dp)), "homography_batch_debug_decompose")
+        return dict(R=de[:, :, :9].reshape(n, 8, 3, 3).copy(), t=de[:, :, 9:12].copy(), normal=de[:, :, 12:15].copy(),
+                    d=de[:, :, 15].copy(), status=st, counts_first=c1, kept=ke, counts_second=c2, choice=cho,
+                    ambiguous=am, sampson=sa, pose=po)
 
 
 MATCH_OK, MATCH_NO_KEYPOINTS, MATCH_NO_MAP = 0, 1, 2
