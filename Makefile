@@ -7,7 +7,8 @@
 #                           tests/cxx/pnp_conformance (the PnP RANSAC helper feeding it),
 #                           tests/cxx/match_conformance (the matching helper feeding that),
 #                           tests/cxx/essential_conformance (the essential-matrix RANSAC helper),
-#                           tests/cxx/homography_conformance (the homography MLESAC helper)
+#                           tests/cxx/homography_conformance (the homography MLESAC helper),
+#                           tests/cxx/sim3_batch_conformance (the Sim(3) measurement and information helper)
 #   make LIB=/some/where/libsim3opt.so   builds the library elsewhere (used by the tests)
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC  := sim3opt_amd/csrc
@@ -34,7 +35,8 @@ conformance: $(LIB) tests/cxx/shim_conformance.cpp tests/cxx/ba_shim_conformance
              tests/cxx/pnp_conformance.cpp include/sim3opt_g2o.hpp include/sim3opt_g2o_ba.hpp include/sim3opt_two_view.hpp \
              include/sim3opt_pnp.hpp tests/cxx/match_conformance.cpp include/sim3opt_match.hpp \
              tests/cxx/essential_conformance.cpp include/sim3opt_essential.hpp \
-             tests/cxx/homography_conformance.cpp include/sim3opt_homography.hpp
+             tests/cxx/homography_conformance.cpp include/sim3opt_homography.hpp \
+             tests/cxx/sim3_batch_conformance.cpp include/sim3opt_sim3_batch.hpp
 	g++ -std=c++17 -Wall -DSIM3OPT_G2O_NAMES -Iinclude $(EIGEN_INC) tests/cxx/shim_conformance.cpp \
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/shim_conformance
 	g++ -std=c++17 -Wall -DSIM3OPT_G2O_BA_NAMES -Iinclude $(EIGEN_INC) tests/cxx/ba_shim_conformance.cpp \
@@ -49,10 +51,12 @@ conformance: $(LIB) tests/cxx/shim_conformance.cpp tests/cxx/ba_shim_conformance
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/essential_conformance
 	g++ -std=c++17 -Wall -Iinclude tests/cxx/homography_conformance.cpp \
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/homography_conformance
+	g++ -std=c++17 -Wall -Iinclude tests/cxx/sim3_batch_conformance.cpp \
+	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/sim3_batch_conformance
 
 clean:
 	rm -f sim3opt_amd/libsim3opt.so oracle/liboracle_sim3.so examples/direct_pgo tests/cxx/shim_conformance \
 	    tests/cxx/ba_shim_conformance tests/cxx/two_view_conformance tests/cxx/pnp_conformance tests/cxx/match_conformance \
-	    tests/cxx/essential_conformance tests/cxx/homography_conformance
+	    tests/cxx/essential_conformance tests/cxx/homography_conformance tests/cxx/sim3_batch_conformance
 
 .PHONY: all example conformance clean

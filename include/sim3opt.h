@@ -1294,6 +1294,120 @@ int sim3opt_homography_batch_debug_decompose(sim3opt_homography_batch* b, const 
                                              int32_t* counts_first, int32_t* kept, int32_t* counts_second,
                                              int32_t* choice, int32_t* ambiguous, double* sampson, double* poses);
 
+/* ---- batched Sim(3) RANSAC and refinement: a loop edge with its information, every candidate in one launch ----
+ * What sim3opt_add_edge / sim3opt_gate_edges consume and nothing upstream produced: a Sim(3) measurement C with
+ * X1 ~ s R X0 + t between the two frames of a candidate, each at its own map's scale, and Omega, the information of C.
+ * PARITY UNPINNED: the reference has no such step.  Its scale is a ratio of median depths (kittiDetector.h:1305-1311;
+ * sim3opt_median_depth_ratio), rotation and translation come from a rigid two-view BA, every loop edge carries
+ * Identity(7) (kitti_surf.cpp:167, 202) and Constraint::fisher_information (kittiDetector.h:404-422) is never filled.
+ * The method is Horn's closed form as ORB-SLAM's Sim3Solver / OptimizeSim3 use it.  Deviations from ORB-SLAM: the
+ * sampler is counter-based; the rotation is the eigenvector of Horn's 4 x 4 matrix by ten cyclic Jacobi sweeps (there:
+ * cv::eigen); errors are taken on the camera plane and scaled by f; the refinement is a Levenberg-Marquardt under this
+ * library's damping rule on a fixed inlier set (there: five g2o iterations, outliers dropped, five more); exp has the
+ * exact small-angle limit of its B coefficient (fix_small_angle_b = 1 of the pose-graph options); there is no early
+ * termination of the hypotheses: all `iterations` are made and scored.
+ * Definition.
+ * Points: (x, y) = ((u - cx) / f, (v - cy) / f), X0 = depth0 (x0, y0, 1), X1 = depth1 (x1, y1, 1), in double, every
+ * product and sum rounded on its own (no fused multiply-add).
+ * Sampler: draw j (0..2) of hypothesis h is splitmix64(seed + (3 h + j + 1) * 0x9E3779B97F4A7C15) modulo n - j, stepped
+ * over the earlier picks in ascending order.
+ * Hypothesis: centred a_i = X0_i - mean, b_i = X1_i - mean; S = sum a_i b_i^T; the unit eigenvector (qw >= 0) of the
+ * largest eigenvalue of Horn's N(S) is R; s = sum b_i . R a_i / sum |a_i|^2 (Horn's asymmetric form);
+ * t = mean1 - s R mean0.  Invalid (the identity stored, not scored): |a x b|^2 <= min_triangle_sin2 |a|^2 |b|^2 for the
+ * edges a, b at the sample's first point in either frame (collinear or repeated points); s not finite and positive; a
+ * sample point with non-positive depth under C or C^-1.
+ * Scoring: Y = s R X0 + t, Z = C^-1 X1; e1 = f^2 |Y.xy / Y.z - (x1, y1)|^2, e0 = f^2 |Z.xy / Z.z - (x0, y0)|^2; a match
+ * is an inlier iff Y.z > 0, Z.z > 0, e1 <= max_pixel_error^2 and e0 <= max_pixel_error^2, and then costs e0 + e1.  Best:
+ * the largest count, then the smallest cost, then the smallest index.
+ * Refinement on the best hypothesis's inliers, fixed: C <- exp(delta) C with delta = [omega, upsilon, sigma] (g2o's
+ * Sim(3) exp), four residuals a match, Huber of width huber_delta per 2-vector (0: none), analytic Jacobians, at most
+ * refine_iters iterations of at most max_trials trials, lambda_0 = tau max diag; it also ends when a step promises less
+ * than 1e-9 of chi2.  The sums are reduced in a fixed order: a thread's matches (t, t + 256, ...) ascending, a
+ * butterfly over the wavefront, the four wavefronts in order.  Points are fixed (ORB-SLAM's choice): Omega is
+ * optimistic -- the back-projected points carry the pixel noise (measured: about 3.5 times in d2 with exact depths)
+ * and depth error is not seen; pixel_noise scales it.
+ * Result: the mask re-derived under the refined C with the scoring rule, its count, RMS = sqrt(sum (e0 + e1) / (2 count)),
+ * Omega = sum w J^T J / pixel_noise^2 over it (w: the Huber weights, J: the derivative by the same left perturbation):
+ * with EdgeSim3's residual log(C S0 S1^-1) an estimate exp(eps) C* has the residual eps at the true vertices, so Omega
+ * is the `info` of sim3opt_add_edge / sim3opt_gate_edges as it stands, with no adjoint.
+ * Device pipeline: sim3opt_amd/csrc/sim3_batch.hip, one workgroup per problem, one launch.  A problem's result does not
+ * depend on the other problems of the batch or on its place among them.  No CPU fallback: SIM3OPT_ERR_NO_DEVICE
+ * without a GPU. */
+typedef struct sim3opt_sim3_batch sim3opt_sim3_batch;
+
+typedef struct sim3opt_sim3_batch_options {
+  double max_pixel_error;   /* inlier: both errors <= max_pixel_error^2 [px]        default sqrt(9.210): chi^2_2 0.99, 1 px */
+  double huber_delta;       /* Huber width per reprojection [px]; 0: no kernel      default sqrt(9.210)                    */
+  double pixel_noise;       /* Omega is divided by its square [px]                   default 1                              */
+  double min_triangle_sin2; /* a sample's triangle is degenerate at or below, [0, 1) default 1e-6                           */
+  double tau;               /* lambda_0 = tau * max diag(J^T W J)                    default 1e-5                           */
+  uint64_t seed;            /* of the sampler                                        default 0                              */
+  int32_t iterations;       /* hypotheses per problem, 1..4096                       default 300                            */
+  int32_t min_points;       /* fewer matches: status 1, nothing run; >= 3            default 9                              */
+  int32_t min_inliers;      /* fewer final inliers: status 3                         default 10                             */
+  int32_t refine_iters;     /* LM iterations at most; 0: none                        default 10                             */
+  int32_t max_trials;       /* LM trials an iteration at most, >= 1                  default 5                              */
+  int32_t device;           /* HIP device ordinal, -1 = current                      default -1                             */
+} sim3opt_sim3_batch_options;
+
+#define SIM3OPT_SIM3_OK 0               /* C, Omega and the inliers                                                     */
+#define SIM3OPT_SIM3_FEW_POINTS 1       /* fewer than min_points matches: nothing run, C the identity, Omega zero        */
+#define SIM3OPT_SIM3_NO_HYPOTHESIS 2    /* no sample gave a C: likewise                                                 */
+#define SIM3OPT_SIM3_FEW_INLIERS 3      /* fewer than min_inliers final inliers; C and Omega as computed                */
+#define SIM3OPT_SIM3_NOT_POSITIVE 4     /* Omega's Cholesky fails on the device; C and Omega as computed                */
+
+void sim3opt_sim3_batch_options_default(sim3opt_sim3_batch_options* o);
+sim3opt_sim3_batch* sim3opt_sim3_batch_create(void);
+void sim3opt_sim3_batch_destroy(sim3opt_sim3_batch* b);
+const char* sim3opt_sim3_batch_last_error(const sim3opt_sim3_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: iterations outside 1..4096; max_pixel_error, pixel_noise or tau <= 0 or not finite;
+ * huber_delta < 0 or not finite; min_triangle_sin2 outside [0, 1); min_inliers < 0; min_points < 3; refine_iters < 0;
+ * max_trials < 1. */
+int sim3opt_sim3_batch_set_options(sim3opt_sim3_batch* b, const sim3opt_sim3_batch_options* o);
+/* n_problems candidates at once: point_ptr (n_problems + 1, ragged, point_ptr[0] = 0), uv0 and uv1 (total x 2), depth0
+ * and depth1 (total) -- exactly the match_ptr, uv0, uv1, depth0, depth1 that sim3opt_match_batch_get_* return -- and
+ * focal / cx / cy.  SIM3OPT_ERR_ARG with nothing changed: n_problems < 1, a problem with no match, a non-monotone
+ * point_ptr, a non-finite number, a depth <= 0, focal <= 0, a NULL array.  A problem with fewer than min_points matches
+ * is accepted and ends with status 1. */
+int sim3opt_sim3_batch_set_problems(sim3opt_sim3_batch* b, int32_t n_problems, const int32_t* point_ptr,
+                                    const double* uv0, const double* uv1, const double* depth0, const double* depth1,
+                                    double focal, double cx, double cy);
+/* Each may be NULL.  tiles[2]: the matches staged in LDS at most and the hypotheses of a chunk: the sizes at which the
+ * kernel takes another path. */
+int sim3opt_sim3_batch_dims(const sim3opt_sim3_batch* b, int32_t* n_problems, int32_t* total_points, int32_t tiles[2]);
+/* Every problem, ONE kernel launch for the batch.  Returns the number of problems with status 0, or a negative
+ * SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no problems set); one problem's failure is its status, never the batch's. */
+int sim3opt_sim3_batch_solve(sim3opt_sim3_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  sim3: n x 8 [qx qy qz qw tx ty tz s], the `meas` of
+ * sim3opt_add_edge(v0 = frame 0, v1 = frame 1); information: n x 49, column-major, its `info`.  One may be NULL. */
+int sim3opt_sim3_batch_get_sim3(const sim3opt_sim3_batch* b, double* sim3, double* information);
+/* mask (total, 1 = final inlier) and / or n_inliers (n) */
+int sim3opt_sim3_batch_get_inliers(const sim3opt_sim3_batch* b, uint8_t* mask, int32_t* n_inliers);
+/* Per problem (each may be NULL): status (SIM3OPT_SIM3_*), the index of the best hypothesis (-1: none), its inlier
+ * count and cost, the RMS pixel error of the final inliers, the LM iterations run, chi2 before and after them (n x 2). */
+int sim3opt_sim3_batch_get_summary(const sim3opt_sim3_batch* b, int32_t* status, int32_t* best_hypothesis,
+                                   int32_t* n_inliers_hypothesis, double* cost_hypothesis, double* rms_px,
+                                   int32_t* refine_iterations, double* chi2);
+/* Diagnostics.  Each leaves the results of the last solve as they were.
+ * What the last solve computed for `problem`, H = options.iterations hypotheses: sample (H x 3 match indices),
+ * n_solutions (1 where valid), valid, sim3 (H x 8; the identity where not valid), count and cost of the scoring (0 where
+ * not valid).  Each may be NULL.  SIM3OPT_ERR_STATE before the first solve. */
+int sim3opt_sim3_batch_debug_hypotheses(sim3opt_sim3_batch* b, int32_t problem, int32_t* sample, int32_t* n_solutions,
+                                        int32_t* valid, double* sim3, int32_t* count, double* cost);
+/* P (1..4096) supplied C per problem (sims: n x P x 8, finite, unit quaternions) through the scoring code of
+ * k_sim3_ransac: count and cost (n x P each, one may be NULL). */
+int sim3opt_sim3_batch_debug_score(sim3opt_sim3_batch* b, int32_t P, const double* sims, int32_t* count, double* cost);
+/* The refinement from a supplied C per problem (sims: n x 8, finite, unit quaternion, s > 0) on a supplied inlier set
+ * (mask: total): the refined C (n x 8), the iterations run (n), chi2 before and after (n x 2), the trials of every
+ * iteration (n x refine_iters, zero beyond those run).  The outputs may be NULL. */
+int sim3opt_sim3_batch_debug_refine(sim3opt_sim3_batch* b, const double* sims, const uint8_t* mask, double* sim_out,
+                                    int32_t* iterations, double* chi2, int32_t* trials);
+/* Omega (n x 49, column-major) and the Huber weights of every match (total x 2: the reprojection in image 1, in image
+ * 0; zero outside the mask) at a supplied C on a supplied mask, with no LM; positive_definite (n): whether Omega's
+ * Cholesky succeeds.  At least one output. */
+int sim3opt_sim3_batch_debug_information(sim3opt_sim3_batch* b, const double* sims, const uint8_t* mask,
+                                         double* information, double* weights, int32_t* positive_definite);
+
 /* ---- batched descriptor matching and map-depth lookup: what the three blocks above consume, every candidate at once ----
  * The front of computeConstraints: matcher.match / knnMatch(.., 2) with the ratio test, the 1/10 image-border filter,
  * the skew filter and the uniqueness pass (kittiDetector.h:1085-1160), then the depth of every kept match in both

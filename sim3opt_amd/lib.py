@@ -179,6 +179,24 @@ class HomographyBatchOptions(C.Structure):
     ]
 
 
+class Sim3BatchOptions(C.Structure):
+    """sim3opt_sim3_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("max_pixel_error", C.c_double),
+        ("huber_delta", C.c_double),
+        ("pixel_noise", C.c_double),
+        ("min_triangle_sin2", C.c_double),
+        ("tau", C.c_double),
+        ("seed", C.c_uint64),
+        ("iterations", C.c_int32),
+        ("min_points", C.c_int32),
+        ("min_inliers", C.c_int32),
+        ("refine_iters", C.c_int32),
+        ("max_trials", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class MatchBatchOptions(C.Structure):
     """sim3opt_match_batch_options (include/sim3opt.h), field for field."""
     _fields_ = [
@@ -415,6 +433,22 @@ SYMBOLS = {
     "sim3opt_homography_batch_debug_refine": (C.c_int, [_vp, _dp, _up, _dp, _dp]),
     "sim3opt_homography_batch_debug_decompose": (C.c_int, [_vp, _dp, _up, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _dp,
                                                            _dp]),
+    "sim3opt_sim3_batch_options_default": (None, [C.POINTER(Sim3BatchOptions)]),
+    "sim3opt_sim3_batch_create": (_vp, []),
+    "sim3opt_sim3_batch_destroy": (None, [_vp]),
+    "sim3opt_sim3_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_sim3_batch_set_options": (C.c_int, [_vp, C.POINTER(Sim3BatchOptions)]),
+    "sim3opt_sim3_batch_set_problems": (C.c_int, [_vp, C.c_int32, _ip, _dp, _dp, _dp, _dp, C.c_double, C.c_double,
+                                                  C.c_double]),
+    "sim3opt_sim3_batch_dims": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "sim3opt_sim3_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_sim3_batch_get_sim3": (C.c_int, [_vp, _dp, _dp]),
+    "sim3opt_sim3_batch_get_inliers": (C.c_int, [_vp, _up, _ip]),
+    "sim3opt_sim3_batch_get_summary": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp, _ip, _dp]),
+    "sim3opt_sim3_batch_debug_hypotheses": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _ip, _dp]),
+    "sim3opt_sim3_batch_debug_score": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp]),
+    "sim3opt_sim3_batch_debug_refine": (C.c_int, [_vp, _dp, _up, _dp, _ip, _dp, _ip]),
+    "sim3opt_sim3_batch_debug_information": (C.c_int, [_vp, _dp, _up, _dp, _dp, _ip]),
     "sim3opt_match_batch_options_default": (None, [C.POINTER(MatchBatchOptions)]),
     "sim3opt_match_batch_create": (_vp, []),
     "sim3opt_match_batch_destroy": (None, [_vp]),
@@ -1427,7 +1461,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -1712,7 +1746,7 @@ class TwoViewBatch(_Handle):
 
 
 class _RansacBatch(_Handle):
-    """What PnpBatch, EssentialBatch and HomographyBatch share (csrc/ransac_frame.hpp): a batch of problems, each owning the rows
+    """What PnpBatch, EssentialBatch, HomographyBatch and Sim3Batch share (csrc/ransac_frame.hpp): a batch of problems, each owning the rows
     point_ptr[k]:point_ptr[k+1] of two flat arrays; one launch makes `iterations` hypotheses per problem from samples
     of _sample points, scores every one and keeps the best model (of shape _model, under the key _key)."""
     _sample = _model = _key = None
@@ -1735,12 +1769,6 @@ class _RansacBatch(_Handle):
     def solve(self):
         """Problems with status 0 (one launch); raises when the library reports an error."""
         return self._count(self._fn("solve")(self._b), f"{self._prefix}_solve")
-
-    def poses(self):
-        """(n, 7) [qx qy qz qw tx ty tz]"""
-        out = np.empty((self.dims()[0], 7))
-        self._chk(self._fn("get_poses")(self._b, _p(out, _dp)), f"{self._prefix}_get_poses")
-        return out
 
     def inliers(self):
         """(mask (total,) uint8, n_inliers (n,))"""
@@ -1771,10 +1799,20 @@ class _RansacBatch(_Handle):
         return co, cs
 
 
+class _PoseRansacBatch(_RansacBatch):
+    """... whose result is a rigid pose (PnpBatch, EssentialBatch, HomographyBatch; Sim3Batch's is a similarity)"""
+
+    def poses(self):
+        """(n, 7) [qx qy qz qw tx ty tz]"""
+        out = np.empty((self.dims()[0], 7))
+        self._chk(self._fn("get_poses")(self._b, _p(out, _dp)), f"{self._prefix}_get_poses")
+        return out
+
+
 PNP_OK, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS, PNP_FEW_INLIERS = 0, 1, 2, 3
 
 
-class PnpBatch(_RansacBatch):
+class PnpBatch(_PoseRansacBatch):
     """sim3opt_pnp_batch*: the loop detector's start pose (cv::solvePnPRansac, kittiDetector.h:1300-1301) of a whole
     batch of loop candidates in one kernel launch -- P3P hypotheses from a reproducible sampler, every one scored,
     an LM refit over the best one's inliers.  Problem k owns the points point_ptr[k]:point_ptr[k+1] of the flat
@@ -1830,7 +1868,7 @@ def median_depth_ratio(point_ptr, depth0, depth1):
 ESSENTIAL_OK, ESSENTIAL_FEW_POINTS, ESSENTIAL_NO_HYPOTHESIS, ESSENTIAL_NO_POSE = 0, 1, 2, 3
 
 
-class EssentialBatch(_RansacBatch):
+class EssentialBatch(_PoseRansacBatch):
     """sim3opt_essential_batch*: the loop detector's essential matrix and relative pose (ExtractCameras,
     kittiDetector.h:279-293: cv::findEssentialMat + cv::recoverPose) of a whole batch of loop candidates in one kernel
     launch -- five-point hypotheses from a reproducible sampler, every one scored by its Sampson inliers, the best
@@ -1888,7 +1926,7 @@ HOMOGRAPHY_OK, HOMOGRAPHY_FEW_POINTS, HOMOGRAPHY_NO_HYPOTHESIS, HOMOGRAPHY_NO_IN
 HOMOGRAPHY_MAX_ROUNDS = 8
 
 
-class HomographyBatch(_RansacBatch):
+class HomographyBatch(_PoseRansacBatch):
     """sim3opt_homography_batch*: the loop detector's planar relative pose (HomographyInit::Compute,
     kittiDetector.h:1387-1443; HomographyInit.cc) of a whole batch of loop candidates in one kernel launch -- four-point
     homographies from a reproducible sampler scored by MLESAC, the best one refined on its inliers by Tukey-reweighted
@@ -1961,6 +1999,86 @@ class HomographyBatch(_RansacBatch):
         return dict(R=de[:, :, :9].reshape(n, 8, 3, 3).copy(), t=de[:, :, 9:12].copy(), normal=de[:, :, 12:15].copy(),
                     d=de[:, :, 15].copy(), status=st, counts_first=c1, kept=ke, counts_second=c2, choice=cho,
                     ambiguous=am, sampson=sa, pose=po)
+
+
+SIM3_OK, SIM3_FEW_POINTS, SIM3_NO_HYPOTHESIS, SIM3_FEW_INLIERS, SIM3_NOT_POSITIVE = 0, 1, 2, 3, 4
+
+
+class Sim3Batch(_RansacBatch):
+    """sim3opt_sim3_batch*: the Sim(3) measurement of a whole batch of loop candidates with its information matrix in
+    one kernel launch -- Horn's closed form on three 3-D -- 3-D matches from a reproducible sampler, every hypothesis
+    scored on the reprojection errors in both images, an LM refinement of the best one on its inliers, Omega over the
+    final inliers.  Problem k owns the matches point_ptr[k]:point_ptr[k+1]: exactly MatchBatch's match_ptr, uv0, uv1,
+    depth0, depth1.  sim3() and information() are the meas and info of Graph.add_edges / Graph.gate_edges."""
+    _prefix, _Options = "sim3_batch", Sim3BatchOptions
+    _sample, _model, _key, _dims_extra = 3, (8,), "sim3", (None,)
+
+    def set_problems(self, point_ptr, uv0, uv1, depth0, depth1, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        ptr = _i32(point_ptr).reshape(-1)
+        a, b = _f64(uv0).reshape(-1, 2), _f64(uv1).reshape(-1, 2)
+        d0, d1 = _f64(depth0).reshape(-1), _f64(depth1).reshape(-1)
+        n = ptr.shape[0] - 1
+        if n >= 1 and not (a.shape[0] == b.shape[0] == d0.shape[0] == d1.shape[0] and a.shape[0] >= ptr.max()):
+            raise ValueError("observation and depth arrays shorter than point_ptr says")
+        self._chk(self._L.sim3opt_sim3_batch_set_problems(self._b, n, _p(ptr, _ip), _p(a, _dp), _p(b, _dp), _p(d0, _dp),
+                                                          _p(d1, _dp), focal, cx, cy), "sim3_batch_set_problems")
+
+    def tiles(self):
+        """(matches staged in LDS at most, hypotheses of a chunk): the sizes at which the kernel takes another path"""
+        t = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.sim3opt_sim3_batch_dims(self._b, None, None, _p(t, _ip)), "sim3_batch_dims")
+        return int(t[0]), int(t[1])
+
+    def sim3(self):
+        """(n, 8) [qx qy qz qw tx ty tz s]: X1 ~ s R X0 + t"""
+        out = np.empty((self.dims()[0], 8))
+        self._chk(self._L.sim3opt_sim3_batch_get_sim3(self._b, _p(out, _dp), None), "sim3_batch_get_sim3")
+        return out
+
+    def information(self):
+        """(n, 7, 7) indexed [k, r, c], tangent order [omega upsilon sigma]: what add_edges / gate_edges take as info"""
+        out = np.empty((self.dims()[0], 49))
+        self._chk(self._L.sim3opt_sim3_batch_get_sim3(self._b, None, _p(out, _dp)), "sim3_batch_get_sim3")
+        return out.reshape(-1, 7, 7).transpose(0, 2, 1).copy()
+
+    def summary(self):
+        """dict of (n,) arrays: status, best_hypothesis, n_inliers_hypothesis, cost_hypothesis, rms_px,
+        refine_iterations, and chi2 (n, 2: before, after the refinement)"""
+        n = self.dims()[0]
+        i = lambda: np.empty(n, dtype=np.int32)
+        st, bh, nh, ch, rm, ri, c2 = i(), i(), i(), np.empty(n), np.empty(n), i(), np.empty((n, 2))
+        self._chk(self._L.sim3opt_sim3_batch_get_summary(self._b, _p(st, _ip), _p(bh, _ip), _p(nh, _ip), _p(ch, _dp),
+                                                         _p(rm, _dp), _p(ri, _ip), _p(c2, _dp)),
+                  "sim3_batch_get_summary")
+        return dict(status=st, best_hypothesis=bh, n_inliers_hypothesis=nh, cost_hypothesis=ch, rms_px=rm,
+                    refine_iterations=ri, chi2=c2)
+
+    def _sims_and_mask(self, sims, mask):
+        n, t = self.dims()
+        q = _f64(sims).reshape(-1)
+        m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        if q.shape[0] != 8 * n or m.shape[0] != t:
+            raise ValueError("sims holds 8 numbers per problem, mask one entry per match")
+        return n, t, q, m
+
+    def debug_refine(self, sims, mask):
+        """The kernel's refinement from sims (n, 8) on mask (total,): dict of sim3 (n, 8), iterations (n,), chi2
+        (n, 2: before, after), trials (n, refine_iters)."""
+        n, t, q, m = self._sims_and_mask(sims, mask)
+        po, it, ch = np.empty((n, 8)), np.empty(n, dtype=np.int32), np.empty((n, 2))
+        tr = np.zeros((n, self._opt.refine_iters), dtype=np.int32)
+        self._chk(self._L.sim3opt_sim3_batch_debug_refine(self._b, _p(q, _dp), _p(m, _up), _p(po, _dp), _p(it, _ip),
+                                                          _p(ch, _dp), _p(tr, _ip)), "sim3_batch_debug_refine")
+        return dict(sim3=po, iterations=it, chi2=ch, trials=tr)
+
+    def debug_information(self, sims, mask):
+        """Omega and the Huber weights at sims (n, 8) on mask (total,), no LM: dict of information (n, 7, 7) [k, r, c],
+        weights (total, 2: image 1, image 0), positive_definite (n,)."""
+        n, t, q, m = self._sims_and_mask(sims, mask)
+        om, w, pd = np.empty((n, 49)), np.empty((t, 2)), np.empty(n, dtype=np.int32)
+        self._chk(self._L.sim3opt_sim3_batch_debug_information(self._b, _p(q, _dp), _p(m, _up), _p(om, _dp), _p(w, _dp),
+                                                               _p(pd, _ip)), "sim3_batch_debug_information")
+        return dict(information=om.reshape(-1, 7, 7).transpose(0, 2, 1).copy(), weights=w, positive_definite=pd)
 
 
 MATCH_OK, MATCH_NO_KEYPOINTS, MATCH_NO_MAP = 0, 1, 2

@@ -1,0 +1,307 @@
+"""An independent numpy restatement of the batched Sim(3) stage (sim3opt_sim3_batch, include/sim3opt.h): the sampler,
+the hypothesis by Umeyama's method through numpy.linalg.svd (the kernel: Horn's 4 x 4 eigenproblem by Jacobi sweeps),
+scoring and every other sum in long double in the order of the matches, the refinement's residuals through
+sim3np.exp, and its Jacobians by fourth-order central differences of those residuals in long double -- no closed form
+is shared with sim3_batch_math.hpp.  The damping rule is restated from g2o's OptimizationAlgorithmLevenberg.
+
+`defect` seeds one wrong line (tests/test_sim3_batch_ref.py shows that each is noticed):
+  scale_swapped, inverse_t_unscaled, tangent_order, right_perturbation, huber_squared, mask_not_rederived,
+  omega_transposed, lane_stride_once
+omega_transposed is contrived on purpose: Omega is symmetric, so a genuine transposition -- row-major where
+column-major is meant -- changes nothing and no test can see it; what is seeded is a lower triangle filled from the wrong
+entries (rolled by one column), the kind of indexing slip a triangular fill can make.
+"""
+import numpy as np
+
+from sim3opt_amd import sim3np
+
+LD = np.longdouble
+DEFAULTS = dict(max_pixel_error=float(np.sqrt(9.210)), huber_delta=float(np.sqrt(9.210)), pixel_noise=1.0,
+                min_triangle_sin2=1e-6, tau=1e-5, seed=0, iterations=300, min_points=9, min_inliers=10, refine_iters=10,
+                max_trials=5)
+GAIN_TOL = 1e-9
+MASK64 = (1 << 64) - 1
+DEFECTS = ("scale_swapped", "inverse_t_unscaled", "tangent_order", "right_perturbation", "huber_squared",
+           "mask_not_rederived", "omega_transposed", "lane_stride_once")
+
+
+def splitmix64(x):
+    z = (x + 0x9E3779B97F4A7C15) & MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & MASK64
+    return z ^ (z >> 31)
+
+
+def sample(seed, h, n, k=3):
+    """k distinct indices below n: draw j picks among the n - j not yet taken, stepped over the earlier picks"""
+    taken, out = [], []
+    for j in range(k):
+        i = splitmix64((seed + (k * h + j + 1) * 0x9E3779B97F4A7C15) & MASK64) % (n - j)
+        for t in sorted(taken):
+            if t <= i:
+                i += 1
+        taken.append(i)
+        out.append(i)
+    return out
+
+
+def points(uv, depth, f, cx, cy):
+    """depth K^-1 (u, v, 1), long double (n, 3)"""
+    uv, d = np.asarray(uv, dtype=LD), np.asarray(depth, dtype=LD)
+    return np.stack([d * (uv[:, 0] - cx) / f, d * (uv[:, 1] - cy) / f, d], axis=1)
+
+
+def quat_to_R(q):
+    x, y, z, w = [LD(v) for v in q]
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], dtype=LD)
+
+
+def both_ways(C, defect=None):
+    """(s R, t, (1 / s) R^T, -(1 / s) R^T t) of C = [q t s], long double"""
+    R, t, s = quat_to_R(C[:4]), np.asarray(C[4:7], dtype=LD), LD(C[7])
+    if defect == "scale_swapped":
+        s = 1 / s
+    Ai = R.T / s
+    ti = -(R.T @ t) if defect == "inverse_t_unscaled" else -(Ai @ t)
+    return s * R, t, Ai, ti
+
+
+def residuals(C, X0, X1, uv0, uv1, f, cx, cy, defect=None):
+    """(r1 (n, 2) = pi(C X0) - uv1, r0 (n, 2) = pi(C^-1 X1) - uv0, front (n,) bool), long double"""
+    A, t, Ai, ti = both_ways(C, defect)
+    Y, Z = X0 @ A.T + t, X1 @ Ai.T + ti
+    with np.errstate(all="ignore"):
+        r1 = np.stack([f * Y[:, 0] / Y[:, 2] + cx, f * Y[:, 1] / Y[:, 2] + cy], axis=1) - np.asarray(uv1, dtype=LD)
+        r0 = np.stack([f * Z[:, 0] / Z[:, 2] + cx, f * Z[:, 1] / Z[:, 2] + cy], axis=1) - np.asarray(uv0, dtype=LD)
+    return r1, r0, (Y[:, 2] > 0) & (Z[:, 2] > 0)
+
+
+def errors(C, D, defect=None):
+    """(e1, e0 (n,) squared pixel errors, front)"""
+    r1, r0, front = residuals(C, D["X0"], D["X1"], D["uv0"], D["uv1"], D["f"], D["cx"], D["cy"], defect)
+    return (r1 ** 2).sum(1), (r0 ** 2).sum(1), front
+
+
+def score(C, D, max2, defect=None):
+    """(mask, count, cost = sum of e0 + e1 over the inliers)"""
+    e1, e0, front = errors(C, D, defect)
+    with np.errstate(invalid="ignore"):
+        mask = front & (e1 <= max2) & (e0 <= max2)
+    return mask, int(mask.sum()), (e0 + e1)[mask].sum(dtype=LD)
+
+
+def data(uv0, uv1, depth0, depth1, f, cx, cy):
+    return dict(uv0=np.asarray(uv0, dtype=np.float64), uv1=np.asarray(uv1, dtype=np.float64), f=f, cx=cx, cy=cy,
+                X0=points(uv0, depth0, f, cx, cy), X1=points(uv1, depth1, f, cx, cy))
+
+
+def triangle_sin2(P):
+    a, b = P[1] - P[0], P[2] - P[0]
+    c = np.cross(a, b)
+    den = (a @ a) * (b @ b)
+    return (c @ c) / den if den > 0 else LD(0)
+
+
+def umeyama(A, B):
+    """(R, t, s, second / first singular value) with B ~ s R A + t, s in Horn's asymmetric form"""
+    ca, cb = A.mean(0), B.mean(0)
+    a, b = A - ca, B - cb
+    M = (b.T @ a).astype(np.float64)
+    U, S, Vt = np.linalg.svd(M)
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0])
+    R = (U @ D @ Vt).astype(LD)
+    s = ((a @ R.T) * b).sum() / (a * a).sum()
+    return R, cb - s * (R @ ca), s, (S[1] / S[0] if S[0] > 0 else 0.0)
+
+
+def hypotheses(D, opts, defect=None):
+    """dict of sample (H, 3), valid (H,), sim3 (H, 8), count (H,), cost (H,), sv_ratio (H,)"""
+    n, H = len(D["uv0"]), opts["iterations"]
+    smp, valid, sims = np.zeros((H, 3), dtype=np.int32), np.zeros(H, dtype=np.int32), sim3np.identity(H)
+    count, cost, ratio = np.zeros(H, dtype=np.int32), np.zeros(H, dtype=LD), np.zeros(H)
+    max2 = LD(opts["max_pixel_error"]) ** 2
+    for h in range(H):
+        idx = sample(opts["seed"], h, n)
+        smp[h] = idx
+        A, B = D["X0"][idx], D["X1"][idx]
+        if not (triangle_sin2(A) > opts["min_triangle_sin2"] and triangle_sin2(B) > opts["min_triangle_sin2"]):
+            continue
+        R, t, s, ratio[h] = umeyama(A, B)
+        if not (np.isfinite(s) and s > 0):
+            continue
+        q = sim3np.R_to_quat(R.astype(np.float64))
+        q = q / np.linalg.norm(q)
+        C = np.concatenate([q if q[3] >= 0 else -q, t.astype(np.float64), [float(s)]])
+        Y, Z = A @ (s * R).T + t, (B - t) @ R / s
+        if not ((Y[:, 2] > 0).all() and (Z[:, 2] > 0).all()):
+            continue
+        valid[h], sims[h] = 1, C
+        _, count[h], cost[h] = score(C, D, max2, defect)
+    return dict(sample=smp, valid=valid, sim3=sims, count=count, cost=cost, sv_ratio=ratio)
+
+
+def huber(e2, delta, defect=None):
+    """(rho, w) of squared lengths e2"""
+    e2 = np.asarray(e2, dtype=LD)
+    if not delta > 0:
+        return e2, np.ones_like(e2)
+    e = np.sqrt(e2)
+    big = e > delta
+    es = np.where(big, e, 1)
+    rho, w = np.where(big, 2 * e * delta - LD(delta) ** 2, e2), np.where(big, LD(delta) / es, LD(1))
+    return rho, (w * w if defect == "huber_squared" else w)
+
+
+def perturbed(C, delta, defect=None):
+    d = np.asarray(delta, dtype=np.float64)
+    if defect == "tangent_order":
+        d = np.concatenate([d[3:6], d[:3], d[6:]])
+    E = sim3np.exp(d, fix_b=1)
+    return sim3np.mul(C, E) if defect == "right_perturbation" else sim3np.mul(E, C)
+
+
+def stacked(C, D, defect=None):
+    r1, r0, _ = residuals(C, D["X0"], D["X1"], D["uv0"], D["uv1"], D["f"], D["cx"], D["cy"], defect)
+    return np.concatenate([r1, r0], axis=1)  # (n, 4)
+
+
+def jacobians(C, D, defect=None, h=2e-3):
+    """(n, 4, 7) d [r1 r0] / d delta at exp(delta) C, by fourth-order central differences"""
+    J = np.zeros((len(D["uv0"]), 4, 7), dtype=LD)
+    for k in range(7):
+        e = np.zeros(7)
+        e[k] = h
+        f = lambda m: stacked(perturbed(C, m * e, defect), D, defect)
+        J[:, :, k] = (8 * (f(1) - f(-1)) - (f(2) - f(-2))) / (12 * LD(h))
+    return J
+
+
+def chi2(C, D, mask, delta, defect=None):
+    r = stacked(C, D, defect)[mask]
+    return huber((r[:, :2] ** 2).sum(1), delta)[0].sum(dtype=LD) + huber((r[:, 2:] ** 2).sum(1), delta)[0].sum(dtype=LD)
+
+
+def normal_equations(C, D, mask, delta, defect=None):
+    """(Hm (7, 7), b (7,), chi2, weights (n, 2: image 1, image 0)) over the masked matches, long double"""
+    mask = np.asarray(mask, dtype=bool)
+    if defect == "lane_stride_once":
+        mask = mask & (np.arange(len(mask)) < 256)
+    r, J = stacked(C, D, defect), jacobians(C, D, defect)
+    Hm, b, chi, W = np.zeros((7, 7), dtype=LD), np.zeros(7, dtype=LD), LD(0), np.zeros((len(mask), 2), dtype=LD)
+    for blk in (0, 1):
+        rr, JJ = r[:, 2 * blk:2 * blk + 2], J[:, 2 * blk:2 * blk + 2, :]
+        rho, w = huber((rr ** 2).sum(1), delta, defect)
+        W[:, blk] = np.where(mask, w, 0)
+        Hm += np.einsum("n,nrk,nrl->kl", W[:, blk], JJ, JJ)
+        b -= np.einsum("n,nrk,nr->k", W[:, blk], JJ, rr)
+        chi += rho[mask].sum(dtype=LD)
+    return Hm, b, chi, W
+
+
+def refine(C, D, mask, opts, defect=None):
+    """dict of sim3, iterations, chi2 (before, after), trials (refine_iters,)"""
+    C = np.array(C, dtype=np.float64)
+    mask = np.asarray(mask, dtype=bool)
+    trials = np.zeros(opts["refine_iters"], dtype=np.int32)
+    iters, lam, ni, go, cur, chi0 = 0, 0.0, 2.0, True, LD(0), LD(0)
+    for it in range(opts["refine_iters"]):
+        if not go:
+            break
+        Hm, b, cur, _ = normal_equations(C, D, mask, opts["huber_delta"], defect)
+        if it == 0:
+            chi0, lam, ni = cur, opts["tau"] * float(np.max(np.diag(Hm))), 2.0
+        rho, q, converged = 0.0, 0, False
+        while True:
+            A = (Hm + lam * np.eye(7)).astype(np.float64)
+            try:
+                np.linalg.cholesky(A)
+                dx = np.linalg.solve(A, b.astype(np.float64))
+                fail = False
+            except np.linalg.LinAlgError:
+                fail = True
+            tmp, scale, nC = LD(np.finfo(np.float64).max), 0.0, C
+            if not fail:
+                scale = float(dx @ (lam * dx + b.astype(np.float64)))
+                if scale <= GAIN_TOL * cur:
+                    converged = True
+                    break
+                nC = perturbed(C, dx, defect)
+                nC[:4] /= np.linalg.norm(nC[:4])
+                tmp = chi2(nC, D, mask if defect != "lane_stride_once" else mask & (np.arange(len(mask)) < 256),
+                           opts["huber_delta"], defect)
+            rho = float(cur - tmp) / (scale + 1e-3)
+            if rho > 0 and np.isfinite(float(tmp)):
+                alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
+                lam *= max(1.0 / 3.0, alpha)
+                ni = 2.0
+                cur, C = tmp, nC
+            else:
+                lam *= ni
+                ni *= 2.0
+            q += 1
+            if not (rho < 0 and q < opts["max_trials"]):
+                break
+        if converged and q == 0:
+            break
+        trials[it] = q
+        iters += 1
+        if converged or q == opts["max_trials"] or rho == 0 or not np.isfinite(lam):
+            go = False
+    if iters == 0:
+        chi0 = cur = chi2(C, D, mask, opts["huber_delta"], defect)
+    return dict(sim3=C, iterations=iters, chi2=np.array([chi0, cur], dtype=np.float64), trials=trials)
+
+
+def information(C, D, mask, opts, defect=None):
+    """dict of information (7, 7) [r, c], weights (n, 2), positive_definite"""
+    Hm, _, _, W = normal_equations(C, D, mask, opts["huber_delta"], defect)
+    Om = (Hm / LD(opts["pixel_noise"]) ** 2).astype(np.float64)
+    Om = (Om + Om.T) / 2
+    if defect == "omega_transposed":
+        Om = np.triu(Om) + np.tril(np.roll(Om, 1, axis=1), -1)
+    try:
+        np.linalg.cholesky((Om + Om.T) / 2)
+        pd = True
+    except np.linalg.LinAlgError:
+        pd = False
+    return dict(information=Om, weights=W.astype(np.float64), positive_definite=pd)
+
+
+def solve(uv0, uv1, depth0, depth1, f, cx, cy, opts, defect=None):
+    """The whole stage for one problem: dict of status, hyp, best, n_hyp, cost_hyp, mask_hyp, sim3, iterations, chi2,
+    trials, mask, n_inliers, rms, information."""
+    n = len(uv0)
+    out = dict(status=0, hyp=None, best=-1, n_hyp=0, cost_hyp=0.0, mask_hyp=np.zeros(n, dtype=bool),
+               sim3=sim3np.identity(), iterations=0, chi2=np.zeros(2), trials=np.zeros(opts["refine_iters"], np.int32),
+               mask=np.zeros(n, dtype=bool), n_inliers=0, rms=0.0, information=np.zeros((7, 7)))
+    if n < opts["min_points"]:
+        out["status"] = 1
+        return out
+    D = data(uv0, uv1, depth0, depth1, f, cx, cy)
+    hyp = out["hyp"] = hypotheses(D, opts, defect)
+    best = -1
+    for h in range(opts["iterations"]):  # larger count, then smaller cost, then smaller index
+        if hyp["valid"][h] and (best < 0 or hyp["count"][h] > hyp["count"][best] or
+                                (hyp["count"][h] == hyp["count"][best] and hyp["cost"][h] < hyp["cost"][best])):
+            best = h
+    if best < 0:
+        out["status"] = 2
+        return out
+    max2 = LD(opts["max_pixel_error"]) ** 2
+    C = hyp["sim3"][best]
+    mask_hyp, _, _ = score(C, D, max2, defect)
+    out.update(best=best, n_hyp=int(hyp["count"][best]), cost_hyp=float(hyp["cost"][best]), mask_hyp=mask_hyp)
+    mask, count, cost = mask_hyp, int(mask_hyp.sum()), hyp["cost"][best]
+    if opts["refine_iters"] > 0:
+        r = refine(C, D, mask_hyp, opts, defect)
+        C = r["sim3"]
+        out.update(iterations=r["iterations"], chi2=r["chi2"], trials=r["trials"])
+        if defect != "mask_not_rederived":
+            mask, count, cost = score(C, D, max2, defect)
+    inf = information(C, D, mask, opts, defect)
+    out.update(sim3=C, mask=mask, n_inliers=count, rms=float(np.sqrt(cost / (2 * count))) if count else 0.0,
+               information=inf["information"],
+               status=3 if count < opts["min_inliers"] else (0 if inf["positive_definite"] else 4))
+    return out
