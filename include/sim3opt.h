@@ -767,7 +767,7 @@ int sim3opt_comm_local_state(sim3opt_graph* g, int64_t out[2]);
  * call it yourself before allocating large device buffers of your own next to a live handle. */
 void sim3opt_release_device_cache(void);
 /* Diagnostic.  out = {blocks, bytes} of device memory the library has handed to its handles and calls and not got
- * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch of the process, on all
+ * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch / sim3opt_place_batch of the process, on all
  * devices; bytes as the block cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
  * that creates no handle and initialises none is what "this call keeps no device memory" means
  * (tests/test_gpu_device_memory.py). */
@@ -1494,6 +1494,139 @@ int sim3opt_match_batch_debug_nn(sim3opt_match_batch* b, int32_t pair, int32_t* 
  * (SIM3OPT_ERR_STATE) with at least one observation in `frame` (SIM3OPT_ERR_ARG), no solve. */
 int sim3opt_match_batch_debug_depth(sim3opt_match_batch* b, int32_t n, int32_t frame, const float* uv, double* depth,
                                     int32_t* neighbours);
+
+/* ---- batched bag-of-words place recognition: the candidate pairs the blocks above start from, every keyframe at once ----
+ * detector.detectLoop(keys, descriptors, result) (kittiDetector.h:1663): DLoopDetector over a DBoW2 SURF-64 vocabulary,
+ * configured at :1549-1564.  It takes the kp_ptr / desc of sim3opt_match_batch_set_frames and returns the pairs of
+ * sim3opt_match_batch_set_pairs.
+ * PARITY UNPINNED: the reference tree holds neither DLoopDetector's nor DBoW2's source, no vocabulary, no descriptors
+ * and no detection results.  Reference-held are FSurf64::distance (FSurf64.cpp:47-58), which d2 below follows exactly,
+ * and the parameter values at the call site (use_nss, alpha, k, di_levels).  Everything else restates the published
+ * algorithm (Galvez-Lopez and Tardos, T-RO 2012) and DLoopDetector's defaults from memory: [upstream recall]
+ * dislocal 20, max_db_results 50, min_nss_factor 0.005, min_matches_per_group 1, max_intragroup_gap 3,
+ * max_distance_between_groups 3, max_distance_between_queries 2, the order of the tests and of the status values, the
+ * L1 normalisation and L1Scoring.  Each of them is an option, so a wrong recollection costs a default.
+ * Definition.
+ * Vocabulary: a tree as arrays.  Node 0 is the root (parent[0] = -1), 0 <= parent[i] < i otherwise; centre (n_nodes x
+ * 64 floats); weight (n_nodes doubles, read at leaves only); word_id (-1 at inner nodes, a permutation of 0..n_words-1
+ * at the leaves).  The children of a node are the nodes naming it as parent, in ascending index, at most 64.  The tree
+ * may be unbalanced.  This is what DBoW2's save() writes (nodes: nodeId, parentId, weight, descriptor; words: wordId,
+ * nodeId); parsing .yml.gz is the caller's.
+ * Word of a descriptor: from the root, at every inner node go to the child of smallest d2, the lower child on equal d2,
+ * until a leaf.  d2(a, b) = sum_k (double) fl32(fl32(a_k - b_k) * fl32(a_k - b_k)): difference and square in FP32,
+ * each rounded once and not fused, the 64 terms added in double in ascending k.
+ * Bag-of-words vector of a frame: for every word of weight > 0 that a descriptor of the frame reaches, value = count *
+ * weight (one multiplication; DBoW2 adds the weight count times), or value = weight with options.accumulate = 0; the
+ * values divided by their sum, taken in double in ascending word id.  A frame without descriptors or without a word of
+ * positive weight has the empty vector.
+ * Score: s(a, b) = -1/2 sum_{w in a and b} (|a_w - b_w| - (|a_w| + |b_w|)) in double, the terms added one after the
+ * other in ascending word id: a function of the two vectors alone and symmetric in them bit for bit; 0 without a
+ * common word.
+ * Per query frame i (entry ids are frame indices):
+ *  1. i <= dislocal: SIM3OPT_PLACE_CLOSE_MATCHES_ONLY.
+ *  2. Results: the frames j <= i - dislocal with s(v_i, v_j) > 0, by score descending and lower j on equal score, the
+ *     first max_db_results of them.  None: SIM3OPT_PLACE_NO_DB_RESULTS.
+ *  3. ns = s(v_i, v_{i-1}) with use_nss, else 1.  With use_nss, ns < min_nss_factor: SIM3OPT_PLACE_LOW_NSS_FACTOR.
+ *  4. Kept: the results with score >= alpha * ns.  None: SIM3OPT_PLACE_LOW_SCORES.  From here on match is reported.
+ *  5. Islands: the kept results in ascending j; runs in which each j is less than max_intragroup_gap above the one
+ *     before.  An island has first, last, score (the sum of its results' scores in ascending j) and best_entry (its
+ *     result of highest score, the lower j on ties); islands of fewer than min_matches_per_group results are dropped.
+ *     None left: SIM3OPT_PLACE_NO_GROUPS with match = the best result.  The chosen island has the highest score, the
+ *     lower first on ties; match = its best_entry.
+ *  6. Temporal window, a recurrence over the queries that reached 5 with an island, state (a1, a2, last_query, n),
+ *     n = 0 at the start: n = 1 if n == 0 or i - last_query > max_distance_between_queries; else n += 1 if [a1, a2]
+ *     and [first, last] intersect or max(a1 - last, first - a2) <= max_distance_between_groups, else n = 1; then
+ *     (a1, a2, last_query) = (first, last, i).  n > k: SIM3OPT_PLACE_CANDIDATE, else
+ *     SIM3OPT_PLACE_NO_TEMPORAL_CONSISTENCY.
+ * Not here: DLoopDetector's geometric check (GEOM_FLANN: a fundamental matrix by RANSAC, at least 12 inliers) is what
+ * sim3opt_match_batch and sim3opt_essential_batch do with the pairs (the caller reads n_inliers), so there is no
+ * NO_GEOMETRICAL_CONSISTENCY status; the direct index (di_levels) serves GEOM_DI only and is not built.
+ * Device pipeline: sim3opt_amd/csrc/place_batch.hip; steps 1-5 run per query on the device, step 6 (an integer
+ * recurrence of n_frames steps) on the host.  The launches of a solve do not depend on the number of frames; a pair's
+ * score and a frame's outcome up to step 5 do not depend on the other frames or on their place in the batch.
+ * No CPU fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_place_batch sim3opt_place_batch;
+
+#define SIM3OPT_PLACE_MAX_FRAMES 16384 /* the scores of all pairs j <= i stay on the device: 8 n (n + 1) / 2 bytes, 1.0 GiB here */
+
+typedef struct sim3opt_place_batch_options {
+  double alpha;                         /* results below alpha * ns go                    default 0.3    :1549-1564         */
+  double min_nss_factor;                /* queries with ns below it are not trusted       default 0.005  [upstream recall]  */
+  int32_t use_nss;                      /* normalise by the score against frame i - 1     default 1      :1549-1564         */
+  int32_t k;                            /* a candidate needs n > k consistent queries     default 3      :1549-1564         */
+  int32_t dislocal;                     /* frames this close before the query are skipped default 20     [upstream recall]  */
+  int32_t max_db_results;               /* results kept per query, 1..1024                default 50     [upstream recall]  */
+  int32_t max_intragroup_gap;           /* j closer than this to the one before: same island  default 3  [upstream recall]  */
+  int32_t min_matches_per_group;        /* results an island needs                        default 1      [upstream recall]  */
+  int32_t max_distance_between_queries; /* a longer break restarts the temporal window    default 2      [upstream recall]  */
+  int32_t max_distance_between_groups;  /* islands this far apart still fit the window    default 3      [upstream recall]  */
+  int32_t accumulate;                   /* 1: value = count * weight (TF-IDF, TF); 0: value = weight (IDF, binary)  default 1 */
+  int32_t device;                       /* HIP device ordinal, -1 = current               default -1                        */
+} sim3opt_place_batch_options;
+
+#define SIM3OPT_PLACE_CANDIDATE 0               /* a loop candidate: (query, match) is a pair                 */
+#define SIM3OPT_PLACE_CLOSE_MATCHES_ONLY 1      /* i <= dislocal                                              */
+#define SIM3OPT_PLACE_NO_DB_RESULTS 2           /* no earlier frame scores above 0                            */
+#define SIM3OPT_PLACE_LOW_NSS_FACTOR 3          /* the score against the frame before is below min_nss_factor */
+#define SIM3OPT_PLACE_LOW_SCORES 4              /* no result reaches alpha * ns                               */
+#define SIM3OPT_PLACE_NO_GROUPS 5               /* no island of min_matches_per_group results                 */
+#define SIM3OPT_PLACE_NO_TEMPORAL_CONSISTENCY 6 /* the window holds k queries or fewer                        */
+
+void sim3opt_place_batch_options_default(sim3opt_place_batch_options* o);
+sim3opt_place_batch* sim3opt_place_batch_create(void);
+void sim3opt_place_batch_destroy(sim3opt_place_batch* b);
+const char* sim3opt_place_batch_last_error(const sim3opt_place_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: alpha or min_nss_factor negative or not finite, use_nss or accumulate not 0 or 1,
+ * k < 0, dislocal < 1, max_db_results outside 1..1024, max_intragroup_gap < 1, min_matches_per_group < 1, a negative
+ * distance.  The frames, their words and vectors stay; the results of the last solve stay too (they are that solve's). */
+int sim3opt_place_batch_set_options(sim3opt_place_batch* b, const sim3opt_place_batch_options* o);
+/* The tree of the definition.  SIM3OPT_ERR_ARG with nothing changed: a NULL array, n_nodes < 2, a parent that is not
+ * smaller than its child, a non-finite centre, a negative or non-finite weight at a leaf, a leaf without a word id, an
+ * inner node with one, a word id repeated or not below the number of leaves, a node with more than 64 children.  A
+ * successful call keeps the frames and drops the results of the last solve. */
+int sim3opt_place_batch_set_vocabulary(sim3opt_place_batch* b, int32_t n_nodes, const int32_t* parent,
+                                       const float* centre, const double* weight, const int32_t* word_id);
+/* The matching stage's arrays as they are: frame f owns the descriptors kp_ptr[f]:kp_ptr[f+1] of desc (x 64); a frame
+ * may have none.  SIM3OPT_ERR_ARG with nothing changed: n_frames < 1 or above SIM3OPT_PLACE_MAX_FRAMES, a NULL array,
+ * a pointer array that does not start at 0 or decreases, a non-finite descriptor.  A successful call keeps the
+ * vocabulary (on the device too) and drops the results of the last solve. */
+int sim3opt_place_batch_set_frames(sim3opt_place_batch* b, int32_t n_frames, const int32_t* kp_ptr, const float* desc);
+/* Each may be NULL.  depth: edges from the root to the deepest leaf.  tiles[6]: the lanes of a wavefront (the vector
+ * entries k_place_score looks up at a time), the lanes of a workgroup (the descriptors of one of k_place_words, the
+ * scan width of k_place_bow and k_place_select), the words k_place_bow stages at a time, the longest query vector
+ * k_place_score keeps in LDS, the database frames of one of its workgroups, the nodes k_place_words stages in LDS:
+ * the sizes at which the kernels take another path. */
+int sim3opt_place_batch_dims(const sim3opt_place_batch* b, int32_t* n_nodes, int32_t* n_words, int32_t* depth,
+                             int32_t* n_frames, int32_t* total_descriptors, int32_t tiles[6]);
+/* Every frame; the same launches whatever their number.  Returns the number of candidates, or a negative SIM3OPT_ERR_*
+ * (SIM3OPT_ERR_STATE: no vocabulary or no frames set); a frame's outcome is its status, never the batch's. */
+int sim3opt_place_batch_solve(sim3opt_place_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  Per frame, each may be NULL: status (SIM3OPT_PLACE_*);
+ * match (-1 before step 4) and its score (0 likewise); ns_factor (0 for the statuses of steps 1 and 2); n_consistent
+ * (the n of step 6, 0 for a query that did not reach it); island (n x 2: first, last of the chosen island, -1 without). */
+int sim3opt_place_batch_get_results(const sim3opt_place_batch* b, int32_t* status, int32_t* match, double* score,
+                                    double* ns_factor, int32_t* n_consistent, int32_t* island);
+/* The rows (query, match) of the candidates in ascending query: the pairs of sim3opt_match_batch_set_pairs, frame0 =
+ * the query side.  n_pairs receives their number whatever the capacity (rows); SIM3OPT_ERR_ARG when they do not fit
+ * (pairs may be NULL with capacity 0: the number alone). */
+int sim3opt_place_batch_get_pairs(const sim3opt_place_batch* b, int32_t capacity, int32_t* n_pairs, int32_t* pairs);
+/* The ragged vectors: bow_ptr (n_frames + 1), word and value (bow_ptr[n_frames] each, by ascending word id within a
+ * frame).  Each may be NULL: call with bow_ptr alone for the sizes. */
+int sim3opt_place_batch_get_bow(const sim3opt_place_batch* b, int32_t* bow_ptr, int32_t* word, double* value);
+/* Diagnostics.  Each leaves the results of the last solve as they were.
+ * n supplied descriptors (n x 64, finite) through the descent code of k_place_words: word (n) and the winning d2 of
+ * every level (path_d2: n x depth, -1 past the leaf).  At least one output.  Needs a vocabulary (SIM3OPT_ERR_STATE). */
+int sim3opt_place_batch_debug_words(sim3opt_place_batch* b, int32_t n, const float* desc, int32_t* word,
+                                    double* path_d2);
+/* The full score row s(v_query, v_j) for every j of the last solve (row: n_frames), without the j <= i - dislocal cut.
+ * SIM3OPT_ERR_STATE before the first solve. */
+int sim3opt_place_batch_debug_scores(sim3opt_place_batch* b, int32_t query, double* row);
+/* Steps 2-5 of one query of the last solve again: the kept results in ascending j (n_kept; kept_j and kept_score with
+ * room for max_db_results) and the islands left after min_matches_per_group in ascending first (n_islands; island:
+ * x 4 = first, last, best_entry, number of results; island_score), room for the max_db_results of that solve each
+ * (1024 always suffices).  Each may be NULL. */
+int sim3opt_place_batch_debug_islands(sim3opt_place_batch* b, int32_t query, int32_t* n_kept, int32_t* kept_j,
+                                      double* kept_score, int32_t* n_islands, int32_t* island, double* island_score);
 
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933

@@ -209,6 +209,24 @@ class MatchBatchOptions(C.Structure):
     ]
 
 
+class PlaceBatchOptions(C.Structure):
+    """sim3opt_place_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("alpha", C.c_double),
+        ("min_nss_factor", C.c_double),
+        ("use_nss", C.c_int32),
+        ("k", C.c_int32),
+        ("dislocal", C.c_int32),
+        ("max_db_results", C.c_int32),
+        ("max_intragroup_gap", C.c_int32),
+        ("min_matches_per_group", C.c_int32),
+        ("max_distance_between_queries", C.c_int32),
+        ("max_distance_between_groups", C.c_int32),
+        ("accumulate", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -465,6 +483,21 @@ SYMBOLS = {
     "sim3opt_match_batch_debug_nn": (C.c_int, [_vp, C.c_int32, _ip, _fp, _ip, _fp]),
     "sim3opt_match_batch_debug_depth": (C.c_int, [_vp, C.c_int32, C.c_int32, _fp, _dp, _ip]),
     "sim3opt_median_depth_ratio": (C.c_int, [C.c_int32, _ip, _dp, _dp, _dp]),
+    "sim3opt_place_batch_options_default": (None, [C.POINTER(PlaceBatchOptions)]),
+    "sim3opt_place_batch_create": (_vp, []),
+    "sim3opt_place_batch_destroy": (None, [_vp]),
+    "sim3opt_place_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_place_batch_set_options": (C.c_int, [_vp, C.POINTER(PlaceBatchOptions)]),
+    "sim3opt_place_batch_set_vocabulary": (C.c_int, [_vp, C.c_int32, _ip, _fp, _dp, _ip]),
+    "sim3opt_place_batch_set_frames": (C.c_int, [_vp, C.c_int32, _ip, _fp]),
+    "sim3opt_place_batch_dims": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_place_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_place_batch_get_results": (C.c_int, [_vp, _ip, _ip, _dp, _dp, _ip, _ip]),
+    "sim3opt_place_batch_get_pairs": (C.c_int, [_vp, C.c_int32, _ip, _ip]),
+    "sim3opt_place_batch_get_bow": (C.c_int, [_vp, _ip, _ip, _dp]),
+    "sim3opt_place_batch_debug_words": (C.c_int, [_vp, C.c_int32, _fp, _ip, _dp]),
+    "sim3opt_place_batch_debug_scores": (C.c_int, [_vp, C.c_int32, _dp]),
+    "sim3opt_place_batch_debug_islands": (C.c_int, [_vp, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp]),
 }
 
 _lib = None
@@ -1461,7 +1494,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch and MatchBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch and PlaceBatch share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -2177,6 +2210,99 @@ class MatchBatch(_Handle):
         self._chk(self._L.sim3opt_match_batch_debug_depth(self._b, n, int(frame), _p(q, _fp), _p(z, _dp), _p(nb, _ip)),
                   "match_batch_debug_depth")
         return z, nb
+
+
+class PlaceBatch(_Handle):
+    """sim3opt_place_batch*: bag-of-words place recognition over a whole sequence of keyframes (detector.detectLoop,
+    kittiDetector.h:1663).  It takes the kp_ptr / desc MatchBatch.set_frames takes; pairs() is what
+    MatchBatch.set_pairs takes.  PARITY UNPINNED: include/sim3opt.h says what is the reference's and what is recalled
+    from upstream."""
+    _prefix, _Options = "place_batch", PlaceBatchOptions
+    TILES = ("wavefront", "workgroup", "bow_chunk", "score_lds", "score_frames", "lds_nodes")
+
+    def set_vocabulary(self, parent, centre, weight, word_id):
+        p, c = _i32(parent).reshape(-1), _f32(centre).reshape(-1, 64)
+        w, i = _f64(weight).reshape(-1), _i32(word_id).reshape(-1)
+        if not p.shape[0] == c.shape[0] == w.shape[0] == i.shape[0]:
+            raise ValueError("parent, centre, weight and word_id hold one entry per node")
+        self._chk(self._L.sim3opt_place_batch_set_vocabulary(self._b, p.shape[0], _p(p, _ip), _p(c, _fp), _p(w, _dp),
+                                                             _p(i, _ip)), "place_batch_set_vocabulary")
+
+    def set_frames(self, kp_ptr, desc):
+        kpp, d = _i32(kp_ptr).reshape(-1), _f32(desc).reshape(-1, 64)
+        n = kpp.shape[0] - 1
+        if n >= 1 and d.shape[0] < kpp.max():
+            raise ValueError("descriptor array shorter than kp_ptr says")
+        if d.shape[0] == 0:
+            d = np.zeros((1, 64), dtype=np.float32)  # (the C-ABI refuses a NULL array; nothing of it is read)
+        self._chk(self._L.sim3opt_place_batch_set_frames(self._b, n, _p(kpp, _ip), _p(d, _fp)), "place_batch_set_frames")
+
+    def dims(self):
+        """dict: n_nodes, n_words, depth, n_frames, total_descriptors and the kernels' tile sizes (TILES)"""
+        v = [C.c_int32() for _ in range(5)]
+        t = (C.c_int32 * 6)()
+        self._chk(self._L.sim3opt_place_batch_dims(self._b, *(C.byref(x) for x in v), t), "place_batch_dims")
+        out = dict(zip(("n_nodes", "n_words", "depth", "n_frames", "total_descriptors"), (x.value for x in v)))
+        out.update(zip(self.TILES, t))
+        return out
+
+    def solve(self):
+        """The number of candidates; raises when the library reports an error."""
+        return self._count(self._L.sim3opt_place_batch_solve(self._b), "place_batch_solve")
+
+    def results(self):
+        """dict of per-frame arrays: status, match, score, ns_factor, n_consistent, island (n, 2)"""
+        n = self.dims()["n_frames"]
+        st, ma, nc = (np.empty(n, dtype=np.int32) for _ in range(3))
+        sc, ns, isl = np.empty(n), np.empty(n), np.empty((n, 2), dtype=np.int32)
+        self._chk(self._L.sim3opt_place_batch_get_results(self._b, _p(st, _ip), _p(ma, _ip), _p(sc, _dp), _p(ns, _dp),
+                                                          _p(nc, _ip), _p(isl, _ip)), "place_batch_get_results")
+        return dict(status=st, match=ma, score=sc, ns_factor=ns, n_consistent=nc, island=isl)
+
+    def pairs(self):
+        """(n_pairs, 2) int32: (query, match) of the candidates in ascending query"""
+        n = C.c_int32()
+        self._chk(self._L.sim3opt_place_batch_get_pairs(self._b, 0, C.byref(n), None), "place_batch_get_pairs")
+        out = np.empty((n.value, 2), dtype=np.int32)
+        self._chk(self._L.sim3opt_place_batch_get_pairs(self._b, n.value, C.byref(n), _p(out, _ip)),
+                  "place_batch_get_pairs")
+        return out
+
+    def bow(self):
+        """(bow_ptr (n + 1,), word, value): the ragged bag-of-words vectors, by ascending word id within a frame"""
+        ptr = np.empty(self.dims()["n_frames"] + 1, dtype=np.int32)
+        self._chk(self._L.sim3opt_place_batch_get_bow(self._b, _p(ptr, _ip), None, None), "place_batch_get_bow")
+        w, v = np.empty(int(ptr[-1]), dtype=np.int32), np.empty(int(ptr[-1]))
+        self._chk(self._L.sim3opt_place_batch_get_bow(self._b, None, _p(w, _ip), _p(v, _dp)), "place_batch_get_bow")
+        return ptr, w, v
+
+    def debug_words(self, desc):
+        """Descriptors (n, 64) through the descent code of k_place_words: (word (n,), path_d2 (n, depth), -1 padded)."""
+        d = _f32(desc).reshape(-1, 64)
+        n = d.shape[0]
+        w, path = np.empty(n, dtype=np.int32), np.empty((n, self.dims()["depth"]))
+        self._chk(self._L.sim3opt_place_batch_debug_words(self._b, n, _p(d, _fp), _p(w, _ip), _p(path, _dp)),
+                  "place_batch_debug_words")
+        return w, path
+
+    def debug_scores(self, query):
+        """s(v_query, v_j) for every frame j of the last solve"""
+        row = np.empty(self.dims()["n_frames"])
+        self._chk(self._L.sim3opt_place_batch_debug_scores(self._b, int(query), _p(row, _dp)), "place_batch_debug_scores")
+        return row
+
+    def debug_islands(self, query):
+        """dict: kept_j, kept_score (ascending j); island (n_islands, 4: first, last, best_entry, results),
+        island_score"""
+        R = 1024  # max_db_results' upper limit: room whatever the last solve ran with
+        nk, ni = C.c_int32(), C.c_int32()
+        kj, ks = np.empty(R, dtype=np.int32), np.empty(R)
+        isl, iss = np.empty((R, 4), dtype=np.int32), np.empty(R)
+        self._chk(self._L.sim3opt_place_batch_debug_islands(self._b, int(query), C.byref(nk), _p(kj, _ip), _p(ks, _dp),
+                                                            C.byref(ni), _p(isl, _ip), _p(iss, _dp)),
+                  "place_batch_debug_islands")
+        return dict(kept_j=kj[:nk.value].copy(), kept_score=ks[:nk.value].copy(), island=isl[:ni.value].copy(),
+                    island_score=iss[:ni.value].copy())
 
 
 def align_trajectory(query_xyz, train_xyz, with_scale=True):
