@@ -767,7 +767,7 @@ int sim3opt_comm_local_state(sim3opt_graph* g, int64_t out[2]);
  * call it yourself before allocating large device buffers of your own next to a live handle. */
 void sim3opt_release_device_cache(void);
 /* Diagnostic.  out = {blocks, bytes} of device memory the library has handed to its handles and calls and not got
- * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch / sim3opt_place_batch of the process, on all
+ * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch / sim3opt_place_batch / sim3opt_vocabulary of the process, on all
  * devices; bytes as the block cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
  * that creates no handle and initialises none is what "this call keeps no device memory" means
  * (tests/test_gpu_device_memory.py). */
@@ -1627,6 +1627,110 @@ int sim3opt_place_batch_debug_scores(sim3opt_place_batch* b, int32_t query, doub
  * (1024 always suffices).  Each may be NULL. */
 int sim3opt_place_batch_debug_islands(sim3opt_place_batch* b, int32_t query, int32_t* n_kept, int32_t* kept_j,
                                       double* kept_score, int32_t* n_islands, int32_t* island, double* island_score);
+
+/* ---- batched vocabulary training: the tree place recognition descends, from the sequence's own descriptors ----
+ * DBoW2's TemplatedVocabulary::create over FSurf64 (the Surf64Vocabulary typedef at kitti_surf.cpp:1231): hierarchical
+ * k-means, k-means++ seeded.  It takes the kp_ptr / desc of sim3opt_place_batch_set_frames (the frames are the training
+ * images) and returns the four arrays sim3opt_place_batch_set_vocabulary takes, with no conversion.
+ * PARITY UNPINNED: the reference tree holds neither DBoW2's source nor a vocabulary file.  Reference-held are
+ * FSurf64::distance and FSurf64::meanValue (FSurf64.cpp:23-58), the two functions create is parameterised by.
+ * Everything else about create is recalled from upstream, marked [upstream recall] below, and an option where it is a
+ * number, so a wrong recollection costs a default.
+ * Definition.
+ * Distance: the d2 of place recognition, word for word: d2(a, b) = sum_k (double) fl32(fl32(a_k - b_k) * fl32(a_k -
+ * b_k)), difference and square in FP32, each rounded once and not fused, the 64 terms added in double in ascending k.
+ * Split of a node with members m_0 < m_1 < ... (ascending descriptor index), n of them, at a level < levels:
+ *  - n <= k: every member is a child of its own, the centre being the member, in member order.  [upstream recall]
+ *  - otherwise k-means++ seeding [upstream recall]: centre 0 is member splitmix64(key(0)) % n.  For c = 1..k-1: w_i is
+ *    the smallest d2 of member i to the centres so far and W = sum w_i; W = 0 ends the seeding with c centres;
+ *    otherwise r = u W with u = (splitmix64(key(c)) >> 11) 2^-53, and the new centre is the first member, in member
+ *    order, whose inclusive prefix sum of w exceeds r (the last member if none does).  key(c) = seed + (64 node + c + 1)
+ *    * 0x9E3779B97F4A7C15 with node the node's output index: it holds the seed, the node and c only.  The prefix sums
+ *    are double, formed in an order that is a function of the inputs alone (a scan within 256 members, the runs of 256
+ *    one after the other).
+ *  - Lloyd: a pass assigns every member to the centre of smallest d2, the lower cluster on equal d2, and then sets the
+ *    centre of every non-empty cluster to its mean; an empty cluster keeps its centre.  Passes repeat until one
+ *    changes no assignment (its means are not taken again: they are the pass before's) or max_iters passes have run;
+ *    a node stopped by max_iters counts in n_unconverged.
+ *  - Mean: the members' coordinates added in double, divided once by the count, rounded once to FP32.  A STATED
+ *    DEVIATION from FSurf64::meanValue, which adds FP32 quotients one after the other in member order: that order is
+ *    serial over up to a million members; the double sum differs from it by its FP32 rounding only.  The order of the
+ *    double sum: runs of 1024 members in member order, each added one member after the other, then the runs one after
+ *    the other.  No floating-point atomics.
+ *  - Children: the non-empty clusters, in cluster order.
+ *  - Leaves: a node whose seeding ended with one centre (all members equal), a node of one member, every node at level
+ *    `levels`.
+ * Numbering: breadth first.  The root is 0, then levels 1, 2, ..., within a level by parent, then cluster; so
+ * 0 <= parent[i] < i.  word_id counts the leaves in ascending node index and is -1 at inner nodes.  The root's centre
+ * is all zeros.
+ * Weights: N = the frames with at least one descriptor; N_i = the frames with a descriptor whose word by the descent
+ * rule of place recognition on the finished tree is leaf i (DBoW2's transform [upstream recall]); weight = log(N / N_i)
+ * in double on the host, 0 for a leaf no descent reaches; with idf = 0 every leaf has weight 1.  The TF part is
+ * sim3opt_place_batch_options.accumulate.
+ * Device pipeline: sim3opt_amd/csrc/vocab_train.hip, level-synchronous; the launches of a seeding round and of a Lloyd
+ * pass do not depend on the number of nodes or descriptors.  No CPU fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_vocabulary sim3opt_vocabulary;
+
+typedef struct sim3opt_vocabulary_options {
+  uint64_t seed;     /* of the seeding's draws                                         default 0                      */
+  int32_t k;         /* branching, 2..64                                               default 10  [upstream recall]  */
+  int32_t levels;    /* L, 1..8 (8: with k = 10 more nodes than an int32 index x 64)   default 5   [upstream recall]  */
+  int32_t max_iters; /* Lloyd passes per node, >= 1 (ours: DBoW2 has no cap)           default 100                    */
+  int32_t idf;       /* 1: weight = log(N / N_i); 0: weight = 1                        default 1   [upstream recall]  */
+  int32_t device;    /* HIP device ordinal, -1 = current                               default -1                     */
+} sim3opt_vocabulary_options;
+
+void sim3opt_vocabulary_options_default(sim3opt_vocabulary_options* o);
+sim3opt_vocabulary* sim3opt_vocabulary_create(void);
+void sim3opt_vocabulary_destroy(sim3opt_vocabulary* b);
+const char* sim3opt_vocabulary_last_error(const sim3opt_vocabulary* b);
+/* SIM3OPT_ERR_ARG, nothing changed: k outside 2..64, levels outside 1..8, max_iters < 1, idf not 0 or 1.  The frames
+ * and the last training's results stay (they are that training's). */
+int sim3opt_vocabulary_set_options(sim3opt_vocabulary* b, const sim3opt_vocabulary_options* o);
+/* The arrays of sim3opt_place_batch_set_frames as they are; a frame may own no descriptor.  SIM3OPT_ERR_ARG with
+ * nothing changed: that call's refusals, and fewer than two distinct descriptors in total (the tree needs two nodes).
+ * A successful call drops the results of the last training. */
+int sim3opt_vocabulary_set_frames(sim3opt_vocabulary* b, int32_t n_frames, const int32_t* kp_ptr, const float* desc);
+/* Returns the number of nodes, or a negative SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no frames set; SIM3OPT_ERR_ARG: the
+ * tree would hold more than INT32_MAX / 64 nodes). */
+int sim3opt_vocabulary_train(sim3opt_vocabulary* b);
+/* Each may be NULL; the first four are 0 before the first training.  depth: edges from the root to the deepest leaf.
+ * passes[8]: the Lloyd passes run at each level (the most of any of its nodes, the pass that changed nothing
+ * included; 0 where no node ran k-means).  tiles[2]: the members of a node one workgroup takes (a lane each) and the
+ * members whose coordinates one wavefront adds one after the other: the sizes at which the kernels take another path. */
+int sim3opt_vocabulary_dims(const sim3opt_vocabulary* b, int32_t* n_nodes, int32_t* n_words, int32_t* depth,
+                            int32_t* n_unconverged, int32_t* n_frames, int32_t* total_descriptors, int32_t passes[8],
+                            int32_t tiles[2]);
+/* The getters return SIM3OPT_ERR_STATE before the first training.  Per node, each may be NULL: what
+ * sim3opt_place_batch_set_vocabulary takes (centre x 64). */
+int sim3opt_vocabulary_get_vocabulary(const sim3opt_vocabulary* b, int32_t* parent, float* centre, double* weight,
+                                      int32_t* word_id);
+/* Per training descriptor, each may be NULL: the leaf node it ended in by clustering, and the leaf node the descent
+ * rule reaches on the finished tree (what the weights were counted from).  The two agree on a converged tree without
+ * equal centres under one parent. */
+int sim3opt_vocabulary_get_assignment(const sim3opt_vocabulary* b, int32_t* node_of_descriptor, int32_t* descent_node);
+/* Read-outs of the last training for tests; they change nothing of its results.
+ * The seeding of output node `node`: the chosen members as descriptor indices (n_chosen; member with room for k), and
+ * W and r of every round run (n_rounds; room for k - 1 each; a round that ended the seeding has W = r = 0).  A node
+ * that was not seeded (a leaf by its size or level, n <= k) has n_chosen = n_rounds = 0.  Each may be NULL. */
+int sim3opt_vocabulary_debug_seeding(sim3opt_vocabulary* b, int32_t node, int32_t* n_chosen, int32_t* member,
+                                     int32_t* n_rounds, double* W, double* r);
+/* The state after `pass` passes (0..passes[level]) of `level`, run again from the stored start of the level: cluster
+ * (per training descriptor: its cluster in its node; its rank in a node of n <= k; -1 where the descriptor's node at
+ * that level is a leaf or the descriptor ended above) and centre (n_level_nodes x k x 64: the centres of every node of
+ * the level, zero where there is none).  first_node: the output index of the level's first node.  Call with cluster and
+ * centre NULL for the sizes.  Needs the device blocks of the last training (SIM3OPT_ERR_STATE after set_frames or a
+ * change of the device). */
+int sim3opt_vocabulary_debug_lloyd(sim3opt_vocabulary* b, int32_t level, int32_t pass, int32_t* first_node,
+                                   int32_t* n_level_nodes, int32_t* cluster, float* centre);
+/* Host only.  The file is this library's: "SIM3VOC\0", then int32 version (1), n_nodes, 64, then parent, centre, weight
+ * and word_id as they are, little endian.  SIM3OPT_ERR_IO: the file cannot be written / read, or is truncated, of
+ * another magic, version or length.  load hands out four blocks for sim3opt_vocabulary_free. */
+int sim3opt_vocabulary_save(const char* path, int32_t n_nodes, const int32_t* parent, const float* centre,
+                            const double* weight, const int32_t* word_id);
+int sim3opt_vocabulary_load(const char* path, int32_t* n_nodes, int32_t** parent, float** centre, double** weight,
+                            int32_t** word_id);
+void sim3opt_vocabulary_free(void* block);
 
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933

@@ -227,6 +227,18 @@ class PlaceBatchOptions(C.Structure):
     ]
 
 
+class VocabularyOptions(C.Structure):
+    """sim3opt_vocabulary_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("k", C.c_int32),
+        ("levels", C.c_int32),
+        ("max_iters", C.c_int32),
+        ("idf", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -498,6 +510,21 @@ SYMBOLS = {
     "sim3opt_place_batch_debug_words": (C.c_int, [_vp, C.c_int32, _fp, _ip, _dp]),
     "sim3opt_place_batch_debug_scores": (C.c_int, [_vp, C.c_int32, _dp]),
     "sim3opt_place_batch_debug_islands": (C.c_int, [_vp, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp]),
+    "sim3opt_vocabulary_options_default": (None, [C.POINTER(VocabularyOptions)]),
+    "sim3opt_vocabulary_create": (_vp, []),
+    "sim3opt_vocabulary_destroy": (None, [_vp]),
+    "sim3opt_vocabulary_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_vocabulary_set_options": (C.c_int, [_vp, C.POINTER(VocabularyOptions)]),
+    "sim3opt_vocabulary_set_frames": (C.c_int, [_vp, C.c_int32, _ip, _fp]),
+    "sim3opt_vocabulary_train": (C.c_int, [_vp]),
+    "sim3opt_vocabulary_dims": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_vocabulary_get_vocabulary": (C.c_int, [_vp, _ip, _fp, _dp, _ip]),
+    "sim3opt_vocabulary_get_assignment": (C.c_int, [_vp, _ip, _ip]),
+    "sim3opt_vocabulary_debug_seeding": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _dp]),
+    "sim3opt_vocabulary_debug_lloyd": (C.c_int, [_vp, C.c_int32, C.c_int32, _ip, _ip, _ip, _fp]),
+    "sim3opt_vocabulary_save": (C.c_int, [C.c_char_p, C.c_int32, _ip, _fp, _dp, _ip]),
+    "sim3opt_vocabulary_load": (C.c_int, [C.c_char_p, _ip, C.POINTER(_ip), C.POINTER(_fp), C.POINTER(_dp), C.POINTER(_ip)]),
+    "sim3opt_vocabulary_free": (None, [_vp]),
 }
 
 _lib = None
@@ -1494,7 +1521,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch and PlaceBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch and VocabularyTrainer share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -2303,6 +2330,106 @@ class PlaceBatch(_Handle):
                   "place_batch_debug_islands")
         return dict(kept_j=kj[:nk.value].copy(), kept_score=ks[:nk.value].copy(), island=isl[:ni.value].copy(),
                     island_score=iss[:ni.value].copy())
+
+
+class VocabularyTrainer(_Handle):
+    """sim3opt_vocabulary*: the vocabulary tree PlaceBatch descends, trained on the descriptors of a sequence by
+    hierarchical k-means (DBoW2's create over FSurf64).  It takes the kp_ptr / desc PlaceBatch.set_frames takes;
+    vocabulary() is what PlaceBatch.set_vocabulary(*...) takes.  PARITY UNPINNED: include/sim3opt.h says what is the
+    reference's and what is recalled from upstream."""
+    _prefix, _Options = "vocabulary", VocabularyOptions
+    TILES = ("chunk", "mean_chunk")
+
+    def set_frames(self, kp_ptr, desc):
+        kpp, d = _i32(kp_ptr).reshape(-1), _f32(desc).reshape(-1, 64)
+        n = kpp.shape[0] - 1
+        if n >= 1 and d.shape[0] < kpp.max():
+            raise ValueError("descriptor array shorter than kp_ptr says")
+        if d.shape[0] == 0:
+            d = np.zeros((1, 64), dtype=np.float32)  # (the C-ABI refuses a NULL array; nothing of it is read)
+        self._chk(self._L.sim3opt_vocabulary_set_frames(self._b, n, _p(kpp, _ip), _p(d, _fp)), "vocabulary_set_frames")
+
+    def train(self):
+        """The number of nodes; raises when the library reports an error."""
+        return self._count(self._L.sim3opt_vocabulary_train(self._b), "vocabulary_train")
+
+    def dims(self):
+        """dict: n_nodes, n_words, depth, n_unconverged, n_frames, total_descriptors, passes (per level, 8) and the
+        kernels' tile sizes (TILES)"""
+        v = [C.c_int32() for _ in range(6)]
+        ps, t = (C.c_int32 * 8)(), (C.c_int32 * 2)()
+        self._chk(self._L.sim3opt_vocabulary_dims(self._b, *(C.byref(x) for x in v), ps, t), "vocabulary_dims")
+        out = dict(zip(("n_nodes", "n_words", "depth", "n_unconverged", "n_frames", "total_descriptors"),
+                       (x.value for x in v)))
+        out["passes"] = list(ps)
+        out.update(zip(self.TILES, t))
+        return out
+
+    def vocabulary(self):
+        """(parent, centre (n, 64), weight, word_id): the arguments of PlaceBatch.set_vocabulary"""
+        n = self.dims()["n_nodes"]
+        p, w = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        c, g = np.empty((n, 64), dtype=np.float32), np.empty(n)
+        self._chk(self._L.sim3opt_vocabulary_get_vocabulary(self._b, _p(p, _ip), _p(c, _fp), _p(g, _dp), _p(w, _ip)),
+                  "vocabulary_get_vocabulary")
+        return p, c, g, w
+
+    def assignment(self, descent=False):
+        """Per training descriptor the leaf node it ended in by clustering; with descent=True also the leaf node the
+        descent rule reaches on the finished tree (what the weights were counted from)."""
+        d = self.dims()["total_descriptors"]
+        a, b = np.empty(d, dtype=np.int32), np.empty(d, dtype=np.int32)
+        self._chk(self._L.sim3opt_vocabulary_get_assignment(self._b, _p(a, _ip), _p(b, _ip)), "vocabulary_get_assignment")
+        return (a, b) if descent else a
+
+    def debug_seeding(self, node):
+        """dict: members (the chosen descriptors), W and r (one per round run)"""
+        nc, nr = C.c_int32(), C.c_int32()
+        m, W, r = np.empty(64, dtype=np.int32), np.empty(64), np.empty(64)
+        self._chk(self._L.sim3opt_vocabulary_debug_seeding(self._b, int(node), C.byref(nc), _p(m, _ip), C.byref(nr),
+                                                           _p(W, _dp), _p(r, _dp)), "vocabulary_debug_seeding")
+        return dict(members=m[:nc.value].copy(), W=W[:nr.value].copy(), r=r[:nr.value].copy())
+
+    def debug_lloyd(self, level, n_pass, k=None):
+        """dict: first_node, cluster (per descriptor) and centre (n_level_nodes, k, 64) after n_pass passes of `level`;
+        k: the branching the last training ran with (the options' by default)"""
+        k = self._opt.k if k is None else k
+        f, n = C.c_int32(), C.c_int32()
+        self._chk(self._L.sim3opt_vocabulary_debug_lloyd(self._b, int(level), int(n_pass), C.byref(f), C.byref(n), None,
+                                                         None), "vocabulary_debug_lloyd")
+        cl = np.empty(self.dims()["total_descriptors"], dtype=np.int32)
+        ce = np.empty((n.value, k, 64), dtype=np.float32)
+        self._chk(self._L.sim3opt_vocabulary_debug_lloyd(self._b, int(level), int(n_pass), C.byref(f), C.byref(n),
+                                                         _p(cl, _ip), _p(ce, _fp)), "vocabulary_debug_lloyd")
+        return dict(first_node=f.value, cluster=cl, centre=ce)
+
+
+def vocabulary_save(path, parent, centre, weight, word_id):
+    """Writes a tree (the four arrays of PlaceBatch.set_vocabulary) into this library's own binary format."""
+    p, c = _i32(parent).reshape(-1), _f32(centre).reshape(-1, 64)
+    w, i = _f64(weight).reshape(-1), _i32(word_id).reshape(-1)
+    if not p.shape[0] == c.shape[0] == w.shape[0] == i.shape[0]:
+        raise ValueError("parent, centre, weight and word_id hold one entry per node")
+    rc = load().sim3opt_vocabulary_save(os.fsencode(path), p.shape[0], _p(p, _ip), _p(c, _fp), _p(w, _dp), _p(i, _ip))
+    if rc != OK:
+        raise Sim3OptError(rc, "vocabulary_save")
+
+
+def vocabulary_load(path):
+    """(parent, centre (n, 64), weight, word_id) of a file vocabulary_save wrote"""
+    L = load()
+    n = C.c_int32()
+    p, c, w, i = _ip(), _fp(), _dp(), _ip()
+    rc = L.sim3opt_vocabulary_load(os.fsencode(path), C.byref(n), C.byref(p), C.byref(c), C.byref(w), C.byref(i))
+    if rc != OK:
+        raise Sim3OptError(rc, "vocabulary_load")
+    try:
+        N = n.value
+        return (np.ctypeslib.as_array(p, (N,)).copy(), np.ctypeslib.as_array(c, (N, 64)).copy(),
+                np.ctypeslib.as_array(w, (N,)).copy(), np.ctypeslib.as_array(i, (N,)).copy())
+    finally:
+        for q in (p, c, w, i):
+            L.sim3opt_vocabulary_free(C.cast(q, C.c_void_p))
 
 
 def align_trajectory(query_xyz, train_xyz, with_scale=True):
