@@ -772,6 +772,30 @@ void sim3opt_release_device_cache(void);
  * that creates no handle and initialises none is what "this call keeps no device memory" means
  * (tests/test_gpu_device_memory.py). */
 void sim3opt_device_memory_in_use(int64_t out[2]);
+/* Test mode of the block cache (tests/test_gpu_stale_memory.py); off by default, switched by this call alone, process-wide.
+ * Recycled blocks are not cleared and sizes are rounded up by up to 12.5 %: a kernel that reads what nobody wrote, or
+ * writes past an array's end into the block's own slack, is silent.  While the mode is on every block handed out -- of
+ * every handle and every call, on every device -- is 256 to about 12.5 % bytes longer than asked for; the bytes asked
+ * for are filled with 0xFF (a quiet NaN as float and as double) where the elements are floating point and with 0
+ * where they are not, the tail behind them with 0xA5; when the block comes back the tail is compared with 0xA5.
+ *   covered:     floating-point reads before writes (the result turns NaN or differs from a run with the mode off),
+ *                writes into a block's own slack (counted by the report below)
+ *   not covered: integer arrays (a stale integer may be an index; a poison must not send a load elsewhere), LDS, pinned
+ *                host memory, accesses outside the block
+ * Blocks handed out while the mode was off are not checked, so it may be switched while handles live.  Every
+ * allocation then synchronises its device: for tests only.  To run a new handle type under it: build it, run it, read
+ * everything out and close it once with the mode off and once with it on (sim3opt_release_device_cache before each) and
+ * compare the bytes; the report must show no overwritten tail and as many blocks checked as filled. */
+void sim3opt_debug_device_memory(int32_t on);
+/* out = {blocks filled, blocks checked when they came back, blocks whose tail was overwritten, offset past the requested
+ * size of the first overwritten byte of the first such block or -1}, since the mode was last switched on. */
+void sim3opt_debug_device_memory_report(int64_t out[4]);
+/* Shows that the check can fail, with no access outside a block: takes a block of `bytes` bytes from the cache (floating:
+ * its elements count as floating point) on the current device, sets `overrun` bytes from offset `bytes` on (refused with
+ * SIM3OPT_ERR_ARG if they would leave the block), copies the block's first out_len bytes to `out` and gives the block
+ * back.  Returns the block's size in bytes, or an error code (< 0). */
+int64_t sim3opt_debug_device_memory_probe(int64_t bytes, int32_t floating, int64_t overrun, unsigned char* out,
+                                          int64_t out_len);
 
 /* ---- reference-format I/O (host C++; the callers either side of the path) ---- */
 /* Builds the graph of testDirectSim3Optimization                   kitti_surf.cpp:562-670

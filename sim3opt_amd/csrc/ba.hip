@@ -53,6 +53,7 @@ constexpr int WG = 256;
 struct Cam {  // T_w2c: unit quaternion (x y z w) and translation; 8th double pads to 64 bytes
   double q[4], t[3], pad;
 };
+constexpr bool dev_block_is_floating(const Cam*) { return true; }  // doubles only (csrc/devmem.hpp's test mode)
 
 struct Scal {
   double chi2, scale, maxdiag;

@@ -291,6 +291,26 @@ void sim3opt_device_memory_in_use(int64_t out[2]) {
   if (out) sim3opt::dev_in_use(out);
 }
 
+void sim3opt_debug_device_memory(int32_t on) { sim3opt::dev_debug(on != 0); }
+
+void sim3opt_debug_device_memory_report(int64_t out[4]) {
+  if (out) sim3opt::dev_debug_report(out);
+}
+
+int64_t sim3opt_debug_device_memory_probe(int64_t bytes, int32_t floating, int64_t overrun, unsigned char* out,
+                                          int64_t out_len) {
+  if (bytes < 0 || overrun < 0 || out_len < 0 || (out_len > 0 && !out) || bytes > ((int64_t)1 << 30))
+    return SIM3OPT_ERR_ARG;
+  size_t size = 0;
+  const hipError_t e = sim3opt::dev_debug_probe((size_t)bytes, floating != 0, (size_t)overrun, out, (size_t)out_len, &size);
+  if (e == hipErrorInvalidValue) return SIM3OPT_ERR_ARG;  // (the overrun would leave the block)
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return SIM3OPT_ERR_HIP;
+  }
+  return (int64_t)size;
+}
+
 int sim3opt_set_options(sim3opt_graph* g, const sim3opt_options* o) {
   if (!g || !o) return fail(g, SIM3OPT_ERR_ARG, "set_options: null argument");
   REFUSE_FINISHED(g);

@@ -52,7 +52,7 @@ int ensure_capacity(Comm& c, int64_t need, hipStream_t stream, std::string& err)
     m = nullptr;
   }
   me.cap = 0;
-  for (double*& m : me.mbox) HIPCHK(dev_malloc((void**)&m, sizeof(double) * (size_t)cap));
+  for (double*& m : me.mbox) HIPCHK(dev_malloc_of((void**)&m, sizeof(double) * (size_t)cap, true));
   me.cap = cap;
   return barrier_wait(c, err);
 }

@@ -1,6 +1,7 @@
 // devmem.cpp -- see devmem.hpp
 #include "devmem.hpp"
 
+#include <atomic>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -14,6 +15,11 @@ namespace {
 constexpr size_t MAX_BLOCK = (size_t)64 << 20;
 constexpr size_t MAX_TOTAL = (size_t)1 << 30;
 
+struct Live {
+  int dev;
+  size_t sz;      // as the driver was asked
+  int64_t asked;  // test mode: the bytes the owner asked for, [asked, sz) is the guarded tail; -1: not guarded
+};
 struct Cache {
   std::mutex mu;
   std::map<int, std::vector<hipStream_t>> streams;                 // idle, per device
@@ -26,22 +32,18 @@ struct Cache {
   std::unordered_map<void*, std::pair<int, size_t>> host_live;
   size_t host_cached = 0;
   std::map<std::pair<int, size_t>, std::vector<void*>> free_blocks;  // (device, rounded size) -> blocks
-  std::unordered_map<void*, std::pair<int, size_t>> live;            // blocks handed out by dev_malloc
+  std::unordered_map<void*, Live> live;                              // blocks handed out by dev_malloc
   size_t cached_bytes = 0;
+  int64_t dbg_filled = 0, dbg_checked = 0, dbg_bad = 0, dbg_first = -1;  // the test mode's counters
 };
+std::atomic<bool> g_debug{false};  // the test mode (devmem.hpp)
 Cache& cache() {
   static Cache* c = new Cache();  // (never destroyed: the driver may already be gone at exit)
   return *c;
 }
 
-// eight steps per octave: at most 12.5 % more than asked for, so that a graph that grew by one edge
-// finds the blocks of its predecessor
-size_t rounded(size_t bytes) {
-  if (bytes < 256) return 256;
-  size_t step = 256;
-  while ((step << 4) <= bytes) step <<= 1;
-  return (bytes + step - 1) / step * step;
-}
+// at most 12.5 % more than asked for, so that a graph that grew by one edge finds the blocks of its predecessor
+size_t rounded(size_t bytes) { return dev_rounded(bytes); }
 
 void release_locked(Cache& c) {
   for (auto& kv : c.free_blocks)
@@ -60,13 +62,17 @@ void release_locked(Cache& c) {
   c.host_cached = 0;
 }
 
-}  // namespace
+void recycle_locked(Cache& c, void* p, int dev, size_t sz) {
+  if (sz <= MAX_BLOCK && c.cached_bytes + sz <= MAX_TOTAL) {
+    c.free_blocks[{dev, sz}].push_back(p);
+    c.cached_bytes += sz;
+  } else {
+    (void)hipFree(p);
+  }
+}
 
-hipError_t dev_malloc(void** p, size_t bytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const size_t sz = rounded(bytes);
-  Cache& c = cache();
+// the block of `asked` bytes (of this device: the current one) as the cache hands it out: from the cache or the driver
+hipError_t acquire(Cache& c, void** p, int dev, size_t sz, int64_t asked) {
   std::lock_guard<std::mutex> lock(c.mu);
   if (sz <= MAX_BLOCK) {
     auto it = c.free_blocks.find({dev, sz});
@@ -74,7 +80,7 @@ hipError_t dev_malloc(void** p, size_t bytes) {
       *p = it->second.back();
       it->second.pop_back();
       c.cached_bytes -= sz;
-      c.live[*p] = {dev, sz};
+      c.live[*p] = {dev, sz, asked};
       return hipSuccess;
     }
   }
@@ -84,27 +90,129 @@ hipError_t dev_malloc(void** p, size_t bytes) {
     release_locked(c);
     e = hipMalloc(p, sz);
   }
-  if (e == hipSuccess) c.live[*p] = {dev, sz};
+  if (e == hipSuccess) c.live[*p] = {dev, sz, asked};
+  return e;
+}
+
+// test mode: poison and canary of a block of the current device; outside the cache's mutex.  The engine's streams do
+// not wait for the null stream, so the device is synchronised before the owner sees the block.
+hipError_t debug_fill(void* p, size_t bytes, size_t sz, bool floating) {
+  hipError_t e = hipSuccess;
+  if (bytes > 0) e = hipMemset(p, floating ? DEBUG_NAN_BYTE : 0x00, bytes);
+  if (e == hipSuccess) e = hipMemset(static_cast<char*>(p) + dev_debug_tail_offset(bytes), DEBUG_CANARY, sz - bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e;
+}
+
+// test mode: the tail of a guarded block against the canary, on the block's own device; outside the cache's mutex
+void debug_check(Cache& c, void* p, const Live& b) {
+  int cur = 0;
+  (void)hipGetDevice(&cur);
+  if (cur != b.dev) (void)hipSetDevice(b.dev);
+  std::vector<unsigned char> tail(b.sz - (size_t)b.asked);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess)
+    e = hipMemcpy(tail.data(), static_cast<char*>(p) + b.asked, tail.size(), hipMemcpyDeviceToHost);
+  if (cur != b.dev) (void)hipSetDevice(cur);
+  if (e != hipSuccess) {  // (not counted as checked: the report then shows fewer blocks checked than filled)
+    (void)hipGetLastError();
+    return;
+  }
+  const int64_t at = dev_debug_first_mismatch(tail.data(), tail.size(), DEBUG_CANARY);
+  std::lock_guard<std::mutex> lock(c.mu);
+  ++c.dbg_checked;
+  if (at >= 0) {
+    if (c.dbg_bad == 0) c.dbg_first = at;
+    ++c.dbg_bad;
+  }
+}
+
+}  // namespace
+
+hipError_t dev_malloc(void** p, size_t bytes) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  Cache& c = cache();
+  if (!g_debug.load(std::memory_order_relaxed)) return acquire(c, p, dev, rounded(bytes), -1);
+  const bool floating = dev_next_floating();
+  dev_next_floating() = false;
+  const size_t sz = dev_debug_size(bytes);
+  hipError_t e = acquire(c, p, dev, sz, (int64_t)bytes);
+  if (e != hipSuccess) return e;
+  e = debug_fill(*p, bytes, sz, floating);
+  {
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (e == hipSuccess) {
+      ++c.dbg_filled;
+    } else {  // (back into the cache unchecked)
+      c.live.erase(*p);
+      recycle_locked(c, *p, dev, sz);
+      *p = nullptr;
+    }
+  }
   return e;
 }
 
 void dev_free(void* p) {
   if (!p) return;
   Cache& c = cache();
+  Live b;
+  {
+    std::lock_guard<std::mutex> lock(c.mu);
+    auto it = c.live.find(p);
+    if (it == c.live.end()) {  // not ours
+      (void)hipFree(p);
+      return;
+    }
+    b = it->second;
+    c.live.erase(it);
+    if (b.asked < 0) {  // (every block while the test mode has never been on)
+      recycle_locked(c, p, b.dev, b.sz);
+      return;
+    }
+  }
+  debug_check(c, p, b);  // (nobody else can be handed the block before it is back in the cache)
   std::lock_guard<std::mutex> lock(c.mu);
-  auto it = c.live.find(p);
-  if (it == c.live.end()) {  // not ours
-    (void)hipFree(p);
-    return;
+  recycle_locked(c, p, b.dev, b.sz);
+}
+
+void dev_debug(bool on) {
+  Cache& c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  if (on) {
+    c.dbg_filled = c.dbg_checked = c.dbg_bad = 0;
+    c.dbg_first = -1;
   }
-  const std::pair<int, size_t> key = it->second;
-  c.live.erase(it);
-  if (key.second <= MAX_BLOCK && c.cached_bytes + key.second <= MAX_TOTAL) {
-    c.free_blocks[key].push_back(p);
-    c.cached_bytes += key.second;
-  } else {
-    (void)hipFree(p);
+  g_debug.store(on, std::memory_order_relaxed);
+}
+
+void dev_debug_report(int64_t out[4]) {
+  Cache& c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  out[0] = c.dbg_filled;
+  out[1] = c.dbg_checked;
+  out[2] = c.dbg_bad;
+  out[3] = c.dbg_first;
+}
+
+hipError_t dev_debug_probe(size_t bytes, bool floating, size_t overrun, unsigned char* out, size_t out_len,
+                           size_t* size) {
+  void* p = nullptr;
+  hipError_t e = dev_malloc_of(&p, bytes, floating);
+  if (e != hipSuccess) return e;
+  Cache& c = cache();
+  size_t sz = 0;
+  {
+    std::lock_guard<std::mutex> lock(c.mu);
+    sz = c.live[p].sz;
   }
+  if (overrun > sz || bytes > sz - overrun) e = hipErrorInvalidValue;  // it would leave the block
+  if (e == hipSuccess && overrun > 0) e = hipMemset(static_cast<char*>(p) + bytes, 0x5A, overrun);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && out && out_len > 0) e = hipMemcpy(out, p, std::min(sz, out_len), hipMemcpyDeviceToHost);
+  dev_free(p);
+  if (size) *size = sz;
+  return e;
 }
 
 void dev_in_use(int64_t out[2]) {
@@ -112,7 +220,7 @@ void dev_in_use(int64_t out[2]) {
   std::lock_guard<std::mutex> lock(c.mu);
   out[0] = (int64_t)c.live.size();
   out[1] = 0;
-  for (const auto& kv : c.live) out[1] += (int64_t)kv.second.second;
+  for (const auto& kv : c.live) out[1] += (int64_t)kv.second.sz;
 }
 
 int handle_count(int delta) {

@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // Returns SIM3OPT_ERR_HIP with "<call>: <hip's message>" in the `err` of the enclosing scope: the one form of "check a
@@ -28,12 +29,64 @@ namespace sim3opt {
 
 hipError_t dev_malloc(void** p, size_t bytes);
 void dev_free(void* p);
+// The element kind of the calling thread's next dev_malloc: what the test mode below fills the block with (it reads and
+// clears it; nothing else looks).  Every caller allocates through dev_malloc_of, which sets it.
+inline bool& dev_next_floating() {
+  static thread_local bool kind = false;
+  return kind;
+}
+inline hipError_t dev_malloc_of(void** p, size_t bytes, bool floating) {
+  dev_next_floating() = floating;
+  return dev_malloc(p, bytes);
+}
 void dev_cache_release();  // gives every cached block back to the driver
 // {blocks, bytes (as rounded)} dev_malloc has handed out and not got back, process-wide (sim3opt_device_memory_in_use)
 void dev_in_use(int64_t out[2]);
 // live handles of the process, of every type handle_device.hpp's handle_create makes (delta = +1 / -1; returns the new
 // count): the cache is released when the last one goes (sim3opt_release_device_cache does it on request)
 int handle_count(int delta);
+
+// ---- the test mode (sim3opt_debug_device_memory; tests/test_gpu_stale_memory.py) --------------------------------------
+// Off: dev_malloc and dev_free test one flag and do what they always did.  On: dev_malloc asks for
+// rounded(bytes + DEBUG_TAIL), so every block ends in a tail of at least DEBUG_TAIL bytes that no owner asked for, fills
+// [0, bytes) with 0xFF bytes (a quiet NaN in float and in double) where the element type is floating point and with
+// 0x00 where it is not (a stale integer may be an index: a poison that could send a load outside its array is not used),
+// and the tail with DEBUG_CANARY; dev_free compares the tail with the canary and counts the blocks that differ.  So a
+// floating-point read before the owner's write turns the result into NaN, and a write past the requested length is
+// counted.  Not covered: integer arrays, LDS, pinned host blocks, accesses outside the block.  The fill is a synchronous
+// hipMemset and a synchronisation of the block's device (the engine's streams are non-blocking), so nothing may allocate
+// inside a stream capture while the mode is on -- nothing does: the PCG's capture region launches kernels only.
+// Blocks handed out while the mode was off are not checked, so the mode may change while handles live.
+constexpr size_t DEBUG_TAIL = 256;  // rounded()'s smallest block
+constexpr unsigned char DEBUG_CANARY = 0xA5, DEBUG_NAN_BYTE = 0xFF;
+void dev_debug(bool on);               // switching it on resets the counters
+// {blocks filled, blocks checked at free, blocks whose tail was overwritten, first overwritten offset past the requested
+// size of the first such block or -1}
+void dev_debug_report(int64_t out[4]);
+// allocates `bytes` through dev_malloc, sets `overrun` bytes from offset `bytes` on (refused if they would leave the
+// block), copies the whole block -- `*size` bytes, at most out_len -- to `out` and frees it
+hipError_t dev_debug_probe(size_t bytes, bool floating, size_t overrun, unsigned char* out, size_t out_len, size_t* size);
+
+// the arithmetic of the mode, on the host alone (tests/cxx/devmem_owners_driver.cpp runs it against a stub allocator)
+inline size_t dev_rounded(size_t bytes) {  // eight steps per octave: at most 12.5 % more than asked for
+  if (bytes < 256) return 256;
+  size_t step = 256;
+  while ((step << 4) <= bytes) step <<= 1;
+  return (bytes + step - 1) / step * step;
+}
+inline size_t dev_debug_size(size_t bytes) { return dev_rounded(bytes + DEBUG_TAIL); }  // what the mode asks the driver for
+inline size_t dev_debug_tail_offset(size_t bytes) { return bytes; }
+inline size_t dev_debug_tail_length(size_t bytes) { return dev_debug_size(bytes) - bytes; }
+// index of the first byte of buf[0, n) that is not `want`, or -1
+inline int64_t dev_debug_first_mismatch(const unsigned char* buf, size_t n, unsigned char want) {
+  for (size_t i = 0; i < n; ++i)
+    if (buf[i] != want) return (int64_t)i;
+  return -1;
+}
+// Is a block of T filled as floating point?  float and double; a struct of doubles only says so by an overload for its
+// own type next to its definition (found through its namespace: sim3::Sim3, the bundle adjuster's Cam).
+template <typename T>
+constexpr bool dev_block_is_floating(const T*) { return std::is_floating_point<T>::value; }
 
 // The same idea for what else an engine creates and destroys around every re-initialisation (round 3: 2.9 of
 // the 4 ms a re-initialisation of KITTI-00 took were a stream, a dozen events, a pinned scalar block and twenty
@@ -78,7 +131,7 @@ class DevBuf {
   hipError_t alloc(size_t count) {  // (not zeroed; an earlier block goes first)
     dev_free(p_);
     p_ = nullptr;
-    return dev_malloc((void**)&p_, sizeof(T) * count);
+    return dev_malloc_of((void**)&p_, sizeof(T) * count, dev_block_is_floating((const T*)nullptr));
   }
   T* get() const { return p_; }
   operator T*() const { return p_; }
@@ -99,7 +152,8 @@ class DevArena {
   template <typename T>
   hipError_t raw(T*& p, size_t count) {
     void* q = nullptr;
-    const hipError_t e = dev_malloc(&q, sizeof(T) * std::max<size_t>(count, 1));
+    const hipError_t e = dev_malloc_of(&q, sizeof(T) * std::max<size_t>(count, 1),
+                                       dev_block_is_floating((const typename std::remove_cv<T>::type*)nullptr));
     if (e != hipSuccess) return e;
     blocks_.push_back(q);
     p = static_cast<T*>(q);

@@ -44,6 +44,7 @@ struct alignas(64) Sim3 {
   double t[3];
   double s;
 };
+constexpr bool dev_block_is_floating(const Sim3*) { return true; }  // doubles only (csrc/devmem.hpp's test mode)
 
 struct Opts {
   double eps;          // 1e-5, branch threshold (sim3_rv.h:133, :258)

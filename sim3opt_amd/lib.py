@@ -368,6 +368,9 @@ SYMBOLS = {
     "sim3opt_load_kitti_gt_loops": (C.c_int, [_vp, C.c_char_p]),
     "sim3opt_release_device_cache": (None, []),
     "sim3opt_device_memory_in_use": (None, [C.POINTER(C.c_int64)]),
+    "sim3opt_debug_device_memory": (None, [C.c_int32]),
+    "sim3opt_debug_device_memory_report": (None, [C.POINTER(C.c_int64)]),
+    "sim3opt_debug_device_memory_probe": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_ubyte), C.c_int64]),
     "sim3opt_write_poses": (C.c_int, [_vp, C.c_char_p, _ip]),
     "sim3opt_stepwise_scale_init": (C.c_int, [_vp, _dp]),
     "sim3opt_read_keyframe_bin": (C.c_int, [C.c_char_p, _ip, _dp, _dp, _ip, C.POINTER(C.c_uint32), _dp,
@@ -598,6 +601,37 @@ def device_memory_in_use():
     o = (C.c_int64 * 2)()
     load().sim3opt_device_memory_in_use(o)
     return int(o[0]), int(o[1])
+
+
+def release_device_cache():
+    """Gives the cached device blocks, streams, events and pinned blocks back to the runtime
+    (sim3opt_release_device_cache)."""
+    load().sim3opt_release_device_cache()
+
+
+def debug_device_memory(on):
+    """Switches the block cache's test mode (sim3opt_debug_device_memory): poisoned blocks with guarded tails.  Switching
+    it on resets the report's counters."""
+    load().sim3opt_debug_device_memory(int(bool(on)))
+
+
+def debug_device_memory_report():
+    """dict of filled, checked, overwritten (blocks) and first_offset (of the first overwritten tail, or -1) since the
+    test mode was last switched on (sim3opt_debug_device_memory_report)."""
+    o = (C.c_int64 * 4)()
+    load().sim3opt_debug_device_memory_report(o)
+    return dict(filled=int(o[0]), checked=int(o[1]), overwritten=int(o[2]), first_offset=int(o[3]))
+
+
+def debug_device_memory_probe(nbytes, floating, overrun=0):
+    """One block of `nbytes` bytes through the cache, `overrun` bytes set behind them, read back whole and freed
+    (sim3opt_debug_device_memory_probe): the block's bytes as a uint8 array."""
+    out = np.empty(int(nbytes) + int(nbytes) // 4 + 1024, dtype=np.uint8)  # (no block is rounded up further than this)
+    size = load().sim3opt_debug_device_memory_probe(int(nbytes), int(bool(floating)), int(overrun),
+                                                    out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.shape[0])
+    if size < 0 or size > out.shape[0]:
+        raise Sim3OptError(int(size), "debug_device_memory_probe")
+    return out[:size].copy()
 
 
 def default_options(**kw):
