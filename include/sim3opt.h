@@ -767,7 +767,7 @@ int sim3opt_comm_local_state(sim3opt_graph* g, int64_t out[2]);
  * call it yourself before allocating large device buffers of your own next to a live handle. */
 void sim3opt_release_device_cache(void);
 /* Diagnostic.  out = {blocks, bytes} of device memory the library has handed to its handles and calls and not got
- * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch / sim3opt_place_batch / sim3opt_vocabulary of the process, on all
+ * back: every live sim3opt_graph / sim3opt_ba / sim3opt_ba_batch / sim3opt_pnp_batch / sim3opt_match_batch / sim3opt_place_batch / sim3opt_vocabulary / sim3opt_surf_batch of the process, on all
  * devices; bytes as the block cache rounds them.  Blocks waiting in the cache for re-use are not counted.  The same before and after any call
  * that creates no handle and initialises none is what "this call keeps no device memory" means
  * (tests/test_gpu_device_memory.py). */
@@ -1755,6 +1755,161 @@ int sim3opt_vocabulary_save(const char* path, int32_t n_nodes, const int32_t* pa
 int sim3opt_vocabulary_load(const char* path, int32_t* n_nodes, int32_t** parent, float** centre, double** weight,
                             int32_t** word_id);
 void sim3opt_vocabulary_free(void* block);
+
+/* ---- batched SURF-64 extraction: keypoints and descriptors from the images, the head of the chain ----
+ * SurfExtractor::operator() (kitti_surf.cpp:501-523): cv::xfeatures2d::SURF::create(400), detect + compute, a 64-float
+ * descriptor per keypoint, once per keyframe.  Grey images in; kp_ptr, kp and desc out, in exactly the layout
+ * sim3opt_match_batch_set_frames, sim3opt_place_batch_set_frames and sim3opt_vocabulary_set_frames take.
+ * PARITY UNPINNED: OpenCV is not part of the reference tree, which holds no image, keypoint or descriptor either.
+ * Reference-held is the call site: minHessian = 400, every other parameter at SURF's default, descriptorSize() == 64,
+ * FSurf64 consuming 64 floats.  Everything about the algorithm is recalled from upstream's surf.cpp, marked [upstream
+ * recall] below, and an option where it is a number, so a wrong recollection costs a default.
+ * Definition.  The definition is the specification: the device is held to it bit for bit, and it to planted truth.
+ * Arithmetic: the integral image is int32 and exact (set_images refuses 255 w h >= 2^31).  Every floating-point step
+ *   below is FP32, rounded once per operation and never fused, in the order written (a + b + c is (a + b) + c);
+ *   "rint" rounds a half to even; no libm function whose last bit may differ between host and device is used: the
+ *   Gaussian tables are made once on the host in double and rounded once to FP32, the angle is the polynomial below,
+ *   sin and cos are the polynomials below, sqrt is correctly rounded.
+ * Integral image: S is (h + 1) x (w + 1) with a zero first row and column; S[y + 1][x + 1] = sum of the pixels [0..y] x
+ *   [0..x].  A box {x1, y1, x2, y2} anchored at (y, x) sums to S[y+y1][x+x1] + S[y+y2][x+x2] - S[y+y2][x+x1] - S[y+y1][x+x2].
+ * Layers: octave o of n_octaves has layers l = 0 .. n_octave_layers + 1; filter size (9 + 6 l) << o, step = 1 << o; the
+ *   response plane has (h / step) x (w / step) entries (upstream's (rows - 1) / step is taken on the integral image's
+ *   rows, which are h + 1: that reading is kept).  [upstream recall]
+ * Response: the size-9 patterns {x1, y1, x2, y2, weight} are Dxx {0,2,3,7,+1} {3,2,6,7,-2} {6,2,9,7,+1}, Dyy their
+ *   transpose, Dxy {1,1,4,4,+1} {5,1,8,4,-1} {1,5,4,8,-1} {5,5,8,8,+1}.  Resized to `size`: every corner coordinate c
+ *   becomes rint(fl(size / 9) * c), the weight fl(weight / fl(fl(x2 - x1) * fl(y2 - y1))).  A response is 0 + (float)
+ *   box_0 * w_0 + (float) box_1 * w_1 + ... in pattern order.  det = fl(dx * dy) - fl(fl(0.81 * dxy) * dxy), trace = dx +
+ *   dy, stored at (i + margin, j + margin) with margin = (size / 2) / step for sample (i, j) anchored at (i step, j
+ *   step), i < 1 + (h - size) / step, j < 1 + (w - size) / step; every other entry of the plane is 0 (ours: upstream
+ *   leaves them unwritten), and a layer whose size exceeds h or w has no samples.
+ * Extrema: middle layers l = 1 .. n_octave_layers; positions margin' <= i < h / step - margin' (j likewise) with
+ *   margin' = (size_{l+1} / 2) / step + 1.  A candidate has det > (float) hessian_threshold and det strictly greater
+ *   than all 26 neighbours in the three layers.  Centre = step (i - (size / 2) / step) + (size - 1) 0.5 in both axes
+ *   (x from j), size = size_l, response = det, laplacian = the sign of trace (-1, 0, 1), octave = o.
+ * Interpolation: with N(dl, di, dj) the 27 values, b = -((N(0,0,1) - N(0,0,-1)) / 2, (N(0,1,0) - N(0,-1,0)) / 2,
+ *   (N(1,0,0) - N(-1,0,0)) / 2); A is symmetric with diagonal (N(0,0,-1) - 2 N(0,0,0)) + N(0,0,1) (and the same in i and
+ *   in l) and off-diagonals (((N(+,+) - N(+,-)) - N(-,+)) + N(-,-)) / 4 over the pair of axes, the layer axis first in
+ *   the signs' order for the two layer terms (xs: N(1,0,1) - N(1,0,-1) - N(-1,0,1) + N(-1,0,-1)).  A x = b by Gaussian
+ *   elimination with partial pivoting (the first row of largest |entry| in the column), back-substitution x2, x1, x0;
+ *   a zero pivot means no solution.  Kept iff a solution exists, x != 0 and every |x_k| <= 1; then pt += (x0, x1)
+ *   step and size = rint(size + x2 (size_l - size_{l-1})).  [upstream recall]
+ * Order and cap: within an image the kept candidates are ordered by response descending, ties by scan index
+ *   ascending (octave, layer, row, column).  A STATED NARROWING of upstream's KeypointGreater, whose further keys can
+ *   only differ on equal responses.  max_keypoints > 0 keeps the first that many (ours).  No atomic decides the order.
+ * Orientation (upright = 1 skips it: angle = 270 [upstream recall]): s = size 1.2 / 9, g = 2 rint(2 s).  The 113 grid
+ *   points (i, j), i^2 + j^2 <= 36, i outer and j inner, weigh G13[i + 6] G13[j + 6] (13 taps of sigma 2.5, scaled to
+ *   sum 1).  Sample k sits at x = rint((pt.x + i s) - (g - 1) / 2), y = rint((pt.y + j s) - (g - 1) / 2) and counts
+ *   when 0 <= x < w + 1 - g and 0 <= y < h + 1 - g; its vx, vy are the Haar responses {0,0,2,4,-1} {2,0,4,4,+1} and
+ *   {0,0,4,2,+1} {0,2,4,4,-1}, resized from 4 to g, times the weight.  A keypoint with no such sample (so also one
+ *   whose g exceeds the integral image) is dropped.  The angle function atan2deg(y, x), degrees in [0, 360]: with
+ *   ax = |x|, ay = |y|, c = min / (max + (float) DBL_EPSILON) and P(c) = (((p7 c^2 + p5) c^2 + p3) c^2 + p1) c, where p1,
+ *   p3, p5, p7 = 0.9997878412794807, -0.3258083974640975, 0.1555786518463281, -0.04432655554792128 each times (float)
+ *   (180 / pi): a = P(c) if ax >= ay else 90 - P(c); x < 0: a = 180 - a; y < 0: a = 360 - a.  [upstream recall; the
+ *   coefficients are the definition either way, they make the function plain arithmetic.]  For each window centre c =
+ *   0, 5, ..., 355 the sums of vx and of vy run over the samples with d = |rint(angle) - c|, d < 30 or d > 330, in
+ *   sample order; the first window of largest sumx^2 + sumy^2 (strictly greater than 0 to start with) gives angle =
+ *   atan2deg(-sumy, sumx): upstream's sign convention, fastAtan2(-besty, bestx).  [upstream recall]
+ * Descriptor: win = (int)(21 s); a keypoint with win < 1 is dropped (ours).  (sin, cos) of the angle: q = (int)(angle /
+ *   90) and r = (angle - 90 q) pi / 180 in double, sin r and cos r by their Taylor polynomials to r^19 and r^18 in nested
+ *   form in double, turned by the quadrant, rounded once to FP32 (ours: upstream calls libm).  With sin_dir = -sin,
+ *   cos_dir = cos and off = -(win - 1) / 2, window sample (row i, column j) is at px = (pt.x + (j + off) cos_dir) + (i
+ *   + off) sin_dir, py = (pt.y - (j + off) sin_dir) + (i + off) cos_dir (ours: in closed form, where upstream adds
+ *   increments one after the other).  Where 0 <= floor(px) < w - 1 and 0 <= floor(py) < h - 1 its value is rint of
+ *   ((p00 (1-a)) (1-b) + (p01 a) (1-b)) + (p10 (1-a)) b + (p11 a) b with a, b the fractions; elsewhere the pixel at (rint
+ *   px, rint py) clamped into the image.  The 21 x 21 patch: cell (u, v) covers [u win/21, (u+1) win/21) in each axis
+ *   (scale = fl(win / 21), bounds fl(u scale)); a sample i weighs fl(min(upper, i + 1) - max(lower, i)) where positive;
+ *   the cell is the sum of (wy wx) sample, row-major, over fl(scale scale), rint, clamped to 0..255 [upstream recall:
+ *   area resize into an 8-bit patch].  On the 20 x 20 interior vx = (((p01 - p00) + p11) - p10) dw and vy = (((p10 -
+ *   p00) + p11) - p01) dw with dw = G20[row] G20[column] (20 taps of sigma 3.3).  Sub-region r = 4 i + j of 5 x 5 gives
+ *   sum vx, sum vy, sum |vx|, sum |vy|, its samples row-major: 64 floats in sub-region order, each times 1 / (sqrt(sum of
+ *   the 64 squares in ascending index) + FLT_EPSILON).  Only the 64-float form exists: `extended` is not an option.
+ * An image's result is a function of the image and the options alone: not of the other images, its place among them
+ * or images_per_pass.  One image size per batch.
+ * Device pipeline: sim3opt_amd/csrc/surf_batch.hip; the launches of a pass do not depend on the number of images in
+ * it; the response planes never leave LDS.  No CPU fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_surf_batch sim3opt_surf_batch;
+
+typedef struct sim3opt_surf_batch_options {
+  double hessian_threshold; /* minHessian, >= 0 and finite                              default 400 (the call site)  */
+  int32_t n_octaves;        /* 1..6                                                     default 4  [upstream recall] */
+  int32_t n_octave_layers;  /* 1..6                                                     default 3  [upstream recall] */
+  int32_t upright;          /* 1: no orientation step, angle = 270                      default 0                    */
+  int32_t max_keypoints;    /* > 0: the strongest that many per image; 0: no cap        default 0                    */
+  int32_t images_per_pass;  /* >= 1: bounds the device memory of a pass                 default 64                   */
+  int32_t device;           /* HIP device ordinal, -1 = current                         default -1                   */
+} sim3opt_surf_batch_options;
+
+#define SIM3OPT_SURF_OK 0            /* the image has keypoints */
+#define SIM3OPT_SURF_NO_KEYPOINTS 1  /* none: no layer fits, nothing above the threshold, or every one dropped */
+
+void sim3opt_surf_batch_options_default(sim3opt_surf_batch_options* o);
+sim3opt_surf_batch* sim3opt_surf_batch_create(void);
+void sim3opt_surf_batch_destroy(sim3opt_surf_batch* b);
+const char* sim3opt_surf_batch_last_error(const sim3opt_surf_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: hessian_threshold negative or not finite, n_octaves or n_octave_layers outside
+ * 1..6, upright not 0 or 1, max_keypoints < 0, images_per_pass < 1. */
+int sim3opt_surf_batch_set_options(sim3opt_surf_batch* b, const sim3opt_surf_batch_options* o);
+/* n_images grey images of one size, row-major, row_stride bytes from row to row and height rows from image to image;
+ * copied.  SIM3OPT_ERR_ARG with nothing changed: n_images < 1, pixels NULL, width or height < 1, row_stride < width,
+ * 255 width height >= 2^31.  A successful call drops the results of the last solve. */
+int sim3opt_surf_batch_set_images(sim3opt_surf_batch* b, int32_t n_images, int32_t width, int32_t height, int32_t row_stride,
+                                  const uint8_t* pixels);
+/* Each may be NULL.  total_keypoints is 0 before the first solve.  tiles[3]: the side of the detection tile, the keys
+ * the ranking stages at a time, the lanes per keypoint: the sizes at which a kernel takes another path. */
+int sim3opt_surf_batch_dims(const sim3opt_surf_batch* b, int32_t* n_images, int32_t* width, int32_t* height,
+                            int32_t* total_keypoints, int32_t tiles[3]);
+/* Returns the number of images with status SIM3OPT_SURF_OK, or a negative SIM3OPT_ERR_* (SIM3OPT_ERR_STATE: no images
+ * set; SIM3OPT_ERR_ARG: a pass of images_per_pass images could hold more candidates than an int32 offset counts, at
+ * most one per 2 x 2 block of every middle layer -- at the defaults 256 images of 4096 x 2056 could, 128 cannot; lower
+ * images_per_pass); an
+ * image's outcome is its status, never the batch's. */
+int sim3opt_surf_batch_solve(sim3opt_surf_batch* b);
+/* The getters return SIM3OPT_ERR_STATE before the first solve.  kp_ptr: n_images + 1. */
+int sim3opt_surf_batch_get_kp_ptr(const sim3opt_surf_batch* b, int32_t* kp_ptr);
+/* Per keypoint, each may be NULL: kp (x, y), desc (x 64), size, angle (degrees), response, octave, laplacian. */
+int sim3opt_surf_batch_get_keypoints(const sim3opt_surf_batch* b, float* kp, float* desc, float* size, float* angle,
+                                     float* response, int32_t* octave, int32_t* laplacian);
+/* Per image, each may be NULL: status (SIM3OPT_SURF_*), the candidates before the interpolation and after it, and the
+ * keypoints dropped at the orientation step.  n_interpolated counts before max_keypoints is applied, so with a cap the
+ * image's keypoints are min(n_interpolated, max_keypoints) - n_dropped.  The drop rule is upstream's and is kept as the
+ * definition, but no image reaches it: a layer yields candidates only where the next layer's filter fits with a margin,
+ * which puts the keypoint at least size / 2 inside the image while g is about 0.53 size, so its central orientation
+ * sample always counts, and win >= 8.  n_dropped is therefore 0 for every image; the path is exercised on the host
+ * alone (tests/cxx/surf_host_driver.cpp calls the description with a size no layer has). */
+int sim3opt_surf_batch_get_summary(const sim3opt_surf_batch* b, int32_t* status, int32_t* n_candidates,
+                                   int32_t* n_interpolated, int32_t* n_dropped);
+/* Read-outs for tests.  Each takes its image through a pass of its own with the options of the last solve, leaves that
+ * solve's results untouched and hands back every block it takes.  SIM3OPT_ERR_STATE before the first solve.
+ * S: (height + 1) x (width + 1). */
+int sim3opt_surf_batch_debug_integral(sim3opt_surf_batch* b, int32_t image, int32_t* S);
+/* The detection kernel's LDS values of layer `layer` (0 .. n_octave_layers + 1) of `octave`, written out by the DUMP
+ * instantiation, whose other stores are the counting one's; trace is computed beside them.  rows x cols = (height >>
+ * octave) x (width >> octave) each; call with det and trace NULL for the sizes. */
+int sim3opt_surf_batch_debug_responses(sim3opt_surf_batch* b, int32_t image, int32_t octave, int32_t layer, int32_t* rows,
+                                       int32_t* cols, float* det, float* trace);
+/* The candidates of an image in scan order: layer (octave * 8 + layer), pos0 (x 3: x, y, size before the
+ * interpolation), response, kept, pos1 (x 3: after it; pos0 where not kept).  Room for the image's n_candidates of
+ * sim3opt_surf_batch_get_summary each; each may be NULL. */
+int sim3opt_surf_batch_debug_candidates(sim3opt_surf_batch* b, int32_t image, int32_t* n_candidates, int32_t* layer,
+                                        float* pos0, float* response, uint8_t* kept, float* pos1);
+/* Of keypoint `keypoint` (an index into the last solve's outputs): per orientation sample (113 each) whether it
+ * counts, vx, vy and its angle; the 72 window magnitudes.  Each may be NULL. */
+int sim3opt_surf_batch_debug_orientation(sim3opt_surf_batch* b, int32_t keypoint, int32_t* valid, float* vx, float* vy,
+                                         float* angle, float* window);
+/* ... and its 21 x 21 patch, row-major. */
+int sim3opt_surf_batch_debug_patch(sim3opt_surf_batch* b, int32_t keypoint, float* patch);
+/* A TEST AID, and the one exception to "no CPU fallback": the definition above restated serially on the host for one
+ * image, in the same FP32 operations and orders (sim3opt_amd/csrc/surf_host.hpp).  It needs no device and is never
+ * used by sim3opt_surf_batch_solve.  Returns the image's number of keypoints (the arrays receive the first `capacity`
+ * of them, each may be NULL) or SIM3OPT_ERR_ARG for what set_options or set_images would refuse.  counts[3]: the
+ * candidates before and after the interpolation, the keypoints dropped.  S as debug_integral; det, trace of (resp_octave,
+ * resp_layer) as debug_responses; the first cand_capacity candidates as debug_candidates.  Each may be NULL. */
+int sim3opt_surf_reference_image(const sim3opt_surf_batch_options* o, int32_t width, int32_t height, int32_t row_stride,
+                                 const uint8_t* pixels, int32_t capacity, float* kp, float* desc, float* size, float* angle,
+                                 float* response, int32_t* octave, int32_t* laplacian, int32_t counts[3], int32_t* S,
+                                 int32_t resp_octave, int32_t resp_layer, float* det, float* trace, int32_t cand_capacity,
+                                 int32_t* cand_layer, float* cand_pos0, float* cand_response, uint8_t* cand_kept,
+                                 float* cand_pos1);
 
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933

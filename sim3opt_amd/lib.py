@@ -239,6 +239,19 @@ class VocabularyOptions(C.Structure):
     ]
 
 
+class SurfBatchOptions(C.Structure):
+    """sim3opt_surf_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("hessian_threshold", C.c_double),
+        ("n_octaves", C.c_int32),
+        ("n_octave_layers", C.c_int32),
+        ("upright", C.c_int32),
+        ("max_keypoints", C.c_int32),
+        ("images_per_pass", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -528,6 +541,25 @@ SYMBOLS = {
     "sim3opt_vocabulary_save": (C.c_int, [C.c_char_p, C.c_int32, _ip, _fp, _dp, _ip]),
     "sim3opt_vocabulary_load": (C.c_int, [C.c_char_p, _ip, C.POINTER(_ip), C.POINTER(_fp), C.POINTER(_dp), C.POINTER(_ip)]),
     "sim3opt_vocabulary_free": (None, [_vp]),
+    "sim3opt_surf_batch_options_default": (None, [C.POINTER(SurfBatchOptions)]),
+    "sim3opt_surf_batch_create": (_vp, []),
+    "sim3opt_surf_batch_destroy": (None, [_vp]),
+    "sim3opt_surf_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_surf_batch_set_options": (C.c_int, [_vp, C.POINTER(SurfBatchOptions)]),
+    "sim3opt_surf_batch_set_images": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _up]),
+    "sim3opt_surf_batch_dims": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_surf_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_surf_batch_get_kp_ptr": (C.c_int, [_vp, _ip]),
+    "sim3opt_surf_batch_get_keypoints": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _ip, _ip]),
+    "sim3opt_surf_batch_get_summary": (C.c_int, [_vp, _ip, _ip, _ip, _ip]),
+    "sim3opt_surf_batch_debug_integral": (C.c_int, [_vp, C.c_int32, _ip]),
+    "sim3opt_surf_batch_debug_responses": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _ip, _ip, _fp, _fp]),
+    "sim3opt_surf_batch_debug_candidates": (C.c_int, [_vp, C.c_int32, _ip, _ip, _fp, _fp, _up, _fp]),
+    "sim3opt_surf_batch_debug_orientation": (C.c_int, [_vp, C.c_int32, _ip, _fp, _fp, _fp, _fp]),
+    "sim3opt_surf_batch_debug_patch": (C.c_int, [_vp, C.c_int32, _fp]),
+    "sim3opt_surf_reference_image": (C.c_int, [C.POINTER(SurfBatchOptions), C.c_int32, C.c_int32, C.c_int32, _up, C.c_int32,
+                                               _fp, _fp, _fp, _fp, _fp, _ip, _ip, _ip, _ip, C.c_int32, C.c_int32, _fp, _fp,
+                                               C.c_int32, _ip, _fp, _fp, _up, _fp]),
 }
 
 _lib = None
@@ -1555,7 +1587,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch and VocabularyTrainer share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch, VocabularyTrainer and SurfBatch share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -2436,6 +2468,167 @@ class VocabularyTrainer(_Handle):
         self._chk(self._L.sim3opt_vocabulary_debug_lloyd(self._b, int(level), int(n_pass), C.byref(f), C.byref(n),
                                                          _p(cl, _ip), _p(ce, _fp)), "vocabulary_debug_lloyd")
         return dict(first_node=f.value, cluster=cl, centre=ce)
+
+
+SURF_OK, SURF_NO_KEYPOINTS = 0, 1
+
+
+class SurfBatch(_Handle):
+    """sim3opt_surf_batch*: SURF-64 keypoints and descriptors of a batch of grey images of one size
+    (SurfExtractor::operator(), kitti_surf.cpp:501-523), the head of the chain: kp_ptr(), and kp / desc of keypoints(),
+    are what MatchBatch.set_frames, PlaceBatch.set_frames and VocabularyTrainer.set_frames take.  PARITY UNPINNED:
+    include/sim3opt.h holds the definition and says what is the call site's and what is recalled from upstream."""
+    _prefix, _Options = "surf_batch", SurfBatchOptions
+    TILES = ("detect_tile", "rank_tile", "keypoint_lanes")
+    FIELDS = ("kp", "desc", "size", "angle", "response", "octave", "laplacian")
+
+    def set_images(self, images):
+        """images: uint8, n x h x w (or h x w for one)"""
+        a = np.ascontiguousarray(images, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("images: n x h x w")
+        n, h, w = a.shape
+        if a.size == 0:
+            a = np.zeros(1, dtype=np.uint8)  # (the C-ABI refuses a NULL array; it refuses the size first)
+        self._chk(self._L.sim3opt_surf_batch_set_images(self._b, n, w, h, w, _p(a, _up)), "surf_batch_set_images")
+
+    def dims(self):
+        """dict: n_images, width, height, total_keypoints and the kernels' tile sizes (TILES)"""
+        v = [C.c_int32() for _ in range(4)]
+        t = (C.c_int32 * 3)()
+        self._chk(self._L.sim3opt_surf_batch_dims(self._b, *(C.byref(x) for x in v), t), "surf_batch_dims")
+        out = dict(zip(("n_images", "width", "height", "total_keypoints"), (x.value for x in v)))
+        out.update(zip(self.TILES, t))
+        return out
+
+    def solve(self):
+        """The number of images with keypoints; raises when the library reports an error."""
+        return self._count(self._L.sim3opt_surf_batch_solve(self._b), "surf_batch_solve")
+
+    def kp_ptr(self):
+        p = np.empty(self.dims()["n_images"] + 1, dtype=np.int32)
+        self._chk(self._L.sim3opt_surf_batch_get_kp_ptr(self._b, _p(p, _ip)), "surf_batch_get_kp_ptr")
+        return p
+
+    @staticmethod
+    def _arrays(n):
+        return dict(kp=np.empty((n, 2), dtype=np.float32), desc=np.empty((n, 64), dtype=np.float32),
+                    size=np.empty(n, dtype=np.float32), angle=np.empty(n, dtype=np.float32),
+                    response=np.empty(n, dtype=np.float32), octave=np.empty(n, dtype=np.int32),
+                    laplacian=np.empty(n, dtype=np.int32))
+
+    def keypoints(self):
+        """dict of FIELDS over all keypoints; image f owns [kp_ptr()[f], kp_ptr()[f + 1])"""
+        o = self._arrays(self.dims()["total_keypoints"])
+        self._chk(self._L.sim3opt_surf_batch_get_keypoints(
+            self._b, *(_p(o[f], _fp) for f in self.FIELDS[:5]), _p(o["octave"], _ip), _p(o["laplacian"], _ip)),
+            "surf_batch_get_keypoints")
+        return o
+
+    def summary(self):
+        """dict of per-image arrays: status, n_candidates, n_interpolated, n_dropped"""
+        n = self.dims()["n_images"]
+        names = ("status", "n_candidates", "n_interpolated", "n_dropped")
+        o = {k: np.empty(n, dtype=np.int32) for k in names}
+        self._chk(self._L.sim3opt_surf_batch_get_summary(self._b, *(_p(o[k], _ip) for k in names)), "surf_batch_get_summary")
+        return o
+
+    def debug_integral(self, image):
+        d = self.dims()
+        S = np.empty((d["height"] + 1, d["width"] + 1), dtype=np.int32)
+        self._chk(self._L.sim3opt_surf_batch_debug_integral(self._b, int(image), _p(S, _ip)), "surf_batch_debug_integral")
+        return S
+
+    def debug_responses(self, image, octave, layer):
+        """(det, trace) of a layer, rows x cols each"""
+        r, c = C.c_int32(), C.c_int32()
+        a = (self._b, int(image), int(octave), int(layer), C.byref(r), C.byref(c))
+        self._chk(self._L.sim3opt_surf_batch_debug_responses(*a, None, None), "surf_batch_debug_responses")
+        det, tr = (np.empty((r.value, c.value), dtype=np.float32) for _ in range(2))
+        if det.size:
+            self._chk(self._L.sim3opt_surf_batch_debug_responses(*a, _p(det, _fp), _p(tr, _fp)), "surf_batch_debug_responses")
+        return det, tr
+
+    @staticmethod
+    def _cand_arrays(n):
+        n = max(n, 1)
+        return dict(layer=np.empty(n, dtype=np.int32), pos0=np.empty((n, 3), dtype=np.float32),
+                    response=np.empty(n, dtype=np.float32), kept=np.empty(n, dtype=np.uint8),
+                    pos1=np.empty((n, 3), dtype=np.float32))
+
+    def debug_candidates(self, image):
+        """dict: octave, layer, pos0 (x, y, size before the interpolation), response, kept, pos1; scan order"""
+        n = C.c_int32()
+        a = (self._b, int(image), C.byref(n))
+        self._chk(self._L.sim3opt_surf_batch_debug_candidates(*a, None, None, None, None, None), "surf_batch_debug_candidates")
+        o = self._cand_arrays(n.value)
+        if n.value:
+            self._chk(self._L.sim3opt_surf_batch_debug_candidates(*a, _p(o["layer"], _ip), _p(o["pos0"], _fp),
+                                                                  _p(o["response"], _fp), _p(o["kept"], _up),
+                                                                  _p(o["pos1"], _fp)), "surf_batch_debug_candidates")
+        return self._cand_out(o, n.value)
+
+    @staticmethod
+    def _cand_out(o, n):
+        o = {k: v[:n].copy() for k, v in o.items()}
+        o["octave"], o["layer"] = o["layer"] // 8, o["layer"] % 8
+        return o
+
+    def debug_orientation(self, keypoint):
+        """dict: valid, vx, vy, angle (113 each) and window (72)"""
+        o = dict(valid=np.empty(113, dtype=np.int32), vx=np.empty(113, dtype=np.float32), vy=np.empty(113, dtype=np.float32),
+                 angle=np.empty(113, dtype=np.float32), window=np.empty(72, dtype=np.float32))
+        self._chk(self._L.sim3opt_surf_batch_debug_orientation(self._b, int(keypoint), _p(o["valid"], _ip), _p(o["vx"], _fp),
+                                                               _p(o["vy"], _fp), _p(o["angle"], _fp), _p(o["window"], _fp)),
+                  "surf_batch_debug_orientation")
+        return o
+
+    def debug_patch(self, keypoint):
+        p = np.empty((21, 21), dtype=np.float32)
+        self._chk(self._L.sim3opt_surf_batch_debug_patch(self._b, int(keypoint), _p(p, _fp)), "surf_batch_debug_patch")
+        return p
+
+    @classmethod
+    def reference_image(cls, img, responses=None, **options):
+        """A test aid: the header's definition restated serially on the host (no device) for one image.  dict of
+        FIELDS, counts (candidates, interpolated, dropped), S, candidates (as debug_candidates) and, with
+        responses=(octave, layer), det and trace of that layer."""
+        L = load()
+        o = SurfBatchOptions()
+        L.sim3opt_surf_batch_options_default(C.byref(o))
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        if a.ndim != 2 or a.size == 0:
+            raise ValueError("img: h x w")
+        h, w = a.shape
+        S = np.empty((h + 1, w + 1), dtype=np.int32)
+        ro, rl = responses if responses is not None else (0, 0)
+        det, tr = (np.empty((h >> ro, w >> ro), dtype=np.float32) for _ in range(2))
+        counts = np.zeros(3, dtype=np.int32)
+        cap, ccap = 4096, 4096
+        while True:
+            k, c = cls._arrays(cap), cls._cand_arrays(ccap)
+            n = L.sim3opt_surf_reference_image(
+                C.byref(o), w, h, w, _p(a, _up), cap, *(_p(k[f], _fp) for f in cls.FIELDS[:5]), _p(k["octave"], _ip),
+                _p(k["laplacian"], _ip), _p(counts, _ip), _p(S, _ip), ro, rl,
+                _p(det, _fp) if responses is not None and det.size else None,
+                _p(tr, _fp) if responses is not None and det.size else None, ccap, _p(c["layer"], _ip), _p(c["pos0"], _fp),
+                _p(c["response"], _fp), _p(c["kept"], _up), _p(c["pos1"], _fp))
+            if n < 0:
+                raise Sim3OptError(n, "surf_reference_image")
+            if n <= cap and counts[0] <= ccap:
+                break
+            cap, ccap = max(cap, n), max(ccap, int(counts[0]))
+        out = {f: v[:n].copy() for f, v in k.items()}
+        out.update(counts=counts, S=S, candidates=cls._cand_out(c, int(counts[0])))
+        if responses is not None:
+            out.update(det=det, trace=tr)
+        return out
 
 
 def vocabulary_save(path, parent, centre, weight, word_id):
