@@ -1911,6 +1911,76 @@ int sim3opt_surf_reference_image(const sim3opt_surf_batch_options* o, int32_t wi
                                  int32_t* cand_layer, float* cand_pos0, float* cand_response, uint8_t* cand_kept,
                                  float* cand_pos1);
 
+/* ---- device-resident frame store (sim3opt_amd/csrc/frames.hip, frames_host.hpp) ----
+ * One owner for "the frames of a sequence" on one device: kp_ptr (int32, n_frames + 1), kp (float, 2 N) and desc
+ * (float, 64 N), contiguous, in the layout sim3opt_match_batch_set_frames, sim3opt_place_batch_set_frames and
+ * sim3opt_vocabulary_set_frames take.  The extractor fills it on the device (sim3opt_surf_batch_solve_into) and the
+ * three consumers read it in place (sim3opt_*_set_frames_from): the descriptors cross the host boundary never, and the
+ * device holds them once.
+ *   Snapshots.  What a store holds is an immutable, reference-counted snapshot.  A fill (sim3opt_frames_set,
+ * sim3opt_surf_batch_solve_into, sim3opt_frames_debug_compact) makes a new one; a consumer that took the earlier one
+ * keeps it alive and unchanged; the blocks go back to the device cache when the last holder -- the store or a consumer
+ * -- lets go.  A fill has synchronised its stream before it returns, so consumers on streams of their own only ever
+ * read finished memory and no event crosses streams.  A failed fill leaves the store as it was.
+ *   The ordered compaction (k_frames_count, k_frames_scan_images, k_frames_move; new with the store): per image the
+ * predicate state == 2 over the slots [cand_ptr[i], cand_ptr[i + 1]) is scanned in tiles of compact_tile slots, the
+ * carry running from tile to tile; the kept rows are written in slot order behind those of the images before; the kept
+ * count of every image is emitted.  No atomic takes part.  A 256-byte descriptor row is moved by 16 lanes with one
+ * 16-byte load and store each, four rows a wavefront.
+ * No CPU fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_frames sim3opt_frames;
+
+typedef struct sim3opt_frames_options {
+  int32_t device; /* -1: the calling thread's current device at the fill [-1] */
+} sim3opt_frames_options;
+
+void sim3opt_frames_options_default(sim3opt_frames_options* o);
+sim3opt_frames* sim3opt_frames_create(void);
+void sim3opt_frames_destroy(sim3opt_frames* s); /* consumers that took its snapshot keep theirs */
+const char* sim3opt_frames_last_error(const sim3opt_frames* s);
+/* SIM3OPT_ERR_ARG, nothing changed: a device below -1.  Another device than before empties the store (consumers keep
+ * what they took). */
+int sim3opt_frames_set_options(sim3opt_frames* s, const sim3opt_frames_options* o);
+/* One upload from host arrays: replaces the three private uploads of the consumers' set_frames.  SIM3OPT_ERR_ARG with
+ * nothing changed, in the words of those entries: n_frames < 1, a NULL array, a pointer array that does not start at 0
+ * or decreases, too many keypoints for the int32 offsets, a non-finite keypoint or descriptor. */
+int sim3opt_frames_set(sim3opt_frames* s, int32_t n_frames, const int32_t* kp_ptr, const float* kp, const float* desc);
+/* Each may be NULL.  Before a fill: zeros, device -1.  desc_bytes: 256 N, the descriptor block as asked of the
+ * allocator.  tiles: {compact_tile, row_lanes}. */
+int sim3opt_frames_get_dims(const sim3opt_frames* s, int32_t* n_frames, int32_t* total_keypoints, int32_t* device,
+                            int64_t* desc_bytes, int32_t tiles[2]);
+/* The read-back (what sim3opt_surf_batch_get_keypoints' desc was): any pointer may be NULL.  SIM3OPT_ERR_STATE before
+ * a fill. */
+int sim3opt_frames_get(sim3opt_frames* s, int32_t* kp_ptr, float* kp, float* desc);
+/* The compaction as an operator: the kernels of sim3opt_surf_batch_solve_into on caller-supplied slot arrays
+ * (cand_ptr: n_images + 1; state: a value of 0 .. 3 per slot; slot_kp: 2 floats, slot_desc: 64 floats per slot); the
+ * store is filled with the rows of state 2 in slot order.  SIM3OPT_ERR_ARG with nothing changed: n_images < 1, a NULL
+ * array, a cand_ptr that does not start at 0 or decreases, a state outside 0 .. 3, a non-finite value. */
+int sim3opt_frames_debug_compact(sim3opt_frames* s, int32_t n_images, const int32_t* cand_ptr, const int32_t* state,
+                                 const float* slot_kp, const float* slot_desc);
+
+/* sim3opt_surf_batch_solve, but kp and desc stay on the device: it replaces solve + get_keypoints(kp, desc) + the
+ * consumers' uploads.  Same kernels and passes; the descriptors are not read back, and the host loop that dropped the
+ * slots without a descriptor is the ordered compaction above for kp and desc.  Passes append: the store's arrays are
+ * joined once, contiguous.  Afterwards get_kp_ptr, get_summary and get_keypoints with desc = NULL answer as after
+ * solve; get_keypoints with desc != NULL answers SIM3OPT_ERR_STATE (read the store: sim3opt_frames_get).  Returns as
+ * solve does.  SIM3OPT_ERR_ARG with the handle, the store and the device memory in use unchanged: a NULL store, a store
+ * whose options.device names another device than the extractor's, a total beyond the int32 offsets. */
+int sim3opt_surf_batch_solve_into(sim3opt_surf_batch* b, sim3opt_frames* store);
+/* The consumers take the store's current snapshot in place of sim3opt_*_set_frames' arrays: no upload, no private
+ * copy; everything downstream behaves as after set_frames with the same arrays.  SIM3OPT_ERR_ARG: a NULL store, a
+ * handle whose options.device resolves to another device than the snapshot's, and what set_frames refuses of the frame
+ * count, the descriptors (the trainer: all equal) or the remaining arguments; SIM3OPT_ERR_STATE: an unfilled store.
+ * A refusal changes nothing.  set_frames afterwards drops the snapshot, and the other way round; set_options with
+ * another device while a snapshot is held is SIM3OPT_ERR_ARG. */
+int sim3opt_vocabulary_set_frames_from(sim3opt_vocabulary* b, const sim3opt_frames* store);
+int sim3opt_place_batch_set_frames_from(sim3opt_place_batch* b, const sim3opt_frames* store);
+/* n_frames (the length of obs_ptr less one: it must be the store's frame count), obs_ptr, obs_uv, obs_depth and the
+ * intrinsics: as sim3opt_match_batch_set_frames */
+int sim3opt_match_batch_set_frames_from(sim3opt_match_batch* b, const sim3opt_frames* store, int32_t n_frames,
+                                        const int32_t* obs_ptr, const float* obs_uv, const float* obs_depth, double focal,
+                                        double cx, double cy, int32_t image_width, int32_t image_height);
+
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933
  * Null vector of the edge equations s_C x[v0] - x[v1] = 0 (the reference: last column of V of

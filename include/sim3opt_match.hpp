@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "sim3opt.h"
+#include "sim3opt_frames.hpp"
 #include "sim3opt_pnp.hpp"
 
 namespace sim3opt_shim {
@@ -100,6 +101,26 @@ class LoopMatchBatch {
       rc = sim3opt_match_batch_set_frames(b_, n_frames(), kp_ptr_.data(), obs_ptr_.data(), kp_.empty() ? &none : kp_.data(),
                                           desc_.empty() ? &none : desc_.data(), obs_uv_.empty() ? &none : obs_uv_.data(),
                                           obs_depth_.empty() ? &none : obs_depth_.data(), f_, cx_, cy_, w_, h_);
+    return finish(rc);
+  }
+
+  // The keypoints and descriptors of a FrameStore, read where they are on the device
+  // (sim3opt_match_batch_set_frames_from); add_frame() gave every keyframe of the store, in order, its map observations
+  // (and whatever keys: they are not looked at).  Returns as solve().
+  int solve(FrameStore& store) {
+    if (!b_) return fail("solve: out of memory", SIM3OPT_ERR_ARG);
+    const float none = 0.f;
+    int rc = sim3opt_match_batch_set_options(b_, &opt_);
+    if (rc == SIM3OPT_OK)
+      rc = sim3opt_match_batch_set_frames_from(b_, store.handle(), n_frames(), obs_ptr_.data(),
+                                               obs_uv_.empty() ? &none : obs_uv_.data(),
+                                               obs_depth_.empty() ? &none : obs_depth_.data(), f_, cx_, cy_, w_, h_);
+    return finish(rc);
+  }
+
+ private:
+  // the pairs, the solve and its results, once the frames are set (rc: what setting them returned)
+  int finish(int rc) {
     if (rc == SIM3OPT_OK) rc = sim3opt_match_batch_set_pairs(b_, n_pairs(), pairs_.data());
     if (rc == SIM3OPT_OK) rc = sim3opt_match_batch_solve(b_);
     if (rc < 0) return fail(sim3opt_match_batch_last_error(b_), rc);
@@ -116,6 +137,7 @@ class LoopMatchBatch {
     return rc;
   }
 
+ public:
   // ---- results of candidate id, after solve() (before: status -1, no matches) ----
   int status(int id) const { return solved_ ? status_[id] : -1; }                         // SIM3OPT_MATCH_*
   int n_matches(int id) const { return solved_ ? ptr_[id + 1] - ptr_[id] : 0; }           // good_matches.size()

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "sim3opt.h"
+#include "sim3opt_frames.hpp"
 #include "sim3opt_match.hpp"
 
 namespace sim3opt_shim {
@@ -90,24 +91,21 @@ class LoopDetectorBatch {
     int rc = sim3opt_place_batch_set_options(b_, &opt_);
     if (rc == SIM3OPT_OK)
       rc = sim3opt_place_batch_set_frames(b_, n_frames(), kp_ptr_.data(), desc_.empty() ? &none : desc_.data());
-    if (rc == SIM3OPT_OK) rc = sim3opt_place_batch_solve(b_);
-    if (rc < 0) return fail(sim3opt_place_batch_last_error(b_), rc);
-    const std::size_t n = (std::size_t)n_frames();
-    std::vector<int32_t> status(n), match(n), consistent(n), island(2 * n);
-    std::vector<double> score(n), ns(n);
-    (void)sim3opt_place_batch_get_results(b_, status.data(), match.data(), score.data(), ns.data(), consistent.data(),
-                                          island.data());
-    results_.assign(n, DetectionResult());
-    for (std::size_t i = 0; i < n; ++i) {
-      DetectionResult& r = results_[i];
-      r.status = status[i]; r.query = (int)i; r.match = match[i]; r.score = score[i]; r.ns_factor = ns[i];
-      r.n_consistent = consistent[i]; r.island_first = island[2 * i]; r.island_last = island[2 * i + 1];
+    return finish(rc);
+  }
+
+  // The keyframes of a FrameStore, read where they are on the device (sim3opt_place_batch_set_frames_from), in place of
+  // those added with add_frame(): they are forgotten.  Returns as detect().
+  int detect(FrameStore& store) {
+    if (!b_) return fail("detect: out of memory", SIM3OPT_ERR_ARG);
+    int rc = sim3opt_place_batch_set_options(b_, &opt_);
+    if (rc == SIM3OPT_OK) rc = sim3opt_place_batch_set_frames_from(b_, store.handle());
+    if (rc == SIM3OPT_OK) {
+      kp_ptr_ = store.kp_ptr();
+      desc_.clear();
+      detected_ = false;
     }
-    int32_t np = 0;
-    pairs_.assign(2 * (std::size_t)rc, 0);
-    (void)sim3opt_place_batch_get_pairs(b_, rc, &np, pairs_.data());
-    detected_ = true;
-    return rc;
+    return finish(rc);
   }
 
   // the keyframe's result; before detect(), and for an index that is no keyframe, status -1
@@ -128,6 +126,28 @@ class LoopDetectorBatch {
 
  private:
   int fail(const std::string& why, int rc = -1) { err_ = why; return rc; }
+
+  // the solve and its results, once the frames are set (rc: what setting them returned)
+  int finish(int rc) {
+    if (rc == SIM3OPT_OK) rc = sim3opt_place_batch_solve(b_);
+    if (rc < 0) return fail(sim3opt_place_batch_last_error(b_), rc);
+    const std::size_t n = (std::size_t)n_frames();
+    std::vector<int32_t> status(n), match(n), consistent(n), island(2 * n);
+    std::vector<double> score(n), ns(n);
+    (void)sim3opt_place_batch_get_results(b_, status.data(), match.data(), score.data(), ns.data(), consistent.data(),
+                                          island.data());
+    results_.assign(n, DetectionResult());
+    for (std::size_t i = 0; i < n; ++i) {
+      DetectionResult& r = results_[i];
+      r.status = status[i]; r.query = (int)i; r.match = match[i]; r.score = score[i]; r.ns_factor = ns[i];
+      r.n_consistent = consistent[i]; r.island_first = island[2 * i]; r.island_last = island[2 * i + 1];
+    }
+    int32_t np = 0;
+    pairs_.assign(2 * (std::size_t)rc, 0);
+    (void)sim3opt_place_batch_get_pairs(b_, rc, &np, pairs_.data());
+    detected_ = true;
+    return rc;
+  }
 
   sim3opt_place_batch* b_;
   sim3opt_place_batch_options opt_;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "sim3opt.h"
+#include "sim3opt_frames.hpp"
 
 namespace sim3opt_shim {
 
@@ -86,6 +87,28 @@ class SurfExtractorBatch {
     return rc;
   }
 
+  // The batch with kp and desc left on the device in `store` (sim3opt_surf_batch_solve_into), for the stages that take a
+  // FrameStore.  Returns as extract(); keys(f), kp_ptr() and count(f) answer as after extract(), desc() is empty and
+  // descriptors(f) / frame_desc(f) have nothing to give: the descriptors are store.get()'s.
+  int extract(FrameStore& store) {
+    if (!b_) return fail("extract: out of memory", SIM3OPT_ERR_ARG);
+    if (n_ < 1) return fail("extract: no image added", SIM3OPT_ERR_STATE);
+    if (int rs = store.prepare()) return fail(store.last_error(), rs);
+    int rc = sim3opt_surf_batch_set_options(b_, &opt_);
+    if (rc == SIM3OPT_OK) rc = sim3opt_surf_batch_set_images(b_, n_, w_, h_, w_, pixels_.data());
+    if (rc == SIM3OPT_OK) rc = sim3opt_surf_batch_solve_into(b_, store.handle());
+    if (rc < 0) return fail(sim3opt_surf_batch_last_error(b_), rc);
+    std::vector<int32_t> ptr((std::size_t)n_ + 1);
+    (void)sim3opt_surf_batch_get_kp_ptr(b_, ptr.data());
+    const std::size_t n = (std::size_t)ptr.back();
+    kp_ptr_.swap(ptr);
+    kp_.assign(2 * n, 0.f); desc_.clear(); size_.assign(n, 0.f); angle_.assign(n, 0.f); response_.assign(n, 0.f);
+    octave_.assign(n, 0); laplacian_.assign(n, 0);
+    (void)sim3opt_surf_batch_get_keypoints(b_, kp_.data(), nullptr, size_.data(), angle_.data(), response_.data(),
+                                           octave_.data(), laplacian_.data());
+    return rc;
+  }
+
   // the flat arrays sim3opt_match_batch_set_frames, sim3opt_place_batch_set_frames and sim3opt_vocabulary_set_frames take
   const std::vector<int32_t>& kp_ptr() const { return kp_ptr_; }
   const std::vector<float>& kp() const { return kp_; }      // x, y per keypoint
@@ -104,7 +127,7 @@ class SurfExtractorBatch {
   }
   std::vector<std::vector<float>> descriptors(int f) const {
     std::vector<std::vector<float>> out;
-    for (int k = 0; k < count(f); ++k) {
+    for (int k = 0; k < count(f) && !desc_.empty(); ++k) {
       const float* d = desc_.data() + 64 * (std::size_t)(kp_ptr_[(std::size_t)f] + k);
       out.emplace_back(d, d + 64);
     }

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "sim3opt.h"
+#include "sim3opt_frames.hpp"
 #include "sim3opt_place.hpp"
 
 namespace sim3opt_shim {
@@ -77,6 +78,20 @@ class VocabularyTrainer {
     const float none = 0.f;  // (the C-ABI refuses a NULL array; images without descriptors still have one)
     int rc = sim3opt_vocabulary_set_options(b_, &opt_);
     if (rc == SIM3OPT_OK) rc = sim3opt_vocabulary_set_frames(b_, n_frames, kp_ptr, desc ? desc : &none);
+    if (rc == SIM3OPT_OK) rc = sim3opt_vocabulary_train(b_);
+    if (rc < 0) return fail(sim3opt_vocabulary_last_error(b_), rc);
+    const std::size_t n = (std::size_t)rc;
+    parent_.assign(n, 0); centre_.assign(64 * n, 0.f); weight_.assign(n, 0.0); word_id_.assign(n, 0);
+    (void)sim3opt_vocabulary_get_vocabulary(b_, parent_.data(), centre_.data(), weight_.data(), word_id_.data());
+    count_words();
+    return rc;
+  }
+
+  // ... and over the frames of a FrameStore, read where they are on the device (sim3opt_vocabulary_set_frames_from)
+  int create(FrameStore& store) {
+    if (!b_) return fail("create: out of memory", SIM3OPT_ERR_ARG);
+    int rc = sim3opt_vocabulary_set_options(b_, &opt_);
+    if (rc == SIM3OPT_OK) rc = sim3opt_vocabulary_set_frames_from(b_, store.handle());
     if (rc == SIM3OPT_OK) rc = sim3opt_vocabulary_train(b_);
     if (rc < 0) return fail(sim3opt_vocabulary_last_error(b_), rc);
     const std::size_t n = (std::size_t)rc;

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "frames_host.hpp"
 #include "handle_device.hpp"
 #include "match_host.hpp"
 
@@ -336,6 +337,7 @@ struct Batch : sim3opt::BatchHandle {
   std::vector<double> m_uv0, m_uv1, m_depth0, m_depth1, m_pts;
   // device
   sim3opt::DevArena frame_mem, pair_mem;  // the blocks of devf; of devp
+  sim3opt_fstore::SnapshotRef snap;       // set_frames_from: kp_ptr / kp / desc of devf are the snapshot's, not frame_mem's
   struct DevFrames {  // the frames, as set
     float *kp, *desc, *obs_uv, *obs_depth;
     int32_t *kp_ptr, *obs_ptr;
@@ -377,13 +379,20 @@ struct Batch : sim3opt::BatchHandle {
     if (n_frames() < 1) { err = std::string(who) + ": no frames set"; return SIM3OPT_ERR_STATE; }
     if (need_pairs && n_pairs() < 1) { err = std::string(who) + ": no pairs set"; return SIM3OPT_ERR_STATE; }
     if (int rc = sim3opt::select_device(opt.device, err)) return rc;
+    if (snap)
+      if (int rc = sim3opt_fstore::check_snapshot_device(*snap, who, opt.device, err)) return rc;
     if (!devf.up) {
       release();
       if (int rc = open_stream()) return rc;
-      HIPCHK(frame_mem.upload(devf.kp_ptr, kp_ptr, stream, nullptr));
-      HIPCHK(frame_mem.upload(devf.obs_ptr, obs_ptr, stream, nullptr));
-      HIPCHK(frame_mem.upload(devf.kp, kp, stream, nullptr));
-      HIPCHK(frame_mem.upload(devf.desc, desc, stream, nullptr));
+      if (snap) {  // read in place: nothing of the keypoints is uploaded
+        devf.kp_ptr = snap->d_kp_ptr; devf.kp = snap->d_kp; devf.desc = snap->d_desc;
+        HIPCHK(frame_mem.upload(devf.obs_ptr, obs_ptr, stream, nullptr));
+      } else {
+        HIPCHK(frame_mem.upload(devf.kp_ptr, kp_ptr, stream, nullptr));
+        HIPCHK(frame_mem.upload(devf.obs_ptr, obs_ptr, stream, nullptr));
+        HIPCHK(frame_mem.upload(devf.kp, kp, stream, nullptr));
+        HIPCHK(frame_mem.upload(devf.desc, desc, stream, nullptr));
+      }
       HIPCHK(frame_mem.upload(devf.obs_uv, obs_uv, stream, nullptr));
       HIPCHK(frame_mem.upload(devf.obs_depth, obs_depth, stream, nullptr));
       HIPCHK(hipStreamSynchronize(stream));
@@ -566,6 +575,10 @@ int sim3opt_match_batch_set_options(sim3opt_match_batch* b, const sim3opt_match_
   if (!b || !o) return SIM3OPT_ERR_ARG;
   const std::string e = sim3opt_match::validate_options(*o);
   if (!e.empty()) { b->err = "match_batch_set_options: " + e; return SIM3OPT_ERR_ARG; }
+  if (o->device != b->opt.device && b->snap) {
+    b->err = "match_batch_set_options: the frames are a store's snapshot on its device; options.device cannot change";
+    return SIM3OPT_ERR_ARG;
+  }
   if (o->device != b->opt.device) b->release();  // the device is chosen at the next solve
   b->opt = *o;
   return SIM3OPT_OK;
@@ -591,6 +604,36 @@ int sim3opt_match_batch_set_frames(sim3opt_match_batch* b, int32_t n_frames, con
     b->plan = sim3opt_match::Plan();
     b->have_run = false;
     b->devf.up = b->devp.up = false;
+    b->snap.reset();
+    return SIM3OPT_OK;
+  });
+}
+
+int sim3opt_match_batch_set_frames_from(sim3opt_match_batch* b, const sim3opt_frames* store, int32_t n_frames,
+                                        const int32_t* obs_ptr, const float* obs_uv, const float* obs_depth, double focal,
+                                        double cx, double cy, int32_t image_width, int32_t image_height) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  return sim3opt::guarded(b, "match_batch_set_frames_from", sim3opt::NO_MEMORY, [&]() -> int {
+    sim3opt_fstore::SnapshotRef s;
+    if (int rc = sim3opt_fstore::take_snapshot(store, "match_batch_set_frames_from", b->opt.device, s, b->err)) return rc;
+    std::string e = sim3opt_match::validate_observations(n_frames, obs_ptr, obs_uv, obs_depth, focal, cx, cy, image_width,
+                                                         image_height);
+    if (e.empty() && n_frames != s->n_frames())
+      e = "obs_ptr is of " + std::to_string(n_frames) + " frames, the store holds " + std::to_string(s->n_frames());
+    if (!e.empty()) { b->err = "match_batch_set_frames_from: " + e; return SIM3OPT_ERR_ARG; }
+    const size_t no = (size_t)obs_ptr[n_frames];
+    std::vector<int32_t> kpp(s->kp_ptr), obp(obs_ptr, obs_ptr + n_frames + 1);
+    std::vector<float> ou(obs_uv, obs_uv + 2 * no), od(obs_depth, obs_depth + no);
+    // nothing failed: the handle changes now
+    b->wait();
+    b->kp_ptr.swap(kpp); b->obs_ptr.swap(obp); b->obs_uv.swap(ou); b->obs_depth.swap(od);
+    std::vector<float>().swap(b->kp); std::vector<float>().swap(b->desc);
+    b->f = focal; b->cx = cx; b->cy = cy; b->width = image_width; b->height = image_height;
+    b->pairs.clear();
+    b->plan = sim3opt_match::Plan();
+    b->have_run = false;
+    b->devf.up = b->devp.up = false;
+    b->snap = std::move(s);
     return SIM3OPT_OK;
   });
 }

@@ -63,6 +63,23 @@ inline std::string validate_frames(int32_t n_frames, const int32_t* kp_ptr, cons
   return "";
 }
 
+// what validate_frames asks of everything but kp_ptr / kp / desc, in its words (set_frames_from: those are the store's)
+inline std::string validate_observations(int32_t n_frames, const int32_t* obs_ptr, const float* obs_uv,
+                                         const float* obs_depth, double focal, double cx, double cy, int32_t image_width,
+                                         int32_t image_height) {
+  if (n_frames < 1) return "n_frames < 1";
+  if (!obs_ptr || !obs_uv || !obs_depth) return "a NULL array";
+  if (!(focal > 0) || !std::isfinite(focal) || !std::isfinite(cx) || !std::isfinite(cy))
+    return "focal <= 0 or a non-finite intrinsic";
+  if (image_width < 1 || image_height < 1) return "a non-positive image size";
+  const std::string e = check_frame_ptr("obs_ptr", n_frames, obs_ptr);
+  if (!e.empty()) return e;
+  const size_t no = (size_t)obs_ptr[n_frames];
+  if (!all_finite(obs_uv, 2 * no)) return "a non-finite observation";
+  if (!all_finite(obs_depth, no)) return "a non-finite depth";
+  return "";
+}
+
 inline std::string validate_pairs(int32_t n_frames, int32_t n_pairs, const int32_t* pairs) {
   if (n_pairs < 1) return "n_pairs < 1";
   if (!pairs) return "a NULL array";

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "frames_host.hpp"
 #include "handle_device.hpp"
 #include "place_host.hpp"
 
@@ -419,6 +420,7 @@ struct Batch : sim3opt::BatchHandle {
   std::vector<double> score, ns, bow_val;
   // device
   sim3opt::DevArena voc_mem, frame_mem;
+  sim3opt_fstore::SnapshotRef snap;  // set_frames_from: kp_ptr / desc of devf are the snapshot's, not frame_mem's
   struct DevVoc {
     float* centre;
     int32_t *first_child, *n_child, *node_word;
@@ -455,6 +457,8 @@ struct Batch : sim3opt::BatchHandle {
     if (voc.n_nodes < 2) { err = std::string(who) + ": no vocabulary set"; return SIM3OPT_ERR_STATE; }
     if (need_frames && n_frames() < 1) { err = std::string(who) + ": no frames set"; return SIM3OPT_ERR_STATE; }
     if (int rc = sim3opt::select_device(opt.device, err)) return rc;
+    if (need_frames && snap)
+      if (int rc = sim3opt_fstore::check_snapshot_device(*snap, who, opt.device, err)) return rc;
     if (!stream) {
       release();
       if (int rc = open_stream()) return rc;
@@ -474,8 +478,12 @@ struct Batch : sim3opt::BatchHandle {
     if (need_frames && !devf.up) {
       release_frames();
       const size_t n = (size_t)n_frames(), d = D();
-      HIPCHK(frame_mem.upload(devf.kp_ptr, kp_ptr, stream, nullptr));
-      HIPCHK(frame_mem.upload(devf.desc, desc, stream, nullptr));
+      if (snap) {  // read in place: nothing of the frames is uploaded
+        devf.kp_ptr = snap->d_kp_ptr; devf.desc = snap->d_desc;
+      } else {
+        HIPCHK(frame_mem.upload(devf.kp_ptr, kp_ptr, stream, nullptr));
+        HIPCHK(frame_mem.upload(devf.desc, desc, stream, nullptr));
+      }
       HIPCHK(frame_mem.raw(devf.word, d));
       HIPCHK(frame_mem.raw(devf.sorted_word, d));
       HIPCHK(frame_mem.raw(devf.sorted_cnt, d));
@@ -689,6 +697,10 @@ int sim3opt_place_batch_set_options(sim3opt_place_batch* b, const sim3opt_place_
   if (!b || !o) return SIM3OPT_ERR_ARG;
   const std::string e = sim3opt_place::validate_options(*o);
   if (!e.empty()) { b->err = "place_batch_set_options: " + e; return SIM3OPT_ERR_ARG; }
+  if (o->device != b->opt.device && b->snap) {
+    b->err = "place_batch_set_options: the frames are a store's snapshot on its device; options.device cannot change";
+    return SIM3OPT_ERR_ARG;
+  }
   if (o->device != b->opt.device) b->release();  // the device is chosen at the next solve
   b->opt = *o;
   return SIM3OPT_OK;
@@ -720,6 +732,26 @@ int sim3opt_place_batch_set_frames(sim3opt_place_batch* b, int32_t n_frames, con
     b->kp_ptr.swap(kpp); b->desc.swap(d);
     b->have_run = false;
     b->devf.up = b->devf.solved = false;  // (the vocabulary stays where it is)
+    b->snap.reset();
+    return SIM3OPT_OK;
+  });
+}
+
+int sim3opt_place_batch_set_frames_from(sim3opt_place_batch* b, const sim3opt_frames* store) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  return sim3opt::guarded(b, "place_batch_set_frames_from", sim3opt::NO_MEMORY, [&]() -> int {
+    sim3opt_fstore::SnapshotRef s;
+    if (int rc = sim3opt_fstore::take_snapshot(store, "place_batch_set_frames_from", b->opt.device, s, b->err)) return rc;
+    if (s->n_frames() > SIM3OPT_PLACE_MAX_FRAMES) {
+      b->err = "place_batch_set_frames_from: n_frames above SIM3OPT_PLACE_MAX_FRAMES"; return SIM3OPT_ERR_ARG;
+    }
+    std::vector<int32_t> kpp(s->kp_ptr);
+    b->wait();
+    b->kp_ptr.swap(kpp);
+    std::vector<float>().swap(b->desc);
+    b->have_run = false;
+    b->devf.up = b->devf.solved = false;  // (the vocabulary stays where it is)
+    b->snap = std::move(s);
     return SIM3OPT_OK;
   });
 }

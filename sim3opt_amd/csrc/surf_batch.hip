@@ -20,7 +20,9 @@
 //                              the 441 patch cells across lanes (each lane walks its cell's window samples; the window
 //                              is never stored), the 16 sub-regions in fixed order
 // The host reads the candidate counts of the pass once (to size the candidate blocks: no capacity is guessed) and drops
-// the keypoints the orientation step refused while it copies the results out, in order.
+// the keypoints the orientation step refused while it copies the results out, in order.  solve_into leaves kp and the
+// descriptors on the device: the ordered compaction of frames.hip does that dropping for them, a chunk per pass, and the
+// chunks are joined once into the frame store's snapshot.
 // No floating-point atomic; the integer atomics count (kept, dropped) and decide no order.
 #include <hip/hip_runtime.h>
 
@@ -32,6 +34,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "frames_device.hpp"
 #include "handle_device.hpp"
 #include "surf_host.hpp"
 
@@ -358,6 +361,12 @@ struct PassOut {  // per image of a pass, appended in image order
   std::vector<float> kp, desc, size, angle, response;
 };
 
+struct Fill {  // solve_into: the compacted kp / desc of the passes so far, on the device
+  struct Chunk { float *kp, *desc; size_t rows; };
+  std::vector<Chunk> chunks;
+  size_t rows = 0;
+};
+
 struct Debug {  // what a read-out asks of a one-image pass
   std::vector<int32_t>* S = nullptr;
   int32_t resp_octave = -1, resp_layer = -1;
@@ -378,8 +387,9 @@ struct Batch : sim3opt::BatchHandle {
   // the last solve
   sim3opt_surf_batch_options run_opt;
   PassOut res;
+  bool desc_in_store = false;  // the last solve was a solve_into: res.desc is empty, the store has the descriptors
   // device
-  sim3opt::DevArena table_mem, pass_mem, cand_mem;
+  sim3opt::DevArena table_mem, pass_mem, cand_mem, chunk_mem;  // chunk_mem: a solve_into's chunks until they are joined
   struct Dev {
     Tables* tables;
     bool up;
@@ -388,7 +398,7 @@ struct Batch : sim3opt::BatchHandle {
   ~Batch() { release(); }
 
   void release() {
-    close_stream(cand_mem, pass_mem, table_mem);
+    close_stream(chunk_mem, cand_mem, pass_mem, table_mem);
     dev = Dev{};
   }
 
@@ -413,14 +423,15 @@ struct Batch : sim3opt::BatchHandle {
   }
 
   // Images [img0, img0 + n) through every stage; appended to `out`.  Every block of the pass is handed back.
-  int run_pass(const sim3opt_surf_batch_options& o, int32_t img0, int32_t n, PassOut& out, const Debug* dbg) {
-    const int rc = pass_body(o, img0, n, out, dbg);
+  int run_pass(const sim3opt_surf_batch_options& o, int32_t img0, int32_t n, PassOut& out, const Debug* dbg,
+               Fill* fill = nullptr) {
+    const int rc = pass_body(o, img0, n, out, dbg, fill);
     wait();
     cand_mem.release(); pass_mem.release();
     return rc;
   }
 
-  int pass_body(const sim3opt_surf_batch_options& o, int32_t img0, int32_t n, PassOut& out, const Debug* dbg) {
+  int pass_body(const sim3opt_surf_batch_options& o, int32_t img0, int32_t n, PassOut& out, const Debug* dbg, Fill* fill) {
     wait();
     cand_mem.release(); pass_mem.release();
     const size_t npix = (size_t)w * (size_t)h, nS = (size_t)(w + 1) * (size_t)(h + 1);
@@ -489,7 +500,7 @@ struct Batch : sim3opt::BatchHandle {
     }
     const size_t total = (size_t)cptr[(size_t)n];
     std::vector<float> s_kp, s_size, s_resp, s_angle, s_desc;
-    std::vector<int32_t> s_oct, s_lap, s_state, h_kept, h_drop;
+    std::vector<int32_t> s_oct, s_lap, s_state, h_kept, h_drop, h_cnt;
     if (total) {
       Cand* cand = nullptr;
       float *slot_kp = nullptr, *slot_size = nullptr, *slot_resp = nullptr, *slot_angle = nullptr, *slot_desc = nullptr;
@@ -541,7 +552,28 @@ struct Batch : sim3opt::BatchHandle {
       HIPCHK(sim3opt::read_back(s_size, slot_size, total, stream));
       HIPCHK(sim3opt::read_back(s_resp, slot_resp, total, stream));
       HIPCHK(sim3opt::read_back(s_angle, slot_angle, total, stream));
-      HIPCHK(sim3opt::read_back(s_desc, slot_desc, total * DESC, stream));
+      if (!fill) {
+        HIPCHK(sim3opt::read_back(s_desc, slot_desc, total * DESC, stream));
+      } else {
+        // the chunk of the pass: room for what the ranking can keep, known from the candidate counts
+        size_t bound = 0;
+        for (int32_t i = 0; i < n; ++i) {
+          const int32_t c = cptr[(size_t)i + 1] - cptr[(size_t)i];
+          bound += (size_t)(o.max_keypoints > 0 ? std::min(c, o.max_keypoints) : c);
+        }
+        Fill::Chunk ch{};
+        int32_t* out_ptr = nullptr;
+        HIPCHK(chunk_mem.raw(ch.kp, 2 * bound));
+        HIPCHK(chunk_mem.raw(ch.desc, bound * DESC));
+        HIPCHK(cand_mem.raw(out_ptr, (size_t)n + 1));
+        sim3opt_fstore::CompactArgs C{};
+        C.n_images = n; C.tiles = (max_n + sim3opt_fstore::COMPACT_TILE - 1) / sim3opt_fstore::COMPACT_TILE;
+        C.cand_ptr = cand_ptr; C.state = slot_state; C.slot_kp = slot_kp; C.slot_desc = slot_desc;
+        C.base = 0; C.kp_ptr_out = out_ptr; C.out_kp = ch.kp; C.out_desc = ch.desc;
+        if (int rc = sim3opt_fstore::compact_enqueue(C, cand_mem, stream, err)) return rc;
+        HIPCHK(sim3opt::read_back(h_cnt, out_ptr, (size_t)n + 1, stream));
+        fill->chunks.push_back(ch);
+      }
       HIPCHK(sim3opt::read_back(s_oct, slot_oct, total, stream));
       HIPCHK(sim3opt::read_back(s_lap, slot_lap, total, stream));
       HIPCHK(sim3opt::read_back(s_state, slot_state, total, stream));
@@ -559,17 +591,25 @@ struct Batch : sim3opt::BatchHandle {
         if (s_state[z] == 1) { err = "surf_batch_solve: internal error (a keypoint without a descriptor)"; return SIM3OPT_ERR_HIP; }
         if (s_state[z] != 2) continue;
         out.kp.push_back(s_kp[2 * z]); out.kp.push_back(s_kp[2 * z + 1]);
-        out.desc.insert(out.desc.end(), s_desc.begin() + (ptrdiff_t)(z * DESC), s_desc.begin() + (ptrdiff_t)((z + 1) * DESC));
+        if (!fill) out.desc.insert(out.desc.end(), s_desc.begin() + (ptrdiff_t)(z * DESC), s_desc.begin() + (ptrdiff_t)((z + 1) * DESC));
         out.size.push_back(s_size[z]); out.angle.push_back(s_angle[z]); out.response.push_back(s_resp[z]);
         out.octave.push_back(s_oct[z]); out.laplacian.push_back(s_lap[z]);
         out.rank.push_back(s - cptr[(size_t)i]);
         ++kept_here;
+      }
+      // (solve_into: the counts the compaction emitted are kp_ptr; the small fields above follow the same predicate)
+      if (fill && total && h_cnt[(size_t)i + 1] - h_cnt[(size_t)i] != kept_here) {
+        err = "surf_batch_solve_into: internal error (the compaction's counts)"; return SIM3OPT_ERR_HIP;
       }
       out.kp_ptr.push_back(out.kp_ptr.back() + kept_here);
       out.status.push_back(kept_here ? SIM3OPT_SURF_OK : SIM3OPT_SURF_NO_KEYPOINTS);
       out.n_cand.push_back(cptr[(size_t)i + 1] - cptr[(size_t)i]);
       out.n_interp.push_back(h_kept[(size_t)i]);
       out.n_dropped.push_back(h_drop[(size_t)i]);
+    }
+    if (fill && total) {
+      fill->chunks.back().rows = (size_t)h_cnt[(size_t)n];
+      fill->rows += (size_t)h_cnt[(size_t)n];
     }
     return SIM3OPT_OK;
   }
@@ -585,6 +625,55 @@ struct Batch : sim3opt::BatchHandle {
     res = std::move(out);
     run_opt = o;
     have_run = true;
+    desc_in_store = false;
+    int32_t ok = 0;
+    for (int32_t s : res.status) ok += s == SIM3OPT_SURF_OK;
+    return ok;
+  }
+
+  // solve(), with kp and desc compacted on the device into a snapshot the store adopts.  Whatever happens, the chunks
+  // and an unfinished snapshot go back once the stream has run dry.
+  int solve_into(sim3opt_frames* store) {
+    std::shared_ptr<sim3opt_fstore::Snapshot> snap;
+    const int rc = solve_into_body(store, snap);
+    wait();
+    chunk_mem.release();
+    return rc;
+  }
+
+  int solve_into_body(sim3opt_frames* store, std::shared_ptr<sim3opt_fstore::Snapshot>& snap) {
+    err.clear();
+    if (!store) { err = "surf_batch_solve_into: NULL store"; return SIM3OPT_ERR_ARG; }
+    if (n_img < 1) { err = "surf_batch_solve_into: no images set"; return SIM3OPT_ERR_STATE; }
+    int device = -1;  // (a refusal comes before anything is put on the device)
+    if (int rc = sim3opt_fstore::resolve_device(opt.device, device, err)) return rc;
+    if (int rc = sim3opt_fstore::check_fill_device(store, "surf_batch_solve_into", device, err)) return rc;
+    if (int rc = ensure_device("surf_batch_solve_into")) return rc;
+    const sim3opt_surf_batch_options o = opt;
+    PassOut out;
+    Fill fill;
+    const int32_t per = std::min(o.images_per_pass, MAX_PASS);
+    for (int32_t i0 = 0; i0 < n_img; i0 += per) {
+      if (int rc = run_pass(o, i0, std::min(per, n_img - i0), out, nullptr, &fill)) return rc;
+      const std::string e = sim3opt_fstore::check_total(fill.rows, 0);
+      if (!e.empty()) { err = "surf_batch_solve_into: " + e; return SIM3OPT_ERR_ARG; }
+    }
+    if (fill.rows != (size_t)out.kp_ptr.back()) { err = "surf_batch_solve_into: internal error (the chunks' rows)"; return SIM3OPT_ERR_HIP; }
+    // the chunks joined once: the store's arrays are contiguous
+    if (int rc = sim3opt_fstore::new_snapshot(out.kp_ptr, snap, err)) return rc;
+    size_t at = 0;
+    for (const Fill::Chunk& c : fill.chunks) {
+      if (!c.rows) continue;
+      HIPCHK(hipMemcpyAsync(snap->d_kp + 2 * at, c.kp, sizeof(float) * 2 * c.rows, hipMemcpyDeviceToDevice, stream));
+      HIPCHK(hipMemcpyAsync(snap->d_desc + DESC * at, c.desc, sizeof(float) * DESC * c.rows, hipMemcpyDeviceToDevice, stream));
+      at += c.rows;
+    }
+    if (int rc = sim3opt_fstore::seal_snapshot(*snap, stream, err)) return rc;
+    sim3opt_fstore::adopt_snapshot(store, std::move(snap));
+    res = std::move(out);
+    run_opt = o;
+    have_run = true;
+    desc_in_store = true;
     int32_t ok = 0;
     for (int32_t s : res.status) ok += s == SIM3OPT_SURF_OK;
     return ok;
@@ -668,6 +757,7 @@ int sim3opt_surf_batch_set_images(sim3opt_surf_batch* b, int32_t n_images, int32
     b->pixels.swap(p);
     b->n_img = n_images; b->w = width; b->h = height;
     b->have_run = false;
+    b->desc_in_store = false;
     b->res = sim3opt_surf::PassOut{};
     return SIM3OPT_OK;
   });
@@ -689,6 +779,11 @@ int sim3opt_surf_batch_solve(sim3opt_surf_batch* b) {
   return sim3opt::guarded(b, "surf_batch_solve", sim3opt::NO_MEMORY_OR_INTERNAL, [&] { return b->solve(); });
 }
 
+int sim3opt_surf_batch_solve_into(sim3opt_surf_batch* b, sim3opt_frames* store) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  return sim3opt::guarded(b, "surf_batch_solve_into", sim3opt::NO_MEMORY_OR_INTERNAL, [&] { return b->solve_into(store); });
+}
+
 int sim3opt_surf_batch_get_kp_ptr(const sim3opt_surf_batch* b, int32_t* kp_ptr) {
   if (!b || !kp_ptr) return SIM3OPT_ERR_ARG;
   if (!b->have_run) return SIM3OPT_ERR_STATE;
@@ -700,6 +795,11 @@ int sim3opt_surf_batch_get_keypoints(const sim3opt_surf_batch* b, float* kp, flo
                                      float* response, int32_t* octave, int32_t* laplacian) {
   if (!b) return SIM3OPT_ERR_ARG;
   if (!b->have_run) return SIM3OPT_ERR_STATE;
+  if (desc && b->desc_in_store) {  // (the handle is the caller's own: only the message changes)
+    const_cast<sim3opt_surf_batch*>(b)->err =
+        "surf_batch_get_keypoints: the descriptors of a solve_into are in the frame store; read them with sim3opt_frames_get";
+    return SIM3OPT_ERR_STATE;
+  }
   const sim3opt_surf::PassOut& r = b->res;
   const size_t n = (size_t)r.kp_ptr.back();
   if (!n) return SIM3OPT_OK;

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "frames_host.hpp"
 #include "handle_device.hpp"
 #include "ransac_sample.hpp"
 #include "vocab_host.hpp"
@@ -411,6 +412,7 @@ struct Trainer : sim3opt::BatchHandle {
   int32_t n_words = 0, depth = 0, n_unconverged = 0;
   // device
   sim3opt::DevArena frame_mem, level_mem;
+  sim3opt_fstore::SnapshotRef snap;  // set_frames_from: dev.desc is the snapshot's, not frame_mem's
   struct Dev {
     float* desc;
     int32_t *perm;  // (levels + 1) x D: the members of every level's nodes
@@ -432,6 +434,8 @@ struct Trainer : sim3opt::BatchHandle {
   int ensure_device(const char* who) {
     if (n_frames() < 1) { err = std::string(who) + ": no frames set"; return SIM3OPT_ERR_STATE; }
     if (int rc = sim3opt::select_device(opt.device, err)) return rc;
+    if (snap)
+      if (int rc = sim3opt_fstore::check_snapshot_device(*snap, who, opt.device, err)) return rc;
     if (!stream) {
       release();
       if (int rc = open_stream()) return rc;
@@ -441,7 +445,8 @@ struct Trainer : sim3opt::BatchHandle {
       level_mem.release(); frame_mem.release();
       dev = Dev{};
       const size_t d = D();
-      HIPCHK(frame_mem.upload(dev.desc, desc, stream, nullptr));
+      if (snap) dev.desc = snap->d_desc;  // read in place: nothing of the frames is uploaded
+      else HIPCHK(frame_mem.upload(dev.desc, desc, stream, nullptr));
       HIPCHK(frame_mem.raw(dev.perm, d * (size_t)(opt.levels + 1)));
       HIPCHK(frame_mem.raw(dev.cl, d));
       HIPCHK(frame_mem.raw(dev.assign, d));
@@ -755,6 +760,10 @@ int sim3opt_vocabulary_set_options(sim3opt_vocabulary* b, const sim3opt_vocabula
   if (!b || !o) return SIM3OPT_ERR_ARG;
   const std::string e = sim3opt_vocab::validate_options(*o);
   if (!e.empty()) { b->err = "vocabulary_set_options: " + e; return SIM3OPT_ERR_ARG; }
+  if (o->device != b->opt.device && b->snap) {
+    b->err = "vocabulary_set_options: the frames are a store's snapshot on its device; options.device cannot change";
+    return SIM3OPT_ERR_ARG;
+  }
   if (o->device != b->opt.device) b->release();  // the device is chosen at the next training
   b->opt = *o;
   return SIM3OPT_OK;
@@ -770,6 +779,27 @@ int sim3opt_vocabulary_set_frames(sim3opt_vocabulary* b, int32_t n_frames, const
     b->kp_ptr.swap(kpp); b->desc.swap(d);
     b->have_run = false;
     b->dev.up = b->dev.trained = false;
+    b->snap.reset();
+    return SIM3OPT_OK;
+  });
+}
+
+int sim3opt_vocabulary_set_frames_from(sim3opt_vocabulary* b, const sim3opt_frames* store) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  return sim3opt::guarded(b, "vocabulary_set_frames_from", sim3opt::NO_MEMORY, [&]() -> int {
+    sim3opt_fstore::SnapshotRef s;
+    if (int rc = sim3opt_fstore::take_snapshot(store, "vocabulary_set_frames_from", b->opt.device, s, b->err)) return rc;
+    std::string e;
+    if (s->n_frames() > SIM3OPT_PLACE_MAX_FRAMES) e = "n_frames above SIM3OPT_PLACE_MAX_FRAMES";
+    else if (!s->distinct) e = sim3opt_vocab::MSG_DISTINCT;  // (the fill looked on the device)
+    if (!e.empty()) { b->err = "vocabulary_set_frames_from: " + e; return SIM3OPT_ERR_ARG; }
+    std::vector<int32_t> kpp(s->kp_ptr);
+    b->wait();
+    b->kp_ptr.swap(kpp);
+    std::vector<float>().swap(b->desc);
+    b->have_run = false;
+    b->dev.up = b->dev.trained = false;
+    b->snap = std::move(s);
     return SIM3OPT_OK;
   });
 }

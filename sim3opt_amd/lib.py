@@ -252,6 +252,13 @@ class SurfBatchOptions(C.Structure):
     ]
 
 
+class FrameStoreOptions(C.Structure):
+    """sim3opt_frames_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -557,6 +564,20 @@ SYMBOLS = {
     "sim3opt_surf_batch_debug_candidates": (C.c_int, [_vp, C.c_int32, _ip, _ip, _fp, _fp, _up, _fp]),
     "sim3opt_surf_batch_debug_orientation": (C.c_int, [_vp, C.c_int32, _ip, _fp, _fp, _fp, _fp]),
     "sim3opt_surf_batch_debug_patch": (C.c_int, [_vp, C.c_int32, _fp]),
+    "sim3opt_frames_options_default": (None, [C.POINTER(FrameStoreOptions)]),
+    "sim3opt_frames_create": (_vp, []),
+    "sim3opt_frames_destroy": (None, [_vp]),
+    "sim3opt_frames_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_frames_set_options": (C.c_int, [_vp, C.POINTER(FrameStoreOptions)]),
+    "sim3opt_frames_set": (C.c_int, [_vp, C.c_int32, _ip, _fp, _fp]),
+    "sim3opt_frames_get_dims": (C.c_int, [_vp, _ip, _ip, _ip, C.POINTER(C.c_int64), _ip]),
+    "sim3opt_frames_get": (C.c_int, [_vp, _ip, _fp, _fp]),
+    "sim3opt_frames_debug_compact": (C.c_int, [_vp, C.c_int32, _ip, _ip, _fp, _fp]),
+    "sim3opt_surf_batch_solve_into": (C.c_int, [_vp, _vp]),
+    "sim3opt_vocabulary_set_frames_from": (C.c_int, [_vp, _vp]),
+    "sim3opt_place_batch_set_frames_from": (C.c_int, [_vp, _vp]),
+    "sim3opt_match_batch_set_frames_from": (C.c_int, [_vp, _vp, C.c_int32, _ip, _fp, _fp, C.c_double, C.c_double,
+                                                      C.c_double, C.c_int32, C.c_int32]),
     "sim3opt_surf_reference_image": (C.c_int, [C.POINTER(SurfBatchOptions), C.c_int32, C.c_int32, C.c_int32, _up, C.c_int32,
                                                _fp, _fp, _fp, _fp, _fp, _ip, _ip, _ip, _ip, C.c_int32, C.c_int32, _fp, _fp,
                                                C.c_int32, _ip, _fp, _fp, _up, _fp]),
@@ -1587,7 +1608,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch, VocabularyTrainer and SurfBatch share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch, VocabularyTrainer, SurfBatch and FrameStore share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -2215,6 +2236,66 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _store_handle(store):
+    """The C handle of a FrameStore (None passes through: the library refuses a NULL store)."""
+    return None if store is None else store._b
+
+
+class FrameStore(_Handle):
+    """sim3opt_frames*: kp_ptr / kp / desc of a sequence on one device, held once.  SurfBatch.solve_into fills it on the
+    device (set() does from host arrays); VocabularyTrainer, PlaceBatch and MatchBatch read it in place through their
+    set_frames_from.  What it holds is an immutable snapshot: a consumer that took it keeps it through a refill or
+    the store's close()."""
+    _prefix, _Options = "frames", FrameStoreOptions
+    TILES = ("compact_tile", "row_lanes")
+
+    def set(self, kp_ptr, kp, desc):
+        kpp, k, d = _i32(kp_ptr).reshape(-1), _f32(kp).reshape(-1, 2), _f32(desc).reshape(-1, 64)
+        n = kpp.shape[0] - 1
+        if n >= 1 and not (k.shape[0] == d.shape[0] and k.shape[0] >= kpp.max()):
+            raise ValueError("keypoint arrays shorter than kp_ptr says")
+        if d.shape[0] == 0:  # (the C-ABI refuses a NULL array; nothing of them is read)
+            k, d = np.zeros((1, 2), dtype=np.float32), np.zeros((1, 64), dtype=np.float32)
+        self._chk(self._L.sim3opt_frames_set(self._b, n, _p(kpp, _ip), _p(k, _fp), _p(d, _fp)), "frames_set")
+
+    def dims(self):
+        """dict: n_frames, total_keypoints, device (-1 before a fill), desc_bytes and the compaction's tile sizes
+        (TILES)"""
+        v = [C.c_int32() for _ in range(3)]
+        nb, t = C.c_int64(), (C.c_int32 * 2)()
+        self._chk(self._L.sim3opt_frames_get_dims(self._b, *(C.byref(x) for x in v), C.byref(nb), t), "frames_get_dims")
+        out = dict(zip(("n_frames", "total_keypoints", "device"), (x.value for x in v)), desc_bytes=nb.value)
+        out.update(zip(self.TILES, t))
+        return out
+
+    def kp_ptr(self):
+        """The host mirror of kp_ptr (nothing is read from the device)"""
+        p = np.empty(self.dims()["n_frames"] + 1, dtype=np.int32)
+        self._chk(self._L.sim3opt_frames_get(self._b, _p(p, _ip), None, None), "frames_get")
+        return p
+
+    def get(self):
+        """(kp_ptr (n_frames + 1,), kp (N, 2), desc (N, 64)) read back from the device"""
+        d = self.dims()
+        p = np.empty(d["n_frames"] + 1, dtype=np.int32)
+        k, e = np.empty((d["total_keypoints"], 2), dtype=np.float32), np.empty((d["total_keypoints"], 64), dtype=np.float32)
+        self._chk(self._L.sim3opt_frames_get(self._b, _p(p, _ip), _p(k, _fp), _p(e, _fp)), "frames_get")
+        return p, k, e
+
+    def debug_compact(self, cand_ptr, state, slot_kp, slot_desc):
+        """The ordered compaction on caller-supplied slot arrays: the store is filled with the slots of state 2."""
+        cp, st = _i32(cand_ptr).reshape(-1), _i32(state).reshape(-1)
+        k, d = _f32(slot_kp).reshape(-1, 2), _f32(slot_desc).reshape(-1, 64)
+        n = cp.shape[0] - 1
+        if n >= 1 and not (st.shape[0] == k.shape[0] == d.shape[0] and st.shape[0] >= cp.max()):
+            raise ValueError("slot arrays shorter than cand_ptr says")
+        if st.shape[0] == 0:
+            st = np.zeros(1, dtype=np.int32)
+            k, d = np.zeros((1, 2), dtype=np.float32), np.zeros((1, 64), dtype=np.float32)
+        self._chk(self._L.sim3opt_frames_debug_compact(self._b, n, _p(cp, _ip), _p(st, _ip), _p(k, _fp), _p(d, _fp)),
+                  "frames_debug_compact")
+
+
 class MatchBatch(_Handle):
     """sim3opt_match_batch*: descriptor matching with the reference's filters (kittiDetector.h:1085-1160) and the
     map-depth lookup (:1229-1279) of a whole batch of loop candidates.  Frames are handed over once, pairs name them;
@@ -2238,6 +2319,20 @@ class MatchBatch(_Handle):
                                                          _p(ou, _fp), _p(od, _fp), focal, cx, cy, int(image_width),
                                                          int(image_height)), "match_batch_set_frames")
         self._n_kp, self._pairs = np.diff(kpp), None  # (what debug_nn sizes its arrays by; the pairs went with the frames)
+
+    def set_frames_from(self, store, obs_ptr, obs_uv, obs_depth, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY,
+                        image_width=KITTI_WIDTH, image_height=KITTI_HEIGHT):
+        """set_frames with kp_ptr / kp / desc read in place from a FrameStore's current snapshot"""
+        obp = _i32(obs_ptr).reshape(-1)
+        ou, od = _f32(obs_uv).reshape(-1, 2), _f32(obs_depth).reshape(-1)
+        if obp.shape[0] >= 2 and not (ou.shape[0] == od.shape[0] and ou.shape[0] >= obp.max()):
+            raise ValueError("observation arrays shorter than obs_ptr says")
+        if ou.shape[0] == 0:  # (the C-ABI refuses a NULL array; nothing of them is read)
+            ou, od = np.zeros((1, 2), dtype=np.float32), np.zeros(1, dtype=np.float32)
+        self._chk(self._L.sim3opt_match_batch_set_frames_from(
+            self._b, _store_handle(store), obp.shape[0] - 1, _p(obp, _ip), _p(ou, _fp), _p(od, _fp), focal, cx, cy,
+            int(image_width), int(image_height)), "match_batch_set_frames_from")
+        self._n_kp, self._pairs = np.diff(store.kp_ptr()), None
 
     def set_pairs(self, pairs):
         p = _i32(pairs).reshape(-1, 2)
@@ -2330,6 +2425,10 @@ class PlaceBatch(_Handle):
             d = np.zeros((1, 64), dtype=np.float32)  # (the C-ABI refuses a NULL array; nothing of it is read)
         self._chk(self._L.sim3opt_place_batch_set_frames(self._b, n, _p(kpp, _ip), _p(d, _fp)), "place_batch_set_frames")
 
+    def set_frames_from(self, store):
+        """set_frames with kp_ptr / desc read in place from a FrameStore's current snapshot"""
+        self._chk(self._L.sim3opt_place_batch_set_frames_from(self._b, _store_handle(store)), "place_batch_set_frames_from")
+
     def dims(self):
         """dict: n_nodes, n_words, depth, n_frames, total_descriptors and the kernels' tile sizes (TILES)"""
         v = [C.c_int32() for _ in range(5)]
@@ -2414,6 +2513,10 @@ class VocabularyTrainer(_Handle):
         if d.shape[0] == 0:
             d = np.zeros((1, 64), dtype=np.float32)  # (the C-ABI refuses a NULL array; nothing of it is read)
         self._chk(self._L.sim3opt_vocabulary_set_frames(self._b, n, _p(kpp, _ip), _p(d, _fp)), "vocabulary_set_frames")
+
+    def set_frames_from(self, store):
+        """set_frames with kp_ptr / desc read in place from a FrameStore's current snapshot"""
+        self._chk(self._L.sim3opt_vocabulary_set_frames_from(self._b, _store_handle(store)), "vocabulary_set_frames_from")
 
     def train(self):
         """The number of nodes; raises when the library reports an error."""
@@ -2507,6 +2610,11 @@ class SurfBatch(_Handle):
         """The number of images with keypoints; raises when the library reports an error."""
         return self._count(self._L.sim3opt_surf_batch_solve(self._b), "surf_batch_solve")
 
+    def solve_into(self, store):
+        """solve(), with kp and desc left on the device in `store` (a FrameStore): keypoints() then gives the small
+        fields only (desc=False) and the descriptors are store.get()'s."""
+        return self._count(self._L.sim3opt_surf_batch_solve_into(self._b, _store_handle(store)), "surf_batch_solve_into")
+
     def kp_ptr(self):
         p = np.empty(self.dims()["n_images"] + 1, dtype=np.int32)
         self._chk(self._L.sim3opt_surf_batch_get_kp_ptr(self._b, _p(p, _ip)), "surf_batch_get_kp_ptr")
@@ -2519,12 +2627,15 @@ class SurfBatch(_Handle):
                     response=np.empty(n, dtype=np.float32), octave=np.empty(n, dtype=np.int32),
                     laplacian=np.empty(n, dtype=np.int32))
 
-    def keypoints(self):
-        """dict of FIELDS over all keypoints; image f owns [kp_ptr()[f], kp_ptr()[f + 1])"""
+    def keypoints(self, desc=True):
+        """dict of FIELDS over all keypoints; image f owns [kp_ptr()[f], kp_ptr()[f + 1]).  desc=False: without the
+        descriptors (after solve_into they are the store's, and asking for them here is refused)."""
         o = self._arrays(self.dims()["total_keypoints"])
+        if not desc:
+            del o["desc"]
         self._chk(self._L.sim3opt_surf_batch_get_keypoints(
-            self._b, *(_p(o[f], _fp) for f in self.FIELDS[:5]), _p(o["octave"], _ip), _p(o["laplacian"], _ip)),
-            "surf_batch_get_keypoints")
+            self._b, *(_p(o[f], _fp) if f in o else None for f in self.FIELDS[:5]), _p(o["octave"], _ip),
+            _p(o["laplacian"], _ip)), "surf_batch_get_keypoints")
         return o
 
     def summary(self):
