@@ -12,7 +12,8 @@
 #                           tests/cxx/place_conformance (the place-recognition helper that names the candidates),
 #                           tests/cxx/vocabulary_conformance (the trainer of the tree that helper descends),
 #                           tests/cxx/surf_conformance (the extractor of the keypoints and descriptors all of them take),
-#                           tests/cxx/frames_conformance (the frame store those stages share on the device)
+#                           tests/cxx/frames_conformance (the frame store those stages share on the device),
+#                           tests/cxx/tracks_conformance (the loop tracks that carry the matches into the bundle adjustment)
 #   make LIB=/some/where/libsim3opt.so   builds the library elsewhere (used by the tests)
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC  := sim3opt_amd/csrc
@@ -44,7 +45,8 @@ conformance: $(LIB) tests/cxx/shim_conformance.cpp tests/cxx/ba_shim_conformance
              tests/cxx/place_conformance.cpp include/sim3opt_place.hpp \
              tests/cxx/vocabulary_conformance.cpp include/sim3opt_vocabulary.hpp \
              tests/cxx/surf_conformance.cpp include/sim3opt_surf.hpp \
-             tests/cxx/frames_conformance.cpp include/sim3opt_frames.hpp
+             tests/cxx/frames_conformance.cpp include/sim3opt_frames.hpp \
+             tests/cxx/tracks_conformance.cpp include/sim3opt_tracks.hpp
 	g++ -std=c++17 -Wall -DSIM3OPT_G2O_NAMES -Iinclude $(EIGEN_INC) tests/cxx/shim_conformance.cpp \
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/shim_conformance
 	g++ -std=c++17 -Wall -DSIM3OPT_G2O_BA_NAMES -Iinclude $(EIGEN_INC) tests/cxx/ba_shim_conformance.cpp \
@@ -69,12 +71,14 @@ conformance: $(LIB) tests/cxx/shim_conformance.cpp tests/cxx/ba_shim_conformance
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/surf_conformance
 	g++ -std=c++17 -Wall -Iinclude tests/cxx/frames_conformance.cpp \
 	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/frames_conformance
+	g++ -std=c++17 -Wall -Iinclude tests/cxx/tracks_conformance.cpp \
+	    -L$(LIBDIR) -lsim3opt -Wl,-rpath,$(LIBDIR) -o tests/cxx/tracks_conformance
 
 clean:
 	rm -f sim3opt_amd/libsim3opt.so oracle/liboracle_sim3.so examples/direct_pgo tests/cxx/shim_conformance \
 	    tests/cxx/ba_shim_conformance tests/cxx/two_view_conformance tests/cxx/pnp_conformance tests/cxx/match_conformance \
 	    tests/cxx/essential_conformance tests/cxx/homography_conformance tests/cxx/sim3_batch_conformance \
 	    tests/cxx/place_conformance tests/cxx/vocabulary_conformance tests/cxx/surf_conformance \
-	    tests/cxx/frames_conformance
+	    tests/cxx/frames_conformance tests/cxx/tracks_conformance
 
 .PHONY: all example conformance clean

@@ -1981,6 +1981,122 @@ int sim3opt_match_batch_set_frames_from(sim3opt_match_batch* b, const sim3opt_fr
                                         const int32_t* obs_ptr, const float* obs_uv, const float* obs_depth, double focal,
                                         double cx, double cy, int32_t image_width, int32_t image_height);
 
+/* ---- batched loop tracks (sim3opt_amd/csrc/track_batch.hip, track_host.hpp, track_math.hpp) ----
+ * The stage between the loop matches and the bundle adjustment: the kept matches of all loop pairs -> multi-view
+ * tracks -> one 3-D point per track in the corrected world -> obs_cam / obs_point / obs_uv rows that
+ * sim3opt_ba_set_problem takes once they are concatenated behind the map's.  computeConstraints records every kept match
+ * as a two-observation track (kittiDetector.h:1493-1501, loopTracks.txt) and SaveAsSfMInit connects those
+ * (kitti_surf.cpp:349-391, "there may be some points observed in several images, connect them").
+ * PARITY: pinned on the reference's loopTracks.txt for the connection; the point, the gates and the BA rows unpinned --
+ * the reference has no such step.
+ *   Inputs.  Frames: kp_ptr (int32, n_frames + 1) and kp (float, 2 N), as every stage takes them; a frame may own
+ * nothing.  Matches: pairs (int32, n_pairs x 2: frame0, frame1), match_ptr (n_pairs + 1), query_idx (a keypoint of
+ * frame0) and train_idx (of frame1) per match and the optional depth0 / depth1 (double per match) exactly as
+ * sim3opt_match_batch_get_match_ptr / _get_matches return them; mask: the uint8 inlier mask a RANSAC stage returns for
+ * the same matches, or NULL.  A pair may have no match.  A depth that is not finite or not > 0 is absent, not an error.
+ * Cameras: n_frames x 8 [qx qy qz qw tx ty tz s], S_iw as sim3opt_get_vertices returns it (q a unit quaternion, R its
+ * rotation matrix: a world point X is seen at s R X + t), and the intrinsics.
+ *   Tracks.  An observation is (frame, keypoint); its global index is g = kp_ptr[frame] + keypoint.  Kept matches are
+ * those whose mask is absent or non-zero.  A track is a connected component of the graph whose vertices are the
+ * observations on a side of a kept match and whose edges are the kept matches.  Tracks are numbered by ascending
+ * smallest kept match index of the component (the key order of the reference's _TrackMap); the observations of a track
+ * are listed by ascending g.
+ *   Status per track, the first that applies in this order: */
+enum {
+  SIM3OPT_TRACK_OK = 0,
+  SIM3OPT_TRACK_CONFLICT = 1,     /* two of the track's observations are in one frame (the reference assert(0)s,
+                                     kitti_surf.cpp:393-407) */
+  SIM3OPT_TRACK_NO_DEPTH = 2,     /* no observation of the track has a depth */
+  SIM3OPT_TRACK_BEHIND = 3,       /* the point has z <= 0 in one of the track's cameras */
+  SIM3OPT_TRACK_REPROJECTION = 4  /* the pixel gate below */
+};
+/*   Point of a track.  The depth of an observation is that of the lowest-indexed kept match having it on a side with a
+ * depth present (side 0 before side 1 where one match has it on both).  For every observation with a depth d:
+ * X_c = d ((u - cx) / f, (v - cy) / f, 1) and X_w = R^T (X_c - t) / s with its frame's state -- sim3opt_reanchor_points'
+ * formula on a back-projected keypoint.  The point is the arithmetic mean of those X_w, summed in double in ascending g
+ * and divided once; n_depths counts them; without any the point is 0.  No fused multiply-add takes part.
+ *   Gate.  With options.max_reproj_px > 0 a track is REPROJECTION when the squared distance of any of its
+ * observations, with or without a depth, from the point's projection (f x / z + cx, f y / z + cy) of s R X + t exceeds
+ * max_reproj_px squared.  With 0 (the default: nothing in the reference fixes a threshold for mean-of-neighbours depths)
+ * only z > 0 is required.
+ *   DEVIATIONS from SaveAsSfMInit: a match between two observations that already sit in different tracks joins the
+ * tracks (the reference prints a warning and drops the match); the order inside a track is by g, not by insertion; a
+ * conflicting track is reported with a status instead of aborting; the point and the gates have no counterpart -- the
+ * reference writes index lists only.
+ *   Kernels (track_batch.hip says which): components by min-label hooking with 32-bit integer atomicMin and pointer
+ * jumping, relaunched until a round hooks nothing -- the host reads one integer a round, and the fixed point (every
+ * observation labelled with its component's smallest g) is unique, so nothing depends on arrival order; numbering and
+ * layout by ordered scans in tiles with a carry; every segment ordered by rank; a lane per track for the point.  Integer
+ * atomics only.  The launches depend on the rounds, never on the number of pairs or tracks.
+ * No CPU fallback: SIM3OPT_ERR_NO_DEVICE without a GPU. */
+typedef struct sim3opt_track_batch sim3opt_track_batch;
+
+typedef struct sim3opt_track_batch_options {
+  double max_reproj_px; /* the pixel gate; 0: none                                              [0]  */
+  int32_t max_rounds;   /* hook-and-jump rounds a solve may take, the one that hooks nothing included [64] */
+  int32_t device;       /* -1: the calling thread's current device                              [-1] */
+} sim3opt_track_batch_options;
+
+void sim3opt_track_batch_options_default(sim3opt_track_batch_options* o);
+sim3opt_track_batch* sim3opt_track_batch_create(void);
+void sim3opt_track_batch_destroy(sim3opt_track_batch* b);
+const char* sim3opt_track_batch_last_error(const sim3opt_track_batch* b);
+/* SIM3OPT_ERR_ARG, nothing changed: max_reproj_px negative or not finite, max_rounds < 1, a device below -1, another
+ * device while a store's snapshot is held. */
+int sim3opt_track_batch_set_options(sim3opt_track_batch* b, const sim3opt_track_batch_options* o);
+/* The setters check on the host and keep a copy; the device is touched by solve.  A refusal changes nothing.  set_frames
+ * (either form) drops the matches and the cameras; set_matches and set_cameras keep what else is set.
+ * SIM3OPT_ERR_ARG: n_frames < 1, a NULL array, a kp_ptr that does not start at 0 or decreases, a non-finite pixel. */
+int sim3opt_track_batch_set_frames(sim3opt_track_batch* b, int32_t n_frames, const int32_t* kp_ptr, const float* kp);
+/* kp_ptr / kp of the store's current snapshot read in place: the snapshot is held the way the other consumers hold it,
+ * and the handle allocates only its own work blocks.  Refusals as sim3opt_*_set_frames_from. */
+int sim3opt_track_batch_set_frames_from(sim3opt_track_batch* b, const sim3opt_frames* store);
+/* mask, depth0, depth1 may be NULL.  SIM3OPT_ERR_STATE before the frames; SIM3OPT_ERR_ARG: n_pairs < 1, a NULL array, a
+ * match_ptr that does not start at 0 or decreases, a pair naming no frame, an index outside its frame, 2^30 matches or
+ * more. */
+int sim3opt_track_batch_set_matches(sim3opt_track_batch* b, int32_t n_pairs, const int32_t* pairs, const int32_t* match_ptr,
+                                    const int32_t* query_idx, const int32_t* train_idx, const uint8_t* mask,
+                                    const double* depth0, const double* depth1);
+/* SIM3OPT_ERR_STATE before the frames; SIM3OPT_ERR_ARG: a NULL array, another frame count than the frames', a
+ * non-finite state or intrinsic, s <= 0, focal <= 0. */
+int sim3opt_track_batch_set_cameras(sim3opt_track_batch* b, int32_t n_frames, const double* states, double focal, double cx,
+                                    double cy);
+/* The number of status-0 tracks (0 with every match masked: no error), or a negative code: SIM3OPT_ERR_STATE before
+ * frames, matches and cameras are set; SIM3OPT_ERR_ARG with "the components did not settle in max_rounds = ..." when
+ * the rounds run out (never an endless loop; the handle solves again with a larger max_rounds). */
+int sim3opt_track_batch_solve(sim3opt_track_batch* b);
+/* Each may be NULL; zeros for what is not there yet.  rounds: the hook-and-jump rounds of the last solve, the one that
+ * hooked nothing included.  tiles: {workgroup size, scan tile, the longest segment a lane orders, the longest a
+ * wavefront orders (longer ones: a workgroup)}. */
+int sim3opt_track_batch_dims(const sim3opt_track_batch* b, int32_t* n_frames, int32_t* n_pairs, int32_t* total_matches,
+                             int32_t* n_tracks, int32_t* n_observations, int32_t* n_kept_tracks,
+                             int32_t* n_kept_observations, int32_t* rounds, int32_t tiles[4]);
+/* The getters: SIM3OPT_ERR_STATE before the first solve; any pointer may be NULL.
+ * Every track: track_ptr (n_tracks + 1), obs_frame / obs_keypoint (n_observations), status and first_match, the
+ * smallest kept match of the track (n_tracks). */
+int sim3opt_track_batch_get_tracks(sim3opt_track_batch* b, int32_t* track_ptr, int32_t* obs_frame, int32_t* obs_keypoint,
+                                   int32_t* status, int32_t* first_match);
+/* the track of every match (total_matches), -1 where masked */
+int sim3opt_track_batch_get_match_track(sim3opt_track_batch* b, int32_t* match_track);
+/* points: n_tracks x 3; n_depths: n_tracks */
+int sim3opt_track_batch_get_points(sim3opt_track_batch* b, double* points, int32_t* n_depths);
+/* The status-0 tracks only, in order: points (n_kept_tracks x 3), and per observation of theirs obs_cam = the frame,
+ * obs_point = point_base + the track's rank among the kept, obs_uv = the keypoint's pixels (double, 2 each): the rows
+ * sim3opt_ba_set_problem takes behind a map of point_base points.  SIM3OPT_ERR_ARG: point_base < 0 or beyond int32. */
+int sim3opt_track_batch_get_ba(sim3opt_track_batch* b, int32_t point_base, double* points, int32_t* obs_cam,
+                               int32_t* obs_point, double* obs_uv);
+/* A test aid: the serial restatement of the definition above (track_host.hpp: union-find, then the arithmetic the
+ * kernels share) on the host, with no handle and no device.  Outputs may be NULL; the caller sizes track_ptr for
+ * total_matches + 1, the per-track arrays for total_matches and the per-observation arrays for 2 total_matches entries.
+ * SIM3OPT_ERR_ARG for what the setters refuse. */
+int sim3opt_track_reference(int32_t n_frames, const int32_t* kp_ptr, const float* kp, int32_t n_pairs, const int32_t* pairs,
+                            const int32_t* match_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                            const uint8_t* mask, const double* depth0, const double* depth1, const double* states,
+                            double focal, double cx, double cy, double max_reproj_px, int32_t* n_tracks,
+                            int32_t* n_observations, int32_t* track_ptr, int32_t* obs_frame, int32_t* obs_keypoint,
+                            int32_t* status, int32_t* first_match, int32_t* match_track, double* points,
+                            int32_t* n_depths);
+
 /* ---- stepwise optimisation, stage 1 (host C++) ----
  * "scale_dlt" of testStepwiseSim3Optimization                        kitti_surf.cpp:887-933
  * Null vector of the edge equations s_C x[v0] - x[v1] = 0 (the reference: last column of V of

@@ -259,6 +259,15 @@ class FrameStoreOptions(C.Structure):
     ]
 
 
+class TrackBatchOptions(C.Structure):
+    """sim3opt_track_batch_options (include/sim3opt.h), field for field."""
+    _fields_ = [
+        ("max_reproj_px", C.c_double),
+        ("max_rounds", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [
         ("ms_spmv", C.c_double), ("n_spmv", C.c_int64),
@@ -581,6 +590,23 @@ SYMBOLS = {
     "sim3opt_surf_reference_image": (C.c_int, [C.POINTER(SurfBatchOptions), C.c_int32, C.c_int32, C.c_int32, _up, C.c_int32,
                                                _fp, _fp, _fp, _fp, _fp, _ip, _ip, _ip, _ip, C.c_int32, C.c_int32, _fp, _fp,
                                                C.c_int32, _ip, _fp, _fp, _up, _fp]),
+    "sim3opt_track_batch_options_default": (None, [C.POINTER(TrackBatchOptions)]),
+    "sim3opt_track_batch_create": (_vp, []),
+    "sim3opt_track_batch_destroy": (None, [_vp]),
+    "sim3opt_track_batch_last_error": (C.c_char_p, [_vp]),
+    "sim3opt_track_batch_set_options": (C.c_int, [_vp, C.POINTER(TrackBatchOptions)]),
+    "sim3opt_track_batch_set_frames": (C.c_int, [_vp, C.c_int32, _ip, _fp]),
+    "sim3opt_track_batch_set_frames_from": (C.c_int, [_vp, _vp]),
+    "sim3opt_track_batch_set_matches": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _ip, _up, _dp, _dp]),
+    "sim3opt_track_batch_set_cameras": (C.c_int, [_vp, C.c_int32, _dp, C.c_double, C.c_double, C.c_double]),
+    "sim3opt_track_batch_solve": (C.c_int, [_vp]),
+    "sim3opt_track_batch_dims": (C.c_int, [_vp] + [_ip] * 9),
+    "sim3opt_track_batch_get_tracks": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "sim3opt_track_batch_get_match_track": (C.c_int, [_vp, _ip]),
+    "sim3opt_track_batch_get_points": (C.c_int, [_vp, _dp, _ip]),
+    "sim3opt_track_batch_get_ba": (C.c_int, [_vp, C.c_int32, _dp, _ip, _ip, _dp]),
+    "sim3opt_track_reference": (C.c_int, [C.c_int32, _ip, _fp, C.c_int32, _ip, _ip, _ip, _ip, _up, _dp, _dp, _dp,
+                                          C.c_double, C.c_double, C.c_double, C.c_double] + [_ip] * 8 + [_dp, _ip]),
 }
 
 _lib = None
@@ -1608,7 +1634,7 @@ KITTI_FOCAL, KITTI_CX, KITTI_CY = 718.856, 607.1928, 185.2157
 
 
 class _Handle:
-    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch, VocabularyTrainer, SurfBatch and FrameStore share: the C handle sim3opt_<_prefix>_* in self._b with
+    """What BundleAdjuster, TwoViewBatch, PnpBatch, EssentialBatch, HomographyBatch, Sim3Batch, MatchBatch, PlaceBatch, VocabularyTrainer, SurfBatch, FrameStore and TrackBatch share: the C handle sim3opt_<_prefix>_* in self._b with
     its creation and destruction, the options (a ctypes Structure, _Options) and the checks of return codes."""
     _prefix = _Options = None
 
@@ -2294,6 +2320,144 @@ class FrameStore(_Handle):
             k, d = np.zeros((1, 2), dtype=np.float32), np.zeros((1, 64), dtype=np.float32)
         self._chk(self._L.sim3opt_frames_debug_compact(self._b, n, _p(cp, _ip), _p(st, _ip), _p(k, _fp), _p(d, _fp)),
                   "frames_debug_compact")
+
+
+def _opt_array(a, conv, n, what):
+    """None, or `a` as a contiguous array of n entries"""
+    if a is None:
+        return None
+    a = conv(a).reshape(-1)
+    if a.shape[0] != n:
+        raise ValueError(f"{what} holds one entry per match")
+    return a
+
+
+def _match_arrays(pairs, match_ptr, query_idx, train_idx, mask, depth0, depth1):
+    """The arrays sim3opt_track_batch_set_matches and sim3opt_track_reference take, checked for their lengths."""
+    pr, mp = _i32(pairs).reshape(-1, 2), _i32(match_ptr).reshape(-1)
+    q, t = _i32(query_idx).reshape(-1), _i32(train_idx).reshape(-1)
+    if mp.shape[0] != pr.shape[0] + 1:
+        raise ValueError("match_ptr holds one entry per pair and one more")
+    M = q.shape[0]
+    if t.shape[0] != M or (mp.shape[0] >= 2 and M < mp.max()):
+        raise ValueError("match arrays shorter than match_ptr says")
+    mk = _opt_array(mask, lambda a: np.ascontiguousarray(a, dtype=np.uint8), M, "mask")
+    d0, d1 = _opt_array(depth0, _f64, M, "depth0"), _opt_array(depth1, _f64, M, "depth1")
+    if M == 0:  # (the C-ABI refuses a NULL array; nothing of them is read)
+        q = t = np.zeros(1, dtype=np.int32)
+    return pr, mp, q, t, mk, d0, d1
+
+
+def _po(a, ptr_type):
+    return None if a is None else _p(a, ptr_type)
+
+
+class TrackBatch(_Handle):
+    """sim3opt_track_batch*: the kept matches of all loop pairs fused into multi-view tracks, one 3-D point per track in
+    the corrected world and the rows BundleAdjuster.set_problem takes behind the map's (SaveAsSfMInit's connection loop,
+    kitti_surf.cpp:349-391, as connected components).  set_matches takes what MatchBatch.match_ptr() / matches() return
+    and a RANSAC stage's inlier mask; set_cameras what Graph.get_vertices() returns.  include/sim3opt.h says what is
+    pinned on the reference's loopTracks.txt (the connection) and what has no counterpart there (the point, the gates,
+    the rows)."""
+    _prefix, _Options = "track_batch", TrackBatchOptions
+    TILES = ("workgroup", "scan_tile", "lane_max", "wave_max")
+    DIMS = ("n_frames", "n_pairs", "total_matches", "n_tracks", "n_observations", "n_kept_tracks", "n_kept_observations",
+            "rounds")
+
+    def set_frames(self, kp_ptr, kp):
+        kpp, k = _i32(kp_ptr).reshape(-1), _f32(kp).reshape(-1, 2)
+        n = kpp.shape[0] - 1
+        if n >= 1 and k.shape[0] < kpp.max():
+            raise ValueError("keypoint array shorter than kp_ptr says")
+        if k.shape[0] == 0:  # (the C-ABI refuses a NULL array; nothing of it is read)
+            k = np.zeros((1, 2), dtype=np.float32)
+        self._chk(self._L.sim3opt_track_batch_set_frames(self._b, n, _p(kpp, _ip), _p(k, _fp)), "track_batch_set_frames")
+
+    def set_frames_from(self, store):
+        """set_frames with kp_ptr / kp read in place from a FrameStore's current snapshot"""
+        self._chk(self._L.sim3opt_track_batch_set_frames_from(self._b, _store_handle(store)), "track_batch_set_frames_from")
+
+    def set_matches(self, pairs, match_ptr, query_idx, train_idx, mask=None, depth0=None, depth1=None):
+        pr, mp, q, t, mk, d0, d1 = _match_arrays(pairs, match_ptr, query_idx, train_idx, mask, depth0, depth1)
+        self._chk(self._L.sim3opt_track_batch_set_matches(self._b, pr.shape[0], _p(pr, _ip), _p(mp, _ip), _p(q, _ip),
+                                                          _p(t, _ip), _po(mk, _up), _po(d0, _dp), _po(d1, _dp)),
+                  "track_batch_set_matches")
+
+    def set_cameras(self, states, focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY):
+        st = _f64(states).reshape(-1, 8)
+        self._chk(self._L.sim3opt_track_batch_set_cameras(self._b, st.shape[0], _p(st, _dp), focal, cx, cy),
+                  "track_batch_set_cameras")
+
+    def dims(self):
+        """dict: DIMS (rounds: the hook-and-jump rounds of the last solve) and the kernels' switch sizes (TILES)"""
+        v = [C.c_int32() for _ in self.DIMS]
+        t = (C.c_int32 * 4)()
+        self._chk(self._L.sim3opt_track_batch_dims(self._b, *(C.byref(x) for x in v), t), "track_batch_dims")
+        out = dict(zip(self.DIMS, (x.value for x in v)))
+        out.update(zip(self.TILES, t))
+        return out
+
+    def solve(self):
+        """Tracks with status 0; raises when the library reports an error."""
+        return self._count(self._L.sim3opt_track_batch_solve(self._b), "track_batch_solve")
+
+    def tracks(self):
+        """dict: track_ptr (T + 1,), obs_frame, obs_keypoint (n_observations,), status, first_match (T,) and
+        match_track (total_matches,), -1 where masked"""
+        d = self.dims()
+        T, n = d["n_tracks"], d["n_observations"]
+        ptr, st, fm = np.empty(T + 1, dtype=np.int32), np.empty(T, dtype=np.int32), np.empty(T, dtype=np.int32)
+        of, ok, mt = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(d["total_matches"], dtype=np.int32)
+        self._chk(self._L.sim3opt_track_batch_get_tracks(self._b, _p(ptr, _ip), _p(of, _ip), _p(ok, _ip), _p(st, _ip),
+                                                         _p(fm, _ip)), "track_batch_get_tracks")
+        self._chk(self._L.sim3opt_track_batch_get_match_track(self._b, _p(mt, _ip)), "track_batch_get_match_track")
+        return dict(track_ptr=ptr, obs_frame=of, obs_keypoint=ok, status=st, first_match=fm, match_track=mt)
+
+    def points(self):
+        """(points (T, 3), n_depths (T,))"""
+        T = self.dims()["n_tracks"]
+        pts, nd = np.empty((T, 3)), np.empty(T, dtype=np.int32)
+        self._chk(self._L.sim3opt_track_batch_get_points(self._b, _p(pts, _dp), _p(nd, _ip)), "track_batch_get_points")
+        return pts, nd
+
+    def ba_rows(self, point_base=0):
+        """dict: points (K, 3), obs_cam, obs_point (= point_base + rank), obs_uv (n, 2) of the status-0 tracks, the rows
+        BundleAdjuster.set_problem takes once concatenated behind a map of point_base points"""
+        d = self.dims()
+        K, n = d["n_kept_tracks"], d["n_kept_observations"]
+        pts, uv = np.empty((K, 3)), np.empty((n, 2))
+        oc, op = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        self._chk(self._L.sim3opt_track_batch_get_ba(self._b, int(point_base), _p(pts, _dp), _p(oc, _ip), _p(op, _ip),
+                                                     _p(uv, _dp)), "track_batch_get_ba")
+        return dict(points=pts, obs_cam=oc, obs_point=op, obs_uv=uv)
+
+    @staticmethod
+    def reference(kp_ptr, kp, pairs, match_ptr, query_idx, train_idx, states, mask=None, depth0=None, depth1=None,
+                  focal=KITTI_FOCAL, cx=KITTI_CX, cy=KITTI_CY, max_reproj_px=0.0):
+        """sim3opt_track_reference, the serial restatement on the host (no device): the dict tracks() returns with
+        points and n_depths added"""
+        L = load()
+        kpp, k, st = _i32(kp_ptr).reshape(-1), _f32(kp).reshape(-1, 2), _f64(states).reshape(-1, 8)
+        if k.shape[0] == 0:
+            k = np.zeros((1, 2), dtype=np.float32)
+        if st.shape[0] != kpp.shape[0] - 1 or k.shape[0] < kpp.max():
+            raise ValueError("one state per frame, one pixel pair per keypoint")
+        pr, mp, q, t, mk, d0, d1 = _match_arrays(pairs, match_ptr, query_idx, train_idx, mask, depth0, depth1)
+        M = int(mp[-1]) if mp.shape[0] else 0
+        nt, no = C.c_int32(), C.c_int32()
+        ptr, stt, fm, nd = (np.zeros(M + 1, dtype=np.int32) for _ in range(4))
+        of, ok = np.zeros(2 * M + 1, dtype=np.int32), np.zeros(2 * M + 1, dtype=np.int32)
+        mt, pts = np.zeros(M + 1, dtype=np.int32), np.zeros((M + 1, 3))
+        rc = L.sim3opt_track_reference(kpp.shape[0] - 1, _p(kpp, _ip), _p(k, _fp), pr.shape[0], _p(pr, _ip), _p(mp, _ip),
+                                       _p(q, _ip), _p(t, _ip), _po(mk, _up), _po(d0, _dp), _po(d1, _dp), _p(st, _dp),
+                                       focal, cx, cy, max_reproj_px, C.byref(nt), C.byref(no), _p(ptr, _ip), _p(of, _ip),
+                                       _p(ok, _ip), _p(stt, _ip), _p(fm, _ip), _p(mt, _ip), _p(pts, _dp), _p(nd, _ip))
+        if rc != OK:
+            raise Sim3OptError(rc, "track_reference: refused")
+        T, n = nt.value, no.value
+        return dict(track_ptr=ptr[:T + 1].copy(), obs_frame=of[:n].copy(), obs_keypoint=ok[:n].copy(),
+                    status=stt[:T].copy(), first_match=fm[:T].copy(), match_track=mt[:M].copy(), points=pts[:T].copy(),
+                    n_depths=nd[:T].copy())
 
 
 class MatchBatch(_Handle):
