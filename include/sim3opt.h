@@ -1538,14 +1538,17 @@ int sim3opt_match_batch_debug_depth(sim3opt_match_batch* b, int32_t n, int32_t f
  * nodeId); parsing .yml.gz is the caller's.
  * Word of a descriptor: from the root, at every inner node go to the child of smallest d2, the lower child on equal d2,
  * until a leaf.  d2(a, b) = sum_k (double) fl32(fl32(a_k - b_k) * fl32(a_k - b_k)): difference and square in FP32,
- * each rounded once and not fused, the 64 terms added in double in ascending k.
+ * each rounded once and not fused, the 64 terms added in double in ascending k.  The roundings are IEEE's: a square
+ * below 2^-126 is a subnormal FP32 and is not flushed to zero, so two descriptors 2^-70 apart have d2 > 0.
  * Bag-of-words vector of a frame: for every word of weight > 0 that a descriptor of the frame reaches, value = count *
  * weight (one multiplication; DBoW2 adds the weight count times), or value = weight with options.accumulate = 0; the
- * values divided by their sum, taken in double in ascending word id.  A frame without descriptors or without a word of
- * positive weight has the empty vector.
+ * values divided by their sum, taken in double in ascending word id: the sum is 0 plus the values one after the other,
+ * not fused with the multiplication, and every value is divided by it once.  A frame without descriptors or without a
+ * word of positive weight has the empty vector.
  * Score: s(a, b) = -1/2 sum_{w in a and b} (|a_w - b_w| - (|a_w| + |b_w|)) in double, the terms added one after the
  * other in ascending word id: a function of the two vectors alone and symmetric in them bit for bit; 0 without a
- * common word.
+ * common word.  The term is associated as written, fabs(a_w - b_w) - (fabs(a_w) + fabs(b_w)): three roundings; the
+ * terms are added to 0; the sum is multiplied once by -0.5; a sum of 0 gives +0.
  * Per query frame i (entry ids are frame indices):
  *  1. i <= dislocal: SIM3OPT_PLACE_CLOSE_MATCHES_ONLY.
  *  2. Results: the frames j <= i - dislocal with s(v_i, v_j) > 0, by score descending and lower j on equal score, the
@@ -1553,8 +1556,9 @@ int sim3opt_match_batch_debug_depth(sim3opt_match_batch* b, int32_t n, int32_t f
  *  3. ns = s(v_i, v_{i-1}) with use_nss, else 1.  With use_nss, ns < min_nss_factor: SIM3OPT_PLACE_LOW_NSS_FACTOR.
  *  4. Kept: the results with score >= alpha * ns.  None: SIM3OPT_PLACE_LOW_SCORES.  From here on match is reported.
  *  5. Islands: the kept results in ascending j; runs in which each j is less than max_intragroup_gap above the one
- *     before.  An island has first, last, score (the sum of its results' scores in ascending j) and best_entry (its
- *     result of highest score, the lower j on ties); islands of fewer than min_matches_per_group results are dropped.
+ *     before.  An island has first, last, score (its results' scores added one after the other in ascending j) and
+ *     best_entry (its result of highest score, the lower j on ties); islands of fewer than min_matches_per_group
+ *     results are dropped.
  *     None left: SIM3OPT_PLACE_NO_GROUPS with match = the best result.  The chosen island has the highest score, the
  *     lower first on ties; match = its best_entry.
  *  6. Temporal window, a recurrence over the queries that reached 5 with an island, state (a1, a2, last_query, n),
@@ -1671,7 +1675,14 @@ int sim3opt_place_batch_debug_islands(sim3opt_place_batch* b, int32_t query, int
  *    order, whose inclusive prefix sum of w exceeds r (the last member if none does).  key(c) = seed + (64 node + c + 1)
  *    * 0x9E3779B97F4A7C15 with node the node's output index: it holds the seed, the node and c only.  The prefix sums
  *    are double, formed in an order that is a function of the inputs alone (a scan within 256 members, the runs of 256
- *    one after the other).
+ *    one after the other).  To the bit: the members are cut into runs of 256 in member order.  A run's scan starts
+ *    from its w followed by zeros up to 256 entries (a partial run is padded, not shortened); then for s = 1, 2, 4, ...,
+ *    128 every entry i >= s becomes itself plus entry i - s, all from the values before the step.  A run's total is
+ *    the scan's entry 255 -- in a partial run another association of the same terms than its last member's entry, so
+ *    the two may differ in the last bit.  carry = 0 before the first run and carry + total after each; a member's
+ *    prefix is its scan entry plus the carry before its run; W is the carry after the last run, and r = u W is one
+ *    multiplication.  W may therefore round above the last member's prefix; r < W then leaves no prefix above r, and
+ *    the choice falls to the last member.
  *  - Lloyd: a pass assigns every member to the centre of smallest d2, the lower cluster on equal d2, and then sets the
  *    centre of every non-empty cluster to its mean; an empty cluster keeps its centre.  Passes repeat until one
  *    changes no assignment (its means are not taken again: they are the pass before's) or max_iters passes have run;
@@ -1680,7 +1691,10 @@ int sim3opt_place_batch_debug_islands(sim3opt_place_batch* b, int32_t query, int
  *    DEVIATION from FSurf64::meanValue, which adds FP32 quotients one after the other in member order: that order is
  *    serial over up to a million members; the double sum differs from it by its FP32 rounding only.  The order of the
  *    double sum: runs of 1024 members in member order, each added one member after the other, then the runs one after
- *    the other.  No floating-point atomics.
+ *    the other.  The runs are the node's (1024 of its members, whatever their clusters); a cluster's sum within a run
+ *    is 0 plus its members there in member order, and its sum is 0 plus the runs' sums in run order.  (The addends are
+ *    FP32, so on unit-norm descriptors this sum is exact and its order invisible in the centres.)  No floating-point
+ *    atomics.
  *  - Children: the non-empty clusters, in cluster order.
  *  - Leaves: a node whose seeding ended with one centre (all members equal), a node of one member, every node at level
  *    `levels`.

@@ -2,8 +2,12 @@
 include/sim3opt.h defines it ("batched bag-of-words place recognition"): the word of a descriptor, the vector of a
 frame (a dict), the score (long-double sums), the per-query tests (sorted()), the temporal window.  `defect` names a
 one-line deviation; tests/test_place_ref.py asserts that the cases of tests/place_cases.py catch each of them.
-While it runs it records every comparison that decides anything with its margin (Detection.margins)."""
+While it runs it records every comparison that decides anything with its margin (Detection.margins).
+detect(exact=True) takes the vectors, the scores and the island scores from tests/rounding_ref.py, in the order the
+header states to the bit, for descriptors off the lattice (tests/rounding_cases.py); the default is unchanged."""
 import numpy as np
+
+import rounding_ref as RR
 
 CANDIDATE, CLOSE_MATCHES_ONLY, NO_DB_RESULTS, LOW_NSS_FACTOR, LOW_SCORES, NO_GROUPS, NO_TEMPORAL_CONSISTENCY = range(7)
 
@@ -50,8 +54,8 @@ def d2(a, centres):
     return np.cumsum(sq.astype(np.float64), axis=1)[:, -1]
 
 
-def word_of(voc, a, defect=None):
-    """(word id, [winning d2 of every level])"""
+def word_of(voc, a, defect=None, d2=d2):
+    """(word id, [winning d2 of every level]); d2: the distance, this module's by default"""
     node, path = 0, []
     while voc.children[node]:
         ch = voc.children[node]
@@ -89,23 +93,38 @@ def score(a, b, defect=None):
 
 class Detection:
     """What detect() returns: per-frame lists status, match, score, ns_factor, n_consistent, island; the words
-    (per frame), vectors (dicts), S (the full score matrix), kept and islands per query (for the diagnostics),
+    (per frame), paths (per descriptor: the winning d2 of every level), vectors (dicts), S (the full score matrix),
+    kept and islands per query (for the diagnostics),
     pairs, and margins: (what, margin) of every deciding comparison that is not an equality by construction."""
 
 
-def detect(voc, kp_ptr, desc, defect=None, **options):
+def detect(voc, kp_ptr, desc, defect=None, exact=False, **options):
+    """exact=True: every double in the order the header states (tests/rounding_ref.py), so that the vectors, the scores
+    and the island scores are the definition's bits; `defect` may then also be one of rounding_ref.DEFECTS.  The
+    default sums the scores in long double and is compared within a tolerance."""
     o = dict(DEFAULTS, **options)
     kp_ptr = np.asarray(kp_ptr)
     desc = np.asarray(desc, dtype=np.float32).reshape(-1, 64)
     n = len(kp_ptr) - 1
     R = Detection()
-    all_words = [word_of(voc, desc[t], defect)[0] for t in range(kp_ptr[-1])]
+    if exact:
+        found = [word_of(voc, desc[t], defect, d2=lambda a, c: RR.d2(a, c, defect)) for t in range(kp_ptr[-1])]
+    else:
+        found = [word_of(voc, desc[t], defect) for t in range(kp_ptr[-1])]
+    all_words, R.paths = [w for w, _ in found], [p for _, p in found]
     R.words = [all_words[kp_ptr[f]:kp_ptr[f + 1]] for f in range(n)]
-    R.vectors = [bow_vector(voc, w, o["accumulate"], defect) for w in R.words]
+    if exact:
+        R.vectors = [RR.bow_vector(voc.word_weight, w, o["accumulate"], defect, defect == "zero_weight_kept",
+                                   defect == "norm_by_word_count") for w in R.words]
+    else:
+        R.vectors = [bow_vector(voc, w, o["accumulate"], defect) for w in R.words]
     S = np.zeros((n, n))
     for i in range(n):
         for j in range(i + 1):
-            S[i, j] = S[j, i] = score(R.vectors[i], R.vectors[j], defect)
+            if exact:
+                S[i, j] = S[j, i] = RR.score(R.vectors[i], R.vectors[j], defect, defect == "no_half")
+            else:
+                S[i, j] = S[j, i] = score(R.vectors[i], R.vectors[j], defect)
     R.S = S
     R.margins = []
     R.status, R.match, R.score, R.ns_factor = [CANDIDATE] * n, [-1] * n, [0.0] * n, [0.0] * n
@@ -159,6 +178,8 @@ def detect(voc, kp_ptr, desc, defect=None, **options):
             total = np.longdouble(0)
             for s, _ in g:
                 total += np.longdouble(s)
+            if exact:
+                total = RR.island_score([s for s, _ in g], defect)
             total = max(s for s, _ in g) if defect == "island_score_max" else float(total)
             best = min(g, key=lambda r: (-r[0], r[1]))
             islands.append(dict(first=g[0][1], last=g[-1][1], score=total, best_entry=best[1], best_score=best[0],

@@ -4,12 +4,15 @@ distance and place_ref.word_of for the descent the weights are counted from.  It
 no permutation, no chunk and no level-wide pass in it.  `defect` names a one-line deviation; tests/test_vocab_ref.py
 asserts that the cases of tests/vocab_cases.py catch each of them.  While it runs it records every comparison that
 decides anything with its margin (Training.margins).  PARITY UNPINNED: only the distance and the mean's operands are
-the reference's (FSurf64.cpp:23-58); the rest restates DBoW2's create from memory."""
+the reference's (FSurf64.cpp:23-58); the rest restates DBoW2's create from memory.  train(exact=True) takes d2, the
+seeding's prefix sums and the mean from tests/rounding_ref.py, in the order the header states to the bit, for
+descriptors off the lattice (tests/rounding_cases.py); the default is unchanged."""
 import math
 
 import numpy as np
 
 import place_ref as PR
+import rounding_ref as RR
 
 DEFAULTS = dict(k=10, levels=5, max_iters=100, idf=1, seed=0)
 
@@ -47,8 +50,12 @@ def _mean(rows, defect):
     return (np.sum(rows.astype(np.float64), axis=0) / len(rows)).astype(np.float32)
 
 
-def train(kp_ptr, desc, defect=None, **options):
+def train(kp_ptr, desc, defect=None, exact=False, **options):
+    """exact=True: d2, the seeding's prefix sums with W, and the mean in the order the header states
+    (tests/rounding_ref.py), so that W, r and the centres are the definition's bits on any descriptors; `defect` may
+    then also be one of rounding_ref.DEFECTS.  The default sums with numpy and is exact on lattice cases only."""
     o = dict(DEFAULTS, **options)
+    d2 = (lambda a, rows: RR.d2(a, rows, defect)) if exact else PR.d2
     k, L, seed = o["k"], o["levels"], o["seed"]
     kp_ptr = np.asarray(kp_ptr)
     desc = np.asarray(desc, dtype=np.float32).reshape(-1, 64)
@@ -77,16 +84,15 @@ def train(kp_ptr, desc, defect=None, **options):
             first = 0 if defect == "first_centre_is_member_0" else draw(seed, node, 0, defect) % n
             chosen, w, Ws, rs = [members[first]], None, [], []
             for c in range(1, k):
-                dist = PR.d2(desc[chosen[-1]], rows)
+                dist = d2(desc[chosen[-1]], rows)
                 w = dist if (w is None or defect == "w_is_last_distance") else np.minimum(w, dist)
-                W = float(np.sum(w))
+                prefix, W = RR.prefix(w, defect) if exact else (np.cumsum(w), float(np.sum(w)))
                 if W == 0:
                     Ws.append(0.0)
                     rs.append(0.0)
                     break
                 u = (draw(seed, node, c - 1 if defect == "r_from_the_round_before" else c, defect) >> 11) * 2.0 ** -53
                 r = u * W
-                prefix = np.cumsum(w)
                 R.margins.append(("r against a prefix boundary", float(np.abs(prefix - r).min()) / W))
                 above = np.nonzero((prefix - w if defect == "exclusive_prefix" else prefix) > r)[0]
                 chosen.append(members[int(above[0]) if len(above) else n - 1])
@@ -101,7 +107,7 @@ def train(kp_ptr, desc, defect=None, **options):
                 limit = o["max_iters"] + (1 if defect == "one_pass_more" else 0)
                 converged = False
                 for p in range(1, limit + 1):
-                    dist = np.stack([PR.d2(centres[c], rows) for c in range(len(centres))], axis=1)  # (n, centres)
+                    dist = np.stack([d2(centres[c], rows) for c in range(len(centres))], axis=1)  # (n, centres)
                     order = np.sort(dist, axis=1)
                     gap = order[:, 1] - order[:, 0]
                     R.margins += [("d2 against d2", float(g / s)) for g, s in zip(gap, order[:, 1]) if g > 0]
@@ -118,7 +124,9 @@ def train(kp_ptr, desc, defect=None, **options):
                     cluster = new
                     for c in range(len(centres)):
                         mine = rows[[i for i in range(n) if cluster[i] == c]]
-                        if len(mine):
+                        if len(mine) and exact:
+                            centres[c] = RR.mean(rows, cluster, c, defect)
+                        elif len(mine):
                             centres[c] = _mean(mine, defect)
                         elif defect == "empty_cluster_zeroed":
                             centres[c] = 0
@@ -142,7 +150,7 @@ def train(kp_ptr, desc, defect=None, **options):
     R.parent, R.centre, R.word_id = np.asarray(parent, dtype=np.int32), np.stack(centre), word_id
     voc = PR.Vocabulary(R.parent, R.centre, np.zeros(N), word_id)
     leaf_of_word = {int(w): i for i, w in enumerate(word_id) if w >= 0}
-    R.descent = np.asarray([leaf_of_word[PR.word_of(voc, desc[t])[0]] for t in range(D)], dtype=np.int64)
+    R.descent = np.asarray([leaf_of_word[PR.word_of(voc, desc[t], d2=d2)[0]] for t in range(D)], dtype=np.int64)
     R.assignment, R.depth, R.passes = assignment, voc.depth, passes
     # the weights
     counted = assignment if defect == "weights_by_membership" else R.descent
