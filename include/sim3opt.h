@@ -930,6 +930,56 @@ int sim3opt_ba_debug_step(sim3opt_ba* b, double lambda, int32_t solver, int32_t 
 int sim3opt_ba_debug_update(sim3opt_ba* b, const double* dx_c, const double* dx_p, double lambda, int32_t with_fail,
                             double* cam_qt, double* points, double* chi2, double* scale);
 
+/* ---- Bundle-adjustment covariances: cameras and points by selected inversion (g2o's computeMarginals) ----
+ * Definition.  H = J^T W J at the CURRENT estimates, with the Huber weights and 1 / pixel_noise^2 exactly as k_ba_obs
+ * forms them; the tangent order is the update's, [omega, upsilon] per camera (T <- exp(.) T), xyz per point.  Fixed
+ * cameras are removed.  lambda >= 0 is added to every diagonal entry, cameras and points (the caller's prior;
+ * computeMarginals is lambda = 0).  With Sigma = (H + lambda I)^-1:
+ *   camera-camera block (a, b), 6 x 6:  Sigma_cc = S^-1, S the reduced camera system of an LM trial with damping lambda.
+ *     Answered for a camera with itself and for every pair on the pattern of the factor of S; every two cameras that
+ *     share a point are on it.  A pair outside it: SIM3OPT_ERR_ARG, nothing written (as sim3opt_marginals).  A fixed
+ *     camera on either side: the block is exactly +0 (a fixed camera stays a row of S, an identity row, so its block
+ *     of S^-1 is not its covariance and is masked).
+ *   point block p, 3 x 3:  Sigma_pp = H_pp^-1 + sum over a, b in obs(p) of Z_a^T Sigma_cc[cam(a), cam(b)] Z_b, over ALL
+ *     ordered pairs of the point's observations in the order of its observation list (ascending observation index; a
+ *     outer, b inner), H_pp^-1 = (H_pp + lambda I)^-1 and Z_o = (A^T B)_o H_pp^-1 as sim3opt_ba_debug_reduced returns them.
+ *     Blocks with a fixed camera contribute nothing.  The result is symmetrised once, (M + M^T) / 2: symmetric bit for bit.
+ *   point-camera block (p, c), 3 x 6:  Sigma_pc = - sum over a in obs(p) of Z_a^T Sigma_cc[cam(a), c].  c fixed: +0.  A
+ *     needed camera pair outside the pattern (possible only when c does not observe p): SIM3OPT_ERR_ARG.
+ * All blocks are column-major (entry (r, c) at r + rows c): 36, 9 and 18 doubles per block.
+ * Singular system: SIM3OPT_ERR_STATE, nothing written, never NaN -- a non-positive pivot of the factorisation of S, a
+ * pivot of it below 1e-13 max |H_dd| (the selected inversion's test), a non-finite result, or ANY point of the problem
+ * (requested or not: every point enters S) whose H_pp + lambda I fails its pivot test: the 3 x 3 LDL^T in x, y, z order
+ * with a pivot <= 1e-13 x the point's largest undamped diagonal entry, or <= 0; the message names the lowest such
+ * point.  A map with points seen once, with a free camera nobody observes with, or with no fixed camera therefore
+ * wants lambda > 0.  (S is stored in 7 x 7 blocks with a unit pad, and a fixed camera is an identity row; where
+ * max |H_dd| exceeds 1e13 those ones would fail the selected inversion's relative pivot test.  Before factoring, the
+ * call sets the pads and the fixed cameras' diagonals to max(1, max |H_dd|): they couple to nothing, so the 6 x 6 blocks
+ * of S^-1 keep their bits, and they pass the test at every scale.)
+ * No side effects: the call factors in a context of its own (built at the first call; a refused plan -- more block
+ * products than SIM3OPT_BA_COV_MAX_PAIRS, else SIM3OPT_BA_MAX_PAIRS, else 30 M -- is SIM3OPT_ERR_STATE, remembered until
+ * the problem changes) and leaves the LM's factorisation, the estimate, the statistics and every later
+ * sim3opt_ba_optimize / sim3opt_ba_chi2 / read-out result bit for bit what they are without it, under either linear
+ * solver.  Deterministic: no floating-point atomics, fixed summation orders; the bits of a block depend neither on the
+ * order, duplicates or split of the request nor on the schedule knobs SIM3OPT_BA_SUBTREE / SIM3OPT_BA_WG_SUB.
+ * One call runs one linearisation, one factorisation and one selected inversion for its three requests (camera pairs
+ * cam_a / cam_b -> cov_cc n_cc x 36; points -> cov_pp n_pp x 9; (pc_point, pc_cam) -> cov_pc n_pc x 18); any of them may
+ * be empty (count 0, arrays NULL).  Unknown indices, a non-finite or negative lambda: SIM3OPT_ERR_ARG; no problem set:
+ * SIM3OPT_ERR_STATE. */
+int sim3opt_ba_covariances(sim3opt_ba* b, double lambda, int32_t n_cc, const int32_t* cam_a, const int32_t* cam_b,
+                           double* cov_cc, int32_t n_pp, const int32_t* point, double* cov_pp, int32_t n_pc,
+                           const int32_t* pc_point, const int32_t* pc_cam, double* cov_pc);
+/* of the last sim3opt_ba_covariances that got as far as its plan: columns of the factor, blocks of L / Z, 7x7x7 products
+ * of the factorisation, of the selected inversion, ordered observation pairs summed for the distinct requested points
+ * (pairs with a fixed camera left out), 1 when the selected inversion ran */
+int sim3opt_ba_covariance_stats(const sim3opt_ba* b, int64_t out[6]);
+/* Diagnostic.  The pattern of the covariances' factor (built if need be): *nb columns (the cameras), *nL stored blocks,
+ * *ngroups workgroups of its schedule; perm (nb: the camera eliminated at position j), colptr (nb + 1) and lrow (nL:
+ * the rows, as positions, of column j's blocks, the diagonal first, ascending) may be NULL (the size query).  Camera
+ * pair (a, b) is answered iff block (max(pos a, pos b), min(pos a, pos b)) is stored. */
+int sim3opt_ba_covariance_plan(sim3opt_ba* b, int32_t* nb, int64_t* nL, int32_t* ngroups, int32_t* perm, int32_t* colptr,
+                               int32_t* lrow);
+
 /* ---- batched two-view bundle adjustment: the loop detector's refinement, every candidate in one launch ----
  * BAOptimize (kittiDetector.h:845-954, helpers :712-788), which the detector calls once per accepted loop
  * candidate (:1325) and whose result is line 4 of a loopConstraints.txt record: two VertexSE3Expmap cameras, the

@@ -124,9 +124,13 @@ class Vertex {  // g2o::OptimizableGraph::Vertex, as far as ba_demo touches it
   void setMarginalized(bool m) { marginalized_ = m; }
   bool marginalized() const { return marginalized_; }
   virtual int dimension() const = 0;
+  // g2o's numbering of the free vertices after initializeOptimization(): the free cameras in ascending id, then the
+  // points in ascending id; -1 for a fixed camera (and before initializeOptimization())
+  int hessianIndex() const { return hidx_; }
 
  protected:
-  int id_ = -1;
+  friend class SparseOptimizer;
+  int id_ = -1, hidx_ = -1;
   bool fixed_ = false, marginalized_ = false;
 };
 
@@ -241,6 +245,38 @@ struct OptimizationAlgorithmLevenberg {
   int max_trials = 10;
 };
 
+// g2o::SparseBlockMatrix<MatrixXd>, as far as computeMarginals fills it: dense blocks of 6 x 6 (camera, camera), 3 x 3
+// (point, point), 3 x 6 (point, camera) and 6 x 3 (camera, point) doubles, addressed by a pair of hessianIndex() values
+class SparseBlockMatrix {
+ public:
+  class Block {
+   public:
+    Block() {}
+    Block(int rows, int cols) : rows_(rows), cols_(cols), d_((size_t)rows * cols, 0.0) {}
+    int rows() const { return rows_; }
+    int cols() const { return cols_; }
+    double operator()(int r, int c) const { return d_[(size_t)r + (size_t)rows_ * c]; }
+    double& operator()(int r, int c) { return d_[(size_t)r + (size_t)rows_ * c]; }
+    const double* data() const { return d_.data(); }  // column-major
+    double* data() { return d_.data(); }
+
+   private:
+    int rows_ = 0, cols_ = 0;
+    std::vector<double> d_;
+  };
+  // the block, or nullptr when it is not stored
+  const Block* block(int r, int c) const {
+    auto it = blocks_.find({r, c});
+    return it == blocks_.end() ? nullptr : &it->second;
+  }
+  Block& set(int r, int c, int rows, int cols) { return blocks_[{r, c}] = Block(rows, cols); }
+  size_t nonZeroBlocks() const { return blocks_.size(); }
+  void clear() { blocks_.clear(); }
+
+ private:
+  std::map<std::pair<int, int>, Block> blocks_;
+};
+
 class SparseOptimizer {  // g2o::SparseOptimizer (bal_example.cpp:71-72, :85, :95, :115, :125, :155, :198, :213)
  public:
   SparseOptimizer() : b_(sim3opt_ba_create()) {
@@ -299,6 +335,12 @@ class SparseOptimizer {  // g2o::SparseOptimizer (bal_example.cpp:71-72, :85, :9
       }
     }
     if (cams_.empty() || pts_.empty() || edges_.empty()) return fail("empty problem");
+    hcam_.clear();
+    for (size_t c = 0; c < cams_.size(); ++c) {
+      cams_[c]->hidx_ = cams_[c]->fixed() ? -1 : (int)hcam_.size();
+      if (!cams_[c]->fixed()) hcam_.push_back((int)c);
+    }
+    for (size_t p = 0; p < pts_.size(); ++p) pts_[p]->hidx_ = (int)(hcam_.size() + p);
     const EdgeProjectXYZ2UV& e0 = *edges_[0];
     const double delta = e0.kernel_ ? e0.kernel_->delta() : 0.0;
     if (!(e0.info_[0] > 0) || e0.info_[0] != e0.info_[3] || e0.info_[1] != 0 || e0.info_[2] != 0)
@@ -348,6 +390,53 @@ class SparseOptimizer {  // g2o::SparseOptimizer (bal_example.cpp:71-72, :85, :9
     for (size_t p = 0; p < pts_.size(); ++p) std::copy(&pp[3 * p], &pp[3 * p] + 3, pts_[p]->data());
     return n;
   }
+  // Marginal covariances (g2o SparseOptimizer::computeMarginals, lambda = 0) at the current estimates: the blocks
+  // (r, c) of H^-1 for the listed pairs of hessianIndex() values, through one sim3opt_ba_covariances call, into
+  // spinv.block(r, c) -- two cameras on the pattern of the reduced system's factor (6 x 6), a point with itself (3 x 3),
+  // a point and a camera in either order (3 x 6, or its transpose 6 x 3).  False (spinv unchanged) for an index out of
+  // range, two different points, a pair the library refuses, or a singular H; lastError() says why.
+  bool computeMarginals(SparseBlockMatrix& spinv, const std::vector<std::pair<int, int>>& blockIndices) {
+    if (!ready_) return fail("computeMarginals before initializeOptimization");
+    err_.clear();
+    const int nfree = (int)hcam_.size(), nh = nfree + (int)pts_.size();
+    std::vector<int32_t> ca, cb, pt, qp, qc;
+    std::vector<std::pair<int, size_t>> where;  // kind (0 cc, 1 pp, 2 pc, 3 pc transposed), index
+    for (const auto& rc : blockIndices) {
+      const int r = rc.first, c = rc.second;
+      if (r < 0 || c < 0 || r >= nh || c >= nh) return fail("computeMarginals: hessianIndex out of range");
+      if (r < nfree && c < nfree) {
+        where.push_back({0, ca.size()});
+        ca.push_back(hcam_[r]); cb.push_back(hcam_[c]);
+      } else if (r >= nfree && c >= nfree) {
+        if (r != c) return fail("computeMarginals: blocks between two different points are not provided");
+        where.push_back({1, pt.size()});
+        pt.push_back(r - nfree);
+      } else {
+        where.push_back({r >= nfree ? 2 : 3, qp.size()});
+        qp.push_back((r >= nfree ? r : c) - nfree);
+        qc.push_back(hcam_[r >= nfree ? c : r]);
+      }
+    }
+    std::vector<double> cc(36 * ca.size() + 1), pp(9 * pt.size() + 1), pc(18 * qp.size() + 1);
+    if (sim3opt_ba_covariances(b_, 0.0, (int32_t)ca.size(), ca.data(), cb.data(), cc.data(), (int32_t)pt.size(),
+                               pt.data(), pp.data(), (int32_t)qp.size(), qp.data(), qc.data(), pc.data()) != SIM3OPT_OK)
+      return false;
+    for (size_t q = 0; q < blockIndices.size(); ++q) {
+      const int kind = where[q].first;
+      const size_t k = where[q].second;
+      const int rows = kind == 0 || kind == 3 ? 6 : 3, cols = kind == 0 || kind == 2 ? 6 : 3;
+      SparseBlockMatrix::Block& B = spinv.set(blockIndices[q].first, blockIndices[q].second, rows, cols);
+      const double* src = kind == 0 ? &cc[36 * k] : kind == 1 ? &pp[9 * k] : &pc[18 * k];
+      for (int c = 0; c < cols; ++c)
+        for (int r = 0; r < rows; ++r) B(r, c) = kind == 3 ? src[c + 3 * r] : src[r + rows * c];
+    }
+    return true;
+  }
+  bool computeMarginals(SparseBlockMatrix& spinv, const Vertex* vertex) {
+    if (!vertex || vertex->hessianIndex() < 0) return fail("computeMarginals: a fixed or unknown vertex");
+    const int h = vertex->hessianIndex();
+    return computeMarginals(spinv, std::vector<std::pair<int, int>>{{h, h}});
+  }
   void computeActiveErrors() {}
   double activeRobustChi2() { double c = 0; sim3opt_ba_chi2(b_, &c); return c; }
   double chi2() { return activeRobustChi2(); }
@@ -366,6 +455,7 @@ class SparseOptimizer {  // g2o::SparseOptimizer (bal_example.cpp:71-72, :85, :9
   std::vector<std::unique_ptr<EdgeProjectXYZ2UV>> edges_;
   std::vector<VertexSE3Expmap*> cams_;
   std::vector<VertexSBAPointXYZ*> pts_;
+  std::vector<int> hcam_;  // camera index of each free camera's hessianIndex
 };
 
 }  // namespace ba
@@ -381,6 +471,7 @@ using sim3opt_shim::ba::EdgeProjectXYZ2UV;
 using sim3opt_shim::ba::OptimizationAlgorithmLevenberg;
 using sim3opt_shim::ba::RobustKernelHuber;
 using sim3opt_shim::ba::SE3Quat;
+using sim3opt_shim::ba::SparseBlockMatrix;
 using sim3opt_shim::ba::SparseOptimizer;
 using sim3opt_shim::ba::VertexSBAPointXYZ;
 using sim3opt_shim::ba::VertexSE3Expmap;

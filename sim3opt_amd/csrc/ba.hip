@@ -26,6 +26,8 @@
 //   k_ba_backsub  thread / point: dx_p = H_pp^-1 b_p - sum Z_o^T dx_c(cam(o))
 //   k_ba_update   exp-map update of the cameras, additive update of the points (backup kept)
 //   k_ba_chi2     thread / observation: robustified chi2, fixed-order block sums
+// Covariances of the refined map (sim3opt_ba_covariances): the same linearisation and reduced system, a second BlockLdl
+// with the selected inversion, and the kernels of ba_cov_kernels.hpp on top of S^-1 (host side: ba_cov_host.hpp).
 // The host runs g2o's lambda policy on three scalars per trial: engine.hip's LmDamping (lm_damping.hpp).
 // The camera / point arithmetic is ba_math.hpp's, shared with the batched two-view kernel (ba_batch.hip).
 #include <hip/hip_runtime.h>
@@ -41,6 +43,7 @@
 #include <vector>
 
 #include "../../include/sim3opt.h"
+#include "ba_cov_host.hpp"
 #include "ba_math.hpp"
 #include "handle_device.hpp"
 #include "direct_factor.hpp"
@@ -489,6 +492,8 @@ __global__ __launch_bounds__(WG) void k_ba_final(const double* __restrict__ pa, 
   }
 }
 
+#include "ba_cov_kernels.hpp"
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -521,11 +526,23 @@ struct Problem {
   int32_t nblk = 0;
   int grid_chi = 1;
   sim3opt::BlockLdl direct;  // exact factorisation of the reduced camera system (not ready: PCG fallback)
+  // sim3opt_ba_covariances: a factorisation context of its own (with the selected inversion), built at the first call
+  sim3opt::BlockLdl cov_factor;
+  sim3opt::DevArena cov_mem;
+  std::string cov_refused;  // why the plan was refused (remembered until the problem changes)
+  CovTables cov_tab;
+  int32_t *d_cslot = nullptr, *d_ctrans = nullptr, *d_cmask = nullptr, *d_cflags = nullptr;
+  double *d_Zc = nullptr, *d_C = nullptr;  // S^-1 on S's blocks: as picked (7x7), masked and compacted (6x6)
+  int64_t cov_stats[6] = {0, 0, 0, 0, 0, 0};
 
   ~Problem() { release(); }
   void release() {
     if (stream) (void)hipStreamSynchronize(stream);
     direct.release();
+    cov_factor.release();
+    cov_mem.release();
+    cov_refused.clear();
+    cov_tab = CovTables();
     mem.release();
     if (h_sc) (void)hipHostFree(h_sc);
     h_sc = nullptr;
@@ -891,6 +908,185 @@ struct Problem {
     HIPCHK(hipStreamSynchronize(stream));
     return SIM3OPT_OK;
   }
+
+  // ---- covariances (include/sim3opt.h, sim3opt_ba_covariances).  Like the read-outs above the call writes only
+  // buffers optimize() rewrites before it reads them (d_lin, H_pp^-1, b_p, Z, S, g, b_c, the diagonals and
+  // d_sc->maxdiag); the factorisation, its flags and everything else are the context's own. ----
+  int cov_init() {
+    if (!cov_refused.empty()) { err = cov_refused; return SIM3OPT_ERR_STATE; }
+    const int NC = nc();
+    std::vector<int32_t> rptr((size_t)NC + 1), bcol((size_t)nblk);
+    int rc;
+    if ((rc = down(rptr.data(), d_rptr, sizeof(int32_t) * rptr.size())) ||
+        (rc = down(bcol.data(), d_bcol, sizeof(int32_t) * bcol.size())))
+      return rc;
+    // the plan the LM's factorisation uses (same knobs), with the limit of an explicit request
+    int64_t max_pairs = 30000000;
+    if (const char* ev = std::getenv("SIM3OPT_BA_MAX_PAIRS")) max_pairs = std::atoll(ev);
+    if (const char* ev = std::getenv("SIM3OPT_BA_COV_MAX_PAIRS")) max_pairs = std::atoll(ev);
+    const int32_t subtree = std::max(16, NC / 6);
+    std::string why;
+    if (!cov_factor.build_plan(NC, rptr.data(), bcol.data(), max_pairs, subtree, "SIM3OPT_BA", true, why)) {
+      cov_refused = "ba_covariances: " + why;
+      err = cov_refused;
+      return SIM3OPT_ERR_STATE;
+    }
+    const sim3opt::DirectPlan& P = cov_factor.plan();
+    const CovFactorPattern F{P.nb, P.perm.data(), P.colptr.data(), P.lrow.data()};
+    why = cov_build_tables(NC, np(), oc, op, cam_fixed, rptr, bcol, F, cov_tab);
+    if (!why.empty()) {
+      cov_factor.release();
+      cov_refused = "ba_covariances: " + why;
+      err = cov_refused;
+      return SIM3OPT_ERR_STATE;
+    }
+    auto body = [&]() -> int {
+      HIPCHK(cov_factor.upload(stream));
+      HIPCHK(cov_mem.upload(d_cslot, cov_tab.sslot, stream, nullptr));
+      HIPCHK(cov_mem.upload(d_ctrans, cov_tab.strans, stream, nullptr));
+      HIPCHK(cov_mem.upload(d_cmask, cov_tab.smask, stream, nullptr));
+      HIPCHK(cov_mem.alloc(d_cflags, 4, stream));
+      HIPCHK(cov_mem.alloc(d_Zc, 49 * (size_t)nblk, stream));
+      HIPCHK(cov_mem.alloc(d_C, 36 * (size_t)nblk, stream));
+      return SIM3OPT_OK;
+    };
+    rc = body();
+    const hipError_t es = hipStreamSynchronize(stream);  // (the uploads read this frame's tables)
+    if (rc == SIM3OPT_OK && es != hipSuccess) {
+      err = std::string("ba_covariances: ") + hipGetErrorString(es);
+      rc = SIM3OPT_ERR_HIP;
+    }
+    if (rc) {
+      cov_factor.release();
+      cov_mem.release();
+      return rc;
+    }
+    if (opt.verbose)
+      std::fprintf(stderr, "sim3opt ba: covariances: %d cameras, %lld blocks of L / Z, %lld + %lld block products, %d groups\n",
+                   NC, (long long)P.nL, (long long)P.npairs, (long long)cov_factor.selinv_plan().nprod, P.ngroups());
+    return SIM3OPT_OK;
+  }
+
+  int covariances(double lambda, int32_t n_cc, const int32_t* cam_a, const int32_t* cam_b, double* cov_cc, int32_t n_pp,
+                  const int32_t* point, double* cov_pp, int32_t n_pc, const int32_t* pc_point, const int32_t* pc_cam,
+                  double* cov_pc) {
+    const std::string pre = "ba_covariances: ";
+    if (!cov_factor.ready()) {
+      int rc = cov_init();
+      if (rc) return rc;
+    }
+    const sim3opt::DirectPlan& P = cov_factor.plan();
+    const CovFactorPattern F{P.nb, P.perm.data(), P.colptr.data(), P.lrow.data()};
+    CovRequest R;
+    const std::string bad = cov_plan_request(cov_tab, F, oc, cam_fixed, n_cc, cam_a, cam_b, n_pp, point, n_pc, pc_point,
+                                             pc_cam, R);
+    if (!bad.empty()) { err = pre + bad; return SIM3OPT_ERR_ARG; }
+    const int32_t npick = (int32_t)R.slot.size(), nup = (int32_t)R.upoint.size(), nx = (int32_t)R.xptr.size() - 1;
+    const bool invert = npick > 0 || nup > 0;
+    cov_stats[0] = P.nb; cov_stats[1] = P.nL; cov_stats[2] = P.npairs; cov_stats[3] = cov_factor.selinv_plan().nprod;
+    cov_stats[4] = R.pair_terms; cov_stats[5] = invert ? 1 : 0;
+    const int NC = nc(), NP = np();
+    // ---- the system at the current estimates, the points' pivots ----
+    launch_linearize();
+    launch_reduced(lambda);
+    launch_maxdiag();
+    HIPCHK(hipMemsetAsync(d_cflags, 0, 4 * sizeof(int32_t), stream));
+    hipLaunchKernelGGL(k_ba_cov_point_pivots, dim3(gpts()), dim3(WG), 0, stream, NP, d_pptr, d_pobs, d_lin, lambda,
+                       d_pdmax, d_cflags);
+    HIPCHK(hipGetLastError());
+    int32_t hflags[4] = {0, 0, 0, 0};
+    int rc = down(hflags, d_cflags, sizeof(hflags));
+    if (rc) return rc;
+    if (hflags[2] != 0) {
+      // (S holds the inverse of a singular block: it is not factored)
+      err = pre + "point " + std::to_string(NP - hflags[2]) + ": H_pp + lambda I is numerically singular (a pivot of its "
+            "LDL^T below 1e-13 of its largest diagonal entry): a point seen once or without parallax wants lambda > 0";
+      return SIM3OPT_ERR_STATE;
+    }
+    // ---- S = L L^T and S^-1 on the pattern of L ----
+    hipLaunchKernelGGL(k_ba_cov_pads, dim3((NC + WG - 1) / WG), dim3(WG), 0, stream, NC, d_rptr, d_fixed,
+                       (const Scal*)d_sc, d_S);
+    cov_factor.gather(d_S, d_g, stream);
+    HIPCHK(cov_factor.factor(0.0, d_cflags, 1, nullptr, stream));  // lambda 0: S carries the damping already
+    cov_factor.selinv(reinterpret_cast<const unsigned long long*>(&d_sc->maxdiag), d_cflags + 1, stream, invert);
+    HIPCHK(hipGetLastError());
+    // ---- the blocks ----
+    // per-call indices, one upload: [slot | trans | mask | upoint | xptr | xobs | xpick]
+    std::vector<int32_t> idx;
+    idx.reserve(3 * (size_t)npick + nup + R.xptr.size() + 2 * R.xobs.size());
+    const size_t o_slot = 0, o_trans = (size_t)npick, o_mask = 2 * (size_t)npick, o_up = 3 * (size_t)npick,
+                 o_xptr = o_up + nup, o_xobs = o_xptr + R.xptr.size(), o_xpick = o_xobs + R.xobs.size();
+    idx.insert(idx.end(), R.slot.begin(), R.slot.end());
+    idx.insert(idx.end(), R.trans.begin(), R.trans.end());
+    idx.insert(idx.end(), R.mask.begin(), R.mask.end());
+    idx.insert(idx.end(), R.upoint.begin(), R.upoint.end());
+    idx.insert(idx.end(), R.xptr.begin(), R.xptr.end());
+    idx.insert(idx.end(), R.xobs.begin(), R.xobs.end());
+    idx.insert(idx.end(), R.xpick.begin(), R.xpick.end());
+    // results, one download: [picked 6x6 blocks | point blocks | point-camera blocks]
+    const size_t r_pp = 36 * (size_t)npick, r_pc = r_pp + 9 * (size_t)nup, r_end = r_pc + 18 * (size_t)std::max(nx, 0);
+    std::vector<double> res(std::max<size_t>(r_end, 1));
+    sim3opt::DevBuf<int32_t> d_idx;
+    sim3opt::DevBuf<double> d_X49, d_res;
+    // (the launches above and below are on the stream: whatever ends this, they are done before the blocks go)
+    auto body = [&]() -> int {
+      HIPCHK(d_idx.alloc(std::max<size_t>(idx.size(), 1)));
+      HIPCHK(d_X49.alloc(49 * (size_t)std::max(npick, 1)));
+      HIPCHK(d_res.alloc(std::max<size_t>(r_end, 1)));
+      if (!idx.empty())
+        HIPCHK(hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, stream));
+      if (invert) {
+        cov_factor.pick(d_cslot, d_ctrans, nblk, d_Zc, stream);
+        hipLaunchKernelGGL(k_ba_cov_cams, dim3((36 * nblk + WG - 1) / WG), dim3(WG), 0, stream, (int)nblk,
+                           (const double*)d_Zc, (const int32_t*)d_cmask, d_C);
+      }
+      if (npick > 0) {
+        cov_factor.pick(d_idx + o_slot, d_idx + o_trans, npick, d_X49, stream);
+        hipLaunchKernelGGL(k_ba_cov_cams, dim3((36 * npick + WG - 1) / WG), dim3(WG), 0, stream, (int)npick,
+                           (const double*)d_X49, (const int32_t*)(d_idx + o_mask), d_res.get());
+      }
+      if (nup > 0) {
+        const CovPointArgs A{nup, d_idx + o_up, d_pptr, d_pobs, d_oc, d_fixed, d_rptr, d_bcol, d_Z, d_Hinv, d_C,
+                             d_res + r_pp};
+        hipLaunchKernelGGL(k_ba_cov_points, dim3((nup + 3) / 4), dim3(WG), 0, stream, A);
+      }
+      if (nx > 0)
+        hipLaunchKernelGGL(k_ba_cov_cross, dim3((18 * nx + WG - 1) / WG), dim3(WG), 0, stream, (int)nx,
+                           (const int32_t*)(d_idx + o_xptr), (const int32_t*)(d_idx + o_xobs),
+                           (const int32_t*)(d_idx + o_xpick), (const double*)d_Z, (const double*)d_res.get(),
+                           d_res + r_pc);
+      HIPCHK(hipGetLastError());
+      if (r_end > 0) HIPCHK(hipMemcpyAsync(res.data(), d_res, sizeof(double) * r_end, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(hflags, d_cflags, sizeof(hflags), hipMemcpyDeviceToHost, stream));
+      return SIM3OPT_OK;
+    };
+    rc = body();
+    const hipError_t es = hipStreamSynchronize(stream);
+    if (rc) return rc;
+    HIPCHK(es);
+    bool finite = true;
+    for (size_t k = 0; k < r_end && finite; ++k) finite = std::isfinite(res[k]);
+    if (hflags[0] || hflags[1] || !finite) {
+      err = pre + (hflags[0] ? "the reduced camera system is not positive definite (a non-positive pivot)"
+                   : hflags[1] ? "the reduced camera system is numerically singular (a pivot below 1e-13 max |H_dd|)"
+                               : "non-finite result");
+      err += ": no fixed camera, a camera nobody observes with, or lambda too small for this map";
+      return SIM3OPT_ERR_STATE;
+    }
+    for (int32_t q = 0; q < n_cc; ++q)
+      std::memcpy(cov_cc + (size_t)36 * q, res.data() + (size_t)36 * R.cc_where[q], sizeof(double) * 36);
+    for (int32_t q = 0; q < n_pp; ++q)
+      std::memcpy(cov_pp + (size_t)9 * q, res.data() + r_pp + (size_t)9 * R.pp_where[q], sizeof(double) * 9);
+    for (int32_t q = 0; q < n_pc; ++q) {
+      double* dst = cov_pc + (size_t)18 * q;
+      if (R.pc_where[q] < 0) {
+        for (int k = 0; k < 18; ++k) dst[k] = 0.0;
+      } else {
+        std::memcpy(dst, res.data() + r_pc + (size_t)18 * R.pc_where[q], sizeof(double) * 18);
+      }
+    }
+    return SIM3OPT_OK;
+  }
 };
 
 }  // namespace sim3opt_bundle
@@ -1145,6 +1341,53 @@ int sim3opt_ba_debug_update(sim3opt_ba* b, const double* dx_c, const double* dx_
   if (!std::isfinite(lambda)) { b->err = "ba_debug_update: lambda is not finite"; return SIM3OPT_ERR_ARG; }
   return b->read_update(dx_c, dx_p, lambda, with_fail != 0, cam_qt, points, chi2, scale);
   });
+}
+
+// ---- covariances (include/sim3opt.h, "Bundle-adjustment covariances") ----
+int sim3opt_ba_covariances(sim3opt_ba* b, double lambda, int32_t n_cc, const int32_t* cam_a, const int32_t* cam_b,
+                           double* cov_cc, int32_t n_pp, const int32_t* point, double* cov_pp, int32_t n_pc,
+                           const int32_t* pc_point, const int32_t* pc_cam, double* cov_pc) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  return sim3opt::guarded(b, "ba_covariances", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
+  b->err.clear();
+  if (n_cc < 0 || n_pp < 0 || n_pc < 0 || (n_cc > 0 && (!cam_a || !cam_b || !cov_cc)) ||
+      (n_pp > 0 && (!point || !cov_pp)) || (n_pc > 0 && (!pc_point || !pc_cam || !cov_pc))) {
+    b->err = "ba_covariances: negative count or NULL array";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (!sim3opt::all_finite(&lambda, 1) || lambda < 0.0) {
+    b->err = "ba_covariances: lambda must be finite and >= 0";
+    return SIM3OPT_ERR_ARG;
+  }
+  if (b->no() < 1) { b->err = "ba_covariances: no problem set"; return SIM3OPT_ERR_STATE; }
+  if (!b->ready) { int rc = b->initialize(); if (rc) return rc; }
+  return b->covariances(lambda, n_cc, cam_a, cam_b, cov_cc, n_pp, point, cov_pp, n_pc, pc_point, pc_cam, cov_pc);
+  });
+}
+
+int sim3opt_ba_covariance_plan(sim3opt_ba* b, int32_t* nb, int64_t* nL, int32_t* ngroups, int32_t* perm, int32_t* colptr,
+                               int32_t* lrow) {
+  if (!b) return SIM3OPT_ERR_ARG;
+  return sim3opt::guarded(b, "ba_covariance_plan", sim3opt::NO_MEMORY_OR_INTERNAL, [&]() -> int {
+  int rc = ba_debug_enter(b, "ba_covariance_plan");
+  if (rc) return rc;
+  if (!nb || !nL || !ngroups) { b->err = "ba_covariance_plan: NULL output"; return SIM3OPT_ERR_ARG; }
+  if (!b->cov_factor.ready() && (rc = b->cov_init())) return rc;
+  const sim3opt::DirectPlan& P = b->cov_factor.plan();
+  *nb = P.nb;
+  *nL = P.nL;
+  *ngroups = P.ngroups();
+  if (perm) std::memcpy(perm, P.perm.data(), sizeof(int32_t) * P.perm.size());
+  if (colptr) std::memcpy(colptr, P.colptr.data(), sizeof(int32_t) * P.colptr.size());
+  if (lrow) std::memcpy(lrow, P.lrow.data(), sizeof(int32_t) * P.lrow.size());
+  return SIM3OPT_OK;
+  });
+}
+
+int sim3opt_ba_covariance_stats(const sim3opt_ba* b, int64_t out[6]) {
+  if (!b || !out) return SIM3OPT_ERR_ARG;
+  for (int k = 0; k < 6; ++k) out[k] = b->cov_stats[k];
+  return SIM3OPT_OK;
 }
 
 int sim3opt_ba_optimize(sim3opt_ba* b, int32_t max_iters) {

@@ -431,6 +431,10 @@ SYMBOLS = {
     "sim3opt_ba_debug_reduced": (C.c_int, [_vp, C.c_double] + [_dp] * 9),
     "sim3opt_ba_debug_step": (C.c_int, [_vp, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp, _dp, _ip, _dp, _ip]),
     "sim3opt_ba_debug_update": (C.c_int, [_vp, _dp, _dp, C.c_double, C.c_int32, _dp, _dp, _dp, _dp]),
+    "sim3opt_ba_covariances": (C.c_int, [_vp, C.c_double, C.c_int32, _ip, _ip, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip,
+                                         _ip, _dp]),
+    "sim3opt_ba_covariance_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "sim3opt_ba_covariance_plan": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip]),
     "sim3opt_ba_batch_options_default": (None, [C.POINTER(BaBatchOptions)]),
     "sim3opt_ba_batch_create": (_vp, []),
     "sim3opt_ba_batch_destroy": (None, [_vp]),
@@ -1753,6 +1757,62 @@ class BundleAdjuster(_Handle):
 
     def write_poses(self, path):
         self._chk(self._L.sim3opt_ba_write_poses(self._b, os.fsencode(path)), "ba_write_poses")
+
+    # ---- covariances (sim3opt_ba_covariances): Sigma = (H + lam I)^-1 at the current estimates, fixed cameras removed;
+    # an optimize() after a call computes bit for bit what it computes without it ----
+    def covariances(self, cam_pairs=None, points=None, point_cams=None, lam=0.0):
+        """Blocks of the covariance in one linearisation, factorisation and selected inversion: cam_pairs (n, 2) ->
+        (n, 6, 6) blocks [omega, upsilon] x [omega, upsilon] (a camera with itself, or two cameras on the pattern of the
+        factor: any two that share a point); points (n,) -> (n, 3, 3); point_cams (n, 2) rows (point, camera) ->
+        (n, 3, 6).  A fixed camera gives exact zeros.  Returns (cc, pp, pc), None for a request not made.  lam >= 0 is
+        added to every diagonal entry; a singular system (no fixed camera, a point seen once, ...) raises ERR_STATE."""
+        def pairs(a):
+            a = _i32(a).reshape(-1, 2)
+            return np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1])
+        ca = cb = pt = qp = qc = cc = pp = pc = None
+        ncc = npp = npc = 0
+        if cam_pairs is not None:
+            ca, cb = pairs(cam_pairs)
+            ncc, cc = ca.shape[0], np.empty((ca.shape[0], 36))
+        if points is not None:
+            pt = _i32(points).reshape(-1)
+            npp, pp = pt.shape[0], np.empty((pt.shape[0], 9))
+        if point_cams is not None:
+            qp, qc = pairs(point_cams)
+            npc, pc = qp.shape[0], np.empty((qp.shape[0], 18))
+        self._chk(self._L.sim3opt_ba_covariances(self._b, float(lam), ncc, _p(ca, _ip), _p(cb, _ip), _p(cc, _dp), npp,
+                                                 _p(pt, _ip), _p(pp, _dp), npc, _p(qp, _ip), _p(qc, _ip), _p(pc, _dp)),
+                  "ba_covariances")
+        # column-major blocks: [q, r, c] is the transpose of the raw [q, c, r]
+        t = lambda a, r, c: None if a is None else np.ascontiguousarray(a.reshape(-1, c, r).transpose(0, 2, 1))
+        return t(cc, 6, 6), t(pp, 3, 3), t(pc, 3, 6)
+
+    def camera_covariances(self, lam=0.0):
+        """(n_cams, 6, 6): every camera's own block (zeros for a fixed camera)."""
+        c = np.arange(self.dims()[0])
+        return self.covariances(cam_pairs=np.stack([c, c], axis=1), lam=lam)[0]
+
+    def point_covariances(self, lam=0.0):
+        """(n_points, 3, 3): every point's own block."""
+        return self.covariances(points=np.arange(self.dims()[1]), lam=lam)[1]
+
+    def covariance_stats(self):
+        """Of the last covariances(): dict of columns, blocks, factor_products, selinv_products, point_pair_terms, selinv."""
+        o = (C.c_int64 * 6)()
+        self._chk(self._L.sim3opt_ba_covariance_stats(self._b, o), "ba_covariance_stats")
+        keys = ("columns", "blocks", "factor_products", "selinv_products", "point_pair_terms", "selinv")
+        return dict(zip(keys, (int(x) for x in o)))
+
+    def covariance_plan(self):
+        """The pattern of the covariances' factor: dict of nb, nL, ngroups, perm (nb), colptr (nb + 1), lrow (nL)."""
+        nb, ng, nl = C.c_int32(), C.c_int32(), C.c_int64()
+        f = self._L.sim3opt_ba_covariance_plan
+        self._chk(f(self._b, C.byref(nb), C.byref(nl), C.byref(ng), None, None, None), "ba_covariance_plan")
+        perm, colptr = np.empty(nb.value, dtype=np.int32), np.empty(nb.value + 1, dtype=np.int32)
+        lrow = np.empty(nl.value, dtype=np.int32)
+        self._chk(f(self._b, C.byref(nb), C.byref(nl), C.byref(ng), _p(perm, _ip), _p(colptr, _ip), _p(lrow, _ip)),
+                  "ba_covariance_plan")
+        return dict(nb=nb.value, nL=nl.value, ngroups=ng.value, perm=perm, colptr=colptr, lrow=lrow)
 
     # ---- diagnostic read-outs (sim3opt_ba_debug_*): nothing in the solver uses them, and an optimize() after one of
     # them computes bit for bit what it computes without it ----
