@@ -234,6 +234,9 @@ __global__ __launch_bounds__(WG) void k_match_compact(MatchArgs A) {
 // nb (when given: K entries of the lane) receives the chosen observations in (distance, index) order, -1 padded.
 __device__ inline float knn_depth(float u, float v, bool active, const float2* ouv, const float* od, int32_t n_obs,
                                   int K, float2* stage, int32_t* nb) {
+  // Contraction is off for the distance below.  (__fmul_rn and __fadd_rn would not do: here they are the plain operators
+  // inside inline functions, and the compiler fused them into fl(dx dx + fl(dy dy)), which orders near ties otherwise.)
+#pragma clang fp contract(off)
   float dk[MAX_K];
   int32_t ik[MAX_K];
 #pragma unroll
@@ -249,8 +252,9 @@ __device__ inline float knn_depth(float u, float v, bool active, const float2* o
     for (int32_t i = 0; i < m; ++i) {
       const float2 o = stage[i];
       // fl(fl(dx dx) + fl(dy dy)): no fused multiply-add, so a restatement gets the same bits
-      const float dx = __fsub_rn(o.x, u), dy = __fsub_rn(o.y, v);
-      const float d = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+      const float dx = o.x - u, dy = o.y - v;
+      const float xx = dx * dx, yy = dy * dy;
+      const float d = xx + yy;
       if (cnt < K || d < worst) {  // (strict: on equal distance the earlier, lower index stays)
         const int pos = cnt < K ? cnt : K - 1;
         if (cnt < K) ++cnt;

@@ -168,7 +168,11 @@ def stacked(C, D, defect=None):
 
 
 def jacobians(C, D, defect=None, h=2e-3):
-    """(n, 4, 7) d [r1 r0] / d delta at exp(delta) C, by fourth-order central differences"""
+    """(n, 4, 7) d [r1 r0] / d delta at exp(delta) C, by fourth-order central differences.  The step is h in scenes at
+    least one map unit deep and h times the nearest depth in shallower ones: the truncation error goes with
+    (h / depth)^4, which at h = 2e-3 is 1e-15 for a point 10 units away and 1e-7 for one 0.07 away (PTAM's KITTI maps)."""
+    nearest = float(min(np.abs(D["X0"][:, 2]).min(), np.abs(D["X1"][:, 2]).min()))
+    h = h * min(1.0, max(nearest, 1e-3))
     J = np.zeros((len(D["uv0"]), 4, 7), dtype=LD)
     for k in range(7):
         e = np.zeros(7)

@@ -3,7 +3,8 @@ workgroup per problem; hypotheses, scoring, pose candidates and vote in one laun
 an independent restatement with another five-point solver.  PARITY UNPINNED (the reference stores no inputs of its
 cv::findEssentialMat runs): what is compared is the restatement and planted truth.  The cases and their reference runs
 are tests/essential_cases.py's; tests/test_essential_ref.py shows on the CPU that the conditions these comparisons rest
-on hold for them, and sets E_LIMIT from the host build of the kernel's arithmetic against the restatement."""
+on hold for them, and sets E_LIMIT from the host build of the kernel's arithmetic against the restatement.  Real inputs, the KITTI 00 keyframes, run in
+tests/test_gpu_real_keyframes.py."""
 import subprocess
 
 import numpy as np

@@ -3,7 +3,8 @@ workgroup per problem; MLESAC hypotheses, inliers, refinement rounds, decomposit
 tests/homography_ref.py, an independent restatement with other linear algebra.  PARITY UNPINNED (the reference cannot
 be built here): what is compared is the restatement and planted truth.  The cases and their reference runs are
 tests/homography_cases.py's; tests/test_homography_ref.py shows on the CPU that the conditions these comparisons rest on
-hold for them, and sets the limits from the host build of the kernel's arithmetic against the restatement."""
+hold for them, and sets the limits from the host build of the kernel's arithmetic against the restatement.  Real inputs, the KITTI 00 keyframes, run in
+tests/test_gpu_real_keyframes.py."""
 import subprocess
 
 import numpy as np

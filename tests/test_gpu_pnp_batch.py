@@ -2,7 +2,8 @@
 hypotheses, scoring, refit and final count in one launch) against tests/pnp_ref.py, an independent restatement with
 another P3P.  PARITY UNPINNED (the reference stores no inputs of its cv::solvePnPRansac runs): what is compared is
 the restatement and planted truth.  The cases and their reference runs are tests/pnp_cases.py's;
-tests/test_pnp_ref.py shows on the CPU that the conditions these comparisons rest on hold for them."""
+tests/test_pnp_ref.py shows on the CPU that the conditions these comparisons rest on hold for them.  Real inputs, the KITTI 00 keyframes, run in
+tests/test_gpu_real_keyframes.py."""
 import os
 import subprocess
 

@@ -5,7 +5,8 @@ independent restatement.  PARITY UNPINNED (the reference has no such step): what
 planted truth, and what the optimiser makes of the information matrix.  The cases and their reference runs are
 tests/sim3_batch_cases.py's; tests/test_sim3_batch_ref.py shows on the CPU that the conditions these comparisons rest on
 hold for them, and sets the limits from the host build against the restatement.  The host build used here is the
-plain one (-O2): the sanitizer build of the same driver belongs to the CPU file alone.
+plain one (-O2): the sanitizer build of the same driver belongs to the CPU file alone.  Real inputs, the KITTI 00 keyframes, run in
+tests/test_gpu_real_keyframes.py.
 
 The refinement goes through exp, sin and cos, whose last bit differs between the device's and the host's libm: the
 refined C, chi2 and Omega of a solve are compared with the host build within the limits, everything before the first
